@@ -22,12 +22,18 @@ received (the same kernels; no exchange) — `config.workload` says which.
 
 Before the W warm-up steps an untimed RAMP of steps (≈0.25 s of device work) lets the card reach its
 steady clocks — the first ≈20 ms after idling run ≈4 % slower; `ramp_steps` is reported.  The timed region
-is exactly K steps.  After it, outside the timed region and at N = 1 only, `extras` puts the other timing
+is exactly K steps (--steps; default 100 for --config 2, 3 for --config 4 / 5).
+
+A plain run does only what the headline needs: set-up, ramp, warm-up, the K timed steps, the outputs (--dump-outputs
+DIR: the histograms the last timed step handed its caller, DIR/histograms.npy in float64; the inputs are the same
+from run to run for the same arguments) and the JSON line.  Everything else is measured with --full only: the
+per-kernel timing and the roofline figures below, the CPU baselines and the bit-exactness check against the oracle,
+and the extras.  With --full, after the timed region and at N = 1 only, `extras` puts the other timing
 points of SURVEY.md §8d on record: pinned host buffers → histogram (ii), FASTQ file → histogram (iii),
 BASELINE configs[2] (k = 31, 100 M reads) from HBM and streamed from pinned host memory, and the
-chunk-lane / large-table shapes.  --no-extras skips them.
+chunk-lane / large-table shapes.  --no-extras / --no-cpu-baseline leave parts of --full out.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, timed with HIP events on the engine's own
+Prints ONE JSON line (rank 0).  With --full: `roofline` is for the dominant kernel, timed with HIP events on the engine's own
 stream inside libshk (SHK_FLAG_TIMING): `achieved` = ALGORITHMIC bytes per launch ÷ its duration; every
 kernel also carries `physical_GBps` = the HBM bytes per launch the committed PMC passes of this round measured
 (profiles/rNN_traffic.json) ÷ the same duration.  `roofline_path` is the whole job against SURVEY.md §8d's B_alg, over
@@ -92,6 +98,24 @@ def cpu_all_cores(orc, hb, ho, k, histo_max, n_bases):
 
 def _timings_ms(eng, reps):
     return {k_: round(v[0] / reps, 4) for k_, v in eng.timings().items()}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64 (exact for counts below 2^53).  An array that would
+    take more than its share of DUMP_MAX_BYTES is written as a fixed, seeded sample of its elements, with the flat
+    indices of the sample beside it (<name>.sample_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(out_dir, f"{name}.sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def extras(sa, torch, dev):
@@ -341,7 +365,7 @@ def extras(sa, torch, dev):
             if force:
                 env["SHK_BENCH_FORCE_DIST"] = "1"
                 env["MASTER_PORT"] = "29543"
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline"], env=env,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline"], env=env,
                                stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300, check=True)
             res[name] = json.loads(r.stdout.decode().strip().splitlines()[-1])["ms_per_step"]
         return {"workload": "config 2's step (bench.py defaults) with SHK_BENCH_FORCE_DIST=1 — fixed-capacity pieces + in-place histogram "
@@ -392,7 +416,7 @@ def owner_config(args, real_stdout):
     if args.config == 5 and world in (2, 3) and mode != "drop":
         raise SystemExit("--config 5 needs 1 GPU (one rank's load, or --mode drop) or >= 4 GPUs (the key space must fit)")
     out = owner_run(args, args.config, mode, dist_ready=False)
-    if args.config == 5 and world == 1 and mode == "exchange" and not args.no_extras:
+    if args.config == 5 and world == 1 and mode == "exchange" and args.full and not args.no_extras:
         try:
             d = owner_run(args, 5, "drop", dist_ready=True)
             out["extras"] = {"drop_mode": {key: d[key] for key in ("value", "ms_per_step", "config", "kernels_ms_per_step", "table", "roofline")}}
@@ -426,8 +450,8 @@ def owner_run(args, config, mode, dist_ready):
     rpr = args.reads or 10**9 // JOB_GPUS         # reads per rank: its share of the job as stated
     # (two warm-up jobs: besides the first job's allocations, the runtime stands 35-50 ms ONCE — inside one call of the
     # second job's 46th round or thereabouts, with or without the timing events, never again afterwards:
-    # tools/absorb_time_probe.py — which a single warm-up job left in the first timed step)
-    steps, warmup = args.steps if args.steps != 100 else 3, args.warmup if args.warmup != 50 else 2
+    # tools/absorb_time_probe.py — which a single warm-up job left in the first timed step: main's default --warmup here)
+    steps, warmup = args.steps, args.warmup
     dev = local_rank if world > 1 else 0
     torch.cuda.set_device(dev)
     import torch.distributed as dist
@@ -439,7 +463,7 @@ def owner_run(args, config, mode, dist_ready):
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", dev))
     n_owners = JOB_GPUS if drop_mode else world
-    flags = sa.FLAG_TIMING
+    flags = sa.FLAG_TIMING if args.full else 0   # (kernel durations: --full's per-kernel figures only)
     eng = sa.KmerEngine(k, lanes, histo_max, device=dev, capacity_hint=genome // n_owners, flags=flags,
                         n_owners=n_owners, owner_id=0 if drop_mode else rank, reserve_cus=args.reserve_cus)
     spec = sa.SynthSpec(genome_len=genome, read_len=L)
@@ -493,14 +517,15 @@ def owner_run(args, config, mode, dist_ready):
         t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{dev}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    tim = eng.timings()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"histograms": hist})
     cnt = eng.counters()
-    if rank == 0:
-        n_bases = rpr * L
-        n_kmers_rank = rpr * (L - k + 1)
-        total_bases = n_bases * world * steps
-        value = total_bases / dt / 1e9
-        cap = cnt["table_capacity"]
+    n_bases = rpr * L
+    n_kmers_rank = rpr * (L - k + 1)
+    cap = cnt["table_capacity"]
+    full, checks = {}, {}
+    if rank == 0 and args.full:
+        tim = eng.timings()
         own_frac = 1.0 / n_owners if drop_mode else 1.0   # the part of a rank's records that ends up in its own page passes
         # algorithmic bytes of a step on ONE rank: its bases read, a 4-byte record per k-mer written by the level-1 pass,
         # read and written by the level-2 pass and read by the page pass (what this rank absorbs: 1/N of N ranks' records —
@@ -539,13 +564,6 @@ def owner_run(args, config, mode, dist_ready):
         path_roof = {"alg_bytes_per_step_per_rank": int(b_alg), "achieved_GBps": round(b_alg / (dt / steps) / 1e9, 1),
                      "frac_driver_clock": round(b_alg / (dt / steps) / 1e9 / HBM_PEAK_GBS, 5)}
         kmers_expected = (L - k + 1) * rpr * world
-        exchange = None
-        if oc is not None and lay_box[0] is not None:
-            lay = lay_box[0]
-            exchange = {"rounds": oc.n_rounds, "n_foreign_rounds": oc.n_foreign_rounds,
-                        "segment_bytes": int((lay.segment_records + lay.regions) * 4),
-                        "link_bytes_per_round": int((lay.segment_records + lay.regions) * 4) if world > 1 else 0,
-                        "wire_bytes_per_rank_per_step": int(oc.wire_bytes), "region_cap": int(lay.region_cap), "regions": int(lay.regions)}
         cpu = None
         if not args.no_cpu_baseline:
             from oracle import oracle as orc
@@ -557,6 +575,20 @@ def owner_run(args, config, mode, dist_ready):
             cpu = {"value": round(ns * L / cdt / 1e9, 5), "unit": "Gbases/s", "cores": 1, "kind": "port",
                    "sample": f"the first {ns} reads of the job ({lanes} chunk lane(s)), single-threaded C restatement of sharkmer's counting path",
                    "cpu_model": cpu_model()}
+        full = {"roofline": roof, "cpu_baseline": cpu, "roofline_path": path_roof, "kernels": per_kernel,
+                "kernels_ms_per_step": {k_: round(v[0] / steps, 3) for k_, v in tim.items() if v[0] > 0}}
+        checks = {"kmers_as_expected": (int(tot["n_kmers_ingested"]) == kmers_expected) if not drop_mode else None,
+                  "histogram_rows_sum_to_distinct": bool(int(hist[-1, 1:].sum()) == int(tot["n_unique_kmers"]))}
+    if rank == 0:
+        total_bases = n_bases * world * steps
+        value = total_bases / dt / 1e9
+        exchange = None
+        if oc is not None and lay_box[0] is not None:
+            lay = lay_box[0]
+            exchange = {"rounds": oc.n_rounds, "n_foreign_rounds": oc.n_foreign_rounds,
+                        "segment_bytes": int((lay.segment_records + lay.regions) * 4),
+                        "link_bytes_per_round": int((lay.segment_records + lay.regions) * 4) if world > 1 else 0,
+                        "wire_bytes_per_rank_per_step": int(oc.wire_bytes), "region_cap": int(lay.region_cap), "regions": int(lay.regions)}
         which = "configs[3]" if config == 4 else "configs[4]"
         how = (f"owner 0 of {n_owners}: every read of the share offered, the other owners' records dropped in the level-1 pass (no exchange)"
                if drop_mode else f"exchange rounds among {world} owner share(s) over RCCL (OwnerCounter)")
@@ -573,12 +605,10 @@ def owner_run(args, config, mode, dist_ready):
                        "reads_per_gpu": rpr, "k": k, "chunks": lanes, "genome": genome, "n_owners": n_owners,
                        "mode": "drop" if drop_mode else "exchange", "round_reads": round_reads,
                        "reserve_cus": args.reserve_cus if args.reserve_cus else ("library default: 16 for n_owners > 1 (SHK_RESERVE_CUS)" if n_owners > 1 else 0)},
-            "roofline": roof, "cpu_baseline": cpu, "roofline_path": path_roof, "kernels": per_kernel,
-            "kernels_ms_per_step": {k_: round(v[0] / steps, 3) for k_, v in tim.items() if v[0] > 0},
+            **full,
             "exchange": exchange,
             "totals": {f: int(tot[f]) for f in ("n_reads_ingested", "n_kmers_ingested", "n_unique_kmers") if f in tot},
-            "kmers_as_expected": (int(tot["n_kmers_ingested"]) == kmers_expected) if not drop_mode else None,
-            "histogram_rows_sum_to_distinct": bool(int(hist[-1, 1:].sum()) == int(tot["n_unique_kmers"])),
+            **checks,
             "table": {"capacity": cap, "n_grows": cnt["n_grows"], "n_spilled": cnt["n_spilled"]},
         }
     else:
@@ -658,9 +688,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: 50 warm-up steps (≈40 ms) because the first ≈20 ms of work after the card has been idle run
-    # ≈4 % slower (measured: scatter 0.48 ms with 3 warm-up steps, 0.46 ms with 50 or 300), then 100 timed steps
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=50)
+    # ≈4 % slower (measured: scatter 0.48 ms with 3 warm-up steps, 0.46 ms with 50 or 300), then 100 timed steps;
+    # --config 4 / 5: two warm-up jobs (owner_run's note), then 3 timed ones
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100 for --config 2, 3 for 4 / 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default: 50 for --config 2, 2 for 4 / 5)")
     ap.add_argument("--config", type=int, choices=[2, 4, 5], default=2,
                     help="2: BASELINE configs[1] (the metric's configuration); 4 / 5: configs[3] / configs[4], a rank's share per GPU")
     ap.add_argument("--mode", choices=["auto", "exchange", "drop"], default="auto",
@@ -679,7 +710,16 @@ def main():
     ap.add_argument("--ramp-ms", type=float, default=250.0, help="untimed clock ramp before the warm-up steps")
     ap.add_argument("--cpu-sample-reads", type=int, default=0,
                     help="reads for the CPU baseline (0 = the whole step batch of rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel timing and roofline, "
+                         "CPU baselines and the bit-exactness check, extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the histograms of the last timed step as DIR/histograms.npy (float64)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 100 if args.config == 2 else 3
+    if args.warmup is None:
+        args.warmup = 50 if args.config == 2 else 2
     if args.config != 2:
         return owner_config(args, real_stdout)
     args.reads = args.reads or 1_000_000
@@ -716,9 +756,10 @@ def main():
     # merged histogram is that of N × 50× coverage
     genome = args.genome
     spec = sa.SynthSpec(genome_len=genome, read_len=L)
-    # kernel durations: HIP events recorded by libshk on its own stream around every launch of every 4th step of
+    # kernel durations (--full): HIP events recorded by libshk on its own stream around every launch of every 4th step of
     # the timed region (SHK_FLAG_TIMING_SAMPLED: bracketing every launch of every step costs ≈3 % of the step)
-    flags = 0 if os.environ.get("SHK_BENCH_NO_TIMING") else sa.FLAG_TIMING | sa.FLAG_TIMING_SAMPLED  # (experiment hook)
+    timing = args.full and not os.environ.get("SHK_BENCH_NO_TIMING")   # (SHK_BENCH_NO_TIMING: experiment hook)
+    flags = sa.FLAG_TIMING | sa.FLAG_TIMING_SAMPLED if timing else 0
     timed_steps = -(-args.steps // 4)  # steps 1, 5, 9, … after reset_timings
     if args.path == "direct":
         flags |= sa.FLAG_FORCE_DIRECT
@@ -764,6 +805,7 @@ def main():
         while (time.perf_counter() - t_r) * 1e3 < args.ramp_ms and ramp_steps < 2000:  # untimed: clocks up
             step()
             ramp_steps += 1
+    step_no[0] = 0   # the warm-up and timed steps count the same batches whatever number of ramp steps the clock allowed
     for _ in range(args.warmup):
         step()
     eng.reset_timings()
@@ -783,13 +825,16 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=f"cuda:{dev}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"histograms": hist})
 
-    tim = eng.timings()
     cnt = eng.counters()
     total_bases = n_bases * n_gpus * args.steps
     value = total_bases / dt / 1e9
 
-    if rank == 0:
+    full = {}
+    if rank == 0 and args.full:
+        tim = eng.timings()
         # ---- roofline (HBM-bound path; algorithmic bytes per launch) --------------
         kpr = L - args.k + 1
         n_kmers = n_reads * kpr
@@ -885,6 +930,11 @@ def main():
                 if not exact:
                     print("ERROR: GPU histogram differs from the CPU oracle", file=sys.stderr)
                     sys.exit(2)
+        full = {"roofline": roof, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all,
+                "roofline_path": path_roof, "kernels": per_kernel,
+                "kernels_ms_per_step": {k_: round(v[0] / timed_steps, 4) for k_, v in tim.items()},
+                "kernel_timing": f"HIP events (libshk, its own stream) around every launch of {timed_steps} of the {args.steps} timed steps (every 4th)"}
+    if rank == 0:
         out = {
             "metric": "Gbases/sec k-mer counted (k=21, 150bp reads); histogram bit-exact vs CPU",
             "value": round(value, 4), "unit": "Gbases/s", "n_gpus": n_gpus, "steps": args.steps,
@@ -897,15 +947,12 @@ def main():
                                    f"steps rotate over {NB} distinct batches",
                        "reads_per_gpu": n_reads, "batches": NB, "k": args.k, "chunks": args.chunks,
                        "genome": genome, "path": args.path},
-            "roofline": roof, "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all,
-            "roofline_path": path_roof, "kernels": per_kernel,
-            "kernels_ms_per_step": {k_: round(v[0] / timed_steps, 4) for k_, v in tim.items()},
-            "kernel_timing": f"HIP events (libshk, its own stream) around every launch of {timed_steps} of the {args.steps} timed steps (every 4th)",
+            **full,
             "table": {"capacity": cnt["table_capacity"], "n_unique": cnt["n_unique_kmers"],
                       "n_grows": cnt["n_grows"], "n_spilled": cnt["n_spilled"]},
             "ramp_steps": ramp_steps,
         }
-        if world == 1 and dist is None and not args.no_extras:
+        if world == 1 and dist is None and args.full and not args.no_extras:
             eng.close()
             d_bases.clear()
             del d_offsets
@@ -913,7 +960,7 @@ def main():
             out["extras"] = extras(sa, torch, dev)
     else:
         out = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         # N > 1: the same ranks then run one rank's share each of BASELINE configs[3] (1 B reads of a 3 Gb genome over
         # 8 GPUs; key-space-partitioned ingest, the records exchanged by owner every round) — the multi-GPU
         # configuration the north star names, on record beside the metric's own configuration
@@ -923,6 +970,7 @@ def main():
         import copy
         a4 = copy.copy(args)
         a4.steps, a4.warmup, a4.reads, a4.no_cpu_baseline = min(args.steps, 3), 2, 0, True   # (two warm-up jobs: owner_run's note)
+        a4.dump_outputs = None   # (the outputs are the headline's)
         c4 = owner_run(a4, 4, "exchange", dist_ready=True)
         if rank == 0:
             out["extras"] = {"config4": {key: c4[key] for key in ("value", "ms_per_step", "n_gpus", "config", "kernels_ms_per_step", "exchange",
