@@ -270,6 +270,48 @@ int shk_lookup(shk_ctx *ctx, const uint64_t *kmers, uint32_t *counts, uint64_t n
 int shk_find_oligos(shk_ctx *ctx, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,
                     uint32_t min_count, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out);
 
+/* One primer direction of sPCR's seed discovery: PCRParams' forward_seq or reverse_seq with the fields
+ * get_primer_kmers reads (src/pcr/primers.rs:234-480; defaults of pcr/mod.rs's PCRParams in brackets). */
+typedef struct shk_primer {
+  const char *seq;     /* IUPAC primer as written (ACGTRYWSKMBDHVN, upper case) */
+  uint32_t trim;       /* [15] keep the last trim bases; trim ≥ k is clamped to k−1 (primers.rs:244-271) */
+  uint32_t mismatches; /* [2] mismatch levels 0..=min(mismatches, trimmed length) (primers.rs:286-313) */
+  uint32_t min_count;  /* [2] a table k-mer counts when its merged count ≥ min_count (primers.rs:212) */
+  uint32_t max_kmers;  /* [40] max_primer_kmers: the cap filled level by level (primers.rs:375-438) */
+} shk_primer;
+
+#define SHK_PRIMER_LEVELS 33 /* level slots per primer in n_variants / level_hits (levels ≤ k−1 ≤ 30) */
+
+/* preprocess_primer_by_mismatch (primers.rs:237-313) for a table of k-mers of length k, on the host (no device
+ * touched, no context needed): *trimmed_len = L, the length of the trimmed primer P; *n_levels = min(mismatches, L) + 1
+ * (0 when P is empty: trim 0 or an empty primer — then nothing is searched and nothing fails);
+ * n_variants[m] = |level m| for m < *n_levels, 0 above (the variant sets are never listed).
+ * Errors (text in err, at most err_len bytes with the terminating NUL; "" on success):
+ *   SHK_ERR_BAD_ARG      more than 10000 resolved variants, the reference's text (primers.rs:273-284);
+ *   SHK_ERR_INVALID_CHAR a character of P outside the IUPAC codes, "Invalid nucleotide {c} in {variant}"
+ *                        (string_to_oligo, primers.rs:33-55) — only when max_kmers > 0 and P is not empty, as the
+ *                        reference converts a variant only in a non-empty round it runs (primers.rs:383-393). */
+int shk_primer_compile(const shk_primer *p, uint32_t k, uint32_t *trimmed_len, uint32_t *n_levels,
+                       uint64_t *n_variants, char *err, size_t err_len);
+
+/* get_primer_kmers (primers.rs:234-480) for n_primers primer directions in ONE pass over the merged table (the
+ * owned pages of an owner share; every share of a multi-device context, then selected over their union).  A table
+ * k-mer x with merged count c ≥ min_count, whose first L bases have f mismatches against P and whose reverse
+ * complement's first L bases have r, yields (x, c) at level f when f ≤ M, and (revcomp(x), c) at level r when
+ * r ≤ M and r ≠ f (the `else if` of find_oligos_in_kmers, primers.rs:212-223, within one level's pass).
+ * Primer i's result is kmers/counts/levels[offsets[i] .. offsets[i+1]) (offsets: n_primers + 1 entries), the first
+ * max_kmers hits in the order level ascending, count descending, k-mer ascending — the insertion order of
+ * discover_primer_kmers_by_round (primers.rs:375-438).  level_hits (optional, n_primers × SHK_PRIMER_LEVELS):
+ * hits at level m before the cap (the reference's "Mismatch level m: n new primer kmers … dropped d" is n + d);
+ * all zero for a primer with max_kmers = 0 or an empty P, which is not searched.  cap ≥ Σ max_kmers.
+ * Errors: the too-many-variants check of every primer first (in order), then the invalid-character check of every
+ * searched one — for a forward/reverse pair that is the reference's order (primers.rs:440-478).  The selection
+ * does not merge equal output k-mers: the table holds canonical k-mers, so two entries never yield the same one.
+ * Tuning: SHK_PRIMER_CANDIDATES (records, read at each call) bounds the first pass's candidate buffer; when it
+ * overflows, each primer's level counts give its cut level and the pass is rerun keeping only levels up to it. */
+int shk_primer_kmers(shk_ctx *ctx, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers,
+                     uint32_t *counts, uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits);
+
 /* PrimerReadFilter::matches over a batch (src/pcr/read_filter.rs:24-55), the read selection in front
  * of sPCR's read threading: out_matches[i] = 1 when read i has no byte outside ACGTN (otherwise
  * kmers_from_ascii fails and the reference returns false for the read) and at least one of its

@@ -1368,6 +1368,95 @@ __global__ void __launch_bounds__(WG) k_find_oligos(TableRef tb, uint64_t slot0,
 }
 
 // ==========================================================================================
+// K_PRIMER: sPCR's primer seed discovery, get_primer_kmers (src/pcr/primers.rs:234-480), for a panel of
+// primer directions and all their mismatch levels in one pass over the merged table.  Level m of a primer
+// P (length L) holds the strings with m positions i whose base is not in allowed(P[i]) (shk_primer.cpp),
+// so per k-mer: four "base equals b" planes (one bit per 2-bit field), ANDed with the primer's allow
+// masks (zero outside the first L fields) → f = L − popcount.  The same on revcomp(key) gives r.  A
+// k-mer yields key at level f (f ≤ M) and revcomp(key) at level r (r ≤ M, r ≠ f: primers.rs:212-223).
+// Records go out through one atomic per wave; per-(primer, level) hit counts are kept in LDS and are
+// complete even when the record buffer overflows (the host then reruns with the levels cut).
+// ==========================================================================================
+struct PrimerDev {  // 48 B
+  uint64_t allow[4];
+  uint32_t L, M;    // M: the highest level kept (the primer's M, or its cut level on a rerun)
+  uint32_t min_count, pad_;
+};
+struct PrimerRec {  // 16 B
+  uint64_t kmer;
+  uint32_t count;
+  uint32_t tag;     // primer << 8 | level
+};
+
+__device__ __forceinline__ void base_planes(uint64_t x, uint64_t eq[4]) {
+  constexpr uint64_t LO = 0x5555555555555555ull;
+#pragma unroll
+  for (uint32_t b = 0; b < 4; ++b) {
+    const uint64_t y = x ^ (LO * b);  // field == b ⇔ both bits of the field zero
+    eq[b] = ~(y | (y >> 1)) & LO;
+  }
+}
+
+__global__ void __launch_bounds__(WG) k_primer_scan(TableRef tb, uint64_t slot0, uint64_t slot1, int k,
+                                                    const PrimerDev *__restrict__ prim, uint32_t n_prim,
+                                                    uint32_t p_base, uint32_t stride /* levels per primer in LDS */,
+                                                    PrimerRec *__restrict__ out, uint64_t cap,
+                                                    unsigned long long *__restrict__ n_out,
+                                                    unsigned long long *__restrict__ hits /* [p][SHK_PRIMER_LEVELS] */) {
+  extern __shared__ uint64_t lds[];
+  PrimerDev *sp = (PrimerDev *)lds;
+  uint32_t *cnt = (uint32_t *)(sp + n_prim);
+  for (uint32_t i = threadIdx.x; i < n_prim * 6; i += WG) lds[i] = ((const uint64_t *)prim)[i];
+  for (uint32_t i = threadIdx.x; i < n_prim * stride; i += WG) cnt[i] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  // the loop bound is per workgroup, so every wave runs every trip (ballots see whole waves)
+  for (uint64_t s0 = slot0 + (uint64_t)blockIdx.x * WG; s0 < slot1; s0 += (uint64_t)gridDim.x * WG) {
+    const uint64_t s = s0 + threadIdx.x;
+    const uint64_t key = s < slot1 ? tb.keys[s] : EMPTY;
+    uint32_t cum = 0;
+    if (key != EMPTY)
+      for (uint32_t l = 0; l < tb.n_lanes; ++l) cum = sat_add_u32(cum, tb.vals[(uint64_t)l * tb.cap + s]);
+    if (!__any(key != EMPTY)) continue;
+    const uint64_t rk = revcomp(key, k);
+    uint64_t ef[4], er[4];
+    base_planes(key, ef);
+    base_planes(rk, er);
+    for (uint32_t p = 0; p < n_prim; ++p) {
+      const PrimerDev &P = sp[p];
+      const bool ok = key != EMPTY && cum >= P.min_count;
+      const uint32_t f = P.L - (uint32_t)__popcll((ef[0] & P.allow[0]) | (ef[1] & P.allow[1]) |
+                                                  (ef[2] & P.allow[2]) | (ef[3] & P.allow[3]));
+      const uint32_t r = P.L - (uint32_t)__popcll((er[0] & P.allow[0]) | (er[1] & P.allow[1]) |
+                                                  (er[2] & P.allow[2]) | (er[3] & P.allow[3]));
+      const bool hf = ok && f <= P.M;
+      const bool hr = ok && r <= P.M && r != f;
+      const uint64_t bf = __ballot(hf), br = __ballot(hr);
+      if (!(bf | br)) continue;
+      const uint32_t nf = (uint32_t)__popcll(bf);
+      unsigned long long at = 0;
+      if (lane == 0) at = atomicAdd(n_out, (unsigned long long)(nf + __popcll(br)));
+      at = __shfl(at, 0);
+      const uint32_t tag = (p_base + p) << 8;
+      if (hf) {
+        const unsigned long long i = at + __popcll(bf & below);
+        if (i < cap) out[i] = PrimerRec{key, cum, tag | f};
+        atomicAdd(&cnt[p * stride + f], 1u);
+      }
+      if (hr) {
+        const unsigned long long i = at + nf + __popcll(br & below);
+        if (i < cap) out[i] = PrimerRec{rk, cum, tag | r};
+        atomicAdd(&cnt[p * stride + r], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_prim * stride; i += WG)
+    if (cnt[i]) atomicAdd(&hits[(uint64_t)(p_base + i / stride) * SHK_PRIMER_LEVELS + i % stride], (unsigned long long)cnt[i]);
+}
+
+// ==========================================================================================
 // K_FILTER: PrimerReadFilter::matches (src/pcr/read_filter.rs:43-49) for a batch of reads: a read
 // matches when kmers_from_ascii accepts it (no byte outside ACGTN — otherwise the reference
 // returns false for the whole read) and at least one of its canonical k-mers is in the set.

@@ -9,6 +9,7 @@
 #include "../../include/shk.h"
 #include "shk_device.hip.h"
 #include "shk_front.h"
+#include "shk_primer.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3453,6 +3454,184 @@ int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint3
   uint64_t m = std::min<uint64_t>(n, cap);
   if (m && kmers) HIPC(c, hipMemcpy(kmers, dk, m * 8, hipMemcpyDeviceToHost));
   if (m && counts) HIPC(c, hipMemcpy(counts, dc, m * 4, hipMemcpyDeviceToHost));
+  return SHK_OK;
+}
+
+namespace {
+
+// One k_primer_scan pass over c's slots (the owned pages of an owner share): the per-(primer, level) hits (dev's
+// order) and, when they fit in `room`, the records.  *n_total = records the pass produced (> room: none returned).
+int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, std::vector<PrimerRec> *recs,
+                std::vector<uint64_t> *hits, uint64_t *n_total) {
+  HIPC(c, hipSetDevice(c->cfg.device));
+  {
+    int rcs = settle(c);
+    if (rcs != SHK_OK) return rcs;
+  }
+  {
+    int rcf = tb_fresh(c);
+    if (rcf != SHK_OK) return rcf;
+  }
+  const uint32_t n = (uint32_t)dev.size();
+  uint32_t stride = 1;  // LDS counters per primer: levels 0..max M
+  for (const PrimerDev &d : dev) stride = std::max(stride, d.M + 1);
+  // primers per launch: their table and counters in 48 KiB of LDS (three workgroups per CU)
+  const uint32_t per_launch = (48u << 10) / (uint32_t)(sizeof(PrimerDev) + 4 * stride);
+  const size_t hits_b = (size_t)n * SHK_PRIMER_LEVELS * 8, prim_b = (size_t)n * sizeof(PrimerDev);
+  HIPC(c, c->misc.ensure(16 + hits_b + prim_b + room * sizeof(PrimerRec)));
+  uint8_t *p = (uint8_t *)c->misc.p;
+  unsigned long long *dn = (unsigned long long *)p;
+  unsigned long long *dhits = (unsigned long long *)(p + 16);
+  PrimerDev *dprim = (PrimerDev *)(p + 16 + hits_b);
+  PrimerRec *drec = (PrimerRec *)(p + 16 + hits_b + prim_b);
+  HIPC(c, hipMemsetAsync(p, 0, 16 + hits_b, c->stream));
+  HIPC(c, hipMemcpyAsync(dprim, dev.data(), prim_b, hipMemcpyHostToDevice, c->stream));
+  uint64_t s0 = 0, s1 = c->tb.cap;
+  if (c->own_set) {
+    own_resolve(c);
+    s0 = c->own_p0 << PAGE_LOG;
+    s1 = c->own_p1 << PAGE_LOG;
+  }
+  for (uint32_t b = 0; b < n; b += per_launch) {
+    const uint32_t nb = std::min(per_launch, n - b);
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_primer_scan, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG),
+                       (size_t)nb * (sizeof(PrimerDev) + 4 * stride), c->stream, c->tb, s0, s1, (int)c->cfg.k,
+                       (const PrimerDev *)(dprim + b), nb, b, stride, drec, (uint64_t)room, dn, dhits);
+  }
+  HIPC(c, hipGetLastError());
+  unsigned long long nt = 0;
+  hits->assign((size_t)n * SHK_PRIMER_LEVELS, 0);
+  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(hits->data(), dhits, hits_b, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps dev alive until its copy ran)
+  *n_total = nt;
+  recs->clear();
+  if (nt <= room && nt) {
+    recs->resize(nt);
+    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
+  }
+  return SHK_OK;
+}
+
+}  // namespace
+
+int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
+                     uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
+  if (n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
+  const uint32_t k = c->cfg.k;
+  // preprocess_primer_by_mismatch of every direction before any scan (primers.rs:440-450), then the conversion
+  // check of the searched ones (their first round, primers.rs:383-393)
+  std::vector<PrimerPlan> plans(n_primers);
+  std::string msg;
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    const int rc = primer_plan(&primers[i], k, &plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
+  }
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    const int rc = primer_check_chars(plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
+  }
+  uint64_t need = 0;
+  for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
+  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
+  if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
+  if (level_hits) std::fill(level_hits, level_hits + (size_t)n_primers * SHK_PRIMER_LEVELS, 0ull);
+  std::vector<uint32_t> who;  // searched primer j = primers[who[j]]
+  std::vector<PrimerDev> dev;
+  for (uint32_t i = 0; i < n_primers; ++i)
+    if (plans[i].scanned()) {
+      const PrimerPlan &pl = plans[i];
+      who.push_back(i);
+      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, pl.min_count, 0});
+    }
+  const uint32_t n = (uint32_t)dev.size();
+  std::vector<shk_ctx *> parts;  // a multi-device context: its shares are disjoint, the answer is the top of the union
+  if (c->group)
+    for (uint32_t d = 0; d < c->group->D; ++d) parts.push_back(c->group->ctx[d]);
+  else
+    parts.push_back(c);
+  auto part_fail = [&](int rc, uint32_t d) { return c->group ? group_fail(c, c->group, rc, d) : rc; };
+  std::vector<PrimerRec> all;
+  std::vector<uint64_t> hits((size_t)n * SHK_PRIMER_LEVELS, 0);
+  if (n) {
+    const int env_room = env_int("SHK_PRIMER_CANDIDATES", 1 << 18);
+    const uint64_t room = (uint64_t)std::max(env_room, 1);
+    std::vector<std::vector<uint64_t>> part_hits(parts.size());
+    std::vector<uint64_t> part_n(parts.size());
+    std::vector<PrimerRec> recs;
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      const int rc = primer_pass(parts[d], dev, room, &recs, &part_hits[d], &part_n[d]);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      all.insert(all.end(), recs.begin(), recs.end());
+      for (size_t j = 0; j < hits.size(); ++j) hits[j] += part_hits[d][j];
+    }
+    // The record buffer overflowed: the counts are complete, so each primer's cut level is known — the first level
+    // at which its hits reach max_kmers.  Nothing above it can be selected; rerun keeping levels ≤ cut, sized exactly.
+    std::vector<PrimerDev> cut = dev;
+    for (uint32_t j = 0; j < n; ++j) {
+      uint64_t acc = 0;
+      for (uint32_t m = 0; m <= dev[j].M; ++m) {
+        acc += hits[(size_t)j * SHK_PRIMER_LEVELS + m];
+        if (acc >= plans[who[j]].max_kmers) {
+          cut[j].M = m;
+          break;
+        }
+      }
+    }
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      if (part_n[d] <= room) continue;
+      uint64_t exact = 0;
+      for (uint32_t j = 0; j < n; ++j)
+        for (uint32_t m = 0; m <= cut[j].M; ++m) exact += part_hits[d][(size_t)j * SHK_PRIMER_LEVELS + m];
+      std::vector<uint64_t> h2;
+      uint64_t n2 = 0;
+      const int rc = primer_pass(parts[d], cut, exact, &recs, &h2, &n2);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      if (n2 != exact)
+        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu",
+                    (unsigned long long)n2, (unsigned long long)exact);
+      all.insert(all.end(), recs.begin(), recs.end());
+    }
+  }
+  // Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
+  // sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
+  // here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
+  // and two entries never yield the same k-mer because the table holds canonical k-mers only — so the reference's
+  // "already found at a lower level" filter (primers.rs:398-403) never drops anything.
+  std::vector<uint64_t> first(n + 1, 0);
+  for (const PrimerRec &r : all) ++first[(r.tag >> 8) + 1];
+  for (uint32_t j = 0; j < n; ++j) first[j + 1] += first[j];
+  std::vector<PrimerRec> by(all.size());
+  {
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (const PrimerRec &r : all) by[at[r.tag >> 8]++] = r;
+  }
+  auto before = [](const PrimerRec &a, const PrimerRec &b) {
+    const uint32_t la = a.tag & 0xFF, lb = b.tag & 0xFF;
+    if (la != lb) return la < lb;
+    if (a.count != b.count) return a.count > b.count;
+    return a.kmer < b.kmer;
+  };
+  uint64_t o = 0;
+  uint32_t j = 0;
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    offsets[i] = o;
+    if (j >= n || who[j] != i) continue;
+    PrimerRec *b = by.data() + first[j], *e = by.data() + first[j + 1];
+    const uint64_t take = std::min<uint64_t>(plans[i].max_kmers, (uint64_t)(e - b));
+    std::partial_sort(b, b + take, e, before);
+    for (uint64_t t = 0; t < take; ++t, ++o) {
+      kmers[o] = b[t].kmer;
+      counts[o] = b[t].count;
+      levels[o] = (uint8_t)(b[t].tag & 0xFF);
+    }
+    if (level_hits) std::copy(hits.begin() + (size_t)j * SHK_PRIMER_LEVELS, hits.begin() + (size_t)(j + 1) * SHK_PRIMER_LEVELS,
+                              level_hits + (size_t)i * SHK_PRIMER_LEVELS);
+    ++j;
+  }
+  offsets[n_primers] = o;
   return SHK_OK;
 }
 

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -92,6 +93,42 @@ class _RunConfig(C.Structure):
                 ("device_ids", C.POINTER(C.c_int32))]
 
 
+class _Primer(C.Structure):
+    _fields_ = [("seq", C.c_char_p), ("trim", C.c_uint32), ("mismatches", C.c_uint32),
+                ("min_count", C.c_uint32), ("max_kmers", C.c_uint32)]
+
+
+PRIMER_LEVELS = 33  # SHK_PRIMER_LEVELS: level slots per primer in level_hits / n_variants (include/shk.h)
+
+
+@dataclass(frozen=True)
+class Primer:
+    """One primer direction of sPCR (PCRParams' forward_seq or reverse_seq, src/pcr/mod.rs) with the fields
+    get_primer_kmers reads (pcr/primers.rs:234-480); defaults are the reference's."""
+    seq: str
+    trim: int = 15
+    mismatches: int = 2
+    min_count: int = 2
+    max_kmers: int = 40  # max_primer_kmers
+
+    def _c(self) -> _Primer:
+        return _Primer(self.seq.encode("latin-1"), self.trim, self.mismatches, self.min_count, self.max_kmers)
+
+
+def primer_compile(primer: Primer, k: int):
+    """preprocess_primer_by_mismatch (pcr/primers.rs:237-313) on the host, no device: (trimmed length, level sizes
+    as a list of n_levels ints).  Raises ShkError with the reference's text (too many variants, invalid character)."""
+    L = load_library()
+    tl, nl = C.c_uint32(0), C.c_uint32(0)
+    nv = (C.c_uint64 * PRIMER_LEVELS)()
+    err = C.create_string_buffer(1024)
+    p = primer._c()
+    rc = L.shk_primer_compile(C.byref(p), k, C.byref(tl), C.byref(nl), nv, err, len(err))
+    if rc != 0:
+        raise ShkError(rc, err.value.decode("utf-8", "replace"))
+    return int(tl.value), [int(x) for x in nv[:nl.value]]
+
+
 class _Synth(C.Structure):
     _fields_ = [("seed_genome", C.c_uint64), ("seed_reads", C.c_uint64), ("genome_len", C.c_uint64),
                 ("read_len", C.c_uint32), ("sub_per_64k", C.c_uint32), ("n_per_64k", C.c_uint32),
@@ -103,7 +140,7 @@ ABI_SYMBOLS = [
     "shk_abi_version", "shk_create", "shk_destroy", "shk_reset", "shk_last_error", "shk_ingest_batch",
     "shk_ingest_reads", "shk_set_read_index", "shk_ingest_reads_device", "shk_insert_counts", "shk_sync", "shk_finalize",
     "shk_histograms", "shk_get_counters", "shk_get_timings", "shk_reset_timings",
-    "shk_export_table", "shk_lookup", "shk_find_oligos", "shk_filter_reads", "shk_kmers_from_reads", "shk_table_geometry", "shk_table_reserve_pages", "shk_owner_counts", "shk_compact_owners",
+    "shk_export_table", "shk_lookup", "shk_find_oligos", "shk_primer_compile", "shk_primer_kmers", "shk_filter_reads", "shk_kmers_from_reads", "shk_table_geometry", "shk_table_reserve_pages", "shk_owner_counts", "shk_compact_owners",
     "shk_merge_entries",
     "shk_table_device_ptrs", "shk_merge_pages", "shk_set_owned_pages", "shk_alloc_pinned",
     "shk_free_pinned", "shk_alloc_device", "shk_free_device", "shk_release_cached_memory", "shk_synth_reads_device",
@@ -229,6 +266,9 @@ def load_library():
     L.shk_export_table.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.shk_lookup.argtypes = [vp, vp, vp, u64, C.c_int]
     L.shk_find_oligos.argtypes = [vp, vp, u32, u32, u32, vp, vp, u64, C.POINTER(u64)]
+    L.shk_primer_compile.argtypes = [C.POINTER(_Primer), u32, C.POINTER(u32), C.POINTER(u32), vp, C.c_char_p,
+                                     C.c_size_t]
+    L.shk_primer_kmers.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, vp]
     L.shk_filter_reads.argtypes = [vp, vp, vp, u64, vp, u64, vp]
     L.shk_kmers_from_reads.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
     L.shk_owner_counts.argtypes = [vp, u32, vp]
@@ -483,6 +523,34 @@ class KmerEngine:
                                                 min_count, keys.ctypes.data, cnts.ctypes.data, cap, C.byref(n)))
         o = np.argsort(keys, kind="stable")
         return keys[o], cnts[o]
+
+    def primer_kmers(self, primers):
+        """get_primer_kmers (pcr/primers.rs:234-480) for every primer direction in one pass over the table
+        (shk_primer_kmers) → per primer (kmers u64, counts u32, levels u8, level_hits u64[PRIMER_LEVELS]), the
+        k-mers in the reference's insertion order: level ascending, count descending, k-mer ascending."""
+        primers = list(primers)
+        n = len(primers)
+        arr = (_Primer * max(n, 1))(*[p._c() for p in primers])
+        cap = sum(p.max_kmers for p in primers)
+        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
+        counts = np.zeros(max(cap, 1), dtype=np.uint32)
+        levels = np.zeros(max(cap, 1), dtype=np.uint8)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        hits = np.zeros((max(n, 1), PRIMER_LEVELS), dtype=np.uint64)
+        self._check(self._L.shk_primer_kmers(self._h, C.cast(arr, C.c_void_p), n, kmers.ctypes.data,
+                                             counts.ctypes.data, levels.ctypes.data, cap, offsets.ctypes.data,
+                                             hits.ctypes.data))
+        out = []
+        for i in range(n):
+            a, b = int(offsets[i]), int(offsets[i + 1])
+            out.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[i].copy()))
+        return out
+
+    def primer_pair_kmers(self, forward: str, reverse: str, **params):
+        """get_primer_kmers (pcr/primers.rs:440-480) for one PCRParams: (forward, reverse), each as primer_kmers
+        returns it.  params: trim, mismatches, min_count, max_kmers (the reference's defaults otherwise)."""
+        fwd, rev = self.primer_kmers([Primer(forward, **params), Primer(reverse, **params)])
+        return fwd, rev
 
     def filter_reads(self, bases: np.ndarray, offsets: np.ndarray, primer_kmers) -> np.ndarray:
         """PrimerReadFilter::matches per read (pcr/read_filter.rs:43-55) → bool array."""
