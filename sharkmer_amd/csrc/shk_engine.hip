@@ -2087,6 +2087,12 @@ int shk_create(const shk_config *cfg, shk_ctx **out) {
     // an owner share starts with enough pages for 4-byte exchange records (2k − level-1 bits ≤ 32, the
     // level-1 fan-out being at most the page bits of the virtual table): k = 21 → 2^10 pages over all owners
     want = std::max<uint64_t>(want, (uint64_t)PAGE_SLOTS << (2 * cfg->k - 32 - c->owner_bits));
+  if (c->is_share() && (uint32_t)env_int("SHK_LEVEL1_LOG", 10) > c->owner_bits)
+    // ... and with the level-1 fan-out's pages over all owners, so that the exchange layout (part_geom: log_p1 =
+    // min(fan-out bits, page bits of the virtual table)) is the same on every share and stays what it is when a
+    // share's table grows: a segment is absorbed at the geometry it was scattered at, and a table that grew between
+    // two absorbs of one round (the flush in front of the second one) used to refuse the rest of the round
+    want = std::max<uint64_t>(want, (uint64_t)PAGE_SLOTS << ((uint32_t)env_int("SHK_LEVEL1_LOG", 10) - c->owner_bits));
   // (the table's memory is not cleared here either: see tb_stale)
   const bool lazy = !env_int("SHK_NO_FRESH", 0);
   int rc = alloc_table(c, log_pages_for(want, c->owner_bits), &c->tb, !lazy);
@@ -2170,6 +2176,7 @@ int shk_reset(shk_ctx *c) {
       if (rc != SHK_OK) return group_fail(c, g, rc, d);
     }
     g->next_read = 0;
+    g->n_inserted = 0;
     g->finalized = g->hist_ready = false;
     c->err.clear();
     return SHK_OK;
@@ -2642,6 +2649,7 @@ int shk_insert_counts(shk_ctx *c, uint32_t chunk_id, const uint64_t *kmers, cons
       const int rc = shk_insert_counts(g->ctx[d], chunk_id, kmers, counts, n);
       if (rc != SHK_OK) return group_fail(c, g, rc, d);
     }
+    g->n_inserted += n;
     return SHK_OK;
   }
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());

@@ -62,6 +62,7 @@ struct shk_group {
   std::vector<int> status;
   // run state
   uint64_t next_read = 0;  // global index of the next read (shk_set_read_index)
+  uint64_t n_inserted = 0;  // entries handed to shk_insert_counts since the last reset: input like reads are (as on one device)
   bool finalized = false, hist_ready = false;
   std::vector<uint64_t> hist;
   shk_counters tot{};
@@ -434,7 +435,7 @@ int group_finalize(shk_ctx *top) {
   if (g->cfg.chunks > 0) t.n_singleton_kmers = g->hist[(size_t)(g->cfg.chunks - 1) * (g->cfg.histo_max + 2) + 1];
   g->tot = t;
   g->hist_ready = true;
-  if (t.n_reads_ingested == 0)  // io.rs:578-580, on the whole job
+  if (t.n_reads_ingested == 0 && g->n_inserted == 0)  // io.rs:578-580, on the whole job
     return fail(top, SHK_ERR_NO_READS, "No reads were ingested. Check that input files contain valid FASTQ records.");
   if (t.n_hashed_kmers != t.n_kmers_ingested)  // io.rs:1042-1047
     return fail(top, SHK_ERR_INVARIANT, "The total count of hashed kmers (%llu) does not equal the number of ingested kmers (%llu)",

@@ -1,0 +1,162 @@
+"""The reference's data model of a counting run, call by call — the expected answer of the call-sequence sweep
+(tests/test_gpu_sequences.py).  CPU only, oracle only.
+
+A context is n_lanes = max(chunks, 1) `KmerCounts` (one per Chunk, io.rs:378-379), a running read index and the
+read/base counters of FastqReadState.  Nothing is merged until somebody looks: an observation builds a fresh merged
+`KmerCounts` and a fresh `Histogram` and extends them lane after lane, taking `get_vector()` after each — literally
+io.rs:1020-1028 — so the model has no state of its own that a call order could leave stale.  What the engine keeps
+between calls (a merged table, lazily cleared blocks, a histogram left behind by a page pass) has no counterpart
+here: that is the point."""
+from __future__ import annotations
+
+import numpy as np
+
+import primer_ref
+
+U32_MAX = 0xFFFFFFFF
+_VALID = np.zeros(256, dtype=bool)
+_VALID[list(b"ACGTN")] = True
+
+NO_READS = "No reads were ingested. Check that input files contain valid FASTQ records."  # io.rs:578-580
+
+
+class ModelError(Exception):
+    """The reference's anyhow error, with its text."""
+
+
+class Observation:
+    """What consolidate_and_histogram leaves (io.rs:1020-1047): the merged table, one histogram column per lane,
+    the saturation warning and the totals."""
+
+    def __init__(self, merged, columns, any_saturated, lane_sum):
+        self.merged, self.columns, self.any_saturated, self.lane_sum = merged, columns, any_saturated, lane_sum
+        self.keys, self.counts = merged.export()
+        self.n_unique = len(merged)
+        self.n_hashed = merged.get_n_kmers()
+
+
+class LaneModel:
+    def __init__(self, orc, k: int, chunks: int, histo_max: int):
+        self.orc, self.k, self.chunks, self.histo_max = orc, k, chunks, histo_max
+        self.n_lanes = max(chunks, 1)  # io.rs:378
+        self.reset()
+
+    # ---- operations ------------------------------------------------------------------------------
+    def reset(self):
+        """A fresh FastqReadState (io.rs:381-387)."""
+        self.lanes = [self.orc.KmerCounts(self.k) for _ in range(self.n_lanes)]
+        self.read_index = 0
+        self.n_reads = self.n_bases_read = self.n_bases_ingested = self.n_inserted = 0
+        self._obs = None
+
+    def set_read_index(self, i: int):
+        self.read_index = int(i)
+
+    @staticmethod
+    def first_bad_byte(bases, offsets):
+        """The first byte outside ACGTN in input order (encoding.rs:353-356), or None."""
+        lo, hi = int(offsets[0]), int(offsets[-1])
+        bad = np.flatnonzero(~_VALID[np.asarray(bases[lo:hi], dtype=np.uint8)])
+        return int(bases[lo + int(bad[0])]) if len(bad) else None
+
+    @staticmethod
+    def bad_byte_message(b: int) -> str:
+        return "Invalid character '%s' in sequence. Only ACGTN allowed." % chr(b)
+
+    def _ingest(self, bases, offsets, lane_of):
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = [int(x) for x in offsets]
+        bad = self.first_bad_byte(bases, off)
+        if bad is not None:
+            raise ModelError(self.bad_byte_message(bad))
+        self._obs = None
+        raw = bases.tobytes()
+        for i in range(len(off) - 1):
+            self.lanes[lane_of(i)].ingest_seq(raw[off[i]:off[i + 1]])  # Chunk::ingest_seq, chunk.rs:25-30
+        n = len(off) - 1
+        self.n_reads += n
+        self.n_bases_read += off[-1] - off[0]
+        self.n_bases_ingested += int((bases[off[0]:off[-1]] != ord("N")).sum())  # chunk.rs:28
+        return n
+
+    def ingest_reads(self, bases, offsets):
+        """read_fastq's cadence: read i goes to lane (i // 1000) % n_lanes (io.rs:340-361)."""
+        first = self.read_index
+        n = self._ingest(bases, offsets, lambda i: ((first + i) // 1000) % self.n_lanes)
+        self.read_index = first + n
+
+    def ingest_batch(self, chunk_id: int, bases, offsets):
+        """drain_batch's body with an explicit chunk (io.rs:356-358); the striping index stays."""
+        assert 0 <= chunk_id < self.n_lanes
+        self._ingest(bases, offsets, lambda i: chunk_id)
+
+    def insert(self, chunk_id: int, kmers, counts):
+        """KmerCounts::insert (counting.rs:152-154): the entry is created whatever the count, the add saturates."""
+        assert 0 <= chunk_id < self.n_lanes
+        self._obs = None
+        for key, c in zip(np.atleast_1d(kmers).tolist(), np.atleast_1d(counts).tolist()):
+            self.lanes[chunk_id].insert(int(key), int(c))
+            self.n_inserted += 1
+
+    # ---- observations ----------------------------------------------------------------------------
+    def is_empty(self) -> bool:
+        return self.n_reads == 0 and self.n_inserted == 0
+
+    def observe(self) -> Observation:
+        if self._obs is None:
+            est = sum(len(l) for l in self.lanes)  # io.rs:1005-1006
+            merged, histo = self.orc.KmerCounts(self.k, est), self.orc.Histogram(self.histo_max)
+            cols, sat = [], False
+            for lane in self.lanes:  # io.rs:1023-1028
+                sat |= merged.extend_with_histogram(lane, histo)
+                cols.append(histo.get_vector())
+            self._obs = Observation(merged, np.stack(cols), sat, sum(l.get_n_kmers() for l in self.lanes))
+        return self._obs
+
+    def columns(self) -> np.ndarray:
+        """histo_vecs: (chunks, histo_max + 2); chunks = 0 has none (io.rs:1133-1158)."""
+        return self.observe().columns[:self.chunks]
+
+    def totals(self) -> dict:
+        o = self.observe()
+        t = dict(n_reads_ingested=self.n_reads, n_bases_read=self.n_bases_read, n_bases_ingested=self.n_bases_ingested,
+                 n_kmers_ingested=o.lane_sum, n_unique_kmers=o.n_unique, n_hashed_kmers=o.n_hashed,
+                 any_saturated=int(o.any_saturated))
+        if self.chunks > 0:
+            t["n_singleton_kmers"] = int(o.columns[-1][1])  # io.rs:1096-1099
+        return t
+
+    def finalize(self) -> Observation:
+        """consolidate_and_histogram's checks in the reference's order; the observation is computed by then."""
+        if self.is_empty():
+            raise ModelError(NO_READS)
+        o = self.observe()
+        if o.n_hashed != o.lane_sum:  # io.rs:1042-1047
+            raise ModelError("The total count of hashed kmers (%d) does not equal the number of ingested kmers (%d)"
+                             % (o.n_hashed, o.lane_sum))
+        if self.chunks > 0:
+            nu = int(o.columns[-1][1:].sum())
+            if nu != o.n_unique:  # io.rs:1127-1132: a key with merged count 0 sits in no bin
+                raise ModelError("The total count of unique kmers in the histogram (%d) does not equal the total "
+                                 "count of hashed kmers (%d)" % (nu, o.n_unique))
+        return o
+
+    def export(self):
+        o = self.observe()
+        return o.keys, o.counts
+
+    def get_count(self, kmers, canonical: bool = False) -> np.ndarray:
+        m = self.observe().merged
+        f = m.get_canonical_count if canonical else m.get_count
+        return np.array([f(int(x)) for x in np.atleast_1d(kmers).tolist()], dtype=np.uint32)
+
+    def find_oligos(self, oligos, oligo_len: int, min_count: int = 1):
+        return self.observe().merged.find_oligos(oligos, oligo_len, min_count)
+
+    def primer_kmers(self, primers):
+        """get_primer_kmers per direction over the merged table (tests/primer_ref.py)."""
+        keys, counts = self.export()
+        for p in primers:
+            primer_ref.check_variant_limit(p.seq, p.trim, self.k)
+        return [primer_ref.get_primer_kmers(p.seq, keys, counts, self.k, p.trim, p.mismatches, p.min_count,
+                                            p.max_kmers, check_variants=False) for p in primers]
