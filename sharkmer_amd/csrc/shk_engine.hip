@@ -287,7 +287,7 @@ struct shk_ctx {
   hipEvent_t copy_done[NST] = {};
   int stage_last = -1;            // the staging set the last slice of the previous host-buffer ingest took (its count may still be in flight)
   bool zero_count_keys = false;   // some key may have been inserted with count 0 (shk_insert_counts, merges): k_histo reads the keys
-  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter_own = false, lds_attr_scatter64 = false;  // hipFuncSetAttribute done for this context's device
+  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter64 = false;  // hipFuncSetAttribute done for this context's device
   HostBuf h_rebased[NST];           // pinned staging of a slice's re-based offsets (a pageable source would make the copy synchronous)
   DevBuf in_bases, in_offsets, st_bases[NST], st_offsets[NST], startbits, tiles, spillA, spillB, misc, part, part2, part3, part_meta;
   DevBuf pk_stage[NST], nm_stage[NST], nz_dev[NST], pk_ascii;
@@ -362,7 +362,17 @@ int fail(shk_ctx *c, int code, const char *fmt, ...) {
   return code;
 }
 
-#define HIPC(c, expr)                                                                       \
+// An invalid byte in the input (stats->bad): identical text to encoding.rs:353-356.  `poison`: the context's table
+// may hold part of the batch, so every later call fails the same way.
+int fail_invalid_char(shk_ctx *c, uint64_t bad, bool poison = true) {
+  if (poison) {
+    c->poisoned = true;
+    c->poison_code = SHK_ERR_INVALID_CHAR;
+  }
+  return fail(c, SHK_ERR_INVALID_CHAR, "Invalid character '%s' in sequence. Only ACGTN allowed.", shk::byte_as_char((uint8_t)(bad & 0xFF)).c_str());
+}
+
+#define HIPC(c, expr)                                                                      \
   do {                                                                                      \
     hipError_t e__ = (expr);                                                                \
     if (e__ != hipSuccess)                                                                  \
@@ -829,13 +839,76 @@ static bool xl_feasible(const shk_ctx *c, const PartGeom &g) {
   return g.two_level && use_scatter32(c, g) && (1u << g.log_sub) <= (uint32_t)MAX_PARTS && c->n_lanes <= shk::SC32_MAX_LANES &&
          g.lpg <= MAX_LOG_PAGES;
 }
-static bool xl64_feasible(const shk_ctx *c, const PartGeom &g);
+// k_scatter64: the 8-byte-record scatter with k_scatter32's shape (records carried in registers, sorted in LDS).
+// (Two 512-thread workgroups per CU on 8 Ki-position tiles and 512 partitions — the shape that lets two workgroups'
+// phases overlap without doubling the reservations per k-mer — measured 12.2 ms against 11.4-11.6 per 24 M reads of
+// config 3, the level-2 pass 3 % slower on top: not kept.)
+static size_t scatter64_lds(uint32_t P1) { return (size_t)(SC32_TT + P1) * 8 + (size_t)P1 * 12 + (size_t)(SC32_NT + 2) * 8 + 32; }
+static bool use_scatter64(const shk_ctx *c, const PartGeom &g) {
+  return !use_rec32(c, g) && g.log_p1 >= 3 && g.P1 <= (uint32_t)SC32_NT && c->cfg.k >= 18 && SC32_NT == 1024 && scatter64_lds(g.P1) <= SC32_LDS_MAX &&
+         env_int("SHK_SCATTER64", 1) != 0;
+}
+// The owner layout with 8-byte records (k > 21: the mixed key's remainder does not fit a word), see xl_scatter below.
+static bool xl64_feasible(const shk_ctx *c, const PartGeom &g) {
+  // (≤ 32 chunk lanes: a round's segments — lanes · 2^log_p1 regions of at least 1024 records — stay below the 4 GiB the scatter addresses)
+  return g.two_level && use_scatter64(c, g) && g.log_sub <= 10 && c->n_lanes <= 32 && g.lpg <= MAX_LOG_PAGES &&
+         env_int("SHK_DEFER", 1) != 0 && env_int("SHK_XL64", 1) != 0;
+}
 // … and the same layout with 8-byte records for a share whose records do not fit a word (k > 21): its own ingest
 static bool xl64_route(const shk_ctx *c, const PartGeom &g) { return c->is_share() && !xl_feasible(c, g) && xl64_feasible(c, g); }
 static bool xl_route(const shk_ctx *c, const PartGeom &g, bool multi, bool defer) {
   if (!xl_feasible(c, g)) return false;
   if (c->is_share()) return true;
   return defer && multi && env_int("SHK_XL", 1) != 0;
+}
+
+// How one paged counting launch goes, as far as the table geometry, the batch's kind (multi: tiles of several chunk
+// lanes) and the path (defer) decide it.  prepare_cursors — which has k_mark_starts clear the launch's cursor words
+// ahead of time — and paged_count both read THIS; what depends on the batch's size (region capacities, the fall-back
+// of all_lanes to a pass per lane) is paged_count's second step, which may use fewer cursor words, never more.
+enum OwnerLayout { XL_NONE, XL_REC32, XL_REC64 };
+enum Scatter1 { SCATTER_32, SCATTER_64_LINEAR, SCATTER_64_INTERLEAVED, SCATTER_SORTED };  // the level-1 kernel
+struct PagedRoute {
+  OwnerLayout owner;      // the owner layout (xl_count) instead of everything below
+  uint32_t rec_bytes;     // 4 or 8
+  Scatter1 scatter;       // (interleaved: the level-1 buffer of a two-level pass, what k_part_rescatter reads tile by tile)
+  bool two_level;
+  bool all_lanes;         // ALL-LANES mode (immediate passes only; deferred: always (lane, page) regions)
+  bool one_pass;          // every lane's tiles in a single scatter launch
+  uint32_t cursor_words;  // per-launch cursor words, from the start of part_meta
+};
+static PagedRoute paged_route(const shk_ctx *c, const PartGeom &g, bool multi, bool defer) {
+  PagedRoute r{};
+  r.two_level = g.two_level;
+  r.owner = xl_route(c, g, multi, defer) ? XL_REC32 : defer && xl64_route(c, g) ? XL_REC64 : XL_NONE;
+  if (r.owner != XL_NONE) {  // one segment's cursors: [lane][super-page of the share]
+    r.rec_bytes = r.owner == XL_REC32 ? 4 : 8;
+    r.scatter = r.owner == XL_REC32 ? SCATTER_32 : SCATTER_64_LINEAR;
+    r.one_pass = r.owner == XL_REC32;
+    r.cursor_words = c->n_lanes << (g.log_p1 - g.lw);
+    return r;
+  }
+  const bool rec32 = use_rec32(c, g);
+  r.rec_bytes = rec32 ? 4 : 8;
+  if (rec32)
+    r.scatter = use_scatter32(c, g) ? SCATTER_32 : SCATTER_SORTED;
+  else if (use_scatter64(c, g))  // (the level-1 regions of k_scatter64 are interleaved in blocks of RS_TILE records)
+    r.scatter = g.two_level && env_int("SHK_S64_INTERLEAVE", 1) != 0 ? SCATTER_64_INTERLEAVED : SCATTER_64_LINEAR;
+  else
+    r.scatter = SCATTER_SORTED;
+  r.all_lanes = use_all_lanes(c, g, multi) && !defer;
+  r.one_pass = r.all_lanes || (defer && !g.two_level && rec32);
+  // deferred: page regions and cursors are the accumulation ones and persist; only a level-1 pass has cursors of its own
+  r.cursor_words = defer ? (g.two_level ? g.P1 : 0) : (r.all_lanes ? c->n_lanes : 1) * g.P1 + (g.two_level ? g.n_pages : 0);
+  return r;
+}
+
+// A chunk lane's share of the k-mers of a batch that is striped over the lanes: blocks of 1000 reads go round the
+// lanes, so a lane holds at most ceil(blocks / lanes) of them; half as much again for uneven read lengths (what
+// still overflows a region takes the spill path).
+static uint64_t striped_lane_ub(const shk_ctx *c, uint64_t sub_kmers_ub) {
+  const uint64_t NL = c->n_lanes, nb = std::max<uint64_t>(c->cur_blocks, 1);
+  return std::min<uint64_t>(sub_kmers_ub, sub_kmers_ub / nb * ((nb + NL - 1) / NL) * 3 / 2 + 2 * TILE_T);
 }
 
 // Which way a counting launch goes.
@@ -850,8 +923,6 @@ static bool xl_route(const shk_ctx *c, const PartGeom &g, bool multi, bool defer
 //   PATH_DIRECT : global atomics; whatever the paged paths cannot take (> 16 lanes, records that
 //                 do not fit 4 bytes on a table too small for an immediate pass, …)
 enum CountPath { PATH_DIRECT, PATH_PAGED, PATH_DEFER };
-static bool paged_feasible(const shk_ctx *c);
-static bool paged_pays(const shk_ctx *c, uint64_t sub_kmers_ub);
 static CountPath count_path(const shk_ctx *c, uint64_t sub_kmers_ub, bool multi = false) {
   if (!paged_feasible(c) || (c->cfg.flags & SHK_FLAG_FORCE_DIRECT)) return PATH_DIRECT;
   // a batch over several chunk lanes into a two-level table: the owner-layout route (ONE level-1 pass, ONE
@@ -1024,71 +1095,58 @@ static bool first_launch_defers(shk_ctx *c, uint64_t kmers_ub, bool multi) { ret
 
 // Bytes of the per-launch cursor buffer (part_meta).  One size for everybody who asks: the buffer
 // must not be reallocated between k_mark_starts (which clears cursors in it) and the partition launch.
-static bool xl64_feasible(const shk_ctx *c, const PartGeom &g);
-static size_t cursor_buf_bytes(const shk_ctx *c, const PartGeom &g, bool multi) {
-  const bool lanes = use_all_lanes(c, g, multi) || xl_feasible(c, g) || xl64_feasible(c, g);  // (the owner layouts: n_lanes · P1 words, whatever the number of segments)
+static size_t cursor_buf_bytes(const shk_ctx *c, const PartGeom &g, const PagedRoute &r) {
+  const bool lanes = r.all_lanes || r.owner != XL_NONE;  // (the owner layouts: n_lanes · P1 words, whatever the number of segments)
   return ((size_t)(lanes ? c->n_lanes : 1) * g.P1 + g.n_pages) * 4 + 64;
 }
 
 // Room for the partition cursors of the next paged pass; *n_words = how many k_mark_starts clears.
 static int prepare_cursors(shk_ctx *c, bool multi, bool defer, uint32_t *n_words) {
   const PartGeom g = part_geom(c);
-  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, multi)));
-  if (defer && (xl_route(c, g, multi, defer) || xl64_route(c, g))) {  // one segment's cursors: [lane][super-page of the share]
-    *n_words = c->n_lanes << (g.log_p1 - g.lw);
-    return SHK_OK;
-  }
-  if (defer) {  // the page regions' cursors persist; only a level-1 pass has per-launch cursors
-    *n_words = g.two_level ? g.P1 : 0;
-    return SHK_OK;
-  }
-  const size_t lanes = use_all_lanes(c, g, multi) ? c->n_lanes : 1;
-  *n_words = (uint32_t)(lanes * g.P1) + (g.two_level ? g.n_pages : 0);
+  const PagedRoute r = paged_route(c, g, multi, defer);
+  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, r)));
+  *n_words = r.cursor_words;
   return SHK_OK;
 }
 
-// k_scatter32 is compiled in eight variants — 64-bit offsets into the accumulation buffer or not; the
+// k_scatter32 is compiled in ten variants — 64-bit offsets into the accumulation buffer or not; the
 // fan-out of 1024 (one partition per thread: what every table from 8 M slots up gets) as a compile-time
-// constant or any fan-out at run time; one chunk lane or all of them in one pass — and asks for more
-// than 64 KiB of dynamic LDS, which has to be allowed per function and device.
-template <bool W, int LP, bool A>
+// constant or any fan-out at run time; one chunk lane or all of them in one pass; and, for all lanes and
+// 32-bit offsets, the owner layout (`own`) — and asks for more than 64 KiB of dynamic LDS, which has to be
+// allowed per function and device.
+template <bool W, int LP, bool A, bool OWN>
 static hipError_t scatter32_variant(shk_ctx *c, bool set_attr, uint32_t G, size_t lds, const BatchRef &b, uint32_t log_p1,
                                     uint32_t lane_filter, unsigned int *cursor, uint32_t cap, uint32_t *buf, SpillRef sp,
-                                    unsigned long long *dbg, uint32_t NL) {
+                                    unsigned long long *dbg, uint32_t NL, OwnerCfg own) {
   if (set_attr)
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scatter32<SC32_NT, SC32_TT, W, LP, A>),
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scatter32<SC32_NT, SC32_TT, W, LP, A, OWN>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC32_LDS_MAX);
-  hipLaunchKernelGGL((k_scatter32<SC32_NT, SC32_TT, W, LP, A>), dim3(G), dim3(SC32_NT), lds, c->stream, b, log_p1,
-                     lane_filter, cursor, cap, buf, c->d_stats, c->d_lane_bases, sp, dbg, NL, OwnerCfg{});
+  hipLaunchKernelGGL((k_scatter32<SC32_NT, SC32_TT, W, LP, A, OWN>), dim3(G), dim3(SC32_NT), lds, c->stream, b, log_p1,
+                     lane_filter, cursor, cap, buf, c->d_stats, c->d_lane_bases, sp, dbg, NL, own);
   return hipSuccess;
 }
 static int launch_scatter32(shk_ctx *c, bool wide, uint32_t G, size_t lds, const BatchRef &b, uint32_t log_p1,
                             uint32_t lane_filter, unsigned int *cursor, uint32_t cap, uint32_t *buf, SpillRef sp,
-                            unsigned long long *dbg, uint32_t NL) {
+                            unsigned long long *dbg, uint32_t NL, const OwnerCfg *own = nullptr) {
   const bool all = lane_filter == 0xFFFFFFFFu, p10 = log_p1 == 10;
-  auto each = [&](bool set_attr, bool w, bool p, bool a) -> hipError_t {
-#define SHK_V(W, LP, A) scatter32_variant<W, LP, A>(c, set_attr, G, lds, b, log_p1, lane_filter, cursor, cap, buf, sp, dbg, NL)
-    if (w) return p ? (a ? SHK_V(true, 10, true) : SHK_V(true, 10, false)) : (a ? SHK_V(true, 0, true) : SHK_V(true, 0, false));
-    return p ? (a ? SHK_V(false, 10, true) : SHK_V(false, 10, false)) : (a ? SHK_V(false, 0, true) : SHK_V(false, 0, false));
+  if (own && (wide || !all)) return fail(c, SHK_ERR_INVARIANT, "the owner layout's scatter takes every lane and 32-bit offsets");
+  const OwnerCfg oc = own ? *own : OwnerCfg{};
+  auto each = [&](bool set_attr, bool w, bool p, bool a, bool o) -> hipError_t {
+#define SHK_V(W, LP, A, O) scatter32_variant<W, LP, A, O>(c, set_attr, G, lds, b, log_p1, lane_filter, cursor, cap, buf, sp, dbg, NL, oc)
+    if (o) return p ? SHK_V(false, 10, true, true) : SHK_V(false, 0, true, true);
+    if (w) return p ? (a ? SHK_V(true, 10, true, false) : SHK_V(true, 10, false, false)) : (a ? SHK_V(true, 0, true, false) : SHK_V(true, 0, false, false));
+    return p ? (a ? SHK_V(false, 10, true, false) : SHK_V(false, 10, false, false)) : (a ? SHK_V(false, 0, true, false) : SHK_V(false, 0, false, false));
 #undef SHK_V
   };
   if (!c->lds_attr_scatter) {
-    for (int v = 0; v < 8; ++v) HIPC(c, each(true, v & 1, v & 2, v & 4));
+    for (int v = 0; v < 8; ++v) HIPC(c, each(true, v & 1, v & 2, v & 4, false));
+    for (int v = 0; v < 2; ++v) HIPC(c, each(true, false, v & 1, true, true));
     c->lds_attr_scatter = true;
   }
-  HIPC(c, each(false, wide, p10, all));
+  HIPC(c, each(false, wide, p10, all, own != nullptr));
   return SHK_OK;
 }
 
-// k_scatter64: the 8-byte-record scatter with k_scatter32's shape (records carried in registers, sorted in LDS).
-// (Two 512-thread workgroups per CU on 8 Ki-position tiles and 512 partitions — the shape that lets two workgroups'
-// phases overlap without doubling the reservations per k-mer — measured 12.2 ms against 11.4-11.6 per 24 M reads of
-// config 3, the level-2 pass 3 % slower on top: not kept.)
-static size_t scatter64_lds(uint32_t P1) { return (size_t)(SC32_TT + P1) * 8 + (size_t)P1 * 12 + (size_t)(SC32_NT + 2) * 8 + 32; }
-static bool use_scatter64(const shk_ctx *c, const PartGeom &g) {
-  return !use_rec32(c, g) && g.log_p1 >= 3 && g.P1 <= (uint32_t)SC32_NT && c->cfg.k >= 18 && SC32_NT == 1024 && scatter64_lds(g.P1) <= SC32_LDS_MAX &&
-         env_int("SHK_SCATTER64", 1) != 0;
-}
 template <int LAYOUT>
 static hipError_t scatter64_variant(shk_ctx *c, bool set_attr, uint32_t G, size_t lds, const BatchRef &b, uint32_t log_p1, uint32_t lane,
                                     unsigned int *cursor, uint32_t cap, uint64_t *buf, SpillRef sp, unsigned long long *dbg,
@@ -1131,61 +1189,52 @@ static XlPlan xl_plan(const shk_ctx *c, const PartGeom &g, uint64_t sub_kmers_ub
   const uint32_t NL = c->n_lanes;
   x.log_p1w = g.log_p1 - g.lw;
   x.n_grp = NL << x.log_p1w;
-  uint64_t lane_kmers_ub = sub_kmers_ub;
-  if (NL > 1) {
-    const uint64_t nb = std::max<uint64_t>(c->cur_blocks, 1);
-    const uint64_t per_lane_blocks = (nb + NL - 1) / NL;
-    lane_kmers_ub = std::min<uint64_t>(sub_kmers_ub, sub_kmers_ub / nb * per_lane_blocks * 3 / 2 + 2 * TILE_T);
-  }
+  const uint64_t lane_kmers_ub = NL > 1 ? striped_lane_ub(c, sub_kmers_ub) : sub_kmers_ub;
   x.cap1 = (region_cap(lane_kmers_ub, g.P1, 0) + (1u << RB_LOG) - 1u) & ~((1u << RB_LOG) - 1u);
   x.n_seg = keep_all ? 1u << g.lw : 1u;
   x.seg_recs = (uint64_t)x.n_grp * x.cap1;
   return x;
 }
 
-template <int LP>
-static hipError_t scatter32_own_variant(shk_ctx *c, bool set_attr, uint32_t G, size_t lds, const BatchRef &b, uint32_t log_p1,
-                                        unsigned int *cursor, uint32_t cap, uint32_t *buf, SpillRef sp, uint32_t NL, OwnerCfg own) {
-  if (set_attr)
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_scatter32<SC32_NT, SC32_TT, false, LP, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC32_LDS_MAX);
-  hipLaunchKernelGGL((k_scatter32<SC32_NT, SC32_TT, false, LP, true, true>), dim3(G), dim3(SC32_NT), lds, c->stream, b, log_p1,
-                     0xFFFFFFFFu, cursor, cap, buf, c->d_stats, c->d_lane_bases, sp, (unsigned long long *)nullptr, NL, own);
-  return hipSuccess;
-}
-
-// Level-1 scatter of b's tiles into the owner layout (c->xbuf, cursors at the start of c->part_meta).
-// keep_all: every owner's records, one segment per owner, overflow to the foreign spill list; otherwise
-// only this context's own records, one segment, overflow to `sp`.
-static int xl_scatter(shk_ctx *c, const BatchRef &b, const PartGeom &g, const XlPlan &x, SpillRef sp, bool keep_all,
+// Level-1 scatter of b's tiles into the owner layout (c->xbuf, cursors at the start of c->part_meta), in records of
+// `rec_bytes`: 4 (k_scatter32 in its owner variant, ONE launch for the tiles of every chunk lane), or 8 for k > 21,
+// where the mixed key's remainder does not fit a word and the canonical k-mer is the record (k_scatter64 in its owner
+// layout, a launch per chunk lane present in the batch).  The same segments either way — [owner][lane][super-page]
+// regions of cap1 records, their fill levels beside them.
+// keep_all: every owner's records, one segment per owner, overflow to the foreign spill list (the exchange rounds);
+// otherwise only this context's own records, one segment, overflow to `sp` (a share's own ingest: xl_count).
+static int xl_scatter(shk_ctx *c, uint32_t rec_bytes, const BatchRef &b, const PartGeom &g, const XlPlan &x, SpillRef sp, bool keep_all,
                       bool prezeroed) {
   const uint32_t NL = c->n_lanes;
   const uint64_t total = (uint64_t)x.n_seg * x.seg_recs;
-  if (total * 4 > 0xFFFFFFFFull)
-    return fail(c, SHK_ERR_INVARIANT, "level-1 buffer of one launch exceeds 4 GiB (%llu records)", (unsigned long long)total);
-  HIPC(c, c->xbuf.ensure(total * 4));
+  if (total * rec_bytes > 0xFFFFFFFFull)
+    return fail(c, SHK_ERR_INVARIANT, "level-1 buffer of one launch exceeds 4 GiB (%llu %u-byte records)", (unsigned long long)total, rec_bytes);
+  HIPC(c, c->xbuf.ensure(total * rec_bytes));
   unsigned int *cursor = (unsigned int *)c->part_meta.p;
   const size_t n_words = (size_t)x.n_seg * x.n_grp;
   if (c->part_meta.cap < n_words * 4) return fail(c, SHK_ERR_INVARIANT, "cursor buffer too small for the owner layout");
   if (!prezeroed) HIPC(c, hipMemsetAsync(cursor, 0, n_words * 4, c->stream));
-  if (!c->lds_attr_scatter_own) {
-    HIPC(c, scatter32_own_variant<0>(c, true, 0, 0, b, 0, nullptr, 0, nullptr, sp, NL, OwnerCfg{}));
-    HIPC(c, scatter32_own_variant<10>(c, true, 0, 0, b, 0, nullptr, 0, nullptr, sp, NL, OwnerCfg{}));
-    c->lds_attr_scatter_own = true;
-  }
   OwnerCfg own{};
   own.log_w = g.lw;
   own.keep = keep_all ? 0xFFFFFFFFu : c->owner_id;
   own.seg_recs = keep_all ? (uint32_t)x.seg_recs : 0u;
-  const uint32_t G = std::min<uint32_t>(grid_for(b.tile_count * (TILE_T / SC32_TT), 1, (uint32_t)env_int("SHK_PART_G", 512)), c->n_cus_scatter * SHK_SC32_WGS);
-  const size_t lds = scatter32_lds(g.P1);
-  {
+  const uint32_t g_cap = (uint32_t)env_int("SHK_PART_G", 512);
+  if (rec_bytes == 4) {
+    const uint32_t G = std::min<uint32_t>(grid_for(b.tile_count * (TILE_T / SC32_TT), 1, g_cap), c->n_cus_scatter * SHK_SC32_WGS);
     ScopedTimer t(c, SHK_K_SCATTER, /*chain=*/prezeroed && c->chain_from_mark);
     c->chain_from_mark = false;
-    if (g.log_p1 == 10)
-      HIPC(c, scatter32_own_variant<10>(c, false, G, lds, b, g.log_p1, cursor, x.cap1, (uint32_t *)c->xbuf.p, sp, NL, own));
-    else
-      HIPC(c, scatter32_own_variant<0>(c, false, G, lds, b, g.log_p1, cursor, x.cap1, (uint32_t *)c->xbuf.p, sp, NL, own));
+    return launch_scatter32(c, false, G, scatter32_lds(g.P1), b, g.log_p1, 0xFFFFFFFFu, cursor, x.cap1, (uint32_t *)c->xbuf.p, sp, nullptr, NL, &own);
+  }
+  int rc = scatter64_attrs(c, b, sp);
+  if (rc != SHK_OK) return rc;
+  const uint32_t G = std::min<uint32_t>(grid_for(b.tile_count, 1, g_cap), c->n_cus_scatter);
+  const size_t lds = scatter64_lds(g.P1);
+  // a batch inside one 1000-read block is one lane's; a tile list (k_build_tiles) may hold every lane's tiles
+  const uint32_t lane_lo = b.tiles ? 0u : b.lane0, lane_hi = b.tiles ? NL : b.lane0 + 1;
+  for (uint32_t lane = lane_lo; lane < lane_hi; ++lane) {
+    ScopedTimer t(c, SHK_K_SCATTER, /*chain=*/lane == lane_lo && c->chain_from_mark);
+    c->chain_from_mark = false;
+    HIPC(c, scatter64_variant<S64_OWNER>(c, false, G, lds, b, g.log_p1, lane, cursor, x.cap1, (uint64_t *)c->xbuf.p, sp, nullptr, own, NL));
   }
   return SHK_OK;
 }
@@ -1212,96 +1261,68 @@ static int launch_rescatter32(shk_ctx *c, uint32_t n_src_regions, const uint32_t
   return SHK_OK;
 }
 
-// Level-2 pass over ONE owner segment (this context's share: `regions` = [lane][super-page] regions of
-// `cap1` records each, fill levels in src_cursor) into the waiting (lane, page) regions.
-static int xl_absorb(shk_ctx *c, const PartGeom &g, const uint32_t *src_buf, const unsigned int *src_cursor, uint32_t cap1,
-                     uint32_t n_grp, SpillRef sp) {
-  const uint32_t NL = c->n_lanes, n_pages = g.n_pages;
-  const uint32_t log_p1w = g.log_p1 - g.lw;
-  if (n_grp != NL << log_p1w) return fail(c, SHK_ERR_BAD_ARG, "segment has %u regions, this context expects %u", n_grp, NL << log_p1w);
-  if (!c->acc_cur.p || c->acc_lp != g.lp || !c->acc_rec32 || c->acc_region_lanes != NL)
-    return fail(c, SHK_ERR_INVARIANT, "accumulation regions not planned for the owner layout");
-  const uint32_t r1_bits = 2 * c->cfg.k - g.log_p1;
-  ScopedTimer t(c, SHK_K_PSCAN, /*chain=*/true);
-  return launch_rescatter32(c, n_grp, src_buf, src_cursor, cap1, g.log_sub, r1_bits, (unsigned int *)c->acc_cur.p, c->acc_cap,
-                            (uint32_t *)c->acc_buf.p, 0u, sp, 0ull, (uint64_t)NL * n_pages, log_p1w, c->owner_id << log_p1w,
-                            (uint64_t)n_pages);
-}
+// Where a partition pass writes: `cursor`/`buf` are one lane's regions of `cap` records each, lane l's are
+// `lane_stride` regions further on (0: one set of regions, whatever the lane).
+struct PartDest {
+  unsigned int *cursor;
+  uint32_t cap;
+  void *buf;
+  uint64_t lane_stride;
+  unsigned int *cursor_of(uint32_t lane) const { return cursor + (size_t)lane * lane_stride; }
+  uint64_t *buf64_of(uint32_t lane) const { return (uint64_t *)buf + (size_t)lane * lane_stride * cap; }
+};
+// the accumulation regions: (lane, page), every lane's set after the other
+static PartDest acc_dest(const shk_ctx *c) { return PartDest{(unsigned int *)c->acc_cur.p, c->acc_cap, c->acc_buf.p, (uint64_t)1 << c->acc_lp}; }
 
-// One deferred counting launch on the owner-layout route: scatter (own records only), then absorb.
-static int xl_count(shk_ctx *c, const BatchRef &b, const PartGeom &g, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed) {
-  const XlPlan x = xl_plan(c, g, sub_kmers_ub, /*keep_all=*/false);
-  int rc = xl_scatter(c, b, g, x, sp, /*keep_all=*/false, prezeroed);
-  if (rc != SHK_OK) return rc;
-  return xl_absorb(c, g, (const uint32_t *)c->xbuf.p, (const unsigned int *)c->part_meta.p, x.cap1, x.n_grp, sp);
-}
-
-// ---- the owner layout with 8-byte records (k > 21: the mixed key's remainder does not fit a word) -------------------
-// The same segments — [owner][lane][super-page] regions of cap1 records, their fill levels beside them — with the
-// canonical k-mer as the record: k_scatter64 in its owner layout at the sender (a launch per chunk lane present in the
-// batch), k_part_rescatter at the receiver (a launch per lane of a segment) into the waiting (lane, page) regions that
-// k_pages counts.  The exchange rounds use it with every owner's records kept (a segment each), a share's own ingest
-// with its own records only (one segment: xl64_count).
-static bool xl64_feasible(const shk_ctx *c, const PartGeom &g) {
-  // (≤ 32 chunk lanes: a round's segments — lanes · 2^log_p1 regions of at least 1024 records — stay below the 4 GiB the scatter addresses)
-  return g.two_level && use_scatter64(c, g) && g.log_sub <= 10 && c->n_lanes <= 32 && g.lpg <= MAX_LOG_PAGES &&
-         env_int("SHK_DEFER", 1) != 0 && env_int("SHK_XL64", 1) != 0;
-}
-static int xl64_scatter(shk_ctx *c, const BatchRef &b, const PartGeom &g, const XlPlan &x, SpillRef sp, bool keep_all = true, bool prezeroed = true) {
-  const uint32_t NL = c->n_lanes;
-  const uint64_t total = (uint64_t)x.n_seg * x.seg_recs;
-  if (total * 8 > 0xFFFFFFFFull)
-    return fail(c, SHK_ERR_INVARIANT, "level-1 buffer of one launch exceeds 4 GiB (%llu 8-byte records)", (unsigned long long)total);
-  HIPC(c, c->xbuf.ensure(total * 8));
-  unsigned int *cursor = (unsigned int *)c->part_meta.p;
-  if (c->part_meta.cap < (size_t)x.n_seg * x.n_grp * 4) return fail(c, SHK_ERR_INVARIANT, "cursor buffer too small for the owner layout");
-  int rc = scatter64_attrs(c, b, sp);
-  if (rc != SHK_OK) return rc;
-  if (!prezeroed) HIPC(c, hipMemsetAsync(cursor, 0, (size_t)x.n_seg * x.n_grp * 4, c->stream));
-  OwnerCfg own{};
-  own.log_w = g.lw;
-  own.keep = keep_all ? 0xFFFFFFFFu : c->owner_id;
-  own.seg_recs = keep_all ? (uint32_t)x.seg_recs : 0u;
-  const uint32_t G = std::min<uint32_t>(grid_for(b.tile_count, 1, (uint32_t)env_int("SHK_PART_G", 512)), c->n_cus_scatter);
-  const size_t lds = scatter64_lds(g.P1);
-  // a batch inside one 1000-read block is one lane's; a tile list (k_build_tiles) may hold every lane's tiles
-  const uint32_t lane_lo = b.tiles ? 0u : b.lane0, lane_hi = b.tiles ? NL : b.lane0 + 1;
-  for (uint32_t lane = lane_lo; lane < lane_hi; ++lane) {
-    ScopedTimer t(c, SHK_K_SCATTER, /*chain=*/lane == lane_lo && c->chain_from_mark);
-    c->chain_from_mark = false;
-    HIPC(c, scatter64_variant<S64_OWNER>(c, false, G, lds, b, g.log_p1, lane, cursor, x.cap1, (uint64_t *)c->xbuf.p, sp, nullptr, own, NL));
-  }
+// k_part_rescatter on the context's stream: `n_src_regions` regions of cap1 8-byte records (fill levels in src_cursor)
+// by the next log_sub bits into `lane`'s regions of dst — or, LIST mode (ls.n > 0), a flat list of ls.n k-mers.
+static int launch_rescatter64(shk_ctx *c, uint32_t n_src_regions, const uint64_t *src_buf, const unsigned int *src_cursor, uint32_t cap1,
+                              uint32_t log_sub, const PartDest &dst, uint32_t lane, SpillRef sp, bool src_interleaved, const RescatterList &ls) {
+  const uint32_t S = 1u << log_sub;
+  const size_t lds = (size_t)RS_TILE * 8 + (((size_t)RS_TILE + S) * 2 + 15) / 16 * 16 + (size_t)S * 12;  // records + 16-bit entries + three words per page
+  const uint32_t tiles_per_region = (uint32_t)(((ls.n ? ls.n : cap1) + RS_TILE - 1) / RS_TILE);
+  hipLaunchKernelGGL(k_part_rescatter, dim3((ls.n ? 1u : n_src_regions) * tiles_per_region), dim3(RS_NT), lds, c->stream, src_buf, src_cursor,
+                     ls.n ? 0u : cap1, tiles_per_region, c->tb.log_pages, log_sub, 2 * c->cfg.k, dst.cursor_of(lane), dst.cap, dst.buf64_of(lane), lane,
+                     c->d_stats, sp, src_interleaved ? 1u : 0u, ls);
+  HIPC(c, hipGetLastError());
   return SHK_OK;
 }
-// Level-2 pass over ONE owner segment of 8-byte records into the waiting (lane, page) regions.
-static int xl64_absorb(shk_ctx *c, const PartGeom &g, const uint64_t *src_buf, const unsigned int *src_cursor, uint32_t cap1, uint32_t n_grp,
-                       SpillRef sp) {
+
+// Level-2 pass over ONE owner segment (this context's share: n_grp = [lane][super-page] regions of `cap1` records
+// of `rec_bytes` each, fill levels in src_cursor) into the waiting (lane, page) regions: one k_part_rescatter32
+// launch, or a k_part_rescatter launch per lane of the segment.
+static int xl_absorb(shk_ctx *c, uint32_t rec_bytes, const PartGeom &g, const void *src_buf, const unsigned int *src_cursor, uint32_t cap1,
+                     uint32_t n_grp, SpillRef sp) {
   const uint32_t NL = c->n_lanes, n_pages = g.n_pages;
   const uint32_t log_p1w = g.log_p1 - g.lw, S1w = 1u << log_p1w;
   if (n_grp != NL << log_p1w) return fail(c, SHK_ERR_BAD_ARG, "segment has %u regions, this context expects %u", n_grp, NL << log_p1w);
-  if (!c->acc_cur.p || c->acc_lp != g.lp || c->acc_rec32 || c->acc_region_lanes != NL)
-    return fail(c, SHK_ERR_INVARIANT, "accumulation regions not planned for 8-byte records");
-  const uint32_t S = 1u << g.log_sub, tiles_per_region = (cap1 + RS_TILE - 1) / RS_TILE;
-  const size_t lds_rs = (size_t)RS_TILE * 8 + (((size_t)RS_TILE + S) * 2 + 15) / 16 * 16 + (size_t)S * 12;
+  if (!c->acc_cur.p || c->acc_lp != g.lp || c->acc_rec32 != (rec_bytes == 4) || c->acc_region_lanes != NL)
+    return fail(c, SHK_ERR_INVARIANT, "accumulation regions not planned for the owner layout's %u-byte records", rec_bytes);
+  if (rec_bytes == 4) {
+    const uint32_t r1_bits = 2 * c->cfg.k - g.log_p1;
+    ScopedTimer t(c, SHK_K_PSCAN, /*chain=*/true);
+    return launch_rescatter32(c, n_grp, (const uint32_t *)src_buf, src_cursor, cap1, g.log_sub, r1_bits, (unsigned int *)c->acc_cur.p, c->acc_cap,
+                              (uint32_t *)c->acc_buf.p, 0u, sp, 0ull, (uint64_t)NL * n_pages, log_p1w, c->owner_id << log_p1w,
+                              (uint64_t)n_pages);
+  }
   RescatterList ls{};  // (not a list: the owner bits of a k-mer's page are this share's, the rest is the page)
   ls.owner_bits = g.lw;
   ls.owner_id = c->tb.owner_id;
   for (uint32_t lane = 0; lane < NL; ++lane) {
     ScopedTimer t(c, SHK_K_PSCAN, /*chain=*/true);
-    hipLaunchKernelGGL(k_part_rescatter, dim3(S1w * tiles_per_region), dim3(RS_NT), lds_rs, c->stream, src_buf + (size_t)lane * S1w * cap1,
-                       src_cursor + (size_t)lane * S1w, cap1, tiles_per_region, g.lp, g.log_sub, 2 * c->cfg.k,
-                       (unsigned int *)c->acc_cur.p + (size_t)lane * n_pages, c->acc_cap,
-                       (uint64_t *)c->acc_buf.p + (size_t)lane * n_pages * c->acc_cap, lane, c->d_stats, sp, 0u, ls);
+    int rc = launch_rescatter64(c, S1w, (const uint64_t *)src_buf + (size_t)lane * S1w * cap1, src_cursor + (size_t)lane * S1w, cap1, g.log_sub,
+                                acc_dest(c), lane, sp, false, ls);
+    if (rc != SHK_OK) return rc;
   }
-  HIPC(c, hipGetLastError());
   return SHK_OK;
 }
-// One deferred counting launch of a share's OWN ingest at k > 21: scatter (own records only, one segment), then absorb.
-static int xl64_count(shk_ctx *c, const BatchRef &b, const PartGeom &g, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed) {
+
+// One deferred counting launch on the owner-layout route: scatter (own records only, one segment), then absorb.
+static int xl_count(shk_ctx *c, uint32_t rec_bytes, const BatchRef &b, const PartGeom &g, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed) {
   const XlPlan x = xl_plan(c, g, sub_kmers_ub, /*keep_all=*/false);
-  int rc = xl64_scatter(c, b, g, x, sp, /*keep_all=*/false, prezeroed);
+  int rc = xl_scatter(c, rec_bytes, b, g, x, sp, /*keep_all=*/false, prezeroed);
   if (rc != SHK_OK) return rc;
-  return xl64_absorb(c, g, (const uint64_t *)c->xbuf.p, (const unsigned int *)c->part_meta.p, x.cap1, x.n_grp, sp);
+  return xl_absorb(c, rec_bytes, g, c->xbuf.p, (const unsigned int *)c->part_meta.p, x.cap1, x.n_grp, sp);
 }
 // the record of an exchange segment at this geometry: 4 bytes (the 4-byte owner layout), 8 (the one above), 0: neither
 static uint32_t xchg_rec_bytes(const shk_ctx *c, const PartGeom &g) {
@@ -1342,7 +1363,7 @@ static int xchg_prepare_cursors(shk_ctx *c, uint32_t *n_words) {
   const PartGeom g = part_geom(c);
   int rc = xchg_check(c, g);
   if (rc != SHK_OK) return rc;
-  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, true)));
+  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, paged_route(c, g, /*multi=*/true, /*defer=*/true))));
   *n_words = c->n_lanes * g.P1;  // every segment's cursors
   return SHK_OK;
 }
@@ -1353,11 +1374,7 @@ static SpillRef xspill_ref(shk_ctx *c) {
 }
 // What an exchange scatter left in the statistics (h_stats read back behind it).
 static int xchg_scatter_outcome(shk_ctx *c, uint64_t *n_foreign) {
-  if (c->h_stats->bad != ~0ull) {
-    c->poisoned = true;
-    c->poison_code = SHK_ERR_INVALID_CHAR;
-    return fail(c, SHK_ERR_INVALID_CHAR, "Invalid character '%s' in sequence. Only ACGTN allowed.", shk::byte_as_char((uint8_t)(c->h_stats->bad & 0xFF)).c_str());
-  }
+  if (c->h_stats->bad != ~0ull) return fail_invalid_char(c, c->h_stats->bad);
   if (c->h_stats->scratch[0] > c->xspill_cap) return fail(c, SHK_ERR_INVARIANT, "foreign spill list overflow");
   *n_foreign = c->h_stats->scratch[0];
   return SHK_OK;
@@ -1390,11 +1407,11 @@ static int xchg_scatter_launch(shk_ctx *c, const BatchRef &b, uint64_t kmers_ub,
   }
   const uint32_t rec_bytes = xchg_rec_bytes(c, g);
   if (kmers_ub) {
-    rc = rec_bytes == 8 ? xl64_scatter(c, b, g, x, xspill_ref(c)) : xl_scatter(c, b, g, x, xspill_ref(c), /*keep_all=*/true, /*prezeroed=*/true);
+    rc = xl_scatter(c, rec_bytes, b, g, x, xspill_ref(c), /*keep_all=*/true, /*prezeroed=*/true);
     if (rc != SHK_OK) return rc;
   } else {  // an empty batch still takes part in the round: all-zero cursors
     HIPC(c, c->xbuf.ensure((uint64_t)x.n_seg * x.seg_recs * rec_bytes));
-    HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, true)));
+    HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, g, paged_route(c, g, /*multi=*/true, /*defer=*/true))));
     HIPC(c, hipMemsetAsync(c->part_meta.p, 0, (size_t)x.n_seg * x.n_grp * 4, c->stream));
   }
   xo->d_records = c->xbuf.p;
@@ -1443,11 +1460,7 @@ static int xw_scatter_launch(shk_ctx *c, const BatchRef &b, uint64_t kmers_ub, X
   HIPC(c, hipMemcpyAsync(h_cnt, d_cnt, (size_t)W * 8, hipMemcpyDeviceToHost, c->stream));
   int rc = read_stats(c);  // (synchronises)
   if (rc != SHK_OK) return rc;
-  if (c->h_stats->bad != ~0ull) {
-    c->poisoned = true;
-    c->poison_code = SHK_ERR_INVALID_CHAR;
-    return fail(c, SHK_ERR_INVALID_CHAR, "Invalid character '%s' in sequence. Only ACGTN allowed.", shk::byte_as_char((uint8_t)(c->h_stats->bad & 0xFF)).c_str());
-  }
+  if (c->h_stats->bad != ~0ull) return fail_invalid_char(c, c->h_stats->bad);
   unsigned long long base[64], at = 0;
   for (uint32_t o = 0; o < W; ++o) {
     base[o] = at;
@@ -1491,133 +1504,141 @@ static int fused_hist_prepare(shk_ctx *c, uint32_t n_pages, FusedHist *fh) {
   return SHK_OK;
 }
 
-static int xl64_count(shk_ctx *c, const BatchRef &b, const PartGeom &g, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed);
+// k_part_scatter_sorted on the context's stream, either record width.
+static void launch_scatter_sorted(shk_ctx *c, bool rec32, uint32_t G, const BatchRef &b, uint32_t log_p1, uint32_t lane, unsigned int *cursor,
+                                  uint32_t cap, void *buf, SpillRef sp, unsigned long long *dbg) {
+  const uint32_t P1 = 1u << log_p1;
+  const size_t lds = (size_t)sort_region_bytes(P1) + (size_t)PACK_WORDS * 8 + (size_t)P1 * 12 + 32;  // (+ the walk's 8 spare counters when P1 < 8)
+  if (rec32)
+    hipLaunchKernelGGL((k_part_scatter_sorted<SC_NT, true>), dim3(G), dim3(SC_NT), lds, c->stream, b, log_p1, lane, cursor, cap, buf, c->d_stats,
+                       c->d_lane_bases, sp, dbg);
+  else
+    hipLaunchKernelGGL((k_part_scatter_sorted<SC_NT, false>), dim3(G), dim3(SC_NT), lds, c->stream, b, log_p1, lane, cursor, cap, buf, c->d_stats,
+                       c->d_lane_bases, sp, dbg);
+}
+
+// k_pages32 on the context's stream: `n_blocks` pages from page0 on, chunk lanes [l_lo, l_hi) of each.  fresh: the
+// table's first pass, which writes every page whole; fuse: it leaves the histogram behind (fresh passes only) — over
+// a lane loop (HIST = 1) or, the launch covering ONE lane, without the loop's running sums (HIST = 2).
+static void launch_pages32(shk_ctx *c, bool fresh, bool fuse, uint32_t n_blocks, uint32_t page0, uint32_t l_lo, uint32_t l_hi, uint32_t lane_stride,
+                           uint32_t n_regions, const unsigned int *cursor, uint32_t cap, const uint32_t *buf, SpillRef sp, const FusedHist &fh) {
+#define SHK_PG(F, H)                                                                                                                       \
+  hipLaunchKernelGGL((k_pages32<F, H>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, n_regions, cursor, cap, \
+                     buf, c->d_stats, sp, page0, fh)
+  if (!fresh)
+    SHK_PG(false, 0);
+  else if (!fuse)
+    SHK_PG(true, 0);
+  else if (l_hi - l_lo == 1)
+    SHK_PG(true, 2);
+  else
+    SHK_PG(true, 1);
+#undef SHK_PG
+}
+// k_pages (8-byte records) on the context's stream.  fresh: the table's first page pass — nothing is read, keys and
+// counts are written whole (k_pages<true, true>).
+static void launch_pages64(shk_ctx *c, bool fresh, uint32_t n_blocks, uint32_t page0, uint32_t l_lo, uint32_t l_hi, uint32_t lane_stride,
+                           const unsigned int *cursor, uint32_t cap, const uint64_t *buf, SpillRef sp) {
+  if (fresh)
+    hipLaunchKernelGGL((k_pages<true, true>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, cursor, cap, buf,
+                       (uint64_t *)c->part2.p, c->d_stats, sp, page0);
+  else
+    hipLaunchKernelGGL((k_pages<false, false>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, cursor, cap, buf,
+                       (uint64_t *)c->part2.p, c->d_stats, sp, page0);
+}
+
 static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed, bool defer) {
   const PartGeom pg = part_geom(c);
-  if (xl_route(c, pg, b.tiles != nullptr, defer)) return xl_count(c, b, pg, sub_kmers_ub, sp, prezeroed);
-  if (defer && xl64_route(c, pg)) return xl64_count(c, b, pg, sub_kmers_ub, sp, prezeroed);
+  const bool multi = b.tiles != nullptr;
+  const PagedRoute r = paged_route(c, pg, multi, defer);
+  if (r.owner != XL_NONE) return xl_count(c, r.rec_bytes, b, pg, sub_kmers_ub, sp, prezeroed);
   if (pg.lw) return fail(c, SHK_ERR_INVARIANT, "an owner share has no paged path besides the owner layout");
   const uint32_t lp = pg.lp, n_pages = pg.n_pages, log_p1 = pg.log_p1, log_sub = pg.log_sub, P1 = pg.P1;
-  const bool two_level = pg.two_level;
+  const bool two_level = r.two_level, rec32 = r.rec_bytes == 4;
   const uint32_t g_cap = (uint32_t)env_int("SHK_PART_G", 512);
   const uint32_t G = grid_for(b.tile_count, 1, g_cap);
   if (two_level && (1u << log_sub) > (uint32_t)MAX_PARTS)
     return fail(c, SHK_ERR_BAD_ARG, "table too large for the two-level partition");
+  if (defer && rec32 && r.scatter != SCATTER_32)  // (count_path defers 4-byte records only with k_scatter32: it alone fills (lane, page) regions in one pass)
+    return fail(c, SHK_ERR_INVARIANT, "deferred 4-byte records without the records-in-LDS scatter");
+  if (defer && (c->acc_lp != lp || !c->acc_cur.p)) return fail(c, SHK_ERR_INVARIANT, "accumulation regions not planned");
+  if (defer && rec32 != c->acc_rec32) return fail(c, SHK_ERR_INVARIANT, "accumulation regions planned for the other record size");
   // Every region is filled by per-tile reservations (one returning atomic per non-empty
   // (tile, region)); a region that still overflows (skewed input: one k-mer making up a large
   // share of the batch) sends the excess through the spill list — exact either way.
   const uint32_t r1_bits = 2 * c->cfg.k >= log_p1 ? 2 * c->cfg.k - log_p1 : 0;
-  const bool rec32 = use_rec32(c, pg);
-  const bool multi = b.tiles != nullptr;
-  bool all_lanes = use_all_lanes(c, pg, multi) && !defer;  // (deferred: always (lane, page) regions, see below)
   const uint32_t NL = c->n_lanes;
-  // per-lane share of the batch's k-mers in ALL-LANES mode: blocks go round the lanes, so a lane
-  // holds at most ceil(blocks / lanes) of them; half as much again for uneven read lengths
-  // (what still overflows a region takes the spill path)
-  uint64_t lane_kmers_ub = sub_kmers_ub;
-  if (all_lanes) {
-    const uint64_t nb = std::max<uint64_t>(c->cur_blocks, 1);
-    const uint64_t per_lane_blocks = (nb + NL - 1) / NL;
-    lane_kmers_ub = std::min<uint64_t>(sub_kmers_ub, sub_kmers_ub / nb * per_lane_blocks * 3 / 2 + 2 * TILE_T);
-  }
-  // (4-byte-record regions are block-interleaved, rec_slot: whole blocks of 2^RB_LOG records)
+
+  // What depends on the batch's size: the regions' capacities, and whether ALL-LANES mode fits 32-bit offsets.
+  // (4-byte-record regions are block-interleaved, rec_slot: whole blocks of 2^RB_LOG records; the level-1 regions of
+  // k_scatter64 are interleaved in blocks of RS_TILE records: whole blocks)
   const uint64_t pads = rec32 ? 0 : b.tile_count;  // (only 8-B record runs are padded, once per (tile, region) at most)
-  // (the level-1 regions of k_scatter64 are interleaved in blocks of RS_TILE records: whole blocks)
-  const bool il64 = !rec32 && two_level && use_scatter64(c, pg) && env_int("SHK_S64_INTERLEAVE", 1) != 0;
-  const uint32_t cap1_unit = il64 ? (uint32_t)RS_TILE : 1u << RB_LOG;
-  uint32_t cap1 = (region_cap(lane_kmers_ub, P1, pads) + cap1_unit - 1u) & ~(cap1_unit - 1u);
+  const uint32_t cap1_unit = r.scatter == SCATTER_64_INTERLEAVED ? (uint32_t)RS_TILE : 1u << RB_LOG;
+  bool all_lanes = r.all_lanes, one_pass = r.one_pass;
+  uint32_t n_cursor_words = r.cursor_words;
+  uint32_t cap1 = (region_cap(all_lanes ? striped_lane_ub(c, sub_kmers_ub) : sub_kmers_ub, P1, pads) + cap1_unit - 1u) & ~(cap1_unit - 1u);
   if (all_lanes && (uint64_t)NL * P1 * cap1 * 4 > 0xFFFFFFFFull) {  // 32-bit byte offsets: fall back to a pass per lane
-    all_lanes = false;
-    cap1 = (region_cap(sub_kmers_ub, P1, pads) + (1u << RB_LOG) - 1u) & ~((1u << RB_LOG) - 1u);
+    all_lanes = one_pass = false;
+    n_cursor_words = P1;
+    cap1 = (region_cap(sub_kmers_ub, P1, pads) + cap1_unit - 1u) & ~(cap1_unit - 1u);
   }
+  if (n_cursor_words > r.cursor_words)  // (k_mark_starts cleared the route's words, and no more, for a prezeroed launch)
+    return fail(c, SHK_ERR_INVARIANT, "a paged launch wants %u cursor words, its route has %u", n_cursor_words, r.cursor_words);
   const uint32_t region_lanes = all_lanes ? NL : 1;
   const uint32_t rs_tile = rec32 ? rs32_tile(log_sub) : (uint32_t)RS_TILE;
   const uint32_t tiles_per_region = (cap1 + rs_tile - 1) / rs_tile;
   const uint32_t cap_pg =
       two_level ? (region_cap(sub_kmers_ub, n_pages, rec32 ? 0 : tiles_per_region) + (1u << RB_LOG) - 1u) & ~((1u << RB_LOG) - 1u) : cap1;
-  DevBuf &buf_pg = defer ? c->acc_buf : (two_level ? c->part3 : c->part);  // what k_pages reads
-  if (defer && (c->acc_lp != lp || !c->acc_cur.p)) return fail(c, SHK_ERR_INVARIANT, "accumulation regions not planned");
-  if (!(defer && !two_level) && (uint64_t)region_lanes * P1 * cap1 * (rec32 ? 4 : 8) > 0xFFFFFFFFull)  // 32-bit byte offsets in the scatter
-    return fail(c, SHK_ERR_INVARIANT, "partition buffer of one launch exceeds 4 GiB");
-  if (!(defer && !two_level)) HIPC(c, c->part.ensure((uint64_t)region_lanes * P1 * cap1 * (rec32 ? 4 : 8)));
-  if (two_level && !defer) HIPC(c, c->part3.ensure((uint64_t)n_pages * cap_pg * (rec32 ? 4 : 8)));
+
+  const bool to_acc1 = defer && !two_level;  // level 1 fills the waiting page regions itself
+  if (!to_acc1) {
+    if ((uint64_t)region_lanes * P1 * cap1 * r.rec_bytes > 0xFFFFFFFFull)  // 32-bit byte offsets in the scatter
+      return fail(c, SHK_ERR_INVARIANT, "partition buffer of one launch exceeds 4 GiB");
+    HIPC(c, c->part.ensure((uint64_t)region_lanes * P1 * cap1 * r.rec_bytes));
+  }
+  if (two_level && !defer) HIPC(c, c->part3.ensure((uint64_t)n_pages * cap_pg * r.rec_bytes));
   if (!rec32 && !defer)
     HIPC(c, c->part2.ensure((uint64_t)n_pages * std::min<uint64_t>((uint64_t)cap_pg + MISS_SLACK, MISS_PAGE_MAX) * 8));  // k_pages miss queues
-  if (defer && rec32 != c->acc_rec32) return fail(c, SHK_ERR_INVARIANT, "accumulation regions planned for the other record size");
-  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, pg, multi)));
+  HIPC(c, c->part_meta.ensure(cursor_buf_bytes(c, pg, r)));
   unsigned int *cursor1 = (unsigned int *)c->part_meta.p;
-  unsigned int *cursor_pg = two_level ? cursor1 + P1 : cursor1;
+  // Where level 1 writes: the per-launch buffer `part` ((lane, page) regions in ALL-LANES mode) — or, a deferred
+  // one-level pass, straight into the accumulation regions.  Where the page regions are — what level 2 writes and
+  // k_pages reads: the accumulation regions (deferred), `part3` behind the level-1 cursors, or level 1's own.
+  const PartDest d1 = to_acc1 ? acc_dest(c) : PartDest{cursor1, cap1, c->part.p, all_lanes ? (uint64_t)P1 : 0ull};
+  const PartDest dpg = defer ? acc_dest(c) : two_level ? PartDest{cursor1 + P1, cap_pg, c->part3.p, 0ull} : d1;
+  const bool wide1 = to_acc1 && (uint64_t)NL * n_pages * c->acc_cap * 4 > 0xFFFFFFFFull;  // 64-bit offsets into the accumulation buffer
   unsigned long long *dbg = nullptr;
 #ifdef SHK_PHASE_TIMING
   HIPC(c, c->misc.ensure((size_t)G * 64));
   dbg = (unsigned long long *)c->misc.p;
 #endif
-  const size_t lds_sorted = (size_t)sort_region_bytes(P1) + (size_t)PACK_WORDS * 8 + (size_t)P1 * 12 + 32;  // (+ the walk's 8 spare counters when P1 < 8)
-  const uint32_t S = 1u << log_sub;
-  const size_t lds_rs = (size_t)RS_TILE * 8 + (((size_t)RS_TILE + S) * 2 + 15) / 16 * 16 + (size_t)S * 12;
-  const size_t lds_s32 = scatter32_lds(P1);
-  const bool lds32 = use_scatter32(c, pg);
   const uint32_t lane_lo = multi ? 0 : b.lane0, lane_hi = multi ? c->n_lanes : b.lane0 + 1;
-  // deferred: page regions and cursors are the accumulation ones and persist; only a level-1 pass
-  // has cursors of its own
-  const size_t n_cursor_words = defer ? (two_level ? P1 : 0) : (size_t)region_lanes * P1 + (two_level ? n_pages : 0);
-  const bool one_pass = all_lanes || (defer && !two_level && rec32);  // every lane's tiles in a single scatter launch
-  const uint32_t acc_wide = (uint64_t)NL * n_pages * c->acc_cap * 4 > 0xFFFFFFFFull;
-  // one pass per chunk lane — or a single pass for all of them (`lane` = ~0 below)
+  // one pass per chunk lane — or a single pass for all of them
   for (uint32_t lane = lane_lo; lane < (one_pass ? lane_lo + 1 : lane_hi); ++lane) {
     if (n_cursor_words && !(prezeroed && lane == lane_lo))  // the first pass's cursors were cleared by k_mark_starts
-      HIPC(c, hipMemsetAsync(cursor1, 0, n_cursor_words * 4, c->stream));
+      HIPC(c, hipMemsetAsync(cursor1, 0, (size_t)n_cursor_words * 4, c->stream));
     {
       ScopedTimer t(c, SHK_K_SCATTER, /*chain=*/prezeroed && lane == lane_lo && c->chain_from_mark);
       c->chain_from_mark = false;
-      if (rec32 && lds32) {
-        int rcl;
-        if (defer && !two_level)  // straight into the accumulation regions, (lane, page) layout
-          rcl = launch_scatter32(c, acc_wide != 0, std::min<uint32_t>(G, c->n_cus_scatter * SHK_SC32_WGS), lds_s32, b, log_p1, 0xFFFFFFFFu,
-                                 (unsigned int *)c->acc_cur.p, c->acc_cap, (uint32_t *)c->acc_buf.p, sp, dbg, NL);
-        else
-          rcl = launch_scatter32(c, false, std::min<uint32_t>(G, c->n_cus_scatter * SHK_SC32_WGS), lds_s32, b, log_p1,
-                                 all_lanes ? 0xFFFFFFFFu : lane, cursor1, cap1, (uint32_t *)c->part.p, sp, dbg, NL);
-        if (rcl != SHK_OK) return rcl;
-      } else if (rec32)
-        hipLaunchKernelGGL((k_part_scatter_sorted<SC_NT, true>), dim3(G), dim3(SC_NT), lds_sorted, c->stream,
-                           b, log_p1, lane, cursor1, cap1, c->part.p, c->d_stats, c->d_lane_bases, sp, dbg);
-      else if (use_scatter64(c, pg)) {  // 8-byte records, k_scatter32's machine (deferred one-level: straight into this lane's accumulation regions)
-        const bool acc1 = defer && !two_level;
-        int rcl = launch_scatter64(c, std::min<uint32_t>(G, c->n_cus_scatter), b, log_p1, lane, acc1 ? (unsigned int *)c->acc_cur.p + (size_t)lane * n_pages : cursor1,
-                                   acc1 ? c->acc_cap : cap1, acc1 ? (uint64_t *)c->acc_buf.p + (size_t)lane * n_pages * c->acc_cap : (uint64_t *)c->part.p, sp, dbg,
-                                   il64);
-        if (rcl != SHK_OK) return rcl;
-      } else if (defer && !two_level)  // straight into this lane's accumulation regions (8-byte records)
-        hipLaunchKernelGGL((k_part_scatter_sorted<SC_NT, false>), dim3(G), dim3(SC_NT), lds_sorted, c->stream,
-                           b, log_p1, lane, (unsigned int *)c->acc_cur.p + (size_t)lane * n_pages, c->acc_cap,
-                           (void *)((uint64_t *)c->acc_buf.p + (size_t)lane * n_pages * c->acc_cap), c->d_stats,
-                           c->d_lane_bases, sp, dbg);
-      else
-        hipLaunchKernelGGL((k_part_scatter_sorted<SC_NT, false>), dim3(G), dim3(SC_NT), lds_sorted, c->stream,
-                           b, log_p1, lane, cursor1, cap1, c->part.p, c->d_stats, c->d_lane_bases, sp, dbg);
+      int rcl = SHK_OK;
+      if (r.scatter == SCATTER_32)
+        rcl = launch_scatter32(c, wide1, std::min<uint32_t>(G, c->n_cus_scatter * SHK_SC32_WGS), scatter32_lds(P1), b, log_p1,
+                               one_pass ? 0xFFFFFFFFu : lane, d1.cursor, d1.cap, (uint32_t *)d1.buf, sp, dbg, NL);
+      else if (r.scatter == SCATTER_SORTED)
+        launch_scatter_sorted(c, rec32, G, b, log_p1, lane, d1.cursor_of(lane), d1.cap, rec32 ? d1.buf : d1.buf64_of(lane), sp, dbg);
+      else  // 8-byte records, k_scatter32's machine
+        rcl = launch_scatter64(c, std::min<uint32_t>(G, c->n_cus_scatter), b, log_p1, lane, d1.cursor_of(lane), d1.cap, d1.buf64_of(lane), sp, dbg,
+                               r.scatter == SCATTER_64_INTERLEAVED);
+      if (rcl != SHK_OK) return rcl;
     }
     if (two_level) {
       ScopedTimer t(c, SHK_K_PSCAN, /*chain=*/true);  // timer slot reused: the level-2 re-scatter
-      if (rec32 && defer) {  // append to this lane's accumulation regions
-        int rcl = launch_rescatter32(c, P1, (const uint32_t *)c->part.p, (const unsigned int *)cursor1, cap1, log_sub, r1_bits,
-                                     (unsigned int *)c->acc_cur.p, c->acc_cap, (uint32_t *)c->acc_buf.p, lane, sp, (uint64_t)lane * n_pages,
-                                     (uint64_t)NL * n_pages, 31u, 0u, 0ull);
-        if (rcl != SHK_OK) return rcl;
-      } else if (rec32) {
-        int rcl = launch_rescatter32(c, P1, (const uint32_t *)c->part.p, (const unsigned int *)cursor1, cap1, log_sub, r1_bits, cursor_pg,
-                                     cap_pg, (uint32_t *)buf_pg.p, lane, sp, 0ull, (uint64_t)n_pages, 31u, 0u, 0ull);
-        if (rcl != SHK_OK) return rcl;
-      }
-      else if (defer)  // append to this lane's accumulation regions (8-byte records)
-        hipLaunchKernelGGL(k_part_rescatter, dim3(P1 * tiles_per_region), dim3(RS_NT), lds_rs, c->stream,
-                           (const uint64_t *)c->part.p, (const unsigned int *)cursor1, cap1, tiles_per_region, lp,
-                           log_sub, 2 * c->cfg.k, (unsigned int *)c->acc_cur.p + (size_t)lane * n_pages, c->acc_cap,
-                           (uint64_t *)c->acc_buf.p + (size_t)lane * n_pages * c->acc_cap, lane, c->d_stats, sp, il64 ? 1u : 0u);
-      else
-        hipLaunchKernelGGL(k_part_rescatter, dim3(P1 * tiles_per_region), dim3(RS_NT), lds_rs, c->stream,
-                           (const uint64_t *)c->part.p, (const unsigned int *)cursor1, cap1, tiles_per_region, lp,
-                           log_sub, 2 * c->cfg.k, cursor_pg, cap_pg, (uint64_t *)buf_pg.p, lane, c->d_stats, sp, il64 ? 1u : 0u);
+      const int rcl = rec32 ? launch_rescatter32(c, P1, (const uint32_t *)d1.buf, d1.cursor, cap1, log_sub, r1_bits, dpg.cursor, dpg.cap,
+                                                 (uint32_t *)dpg.buf, lane, sp, lane * dpg.lane_stride,
+                                                 dpg.lane_stride ? (uint64_t)NL * n_pages : (uint64_t)n_pages, 31u, 0u, 0ull)
+                            : launch_rescatter64(c, P1, (const uint64_t *)d1.buf, d1.cursor, cap1, log_sub, dpg, lane, sp,
+                                                 r.scatter == SCATTER_64_INTERLEAVED, RescatterList{});
+      if (rcl != SHK_OK) return rcl;
     }
     if (!defer) {
       const uint32_t l_lo = all_lanes ? 0u : lane, l_hi = all_lanes ? NL : lane + 1;
@@ -1633,30 +1654,16 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
         if (rch != SHK_OK) return rch;
       }
       ScopedTimer t(c, SHK_K_PAGES, /*chain=*/true);
-      if (rec32 && fresh) {
-        if (fuse && l_hi - l_lo == 1)
-          hipLaunchKernelGGL((k_pages32<true, 2>), dim3(n_pages), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi,
-                             all_lanes ? n_pages : 0u, (uint32_t)region_lanes * n_pages,
-                             (const unsigned int *)cursor_pg, cap_pg, (const uint32_t *)buf_pg.p, c->d_stats, sp, 0u, fh);
-        else if (fuse)
-          hipLaunchKernelGGL((k_pages32<true, 1>), dim3(n_pages), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi,
-                             all_lanes ? n_pages : 0u, (uint32_t)region_lanes * n_pages,
-                             (const unsigned int *)cursor_pg, cap_pg, (const uint32_t *)buf_pg.p, c->d_stats, sp, 0u, fh);
-        else
-          hipLaunchKernelGGL((k_pages32<true, 0>), dim3(n_pages), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi,
-                             all_lanes ? n_pages : 0u, (uint32_t)region_lanes * n_pages,
-                             (const unsigned int *)cursor_pg, cap_pg, (const uint32_t *)buf_pg.p, c->d_stats, sp, 0u, fh);
-        c->tb_stale = false;
-        c->fused_valid = fuse;
-        c->fused_pages = n_pages;
-      } else if (rec32)
-        hipLaunchKernelGGL((k_pages32<false, 0>), dim3(n_pages), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi,
-                           all_lanes ? n_pages : 0u, (uint32_t)region_lanes * n_pages,
-                           (const unsigned int *)cursor_pg, cap_pg, (const uint32_t *)buf_pg.p, c->d_stats, sp);
-      else
-        hipLaunchKernelGGL((k_pages<false, false>), dim3(n_pages), dim3(PG_WG), 0, c->stream, c->tb, lane, lane + 1, 0u,
-                           (const unsigned int *)cursor_pg, cap_pg, (const uint64_t *)buf_pg.p,
-                           (uint64_t *)c->part2.p, c->d_stats, sp);
+      if (rec32) {
+        launch_pages32(c, fresh, fuse, n_pages, 0u, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cursor, dpg.cap,
+                       (const uint32_t *)dpg.buf, sp, fh);
+        if (fresh) {
+          c->tb_stale = false;
+          c->fused_valid = fuse;
+          c->fused_pages = n_pages;
+        }
+      } else
+        launch_pages64(c, false, n_pages, 0u, lane, lane + 1, 0u, dpg.cursor, dpg.cap, (const uint64_t *)dpg.buf, sp);
     }
 #ifdef SHK_PHASE_TIMING
     {
@@ -1748,13 +1755,7 @@ static void own_resolve(shk_ctx *c) {
 
 static int settle_checked(shk_ctx *c) {
   c->unsettled = false;
-  if (c->h_stats->bad != ~0ull) {
-    // identical text to encoding.rs:353-356
-    c->poisoned = true;
-    c->poison_code = SHK_ERR_INVALID_CHAR;
-    return fail(c, SHK_ERR_INVALID_CHAR, "Invalid character '%s' in sequence. Only ACGTN allowed.",
-                shk::byte_as_char((uint8_t)(c->h_stats->bad & 0xFF)).c_str());
-  }
+  if (c->h_stats->bad != ~0ull) return fail_invalid_char(c, c->h_stats->bad);
   int rc = drain_spill(c, c->unsettled_spill_cap);
   if (rc != SHK_OK) return rc;
   if (!c->held_keys.empty() && !c->acc_active) {  // what a grouped flush took off the device goes back in now
@@ -1872,39 +1873,15 @@ static int flush_acc(shk_ctx *c) {
   }
   for (uint64_t p0 = 0; p0 < n_pages; p0 += ppg) {
     const uint32_t gp = (uint32_t)std::min<uint64_t>(ppg, n_pages - p0);
-    if (c->acc_rec32) {
-      ScopedTimer t(c, SHK_K_PAGES);
-      if (fresh && fuse && NL == 1)
-        hipLaunchKernelGGL((k_pages32<true, 2>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, 0u,
-                           NL * n_pages, (const unsigned int *)c->acc_cur.p, c->acc_cap, (const uint32_t *)c->acc_buf.p,
-                           c->d_stats, sp, (uint32_t)p0, fh);
-      else if (fresh && fuse)
-        hipLaunchKernelGGL((k_pages32<true, 1>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, NL > 1 ? n_pages : 0u,
-                           NL * n_pages, (const unsigned int *)c->acc_cur.p, c->acc_cap, (const uint32_t *)c->acc_buf.p,
-                           c->d_stats, sp, (uint32_t)p0, fh);
-      else if (fresh)
-        hipLaunchKernelGGL((k_pages32<true, 0>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, NL > 1 ? n_pages : 0u,
-                           NL * n_pages, (const unsigned int *)c->acc_cur.p, c->acc_cap, (const uint32_t *)c->acc_buf.p,
-                           c->d_stats, sp, (uint32_t)p0, fh);
-      else
-        hipLaunchKernelGGL((k_pages32<false, 0>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, NL > 1 ? n_pages : 0u,
-                           NL * n_pages, (const unsigned int *)c->acc_cur.p, c->acc_cap, (const uint32_t *)c->acc_buf.p,
-                           c->d_stats, sp, (uint32_t)p0);
-    } else {  // 8-byte records: every lane's regions of a page in one launch (the keys stay in LDS over the lanes)
+    {  // every lane's regions of a page in one launch (the keys stay in LDS over the lanes), either record width
       ScopedTimer t(c, SHK_K_PAGES);
       const unsigned int *cur = (const unsigned int *)c->acc_cur.p;
-      const uint64_t *buf = (const uint64_t *)c->acc_buf.p;
-      if (fresh8)  // the table's first page pass: nothing is read, keys and counts are written whole
-        hipLaunchKernelGGL((k_pages<true, true>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, n_pages, cur, c->acc_cap, buf, (uint64_t *)c->part2.p, c->d_stats, sp, (uint32_t)p0);
+      if (c->acc_rec32)
+        launch_pages32(c, fresh, fuse, gp, (uint32_t)p0, 0u, NL, NL > 1 ? n_pages : 0u, NL * n_pages, cur, c->acc_cap, (const uint32_t *)c->acc_buf.p, sp, fh);
       else
-        hipLaunchKernelGGL((k_pages<false, false>), dim3(gp), dim3(PG_WG), 0, c->stream, c->tb, 0u, NL, n_pages, cur, c->acc_cap, buf, (uint64_t *)c->part2.p, c->d_stats, sp, (uint32_t)p0);
-      if (grouped) {
-        int rc = read_stats(c);
-        if (rc == SHK_OK) rc = hold_spills(c, spill_cap);
-        if (rc != SHK_OK) return rc;
-      }
+        launch_pages64(c, fresh8, gp, (uint32_t)p0, 0u, NL, n_pages, cur, c->acc_cap, (const uint64_t *)c->acc_buf.p, sp);
     }
-    if (grouped && c->acc_rec32) {
+    if (grouped) {
       int rc = read_stats(c);
       if (rc == SHK_OK) rc = hold_spills(c, spill_cap);
       if (rc != SHK_OK) return rc;
@@ -2585,11 +2562,11 @@ int shk_pack_reads_device(shk_ctx *c, const void *d_bases, uint64_t n_bases, voi
   int rc = read_stats(c);
   if (rc != SHK_OK) return rc;
   if (c->h_stats->bad != ~0ull) {  // encoding.rs:353-356; the context's table was not touched: no poisoning
-    const std::string bad = shk::byte_as_char((uint8_t)(c->h_stats->bad & 0xFF));
+    const uint64_t bad = c->h_stats->bad;
     HIPC(c, hipMemsetAsync(&c->d_stats->bad, 0xFF, 8, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     c->h_stats->bad = ~0ull;
-    return fail(c, SHK_ERR_INVALID_CHAR, "Invalid character '%s' in sequence. Only ACGTN allowed.", bad.c_str());
+    return fail_invalid_char(c, bad, /*poison=*/false);
   }
   return SHK_OK;
 }
@@ -2831,8 +2808,7 @@ int shk_xchg_absorb(shk_ctx *c, const void *d_records, const void *d_cursors, co
     HIPC(c, c->spillA.ensure(spill_cap * 16));
   }
   SpillRef sp = spill_ref(c->spillA, spill_cap);
-  rc = rec8 ? xl64_absorb(c, g, (const uint64_t *)d_records, (const unsigned int *)d_cursors, lay->region_cap, lay->regions, sp)
-            : xl_absorb(c, g, (const uint32_t *)d_records, (const unsigned int *)d_cursors, lay->region_cap, lay->regions, sp);
+  rc = xl_absorb(c, rec8 ? 8 : 4, g, d_records, (const unsigned int *)d_cursors, lay->region_cap, lay->regions, sp);
   if (rc != SHK_OK) return rc;
   if (trace_on()) {  // (debugging aid: where did the segment's records go?)
     const size_t nreg = (size_t)c->n_lanes << c->tb.log_pages;
@@ -2909,44 +2885,37 @@ static int insert_list_paged(shk_ctx *c, const uint64_t *d_kmers, const uint32_t
   if (rc != SHK_OK) return rc;
   if (!insert_list_paged_ok(c, nullptr, n)) return SHK_ERR_STATE;  // (a flush in acc_prepare grew the table out of the route: the caller falls back)
   const PartGeom g = part_geom(c);
-  const uint32_t lp = g.lp, n_pages = g.n_pages, S1_log = g.log_p1 - g.lw, S1 = 1u << S1_log, log_sub = g.log_sub, S2 = 1u << log_sub;
+  const uint32_t S1_log = g.log_p1 - g.lw, S1 = 1u << S1_log, log_sub = g.log_sub;
   const uint32_t tiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
   const uint32_t cap1 = (region_cap(n, S1, tiles) + 1u) & ~1u;
   HIPC(c, c->part.ensure((uint64_t)S1 * cap1 * 8));
-  HIPC(c, c->part_meta.ensure(std::max<size_t>(cursor_buf_bytes(c, g, false), (size_t)S1 * 4 + 64)));
+  HIPC(c, c->part_meta.ensure(std::max<size_t>(cursor_buf_bytes(c, g, paged_route(c, g, /*multi=*/false, /*defer=*/true)), (size_t)S1 * 4 + 64)));
   unsigned int *cursor1 = (unsigned int *)c->part_meta.p;
   const uint64_t spill_cap = std::max<uint64_t>(c->acc_spill_cap, n);
   c->acc_spill_cap = spill_cap;
   HIPC(c, c->spillA.ensure(spill_cap * 16));
   SpillRef sp = spill_ref(c->spillA, spill_cap);
   HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
-  auto lds_for = [](uint32_t S) { return (size_t)RS_TILE * 8 + (((size_t)RS_TILE + S) * 2 + 15) / 16 * 16 + (size_t)S * 12; };
-  const uint32_t tiles_per_region = (cap1 + RS_TILE - 1) / RS_TILE;
+  const PartDest d1{cursor1, cap1, c->part.p, 0ull};
+  RescatterList ls{}, l2{};
+  ls.lanes = NL > 1 ? d_lanes : nullptr;
+  ls.n = n;
+  ls.sub_shift = log_sub;
+  ls.owner_bits = l2.owner_bits = g.lw;
+  ls.owner_id = l2.owner_id = c->tb.owner_id;
   for (uint32_t lane = 0; lane < NL; ++lane) {
     HIPC(c, hipMemsetAsync(cursor1, 0, (size_t)S1 * 4, c->stream));
-    RescatterList ls{};
-    ls.lanes = NL > 1 ? d_lanes : nullptr;
-    ls.n = n;
-    ls.sub_shift = log_sub;
-    ls.owner_bits = g.lw;
-    ls.owner_id = c->tb.owner_id;
     {
       ScopedTimer t(c, SHK_K_SCATTER);  // level 1: list → the share's super-page regions
-      hipLaunchKernelGGL(k_part_rescatter, dim3(tiles), dim3(RS_NT), lds_for(S1), c->stream, d_kmers, (const unsigned int *)nullptr, 0u, tiles, lp, S1_log,
-                         2 * c->cfg.k, cursor1, cap1, (uint64_t *)c->part.p, lane, c->d_stats, sp, 0u, ls);
+      rc = launch_rescatter64(c, 1, d_kmers, nullptr, 0u, S1_log, d1, lane, sp, false, ls);
+      if (rc != SHK_OK) return rc;
     }
     {
       ScopedTimer t(c, SHK_K_PSCAN, /*chain=*/true);  // level 2: → this lane's waiting page regions
-      RescatterList l2{};
-      l2.owner_bits = g.lw;
-      l2.owner_id = c->tb.owner_id;
-      hipLaunchKernelGGL(k_part_rescatter, dim3(S1 * tiles_per_region), dim3(RS_NT), lds_for(S2), c->stream, (const uint64_t *)c->part.p,
-                         (const unsigned int *)cursor1, cap1, tiles_per_region, lp, log_sub, 2 * c->cfg.k,
-                         (unsigned int *)c->acc_cur.p + (size_t)lane * n_pages, c->acc_cap,
-                         (uint64_t *)c->acc_buf.p + (size_t)lane * n_pages * c->acc_cap, lane, c->d_stats, sp, 0u, l2);
+      rc = launch_rescatter64(c, S1, (const uint64_t *)c->part.p, cursor1, cap1, log_sub, acc_dest(c), lane, sp, false, l2);
+      if (rc != SHK_OK) return rc;
     }
   }
-  HIPC(c, hipGetLastError());
   c->acc_active = true;
   acc_book(c, n, NL == 1 ? 0 : -1, n);
   c->unsettled = true;

@@ -596,12 +596,23 @@ def test_skewed_low_complexity_input(orc, flags):
 
 # ---- two-level partition (tables with more pages than one LDS sort fans out to) -------------------------
 
-@pytest.mark.parametrize("k,chunks,lvl1", [(21, 1, 2), (31, 3, 3), (13, 2, 0), (23, 2, 2), (25, 3, 3), (24, 1, 1)])
-def test_two_level_partition_small(orc, monkeypatch, k, chunks, lvl1):
+def _rows_with_hooks(rows, hooked):
+    """Parameter rows (ids as pytest makes them from the values) + rows that also switch one engine hook off."""
+    return ([pytest.param(*r, None, id="-".join(map(str, r))) for r in rows] +
+            [pytest.param(*r, hook, id="-".join(map(str, r)) + "-" + hook + "=0") for r, hook in hooked])
+
+
+@pytest.mark.parametrize("k,chunks,lvl1,hook_off", _rows_with_hooks(
+    [(21, 1, 2), (31, 3, 3), (13, 2, 0), (23, 2, 2), (25, 3, 3), (24, 1, 1)],
+    [((25, 3, 3), "SHK_S64_INTERLEAVE"),    # k_scatter64 in its linear layout feeds the plain re-scatter
+     ((31, 3, 3), "SHK_SCATTER64")]))       # k_part_scatter_sorted at a fan-out k_scatter64 would otherwise take
+def test_two_level_partition_small(orc, monkeypatch, k, chunks, lvl1, hook_off):
     """Force the super-page + re-scatter path on a small table: 8+ pages, level 1 fans out to
     2^lvl1 super-pages, level 2 to the pages inside each."""
     monkeypatch.setenv("SHK_TWO_LEVEL_MIN_PAGES", "4")
     monkeypatch.setenv("SHK_LEVEL1_LOG", str(lvl1))
+    if hook_off:
+        monkeypatch.setenv(hook_off, "0")
     spec = sa.SynthSpec(genome_len=150_000, sub_per_64k=328, n_per_64k=66)
     bases, offsets = sa.synth_reads(spec, 0, 60_000)
     cnt = check_against_oracle(orc, bases, offsets, k, chunks, 200, flags=sa.FLAG_FORCE_PAGED,
@@ -882,14 +893,17 @@ def test_deferred_page_passes(orc, monkeypatch, k, chunks, hint, budget):
     _deferred_page_passes(orc, monkeypatch, k, chunks, hint, budget)
 
 
-@pytest.mark.parametrize("k,chunks,hint,budget,lvl1", [(31, 2, 1_100_000, 0, 3), (29, 3, 1_100_000, 300_000, 5),
-                                                       (21, 2, 4_200_000, 500_000, 4), (23, 2, 1_100_000, 0, 3),
-                                                       (25, 3, 1_100_000, 300_000, 4), (23, 1, 2_200_000, 250_000, 2)])
-def test_deferred_page_passes_two_level(orc, monkeypatch, k, chunks, hint, budget, lvl1):
+@pytest.mark.parametrize("k,chunks,hint,budget,lvl1,hook_off", _rows_with_hooks(
+    [(31, 2, 1_100_000, 0, 3), (29, 3, 1_100_000, 300_000, 5), (21, 2, 4_200_000, 500_000, 4), (23, 2, 1_100_000, 0, 3),
+     (25, 3, 1_100_000, 300_000, 4), (23, 1, 2_200_000, 250_000, 2)],
+    [((29, 3, 1_100_000, 300_000, 5), "SHK_S64_INTERLEAVE")]))   # the deferred level-2 pass reads a linear level-1 buffer
+def test_deferred_page_passes_two_level(orc, monkeypatch, k, chunks, hint, budget, lvl1, hook_off):
     """The same with the super-page + re-scatter partition forced: the level-2 pass appends to the
     waiting page regions (8-byte records for k = 31 / 29 / 25 / 23, 4-byte ones for k = 21)."""
     monkeypatch.setenv("SHK_TWO_LEVEL_MIN_PAGES", "4")
     monkeypatch.setenv("SHK_LEVEL1_LOG", str(lvl1))
+    if hook_off:
+        monkeypatch.setenv(hook_off, "0")
     _deferred_page_passes(orc, monkeypatch, k, chunks, hint, budget)
 
 
