@@ -139,7 +139,8 @@ enum {
   SHK_K_MERGE = 11,
   SHK_K_PCOUNT = 12,   /* validate + count k-mers per partition (k_part_count) */
   SHK_K_PSCAN = 13,    /* the two small exclusive scans between count and scatter */
-  SHK_K_HISTO_ROWS = 14 /* histograms + totals from the rows the (one) fresh page pass of a job left behind, instead of SHK_K_HISTO's scan */
+  SHK_K_HISTO_ROWS = 14, /* histograms + totals from the rows the (one) fresh page pass of a job left behind, instead of SHK_K_HISTO's scan */
+  SHK_K_EXTEND = 15    /* shk_neighborhood: seed, narrow and wide level launches */
 };
 
 /* ---- lifecycle ------------------------------------------------------------ */
@@ -331,6 +332,61 @@ int shk_filter_reads(shk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets
  * kmers_cap must be ≥ koff(n_seqs).  Host buffers; the context's table is not touched. */
 int shk_kmers_from_reads(shk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
                          uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte);
+
+/* The bulk neighbourhood of a seed set in sPCR's extension graph: every table lookup extend_graph
+ * (src/pcr/graph.rs:377-525) can make from these seeds at this threshold, fetched breadth-first on the device, many
+ * levels per launch.  For a context of k-mer length k ≥ 2, mask = (1 << 2(k−1)) − 1:
+ *   node   a (k−1)-mer as a 2-bit value (DBNode.sub_kmer), ≤ mask;
+ *   dir    bit 0 forward, bit 1 reverse; 3 stands for the two entries (node, F) and (node, R);
+ *   the expansion of (s, F) is the four k-mers (s << 2) | b, of (s, R) the four (b << 2(k−1)) | s (graph.rs:419-423);
+ *   x is ACCEPTED when the merged count c of min(x, revcomp(x)) — what shk_lookup(canonical = 1) returns — is
+ *   ≥ min_count (0 is treated as 1); its successor, x & mask for F and x >> 2 for R, keeps the dir (graph.rs:441-444).
+ * Level 0 is the set of distinct seed (node, dir) pairs; level i + 1 the distinct successors of level i's accepted
+ * k-mers that are in no level ≤ i; K_L the distinct canonical k-mers accepted in the expansions of levels 0..L−1.
+ * The call expands WHOLE levels: level L if and only if L < max_levels (0: no limit), level L is not empty, and
+ * afterwards |K_{L+1}| ≤ cap and |level L+1| ≤ fringe_cap; otherwise it stops with level L unexpanded, and nothing of
+ * a level that did not fit shows.  Out: K_L in kmers/counts ascending by k-mer (*n_out entries), level L in
+ * fringe_nodes/fringe_dirs ascending by (node, dir) with one dir bit per entry (*n_fringe entries; 0 when the
+ * neighbourhood is complete), *levels_done = L.  Calling again with the fringe as seeds continues the search (it may
+ * report k-mers and entries again that an earlier call reported).  A deterministic function of table and arguments.
+ * Errors: dir 0 or > 3, a node > mask, more distinct seeds than fringe_cap: SHK_ERR_BAD_ARG; a multi-device context
+ * or an owner share (a neighbour's count may live on another share): SHK_ERR_STATE.  Valid whenever shk_lookup is;
+ * the table is not touched.  cap, fringe_cap ≤ 2^32; the device scratch is about 100 bytes per unit of cap. */
+int shk_neighborhood(shk_ctx *ctx, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds,
+                     uint32_t min_count, uint32_t max_levels,
+                     uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
+                     uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
+                     uint32_t *levels_done);
+
+/* create_seed_graph + extend_graph (src/pcr/graph.rs:196-528) under the threshold sweep of do_pcr
+ * (src/pcr/mod.rs:559-619), replayed on the host statement for statement over counts that shk_neighborhood fetched
+ * (defaults of the reference in brackets). */
+typedef struct shk_pcr_extend_params {
+  uint32_t min_count;          /* PCRParams.min_count [2]: the sweep's lowest threshold */
+  uint32_t table_min_count;    /* FilteredKmerCounts' floor, cli --min-kmer-count [2] (counting.rs:306-345) */
+  double   high_coverage_ratio;/* [10.0] graph.rs:495 */
+  uint64_t max_num_nodes;      /* compute_node_budget(n_bases_ingested) or the caller's; graph.rs:389 */
+  uint32_t sweep;              /* 1: thresholds of compute_coverage_thresholds (mod.rs:403-428), stop at the first
+                                  step that finds a path (mod.rs:585-619); 0: one extension at min_count */
+  uint32_t reserved;
+} shk_pcr_extend_params;
+/* fwd_/rev_kmers: the two primer k-mer sets as shk_primer_kmers returns them (primer at the 5' end); their counts
+ * feed the sweep's min(max fwd, max rev) (mod.rs:542-562).  Out: the graph of the last step run (current_graph,
+ * mod.rs:613) — nodes in NodeIndex order (sub_kmer, flags: 1 is_start, 2 is_end), edges in EdgeIndex order (source
+ * and target node index, DBEdge.count) — *found_path of that step, its threshold, the steps run.  An empty set is not
+ * an error (do_pcr returns before, mod.rs:446-468): the other set's seeds are extended and no path is found.
+ * node_cap / edge_cap too small: SHK_ERR_BAD_ARG with *n_nodes / *n_edges set to what is needed.  A k-mer counts
+ * when its merged count ≥ max(threshold, table_min_count, 1).  Multi-device contexts and owner shares:
+ * SHK_ERR_STATE, as shk_neighborhood.  Tuning: SHK_PCR_FETCH_CAP (k-mers, read at each call) bounds one
+ * shk_neighborhood fetch; the result does not depend on it. */
+int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
+                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev,
+                   const shk_pcr_extend_params *p,
+                   uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes,
+                   uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges,
+                   uint32_t *found_path, uint32_t *threshold_used, uint32_t *steps_run);
+/* compute_node_budget (graph.rs:40-52): 100 000 nodes up to 150 Mbp ingested, 500 000 from 750 Mbp, linear between. */
+uint64_t shk_pcr_node_budget(uint64_t n_bases_ingested);
 
 /* ---- multi-GPU hooks (device pointers; exchanged by the caller over RCCL) ---- */
 

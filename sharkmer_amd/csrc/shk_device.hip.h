@@ -1316,6 +1316,163 @@ __global__ void __launch_bounds__(WG) k_export(TableRef tb, uint64_t slot0, uint
 }
 
 // ==========================================================================================
+// K_EXTEND: the bulk neighbourhood of a seed set (shk_neighborhood), the table side of sPCR's graph extension
+// (extend_graph, src/pcr/graph.rs:377-525): breadth-first over (node, dir) entries — a node is a (k−1)-mer, dir 0
+// extends it forward ((node << 2) | b), dir 1 backward ((b << 2(k−1)) | node) — where an entry's four candidate
+// k-mers are looked up in the merged table and the accepted ones (merged count ≥ min_count) lead to the next level.
+//
+// Two sets in device memory, both open addressing over 64-bit words probed with atomicCAS only (so that every access
+// is served by L2 and no wave reads a stale line): `vis`, the entries (node << 1 | dir) of every level so far, and
+// `kset`, the accepted canonical k-mers.  Whoever wins an insert appends: to the k-mer list, or to the next level.
+// Fills past a list's capacity are counted but not written; the level then did not fit and the host drops it (the
+// k-mer list is cut back to its fill at the level's start, the entry list of the level itself is untouched).
+// ==========================================================================================
+constexpr int NB_WG = 1024;            // k_nb_narrow: one workgroup
+constexpr uint32_t NB_NARROW = 1024;   // … carries a level of up to this many entries
+constexpr uint32_t NB_RUN = 0, NB_COMPLETE = 1, NB_LIMIT = 2, NB_OVERFLOW = 3, NB_WIDE = 4;
+
+struct NbCtl {                 // host ↔ device state of one shk_neighborhood call
+  unsigned long long k_n;      // accepted k-mers appended so far
+  unsigned long long next_n;   // entries of the level under construction (counted past fringe_cap)
+  unsigned long long cur_n;    // entries of the current (unexpanded) level
+  uint32_t levels_done;
+  uint32_t cur_sel;            // which of the two entry lists holds the current level
+  uint32_t status;             // NB_*
+  uint32_t set_full;           // a set ran out of slots: only in a level that does not fit the capacities the sets are sized for
+};
+
+struct NbRef {
+  uint64_t *vis, *kset;        // EMPTY-filled
+  uint64_t vis_mask, kset_mask;
+  uint64_t *list[2];           // entry lists, fringe_cap each
+  uint64_t *kmers;             // cap
+  uint32_t *counts;            // cap
+  uint64_t cap, fringe_cap;
+  uint32_t min_count, max_levels;
+  int k;
+};
+
+// 1: inserted, 0: was there, −1: no free slot
+__device__ __forceinline__ int nb_set_insert(uint64_t *set, uint64_t mask, uint64_t key) {
+  uint64_t s = ((key ^ (key >> 29)) * MIX_M64 >> 20) & mask;
+  for (uint64_t i = 0; i <= mask; ++i) {
+    const uint64_t prev = atomicCAS((unsigned long long *)&set[s], (unsigned long long)EMPTY, (unsigned long long)key);
+    if (prev == EMPTY) return 1;
+    if (prev == key) return 0;
+    s = (s + 1) & mask;
+  }
+  return -1;
+}
+
+// One (entry, base) pair of the current level.  k_n / next_n: the two fill counters (LDS in k_nb_narrow, the control
+// block in k_nb_wide); lds_next: where k_nb_narrow keeps the first NB_NARROW entries of the next level.
+__device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, uint64_t entry, uint32_t b,
+                                          uint64_t *next_list, unsigned long long *k_n, unsigned long long *next_n,
+                                          uint32_t *set_full, uint64_t *lds_next) {
+  const uint64_t node = entry >> 1, dir = entry & 1ull;
+  const int sh = 2 * (nb.k - 1);
+  const uint64_t x = dir ? ((uint64_t)b << sh) | node : (node << 2) | b;
+  const uint64_t rc = revcomp(x, nb.k);
+  const uint64_t cn = x < rc ? x : rc;
+  const uint32_t cnt = merged_count(tb, cn);
+  if (cnt < nb.min_count) return;
+  const int ins = nb_set_insert(nb.kset, nb.kset_mask, cn);
+  if (ins < 0) {
+    atomicOr(set_full, 1u);
+    return;
+  }
+  if (ins) {
+    const unsigned long long at = atomicAdd(k_n, 1ull);
+    if (at >= nb.cap) return;  // the level does not fit: nothing of it will be kept
+    nb.kmers[at] = cn;
+    nb.counts[at] = cnt;
+  }
+  const uint64_t succ = (dir ? x >> 2 : x & ((1ull << sh) - 1ull)) << 1 | dir;
+  const int v = nb_set_insert(nb.vis, nb.vis_mask, succ);
+  if (v < 0) atomicOr(set_full, 1u);
+  if (v <= 0) return;
+  const unsigned long long at = atomicAdd(next_n, 1ull);
+  if (at < nb.fringe_cap) next_list[at] = succ;
+  if (lds_next && at < NB_NARROW) lds_next[at] = succ;
+}
+
+// Level 0 into the visited set.
+__global__ void __launch_bounds__(WG) k_nb_seed(NbRef nb, uint64_t n, NbCtl *ctl) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  if (nb_set_insert(nb.vis, nb.vis_mask, nb.list[0][i]) < 0) atomicOr(&ctl->set_full, 1u);
+}
+
+// WIDE: one level per launch, one thread per (entry, base); the host reads the two fills back and decides.
+__global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ctl, uint32_t cur_sel, uint64_t cur_n) {
+  const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= cur_n * 4) return;
+  nb_expand(tb, nb, nb.list[cur_sel][t >> 2], (uint32_t)(t & 3), nb.list[cur_sel ^ 1], &ctl->k_n, &ctl->next_n,
+            &ctl->set_full, nullptr);
+}
+
+// NARROW: one workgroup takes a level of at most NB_NARROW entries through as many levels as it stays that thin —
+// the two entry lists and the fill counters in LDS, a workgroup barrier between levels, no host round trip.  It
+// stops with ctl->status = why: the neighbourhood is complete, max_levels reached, the next level did not fit the
+// caller's capacities (ctl then describes the level before it), or it is too wide for one workgroup (k_nb_wide's).
+__global__ void __launch_bounds__(NB_WG) k_nb_narrow(TableRef tb, NbRef nb, NbCtl *ctl) {
+  __shared__ uint64_t s_list[2][NB_NARROW];
+  __shared__ unsigned long long s_kn, s_kstart, s_nextn, s_curfull;  // s_curfull: the current level's size, s_curn capped
+  __shared__ uint32_t s_full, s_status, s_curn, s_sel, s_levels;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) {
+    s_kn = s_kstart = ctl->k_n;
+    s_curfull = ctl->cur_n;
+    s_nextn = 0;
+    s_full = 0;
+    s_status = NB_RUN;
+    s_curn = (uint32_t)ctl->cur_n;  // ≤ NB_NARROW: the host's launch condition
+    s_sel = ctl->cur_sel;
+    s_levels = ctl->levels_done;
+  }
+  __syncthreads();
+  const uint32_t sel0 = s_sel;
+  for (uint32_t i = tid; i < s_curn; i += NB_WG) s_list[sel0][i] = nb.list[sel0][i];
+  __syncthreads();
+  while (true) {
+    const uint32_t sel = s_sel, cur_n = s_curn;
+    for (uint32_t t = tid; t < cur_n * 4; t += NB_WG)
+      nb_expand(tb, nb, s_list[sel][t >> 2], t & 3, nb.list[sel ^ 1], &s_kn, &s_nextn, &s_full, s_list[sel ^ 1]);
+    __syncthreads();
+    if (tid == 0) {
+      if (s_full || s_kn > nb.cap || s_nextn > nb.fringe_cap) {
+        s_kn = s_kstart;  // the level is dropped: the k-mer list back to its start, the entry list as it was
+        s_status = NB_OVERFLOW;
+      } else {
+        s_levels += 1;
+        s_sel = sel ^ 1;
+        s_kstart = s_kn;
+        s_curfull = s_nextn;
+        s_curn = (uint32_t)(s_nextn < NB_NARROW ? s_nextn : NB_NARROW);
+        if (s_nextn == 0)
+          s_status = NB_COMPLETE;
+        else if (nb.max_levels && s_levels >= nb.max_levels)
+          s_status = NB_LIMIT;
+        else if (s_nextn > NB_NARROW)
+          s_status = NB_WIDE;
+        s_nextn = 0;
+      }
+    }
+    __syncthreads();
+    if (s_status != NB_RUN) break;
+  }
+  if (tid == 0) {
+    ctl->k_n = s_kn;
+    ctl->next_n = 0;
+    ctl->cur_n = s_curfull;
+    ctl->levels_done = s_levels;
+    ctl->cur_sel = s_sel;
+    ctl->status = s_status;
+    ctl->set_full = s_full;
+  }
+}
+
+// ==========================================================================================
 // K_OLIGO: the primer seed scan of sPCR, find_oligos_in_kmers (src/pcr/primers.rs:163-226): one
 // bandwidth-bound pass over the merged table.  A k-mer with count ≥ min_count is reported as
 // is when its first oligo_len bases equal one of the oligos, or reverse-complemented when its

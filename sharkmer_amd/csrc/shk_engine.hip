@@ -10,6 +10,7 @@
 #include "shk_device.hip.h"
 #include "shk_front.h"
 #include "shk_primer.h"
+#include "shk_pcr.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3353,6 +3354,201 @@ int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, 
   }
   HIPC(c, hipMemcpyAsync(counts, dc, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
+  return SHK_OK;
+}
+
+int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds, uint32_t min_count,
+                     uint32_t max_levels, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
+                     uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
+                     uint32_t *levels_done) {
+  if (!c || !n_out || !n_fringe || !levels_done || (n_seeds && (!nodes || !dirs))) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  if ((cap && (!kmers || !counts)) || (fringe_cap && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
+  if (cap > (1ull << 32) || fringe_cap > (1ull << 32))
+    return fail(c, SHK_ERR_BAD_ARG, "cap %llu / fringe_cap %llu above 2^32", (unsigned long long)cap, (unsigned long long)fringe_cap);
+  const uint64_t node_mask = (1ull << (2 * (k - 1))) - 1ull;
+  // level 0: the distinct (node, dir) pairs, as entries node << 1 | (0 forward, 1 reverse)
+  std::vector<uint64_t> seeds;
+  seeds.reserve(n_seeds);
+  for (uint64_t i = 0; i < n_seeds; ++i) {
+    if (dirs[i] == 0 || dirs[i] > 3) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: dir %u is not 1 (forward), 2 (reverse) or 3 (both)", (unsigned long long)i, dirs[i]);
+    if (nodes[i] > node_mask) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: node 0x%llx is not a %u-mer", (unsigned long long)i, (unsigned long long)nodes[i], k - 1);
+    if (dirs[i] & 1) seeds.push_back(nodes[i] << 1);
+    if (dirs[i] & 2) seeds.push_back(nodes[i] << 1 | 1ull);
+  }
+  std::sort(seeds.begin(), seeds.end());
+  seeds.erase(std::unique(seeds.begin(), seeds.end()), seeds.end());
+  if (seeds.size() > fringe_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "%llu distinct seeds do not fit fringe_cap %llu", (unsigned long long)seeds.size(), (unsigned long long)fringe_cap);
+  *n_out = 0;
+  *n_fringe = 0;
+  *levels_done = 0;
+  if (seeds.empty()) return SHK_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  {
+    int rcs = settle(c);
+    if (rcs != SHK_OK) return rcs;
+  }
+  {
+    int rcf = tb_fresh(c);
+    if (rcf != SHK_OK) return rcf;
+  }
+  // An accepted k-mer has two orientations and an orientation one successor per dir: through a level that fits, the
+  // visited set never holds more than the seeds and 4·cap entries, the k-mer set cap.  Both at most half full then; a
+  // set that fills up (probes are bounded) belongs to a level that does not fit and is dropped.
+  auto pow2_above = [](uint64_t n) {
+    uint64_t s = 16;
+    while (s < n) s <<= 1;
+    return s;
+  };
+  const uint64_t vis_slots = pow2_above(2 * (seeds.size() + 4 * cap) + 2), kset_slots = pow2_above(2 * cap + 2);
+  const uint64_t fc = std::max<uint64_t>(fringe_cap, 1), kc = std::max<uint64_t>(cap, 1);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 15) & ~(size_t)15;
+    return at;
+  };
+  const size_t o_ctl = take(sizeof(NbCtl)), o_vis = take(vis_slots * 8), o_kset = take(kset_slots * 8);
+  const size_t o_l0 = take(fc * 8), o_l1 = take(fc * 8), o_km = take(kc * 8), o_ct = take(kc * 4);
+  HIPC(c, c->misc.ensure(off));
+  uint8_t *p = (uint8_t *)c->misc.p;
+  NbCtl *dctl = (NbCtl *)(p + o_ctl);
+  NbRef nb{};
+  nb.vis = (uint64_t *)(p + o_vis);
+  nb.kset = (uint64_t *)(p + o_kset);
+  nb.vis_mask = vis_slots - 1;
+  nb.kset_mask = kset_slots - 1;
+  nb.list[0] = (uint64_t *)(p + o_l0);
+  nb.list[1] = (uint64_t *)(p + o_l1);
+  nb.kmers = (uint64_t *)(p + o_km);
+  nb.counts = (uint32_t *)(p + o_ct);
+  nb.cap = cap;
+  nb.fringe_cap = fringe_cap;
+  nb.min_count = std::max(min_count, 1u);
+  nb.max_levels = max_levels;
+  nb.k = (int)k;
+  NbCtl h{};
+  h.cur_n = seeds.size();
+  HIPC(c, hipMemsetAsync(nb.vis, 0xFF, (o_l0 - o_vis), c->stream));  // both sets ← EMPTY
+  HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(nb.list[0], seeds.data(), seeds.size() * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_seed, dim3((uint32_t)((seeds.size() + WG - 1) / WG)), dim3(WG), 0, c->stream, nb,
+                       (uint64_t)seeds.size(), dctl);
+  }
+  // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
+  while (h.status == NB_RUN || h.status == NB_WIDE) {
+    if (h.cur_n == 0) {
+      h.status = NB_COMPLETE;
+      break;
+    }
+    if (max_levels && h.levels_done >= max_levels) {
+      h.status = NB_LIMIT;
+      break;
+    }
+    if (h.cur_n <= NB_NARROW) {
+      {
+        ScopedTimer t(c, SHK_K_EXTEND);
+        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
+      }
+      HIPC(c, hipGetLastError());
+      HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+      HIPC(c, hipStreamSynchronize(c->stream));
+      continue;
+    }
+    const unsigned long long k_start = h.k_n;
+    {
+      ScopedTimer t(c, SHK_K_EXTEND);
+      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
+                         dctl, h.cur_sel, (uint64_t)h.cur_n);
+    }
+    HIPC(c, hipGetLastError());
+    NbCtl r{};
+    HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (r.set_full || r.k_n > cap || r.next_n > fringe_cap) {  // the level did not fit: the k-mer list back to its start
+      h.k_n = k_start;
+      h.status = NB_OVERFLOW;
+      break;
+    }
+    h.k_n = r.k_n;
+    h.cur_n = r.next_n;
+    h.cur_sel ^= 1u;
+    h.levels_done += 1;
+    h.next_n = 0;
+    h.status = NB_RUN;
+    HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));  // (h is a pageable source: the copy has read it)
+  }
+  // the arrival order of the appends is not part of the result: sorted
+  const uint64_t nk = h.k_n, nf = h.status == NB_COMPLETE ? 0 : h.cur_n;
+  std::vector<uint64_t> hk(nk), hf(nf);
+  std::vector<uint32_t> hc(nk);
+  if (nk) {
+    HIPC(c, hipMemcpy(hk.data(), nb.kmers, nk * 8, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(hc.data(), nb.counts, nk * 4, hipMemcpyDeviceToHost));
+  }
+  if (nf) HIPC(c, hipMemcpy(hf.data(), nb.list[h.cur_sel], nf * 8, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> order(nk);
+  for (uint64_t i = 0; i < nk; ++i) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
+  for (uint64_t i = 0; i < nk; ++i) {
+    kmers[i] = hk[order[i]];
+    counts[i] = hc[order[i]];
+  }
+  std::sort(hf.begin(), hf.end());
+  for (uint64_t i = 0; i < nf; ++i) {
+    fringe_nodes[i] = hf[i] >> 1;
+    fringe_dirs[i] = (uint8_t)(1u << (hf[i] & 1ull));
+  }
+  *n_out = nk;
+  *n_fringe = nf;
+  *levels_done = h.levels_done;
+  return SHK_OK;
+}
+
+int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
+                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev, const shk_pcr_extend_params *p,
+                   uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes, uint32_t *edge_src,
+                   uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges, uint32_t *found_path,
+                   uint32_t *threshold_used, uint32_t *steps_run) {
+  if (!c || !p || !n_nodes || !n_edges || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
+  if ((n_fwd && (!fwd_kmers || !fwd_counts)) || (n_rev && (!rev_kmers || !rev_counts))) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  const uint64_t kmask = ~0ull >> (64 - 2 * k);
+  for (uint64_t i = 0; i < n_fwd; ++i)
+    if (fwd_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "forward primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
+  for (uint64_t i = 0; i < n_rev; ++i)
+    if (rev_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "reverse primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
+  PcrGraph g;
+  std::string msg;
+  const int rc = pcr_extend_run(c, k, fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev, *p, &g, threshold_used,
+                                steps_run, &msg);
+  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood's own text stands)
+  *n_nodes = g.sub_kmer.size();
+  *n_edges = g.esrc.size();
+  *found_path = g.found_path ? 1u : 0u;
+  if (*n_nodes > node_cap || *n_edges > edge_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "graph of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu",
+                (unsigned long long)*n_nodes, (unsigned long long)*n_edges, (unsigned long long)node_cap, (unsigned long long)edge_cap);
+  if ((*n_nodes && (!node_sub_kmers || !node_flags)) || (*n_edges && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
+  std::copy(g.sub_kmer.begin(), g.sub_kmer.end(), node_sub_kmers);
+  std::copy(g.flags.begin(), g.flags.end(), node_flags);
+  std::copy(g.esrc.begin(), g.esrc.end(), edge_src);
+  std::copy(g.etgt.begin(), g.etgt.end(), edge_tgt);
+  std::copy(g.ecount.begin(), g.ecount.end(), edge_counts);
   return SHK_OK;
 }
 

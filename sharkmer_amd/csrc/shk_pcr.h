@@ -1,0 +1,31 @@
+// shk_pcr.h — host side of sPCR's graph extension (create_seed_graph + extend_graph, src/pcr/graph.rs:196-528, under
+// the threshold sweep of do_pcr, src/pcr/mod.rs:559-619): the reference's order-dependent logic replayed statement for
+// statement over counts fetched in bulk by shk_neighborhood (plain C++: no HIP; the device is reached through that
+// entry point only).
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/shk.h"
+
+struct PcrGraph {                       // StableDiGraph<DBNode, DBEdge> as arrays in index order
+  std::vector<uint64_t> sub_kmer;       // DBNode.sub_kmer, NodeIndex order
+  std::vector<uint8_t> flags;           // 1 is_start, 2 is_end
+  std::vector<uint32_t> esrc, etgt, ecount;  // EdgeIndex order
+  bool found_path = false;
+};
+
+// median_via_select (graph.rs:82-103) of edge counts; `dflt` when there are none (compute_median_edge_count)
+double pcr_median_u32(std::vector<uint32_t> counts, double dflt);
+// compute_coverage_thresholds (mod.rs:403-428)
+std::vector<uint32_t> pcr_coverage_thresholds(uint32_t primer_count, uint32_t min_count);
+
+// The sweep over a context of k-mer length k.  *threshold_used / *steps_run describe the last step run, whose graph is
+// *out.  Returns SHK_OK or the code of a failed shk_neighborhood (its text is the context's last error); *err is set
+// for failures of its own.
+int pcr_extend_run(shk_ctx *ctx, uint32_t k, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
+                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev,
+                   const shk_pcr_extend_params &p, PcrGraph *out, uint32_t *threshold_used, uint32_t *steps_run,
+                   std::string *err);

@@ -29,7 +29,7 @@ FASTQ_GZIP_ALL_MEMBERS = 1  # shk_fastq_open_ex / shk_run_config.fastq_flags (in
 FLAG_DEFER_ERRORS = 8  # host-buffer ingests return once queued; errors surface at the next call (include/shk.h)
 
 KERNEL_NAMES = ["mark", "scan", "direct", "scatter", "pages", "histo", "grow", "insert",
-                "lookup", "export", "synth", "merge", "pcount", "pscan", "histo_rows"]
+                "lookup", "export", "synth", "merge", "pcount", "pscan", "histo_rows", "extend"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -129,6 +129,30 @@ def primer_compile(primer: Primer, k: int):
     return int(tl.value), [int(x) for x in nv[:nl.value]]
 
 
+class _PcrExtendParams(C.Structure):
+    _fields_ = [("min_count", C.c_uint32), ("table_min_count", C.c_uint32), ("high_coverage_ratio", C.c_double),
+                ("max_num_nodes", C.c_uint64), ("sweep", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+@dataclass
+class PcrGraph:
+    """What shk_pcr_extend returns: the graph of the last threshold step run (current_graph, pcr/mod.rs:613) as
+    arrays — nodes in NodeIndex order, edges in EdgeIndex order."""
+    node_sub_kmers: np.ndarray  # u64, DBNode.sub_kmer
+    node_flags: np.ndarray      # u8: 1 is_start, 2 is_end
+    edge_src: np.ndarray        # u32 node indices
+    edge_tgt: np.ndarray
+    edge_counts: np.ndarray     # u32, DBEdge.count
+    found_path: bool
+    threshold_used: int
+    steps_run: int
+
+
+def pcr_node_budget(n_bases_ingested: int) -> int:
+    """compute_node_budget (pcr/graph.rs:40-52)."""
+    return int(load_library().shk_pcr_node_budget(n_bases_ingested))
+
+
 class _Synth(C.Structure):
     _fields_ = [("seed_genome", C.c_uint64), ("seed_reads", C.c_uint64), ("genome_len", C.c_uint64),
                 ("read_len", C.c_uint32), ("sub_per_64k", C.c_uint32), ("n_per_64k", C.c_uint32),
@@ -152,6 +176,7 @@ ABI_SYMBOLS = [
     "shk_stream", "shk_compact_owners_packed", "shk_compact_owners_fixed", "shk_merge_pieces_max", "shk_merge_pieces", "shk_set_owner_share", "shk_finalize_begin", "shk_finalize_end",
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
+    "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget",
 ]
 
 _lib = None
@@ -271,6 +296,12 @@ def load_library():
     L.shk_primer_kmers.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, vp]
     L.shk_filter_reads.argtypes = [vp, vp, vp, u64, vp, u64, vp]
     L.shk_kmers_from_reads.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
+    L.shk_neighborhood.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64),
+                                   C.POINTER(u32)]
+    L.shk_pcr_extend.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(_PcrExtendParams), vp, vp, u64, C.POINTER(u64),
+                                 vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.shk_pcr_node_budget.argtypes = [u64]
+    L.shk_pcr_node_budget.restype = u64
     L.shk_owner_counts.argtypes = [vp, u32, vp]
     L.shk_compact_owners.argtypes = [vp, u32, vp, vp, vp, u64, C.c_int32]
     L.shk_merge_entries.argtypes = [vp, vp, vp, u64, u64]
@@ -551,6 +582,58 @@ class KmerEngine:
         returns it.  params: trim, mismatches, min_count, max_kmers (the reference's defaults otherwise)."""
         fwd, rev = self.primer_kmers([Primer(forward, **params), Primer(reverse, **params)])
         return fwd, rev
+
+    def neighborhood(self, nodes, dirs, min_count: int, max_levels: int = 0, cap: int = 1 << 16,
+                     fringe_cap: int = 1 << 16):
+        """shk_neighborhood: the bulk neighbourhood of seed (node, dir) pairs in sPCR's extension graph (nodes are
+        (k−1)-mers; dir 1 forward, 2 reverse, 3 both), expanded in whole levels while the accepted k-mers fit `cap` and a
+        level fits `fringe_cap` → (kmers u64 ascending, counts u32, fringe_nodes u64, fringe_dirs u8, levels_done); an
+        empty fringe says the neighbourhood is complete."""
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.uint64)
+        dirs = np.ascontiguousarray(np.atleast_1d(dirs), dtype=np.uint8)
+        if len(nodes) != len(dirs):
+            raise ValueError("nodes and dirs differ in length")
+        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
+        counts = np.zeros(max(cap, 1), dtype=np.uint32)
+        fn = np.zeros(max(fringe_cap, 1), dtype=np.uint64)
+        fd = np.zeros(max(fringe_cap, 1), dtype=np.uint8)
+        n_out, n_fr, lv = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(self._L.shk_neighborhood(self._h, nodes.ctypes.data, dirs.ctypes.data, len(nodes), min_count,
+                                             max_levels, kmers.ctypes.data, counts.ctypes.data, cap, C.byref(n_out),
+                                             fn.ctypes.data, fd.ctypes.data, fringe_cap, C.byref(n_fr), C.byref(lv)))
+        a, b = int(n_out.value), int(n_fr.value)
+        return kmers[:a].copy(), counts[:a].copy(), fn[:b].copy(), fd[:b].copy(), int(lv.value)
+
+    def pcr_extend(self, fwd, rev, min_count: int = 2, table_min_count: int = 2, high_coverage_ratio: float = 10.0,
+                   max_num_nodes: int | None = None, sweep: bool = True) -> PcrGraph:
+        """create_seed_graph + extend_graph under do_pcr's threshold sweep (pcr/graph.rs:196-528, pcr/mod.rs:559-619)
+        → PcrGraph.  fwd, rev: the two tuples of primer_pair_kmers (k-mers first, counts second).  max_num_nodes:
+        None = compute_node_budget of the bases this context has ingested."""
+        fk = np.ascontiguousarray(fwd[0], dtype=np.uint64)
+        fc = np.ascontiguousarray(fwd[1], dtype=np.uint32)
+        rk = np.ascontiguousarray(rev[0], dtype=np.uint64)
+        rc = np.ascontiguousarray(rev[1], dtype=np.uint32)
+        if max_num_nodes is None:
+            max_num_nodes = pcr_node_budget(self.counters()["n_bases_ingested"])
+        prm = _PcrExtendParams(min_count, table_min_count, high_coverage_ratio, max_num_nodes, 1 if sweep else 0, 0)
+        node_cap, edge_cap = 4096, 8192
+        while True:
+            sub = np.zeros(node_cap, dtype=np.uint64)
+            flags = np.zeros(node_cap, dtype=np.uint8)
+            es, et, ec = (np.zeros(edge_cap, dtype=np.uint32) for _ in range(3))
+            nn, ne = C.c_uint64(0), C.c_uint64(0)
+            found, thr, steps = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+            rcode = self._L.shk_pcr_extend(self._h, fk.ctypes.data, fc.ctypes.data, len(fk), rk.ctypes.data,
+                                           rc.ctypes.data, len(rk), C.byref(prm), sub.ctypes.data, flags.ctypes.data,
+                                           node_cap, C.byref(nn), es.ctypes.data, et.ctypes.data, ec.ctypes.data, edge_cap,
+                                           C.byref(ne), C.byref(found), C.byref(thr), C.byref(steps))
+            n, e = int(nn.value), int(ne.value)
+            if rcode == -2 and (n > node_cap or e > edge_cap):  # the buffers were too small: it says what it needs
+                node_cap, edge_cap = max(node_cap, n), max(edge_cap, e)
+                continue
+            self._check(rcode)
+            return PcrGraph(sub[:n].copy(), flags[:n].copy(), es[:e].copy(), et[:e].copy(), ec[:e].copy(),
+                            bool(found.value), int(thr.value), int(steps.value))
 
     def filter_reads(self, bases: np.ndarray, offsets: np.ndarray, primer_kmers) -> np.ndarray:
         """PrimerReadFilter::matches per read (pcr/read_filter.rs:43-55) → bool array."""
