@@ -11,9 +11,11 @@ from __future__ import annotations
 
 import numpy as np
 
+import pcr_ref
 import primer_ref
 
 U32_MAX = 0xFFFFFFFF
+SHK_ERR_BAD_ARG, SHK_ERR_STATE = -2, -11  # include/shk.h
 _VALID = np.zeros(256, dtype=bool)
 _VALID[list(b"ACGTN")] = True
 
@@ -21,7 +23,12 @@ NO_READS = "No reads were ingested. Check that input files contain valid FASTQ r
 
 
 class ModelError(Exception):
-    """The reference's anyhow error, with its text."""
+    """The reference's anyhow error, with its text — or, where the reference has no such call and include/shk.h states
+    the error, the ABI's code."""
+
+    def __init__(self, text, code=None):
+        super().__init__(text)
+        self.code = code
 
 
 class Observation:
@@ -35,9 +42,21 @@ class Observation:
         self.n_hashed = merged.get_n_kmers()
 
 
+class MergedView:
+    """The merged table read key by key, as much of a {k-mer: count} dict as tests/pcr_ref.py asks for: a key inserted
+    with count 0 is there with 0, an absent one gives the default."""
+
+    def __init__(self, merged):
+        self.merged = merged
+
+    def get(self, kmer, default=None):
+        return self.merged.get_count(kmer) if self.merged.contains(kmer) else default
+
+
 class LaneModel:
-    def __init__(self, orc, k: int, chunks: int, histo_max: int):
+    def __init__(self, orc, k: int, chunks: int, histo_max: int, multi_device: bool = False):
         self.orc, self.k, self.chunks, self.histo_max = orc, k, chunks, histo_max
+        self.multi_device = multi_device  # (the same data model: only what the ABI refuses on such a context differs)
         self.n_lanes = max(chunks, 1)  # io.rs:378
         self.reset()
 
@@ -160,3 +179,33 @@ class LaneModel:
             primer_ref.check_variant_limit(p.seq, p.trim, self.k)
         return [primer_ref.get_primer_kmers(p.seq, keys, counts, self.k, p.trim, p.mismatches, p.min_count,
                                             p.max_kmers, check_variants=False) for p in primers]
+
+    # ---- sPCR's graph extension (tests/pcr_ref.py) -----------------------------------------------
+    def graph_table(self, what: str) -> MergedView:
+        """The merged table as shk_lookup(canonical = 1) sees it — the saturating sum over the lanes, a key inserted
+        with count 0 present with 0 — or the refusal include/shk.h states for `what`."""
+        if self.multi_device:
+            raise ModelError("%s needs the whole table on one device: this is a multi-device context (n_devices > 1)" % what,
+                             SHK_ERR_STATE)
+        if self.k < 2:
+            raise ModelError("%s needs k >= 2 (a node is a (k-1)-mer), got k=%d" % (what, self.k), SHK_ERR_BAD_ARG)
+        return MergedView(self.observe().merged)
+
+    def neighborhood(self, nodes, dirs, min_count: int, max_levels: int = 0, cap: int = 1 << 16, fringe_cap: int = 1 << 16):
+        """shk_neighborhood → (kmers, counts, fringe_nodes, fringe_dirs, levels_done) as lists."""
+        table = self.graph_table("shk_neighborhood")
+        mask = (1 << (2 * (self.k - 1))) - 1
+        for i, (n, d) in enumerate(zip(nodes, dirs)):
+            if not 1 <= int(d) <= 3 or int(n) > mask:
+                raise ModelError("seed %d: (node 0x%x, dir %d) is no (k-1)-mer with a dir of 1, 2 or 3" % (i, int(n), int(d)),
+                                 SHK_ERR_BAD_ARG)
+        try:
+            return pcr_ref.neighborhood(nodes, dirs, table, self.k, min_count, max_levels, cap, fringe_cap)
+        except ValueError as e:  # more distinct seeds than fringe_cap
+            raise ModelError(str(e), SHK_ERR_BAD_ARG) from e
+
+    def pcr_extend(self, fwd, rev, **params):
+        """shk_pcr_extend → (pcr_ref.Graph of the last step run, threshold used, steps run).  fwd, rev: (k-mers,
+        counts); params: pcr_ref.pcr_extend's (min_count, table_min_count, high_coverage_ratio, max_num_nodes, sweep)."""
+        table = self.graph_table("shk_pcr_extend")
+        return pcr_ref.pcr_extend(fwd, rev, table, self.k, **params)

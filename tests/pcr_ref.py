@@ -215,9 +215,10 @@ def pcr_extend(fwd, rev, table: dict[int, int], k: int, min_count: int = 2, tabl
     return cur, used, steps
 
 
-def neighborhood_levels(nodes, dirs, table: dict[int, int], k: int, min_count: int):
-    """Every level of the complete neighbourhood and the accepted k-mers each level's expansion adds:
-    [(level entries as a sorted list of (node, dir bit), {canonical k-mer: count} new in its expansion)]."""
+def iter_levels(nodes, dirs, table, k: int, min_count: int):
+    """Level after level of the complete neighbourhood, each with the accepted k-mers its expansion adds: yields
+    (level entries as a sorted list of (node, dir bit), {canonical k-mer: count} new in its expansion).  `table`: a
+    dict, or anything with its `get`.  Lazy: who stops asking pays for no further level."""
     mask = (1 << (2 * (k - 1))) - 1
     sh = 2 * (k - 1)
     mc = max(min_count, 1)
@@ -229,7 +230,7 @@ def neighborhood_levels(nodes, dirs, table: dict[int, int], k: int, min_count: i
             level.add((n, 1))
         if d & 2:
             level.add((n, 2))
-    seen, kseen, out = set(level), set(), []
+    seen, kseen = set(level), set()
     while level:
         new_k, nxt = {}, set()
         for n, d in level:
@@ -246,27 +247,34 @@ def neighborhood_levels(nodes, dirs, table: dict[int, int], k: int, min_count: i
                     nxt.add(s)
         kseen |= set(new_k)
         seen |= nxt
-        out.append((sorted(level), new_k))
+        yield sorted(level), new_k
         level = nxt
-    return out
+
+
+def neighborhood_levels(nodes, dirs, table: dict[int, int], k: int, min_count: int):
+    """Every level of the complete neighbourhood: [(level entries, {canonical k-mer: count} new in its expansion)]."""
+    return list(iter_levels(nodes, dirs, table, k, min_count))
 
 
 def neighborhood(nodes, dirs, table: dict[int, int], k: int, min_count: int, max_levels: int = 0, cap: int = 1 << 62,
                  fringe_cap: int = 1 << 62, levels=None):
     """shk_neighborhood's whole-level rule (include/shk.h) → (kmers, counts, fringe_nodes, fringe_dirs, levels_done) as
-    lists.  `levels`: neighborhood_levels of the same seeds, if the caller has it already."""
-    if levels is None:
-        levels = neighborhood_levels(nodes, dirs, table, k, min_count)
-    if levels and len(levels[0][0]) > fringe_cap:
+    lists.  `levels`: neighborhood_levels of the same seeds, if the caller has it already; otherwise the levels are
+    walked only as far as the rule looks (one past the last it expands)."""
+    it = iter(levels) if levels is not None else iter_levels(nodes, dirs, table, k, min_count)
+    cur = next(it, None)
+    if cur is not None and len(cur[0]) > fringe_cap:
         raise ValueError("more distinct seeds than fringe_cap")
     K, L = {}, 0
-    while L < len(levels) and not (max_levels and L >= max_levels):
-        nk = len(K) + len(levels[L][1])
-        nf = len(levels[L + 1][0]) if L + 1 < len(levels) else 0
+    while cur is not None and not (max_levels and L >= max_levels):
+        nxt = next(it, None)
+        nk = len(K) + len(cur[1])
+        nf = len(nxt[0]) if nxt is not None else 0
         if nk > cap or nf > fringe_cap:
             break
-        K.update(levels[L][1])
+        K.update(cur[1])
         L += 1
-    fringe = levels[L][0] if L < len(levels) else []
+        cur = nxt
+    fringe = cur[0] if cur is not None else []
     ks = sorted(K)
     return ks, [K[x] for x in ks], [n for n, _ in fringe], [d for _, d in fringe], L

@@ -11,6 +11,12 @@ life of two contexts) and 10-30 operations — ingests by every route, explicit 
 (count 0 and near-saturating ones too), resets, and between them every observation the ABI has — which are applied
 to the engine and to the model in lockstep.  Every comparison is integer equality.
 
+shk_neighborhood and shk_pcr_extend are drawn by a second generator and interleaved, about one to five operations
+(the first draw is what it was before they existed: tests/test_lane_model_cpu.py holds a hash of it).  They are
+observations that settle, clear and may grow the table on their way (shk.h: "the table is not touched"): what is checked
+is their own answer and, since the sequence goes on over a model they did not touch, every finalize, histogram column,
+counter and export after them.
+
 SHK_SEQ_SEEDS: how many seeds; SHK_SEQ_FIRST: the first one.  A failing case prints its seed, its context and the
 operations applied so far (name + parameters): SHK_SEQ_FIRST=<seed> SHK_SEQ_SEEDS=1 replays it.  `dry_run(seed)`
 runs the draw and the model without an engine (tests/test_lane_model_cpu.py checks the default set's coverage so)."""
@@ -20,16 +26,20 @@ import numpy as np
 import pytest
 
 import sharkmer_amd as sa
-from lane_model import LaneModel, ModelError, NO_READS, U32_MAX
+from lane_model import LaneModel, ModelError, NO_READS, SHK_ERR_STATE, U32_MAX
 from test_gpu_fuzz import HOOKS, draw_reads
 
 pytestmark = pytest.mark.gpu
 
 # 96 seeds from 0.  Positions and kinds follow from the draw alone and are checked without an engine
-# (tests/test_lane_model_cpu.py): the rarest, the poison step and the saturated count, are met by 8 seeds each.  The
-# routes need the engine: on an MI355X the rarest, `histo_rows` (a job whose one fresh page pass is finalized as it
-# is, on a FLAG_TIMING seed), was met by no seed of the first 48 and is met by seeds 25, 75 and 94; `grow` by 11 seeds.
-# The 96 sequences take 54 s there, against 430 s for the rest of the GPU suite.
+# (tests/test_lane_model_cpu.py): the rarest, "neighborhood after a zero-count insert", is met by seeds 17, 47 and 55,
+# "neighborhood on a saturated count" by 12, 19, 24, 49, 73 and 93, the poison step and the saturated count by 8 seeds
+# each.  The routes need the engine: on an MI355X the rarest, `histo_rows` (a job whose one fresh page pass is
+# finalized as it is, on a FLAG_TIMING seed), was met by no seed of the first 48 and is met by seeds 25, 75 and 94 —
+# a neighborhood call in front of such a finalize drops the fused histogram on purpose (seed 25's first job has one),
+# and the three seeds still meet the route; `grow` by 11 seeds, `extend` by 16.
+# The 96 sequences (and the fixed ones below) take 59.3 s there with the two graph observations, 53.9 s without them
+# (the parent of the change that added them, same machine, same day), against 430 s for the rest of the GPU suite.
 DEFAULT_SEEDS = 96
 OVERRIDDEN = "SHK_SEQ_SEEDS" in os.environ or "SHK_SEQ_FIRST" in os.environ
 N_SEEDS = int(os.environ.get("SHK_SEQ_SEEDS", str(DEFAULT_SEEDS)))
@@ -42,8 +52,14 @@ MAX_BASES = 2_000_000
 PRE_FINALIZE = ("n_reads_ingested", "n_bases_read", "n_bases_ingested")
 POSITIONS = ("observation before the first finalize", "observation between two ingests",
              "ingest after finalize, then a second finalize", "reset followed by a job", "finalize twice",
-             "poison step", "two-context life", "zero-count insert", "saturated count")
-ROUTES = ("direct", "scatter", "pages", "histo", "histo_rows", "grow", "insert", "lookup", "export")
+             "poison step", "two-context life", "zero-count insert", "saturated count",
+             "neighborhood between two ingests", "neighborhood before the first finalize",
+             "neighborhood after a zero-count insert", "neighborhood on a saturated count", "pcr_extend after a reset",
+             "neighborhood refused on a multi-device context")
+ROUTES = ("direct", "scatter", "pages", "histo", "histo_rows", "grow", "insert", "lookup", "export", "extend")
+GRAPH_OPS = ("neighborhood", "pcr_extend")
+GRAPH_SEED = 7_000_000   # the second generator: GRAPH_SEED + the sequence seed
+GRAPH_RATE = 0.2
 RECORD = {"positions": {}, "routes": {}, "kinds": {}, "seeds": set()}   # item → the seeds that met it
 
 
@@ -61,6 +77,19 @@ def draw_context(rng, kind=None):
 
 
 def draw_plan(seed):
+    """→ (contexts, hooks, operations): draw_base_plan's, with the graph observations of the second generator after
+    about every fifth operation (name + sub-seed: nodes and parameters come from the model's table when applied)."""
+    contexts, hooks, base = draw_base_plan(seed)
+    rng = np.random.default_rng(GRAPH_SEED + seed)
+    ops = []
+    for op in base:
+        ops.append(op)
+        if rng.random() < GRAPH_RATE:
+            ops.append((GRAPH_OPS[int(rng.random() < 0.3)], dict(r=int(rng.integers(1, 1 << 30)))))
+    return contexts, hooks, ops
+
+
+def draw_base_plan(seed):
     """→ (contexts, hooks, operations).  Operations are (name, parameters); data comes from the sub-seeds in the
     parameters when the operation is applied.  What a context kind does not take is left out HERE: packed and device
     buffers on a multi-device context, near-saturating counts on more than one lane (Σ lane counts would differ from
@@ -175,23 +204,27 @@ class Positions:
     def fresh(self, after_reset=False):
         self.n_final = 0          # successful finalizes since create / reset
         self.nonempty = False
-        self.trail = ""           # i: ingest, o: observation, f: finalize — since create / reset
+        self.trail = ""           # i: ingest, o: observation, n: a neighborhood call, f: finalize — since create / reset
         self.after_reset = after_reset
 
     def ingest(self):
         self.nonempty = True
         last = self.trail.rfind("i")
-        if last >= 0 and "o" in self.trail[last + 1:]:
+        if last >= 0 and ("o" in self.trail[last + 1:] or "n" in self.trail[last + 1:]):
             self.met("observation between two ingests")
+        if last >= 0 and "n" in self.trail[last + 1:]:
+            self.met("neighborhood between two ingests")
         self.trail += "i"
 
     def mutate(self):
         self.nonempty = True
 
-    def observe(self):
+    def observe(self, neighborhood=False):
         if self.nonempty and self.n_final == 0:
             self.met("observation before the first finalize")
-        self.trail += "o"
+            if neighborhood:
+                self.met("neighborhood before the first finalize")
+        self.trail += "n" if neighborhood else "o"
 
     def finalized(self):
         self.n_final += 1
@@ -238,9 +271,21 @@ class Sequence:
         else:
             raise AssertionError(self.report("%s did not fail; expected %r" % (name, text)))
 
+    def refused(self, e, name, *a, **kw):
+        """The model refused with one of the ABI's codes (include/shk.h): so must the engine."""
+        assert e.code is not None, self.report("the model refused: %s" % e)
+        if not self.live:
+            return
+        try:
+            getattr(self.eng, name)(*a, **kw)
+        except sa.ShkError as got:
+            assert got.code == e.code, self.report("%s: code %d (%s), expected %d" % (name, got.code, got.msg, e.code))
+        else:
+            raise AssertionError(self.report("%s did not fail; expected code %d" % (name, e.code)))
+
     def open(self, ctx):
         self.ctx, self.multi = ctx, ctx["kind"] != "plain"
-        self.model = LaneModel(self.orc, ctx["k"], ctx["chunks"], ctx["histo_max"])
+        self.model = LaneModel(self.orc, ctx["k"], ctx["chunks"], ctx["histo_max"], multi_device=self.multi)
         self.pos.fresh()
         self.met_here.add("kind " + ("multi-device" if self.multi else "plain"))
         if self.live:
@@ -485,6 +530,86 @@ class Sequence:
             for g, w, p in zip(got, want, primers):
                 for what, a, b in zip(("k-mers", "counts", "levels", "level hits"), g, w):
                     self.same(a, b, "primer_kmers %s of %s" % (what, p))
+        self.pos.observe()
+
+    def graph_seeds(self, rng):
+        """(node, dir) seeds cut from k-mers the model holds — a zero-count key and a saturated one among them when
+        there are any — as the prefix or the suffix of either orientation, and a few nodes from nowhere."""
+        k = self.ctx["k"]
+        keys, counts = self.model.export()
+        mask = (1 << (2 * (k - 1))) - 1
+        picked, marks = [], []
+        if len(keys):
+            picked += keys[rng.integers(0, len(keys), size=5)].tolist()
+            for special, where in ((0, "neighborhood after a zero-count insert"), (U32_MAX, "neighborhood on a saturated count")):
+                at = np.flatnonzero(counts == special)
+                if len(at):
+                    picked.append(int(keys[at[int(rng.integers(0, len(at)))]]))
+                    marks.append(where)
+        nodes = []
+        for x in picked:
+            if rng.random() < 0.5:
+                x = int(revcomp(np.array([x], dtype=np.uint64), k)[0])
+            nodes.append(x >> 2 if rng.random() < 0.5 else x & mask)
+        nodes += [int(x) for x in rng.integers(0, mask + 1, size=2, dtype=np.uint64)]
+        dirs = [int(d) for d in rng.integers(1, 4, size=len(nodes))]
+        return nodes, dirs, counts, marks
+
+    def op_neighborhood(self, r):
+        """shk_neighborhood in the middle of a job, bounded so that the model stays cheap: at most 6 levels, 4096 k-mers
+        and a level of 4096.  The model is not touched; the sequence goes on."""
+        rng = np.random.default_rng(r)
+        nodes, dirs, counts, marks = self.graph_seeds(rng) if self.ctx["k"] >= 2 else ([0], [1], np.zeros(0, np.uint32), [])
+        n_distinct = len({(n, b) for n, d in zip(nodes, dirs) for b in (1, 2) if d & b})
+        a = dict(min_count=int(rng.choice([0, 1, 2, int(counts[int(rng.integers(0, len(counts)))]) if len(counts) else 3, U32_MAX])),
+                 max_levels=int(rng.integers(1, 7)), cap=int(rng.choice([0, 1, 64, 4096])),
+                 fringe_cap=int(rng.choice([n_distinct, 64, 4096])))
+        self.done[-1] = ("neighborhood", dict(r=r, nodes=nodes, dirs=dirs, **a))
+        try:
+            want = self.model.neighborhood(nodes, dirs, **a)
+        except ModelError as e:   # a multi-device context (SHK_ERR_STATE), k = 1 (SHK_ERR_BAD_ARG)
+            self.refused(e, "neighborhood", nodes, dirs, **a)
+            if e.code == SHK_ERR_STATE:
+                self.met_here.add("neighborhood refused on a multi-device context")
+            return
+        got = self.call("neighborhood", nodes, dirs, **a)
+        if self.live:
+            for what, g, w in zip(("k-mers", "counts", "fringe nodes", "fringe dirs", "levels done"), got, want):
+                self.same(g, w, "neighborhood %s" % what)
+        self.met_here.update(marks)
+        self.pos.observe(neighborhood=True)
+
+    def op_pcr_extend(self, r):
+        """shk_pcr_extend from the model's top-count k-mers in both orientations, the node budget small."""
+        rng = np.random.default_rng(r)
+        k = self.ctx["k"]
+        keys, counts = self.model.export()
+        top = np.argsort(counts, kind="stable")[::-1][:8]
+        sets = []
+        for part in (top[0::2], top[1::2]):
+            ks, cs = keys[part].copy(), counts[part].copy()
+            flip = rng.random(len(ks)) < 0.5
+            if k >= 2:
+                ks[flip] = revcomp(ks[flip], k)
+            sets.append((ks, cs))
+        a = dict(min_count=int(rng.integers(1, 4)), table_min_count=int(rng.choice([1, 2])),
+                 high_coverage_ratio=float(rng.choice([1.5, 10.0])), max_num_nodes=int(rng.choice([50, 1200])),
+                 sweep=bool(rng.random() < 0.5))
+        self.done[-1] = ("pcr_extend", dict(r=r, fwd=sets[0][0].tolist(), rev=sets[1][0].tolist(), **a))
+        try:
+            want, used, steps = self.model.pcr_extend(sets[0], sets[1], **a)
+        except ModelError as e:
+            self.refused(e, "pcr_extend", sets[0], sets[1], **a)
+            return
+        got = self.call("pcr_extend", sets[0], sets[1], **a)
+        if self.live:
+            self.same(got.node_sub_kmers, want.sub_kmer, "pcr_extend nodes")
+            self.same(got.node_flags, want.flags(), "pcr_extend node flags")
+            for i, (what, g) in enumerate((("sources", got.edge_src), ("targets", got.edge_tgt), ("counts", got.edge_counts))):
+                self.same(g, np.array([e[i] for e in want.edges], dtype=np.uint32), "pcr_extend edge %s" % what)
+            self.same((got.found_path, got.threshold_used, got.steps_run), (want.found_path, used, steps), "pcr_extend outcome")
+        if self.pos.after_reset and self.pos.nonempty:
+            self.met_here.add("pcr_extend after a reset")
         self.pos.observe()
 
     def op_filter_reads(self, r):

@@ -3,13 +3,15 @@ whatever the model and the oracle's one-shot driver share — histogram columns,
 equal when the model is fed the same reads in any number of calls, and its insert must be KmerCounts::insert with
 the saturating cases of test_oracle_kat.py.  No GPU."""
 import gzip
+import hashlib
 import json
 import os
 
 import numpy as np
 import pytest
 
-from lane_model import LaneModel, ModelError, U32_MAX
+import pcr_ref
+from lane_model import LaneModel, ModelError, SHK_ERR_BAD_ARG, SHK_ERR_STATE, U32_MAX
 from test_gpu_fuzz import draw_reads
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -178,3 +180,95 @@ def test_the_sweep_s_default_draw_covers_every_position_and_kind(orc):
             met.setdefault(item, []).append(seed)
     missing = [p for p in seq.POSITIONS + ("kind plain", "kind multi-device") if len(met.get(p, ())) < 2]
     assert not missing, (missing, met)
+
+
+def test_the_graph_observations_leave_the_first_draw_as_it_was():
+    """shk_neighborhood and shk_pcr_extend come from a second generator: without them draw_plan(seed) is, for every
+    default seed, the plan the sweep drew before they existed (the hash is of that draw's repr)."""
+    import test_gpu_sequences as seq
+    h = hashlib.sha256()
+    n_graph = 0
+    for seed in range(seq.DEFAULT_SEEDS):
+        contexts, hooks, ops = seq.draw_plan(seed)
+        base = [o for o in ops if o[0] not in seq.GRAPH_OPS]
+        assert (contexts, hooks, base) == seq.draw_base_plan(seed)
+        n_graph += len(ops) - len(base)
+        h.update(repr((contexts, hooks, base)).encode())
+    assert seq.DEFAULT_SEEDS == 96 and h.hexdigest() == "4a017601738b1b7d2396d1b9a9f163ef8f466ec8ee85b189defd05e8fa99e9a3"
+    assert n_graph > 2 * seq.DEFAULT_SEEDS  # (about one to five operations of 10-30)
+
+
+def test_neighborhood_and_pcr_extend_over_the_merged_table(orc):
+    """The model's two graph calls are tests/pcr_ref.py over the oracle's merged table after the same ingests (in
+    several calls, three lanes), whatever the bounds; an insert with count 0 leaves a key that stops a walk."""
+    _, bases, offsets = draw_reads(np.random.default_rng(12))
+    n = min(len(offsets) - 1, 1500)
+    bases, offsets = bases[:int(offsets[n])], offsets[:n + 1]
+    k, chunks = 15, 3
+    run = orc.run_batch(bases, offsets, k, chunks, 50)
+    keys, counts = run.merged().export()
+    table = pcr_ref.table_dict(keys, counts)
+    model = LaneModel(orc, k, chunks, 50)
+    for a in range(0, n, 700):
+        model.ingest_reads(bases, offsets[a:min(a + 700, n) + 1])
+    mask = (1 << (2 * (k - 1))) - 1
+    top = np.argsort(counts, kind="stable")[::-1][:12]
+    nodes = [int(x) >> 2 for x in keys[top[:6]]] + [int(x) & mask for x in keys[top[6:]]] + [5, mask]
+    dirs = [1 + i % 3 for i in range(len(nodes))]
+    walked = 0
+    for kw in (dict(min_count=1), dict(min_count=2, max_levels=3), dict(min_count=1, cap=64), dict(min_count=1, cap=0),
+               dict(min_count=1, fringe_cap=64, max_levels=6), dict(min_count=int(counts.max())), dict(min_count=0, max_levels=1)):
+        got = model.neighborhood(nodes, dirs, **kw)
+        want = pcr_ref.neighborhood(nodes, dirs, table, k, kw["min_count"], kw.get("max_levels", 0), kw.get("cap", 1 << 16),
+                                    kw.get("fringe_cap", 1 << 16), levels=pcr_ref.neighborhood_levels(nodes, dirs, table, k, kw["min_count"]))
+        assert got == want, kw
+        walked += got[4]
+    assert walked > 10
+    some = np.flatnonzero(counts >= 2)  # (the top counts of these reads are low-complexity runs: few neighbours)
+    some = some[::len(some) // 8][:8]
+    fwd = (keys[some[:4]], counts[some[:4]])
+    rev = (keys[some[4:]], counts[some[4:]])
+    for kw in (dict(min_count=2, table_min_count=2, high_coverage_ratio=10.0, max_num_nodes=1200, sweep=True),
+               dict(min_count=2, table_min_count=1, high_coverage_ratio=1.5, max_num_nodes=50, sweep=False)):
+        g, used, steps = model.pcr_extend(fwd, rev, **kw)
+        w, wused, wsteps = pcr_ref.pcr_extend(fwd, rev, table, k, **kw)
+        assert (g.sub_kmer, g.flags(), g.edges, g.found_path, used, steps) == (w.sub_kmer, w.flags(), w.edges, w.found_path, wused, wsteps)
+        assert len(g.sub_kmer) > 8 and g.edges
+    # a key of count 0 is in the table and is no edge
+    x = int(keys[top[0]])
+    node = x >> 2
+    first = model.neighborhood([node], [1], 1, max_levels=1)
+    assert x in first[0] or int(pcr_ref.revcomp(x, k)) in first[0]
+    zeroed = LaneModel(orc, k, 1, 50)
+    zeroed.insert(0, [x], [0])
+    assert zeroed.neighborhood([node], [1], 0, max_levels=1) == ([], [], [], [], 1)
+    assert list(zeroed.export()[1]) == [0]
+
+
+def test_the_graph_calls_sum_lanes_with_saturation_and_refuse_as_the_abi_does(orc):
+    """Two lanes whose counts add past 2^32 − 1: the count reported is 2^32 − 1, accepted at min_count 2^32 − 1 where
+    2^32 − 2 is not.  A multi-device context is SHK_ERR_STATE, k = 1 and more seeds than fringe_cap SHK_ERR_BAD_ARG."""
+    k = 5
+    m = LaneModel(orc, k, 2, 10)
+    x, y = 0b0001101100, 0b0110110001  # ACGTA → CGTAC, canonical both (AC… < GT…)
+    assert x <= pcr_ref.revcomp(x, k) and y <= pcr_ref.revcomp(y, k) and (x & 0xFF) == y >> 2
+    m.insert(0, [x, y], [U32_MAX - 1, U32_MAX - 2])
+    m.insert(1, [x], [7])
+    assert m.neighborhood([x >> 2], [1], U32_MAX) == ([x], [U32_MAX], [], [], 2)
+    assert m.neighborhood([x >> 2], [1], U32_MAX - 2)[:2] == ([x, y], [U32_MAX, U32_MAX - 2])
+    g, used, steps = m.pcr_extend(([x], [U32_MAX]), ([], []), min_count=U32_MAX, table_min_count=1, high_coverage_ratio=10.0,
+                                  max_num_nodes=100, sweep=False)
+    assert g.edges == [(0, 1, U32_MAX)] and (used, steps) == (U32_MAX, 1)  # (y, at 2^32 − 3, is below the threshold)
+    with pytest.raises(ModelError) as e:
+        m.neighborhood([1, 2], [3, 1], 1, fringe_cap=2)
+    assert e.value.code == SHK_ERR_BAD_ARG
+    with pytest.raises(ModelError) as e:
+        m.neighborhood([1 << 8], [1], 1)
+    assert e.value.code == SHK_ERR_BAD_ARG
+    for call in (lambda mm: mm.neighborhood([0], [1], 1), lambda mm: mm.pcr_extend(([], []), ([], []))):
+        with pytest.raises(ModelError) as e:
+            call(LaneModel(orc, k, 2, 10, multi_device=True))
+        assert e.value.code == SHK_ERR_STATE and "multi-device context" in str(e.value)
+        with pytest.raises(ModelError) as e:
+            call(LaneModel(orc, 1, 2, 10))
+        assert e.value.code == SHK_ERR_BAD_ARG

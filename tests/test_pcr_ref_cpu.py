@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import nb_cases
 import pcr_ref as ref
 import primer_ref
 
@@ -139,3 +140,44 @@ def test_neighborhood_whole_level_rule():
     assert ref.neighborhood([0b1111], [2], table, 3, 1) == ([1, 6], [10, 8], [], [], 5)  # TT backwards: the same k-mers
     with pytest.raises(ValueError):
         ref.neighborhood([0, 1], [1, 1], table, 3, 1, fringe_cap=1)
+
+
+# ---- the crafted tables of tests/nb_cases.py ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(nb_cases.CASES))
+def test_crafted_cases_have_their_designed_level_sizes(name):
+    """Each builder's table, walked by the model alone, has exactly the level sizes it was designed to have (chains
+    that met by chance would change them: the builders' generator seed is the first at which this passes) — so the
+    GPU comparison on the same table (tests/test_gpu_nb_edges.py) is one at that shape.  Canonical keys only."""
+    case = nb_cases.CASES[name]()
+    table = nb_cases.merged_table(case.inserts)
+    assert all(x <= ref.revcomp(x, case.k) for x in table) and len(case.seeds) == len(case.dirs)
+    assert all(0 <= lane < max(case.chunks, 1) and len(ks) == len(cs) for lane, ks, cs in case.inserts)
+    lv = ref.neighborhood_levels(case.seeds, case.dirs, table, case.k, case.min_count)
+    assert [len(e) for e, _ in lv] == case.sizes, name
+    if case.hand_over:  # the level where the search changes kernels: the first past the narrow kernel's size, or back
+        a, b = case.sizes[case.hand_over - 1], case.sizes[case.hand_over]
+        assert (a > nb_cases.NARROW) != (b > nb_cases.NARROW)
+
+
+def test_crafted_lane_counts_meet_their_thresholds_only_summed():
+    """The lanes table: no single lane's count of a chain-A key reaches the threshold, the sum is exactly it, chain B's
+    is one short; two keys saturate over lanes, one is 2^32 − 2, one was inserted with count 0 and nothing else."""
+    case = nb_cases.lanes()[0]
+    table = nb_cases.merged_table(case.inserts)
+    per_lane = [dict(zip(ks, cs)) for _, ks, cs in case.inserts]
+    hist = sorted(table.values())
+    assert hist.count(nb_cases.LANES_MIN) == 5 and hist.count(nb_cases.LANES_MIN - 1) == 5
+    for x, c in table.items():
+        if c in (nb_cases.LANES_MIN, nb_cases.LANES_MIN - 1):
+            assert max(l.get(x, 0) for l in per_lane) < nb_cases.LANES_MIN and sum(l.get(x, 0) for l in per_lane) == c
+    assert hist.count(nb_cases.U32_MAX) == 2 and hist.count(nb_cases.U32_MAX - 1) == 1 and hist.count(0) == 1
+    for x, c in table.items():
+        if c == nb_cases.U32_MAX:
+            assert sum(l.get(x, 0) for l in per_lane) > nb_cases.U32_MAX > max(l.get(x, 0) for l in per_lane)
+
+
+def test_growth_inserts_are_out_of_every_canonical_lookup_s_reach():
+    lane, keys, counts = nb_cases.growth_inserts()
+    assert len(keys) == len(counts) == 300_000 and lane == 0
+    assert all(x > ref.revcomp(x, 7) for x in set(keys))
