@@ -382,6 +382,36 @@ int fail_invalid_char(shk_ctx *c, uint64_t bad, bool poison = true) {
                   #expr);                                                                   \
   } while (0)
 
+// A step that answers an SHK_* code: anything but SHK_OK ends the caller with it.
+#define SHK_TRY(expr)                \
+  do {                               \
+    const int rc__ = (expr);         \
+    if (rc__ != SHK_OK) return rc__; \
+  } while (0)
+
+// Opens the calls that a multi-device context does not offer (the order of the two checks and the text are behaviour).
+int single_device_only(shk_ctx *c) {
+  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
+  if (!c) return SHK_ERR_BAD_ARG;
+  return SHK_OK;
+}
+
+// One call's arrays in a grow-only device buffer: take<T>(n) per array, in order (offsets, 16-byte aligned), one ensure()
+// of the total, then at<T>(offset).  Arrays taken one after the other are adjacent up to that padding.
+struct Scratch {
+  DevBuf &buf;
+  size_t total = 0;
+  template <typename T>
+  size_t take(size_t n) {
+    const size_t off = total;
+    total += (n * sizeof(T) + 15) & ~(size_t)15;
+    return off;
+  }
+  hipError_t ensure() { return buf.ensure(total); }
+  template <typename T>
+  T *at(size_t off) const { return (T *)((uint8_t *)buf.p + off); }
+};
+
 // HIP-event timer around one launch.  Back-to-back launches can CHAIN: a timer constructed with
 // chain = true starts from the end event of the previous timer (c->chain_ev, valid only if nothing
 // else has been enqueued on the stream since) instead of recording an event of its own — every
@@ -475,6 +505,32 @@ int tb_fresh(shk_ctx *c) {
   if (!c->tb_stale) return SHK_OK;
   c->tb_stale = false;
   return fill_state(c, c->tb, false);
+}
+
+// How a call that reads the table, or hands it to a peer, begins: on the context's device, with every launch looked at
+// and repaired and the table cleared if that was still owed.  A call that begins otherwise says why where it does.
+int table_read_begin(shk_ctx *c) {
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));
+  return tb_fresh(c);
+}
+
+// An owned range given as a share (shk_set_owner_share) follows the table when it grows.
+void own_resolve(shk_ctx *c) {
+  if (!c->own_share_n) return;
+  const uint64_t per = (1ull << c->tb.log_pages) / c->own_share_n;
+  c->own_p0 = per * c->own_share_id;
+  c->own_p1 = per * (c->own_share_id + 1);
+}
+
+// The slots [s0, s1) a scan of this context reads: the owned pages if a range is set, else the whole table.
+struct SlotRange {
+  uint64_t s0, s1;
+};
+SlotRange owned_slots(shk_ctx *c) {
+  if (!c->own_set) return {0, c->tb.cap};
+  own_resolve(c);
+  return {c->own_p0 << PAGE_LOG, c->own_p1 << PAGE_LOG};
 }
 
 static void free_table(TableRef &t) {
@@ -576,10 +632,7 @@ SpillRef spill_ref(DevBuf &b, uint64_t cap) {
 // found its page full, and from then on the table at least doubles per round.
 int drain_spill(shk_ctx *c, uint64_t spill_cap) {
   DevBuf *cur = &c->spillA, *nxt = &c->spillB;
-  if (c->h_stats->spill_count > 0) {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
+  if (c->h_stats->spill_count > 0) SHK_TRY(tb_fresh(c));
   for (uint32_t round = 0; c->h_stats->spill_count > 0; ++round) {
     uint64_t n = c->h_stats->spill_count;
     if (n > spill_cap)
@@ -633,10 +686,7 @@ constexpr uint64_t MAX_SUB_BASES = 1ull << 28;  // bases per counting launch (bo
 int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs,
                 uint64_t n_bases, int64_t lane_fixed, XchgOut *xo = nullptr, uint64_t off_bias = 0) {
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
-  if (!(xo && xo->late_settle)) {
-    int rc0 = settle_light(c);  // the previous launch's spill list / scratch must be done with
-    if (rc0 != SHK_OK) return rc0;
-  }
+  if (!(xo && xo->late_settle)) SHK_TRY(settle_light(c));  // the previous launch's spill list / scratch must be done with
   c->finalized = c->hist_ready = false;
   c->chain_from_mark = false;
   const uint64_t g0 = c->n_reads_read;
@@ -735,10 +785,7 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
     uint64_t sub_kmers_ub = tn * TILE_T;
     b.tile_first = ta;
     b.tile_count = tn;
-    if (ta) {
-      int rcs = settle_light(c);
-      if (rcs != SHK_OK) return rcs;
-    }
+    if (ta) SHK_TRY(settle_light(c));
     int rc = ta ? ensure_capacity(c, c->cfg.table_capacity_hint ? 0 : (sub_kmers_ub / 4) >> c->owner_bits) : SHK_OK;
     if (rc != SHK_OK) return rc;
     rc = count_tiles(c, b, sub_kmers_ub, /*prezeroed=*/ta == 0);
@@ -1644,16 +1691,10 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
     if (!defer) {
       const uint32_t l_lo = all_lanes ? 0u : lane, l_hi = all_lanes ? NL : lane + 1;
       const bool fresh = c->tb_stale && rec32 && l_lo == 0 && l_hi == c->n_lanes && !env_int("SHK_NO_FRESH", 0);
-      if (!fresh) {
-        int rcf = tb_fresh(c);
-        if (rcf != SHK_OK) return rcf;
-      }
+      if (!fresh) SHK_TRY(tb_fresh(c));
       FusedHist fh{};
       const bool fuse = rec32 && fresh && fused_hist_wanted(c);
-      if (fuse) {
-        int rch = fused_hist_prepare(c, n_pages, &fh);
-        if (rch != SHK_OK) return rch;
-      }
+      if (fuse) SHK_TRY(fused_hist_prepare(c, n_pages, &fh));
       ScopedTimer t(c, SHK_K_PAGES, /*chain=*/true);
       if (rec32) {
         launch_pages32(c, fresh, fuse, n_pages, 0u, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cursor, dpg.cap,
@@ -1706,10 +1747,7 @@ static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, boo
     path = count_path(c, sub_kmers_ub, b.tiles != nullptr);  // a flush may have grown the table
     if (path == PATH_DEFER && !c->acc_cur.p) return fail(c, SHK_ERR_INVARIANT, "accumulation regions missing");
   }
-  if (path != PATH_DEFER && c->acc_active) {  // the other paths work on the table itself
-    int rc = settle(c);
-    if (rc != SHK_OK) return rc;
-  }
+  if (path != PATH_DEFER && c->acc_active) SHK_TRY(settle(c));  // the other paths work on the table itself
   // (deferred: the partition launches of a window and its page pass append to one spill list)
   const uint64_t spill_cap = path == PATH_DEFER ? std::max<uint64_t>(c->acc_spill_cap, sub_kmers_ub) : sub_kmers_ub;
   if (path == PATH_DEFER) c->acc_spill_cap = spill_cap;
@@ -1730,10 +1768,7 @@ static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, boo
       hipLaunchKernelGGL(k_scan, dim3(grid_for(b.tile_count, 1, 4096)), dim3(WG), 0, c->stream, b,
                          c->d_stats, c->d_lane_bases);
     }
-    {
-      int rcf = tb_fresh(c);
-      if (rcf != SHK_OK) return rcf;
-    }
+    SHK_TRY(tb_fresh(c));
     ScopedTimer t(c, SHK_K_DIRECT);
     hipLaunchKernelGGL(k_direct, dim3(grid_for(b.tile_count, 1, 256 * 8)), dim3(WG), 0, c->stream, b,
                        c->tb, c->d_stats, sp);
@@ -1746,14 +1781,6 @@ static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, boo
 }
 
 // Outcome of the last counting launch, h_stats already read back and synchronised.
-// An owned range given as a share (shk_set_owner_share) follows the table when it grows.
-static void own_resolve(shk_ctx *c) {
-  if (!c->own_share_n) return;
-  const uint64_t per = (1ull << c->tb.log_pages) / c->own_share_n;
-  c->own_p0 = per * c->own_share_id;
-  c->own_p1 = per * (c->own_share_id + 1);
-}
-
 static int settle_checked(shk_ctx *c) {
   c->unsettled = false;
   if (c->h_stats->bad != ~0ull) return fail_invalid_char(c, c->h_stats->bad);
@@ -1844,10 +1871,7 @@ static int flush_acc(shk_ctx *c) {
   // instead of a fill of the table beforehand that it would then read back: 26 GB of configs[2]'s traffic)
   const bool fresh8 = c->tb_stale && !c->acc_rec32 && NL == c->n_lanes && !env_int("SHK_NO_FRESH", 0) && env_int("SHK_FRESH8", 1) != 0;
   if (fresh8) fused_drop(c);
-  if (!fresh && !fresh8) {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
+  if (!fresh && !fresh8) SHK_TRY(tb_fresh(c));
   // pages per launch so that even if every record of every one of them spilled the list would hold them
   const uint64_t per_page_ub = (uint64_t)NL * c->acc_cap;  // (every lane's regions of a page in one launch, either record width)
   uint64_t ppg = std::max<uint64_t>(spill_cap / std::max<uint64_t>(per_page_ub, 1), 1);
@@ -1868,10 +1892,7 @@ static int flush_acc(shk_ctx *c) {
   // (only the flush a finalize asked for: a window that ends on its budget is followed by another, whose pass would
   // overtake this one's histogram — configs[4]'s share, ten lanes: 4.5 ms of fold for nothing)
   const bool fuse = fresh && c->acc_rec32 && c->flush_for_finalize && fused_hist_wanted(c);
-  if (fuse) {
-    int rch = fused_hist_prepare(c, n_pages, &fh);
-    if (rch != SHK_OK) return rch;
-  }
+  if (fuse) SHK_TRY(fused_hist_prepare(c, n_pages, &fh));
   for (uint64_t p0 = 0; p0 < n_pages; p0 += ppg) {
     const uint32_t gp = (uint32_t)std::min<uint64_t>(ppg, n_pages - p0);
     {  // every lane's regions of a page in one launch (the keys stay in LDS over the lanes), either record width
@@ -2549,15 +2570,11 @@ int shk_ingest_packed(shk_ctx *c, const uint8_t *packed, const uint32_t *nmask, 
 }
 
 int shk_pack_reads_device(shk_ctx *c, const void *d_bases, uint64_t n_bases, void *d_packed, void *d_nmask) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
   if (n_bases == 0) return SHK_OK;
   if (!d_bases || !d_packed || !d_nmask) return fail(c, SHK_ERR_BAD_ARG, "null buffer");
   HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);  // (stats->bad below belongs to this call alone)
-    if (rcs != SHK_OK) return rcs;
-  }
+  SHK_TRY(settle(c));  // (stats->bad below belongs to this call alone)
   hipLaunchKernelGGL(k_pack, dim3((uint32_t)((n_bases + 32ull * WG - 1) / (32ull * WG))), dim3(WG), 0, c->stream,
                      (const uint8_t *)d_bases, n_bases, (uint8_t *)d_packed, (uint32_t *)d_nmask, c->d_stats);
   int rc = read_stats(c);
@@ -2573,8 +2590,7 @@ int shk_pack_reads_device(shk_ctx *c, const void *d_bases, uint64_t n_bases, voi
 }
 
 int shk_unpack_reads_device(shk_ctx *c, const void *d_packed, const void *d_nmask, uint64_t n_bases, void *d_bases) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
   if (n_bases == 0) return SHK_OK;
   if (!d_bases || !d_packed || !d_nmask) return fail(c, SHK_ERR_BAD_ARG, "null buffer");
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -2595,10 +2611,7 @@ int shk_ingest_packed_device(shk_ctx *c, const void *d_packed, const void *d_nma
     HIPC(c, hipStreamSynchronize(c->stream));
   }
   HIPC(c, c->pk_ascii.ensure(n_bases + 64));
-  if (n_bases) {
-    int rc = shk_unpack_reads_device(c, d_packed, d_nmask, n_bases, c->pk_ascii.p);
-    if (rc != SHK_OK) return rc;
-  }
+  if (n_bases) SHK_TRY(shk_unpack_reads_device(c, d_packed, d_nmask, n_bases, c->pk_ascii.p));
   return ingest_core(c, (const uint8_t *)c->pk_ascii.p, (const uint64_t *)d_offsets, n_seqs, n_bases, -1);
 }
 
@@ -2631,17 +2644,13 @@ int shk_insert_counts(shk_ctx *c, uint32_t chunk_id, const uint64_t *kmers, cons
     return SHK_OK;
   }
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
+  // (not table_read_begin: a failure that was still pending is reported before the arguments are looked at, also when
+  // there is nothing to insert, and only a call that does insert has the table cleared)
+  SHK_TRY(settle(c));
   if (chunk_id >= c->n_lanes) return fail(c, SHK_ERR_BAD_ARG, "chunk_id out of range");
   if (n == 0) return SHK_OK;
   HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
+  SHK_TRY(tb_fresh(c));
   c->finalized = c->hist_ready = false;
   const uint64_t kmax = c->cfg.k >= 32 ? ~0ull : ((1ull << (2 * c->cfg.k)) - 1);
   for (uint64_t i = 0; i < n; ++i) {
@@ -2649,12 +2658,13 @@ int shk_insert_counts(shk_ctx *c, uint32_t chunk_id, const uint64_t *kmers, cons
                                      (unsigned long long)kmers[i], c->cfg.k);
     if (counts[i] == 0) c->zero_count_keys = true;  // counting.rs:152-154 creates the entry all the same
   }
-  int rc = ensure_capacity(c, n);
-  if (rc != SHK_OK) return rc;
+  SHK_TRY(ensure_capacity(c, n));
   c->n_inserted += n;
-  HIPC(c, c->misc.ensure(n * 12));
-  uint64_t *dk = (uint64_t *)c->misc.p;
-  uint32_t *dc = (uint32_t *)((uint8_t *)c->misc.p + n * 8);
+  Scratch m{c->misc};
+  const size_t o_k = m.take<uint64_t>(n), o_c = m.take<uint32_t>(n);
+  HIPC(c, m.ensure());
+  uint64_t *dk = m.at<uint64_t>(o_k);
+  uint32_t *dc = m.at<uint32_t>(o_c);
   HIPC(c, hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemcpyAsync(dc, counts, n * 4, hipMemcpyHostToDevice, c->stream));
   HIPC(c, c->spillA.ensure(n * 16));
@@ -2665,8 +2675,7 @@ int shk_insert_counts(shk_ctx *c, uint32_t chunk_id, const uint64_t *kmers, cons
     hipLaunchKernelGGL(k_insert, dim3(grid_for(n, WG, 4096)), dim3(WG), 0, c->stream, dk,
                        (const uint32_t *)nullptr, dc, n, chunk_id, c->tb, c->d_stats, sp);
   }
-  rc = read_stats(c);
-  if (rc != SHK_OK) return rc;
+  SHK_TRY(read_stats(c));
   return drain_spill(c, n);
 }
 
@@ -2685,8 +2694,8 @@ static int xchg_late_settle(shk_ctx *c, bool late, bool absorbs_since) {
 // The exchange scatter, in one call (the outcome waited for) or in two (shk_xchg_scatter_begin / _end).
 static int xchg_scatter_call(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases, uint64_t layout_bases,
                              void **d_records, void **d_cursors, shk_xchg_layout *layout, uint64_t *n_foreign_spilled, bool two_calls) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !d_records || !d_cursors || !layout) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  if (!d_records || !d_cursors || !layout) return SHK_ERR_BAD_ARG;
   HIPC(c, hipSetDevice(c->cfg.device));
   if (c->xs_pending) return fail(c, SHK_ERR_STATE, "an exchange scatter is begun and not ended (shk_xchg_scatter_end)");
   if (n_bases > SHK_XCHG_MAX_BASES || (layout_bases && layout_bases > SHK_XCHG_MAX_BASES))
@@ -2701,10 +2710,7 @@ static int xchg_scatter_call(shk_ctx *c, const void *d_bases, const void *d_offs
   // touch, and it is in front of this scatter on the stream).  Waiting for it before launching cost a host round trip
   // with the GPU idle every round; the scatter's own read of the outcome, below, sees the absorb's too.
   xo.late_settle = c->unsettled && c->acc_active && !c->poisoned && env_int("SHK_XCHG_LATE_SETTLE", 1) != 0;
-  if (!xo.late_settle) {
-    int rcs = settle_light(c);
-    if (rcs != SHK_OK) return rcs;
-  }
+  if (!xo.late_settle) SHK_TRY(settle_light(c));
   std::swap(c->xbuf, c->xbuf_alt);
   std::swap(c->part_meta, c->part_meta_alt);
   int rc = ingest_core(c, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_seqs, n_bases, c->xchg_lane_fixed, &xo);
@@ -2734,8 +2740,7 @@ int shk_xchg_scatter_begin(shk_ctx *c, const void *d_bases, const void *d_offset
 }
 
 int shk_xchg_scatter_end(shk_ctx *c, uint64_t *n_foreign_spilled) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
   if (!c->xs_pending) return fail(c, SHK_ERR_STATE, "no exchange scatter is begun (shk_xchg_scatter_begin)");
   c->xs_pending = false;
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -2750,8 +2755,8 @@ int shk_xchg_scatter_end(shk_ctx *c, uint64_t *n_foreign_spilled) {
 
 int shk_xchg_wide_scatter_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                                  void **d_kmers, void **d_lanes, uint64_t *counts) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !d_kmers || !d_lanes || !counts) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  if (!d_kmers || !d_lanes || !counts) return SHK_ERR_BAD_ARG;
   if (!c->is_share()) return fail(c, SHK_ERR_STATE, "not an owner share (shk_config.n_owners = 0: say 1 for a share that is the whole key space)");
   HIPC(c, hipSetDevice(c->cfg.device));
   if (n_bases > SHK_XCHG_MAX_BASES) return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)SHK_XCHG_MAX_BASES);
@@ -2772,8 +2777,8 @@ int shk_xchg_feasible(shk_ctx *c) {
 }
 
 int shk_xchg_absorb(shk_ctx *c, const void *d_records, const void *d_cursors, const shk_xchg_layout *lay) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !lay) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  if (!lay) return SHK_ERR_BAD_ARG;
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   HIPC(c, hipSetDevice(c->cfg.device));
   PartGeom g = part_geom(c);
@@ -2840,8 +2845,8 @@ int shk_xchg_absorb(shk_ctx *c, const void *d_records, const void *d_cursors, co
 }
 
 int shk_xchg_spill(shk_ctx *c, void **d_kmers, void **d_lanes, void **d_counts, uint64_t *n) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !n) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  if (!n) return SHK_ERR_BAD_ARG;
   HIPC(c, hipSetDevice(c->cfg.device));
   int rc = read_stats(c);
   if (rc != SHK_OK) return rc;
@@ -2854,8 +2859,7 @@ int shk_xchg_spill(shk_ctx *c, void **d_kmers, void **d_lanes, void **d_counts, 
 }
 
 int shk_xchg_spill_clear(shk_ctx *c) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
   HIPC(c, hipMemsetAsync(&c->d_stats->scratch[0], 0, sizeof(unsigned long long), c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
@@ -2925,8 +2929,7 @@ static int insert_list_paged(shk_ctx *c, const uint64_t *d_kmers, const uint32_t
 }
 
 int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, const void *d_counts, uint64_t n) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   HIPC(c, hipSetDevice(c->cfg.device));
   if (d_kmers && insert_list_paged_ok(c, d_counts, n) && (d_lanes || c->n_lanes == 1)) {
@@ -2939,14 +2942,8 @@ int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, cons
     }
     if (rcp != SHK_ERR_STATE) return rcp;  // (SHK_ERR_STATE: not this way after all — the general path below)
   }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
+  SHK_TRY(tb_fresh(c));
+  SHK_TRY(settle(c));
   if (n == 0) return SHK_OK;
   if (!d_kmers) return fail(c, SHK_ERR_BAD_ARG, "null k-mers");
   c->finalized = c->hist_ready = false;
@@ -3010,10 +3007,7 @@ static int finalize_scan(shk_ctx *c) {
   }
   // the histogram the (one) fresh page pass left behind, if the table is still as that pass wrote it
   const bool fused = c->fused_valid && !c->tb_stale && !c->own_set && !c->zero_count_keys && c->fused_pages == (1u << c->tb.log_pages);
-  if (!fused) {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
+  if (!fused) SHK_TRY(tb_fresh(c));
   const uint32_t n_cols = c->cfg.chunks;
   const uint64_t hlen = c->cfg.histo_max + 2;
   if (fused) {
@@ -3041,12 +3035,7 @@ static int finalize_scan(shk_ctx *c) {
     c->hist_dirty = false;
   }
   // d_hist and d_tot are zero here
-  uint64_t s0 = 0, s1 = c->tb.cap;
-  if (c->own_set) {
-    own_resolve(c);
-    s0 = c->own_p0 << PAGE_LOG;
-    s1 = c->own_p1 << PAGE_LOG;
-  }
+  const auto [s0, s1] = owned_slots(c);
   uint32_t lds_bins = n_cols ? std::max<uint32_t>(32, 16384 / n_cols) : 0;
   if (lds_bins > hlen) lds_bins = (uint32_t)hlen;
   if (n_cols && (uint64_t)lds_bins * n_cols * 4 > 65536) lds_bins = 65536 / 4 / n_cols;
@@ -3204,10 +3193,7 @@ int shk_get_counters(shk_ctx *c, shk_counters *o) {
   if (!c || !o) return SHK_ERR_BAD_ARG;
   if (c->group) return group_counters(c, o);
   HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
+  SHK_TRY(settle(c));
   memset(o, 0, sizeof *o);
   for (auto v : c->lane_reads) o->n_reads_ingested += v;
   o->n_bases_read = c->n_bases_read;
@@ -3267,949 +3253,6 @@ int shk_reset_timings(shk_ctx *c) {
   memset(&c->timings, 0, sizeof c->timings);
   c->job_idx = 0;
   c->timing_now = true;
-  return SHK_OK;
-}
-
-int shk_export_table(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
-  if (!c || !n_out) return SHK_ERR_BAD_ARG;
-  if (c->group) {  // the shares are disjoint: one after the other
-    uint64_t at = 0;
-    for (uint32_t d = 0; d < c->group->D; ++d) {
-      uint64_t n = 0;
-      const uint64_t room = at < cap ? cap - at : 0;
-      const int rc = shk_export_table(c->group->ctx[d], kmers ? kmers + std::min(at, cap) : nullptr,
-                                      counts ? counts + std::min(at, cap) : nullptr, room, &n);
-      if (rc != SHK_OK) return group_fail(c, c->group, rc, d);
-      at += n;
-    }
-    *n_out = at;
-    return SHK_OK;
-  }
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, c->misc.ensure(cap * 12 + 16));
-  uint8_t *p = (uint8_t *)c->misc.p;
-  unsigned long long *dn = (unsigned long long *)p;
-  uint64_t *dk = (uint64_t *)(p + 16);
-  uint32_t *dc = (uint32_t *)(p + 16 + cap * 8);
-  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
-  uint64_t s0 = 0, s1 = c->tb.cap;
-  if (c->own_set) {
-    own_resolve(c);
-    s0 = c->own_p0 << PAGE_LOG;
-    s1 = c->own_p1 << PAGE_LOG;
-  }
-  {
-    ScopedTimer t(c, SHK_K_EXPORT);
-    hipLaunchKernelGGL(k_export, dim3(grid_for(s1 - s0, WG * 4, 4096)), dim3(WG), 0, c->stream, c->tb, s0,
-                       s1, dk, dc, cap, dn);
-  }
-  unsigned long long n = 0;
-  HIPC(c, hipMemcpyAsync(&n, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  *n_out = n;
-  uint64_t m = std::min<uint64_t>(n, cap);
-  if (m && kmers) HIPC(c, hipMemcpy(kmers, dk, m * 8, hipMemcpyDeviceToHost));
-  if (m && counts) HIPC(c, hipMemcpy(counts, dc, m * 4, hipMemcpyDeviceToHost));
-  return SHK_OK;
-}
-
-int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical) {
-  if (c && c->group) {  // exactly one share owns a k-mer; the others answer 0
-    std::vector<uint32_t> part(n);
-    std::fill(counts, counts + n, 0u);
-    for (uint32_t d = 0; d < c->group->D; ++d) {
-      const int rc = shk_lookup(c->group->ctx[d], kmers, part.data(), n, canonical);
-      if (rc != SHK_OK) return group_fail(c, c->group, rc, d);
-      for (uint64_t i = 0; i < n; ++i) counts[i] += part[i];
-    }
-    return SHK_OK;
-  }
-  if (!c) return SHK_ERR_BAD_ARG;
-  if (n == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, c->misc.ensure(n * 12));
-  uint64_t *dk = (uint64_t *)c->misc.p;
-  uint32_t *dc = (uint32_t *)((uint8_t *)c->misc.p + n * 8);
-  HIPC(c, hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_lookup, dim3((uint32_t)((n + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, dk, dc,
-                       n, canonical, (int)c->cfg.k);
-  }
-  HIPC(c, hipMemcpyAsync(counts, dc, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return SHK_OK;
-}
-
-int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds, uint32_t min_count,
-                     uint32_t max_levels, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
-                     uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
-                     uint32_t *levels_done) {
-  if (!c || !n_out || !n_fringe || !levels_done || (n_seeds && (!nodes || !dirs))) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this context is an owner share (n_owners > 1)");
-  const uint32_t k = c->cfg.k;
-  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
-  if ((cap && (!kmers || !counts)) || (fringe_cap && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
-  if (cap > (1ull << 32) || fringe_cap > (1ull << 32))
-    return fail(c, SHK_ERR_BAD_ARG, "cap %llu / fringe_cap %llu above 2^32", (unsigned long long)cap, (unsigned long long)fringe_cap);
-  const uint64_t node_mask = (1ull << (2 * (k - 1))) - 1ull;
-  // level 0: the distinct (node, dir) pairs, as entries node << 1 | (0 forward, 1 reverse)
-  std::vector<uint64_t> seeds;
-  seeds.reserve(n_seeds);
-  for (uint64_t i = 0; i < n_seeds; ++i) {
-    if (dirs[i] == 0 || dirs[i] > 3) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: dir %u is not 1 (forward), 2 (reverse) or 3 (both)", (unsigned long long)i, dirs[i]);
-    if (nodes[i] > node_mask) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: node 0x%llx is not a %u-mer", (unsigned long long)i, (unsigned long long)nodes[i], k - 1);
-    if (dirs[i] & 1) seeds.push_back(nodes[i] << 1);
-    if (dirs[i] & 2) seeds.push_back(nodes[i] << 1 | 1ull);
-  }
-  std::sort(seeds.begin(), seeds.end());
-  seeds.erase(std::unique(seeds.begin(), seeds.end()), seeds.end());
-  if (seeds.size() > fringe_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "%llu distinct seeds do not fit fringe_cap %llu", (unsigned long long)seeds.size(), (unsigned long long)fringe_cap);
-  *n_out = 0;
-  *n_fringe = 0;
-  *levels_done = 0;
-  if (seeds.empty()) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  // An accepted k-mer has two orientations and an orientation one successor per dir: through a level that fits, the
-  // visited set never holds more than the seeds and 4·cap entries, the k-mer set cap.  Both at most half full then; a
-  // set that fills up (probes are bounded) belongs to a level that does not fit and is dropped.
-  auto pow2_above = [](uint64_t n) {
-    uint64_t s = 16;
-    while (s < n) s <<= 1;
-    return s;
-  };
-  const uint64_t vis_slots = pow2_above(2 * (seeds.size() + 4 * cap) + 2), kset_slots = pow2_above(2 * cap + 2);
-  const uint64_t fc = std::max<uint64_t>(fringe_cap, 1), kc = std::max<uint64_t>(cap, 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return at;
-  };
-  const size_t o_ctl = take(sizeof(NbCtl)), o_vis = take(vis_slots * 8), o_kset = take(kset_slots * 8);
-  const size_t o_l0 = take(fc * 8), o_l1 = take(fc * 8), o_km = take(kc * 8), o_ct = take(kc * 4);
-  HIPC(c, c->misc.ensure(off));
-  uint8_t *p = (uint8_t *)c->misc.p;
-  NbCtl *dctl = (NbCtl *)(p + o_ctl);
-  NbRef nb{};
-  nb.vis = (uint64_t *)(p + o_vis);
-  nb.kset = (uint64_t *)(p + o_kset);
-  nb.vis_mask = vis_slots - 1;
-  nb.kset_mask = kset_slots - 1;
-  nb.list[0] = (uint64_t *)(p + o_l0);
-  nb.list[1] = (uint64_t *)(p + o_l1);
-  nb.kmers = (uint64_t *)(p + o_km);
-  nb.counts = (uint32_t *)(p + o_ct);
-  nb.cap = cap;
-  nb.fringe_cap = fringe_cap;
-  nb.min_count = std::max(min_count, 1u);
-  nb.max_levels = max_levels;
-  nb.k = (int)k;
-  NbCtl h{};
-  h.cur_n = seeds.size();
-  HIPC(c, hipMemsetAsync(nb.vis, 0xFF, (o_l0 - o_vis), c->stream));  // both sets ← EMPTY
-  HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(nb.list[0], seeds.data(), seeds.size() * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_EXTEND);
-    hipLaunchKernelGGL(k_nb_seed, dim3((uint32_t)((seeds.size() + WG - 1) / WG)), dim3(WG), 0, c->stream, nb,
-                       (uint64_t)seeds.size(), dctl);
-  }
-  // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
-  while (h.status == NB_RUN || h.status == NB_WIDE) {
-    if (h.cur_n == 0) {
-      h.status = NB_COMPLETE;
-      break;
-    }
-    if (max_levels && h.levels_done >= max_levels) {
-      h.status = NB_LIMIT;
-      break;
-    }
-    if (h.cur_n <= NB_NARROW) {
-      {
-        ScopedTimer t(c, SHK_K_EXTEND);
-        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
-      }
-      HIPC(c, hipGetLastError());
-      HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-      HIPC(c, hipStreamSynchronize(c->stream));
-      continue;
-    }
-    const unsigned long long k_start = h.k_n;
-    {
-      ScopedTimer t(c, SHK_K_EXTEND);
-      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
-                         dctl, h.cur_sel, (uint64_t)h.cur_n);
-    }
-    HIPC(c, hipGetLastError());
-    NbCtl r{};
-    HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (r.set_full || r.k_n > cap || r.next_n > fringe_cap) {  // the level did not fit: the k-mer list back to its start
-      h.k_n = k_start;
-      h.status = NB_OVERFLOW;
-      break;
-    }
-    h.k_n = r.k_n;
-    h.cur_n = r.next_n;
-    h.cur_sel ^= 1u;
-    h.levels_done += 1;
-    h.next_n = 0;
-    h.status = NB_RUN;
-    HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));  // (h is a pageable source: the copy has read it)
-  }
-  // the arrival order of the appends is not part of the result: sorted
-  const uint64_t nk = h.k_n, nf = h.status == NB_COMPLETE ? 0 : h.cur_n;
-  std::vector<uint64_t> hk(nk), hf(nf);
-  std::vector<uint32_t> hc(nk);
-  if (nk) {
-    HIPC(c, hipMemcpy(hk.data(), nb.kmers, nk * 8, hipMemcpyDeviceToHost));
-    HIPC(c, hipMemcpy(hc.data(), nb.counts, nk * 4, hipMemcpyDeviceToHost));
-  }
-  if (nf) HIPC(c, hipMemcpy(hf.data(), nb.list[h.cur_sel], nf * 8, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> order(nk);
-  for (uint64_t i = 0; i < nk; ++i) order[i] = (uint32_t)i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
-  for (uint64_t i = 0; i < nk; ++i) {
-    kmers[i] = hk[order[i]];
-    counts[i] = hc[order[i]];
-  }
-  std::sort(hf.begin(), hf.end());
-  for (uint64_t i = 0; i < nf; ++i) {
-    fringe_nodes[i] = hf[i] >> 1;
-    fringe_dirs[i] = (uint8_t)(1u << (hf[i] & 1ull));
-  }
-  *n_out = nk;
-  *n_fringe = nf;
-  *levels_done = h.levels_done;
-  return SHK_OK;
-}
-
-int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
-                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev, const shk_pcr_extend_params *p,
-                   uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes, uint32_t *edge_src,
-                   uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges, uint32_t *found_path,
-                   uint32_t *threshold_used, uint32_t *steps_run) {
-  if (!c || !p || !n_nodes || !n_edges || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
-  if ((n_fwd && (!fwd_kmers || !fwd_counts)) || (n_rev && (!rev_kmers || !rev_counts))) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this context is an owner share (n_owners > 1)");
-  const uint32_t k = c->cfg.k;
-  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
-  const uint64_t kmask = ~0ull >> (64 - 2 * k);
-  for (uint64_t i = 0; i < n_fwd; ++i)
-    if (fwd_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "forward primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
-  for (uint64_t i = 0; i < n_rev; ++i)
-    if (rev_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "reverse primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
-  PcrGraph g;
-  std::string msg;
-  const int rc = pcr_extend_run(c, k, fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev, *p, &g, threshold_used,
-                                steps_run, &msg);
-  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood's own text stands)
-  *n_nodes = g.sub_kmer.size();
-  *n_edges = g.esrc.size();
-  *found_path = g.found_path ? 1u : 0u;
-  if (*n_nodes > node_cap || *n_edges > edge_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "graph of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu",
-                (unsigned long long)*n_nodes, (unsigned long long)*n_edges, (unsigned long long)node_cap, (unsigned long long)edge_cap);
-  if ((*n_nodes && (!node_sub_kmers || !node_flags)) || (*n_edges && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
-  std::copy(g.sub_kmer.begin(), g.sub_kmer.end(), node_sub_kmers);
-  std::copy(g.flags.begin(), g.flags.end(), node_flags);
-  std::copy(g.esrc.begin(), g.esrc.end(), edge_src);
-  std::copy(g.etgt.begin(), g.etgt.end(), edge_tgt);
-  std::copy(g.ecount.begin(), g.ecount.end(), edge_counts);
-  return SHK_OK;
-}
-
-int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,
-                    uint32_t min_count, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
-  if (c && c->group) {  // the shares are disjoint: one after the other
-    uint64_t at = 0;
-    for (uint32_t d = 0; d < c->group->D; ++d) {
-      uint64_t n = 0;
-      const uint64_t room = at < cap ? cap - at : 0;
-      const int rc = shk_find_oligos(c->group->ctx[d], oligos, n_oligos, oligo_len, min_count, kmers ? kmers + std::min(at, cap) : nullptr,
-                                     counts ? counts + std::min(at, cap) : nullptr, room, &n);
-      if (rc != SHK_OK) return group_fail(c, c->group, rc, d);
-      at += n;
-    }
-    if (n_out) *n_out = at;
-    return SHK_OK;
-  }
-  if (!c || !n_out) return SHK_ERR_BAD_ARG;
-  const uint32_t k = c->cfg.k;
-  // the reference asserts these (primers.rs:169-186)
-  if (n_oligos == 0 || !oligos) return fail(c, SHK_ERR_BAD_ARG, "find_oligos_in_kmers called with no oligos");
-  if (!(oligo_len > 0 && oligo_len < k))
-    return fail(c, SHK_ERR_BAD_ARG, "oligo length %u out of range for k=%u (must be 1..k-1); trim must be < k",
-                oligo_len, k);
-  if (n_oligos > 3000) return fail(c, SHK_ERR_BAD_ARG, "too many oligos (%u > 3000)", n_oligos);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  auto rc_of = [](uint64_t x, int len) {  // reverse complement of a len-base value (host side)
-    uint64_t r = 0;
-    for (int i = 0; i < len; ++i) {
-      r = (r << 2) | (3 - (x & 3));
-      x >>= 2;
-    }
-    return r;
-  };
-  std::vector<uint64_t> fwd(n_oligos), rc(n_oligos);
-  for (uint32_t i = 0; i < n_oligos; ++i) {
-    fwd[i] = oligos[i] << (2 * (k - oligo_len));  // primers.rs:189-192
-    rc[i] = rc_of(oligos[i], (int)oligo_len);      // primers.rs:206-209
-  }
-  std::sort(fwd.begin(), fwd.end());
-  std::sort(rc.begin(), rc.end());
-  HIPC(c, c->misc.ensure((size_t)n_oligos * 16 + cap * 12 + 64));
-  uint8_t *p = (uint8_t *)c->misc.p;
-  unsigned long long *dn = (unsigned long long *)p;
-  uint64_t *dsets = (uint64_t *)(p + 16);
-  uint64_t *dk = dsets + 2 * (size_t)n_oligos;
-  uint32_t *dc = (uint32_t *)(dk + cap);
-  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
-  HIPC(c, hipMemcpyAsync(dsets, fwd.data(), (size_t)n_oligos * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dsets + n_oligos, rc.data(), (size_t)n_oligos * 8, hipMemcpyHostToDevice, c->stream));
-  uint64_t s0 = 0, s1 = c->tb.cap;
-  if (c->own_set) {
-    own_resolve(c);
-    s0 = c->own_p0 << PAGE_LOG;
-    s1 = c->own_p1 << PAGE_LOG;
-  }
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_find_oligos, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG), (size_t)n_oligos * 16,
-                       c->stream, c->tb, s0, s1, (int)k, (int)oligo_len, min_count, (const uint64_t *)dsets,
-                       (const uint64_t *)(dsets + n_oligos), n_oligos, dk, dc, cap, dn);
-  }
-  unsigned long long n = 0;
-  HIPC(c, hipMemcpyAsync(&n, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // also keeps fwd/rc alive until their copies ran
-  *n_out = n;
-  uint64_t m = std::min<uint64_t>(n, cap);
-  if (m && kmers) HIPC(c, hipMemcpy(kmers, dk, m * 8, hipMemcpyDeviceToHost));
-  if (m && counts) HIPC(c, hipMemcpy(counts, dc, m * 4, hipMemcpyDeviceToHost));
-  return SHK_OK;
-}
-
-namespace {
-
-// One k_primer_scan pass over c's slots (the owned pages of an owner share): the per-(primer, level) hits (dev's
-// order) and, when they fit in `room`, the records.  *n_total = records the pass produced (> room: none returned).
-int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, std::vector<PrimerRec> *recs,
-                std::vector<uint64_t> *hits, uint64_t *n_total) {
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  const uint32_t n = (uint32_t)dev.size();
-  uint32_t stride = 1;  // LDS counters per primer: levels 0..max M
-  for (const PrimerDev &d : dev) stride = std::max(stride, d.M + 1);
-  // primers per launch: their table and counters in 48 KiB of LDS (three workgroups per CU)
-  const uint32_t per_launch = (48u << 10) / (uint32_t)(sizeof(PrimerDev) + 4 * stride);
-  const size_t hits_b = (size_t)n * SHK_PRIMER_LEVELS * 8, prim_b = (size_t)n * sizeof(PrimerDev);
-  HIPC(c, c->misc.ensure(16 + hits_b + prim_b + room * sizeof(PrimerRec)));
-  uint8_t *p = (uint8_t *)c->misc.p;
-  unsigned long long *dn = (unsigned long long *)p;
-  unsigned long long *dhits = (unsigned long long *)(p + 16);
-  PrimerDev *dprim = (PrimerDev *)(p + 16 + hits_b);
-  PrimerRec *drec = (PrimerRec *)(p + 16 + hits_b + prim_b);
-  HIPC(c, hipMemsetAsync(p, 0, 16 + hits_b, c->stream));
-  HIPC(c, hipMemcpyAsync(dprim, dev.data(), prim_b, hipMemcpyHostToDevice, c->stream));
-  uint64_t s0 = 0, s1 = c->tb.cap;
-  if (c->own_set) {
-    own_resolve(c);
-    s0 = c->own_p0 << PAGE_LOG;
-    s1 = c->own_p1 << PAGE_LOG;
-  }
-  for (uint32_t b = 0; b < n; b += per_launch) {
-    const uint32_t nb = std::min(per_launch, n - b);
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_primer_scan, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG),
-                       (size_t)nb * (sizeof(PrimerDev) + 4 * stride), c->stream, c->tb, s0, s1, (int)c->cfg.k,
-                       (const PrimerDev *)(dprim + b), nb, b, stride, drec, (uint64_t)room, dn, dhits);
-  }
-  HIPC(c, hipGetLastError());
-  unsigned long long nt = 0;
-  hits->assign((size_t)n * SHK_PRIMER_LEVELS, 0);
-  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(hits->data(), dhits, hits_b, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps dev alive until its copy ran)
-  *n_total = nt;
-  recs->clear();
-  if (nt <= room && nt) {
-    recs->resize(nt);
-    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
-  }
-  return SHK_OK;
-}
-
-}  // namespace
-
-int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
-                     uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
-  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
-  if (n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
-  const uint32_t k = c->cfg.k;
-  // preprocess_primer_by_mismatch of every direction before any scan (primers.rs:440-450), then the conversion
-  // check of the searched ones (their first round, primers.rs:383-393)
-  std::vector<PrimerPlan> plans(n_primers);
-  std::string msg;
-  for (uint32_t i = 0; i < n_primers; ++i) {
-    const int rc = primer_plan(&primers[i], k, &plans[i], &msg);
-    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
-  }
-  for (uint32_t i = 0; i < n_primers; ++i) {
-    const int rc = primer_check_chars(plans[i], &msg);
-    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
-  }
-  uint64_t need = 0;
-  for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
-  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
-  if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
-  if (level_hits) std::fill(level_hits, level_hits + (size_t)n_primers * SHK_PRIMER_LEVELS, 0ull);
-  std::vector<uint32_t> who;  // searched primer j = primers[who[j]]
-  std::vector<PrimerDev> dev;
-  for (uint32_t i = 0; i < n_primers; ++i)
-    if (plans[i].scanned()) {
-      const PrimerPlan &pl = plans[i];
-      who.push_back(i);
-      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, pl.min_count, 0});
-    }
-  const uint32_t n = (uint32_t)dev.size();
-  std::vector<shk_ctx *> parts;  // a multi-device context: its shares are disjoint, the answer is the top of the union
-  if (c->group)
-    for (uint32_t d = 0; d < c->group->D; ++d) parts.push_back(c->group->ctx[d]);
-  else
-    parts.push_back(c);
-  auto part_fail = [&](int rc, uint32_t d) { return c->group ? group_fail(c, c->group, rc, d) : rc; };
-  std::vector<PrimerRec> all;
-  std::vector<uint64_t> hits((size_t)n * SHK_PRIMER_LEVELS, 0);
-  if (n) {
-    const int env_room = env_int("SHK_PRIMER_CANDIDATES", 1 << 18);
-    const uint64_t room = (uint64_t)std::max(env_room, 1);
-    std::vector<std::vector<uint64_t>> part_hits(parts.size());
-    std::vector<uint64_t> part_n(parts.size());
-    std::vector<PrimerRec> recs;
-    for (uint32_t d = 0; d < parts.size(); ++d) {
-      const int rc = primer_pass(parts[d], dev, room, &recs, &part_hits[d], &part_n[d]);
-      if (rc != SHK_OK) return part_fail(rc, d);
-      all.insert(all.end(), recs.begin(), recs.end());
-      for (size_t j = 0; j < hits.size(); ++j) hits[j] += part_hits[d][j];
-    }
-    // The record buffer overflowed: the counts are complete, so each primer's cut level is known — the first level
-    // at which its hits reach max_kmers.  Nothing above it can be selected; rerun keeping levels ≤ cut, sized exactly.
-    std::vector<PrimerDev> cut = dev;
-    for (uint32_t j = 0; j < n; ++j) {
-      uint64_t acc = 0;
-      for (uint32_t m = 0; m <= dev[j].M; ++m) {
-        acc += hits[(size_t)j * SHK_PRIMER_LEVELS + m];
-        if (acc >= plans[who[j]].max_kmers) {
-          cut[j].M = m;
-          break;
-        }
-      }
-    }
-    for (uint32_t d = 0; d < parts.size(); ++d) {
-      if (part_n[d] <= room) continue;
-      uint64_t exact = 0;
-      for (uint32_t j = 0; j < n; ++j)
-        for (uint32_t m = 0; m <= cut[j].M; ++m) exact += part_hits[d][(size_t)j * SHK_PRIMER_LEVELS + m];
-      std::vector<uint64_t> h2;
-      uint64_t n2 = 0;
-      const int rc = primer_pass(parts[d], cut, exact, &recs, &h2, &n2);
-      if (rc != SHK_OK) return part_fail(rc, d);
-      if (n2 != exact)
-        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu",
-                    (unsigned long long)n2, (unsigned long long)exact);
-      all.insert(all.end(), recs.begin(), recs.end());
-    }
-  }
-  // Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
-  // sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
-  // here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
-  // and two entries never yield the same k-mer because the table holds canonical k-mers only — so the reference's
-  // "already found at a lower level" filter (primers.rs:398-403) never drops anything.
-  std::vector<uint64_t> first(n + 1, 0);
-  for (const PrimerRec &r : all) ++first[(r.tag >> 8) + 1];
-  for (uint32_t j = 0; j < n; ++j) first[j + 1] += first[j];
-  std::vector<PrimerRec> by(all.size());
-  {
-    std::vector<uint64_t> at(first.begin(), first.end() - 1);
-    for (const PrimerRec &r : all) by[at[r.tag >> 8]++] = r;
-  }
-  auto before = [](const PrimerRec &a, const PrimerRec &b) {
-    const uint32_t la = a.tag & 0xFF, lb = b.tag & 0xFF;
-    if (la != lb) return la < lb;
-    if (a.count != b.count) return a.count > b.count;
-    return a.kmer < b.kmer;
-  };
-  uint64_t o = 0;
-  uint32_t j = 0;
-  for (uint32_t i = 0; i < n_primers; ++i) {
-    offsets[i] = o;
-    if (j >= n || who[j] != i) continue;
-    PrimerRec *b = by.data() + first[j], *e = by.data() + first[j + 1];
-    const uint64_t take = std::min<uint64_t>(plans[i].max_kmers, (uint64_t)(e - b));
-    std::partial_sort(b, b + take, e, before);
-    for (uint64_t t = 0; t < take; ++t, ++o) {
-      kmers[o] = b[t].kmer;
-      counts[o] = b[t].count;
-      levels[o] = (uint8_t)(b[t].tag & 0xFF);
-    }
-    if (level_hits) std::copy(hits.begin() + (size_t)j * SHK_PRIMER_LEVELS, hits.begin() + (size_t)(j + 1) * SHK_PRIMER_LEVELS,
-                              level_hits + (size_t)i * SHK_PRIMER_LEVELS);
-    ++j;
-  }
-  offsets[n_primers] = o;
-  return SHK_OK;
-}
-
-int shk_filter_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
-                     const uint64_t *primer_kmers, uint64_t n_kmers, uint8_t *out_matches) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_filter_reads(c->group->ctx[0], bases, offsets, n_seqs, primer_kmers, n_kmers, out_matches);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || (n_seqs && (!offsets || !out_matches))) return SHK_ERR_BAD_ARG;
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  const uint32_t k = c->cfg.k;
-  // the union of the primer k-mers (read_filter.rs:24-41) as an open-addressing set at load ≤ 1/2
-  uint64_t cap = 16;
-  while (cap < 2 * n_kmers) cap <<= 1;
-  if (cap > (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "primer k-mer set too large");
-  std::vector<uint64_t> set(cap, ~0ull);
-  for (uint64_t j = 0; j < n_kmers; ++j) {
-    const uint64_t key = primer_kmers[j];
-    if (2 * k < 64 && (key >> (2 * k)) != 0)
-      return fail(c, SHK_ERR_BAD_ARG, "primer k-mer %llu does not fit %u bases", (unsigned long long)key, k);
-    for (uint64_t sl = set_hash(key) & (cap - 1);; sl = (sl + 1) & (cap - 1)) {
-      if (set[sl] == key) break;
-      if (set[sl] == ~0ull) {
-        set[sl] = key;
-        break;
-      }
-    }
-  }
-  const uint64_t n_bases = offsets[n_seqs];
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  HIPC(c, c->misc.ensure(cap * 8 + n_seqs));
-  uint64_t *dset = (uint64_t *)c->misc.p;
-  uint8_t *dout = (uint8_t *)c->misc.p + cap * 8;
-  {
-    int rcs = settle(c);  // the staging buffers may still feed a counting launch
-    if (rcs != SHK_OK) return rcs;
-  }
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dset, set.data(), cap * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_filter_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
-                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, n_seqs, (int)k,
-                       (const uint64_t *)dset, (uint32_t)(cap - 1), dout);
-  }
-  HIPC(c, hipMemcpyAsync(out_matches, dout, n_seqs, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `set` alive until its copy ran)
-  return SHK_OK;
-}
-
-int shk_kmers_from_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
-                         uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_kmers_from_reads(c->group->ctx[0], bases, offsets, n_seqs, kmers, kmers_cap, n_kmers, bad_byte);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || (n_seqs && (!offsets || !n_kmers || !bad_byte))) return SHK_ERR_BAD_ARG;
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  const uint32_t k = c->cfg.k;
-  // koff(i): every read gets room for the most k-mers it can yield
-  std::vector<uint64_t> koff(n_seqs + 1);
-  koff[0] = 0;
-  for (uint64_t i = 0; i < n_seqs; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
-    const uint64_t len = offsets[i + 1] - offsets[i];
-    koff[i + 1] = koff[i] + (len >= k ? len - k + 1 : 0);
-  }
-  const uint64_t n_total = koff[n_seqs];
-  if (n_total > kmers_cap || (n_total && !kmers))
-    return fail(c, SHK_ERR_BAD_ARG, "kmers_cap %llu is below the %llu k-mers these reads can yield",
-                (unsigned long long)kmers_cap, (unsigned long long)n_total);
-  const uint64_t n_bases = offsets[n_seqs];
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  const uint64_t o_koff = 0, o_kmers = (n_seqs + 1) * 8, o_n = o_kmers + (n_total + 1) * 8,
-                 o_bad = o_n + n_seqs * 4;
-  HIPC(c, c->misc.ensure(o_bad + n_seqs));
-  char *m = (char *)c->misc.p;
-  {
-    int rcs = settle(c);  // the staging buffers may still feed a counting launch
-    if (rcs != SHK_OK) return rcs;
-  }
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m + o_koff, koff.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_kmers_from_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
-                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p,
-                       (const uint64_t *)(m + o_koff), n_seqs, (int)k, (uint64_t *)(m + o_kmers),
-                       (uint32_t *)(m + o_n), (uint8_t *)(m + o_bad));
-  }
-  // a read's span is copied back whole; only its first n_kmers[i] entries mean anything
-  if (n_total) HIPC(c, hipMemcpyAsync(kmers, m + o_kmers, n_total * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(n_kmers, m + o_n, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(bad_byte, m + o_bad, n_seqs, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `koff` alive until its copy ran)
-  return SHK_OK;
-}
-
-int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);  // a pending spill may still grow the table
-    if (rcs != SHK_OK) return rcs;
-  }
-  if (n_pages) *n_pages = 1ull << c->tb.log_pages;
-  if (page_slots) *page_slots = PAGE_SLOTS;
-  if (n_lanes) *n_lanes = c->n_lanes;
-  return SHK_OK;
-}
-
-int shk_table_reserve_pages(shk_ctx *c, uint64_t n_pages) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  uint32_t lp = 0;
-  while ((1ull << lp) < n_pages) lp++;
-  c->finalized = c->hist_ready = false;
-  return grow_to(c, lp);
-}
-
-int shk_table_device_ptrs(shk_ctx *c, void **d_keys, void **d_vals) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (d_keys) *d_keys = c->tb.keys;
-  if (d_vals) *d_vals = c->tb.vals;
-  return SHK_OK;
-}
-
-int shk_merge_pages(shk_ctx *c, uint64_t p0, uint64_t p1, const void *d_keys, const void *d_vals,
-                    uint64_t vals_lane_stride) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  if (p1 <= p0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  c->finalized = c->hist_ready = false;
-  c->zero_count_keys = true;  // (a peer's table may hold keys inserted with count 0: keep reading the keys)
-  const uint64_t n_slots = (p1 - p0) << PAGE_LOG;
-  // worst case every peer key is new here
-  HIPC(c, c->spillA.ensure(n_slots * c->n_lanes * 16));
-  SpillRef sp = spill_ref(c->spillA, n_slots * c->n_lanes);
-  HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
-  {
-    ScopedTimer t(c, SHK_K_MERGE);
-    hipLaunchKernelGGL(k_merge, dim3(grid_for(n_slots, WG, 8192)), dim3(WG), 0, c->stream, c->tb,
-                       n_slots, vals_lane_stride, (const uint64_t *)d_keys, (const uint32_t *)d_vals,
-                       c->d_stats, sp, 0ull, ~0u);
-  }
-  int rc = read_stats(c);
-  if (rc != SHK_OK) return rc;
-  return drain_spill(c, n_slots * c->n_lanes);
-}
-
-int shk_owner_counts(shk_ctx *c, uint32_t n_owners, uint64_t *counts) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !counts || n_owners == 0) return SHK_ERR_BAD_ARG;
-  const uint64_t n_pages = 1ull << c->tb.log_pages;
-  if (n_pages % n_owners) return fail(c, SHK_ERR_BAD_ARG, "%llu pages do not split over %u owners",
-                                      (unsigned long long)n_pages, n_owners);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, c->misc.ensure((size_t)n_owners * 16));
-  unsigned long long *dc = (unsigned long long *)c->misc.p;
-  HIPC(c, hipMemsetAsync(dc, 0, (size_t)n_owners * 8, c->stream));
-  const uint32_t bpo = std::min<uint32_t>(1024, std::max<uint32_t>(16, 2048 / n_owners));  // blocks per owner
-  hipLaunchKernelGGL(k_owner_counts, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb,
-                     c->tb.cap / n_owners, bpo, dc);
-  HIPC(c, hipMemcpyAsync(counts, dc, (size_t)n_owners * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return SHK_OK;
-}
-
-int shk_compact_owners(shk_ctx *c, uint32_t n_owners, const uint64_t *seg_offsets, void *d_keys, void *d_vals,
-                       uint64_t vals_lane_stride, int32_t skip_owner) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !seg_offsets || n_owners == 0) return SHK_ERR_BAD_ARG;
-  const uint64_t n_pages = 1ull << c->tb.log_pages;
-  if (n_pages % n_owners) return fail(c, SHK_ERR_BAD_ARG, "%llu pages do not split over %u owners",
-                                      (unsigned long long)n_pages, n_owners);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, c->misc.ensure((size_t)n_owners * 16));
-  unsigned long long *doff = (unsigned long long *)c->misc.p, *dcur = doff + n_owners;
-  HIPC(c, hipMemcpyAsync(doff, seg_offsets, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dcur, 0, (size_t)n_owners * 8, c->stream));
-  const uint32_t bpo = std::min<uint32_t>(1024, std::max<uint32_t>(16, 2048 / n_owners));  // blocks per owner
-  hipLaunchKernelGGL(k_compact_owners, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb,
-                     c->tb.cap / n_owners, (const unsigned long long *)doff, dcur, (uint64_t *)d_keys,
-                     (uint32_t *)d_vals, vals_lane_stride, skip_owner < 0 ? ~0u : (uint32_t)skip_owner, bpo,
-                     (const unsigned long long *)nullptr, 0ull, (unsigned long long *)nullptr);
-  HIPC(c, hipStreamSynchronize(c->stream));  // the caller hands the buffers to a collective next
-  return SHK_OK;
-}
-
-int shk_compact_owners_packed(shk_ctx *c, uint32_t n_owners, const uint64_t *counts, void *d_buf, int32_t skip_owner) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !counts || n_owners == 0) return SHK_ERR_BAD_ARG;
-  const uint64_t n_pages = 1ull << c->tb.log_pages;
-  if (n_pages % n_owners) return fail(c, SHK_ERR_BAD_ARG, "%llu pages do not split over %u owners",
-                                      (unsigned long long)n_pages, n_owners);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  // device: [seg offsets (entries) × W][cursors × W][counts × W], staged through pinned memory
-  HIPC(c, c->misc.ensure((size_t)n_owners * 24));
-  HIPC(c, c->h_rebased[0].ensure((size_t)n_owners * 16));
-  unsigned long long *h = (unsigned long long *)c->h_rebased[0].p;
-  unsigned long long run = 0;
-  for (uint32_t o = 0; o < n_owners; ++o) {
-    h[o] = run;
-    h[n_owners + o] = counts[o];
-    run += counts[o];
-  }
-  unsigned long long *doff = (unsigned long long *)c->misc.p, *dcur = doff + n_owners, *dcnt = dcur + n_owners;
-  HIPC(c, hipMemcpyAsync(doff, h, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dcnt, h + n_owners, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dcur, 0, (size_t)n_owners * 8, c->stream));
-  const uint32_t bpo = std::min<uint32_t>(1024, std::max<uint32_t>(16, 2048 / n_owners));  // blocks per owner
-  hipLaunchKernelGGL(k_compact_owners, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb,
-                     c->tb.cap / n_owners, (const unsigned long long *)doff, dcur, (uint64_t *)d_buf,
-                     (uint32_t *)nullptr, 0ull, skip_owner < 0 ? ~0u : (uint32_t)skip_owner, bpo,
-                     (const unsigned long long *)dcnt, 0ull, (unsigned long long *)nullptr);
-  HIPC(c, hipGetLastError());
-  return SHK_OK;  // (asynchronous on the context's stream: run the collective on shk_stream())
-}
-
-int shk_compact_owners_fixed(shk_ctx *c, uint32_t n_owners, uint64_t capacity, void *d_buf, int32_t skip_owner) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || n_owners == 0 || capacity == 0 || !d_buf) return SHK_ERR_BAD_ARG;
-  const uint64_t n_pages = 1ull << c->tb.log_pages;
-  if (n_pages % n_owners) return fail(c, SHK_ERR_BAD_ARG, "%llu pages do not split over %u owners",
-                                      (unsigned long long)n_pages, n_owners);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  if (c->acc_active) {  // records still waiting for their page pass
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  // (Otherwise nothing is waited for: a counting launch nobody has looked at yet may have spilled records, in which
-  // case the table read here is incomplete — k_piece_headers sees that on the device and poisons every header, no
-  // rank merges anything, and the finalize that follows repairs the table before the exchange is repeated.)
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  HIPC(c, c->misc.ensure((size_t)n_owners * 24));
-  HIPC(c, c->h_rebased[0].ensure((size_t)n_owners * 16));
-  unsigned long long *h = (unsigned long long *)c->h_rebased[0].p;
-  for (uint32_t o = 0; o < n_owners; ++o) {
-    h[o] = (unsigned long long)o * capacity;  // every piece at its fixed place
-    h[n_owners + o] = capacity;
-  }
-  unsigned long long *doff = (unsigned long long *)c->misc.p, *dcur = doff + n_owners, *dcnt = dcur + n_owners;
-  const size_t piece_bytes = 8 + capacity * (8 + 4 * (size_t)c->n_lanes);
-  HIPC(c, hipMemcpyAsync(doff, h, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dcnt, h + n_owners, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dcur, 0, (size_t)n_owners * 8, c->stream));
-  // unused places read as EMPTY k-mers, which the merge skips
-  HIPC(c, hipMemsetAsync(d_buf, 0xFF, (size_t)n_owners * piece_bytes, c->stream));
-  HIPC(c, hipMemsetAsync(&c->d_stats->scratch[1], 0, 16, c->stream));  // [1]: fullest range here, [2]: … anywhere (merge)
-  const uint32_t bpo = std::min<uint32_t>(1024, std::max<uint32_t>(16, 2048 / n_owners));  // blocks per owner
-  hipLaunchKernelGGL(k_compact_owners, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb,
-                     c->tb.cap / n_owners, (const unsigned long long *)doff, dcur, (uint64_t *)d_buf,
-                     (uint32_t *)nullptr, 0ull, skip_owner < 0 ? ~0u : (uint32_t)skip_owner, bpo,
-                     (const unsigned long long *)dcnt, 8ull, &c->d_stats->scratch[1]);
-  hipLaunchKernelGGL(k_piece_headers, dim3((n_owners + 63) / 64), dim3(64), 0, c->stream, (uint32_t *)d_buf, n_owners,
-                     (unsigned long long)(piece_bytes / 4), (const DevStats *)c->d_stats);
-  HIPC(c, hipGetLastError());
-  return SHK_OK;
-}
-
-int shk_merge_pieces_max(shk_ctx *c, uint64_t *max_count) {
-  if (!c || !max_count) return SHK_ERR_BAD_ARG;
-  if (c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  HIPC(c, hipSetDevice(c->cfg.device));
-  if (!c->finalized && !c->hist_ready) {  // (a finalize has just brought the control block back otherwise)
-    int rc = read_stats(c);
-    if (rc != SHK_OK) return rc;
-  }
-  *max_count = c->h_stats->scratch[2];
-  return SHK_OK;
-}
-
-static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride,
-                        uint64_t piece_cap, uint32_t skip_piece);
-
-int shk_merge_entries(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  if (n == 0) return SHK_OK;
-  return merge_launch(c, d_keys, d_vals, n, vals_lane_stride, 0, ~0u);
-}
-
-int shk_merge_pieces(shk_ctx *c, const void *d_buf, uint32_t n_pieces, uint64_t capacity, int32_t skip_piece) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !d_buf) return SHK_ERR_BAD_ARG;
-  if (n_pieces == 0 || capacity == 0) return SHK_OK;
-  return merge_launch(c, d_buf, nullptr, (uint64_t)n_pieces * capacity, capacity, capacity, skip_piece < 0 ? ~0u : (uint32_t)skip_piece);
-}
-
-static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride,
-                        uint64_t piece_cap, uint32_t skip_piece) {
-  HIPC(c, hipSetDevice(c->cfg.device));
-  {
-    int rcf = tb_fresh(c);
-    if (rcf != SHK_OK) return rcf;
-  }
-  // Fixed-capacity pieces behind a counting launch nobody has looked at yet: nothing is waited for.  If that
-  // launch spilled, the senders' headers are poisoned and k_merge touches nothing; if not, what the merge spills
-  // goes on the same list (same capacity, the counter runs on) and the finalize that follows repairs it.
-  // (Only when that list could take the merge's own worst case — every entry spilling on every lane, which is what
-  // W pieces' worth of new keys do to pages sized for the local shard alone: k_merge drops what does not fit the list,
-  // and the settle that follows would fail the job with "spill list overflow" where the exact-count protocol would
-  // have finished.  A counting launch's list has a place per k-mer of the launch, so this holds whenever the pieces
-  // are no larger than the batch.)
-  const bool ride_on = piece_cap && c->unsettled && !c->acc_active && c->unsettled_spill_cap >= n * c->n_lanes &&
-                       c->spillA.cap >= c->unsettled_spill_cap * 16;
-  if (!ride_on) {
-    int rcs = settle(c);
-    if (rcs != SHK_OK) return rcs;
-  }
-  c->finalized = c->hist_ready = false;
-  c->zero_count_keys = true;  // (a peer's table may hold keys inserted with count 0: keep reading the keys)
-  const uint64_t spill_cap = ride_on ? c->unsettled_spill_cap : n * c->n_lanes;  // worst case every entry spills on every lane
-  if (!ride_on) {
-    HIPC(c, c->spillA.ensure(spill_cap * 16));
-    HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
-  }
-  SpillRef sp = spill_ref(c->spillA, spill_cap);
-  {
-    ScopedTimer t(c, SHK_K_MERGE);
-    hipLaunchKernelGGL(k_merge, dim3(grid_for(n, WG, 8192)), dim3(WG), 0, c->stream, c->tb, n, vals_lane_stride,
-                       (const uint64_t *)d_keys, (const uint32_t *)d_vals, c->d_stats, sp, piece_cap, skip_piece);
-  }
-  // (nothing is waited for: the outcome — spilled entries, load factor — is looked at by the next call that
-  // needs the table, at the latest finalize)
-  c->unsettled = true;
-  c->unsettled_spill_cap = spill_cap;
-  return SHK_OK;
-}
-
-int shk_set_owned_pages(shk_ctx *c, uint64_t p0, uint64_t p1) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  if (p1 < p0 || p1 > (1ull << c->tb.log_pages)) return fail(c, SHK_ERR_BAD_ARG, "bad page range");
-  c->own_p0 = p0;
-  c->own_p1 = p1;
-  c->own_set = true;
-  c->own_share_n = 0;
-  c->finalized = c->hist_ready = false;
-  return SHK_OK;
-}
-
-int shk_set_owner_share(shk_ctx *c, uint32_t n_owners, uint32_t owner) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c) return SHK_ERR_BAD_ARG;
-  if (n_owners == 0 || (n_owners & (n_owners - 1)) || owner >= n_owners || n_owners > (1ull << c->tb.log_pages))
-    return fail(c, SHK_ERR_BAD_ARG, "bad owner share %u of %u", owner, n_owners);
-  c->own_share_n = n_owners;  // (no settle: the range is worked out from the page count of the moment a scan is launched)
-  c->own_share_id = owner;
-  c->own_set = true;
-  c->finalized = c->hist_ready = false;
   return SHK_OK;
 }
 
@@ -4281,8 +3324,8 @@ void shk_free_device(shk_ctx *c, void *p) {
 
 int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_read, uint64_t n_reads,
                            void *d_bases, void *d_offsets) {
-  if (c && c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
-  if (!c || !spec) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  if (!spec) return SHK_ERR_BAD_ARG;
   if (spec->read_len == 0 || spec->genome_len < spec->read_len)
     return fail(c, SHK_ERR_BAD_ARG, "bad synth spec");
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -4301,3 +3344,6 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 }
 
 }  // extern "C"
+
+// shk_export_table … shk_set_owner_share: the calls that read the table or hand it to a peer
+#include "shk_table_api.hip.h"

@@ -1,0 +1,840 @@
+// The part of the C ABI that reads the table or hands it to a peer: export, lookup, the sPCR scans (neighborhood, extend,
+// find_oligos, primer_kmers), the read filters, and the owner exchange (geometry, merge, counts, compaction, owned ranges).
+// Included at the end of shk_engine.hip (one translation unit: the context, settle and the helpers beside HIPC are there).
+//
+// A call that reads the table begins with table_read_begin; one that does not says why where it departs.
+
+// What the table-read and owner-exchange entry points share.
+namespace {
+
+// A scan of a multi-device context that appends to (kmers, counts): the shares are disjoint, so one after the other,
+// each with the room those before it left.  call(share, kmers, counts, room, &n) is the scan of one share.
+template <typename F>
+int each_share_appends(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out, F call) {
+  uint64_t at = 0;
+  for (uint32_t d = 0; d < c->group->D; ++d) {
+    uint64_t n = 0;
+    const uint64_t room = at < cap ? cap - at : 0;
+    const int rc = call(c->group->ctx[d], kmers ? kmers + std::min(at, cap) : nullptr, counts ? counts + std::min(at, cap) : nullptr, room, &n);
+    if (rc != SHK_OK) return group_fail(c, c->group, rc, d);
+    at += n;
+  }
+  if (n_out) *n_out = at;
+  return SHK_OK;
+}
+
+// The end of an appending scan: *n_out = the entries it found (dn; may exceed cap), and the first min(*n_out, cap) of
+// them for the arrays the caller gave.  (The wait also keeps the caller's host sources alive until their copies ran.)
+int fetch_appended(shk_ctx *c, const unsigned long long *dn, const uint64_t *dk, const uint32_t *dc, uint64_t cap, uint64_t *kmers,
+                   uint32_t *counts, uint64_t *n_out) {
+  unsigned long long n = 0;
+  HIPC(c, hipMemcpyAsync(&n, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  *n_out = n;
+  const uint64_t m = std::min<uint64_t>(n, cap);
+  if (m && kmers) HIPC(c, hipMemcpy(kmers, dk, m * 8, hipMemcpyDeviceToHost));
+  if (m && counts) HIPC(c, hipMemcpy(counts, dc, m * 4, hipMemcpyDeviceToHost));
+  return SHK_OK;
+}
+
+// An owner is a run of whole pages: the page count has to split evenly.
+int owner_split_check(shk_ctx *c, uint32_t n_owners) {
+  const uint64_t n_pages = 1ull << c->tb.log_pages;
+  if (n_pages % n_owners) return fail(c, SHK_ERR_BAD_ARG, "%llu pages do not split over %u owners",
+                                      (unsigned long long)n_pages, n_owners);
+  return SHK_OK;
+}
+uint32_t owner_blocks(uint32_t n_owners) { return std::min<uint32_t>(1024, std::max<uint32_t>(16, 2048 / n_owners)); }  // blocks per owner
+
+// The k_compact_owners launch of the three shk_compact_owners* calls.  device: [seg offsets (entries) × W][cursors × W]
+// [counts × W].  h_off: where each owner's entries start in the destination; h_cnt: how many it was promised (the packed
+// layouts; nullptr: separate key and count arrays); header_bytes: what a piece keeps in front of its entries; fullest:
+// the word that takes the fullest owner range's entries (nullptr: nobody asks).
+int compact_owners_launch(shk_ctx *c, uint32_t n_owners, const uint64_t *h_off, const uint64_t *h_cnt, void *d_keys, void *d_vals,
+                          uint64_t vals_lane_stride, int32_t skip_owner, unsigned long long header_bytes, unsigned long long *fullest) {
+  using ull = unsigned long long;
+  Scratch m{c->misc};
+  const size_t o_off = m.take<ull>(n_owners), o_cur = m.take<ull>(n_owners), o_cnt = m.take<ull>(h_cnt ? n_owners : 0);
+  HIPC(c, m.ensure());
+  ull *doff = m.at<ull>(o_off), *dcur = m.at<ull>(o_cur), *dcnt = h_cnt ? m.at<ull>(o_cnt) : nullptr;
+  HIPC(c, hipMemcpyAsync(doff, h_off, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
+  if (h_cnt) HIPC(c, hipMemcpyAsync(dcnt, h_cnt, (size_t)n_owners * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemsetAsync(dcur, 0, (size_t)n_owners * 8, c->stream));
+  const uint32_t bpo = owner_blocks(n_owners);
+  hipLaunchKernelGGL(k_compact_owners, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb, c->tb.cap / n_owners,
+                     (const ull *)doff, dcur, (uint64_t *)d_keys, (uint32_t *)d_vals, vals_lane_stride,
+                     skip_owner < 0 ? ~0u : (uint32_t)skip_owner, bpo, (const ull *)dcnt, header_bytes, fullest);
+  return SHK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shk_export_table(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
+  if (!c || !n_out) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return each_share_appends(c, kmers, counts, cap, n_out, [](shk_ctx *s, uint64_t *k, uint32_t *ct, uint64_t room, uint64_t *n) {
+      return shk_export_table(s, k, ct, room, n);
+    });
+  SHK_TRY(table_read_begin(c));
+  Scratch m{c->misc};
+  const size_t o_n = m.take<unsigned long long>(1), o_k = m.take<uint64_t>(cap), o_c = m.take<uint32_t>(cap);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n);
+  uint64_t *dk = m.at<uint64_t>(o_k);
+  uint32_t *dc = m.at<uint32_t>(o_c);
+  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
+  const auto [s0, s1] = owned_slots(c);
+  {
+    ScopedTimer t(c, SHK_K_EXPORT);
+    hipLaunchKernelGGL(k_export, dim3(grid_for(s1 - s0, WG * 4, 4096)), dim3(WG), 0, c->stream, c->tb, s0,
+                       s1, dk, dc, cap, dn);
+  }
+  return fetch_appended(c, dn, dk, dc, cap, kmers, counts, n_out);
+}
+
+int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical) {
+  if (c && c->group) {  // exactly one share owns a k-mer; the others answer 0
+    std::vector<uint32_t> part(n);
+    std::fill(counts, counts + n, 0u);
+    for (uint32_t d = 0; d < c->group->D; ++d) {
+      const int rc = shk_lookup(c->group->ctx[d], kmers, part.data(), n, canonical);
+      if (rc != SHK_OK) return group_fail(c, c->group, rc, d);
+      for (uint64_t i = 0; i < n; ++i) counts[i] += part[i];
+    }
+    return SHK_OK;
+  }
+  if (!c) return SHK_ERR_BAD_ARG;
+  if (n == 0) return SHK_OK;
+  SHK_TRY(table_read_begin(c));
+  Scratch m{c->misc};
+  const size_t o_k = m.take<uint64_t>(n), o_c = m.take<uint32_t>(n);
+  HIPC(c, m.ensure());
+  uint64_t *dk = m.at<uint64_t>(o_k);
+  uint32_t *dc = m.at<uint32_t>(o_c);
+  HIPC(c, hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_lookup, dim3((uint32_t)((n + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, dk, dc,
+                       n, canonical, (int)c->cfg.k);
+  }
+  HIPC(c, hipMemcpyAsync(counts, dc, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return SHK_OK;
+}
+
+int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds, uint32_t min_count,
+                     uint32_t max_levels, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
+                     uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
+                     uint32_t *levels_done) {
+  if (!c || !n_out || !n_fringe || !levels_done || (n_seeds && (!nodes || !dirs))) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  if ((cap && (!kmers || !counts)) || (fringe_cap && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
+  if (cap > (1ull << 32) || fringe_cap > (1ull << 32))
+    return fail(c, SHK_ERR_BAD_ARG, "cap %llu / fringe_cap %llu above 2^32", (unsigned long long)cap, (unsigned long long)fringe_cap);
+  const uint64_t node_mask = (1ull << (2 * (k - 1))) - 1ull;
+  // level 0: the distinct (node, dir) pairs, as entries node << 1 | (0 forward, 1 reverse)
+  std::vector<uint64_t> seeds;
+  seeds.reserve(n_seeds);
+  for (uint64_t i = 0; i < n_seeds; ++i) {
+    if (dirs[i] == 0 || dirs[i] > 3) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: dir %u is not 1 (forward), 2 (reverse) or 3 (both)", (unsigned long long)i, dirs[i]);
+    if (nodes[i] > node_mask) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: node 0x%llx is not a %u-mer", (unsigned long long)i, (unsigned long long)nodes[i], k - 1);
+    if (dirs[i] & 1) seeds.push_back(nodes[i] << 1);
+    if (dirs[i] & 2) seeds.push_back(nodes[i] << 1 | 1ull);
+  }
+  std::sort(seeds.begin(), seeds.end());
+  seeds.erase(std::unique(seeds.begin(), seeds.end()), seeds.end());
+  if (seeds.size() > fringe_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "%llu distinct seeds do not fit fringe_cap %llu", (unsigned long long)seeds.size(), (unsigned long long)fringe_cap);
+  *n_out = 0;
+  *n_fringe = 0;
+  *levels_done = 0;
+  if (seeds.empty()) return SHK_OK;
+  SHK_TRY(table_read_begin(c));
+  // An accepted k-mer has two orientations and an orientation one successor per dir: through a level that fits, the
+  // visited set never holds more than the seeds and 4·cap entries, the k-mer set cap.  Both at most half full then; a
+  // set that fills up (probes are bounded) belongs to a level that does not fit and is dropped.
+  auto pow2_above = [](uint64_t n) {
+    uint64_t s = 16;
+    while (s < n) s <<= 1;
+    return s;
+  };
+  const uint64_t vis_slots = pow2_above(2 * (seeds.size() + 4 * cap) + 2), kset_slots = pow2_above(2 * cap + 2);
+  const uint64_t fc = std::max<uint64_t>(fringe_cap, 1), kc = std::max<uint64_t>(cap, 1);
+  Scratch m{c->misc};
+  const size_t o_ctl = m.take<NbCtl>(1), o_vis = m.take<uint64_t>(vis_slots), o_kset = m.take<uint64_t>(kset_slots);  // (vis, kset: adjacent)
+  const size_t o_l0 = m.take<uint64_t>(fc), o_l1 = m.take<uint64_t>(fc), o_km = m.take<uint64_t>(kc), o_ct = m.take<uint32_t>(kc);
+  HIPC(c, m.ensure());
+  NbCtl *dctl = m.at<NbCtl>(o_ctl);
+  NbRef nb{};
+  nb.vis = m.at<uint64_t>(o_vis);
+  nb.kset = m.at<uint64_t>(o_kset);
+  nb.vis_mask = vis_slots - 1;
+  nb.kset_mask = kset_slots - 1;
+  nb.list[0] = m.at<uint64_t>(o_l0);
+  nb.list[1] = m.at<uint64_t>(o_l1);
+  nb.kmers = m.at<uint64_t>(o_km);
+  nb.counts = m.at<uint32_t>(o_ct);
+  nb.cap = cap;
+  nb.fringe_cap = fringe_cap;
+  nb.min_count = std::max(min_count, 1u);
+  nb.max_levels = max_levels;
+  nb.k = (int)k;
+  NbCtl h{};
+  h.cur_n = seeds.size();
+  HIPC(c, hipMemsetAsync(nb.vis, 0xFF, (o_l0 - o_vis), c->stream));  // both sets ← EMPTY
+  HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(nb.list[0], seeds.data(), seeds.size() * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_seed, dim3((uint32_t)((seeds.size() + WG - 1) / WG)), dim3(WG), 0, c->stream, nb,
+                       (uint64_t)seeds.size(), dctl);
+  }
+  // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
+  while (h.status == NB_RUN || h.status == NB_WIDE) {
+    if (h.cur_n == 0) {
+      h.status = NB_COMPLETE;
+      break;
+    }
+    if (max_levels && h.levels_done >= max_levels) {
+      h.status = NB_LIMIT;
+      break;
+    }
+    if (h.cur_n <= NB_NARROW) {
+      {
+        ScopedTimer t(c, SHK_K_EXTEND);
+        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
+      }
+      HIPC(c, hipGetLastError());
+      HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+      HIPC(c, hipStreamSynchronize(c->stream));
+      continue;
+    }
+    const unsigned long long k_start = h.k_n;
+    {
+      ScopedTimer t(c, SHK_K_EXTEND);
+      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
+                         dctl, h.cur_sel, (uint64_t)h.cur_n);
+    }
+    HIPC(c, hipGetLastError());
+    NbCtl r{};
+    HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (r.set_full || r.k_n > cap || r.next_n > fringe_cap) {  // the level did not fit: the k-mer list back to its start
+      h.k_n = k_start;
+      h.status = NB_OVERFLOW;
+      break;
+    }
+    h.k_n = r.k_n;
+    h.cur_n = r.next_n;
+    h.cur_sel ^= 1u;
+    h.levels_done += 1;
+    h.next_n = 0;
+    h.status = NB_RUN;
+    HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));  // (h is a pageable source: the copy has read it)
+  }
+  // the arrival order of the appends is not part of the result: sorted
+  const uint64_t nk = h.k_n, nf = h.status == NB_COMPLETE ? 0 : h.cur_n;
+  std::vector<uint64_t> hk(nk), hf(nf);
+  std::vector<uint32_t> hc(nk);
+  if (nk) {
+    HIPC(c, hipMemcpy(hk.data(), nb.kmers, nk * 8, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(hc.data(), nb.counts, nk * 4, hipMemcpyDeviceToHost));
+  }
+  if (nf) HIPC(c, hipMemcpy(hf.data(), nb.list[h.cur_sel], nf * 8, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> order(nk);
+  for (uint64_t i = 0; i < nk; ++i) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
+  for (uint64_t i = 0; i < nk; ++i) {
+    kmers[i] = hk[order[i]];
+    counts[i] = hc[order[i]];
+  }
+  std::sort(hf.begin(), hf.end());
+  for (uint64_t i = 0; i < nf; ++i) {
+    fringe_nodes[i] = hf[i] >> 1;
+    fringe_dirs[i] = (uint8_t)(1u << (hf[i] & 1ull));
+  }
+  *n_out = nk;
+  *n_fringe = nf;
+  *levels_done = h.levels_done;
+  return SHK_OK;
+}
+
+int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
+                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev, const shk_pcr_extend_params *p,
+                   uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes, uint32_t *edge_src,
+                   uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges, uint32_t *found_path,
+                   uint32_t *threshold_used, uint32_t *steps_run) {
+  if (!c || !p || !n_nodes || !n_edges || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
+  if ((n_fwd && (!fwd_kmers || !fwd_counts)) || (n_rev && (!rev_kmers || !rev_counts))) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  const uint64_t kmask = ~0ull >> (64 - 2 * k);
+  for (uint64_t i = 0; i < n_fwd; ++i)
+    if (fwd_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "forward primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
+  for (uint64_t i = 0; i < n_rev; ++i)
+    if (rev_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "reverse primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
+  PcrGraph g;
+  std::string msg;
+  const int rc = pcr_extend_run(c, k, fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev, *p, &g, threshold_used,
+                                steps_run, &msg);
+  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood's own text stands)
+  *n_nodes = g.sub_kmer.size();
+  *n_edges = g.esrc.size();
+  *found_path = g.found_path ? 1u : 0u;
+  if (*n_nodes > node_cap || *n_edges > edge_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "graph of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu",
+                (unsigned long long)*n_nodes, (unsigned long long)*n_edges, (unsigned long long)node_cap, (unsigned long long)edge_cap);
+  if ((*n_nodes && (!node_sub_kmers || !node_flags)) || (*n_edges && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
+  std::copy(g.sub_kmer.begin(), g.sub_kmer.end(), node_sub_kmers);
+  std::copy(g.flags.begin(), g.flags.end(), node_flags);
+  std::copy(g.esrc.begin(), g.esrc.end(), edge_src);
+  std::copy(g.etgt.begin(), g.etgt.end(), edge_tgt);
+  std::copy(g.ecount.begin(), g.ecount.end(), edge_counts);
+  return SHK_OK;
+}
+
+int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,
+                    uint32_t min_count, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
+  if (c && c->group)
+    return each_share_appends(c, kmers, counts, cap, n_out, [&](shk_ctx *s, uint64_t *k, uint32_t *ct, uint64_t room, uint64_t *n) {
+      return shk_find_oligos(s, oligos, n_oligos, oligo_len, min_count, k, ct, room, n);
+    });
+  if (!c || !n_out) return SHK_ERR_BAD_ARG;
+  const uint32_t k = c->cfg.k;
+  // the reference asserts these (primers.rs:169-186)
+  if (n_oligos == 0 || !oligos) return fail(c, SHK_ERR_BAD_ARG, "find_oligos_in_kmers called with no oligos");
+  if (!(oligo_len > 0 && oligo_len < k))
+    return fail(c, SHK_ERR_BAD_ARG, "oligo length %u out of range for k=%u (must be 1..k-1); trim must be < k",
+                oligo_len, k);
+  if (n_oligos > 3000) return fail(c, SHK_ERR_BAD_ARG, "too many oligos (%u > 3000)", n_oligos);
+  SHK_TRY(table_read_begin(c));
+  auto rc_of = [](uint64_t x, int len) {  // reverse complement of a len-base value (host side)
+    uint64_t r = 0;
+    for (int i = 0; i < len; ++i) {
+      r = (r << 2) | (3 - (x & 3));
+      x >>= 2;
+    }
+    return r;
+  };
+  std::vector<uint64_t> fwd(n_oligos), rc(n_oligos);
+  for (uint32_t i = 0; i < n_oligos; ++i) {
+    fwd[i] = oligos[i] << (2 * (k - oligo_len));  // primers.rs:189-192
+    rc[i] = rc_of(oligos[i], (int)oligo_len);      // primers.rs:206-209
+  }
+  std::sort(fwd.begin(), fwd.end());
+  std::sort(rc.begin(), rc.end());
+  Scratch m{c->misc};
+  const size_t o_n = m.take<unsigned long long>(1), o_sets = m.take<uint64_t>(2 * (size_t)n_oligos), o_k = m.take<uint64_t>(cap),
+               o_c = m.take<uint32_t>(cap);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n);
+  uint64_t *dsets = m.at<uint64_t>(o_sets);  // the forward set, then the reverse-complement set
+  uint64_t *dk = m.at<uint64_t>(o_k);
+  uint32_t *dc = m.at<uint32_t>(o_c);
+  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
+  HIPC(c, hipMemcpyAsync(dsets, fwd.data(), (size_t)n_oligos * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(dsets + n_oligos, rc.data(), (size_t)n_oligos * 8, hipMemcpyHostToDevice, c->stream));
+  const auto [s0, s1] = owned_slots(c);
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_find_oligos, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG), (size_t)n_oligos * 16,
+                       c->stream, c->tb, s0, s1, (int)k, (int)oligo_len, min_count, (const uint64_t *)dsets,
+                       (const uint64_t *)(dsets + n_oligos), n_oligos, dk, dc, cap, dn);
+  }
+  return fetch_appended(c, dn, dk, dc, cap, kmers, counts, n_out);  // (its wait keeps fwd/rc alive until their copies ran)
+}
+
+namespace {
+
+// One k_primer_scan pass over c's slots (the owned pages of an owner share): the per-(primer, level) hits (dev's
+// order) and, when they fit in `room`, the records.  *n_total = records the pass produced (> room: none returned).
+int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, std::vector<PrimerRec> *recs,
+                std::vector<uint64_t> *hits, uint64_t *n_total) {
+  SHK_TRY(table_read_begin(c));
+  const uint32_t n = (uint32_t)dev.size();
+  uint32_t stride = 1;  // LDS counters per primer: levels 0..max M
+  for (const PrimerDev &d : dev) stride = std::max(stride, d.M + 1);
+  // primers per launch: their table and counters in 48 KiB of LDS (three workgroups per CU)
+  const uint32_t per_launch = (48u << 10) / (uint32_t)(sizeof(PrimerDev) + 4 * stride);
+  const size_t hits_b = (size_t)n * SHK_PRIMER_LEVELS * 8, prim_b = (size_t)n * sizeof(PrimerDev);
+  Scratch m{c->misc};
+  const size_t o_n = m.take<unsigned long long>(1), o_hits = m.take<unsigned long long>((size_t)n * SHK_PRIMER_LEVELS);  // (adjacent)
+  const size_t o_prim = m.take<PrimerDev>(n), o_rec = m.take<PrimerRec>(room);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n), *dhits = m.at<unsigned long long>(o_hits);
+  PrimerDev *dprim = m.at<PrimerDev>(o_prim);
+  PrimerRec *drec = m.at<PrimerRec>(o_rec);
+  HIPC(c, hipMemsetAsync(dn, 0, o_prim - o_n, c->stream));  // the record counter and the hits
+  HIPC(c, hipMemcpyAsync(dprim, dev.data(), prim_b, hipMemcpyHostToDevice, c->stream));
+  const auto [s0, s1] = owned_slots(c);
+  for (uint32_t b = 0; b < n; b += per_launch) {
+    const uint32_t nb = std::min(per_launch, n - b);
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_primer_scan, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG),
+                       (size_t)nb * (sizeof(PrimerDev) + 4 * stride), c->stream, c->tb, s0, s1, (int)c->cfg.k,
+                       (const PrimerDev *)(dprim + b), nb, b, stride, drec, (uint64_t)room, dn, dhits);
+  }
+  HIPC(c, hipGetLastError());
+  unsigned long long nt = 0;
+  hits->assign((size_t)n * SHK_PRIMER_LEVELS, 0);
+  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(hits->data(), dhits, hits_b, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps dev alive until its copy ran)
+  *n_total = nt;
+  recs->clear();
+  if (nt <= room && nt) {
+    recs->resize(nt);
+    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
+  }
+  return SHK_OK;
+}
+
+}  // namespace
+
+int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
+                     uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
+  if (n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
+  const uint32_t k = c->cfg.k;
+  // preprocess_primer_by_mismatch of every direction before any scan (primers.rs:440-450), then the conversion
+  // check of the searched ones (their first round, primers.rs:383-393)
+  std::vector<PrimerPlan> plans(n_primers);
+  std::string msg;
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    const int rc = primer_plan(&primers[i], k, &plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
+  }
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    const int rc = primer_check_chars(plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
+  }
+  uint64_t need = 0;
+  for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
+  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
+  if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
+  if (level_hits) std::fill(level_hits, level_hits + (size_t)n_primers * SHK_PRIMER_LEVELS, 0ull);
+  std::vector<uint32_t> who;  // searched primer j = primers[who[j]]
+  std::vector<PrimerDev> dev;
+  for (uint32_t i = 0; i < n_primers; ++i)
+    if (plans[i].scanned()) {
+      const PrimerPlan &pl = plans[i];
+      who.push_back(i);
+      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, pl.min_count, 0});
+    }
+  const uint32_t n = (uint32_t)dev.size();
+  std::vector<shk_ctx *> parts;  // a multi-device context: its shares are disjoint, the answer is the top of the union
+  if (c->group)
+    for (uint32_t d = 0; d < c->group->D; ++d) parts.push_back(c->group->ctx[d]);
+  else
+    parts.push_back(c);
+  auto part_fail = [&](int rc, uint32_t d) { return c->group ? group_fail(c, c->group, rc, d) : rc; };
+  std::vector<PrimerRec> all;
+  std::vector<uint64_t> hits((size_t)n * SHK_PRIMER_LEVELS, 0);
+  if (n) {
+    const int env_room = env_int("SHK_PRIMER_CANDIDATES", 1 << 18);
+    const uint64_t room = (uint64_t)std::max(env_room, 1);
+    std::vector<std::vector<uint64_t>> part_hits(parts.size());
+    std::vector<uint64_t> part_n(parts.size());
+    std::vector<PrimerRec> recs;
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      const int rc = primer_pass(parts[d], dev, room, &recs, &part_hits[d], &part_n[d]);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      all.insert(all.end(), recs.begin(), recs.end());
+      for (size_t j = 0; j < hits.size(); ++j) hits[j] += part_hits[d][j];
+    }
+    // The record buffer overflowed: the counts are complete, so each primer's cut level is known — the first level
+    // at which its hits reach max_kmers.  Nothing above it can be selected; rerun keeping levels ≤ cut, sized exactly.
+    std::vector<PrimerDev> cut = dev;
+    for (uint32_t j = 0; j < n; ++j) {
+      uint64_t acc = 0;
+      for (uint32_t m = 0; m <= dev[j].M; ++m) {
+        acc += hits[(size_t)j * SHK_PRIMER_LEVELS + m];
+        if (acc >= plans[who[j]].max_kmers) {
+          cut[j].M = m;
+          break;
+        }
+      }
+    }
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      if (part_n[d] <= room) continue;
+      uint64_t exact = 0;
+      for (uint32_t j = 0; j < n; ++j)
+        for (uint32_t m = 0; m <= cut[j].M; ++m) exact += part_hits[d][(size_t)j * SHK_PRIMER_LEVELS + m];
+      std::vector<uint64_t> h2;
+      uint64_t n2 = 0;
+      const int rc = primer_pass(parts[d], cut, exact, &recs, &h2, &n2);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      if (n2 != exact)
+        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu",
+                    (unsigned long long)n2, (unsigned long long)exact);
+      all.insert(all.end(), recs.begin(), recs.end());
+    }
+  }
+  // Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
+  // sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
+  // here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
+  // and two entries never yield the same k-mer because the table holds canonical k-mers only — so the reference's
+  // "already found at a lower level" filter (primers.rs:398-403) never drops anything.
+  std::vector<uint64_t> first(n + 1, 0);
+  for (const PrimerRec &r : all) ++first[(r.tag >> 8) + 1];
+  for (uint32_t j = 0; j < n; ++j) first[j + 1] += first[j];
+  std::vector<PrimerRec> by(all.size());
+  {
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (const PrimerRec &r : all) by[at[r.tag >> 8]++] = r;
+  }
+  auto before = [](const PrimerRec &a, const PrimerRec &b) {
+    const uint32_t la = a.tag & 0xFF, lb = b.tag & 0xFF;
+    if (la != lb) return la < lb;
+    if (a.count != b.count) return a.count > b.count;
+    return a.kmer < b.kmer;
+  };
+  uint64_t o = 0;
+  uint32_t j = 0;
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    offsets[i] = o;
+    if (j >= n || who[j] != i) continue;
+    PrimerRec *b = by.data() + first[j], *e = by.data() + first[j + 1];
+    const uint64_t take = std::min<uint64_t>(plans[i].max_kmers, (uint64_t)(e - b));
+    std::partial_sort(b, b + take, e, before);
+    for (uint64_t t = 0; t < take; ++t, ++o) {
+      kmers[o] = b[t].kmer;
+      counts[o] = b[t].count;
+      levels[o] = (uint8_t)(b[t].tag & 0xFF);
+    }
+    if (level_hits) std::copy(hits.begin() + (size_t)j * SHK_PRIMER_LEVELS, hits.begin() + (size_t)(j + 1) * SHK_PRIMER_LEVELS,
+                              level_hits + (size_t)i * SHK_PRIMER_LEVELS);
+    ++j;
+  }
+  offsets[n_primers] = o;
+  return SHK_OK;
+}
+
+int shk_filter_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
+                     const uint64_t *primer_kmers, uint64_t n_kmers, uint8_t *out_matches) {
+  if (c && c->group) {  // stateless: any device will do
+    const int rc = shk_filter_reads(c->group->ctx[0], bases, offsets, n_seqs, primer_kmers, n_kmers, out_matches);
+    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
+  }
+  if (!c || (n_seqs && (!offsets || !out_matches))) return SHK_ERR_BAD_ARG;
+  if (n_seqs == 0) return SHK_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  const uint32_t k = c->cfg.k;
+  // the union of the primer k-mers (read_filter.rs:24-41) as an open-addressing set at load ≤ 1/2
+  uint64_t cap = 16;
+  while (cap < 2 * n_kmers) cap <<= 1;
+  if (cap > (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "primer k-mer set too large");
+  std::vector<uint64_t> set(cap, ~0ull);
+  for (uint64_t j = 0; j < n_kmers; ++j) {
+    const uint64_t key = primer_kmers[j];
+    if (2 * k < 64 && (key >> (2 * k)) != 0)
+      return fail(c, SHK_ERR_BAD_ARG, "primer k-mer %llu does not fit %u bases", (unsigned long long)key, k);
+    for (uint64_t sl = set_hash(key) & (cap - 1);; sl = (sl + 1) & (cap - 1)) {
+      if (set[sl] == key) break;
+      if (set[sl] == ~0ull) {
+        set[sl] = key;
+        break;
+      }
+    }
+  }
+  const uint64_t n_bases = offsets[n_seqs];
+  HIPC(c, c->in_bases.ensure(n_bases + 16));
+  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
+  Scratch m{c->misc};
+  const size_t o_set = m.take<uint64_t>(cap), o_out = m.take<uint8_t>(n_seqs);
+  HIPC(c, m.ensure());
+  uint64_t *dset = m.at<uint64_t>(o_set);
+  uint8_t *dout = m.at<uint8_t>(o_out);
+  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(dset, set.data(), cap * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_filter_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
+                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, n_seqs, (int)k,
+                       (const uint64_t *)dset, (uint32_t)(cap - 1), dout);
+  }
+  HIPC(c, hipMemcpyAsync(out_matches, dout, n_seqs, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `set` alive until its copy ran)
+  return SHK_OK;
+}
+
+int shk_kmers_from_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
+                         uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte) {
+  if (c && c->group) {  // stateless: any device will do
+    const int rc = shk_kmers_from_reads(c->group->ctx[0], bases, offsets, n_seqs, kmers, kmers_cap, n_kmers, bad_byte);
+    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
+  }
+  if (!c || (n_seqs && (!offsets || !n_kmers || !bad_byte))) return SHK_ERR_BAD_ARG;
+  if (n_seqs == 0) return SHK_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  const uint32_t k = c->cfg.k;
+  // koff(i): every read gets room for the most k-mers it can yield
+  std::vector<uint64_t> koff(n_seqs + 1);
+  koff[0] = 0;
+  for (uint64_t i = 0; i < n_seqs; ++i) {
+    if (offsets[i + 1] < offsets[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
+    const uint64_t len = offsets[i + 1] - offsets[i];
+    koff[i + 1] = koff[i] + (len >= k ? len - k + 1 : 0);
+  }
+  const uint64_t n_total = koff[n_seqs];
+  if (n_total > kmers_cap || (n_total && !kmers))
+    return fail(c, SHK_ERR_BAD_ARG, "kmers_cap %llu is below the %llu k-mers these reads can yield",
+                (unsigned long long)kmers_cap, (unsigned long long)n_total);
+  const uint64_t n_bases = offsets[n_seqs];
+  HIPC(c, c->in_bases.ensure(n_bases + 16));
+  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
+  Scratch m{c->misc};
+  const size_t o_koff = m.take<uint64_t>(n_seqs + 1), o_kmers = m.take<uint64_t>(n_total + 1), o_n = m.take<uint32_t>(n_seqs),
+               o_bad = m.take<uint8_t>(n_seqs);
+  HIPC(c, m.ensure());
+  uint64_t *dkoff = m.at<uint64_t>(o_koff), *dkm = m.at<uint64_t>(o_kmers);
+  uint32_t *dnk = m.at<uint32_t>(o_n);
+  uint8_t *dbad = m.at<uint8_t>(o_bad);
+  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(dkoff, koff.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_kmers_from_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
+                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p,
+                       (const uint64_t *)dkoff, n_seqs, (int)k, dkm, dnk, dbad);
+  }
+  // a read's span is copied back whole; only its first n_kmers[i] entries mean anything
+  if (n_total) HIPC(c, hipMemcpyAsync(kmers, dkm, n_total * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(n_kmers, dnk, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(bad_byte, dbad, n_seqs, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `koff` alive until its copy ran)
+  return SHK_OK;
+}
+
+int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {
+  SHK_TRY(single_device_only(c));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));  // a pending spill may still grow the table
+  if (n_pages) *n_pages = 1ull << c->tb.log_pages;
+  if (page_slots) *page_slots = PAGE_SLOTS;
+  if (n_lanes) *n_lanes = c->n_lanes;
+  return SHK_OK;
+}
+
+int shk_table_reserve_pages(shk_ctx *c, uint64_t n_pages) {
+  SHK_TRY(single_device_only(c));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));  // (no tb_fresh: grow_to carries nothing over from a table that was still to be cleared)
+  uint32_t lp = 0;
+  while ((1ull << lp) < n_pages) lp++;
+  c->finalized = c->hist_ready = false;
+  return grow_to(c, lp);
+}
+
+int shk_table_device_ptrs(shk_ctx *c, void **d_keys, void **d_vals) {
+  SHK_TRY(single_device_only(c));
+  SHK_TRY(table_read_begin(c));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  if (d_keys) *d_keys = c->tb.keys;
+  if (d_vals) *d_vals = c->tb.vals;
+  return SHK_OK;
+}
+
+int shk_merge_pages(shk_ctx *c, uint64_t p0, uint64_t p1, const void *d_keys, const void *d_vals,
+                    uint64_t vals_lane_stride) {
+  SHK_TRY(single_device_only(c));
+  if (p1 <= p0) return SHK_OK;
+  SHK_TRY(table_read_begin(c));
+  c->finalized = c->hist_ready = false;
+  c->zero_count_keys = true;  // (a peer's table may hold keys inserted with count 0: keep reading the keys)
+  const uint64_t n_slots = (p1 - p0) << PAGE_LOG;
+  // worst case every peer key is new here
+  HIPC(c, c->spillA.ensure(n_slots * c->n_lanes * 16));
+  SpillRef sp = spill_ref(c->spillA, n_slots * c->n_lanes);
+  HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
+  {
+    ScopedTimer t(c, SHK_K_MERGE);
+    hipLaunchKernelGGL(k_merge, dim3(grid_for(n_slots, WG, 8192)), dim3(WG), 0, c->stream, c->tb,
+                       n_slots, vals_lane_stride, (const uint64_t *)d_keys, (const uint32_t *)d_vals,
+                       c->d_stats, sp, 0ull, ~0u);
+  }
+  SHK_TRY(read_stats(c));
+  return drain_spill(c, n_slots * c->n_lanes);
+}
+
+int shk_owner_counts(shk_ctx *c, uint32_t n_owners, uint64_t *counts) {
+  SHK_TRY(single_device_only(c));
+  if (!counts || n_owners == 0) return SHK_ERR_BAD_ARG;
+  SHK_TRY(owner_split_check(c, n_owners));
+  SHK_TRY(table_read_begin(c));
+  Scratch m{c->misc};
+  const size_t o_c = m.take<unsigned long long>(n_owners);
+  HIPC(c, m.ensure());
+  unsigned long long *dc = m.at<unsigned long long>(o_c);
+  HIPC(c, hipMemsetAsync(dc, 0, (size_t)n_owners * 8, c->stream));
+  const uint32_t bpo = owner_blocks(n_owners);
+  hipLaunchKernelGGL(k_owner_counts, dim3(n_owners * bpo), dim3(WG), 0, c->stream, c->tb,
+                     c->tb.cap / n_owners, bpo, dc);
+  HIPC(c, hipMemcpyAsync(counts, dc, (size_t)n_owners * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return SHK_OK;
+}
+
+// (No settle, unlike table_read_begin: the exact-count protocol calls this behind shk_owner_counts, which settled, with
+// nothing launched in between — the segment offsets it is given were worked out from those counts.)
+int shk_compact_owners(shk_ctx *c, uint32_t n_owners, const uint64_t *seg_offsets, void *d_keys, void *d_vals,
+                       uint64_t vals_lane_stride, int32_t skip_owner) {
+  SHK_TRY(single_device_only(c));
+  if (!seg_offsets || n_owners == 0) return SHK_ERR_BAD_ARG;
+  SHK_TRY(owner_split_check(c, n_owners));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(tb_fresh(c));
+  SHK_TRY(compact_owners_launch(c, n_owners, seg_offsets, nullptr, d_keys, d_vals, vals_lane_stride, skip_owner, 0ull, nullptr));
+  HIPC(c, hipStreamSynchronize(c->stream));  // the caller hands the buffers to a collective next
+  return SHK_OK;
+}
+
+// (No settle either, for the same reason: `counts` are shk_owner_counts' answer.)
+int shk_compact_owners_packed(shk_ctx *c, uint32_t n_owners, const uint64_t *counts, void *d_buf, int32_t skip_owner) {
+  SHK_TRY(single_device_only(c));
+  if (!counts || n_owners == 0) return SHK_ERR_BAD_ARG;
+  SHK_TRY(owner_split_check(c, n_owners));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(tb_fresh(c));
+  HIPC(c, c->h_rebased[0].ensure((size_t)n_owners * 16));  // offsets and counts staged through pinned memory
+  uint64_t *h = (uint64_t *)c->h_rebased[0].p;
+  uint64_t run = 0;
+  for (uint32_t o = 0; o < n_owners; ++o) {
+    h[o] = run;
+    h[n_owners + o] = counts[o];
+    run += counts[o];
+  }
+  SHK_TRY(compact_owners_launch(c, n_owners, h, h + n_owners, d_buf, nullptr, 0, skip_owner, 0ull, nullptr));
+  HIPC(c, hipGetLastError());
+  return SHK_OK;  // (asynchronous on the context's stream: run the collective on shk_stream())
+}
+
+int shk_compact_owners_fixed(shk_ctx *c, uint32_t n_owners, uint64_t capacity, void *d_buf, int32_t skip_owner) {
+  SHK_TRY(single_device_only(c));
+  if (n_owners == 0 || capacity == 0 || !d_buf) return SHK_ERR_BAD_ARG;
+  SHK_TRY(owner_split_check(c, n_owners));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  if (c->acc_active) SHK_TRY(settle(c));  // records still waiting for their page pass
+  // (Otherwise nothing is waited for: a counting launch nobody has looked at yet may have spilled records, in which
+  // case the table read here is incomplete — k_piece_headers sees that on the device and poisons every header, no
+  // rank merges anything, and the finalize that follows repairs the table before the exchange is repeated.)
+  SHK_TRY(tb_fresh(c));
+  HIPC(c, c->h_rebased[0].ensure((size_t)n_owners * 16));
+  uint64_t *h = (uint64_t *)c->h_rebased[0].p;
+  for (uint32_t o = 0; o < n_owners; ++o) {
+    h[o] = (uint64_t)o * capacity;  // every piece at its fixed place
+    h[n_owners + o] = capacity;
+  }
+  const size_t piece_bytes = 8 + capacity * (8 + 4 * (size_t)c->n_lanes);
+  // unused places read as EMPTY k-mers, which the merge skips
+  HIPC(c, hipMemsetAsync(d_buf, 0xFF, (size_t)n_owners * piece_bytes, c->stream));
+  HIPC(c, hipMemsetAsync(&c->d_stats->scratch[1], 0, 16, c->stream));  // [1]: fullest range here, [2]: … anywhere (merge)
+  SHK_TRY(compact_owners_launch(c, n_owners, h, h + n_owners, d_buf, nullptr, 0, skip_owner, 8ull, &c->d_stats->scratch[1]));
+  hipLaunchKernelGGL(k_piece_headers, dim3((n_owners + 63) / 64), dim3(64), 0, c->stream, (uint32_t *)d_buf, n_owners,
+                     (unsigned long long)(piece_bytes / 4), (const DevStats *)c->d_stats);
+  HIPC(c, hipGetLastError());
+  return SHK_OK;
+}
+
+int shk_merge_pieces_max(shk_ctx *c, uint64_t *max_count) {
+  if (!c || !max_count) return SHK_ERR_BAD_ARG;
+  if (c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
+  HIPC(c, hipSetDevice(c->cfg.device));
+  if (!c->finalized && !c->hist_ready) SHK_TRY(read_stats(c));  // (a finalize has just brought the control block back otherwise)
+  *max_count = c->h_stats->scratch[2];
+  return SHK_OK;
+}
+
+static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride,
+                        uint64_t piece_cap, uint32_t skip_piece);
+
+int shk_merge_entries(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride) {
+  SHK_TRY(single_device_only(c));
+  if (n == 0) return SHK_OK;
+  return merge_launch(c, d_keys, d_vals, n, vals_lane_stride, 0, ~0u);
+}
+
+int shk_merge_pieces(shk_ctx *c, const void *d_buf, uint32_t n_pieces, uint64_t capacity, int32_t skip_piece) {
+  SHK_TRY(single_device_only(c));
+  if (!d_buf) return SHK_ERR_BAD_ARG;
+  if (n_pieces == 0 || capacity == 0) return SHK_OK;
+  return merge_launch(c, d_buf, nullptr, (uint64_t)n_pieces * capacity, capacity, capacity, skip_piece < 0 ? ~0u : (uint32_t)skip_piece);
+}
+
+static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride,
+                        uint64_t piece_cap, uint32_t skip_piece) {
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(tb_fresh(c));
+  // (Not table_read_begin: the settle depends on ride_on.)
+  // Fixed-capacity pieces behind a counting launch nobody has looked at yet: nothing is waited for.  If that
+  // launch spilled, the senders' headers are poisoned and k_merge touches nothing; if not, what the merge spills
+  // goes on the same list (same capacity, the counter runs on) and the finalize that follows repairs it.
+  // (Only when that list could take the merge's own worst case — every entry spilling on every lane, which is what
+  // W pieces' worth of new keys do to pages sized for the local shard alone: k_merge drops what does not fit the list,
+  // and the settle that follows would fail the job with "spill list overflow" where the exact-count protocol would
+  // have finished.  A counting launch's list has a place per k-mer of the launch, so this holds whenever the pieces
+  // are no larger than the batch.)
+  const bool ride_on = piece_cap && c->unsettled && !c->acc_active && c->unsettled_spill_cap >= n * c->n_lanes &&
+                       c->spillA.cap >= c->unsettled_spill_cap * 16;
+  if (!ride_on) SHK_TRY(settle(c));
+  c->finalized = c->hist_ready = false;
+  c->zero_count_keys = true;  // (a peer's table may hold keys inserted with count 0: keep reading the keys)
+  const uint64_t spill_cap = ride_on ? c->unsettled_spill_cap : n * c->n_lanes;  // worst case every entry spills on every lane
+  if (!ride_on) {
+    HIPC(c, c->spillA.ensure(spill_cap * 16));
+    HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
+  }
+  SpillRef sp = spill_ref(c->spillA, spill_cap);
+  {
+    ScopedTimer t(c, SHK_K_MERGE);
+    hipLaunchKernelGGL(k_merge, dim3(grid_for(n, WG, 8192)), dim3(WG), 0, c->stream, c->tb, n, vals_lane_stride,
+                       (const uint64_t *)d_keys, (const uint32_t *)d_vals, c->d_stats, sp, piece_cap, skip_piece);
+  }
+  // (nothing is waited for: the outcome — spilled entries, load factor — is looked at by the next call that
+  // needs the table, at the latest finalize)
+  c->unsettled = true;
+  c->unsettled_spill_cap = spill_cap;
+  return SHK_OK;
+}
+
+int shk_set_owned_pages(shk_ctx *c, uint64_t p0, uint64_t p1) {
+  SHK_TRY(single_device_only(c));
+  if (p1 < p0 || p1 > (1ull << c->tb.log_pages)) return fail(c, SHK_ERR_BAD_ARG, "bad page range");
+  c->own_p0 = p0;
+  c->own_p1 = p1;
+  c->own_set = true;
+  c->own_share_n = 0;
+  c->finalized = c->hist_ready = false;
+  return SHK_OK;
+}
+
+int shk_set_owner_share(shk_ctx *c, uint32_t n_owners, uint32_t owner) {
+  SHK_TRY(single_device_only(c));
+  if (n_owners == 0 || (n_owners & (n_owners - 1)) || owner >= n_owners || n_owners > (1ull << c->tb.log_pages))
+    return fail(c, SHK_ERR_BAD_ARG, "bad owner share %u of %u", owner, n_owners);
+  c->own_share_n = n_owners;  // (no settle: the range is worked out from the page count of the moment a scan is launched)
+  c->own_share_id = owner;
+  c->own_set = true;
+  c->finalized = c->hist_ready = false;
+  return SHK_OK;
+}
+
+}  // extern "C"
