@@ -333,6 +333,60 @@ int shk_filter_reads(shk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets
 int shk_kmers_from_reads(shk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
                          uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte);
 
+/* threading::thread_reads / thread_reads_paired (src/pcr/threading.rs:87-192, called at src/pcr/mod.rs:663-697): a
+ * batch of reads threaded through a graph on the device; what comes back is the annotation, not the k-mers.
+ * GRAPH: any graph as arrays — node v = position v of node_sub_kmers (a (k−1)-mer ≤ (1 << 2(k−1)) − 1, k of the
+ *   context), edge e = position e of edge_src / edge_tgt (node positions): the surviving nodes and edges of the caller's
+ *   StableDiGraph in ascending NodeIndex / EdgeIndex, which is the form shk_pcr_extend hands out.
+ * EDGE K-MER: (sub_kmer[src] << 2) | (sub_kmer[tgt] & 3) (reconstruct_edge_kmer, graph.rs:127-134), whether or not the
+ *   two nodes overlap; its lookup key is min(x, revcomp(x)).  The CANDIDATES of a key are all edges with that key in
+ *   ascending edge index (build_edge_lookup, threading.rs:203-220) — any number of them, as the reference's SmallVec.
+ * PER READ: the list of kmers_from_ascii (encoding.rs:332-371): an N drops the windows that contain it and leaves no
+ *   gap, so the k-mers either side of it are neighbours in the list.  A byte outside ACGTN anywhere in the read makes
+ *   the read contribute nothing (threading.rs:98-101; read_edges = 0) and is no error of the call.  Walking the list
+ *   (find_contiguous_runs + resolve_candidates, threading.rs:233-315): prev = the edge chosen for the previous element
+ *   if that element had candidates, else none; an element with candidates chooses the first whose source is
+ *   tgt(prev), or candidate 0 when there is none or no prev; a run breaks before an element when the previous one had
+ *   no candidates or tgt(prev) != src(chosen); an element without candidates is in no run.
+ * PER RUN (threading.rs:106-118, 321-364): degrees are edge counts (parallel edges count severally, a self-loop in
+ *   both), v is a BRANCH NODE when in_deg(v) > 1 or out_deg(v) > 1.  Every consecutive pair (a, b) of a run whose
+ *   v = tgt(a) is a branch node adds 1 to the link (a, b) and makes the run ambiguous.  Every element of a run adds 1
+ *   to support_total of its edge (per occurrence), and in an unambiguous run to support_unambiguous too; a run of
+ *   one element is unambiguous.
+ * PAIRED (read_index and mate both given; mate 0 unpaired, 1 R1, 2 R2): the same annotations, and n_paired_links =
+ *   the distinct read_index / 2 for which some R1 read and some R2 read each mapped to at least one edge
+ *   (threading.rs:166-189); both mates of a pair have to be in one call.
+ * OUT: per call (additive over batches, n_paired_links excepted).  Links ascending by (in, out); link_cap too small:
+ *   SHK_ERR_BAD_ARG with n_links set to the need (the other outputs are complete then).  n_edges == 0 or n_seqs == 0:
+ *   all zero.
+ * Errors, SHK_ERR_BAD_ARG: an endpoint ≥ n_nodes, a sub_kmer above the mask, k < 2, n_nodes or n_edges ≥ 2^32,
+ *   decreasing offsets, one of read_index / mate without the other, mate > 2; also a read of 2^31 bases or more, and a
+ *   graph whose branch nodes have more than 2^31 (incoming, outgoing) pairs between them — every such pair has a
+ *   counter of its own on the device.
+ * The context's table is neither read nor written; valid whenever shk_filter_reads is, on owner shares too; a
+ * multi-device context runs it on its first device.  Tuning: SHK_THREAD_LDS_EDGES (edges, read at each call; default
+ * 2048): graphs up to that size keep their lookup set in LDS, larger ones in global memory; the result does not depend
+ * on it. */
+typedef struct shk_thread_out {   /* every pointer optional except the two support arrays */
+  uint32_t *support_total;        /* [n_edges] EdgeReadSupport.read_support_total        */
+  uint32_t *support_unambiguous;  /* [n_edges] EdgeReadSupport.read_support_unambiguous  */
+  uint32_t *link_in, *link_out, *link_counts; uint64_t link_cap, n_links;  /* BranchLink -> count */
+  uint32_t *read_edges;           /* [n_seqs] edges this read was mapped to (sum of its run lengths) */
+  uint64_t n_paired_links;        /* thread_reads_paired's paired_links.len(); 0 when mate == NULL */
+} shk_thread_out;
+/* Host buffers (bases / offsets as shk_ingest_reads): stages the batch, then as the device form. */
+int shk_thread_reads(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64_t n_nodes,
+                     const uint32_t *edge_src, const uint32_t *edge_tgt, uint64_t n_edges,
+                     const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
+                     const uint64_t *read_index, const uint8_t *mate, /* both NULL: thread_reads; else thread_reads_paired */
+                     shk_thread_out *out);
+/* The batch resident in device memory (d_bases: n_bases bytes, d_offsets: n_seqs + 1 u64, as shk_ingest_reads_device);
+ * everything else on the host.  Returns when the annotation is complete. */
+int shk_thread_reads_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64_t n_nodes,
+                            const uint32_t *edge_src, const uint32_t *edge_tgt, uint64_t n_edges,
+                            const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                            const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out);
+
 /* The bulk neighbourhood of a seed set in sPCR's extension graph: every table lookup extend_graph
  * (src/pcr/graph.rs:377-525) can make from these seeds at this threshold, fetched breadth-first on the device, many
  * levels per launch.  For a context of k-mer length k ≥ 2, mask = (1 << 2(k−1)) − 1:

@@ -1693,6 +1693,221 @@ __global__ void __launch_bounds__(WG) k_kmers_from_reads(const uint8_t *__restri
 }
 
 // ==========================================================================================
+// K_THREAD: thread_reads (src/pcr/threading.rs:87-192) for a batch of reads against a graph given as a lookup set
+// the host built (shk_thread_reads).  One WAVE per read, THREAD_TILE = 64 window start positions per
+// step, one per lane:
+//   bases      64 new bytes per step, one per lane, turned into wave-wide bit planes by ballots (code bit 0, code
+//              bit 1, N, invalid) that live in scalar registers; lane l's window is bits l … l+k−1 of two steps'
+//              planes, bit-reversed and interleaved into the k-mer (the complement planes, not reversed, give the
+//              reverse complement).  A window with an N is no list element (kmers_from_ascii drops it and leaves no
+//              gap, encoding.rs:346-352): its lane sits out, and "the previous element" of a lane is the nearest
+//              lower lane that has one — or the carry from the step before.
+//   probe      position-parallel: open addressing over min(x, revcomp(x)) → first candidate (build_edge_lookup,
+//              threading.rs:203-220).  An element with ONE candidate has its edge there and then.
+//   resolve    the only sequential step (resolve_candidates, threading.rs:233-256): elements with more candidates,
+//              in list order (a ballot and a loop over its bits, wave-uniform), each after its predecessor is final.
+//   runs       from the neighbour lanes (find_contiguous_runs, threading.rs:261-315): an element CONTINUES the run
+//              when its predecessor hit and tgt(prev) == src(this); a continuing pair over a branch node is a BRANCH
+//              PAIR (record_branch_links, threading.rs:341-364).  "some branch pair between the run's start and
+//              here" (pre) is a few mask operations on two ballots.
+// What crosses a step: the last element's (hit, target, link base, pre).  What a read's counters need and a step
+// cannot know — whether the read is valid at all (an invalid byte anywhere cancels it, threading.rs:98-101) and
+// whether the run goes on to meet a branch pair LATER (is_run_unambiguous, threading.rs:321-337) — is why the first
+// sweep only writes (edge, flags | link slot) per position to the wave's scratch, and a second sweep, last step
+// first, carrying "a branch pair between here and the run's end" (suf) the other way, does every atomic: support_total
+// per element, support_unambiguous when neither pre nor suf, the link's slot per branch pair.
+// LDS = true: the whole set lies in LDS (copied by every workgroup once; it then walks many reads) and the two
+// support counters are LDS-private, flushed at the end; false: the same code over the global arrays.
+// ==========================================================================================
+constexpr int THREAD_WG = 1024;                    // 16 waves: one workgroup per CU when the set fills its LDS
+constexpr uint32_t THREAD_TILE = 64;               // list elements per wave step (engine.py mirrors it as THREAD_TILE)
+constexpr uint32_t TH_NONE = 0xFFFFFFFFu;          // no edge / no link base (edge indices and slots stay below)
+static_assert(THREAD_TILE == 64, "one window per lane of a wave");
+constexpr int THREAD_LDS_EDGES = 2048;             // graphs up to this many edges keep their set in LDS (SHK_THREAD_LDS_EDGES) …
+constexpr size_t THREAD_LDS_MAX = 128u << 10;      // … if it fits this much of a CU's 160 KiB (2048 edges: at most 104.3 KiB)
+
+struct ThreadSet {
+  const uint64_t *keys;   // [mask + 1] canonical edge k-mer or EMPTY, open addressing by set_hash, load ≤ 1/2
+  const uint32_t *start;  // [mask + 1] the key's first candidate in cand
+  const uint32_t *cand;   // [n_edges] edges ascending by (key, edge)
+  const uint32_t *last;   // bit i: cand[i] is the last candidate of its key
+  const uint4 *meta;      // [n_edges] {src, tgt, link slot base of the pairs (e, ·) or TH_NONE, rank of e among its source's out-edges}
+  uint32_t mask;
+  uint32_t n_edges;
+};
+// bytes of LDS the set and the two private counters take (the order of k_thread_reads<true>)
+__host__ __device__ inline size_t thread_lds_bytes(uint32_t cap, uint32_t n_edges) {
+  return (size_t)cap * 12 + (size_t)n_edges * 28 + (size_t)((n_edges + 31) / 32) * 4;
+}
+
+// bit i of x → bit 2i
+__device__ __forceinline__ uint64_t spread2(uint32_t x) {
+  uint64_t v = x;
+  v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
+  v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
+  v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
+  v = (v | (v << 2)) & 0x3333333333333333ull;
+  v = (v | (v << 1)) & 0x5555555555555555ull;
+  return v;
+}
+// bits l … l+31 of the 128-bit value hi:lo (l < 64)
+__device__ __forceinline__ uint32_t window32(uint64_t lo, uint64_t hi, uint32_t l) {
+  return (uint32_t)((lo >> l) | ((hi << 1) << (63 - l)));
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                            uint64_t n_seqs, int k, ThreadSet gs, uint2 *__restrict__ scratch,
+                                                            uint32_t scr_stride, uint32_t *__restrict__ total,
+                                                            uint32_t *__restrict__ unamb, uint32_t *__restrict__ links,
+                                                            uint32_t *__restrict__ read_edges) {
+  extern __shared__ __align__(16) uint8_t th_lds[];
+  const uint32_t cap = gs.mask + 1, E = gs.n_edges;
+  uint64_t *lk = (uint64_t *)th_lds;  // (cap ≥ 16: every array below starts 16-byte aligned where it has to)
+  uint4 *lm = (uint4 *)(lk + cap);
+  uint32_t *ls = (uint32_t *)(lm + E), *lc = ls + cap, *ll = lc + E, *lt = ll + (E + 31) / 32, *lu = lt + E;
+  if (LDS) {
+    for (uint32_t i = threadIdx.x; i < cap; i += THREAD_WG) lk[i] = gs.keys[i], ls[i] = gs.start[i];
+    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gs.meta[i], lc[i] = gs.cand[i], lt[i] = 0, lu[i] = 0;
+    for (uint32_t i = threadIdx.x; i < (E + 31) / 32; i += THREAD_WG) ll[i] = gs.last[i];
+    __syncthreads();
+  }
+  const uint64_t *keys = LDS ? lk : gs.keys;
+  const uint32_t *start = LDS ? ls : gs.start, *cand = LDS ? lc : gs.cand, *last = LDS ? ll : gs.last;
+  const uint4 *meta = LDS ? lm : gs.meta;
+  uint32_t *ctot = LDS ? lt : total, *cun = LDS ? lu : unamb;
+
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (THREAD_WG / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t n_waves = (uint64_t)gridDim.x * (THREAD_WG / 64);
+  uint2 *scr = scratch + wave * scr_stride;
+  const uint32_t km = (1u << k) - 1u;         // k ≤ 31
+  const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
+  const uint64_t upto = below | (1ull << lane);
+
+  for (uint64_t r = wave; r < n_seqs; r += n_waves) {
+    const uint64_t b0 = offsets[r];
+    const uint32_t len = (uint32_t)(offsets[r + 1] - b0);
+    const uint32_t n_win = len >= (uint32_t)k ? len - (uint32_t)k + 1u : 0u;  // (a shorter read has no k-mer, valid or not)
+    const uint8_t *rb = bases + b0;
+    uint32_t n_hit = 0;
+    bool bad = false;
+    // ---- sweep 1, first step first: edges, run flags, link slots → scratch
+    uint32_t c_hit = 0, c_tgt = 0, c_lbase = TH_NONE, c_pre = 0;  // the last list element so far
+    uint64_t p0lo = 0, p1lo = 0, nlo = 0;
+    if (n_win) {
+      const uint32_t c = lane < len ? rb[lane] : (uint32_t)'A';
+      const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
+      p0lo = __ballot(b2 & 1u), p1lo = __ballot(b2 >> 1), nlo = __ballot(c == 'N');
+      bad = __ballot(!byte_is_acgtn(c)) != 0;
+    }
+    for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
+      const uint32_t p = s0 + THREAD_TILE + lane;  // the step's new bytes: the upper half of its windows' span
+      const uint32_t c = p < len ? rb[p] : (uint32_t)'A';
+      const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
+      const uint64_t p0hi = __ballot(b2 & 1u), p1hi = __ballot(b2 >> 1), nhi = __ballot(c == 'N');
+      if (__ballot(!byte_is_acgtn(c)) != 0) {  // encoding.rs:353-356 → Err → the read is skipped whole
+        bad = true;
+        break;
+      }
+      const bool v = s0 + lane < n_win && (window32(nlo, nhi, lane) & km) == 0;  // a list element
+      uint32_t edge = TH_NONE, src = 0, tgt = 0, lbase = TH_NONE, orank = 0, cstart = 0;
+      int hit = 0;
+      bool multi = false;
+      if (v) {
+        const uint32_t w0 = window32(p0lo, p0hi, lane) & km, w1 = window32(p1lo, p1hi, lane) & km;
+        const uint64_t fwd = spread2(__brev(w0) >> (32 - k)) | (spread2(__brev(w1) >> (32 - k)) << 1);
+        const uint64_t rev = spread2(~w0 & km) | (spread2(~w1 & km) << 1);
+        const uint64_t key = fwd < rev ? fwd : rev;
+        for (uint32_t s = set_hash(key) & gs.mask;; s = (s + 1) & gs.mask) {
+          const uint64_t cur = keys[s];
+          if (cur == key) hit = 1, cstart = start[s];
+          if (cur == key || cur == EMPTY) break;
+        }
+        if (hit) {
+          multi = !((last[cstart >> 5] >> (cstart & 31u)) & 1u);
+          if (!multi) {
+            edge = cand[cstart];
+            const uint4 m = meta[edge];
+            src = m.x, tgt = m.y, lbase = m.z, orank = m.w;
+          }
+        }
+      }
+      const uint64_t vm = __ballot(v);
+      for (uint64_t mm = __ballot(multi); mm; mm &= mm - 1) {  // in list order; everything here is wave-uniform
+        const int m = __ffsll((unsigned long long)mm) - 1;
+        const uint64_t under = vm & ((1ull << m) - 1);
+        const int pl = under ? 63 - __clzll((long long)under) : 0;
+        const int sh = __shfl(hit, pl);
+        const uint32_t st = __shfl(tgt, pl);
+        const bool ph = under ? sh != 0 : c_hit != 0;
+        const uint32_t pt = under ? st : c_tgt;
+        const uint32_t first = __shfl(cstart, m);
+        uint32_t pick = cand[first];  // no previous edge, or none adjacent: candidate 0 (threading.rs:255)
+        if (ph)
+          for (uint32_t i = first;; ++i) {
+            const uint32_t e = cand[i];
+            if (meta[e].x == pt) {
+              pick = e;
+              break;
+            }
+            if ((last[i >> 5] >> (i & 31u)) & 1u) break;
+          }
+        const uint4 pm = meta[pick];
+        if ((int)lane == m) edge = pick, src = pm.x, tgt = pm.y, lbase = pm.z, orank = pm.w;
+      }
+      // my predecessor in the list
+      const uint64_t under = vm & below;
+      const int pl = under ? 63 - __clzll((long long)under) : 0;
+      const int sh = __shfl(hit, pl);
+      const uint32_t st = __shfl(tgt, pl), sl = __shfl(lbase, pl);
+      const bool ph = under ? sh != 0 : c_hit != 0;
+      const uint32_t pt = under ? st : c_tgt, plb = under ? sl : c_lbase;
+      const bool cont = hit && ph && pt == src;
+      const bool bp = cont && plb != TH_NONE;
+      const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
+      const uint64_t s_le = sm & upto;
+      const bool pre = s_le ? (bm & upto & ~((1ull << (63 - __clzll((long long)s_le))) - 1)) != 0 : ((bm & upto) != 0 || c_pre != 0);
+      scr[s0 + lane] = make_uint2(edge, bp ? plb + orank : 0x80000000u | (v ? 4u : 0u) | (pre ? 2u : 0u) | (cont ? 1u : 0u));
+      n_hit += (uint32_t)__popcll(__ballot(hit));
+      if (vm) {
+        const int top = 63 - __clzll((long long)vm);
+        c_hit = (uint32_t)__shfl(hit, top), c_tgt = __shfl(tgt, top), c_lbase = __shfl(lbase, top);
+        c_pre = (uint32_t)__shfl((int)pre, top);
+      }
+      p0lo = p0hi, p1lo = p1hi, nlo = nhi;
+    }
+    if (bad) n_hit = 0;
+    if (read_edges && lane == 0) read_edges[r] = n_hit;
+    if (!n_hit) continue;
+    // ---- sweep 2, last step first: the atomics
+    __threadfence_block();  // the wave reads what its other lanes wrote
+    uint32_t c_suf = 0;     // a branch pair between the next step's start and the end of the run that enters it
+    for (uint32_t s0 = (n_win - 1) & ~(THREAD_TILE - 1);; s0 -= THREAD_TILE) {
+      const uint2 q = scr[s0 + lane];
+      const bool bp = !(q.y >> 31), v = bp || (q.y & 4u), cont = bp || (q.y & 1u), pre = bp || (q.y & 2u);
+      const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
+      const uint64_t s_gt = sm & ~upto;
+      const bool suf = s_gt ? (bm & ~upto & ((1ull << (__ffsll((unsigned long long)s_gt) - 1)) - 1)) != 0 : ((bm & ~upto) != 0 || c_suf != 0);
+      if (q.x != TH_NONE) {
+        atomicAdd(&ctot[q.x], 1u);
+        if (!pre && !suf) atomicAdd(&cun[q.x], 1u);
+      }
+      if (bp) atomicAdd(&links[q.y], 1u);
+      c_suf = sm ? (bm & ((1ull << (__ffsll((unsigned long long)sm) - 1)) - 1)) != 0 : (bm != 0 || c_suf != 0);
+      if (s0 == 0) break;
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) {
+      if (lt[i]) atomicAdd(&total[i], lt[i]);
+      if (lu[i]) atomicAdd(&unamb[i], lu[i]);
+    }
+  }
+}
+
+// ==========================================================================================
 // K_OWNER_COUNTS / K_COMPACT_OWNERS: the sender side of the multi-GPU merge.  Owner o of W owns the
 // slots [o·spo, (o+1)·spo) (a contiguous page range).  Instead of shipping its range as it lies
 // in the table — EMPTY slots included, ≥ half of it — a rank ships only the occupied (key, counts)

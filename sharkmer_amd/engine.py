@@ -148,6 +148,26 @@ class PcrGraph:
     steps_run: int
 
 
+THREAD_TILE = 64  # the list elements one wave step of k_thread_reads covers (THREAD_TILE in csrc/shk_device.hip.h)
+
+
+class _ThreadOut(C.Structure):
+    _fields_ = [("support_total", C.c_void_p), ("support_unambiguous", C.c_void_p), ("link_in", C.c_void_p),
+                ("link_out", C.c_void_p), ("link_counts", C.c_void_p), ("link_cap", C.c_uint64), ("n_links", C.c_uint64),
+                ("read_edges", C.c_void_p), ("n_paired_links", C.c_uint64)]
+
+
+@dataclass
+class ThreadingAnnotations:
+    """What shk_thread_reads returns: ThreadingAnnotations of pcr/threading.rs:54-62 as arrays."""
+    support_total: np.ndarray        # u32 per edge, EdgeReadSupport.read_support_total
+    support_unambiguous: np.ndarray  # u32 per edge, EdgeReadSupport.read_support_unambiguous
+    links: np.ndarray                # m × 2 u32 (incoming edge, outgoing edge), ascending
+    link_counts: np.ndarray          # u32 per link
+    read_edges: np.ndarray           # u32 per read: edges it was mapped to
+    n_paired_links: int              # paired_links.len(); 0 for the unpaired form
+
+
 def pcr_node_budget(n_bases_ingested: int) -> int:
     """compute_node_budget (pcr/graph.rs:40-52)."""
     return int(load_library().shk_pcr_node_budget(n_bases_ingested))
@@ -177,6 +197,7 @@ ABI_SYMBOLS = [
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
     "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget",
+    "shk_thread_reads", "shk_thread_reads_device",
 ]
 
 _lib = None
@@ -301,6 +322,8 @@ def load_library():
     L.shk_pcr_extend.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(_PcrExtendParams), vp, vp, u64, C.POINTER(u64),
                                  vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.shk_pcr_node_budget.argtypes = [u64]
+    L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
+    L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_pcr_node_budget.restype = u64
     L.shk_owner_counts.argtypes = [vp, u32, vp]
     L.shk_compact_owners.argtypes = [vp, u32, vp, vp, vp, u64, C.c_int32]
@@ -634,6 +657,53 @@ class KmerEngine:
             self._check(rcode)
             return PcrGraph(sub[:n].copy(), flags[:n].copy(), es[:e].copy(), et[:e].copy(), ec[:e].copy(),
                             bool(found.value), int(thr.value), int(steps.value))
+
+    def thread_reads(self, graph, bases, offsets, read_index=None, mate=None, device: bool = False) -> ThreadingAnnotations:
+        """thread_reads / thread_reads_paired (pcr/threading.rs:87-192) of a batch through `graph` — a PcrGraph or a
+        (node_sub_kmers, edge_src, edge_tgt) tuple, any graph at all — on the device (shk_thread_reads).  read_index
+        and mate (0 unpaired, 1 R1, 2 R2) together give the paired form.  device=True: bases and offsets are torch
+        tensors on this context's device (shk_thread_reads_device)."""
+        if isinstance(graph, PcrGraph):
+            graph = (graph.node_sub_kmers, graph.edge_src, graph.edge_tgt)
+        sub = np.ascontiguousarray(graph[0], dtype=np.uint64)
+        es = np.ascontiguousarray(graph[1], dtype=np.uint32)
+        et = np.ascontiguousarray(graph[2], dtype=np.uint32)
+        if len(es) != len(et):
+            raise ValueError("edge_src and edge_tgt differ in length")
+        n = len(offsets) - 1
+        ne = len(es)
+        ri = None if read_index is None else np.ascontiguousarray(read_index, dtype=np.uint64)
+        mt = None if mate is None else np.ascontiguousarray(mate, dtype=np.uint8)
+        for a in (ri, mt):
+            if a is not None and len(a) != n:
+                raise ValueError("read_index and mate take one entry per read")
+        tot, una = np.zeros(max(ne, 1), dtype=np.uint32), np.zeros(max(ne, 1), dtype=np.uint32)
+        re = np.zeros(max(n, 1), dtype=np.uint32)
+        if device:
+            args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
+            call = self._L.shk_thread_reads_device
+        else:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            args = (bases.ctypes.data, offsets.ctypes.data, n)
+            call = self._L.shk_thread_reads
+        # room for every link there can be: Σ in_deg · out_deg over the branch nodes (the retry is for graphs beyond 2^22)
+        ind, outd = (np.bincount(a, minlength=len(sub) + 1).astype(np.int64) for a in (et, es))
+        m = min(len(ind), len(outd))
+        link_cap = max(1, min(int((ind[:m] * outd[:m])[(ind[:m] > 1) | (outd[:m] > 1)].sum()), 1 << 22))
+        while True:
+            li, lo, lc = (np.zeros(link_cap, dtype=np.uint32) for _ in range(3))
+            out = _ThreadOut(tot.ctypes.data, una.ctypes.data, li.ctypes.data, lo.ctypes.data, lc.ctypes.data, link_cap, 0,
+                             re.ctypes.data, 0)
+            rcode = call(self._h, sub.ctypes.data, len(sub), es.ctypes.data, et.ctypes.data, ne, *args,
+                         None if ri is None else ri.ctypes.data, None if mt is None else mt.ctypes.data, C.byref(out))
+            m = int(out.n_links)
+            if rcode == -2 and m > link_cap:  # the link arrays were too small: it says what it needs
+                link_cap = m
+                continue
+            self._check(rcode)
+            return ThreadingAnnotations(tot[:ne].copy(), una[:ne].copy(), np.stack([li[:m], lo[:m]], axis=1), lc[:m].copy(),
+                                        re[:n].copy(), int(out.n_paired_links))
 
     def filter_reads(self, bases: np.ndarray, offsets: np.ndarray, primer_kmers) -> np.ndarray:
         """PrimerReadFilter::matches per read (pcr/read_filter.rs:43-55) → bool array."""
