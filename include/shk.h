@@ -387,6 +387,50 @@ int shk_thread_reads_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64
                             const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                             const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out);
 
+/* PrimerReadFilter::filter_reads (src/pcr/read_filter.rs:24-55) for a whole sPCR panel in ONE pass over the batch:
+ * do_pcr runs once per gene (stats.rs:85-87) and filters every retained read against that gene's primer k-mers
+ * (pcr/mod.rs:470-485); this call walks the reads once and answers for all n_genes genes.
+ * PANEL: gene g's primer set is primer_kmers[gene_offsets[g] .. gene_offsets[g+1]) (gene_offsets: n_genes + 1 entries,
+ *   non-decreasing): canonical 2-bit k-mers (k of the context), the union of the gene's forward and reverse tables
+ *   (from_primer_kmers, read_filter.rs:24-41).  Duplicates inside a gene are allowed, a k-mer may be in any number
+ *   of genes, a gene may be empty.  n_genes ≤ SHK_FILTER_MAX_GENES: every wave of the kernel keeps one bit per gene in
+ *   LDS, 512 bytes × the 16 waves of a workgroup at the limit.
+ * MATCH: read i matches gene g exactly when PrimerReadFilter::matches (read_filter.rs:43-49) is true for it against
+ *   g's set: no byte outside ACGTN anywhere in the read, and at least one of its kmers_from_ascii k-mers in the set.
+ *   A window that contains an N is not a k-mer; a read shorter than k matches nothing; a read with an invalid byte,
+ *   wherever it lies, matches no gene and is no error of the call.
+ * OUT: match_reads[match_offsets[g] .. match_offsets[g+1]) are the indices of the reads that match gene g, ascending —
+ *   the order of filter_reads (read_filter.rs:52-54); match_offsets has n_genes + 1 entries, *n_matches is the total.
+ *   match_cap too small: SHK_ERR_BAD_ARG with *n_matches set to the need and match_offsets complete.  n_genes == 0 or
+ *   n_seqs == 0: all zero.  With n_genes == 1 the list is the positions where shk_filter_reads writes 1.
+ * Errors, SHK_ERR_BAD_ARG: decreasing gene_offsets or read offsets, a k-mer that does not fit k bases, a read of 2^31
+ *   bases or more, n_genes above SHK_FILTER_MAX_GENES.
+ * The context's table is neither read nor written; valid whenever shk_filter_reads is, on owner shares too; a
+ * multi-device context runs it on its first device.  Tuning, both read at each call, neither changes the result:
+ * SHK_FILTER_LDS_KEYS (distinct k-mers of the panel, default 4096): panels up to that size keep their lookup set in
+ * LDS (if it fits 128 KiB), larger ones in global memory; SHK_FILTER_CANDIDATES ((gene, read) records, default 2^20)
+ * sizes the first pass's record list — when it overflows, the pass has counted the records and is rerun with room
+ * for exactly that many. */
+#define SHK_FILTER_MAX_GENES 4096
+/* Host buffers (bases / offsets as shk_ingest_reads): stages the batch, then as the device form. */
+int shk_filter_reads_panel(shk_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
+                           const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes,
+                           uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches);
+/* The batch resident in device memory (d_bases: n_bases bytes, d_offsets: n_seqs + 1 u64, as shk_ingest_reads_device);
+ * the panel and the outputs on the host. */
+int shk_filter_reads_panel_device(shk_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                                  const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes,
+                                  uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches);
+/* A subset of a device-resident batch as a batch of its own, on the device — what carries a gene's match list to
+ * shk_thread_reads_device without the reads leaving HBM.  read_ids (host; any order, repeats allowed, each below
+ * n_seqs) name reads of (d_bases, d_offsets); they are copied into d_out_bases back to back in list order,
+ * d_out_offsets gets n_ids + 1 u64 starting at 0, *n_out_bases is the total.  The call copies d_offsets back (8 bytes
+ * per read) to size and place the output.  out_bases_cap too small: SHK_ERR_BAD_ARG with *n_out_bases set to the need
+ * and nothing written.  Also SHK_ERR_BAD_ARG: an id ≥ n_seqs, decreasing offsets.  Stateless like the filter. */
+int shk_gather_reads_device(shk_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs,
+                            const uint64_t *read_ids, uint64_t n_ids,
+                            void *d_out_bases, uint64_t out_bases_cap, void *d_out_offsets, uint64_t *n_out_bases);
+
 /* The bulk neighbourhood of a seed set in sPCR's extension graph: every table lookup extend_graph
  * (src/pcr/graph.rs:377-525) can make from these seeds at this threshold, fetched breadth-first on the device, many
  * levels per launch.  For a context of k-mer length k ≥ 2, mask = (1 << 2(k−1)) − 1:

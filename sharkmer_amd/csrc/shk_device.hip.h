@@ -1908,6 +1908,156 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
 }
 
 // ==========================================================================================
+// K_FILTER_PANEL: PrimerReadFilter::matches (src/pcr/read_filter.rs:43-49) of every read of a batch against every
+// gene of a panel in one walk (shk_filter_reads_panel).  The lookup set the host built maps a canonical
+// k-mer to the genes that hold it.  One WAVE per read, 64 window start positions per step as in K_THREAD:
+//   bases      64 new bytes per step, one per lane, turned into the code, N and invalid bit planes by four ballots
+//              (read_planes); lane l's window is bits l … l+k−1 of two steps' planes, so every byte is loaded once.
+//   probe      position-parallel; a read of a run mostly belongs to no amplicon, so the common step is load, four
+//              ballots and one probe that ends on an EMPTY slot.
+//   hit        the lane ORs its key's genes into the wave's bitmap of n_genes bits in LDS.
+//   emit       only behind the read's last byte — a later invalid byte cancels the read (kmers_from_ascii fails as
+//              a whole, encoding.rs:353-356): the lanes walk the bitmap's words, append one (gene, read) record per
+//              set bit to a global list (a ballot and one atomic per round, as k_primer_scan) and clear the words;
+//              an invalid read only clears.  Records past `cap` are counted, not written: the host reruns with room.
+// A record is gene << FILTER_READ_BITS | read, so that sorting the list as numbers gives (gene, read).
+// LDS = true: keys and gene runs are copied into LDS by every workgroup once; false: the global arrays, which L2 serves.
+// ==========================================================================================
+constexpr int FILTER_WG = 1024;                    // 16 waves, as K_THREAD
+constexpr uint32_t FILTER_MAX_GENES = 4096;        // a wave's bitmap: 512 bytes at the limit, 8 KiB per workgroup
+static_assert(FILTER_MAX_GENES == SHK_FILTER_MAX_GENES, "the header states the limit");
+constexpr int FILTER_LDS_KEYS = 4096;              // panels up to this many distinct keys keep their set in LDS (SHK_FILTER_LDS_KEYS) …
+constexpr size_t FILTER_LDS_MAX = 128u << 10;      // … if set and bitmaps fit this much of a CU's 160 KiB
+constexpr int FILTER_READ_BITS = 52;               // of a record; the gene above (12 bits)
+static_assert((FILTER_MAX_GENES - 1) >> (64 - FILTER_READ_BITS) == 0, "a gene fits a record's top bits");
+
+struct PanelSet {
+  const uint64_t *keys;   // [mask + 1] canonical primer k-mer or EMPTY, open addressing by set_hash, load ≤ 1/2
+  const uint32_t *start;  // [mask + 1] the key's first entry in genes
+  const uint32_t *genes;  // [n_pairs] gene ids by (key, gene), each (key, gene) once
+  const uint32_t *last;   // bit i: genes[i] is the last gene of its key
+  uint32_t mask, n_pairs, n_genes;
+};
+// bytes of dynamic LDS: the 16 bitmaps first (both variants), then the set (k_filter_panel<true>)
+__host__ __device__ inline size_t filter_bitmap_bytes(uint32_t n_genes) { return (size_t)(FILTER_WG / 64) * ((n_genes + 31) / 32) * 4; }
+__host__ __device__ inline size_t filter_set_bytes(uint32_t cap, uint32_t n_pairs) {
+  return (size_t)cap * 12 + (size_t)n_pairs * 4 + (size_t)((n_pairs + 31) / 32) * 4;
+}
+
+// One step's bytes rb[p0 + lane] (beyond len: 'A') as wave-wide bit planes: code bit 0, code bit 1, N, and whether any
+// of them is outside ACGTN.
+struct ReadPlanes {
+  uint64_t p0, p1, n;
+  bool bad;
+};
+__device__ __forceinline__ ReadPlanes read_planes(const uint8_t *__restrict__ rb, uint32_t p, uint32_t len) {
+  const uint32_t c = p < len ? rb[p] : (uint32_t)'A';
+  const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
+  return ReadPlanes{__ballot(b2 & 1u), __ballot(b2 >> 1), __ballot(c == 'N'), __ballot(!byte_is_acgtn(c)) != 0};
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                            uint64_t n_seqs, int k, PanelSet gs, unsigned long long *__restrict__ out,
+                                                            uint64_t cap, unsigned long long *__restrict__ n_out) {
+  extern __shared__ __align__(16) uint8_t fp_lds[];
+  const uint32_t n_words = (gs.n_genes + 31) / 32, scap = gs.mask + 1, P = gs.n_pairs;
+  uint32_t *bm_all = (uint32_t *)fp_lds;  // (16 · n_words words: a multiple of 64 bytes, so the keys behind stay aligned)
+  uint64_t *lk = (uint64_t *)(bm_all + (FILTER_WG / 64) * n_words);
+  uint32_t *ls = (uint32_t *)(lk + (LDS ? scap : 0)), *lg = ls + (LDS ? scap : 0), *ll = lg + (LDS ? P : 0);
+  for (uint32_t i = threadIdx.x; i < (FILTER_WG / 64) * n_words; i += FILTER_WG) bm_all[i] = 0;
+  if (LDS) {
+    for (uint32_t i = threadIdx.x; i < scap; i += FILTER_WG) lk[i] = gs.keys[i], ls[i] = gs.start[i];
+    for (uint32_t i = threadIdx.x; i < P; i += FILTER_WG) lg[i] = gs.genes[i];
+    for (uint32_t i = threadIdx.x; i < (P + 31) / 32; i += FILTER_WG) ll[i] = gs.last[i];
+  }
+  __syncthreads();
+  const uint64_t *keys = LDS ? lk : gs.keys;
+  const uint32_t *start = LDS ? ls : gs.start, *genes = LDS ? lg : gs.genes, *last = LDS ? ll : gs.last;
+
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t wave = (uint64_t)blockIdx.x * (FILTER_WG / 64) + wib;
+  const uint64_t n_waves = (uint64_t)gridDim.x * (FILTER_WG / 64);
+  uint32_t *bm = bm_all + wib * n_words;      // this wave's bitmap: all zero between two reads
+  const uint32_t km = (1u << k) - 1u;         // k ≤ 31
+  const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
+
+  for (uint64_t r = wave; r < n_seqs; r += n_waves) {
+    const uint64_t b0 = offsets[r];
+    const uint32_t len = (uint32_t)(offsets[r + 1] - b0);
+    if (len < (uint32_t)k) continue;  // no k-mer, valid or not: matches nothing
+    const uint32_t n_win = len - (uint32_t)k + 1u;
+    const uint8_t *rb = bases + b0;
+    ReadPlanes lo = read_planes(rb, lane, len);
+    bool bad = lo.bad, any = false;
+    for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += 64) {
+      const ReadPlanes hi = read_planes(rb, s0 + 64 + lane, len);  // the step's new bytes: the upper half of its windows' span
+      if (hi.bad) {  // encoding.rs:353-356 → Err → matches() is false for every gene
+        bad = true;
+        break;
+      }
+      bool hit = false;
+      if (s0 + lane < n_win && (window32(lo.n, hi.n, lane) & km) == 0) {  // a window without an N: a k-mer
+        const uint32_t w0 = window32(lo.p0, hi.p0, lane) & km, w1 = window32(lo.p1, hi.p1, lane) & km;
+        const uint64_t fwd = spread2(__brev(w0) >> (32 - k)) | (spread2(__brev(w1) >> (32 - k)) << 1);
+        const uint64_t rev = spread2(~w0 & km) | (spread2(~w1 & km) << 1);
+        const uint64_t key = fwd < rev ? fwd : rev;
+        for (uint32_t s = set_hash(key) & gs.mask;; s = (s + 1) & gs.mask) {
+          const uint64_t cur = keys[s];
+          if (cur == key) {
+            hit = true;
+            for (uint32_t i = start[s];; ++i) {
+              const uint32_t g = genes[i];
+              atomicOr(&bm[g >> 5], 1u << (g & 31u));
+              if ((last[i >> 5] >> (i & 31u)) & 1u) break;
+            }
+          }
+          if (cur == key || cur == EMPTY) break;
+        }
+      }
+      any |= __ballot(hit) != 0;
+      lo = hi;
+    }
+    if (!any) continue;
+    __threadfence_block();  // the wave reads what its other lanes set
+    for (uint32_t w0 = 0; w0 < n_words; w0 += 64) {
+      const uint32_t wi = w0 + lane;
+      uint32_t word = wi < n_words ? bm[wi] : 0u;
+      if (word) bm[wi] = 0;
+      if (bad) word = 0;  // an invalid read clears and emits nothing
+      for (uint64_t m = __ballot(word != 0); m; m = __ballot(word != 0)) {  // a round: every lane's lowest gene
+        unsigned long long at = 0;
+        if (lane == 0) at = atomicAdd(n_out, (unsigned long long)__popcll(m));
+        at = __shfl(at, 0);
+        if (word) {
+          const uint32_t g = wi * 32u + (uint32_t)__ffs((int)word) - 1u;
+          const unsigned long long i = at + (unsigned long long)__popcll(m & below);
+          if (i < cap) out[i] = ((unsigned long long)g << FILTER_READ_BITS) | r;
+          word &= word - 1u;
+        }
+      }
+    }
+    __threadfence_block();  // the cleared words, before the next read's hits
+  }
+}
+
+// K_GATHER_READS: reads ids[j] of a batch copied back to back into a batch of their own (shk_gather_reads_device):
+// one wave per read, its lanes on consecutive bytes.  out_offsets is the host's prefix sum of the lengths.
+__global__ void __launch_bounds__(WG) k_gather_reads(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                     const uint64_t *__restrict__ ids, uint64_t n_ids,
+                                                     const uint64_t *__restrict__ out_offsets, uint8_t *__restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t wave = (uint64_t)blockIdx.x * (WG / 64) + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * (WG / 64);
+  for (uint64_t j = wave; j < n_ids; j += n_waves) {
+    const uint64_t id = ids[j], b0 = offsets[id], len = offsets[id + 1] - b0;
+    const uint8_t *src = bases + b0;
+    uint8_t *dst = out + out_offsets[j];
+    for (uint64_t p = lane; p < len; p += 64) dst[p] = src[p];
+  }
+}
+
+// ==========================================================================================
 // K_OWNER_COUNTS / K_COMPACT_OWNERS: the sender side of the multi-GPU merge.  Owner o of W owns the
 // slots [o·spo, (o+1)·spo) (a contiguous page range).  Instead of shipping its range as it lies
 // in the table — EMPTY slots included, ≥ half of it — a rank ships only the occupied (key, counts)

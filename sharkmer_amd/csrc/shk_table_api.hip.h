@@ -727,7 +727,8 @@ void thread_out_zero(shk_thread_out *out, uint64_t n_edges, uint64_t n_seqs) {
 }
 
 // offsets as a batch of reads over n_bases bytes (a read's length is a 31-bit number in the kernel)
-int thread_check_offsets(shk_ctx *c, const uint64_t *offsets, uint64_t n_seqs, uint64_t n_bases, uint64_t *max_len) {
+int thread_check_offsets(shk_ctx *c, const uint64_t *offsets, uint64_t n_seqs, uint64_t n_bases, uint64_t *max_len,
+                         const char *who = "shk_thread_reads") {
   *max_len = 0;
   for (uint64_t i = 0; i < n_seqs; ++i) {
     if (offsets[i + 1] < offsets[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
@@ -735,7 +736,7 @@ int thread_check_offsets(shk_ctx *c, const uint64_t *offsets, uint64_t n_seqs, u
   }
   if (offsets[n_seqs] > n_bases)
     return fail(c, SHK_ERR_BAD_ARG, "offsets end at %llu, beyond the %llu bases", (unsigned long long)offsets[n_seqs], (unsigned long long)n_bases);
-  if (*max_len >= (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "a read of %llu bases: shk_thread_reads takes reads below 2^31", (unsigned long long)*max_len);
+  if (*max_len >= (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "a read of %llu bases: %s takes reads below 2^31", (unsigned long long)*max_len, who);
   return SHK_OK;
 }
 
@@ -879,6 +880,236 @@ int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_node
   if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
   return thread_core(c, pl, (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, max_len, n_seqs, read_index, mate, out);
+}
+
+namespace {
+
+// A panel as k_filter_panel wants it: the distinct k-mers of all genes in one open-addressing table,
+// each with the run of genes that hold it — ThreadPlan's keys / start / cand / last without the edge words.
+struct PanelPlan {
+  std::vector<uint64_t> keys;                // open addressing by set_hash, EMPTY where free, load ≤ 1/2
+  std::vector<uint32_t> start, genes, last;  // a key's first gene; gene ids by (key, gene), each pair once; bit i: genes[i] ends its key's run
+  uint64_t n_keys = 0;
+};
+
+// Everything the panel filter refuses before the device is touched, and the plan of a panel that has k-mers.
+int panel_plan(shk_ctx *c, const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes, PanelPlan *pl) {
+  const uint32_t k = c->cfg.k;
+  if (n_genes > FILTER_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u is above the limit of %u", n_genes, FILTER_MAX_GENES);
+  if (!n_genes) return SHK_OK;
+  if (!gene_offsets) return SHK_ERR_BAD_ARG;
+  for (uint32_t g = 0; g < n_genes; ++g)
+    if (gene_offsets[g + 1] < gene_offsets[g]) return fail(c, SHK_ERR_BAD_ARG, "gene_offsets must be non-decreasing");
+  const uint64_t k0 = gene_offsets[0], k1 = gene_offsets[n_genes];
+  if (k1 > k0 && !primer_kmers) return SHK_ERR_BAD_ARG;
+  if (k1 - k0 > (1ull << 30)) return fail(c, SHK_ERR_NOMEM, "panel of %llu k-mers: the lookup set would not fit", (unsigned long long)(k1 - k0));
+  std::vector<std::pair<uint64_t, uint32_t>> pairs;
+  pairs.reserve(k1 - k0);
+  for (uint32_t g = 0; g < n_genes; ++g)
+    for (uint64_t j = gene_offsets[g]; j < gene_offsets[g + 1]; ++j) {
+      const uint64_t key = primer_kmers[j];
+      if ((key >> (2 * k)) != 0)  // (k ≤ 31)
+        return fail(c, SHK_ERR_BAD_ARG, "primer k-mer %llu does not fit %u bases", (unsigned long long)key, k);
+      pairs.emplace_back(key, g);
+    }
+  std::sort(pairs.begin(), pairs.end());
+  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+  const uint32_t P = (uint32_t)pairs.size();
+  if (!P) return SHK_OK;
+  for (uint32_t i = 0; i < P; ++i) pl->n_keys += i == 0 || pairs[i].first != pairs[i - 1].first;
+  uint64_t cap = 16;
+  while (cap < 2 * pl->n_keys) cap <<= 1;
+  pl->keys.assign(cap, EMPTY);
+  pl->start.assign(cap, 0);
+  pl->genes.resize(P);
+  pl->last.assign((P + 31) / 32, 0);
+  for (uint32_t i = 0; i < P; ++i) {
+    const uint64_t key = pairs[i].first;
+    pl->genes[i] = pairs[i].second;
+    if (i + 1 == P || pairs[i + 1].first != key) pl->last[i >> 5] |= 1u << (i & 31);
+    if (i && pairs[i - 1].first == key) continue;
+    uint64_t s = set_hash(key) & (cap - 1);
+    while (pl->keys[s] != EMPTY) s = (s + 1) & (cap - 1);
+    pl->keys[s] = key;
+    pl->start[s] = i;
+  }
+  return SHK_OK;
+}
+
+// One k_filter_panel pass with room for `room` records: *n_total = the records the batch has; recs = all of them when
+// they fit (else empty).  The batch is resident, its offsets checked; the context is settled and its stream idle.
+int panel_pass(shk_ctx *c, const PanelPlan &pl, uint32_t n_genes, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs,
+               uint64_t room, std::vector<uint64_t> *recs, uint64_t *n_total) {
+  const uint32_t cap = (uint32_t)pl.keys.size(), P = (uint32_t)pl.genes.size();
+  const int lds_keys = env_int("SHK_FILTER_LDS_KEYS", FILTER_LDS_KEYS);
+  const size_t bitmaps = filter_bitmap_bytes(n_genes), lds = bitmaps + filter_set_bytes(cap, P);
+  const bool use_lds = (int64_t)pl.n_keys <= (int64_t)lds_keys && lds <= FILTER_LDS_MAX;
+  const uint64_t wpb = FILTER_WG / 64;
+  const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_seqs + wpb - 1) / wpb, (uint64_t)c->n_cus * (use_lds ? 1 : 2)));
+  Scratch m{c->misc};
+  const size_t o_keys = m.take<uint64_t>(cap), o_start = m.take<uint32_t>(cap), o_genes = m.take<uint32_t>(P), o_last = m.take<uint32_t>(pl.last.size()),
+               o_n = m.take<unsigned long long>(1), o_rec = m.take<unsigned long long>(room);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n), *drec = m.at<unsigned long long>(o_rec);
+  HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_keys), pl.keys.data(), (size_t)cap * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_start), pl.start.data(), (size_t)cap * 4, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_genes), pl.genes.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_last), pl.last.data(), pl.last.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
+  if (getenv("SHK_TRACE"))  // (read at each call, like SHK_FILTER_LDS_KEYS: the tests look for this line)
+    fprintf(stderr, "[shk] filter_panel: %u genes, %llu keys, set of %zu bytes in %s, room %llu, %llu blocks\n", n_genes,
+            (unsigned long long)pl.n_keys, lds - bitmaps, use_lds ? "LDS" : "global memory", (unsigned long long)room, (unsigned long long)blocks);
+  const PanelSet set{m.at<uint64_t>(o_keys), m.at<uint32_t>(o_start), m.at<uint32_t>(o_genes), m.at<uint32_t>(o_last), cap - 1, P, n_genes};
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    if (use_lds) {
+      if (!c->lds_attr_filter) {  // > 64 KiB of dynamic LDS has to be asked for
+        HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_filter_panel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FILTER_LDS_MAX));
+        c->lds_attr_filter = true;
+      }
+      hipLaunchKernelGGL(k_filter_panel<true>, dim3((uint32_t)blocks), dim3(FILTER_WG), lds, c->stream, d_bases, d_offsets, n_seqs, (int)c->cfg.k, set,
+                         drec, room, dn);
+    } else {
+      hipLaunchKernelGGL(k_filter_panel<false>, dim3((uint32_t)blocks), dim3(FILTER_WG), bitmaps, c->stream, d_bases, d_offsets, n_seqs, (int)c->cfg.k,
+                         set, drec, room, dn);
+    }
+  }
+  HIPC(c, hipGetLastError());
+  unsigned long long nt = 0;
+  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the plan alive until its copies ran)
+  *n_total = nt;
+  recs->clear();
+  if (nt && nt <= room) {
+    recs->resize(nt);
+    HIPC(c, hipMemcpy(recs->data(), drec, nt * 8, hipMemcpyDeviceToHost));
+  }
+  return SHK_OK;
+}
+
+// The passes and what follows them: the records sorted by (gene, read) are the answer.  Same preconditions as panel_pass.
+int panel_core(shk_ctx *c, const PanelPlan &pl, uint32_t n_genes, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs,
+               uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
+  if (n_seqs >> FILTER_READ_BITS) return fail(c, SHK_ERR_BAD_ARG, "a batch of %llu reads", (unsigned long long)n_seqs);
+  const uint64_t room = (uint64_t)std::max(env_int("SHK_FILTER_CANDIDATES", 1 << 20), 1);
+  std::vector<uint64_t> recs;
+  uint64_t nt = 0;
+  SHK_TRY(panel_pass(c, pl, n_genes, d_bases, d_offsets, n_seqs, room, &recs, &nt));
+  if (nt > room) {  // the list overflowed: the pass counted what there is, so the second one has room for exactly that
+    uint64_t n2 = 0;
+    SHK_TRY(panel_pass(c, pl, n_genes, d_bases, d_offsets, n_seqs, nt, &recs, &n2));
+    if (n2 != nt)
+      return fail(c, SHK_ERR_INVARIANT, "panel filter rerun produced %llu records, expected %llu", (unsigned long long)n2, (unsigned long long)nt);
+  }
+  std::sort(recs.begin(), recs.end());  // arrival order is not part of the result
+  for (const uint64_t r : recs) ++match_offsets[(r >> FILTER_READ_BITS) + 1];
+  for (uint32_t g = 0; g < n_genes; ++g) match_offsets[g + 1] += match_offsets[g];
+  *n_matches = nt;
+  if (nt > match_cap || (nt && !match_reads))
+    return fail(c, SHK_ERR_BAD_ARG, "%llu matches do not fit match_cap %llu", (unsigned long long)nt, (unsigned long long)match_cap);
+  for (uint64_t i = 0; i < nt; ++i) match_reads[i] = recs[i] & ((1ull << FILTER_READ_BITS) - 1);
+  return SHK_OK;
+}
+
+}  // namespace
+
+int shk_filter_reads_panel_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                                  const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets,
+                                  uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
+  if (c && c->group) {  // stateless: any device will do
+    const int rc = shk_filter_reads_panel_device(c->group->ctx[0], d_bases, d_offsets, n_seqs, n_bases, primer_kmers, gene_offsets, n_genes,
+                                                 match_offsets, match_reads, match_cap, n_matches);
+    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
+  }
+  if (!c || !match_offsets || !n_matches || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
+  PanelPlan pl;
+  SHK_TRY(panel_plan(c, primer_kmers, gene_offsets, n_genes, &pl));
+  std::fill(match_offsets, match_offsets + n_genes + 1, 0ull);
+  *n_matches = 0;
+  if (n_seqs == 0) return SHK_OK;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read)
+  std::vector<uint64_t> h_off(n_seqs + 1);
+  HIPC(c, hipMemcpyAsync(h_off.data(), d_offsets, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  uint64_t max_len = 0;
+  SHK_TRY(thread_check_offsets(c, h_off.data(), n_seqs, n_bases, &max_len, "shk_filter_reads_panel"));
+  if (pl.genes.empty()) return SHK_OK;
+  return panel_core(c, pl, n_genes, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_seqs, match_offsets, match_reads, match_cap, n_matches);
+}
+
+int shk_filter_reads_panel(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *primer_kmers,
+                           const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap,
+                           uint64_t *n_matches) {
+  if (c && c->group) {  // stateless: any device will do
+    const int rc = shk_filter_reads_panel(c->group->ctx[0], bases, offsets, n_seqs, primer_kmers, gene_offsets, n_genes, match_offsets,
+                                          match_reads, match_cap, n_matches);
+    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
+  }
+  if (!c || !match_offsets || !n_matches || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
+  PanelPlan pl;
+  SHK_TRY(panel_plan(c, primer_kmers, gene_offsets, n_genes, &pl));
+  std::fill(match_offsets, match_offsets + n_genes + 1, 0ull);
+  *n_matches = 0;
+  if (n_seqs == 0) return SHK_OK;
+  uint64_t max_len = 0;
+  SHK_TRY(thread_check_offsets(c, offsets, n_seqs, offsets[n_seqs], &max_len, "shk_filter_reads_panel"));
+  if (pl.genes.empty()) return SHK_OK;
+  // the device form's passes over the staged batch (its offsets are already here: no copy back)
+  const uint64_t n_bases = offsets[n_seqs];
+  if (n_bases && !bases) return SHK_ERR_BAD_ARG;
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
+  HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, c->in_bases.ensure(n_bases + 16));
+  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
+  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  return panel_core(c, pl, n_genes, (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, n_seqs, match_offsets, match_reads,
+                    match_cap, n_matches);
+}
+
+int shk_gather_reads_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, const uint64_t *read_ids, uint64_t n_ids,
+                            void *d_out_bases, uint64_t out_bases_cap, void *d_out_offsets, uint64_t *n_out_bases) {
+  if (c && c->group) {  // stateless: any device will do
+    const int rc = shk_gather_reads_device(c->group->ctx[0], d_bases, d_offsets, n_seqs, read_ids, n_ids, d_out_bases, out_bases_cap,
+                                           d_out_offsets, n_out_bases);
+    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
+  }
+  if (!c || !n_out_bases || (n_ids && !read_ids) || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
+  *n_out_bases = 0;
+  for (uint64_t j = 0; j < n_ids; ++j)
+    if (read_ids[j] >= n_seqs)
+      return fail(c, SHK_ERR_BAD_ARG, "read_ids[%llu] = %llu is outside the %llu reads", (unsigned long long)j, (unsigned long long)read_ids[j],
+                  (unsigned long long)n_seqs);
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));  // (the call's scratch and stream are the context's)
+  std::vector<uint64_t> h_off(n_seqs + 1, 0), out_off(n_ids + 1, 0);
+  if (n_seqs) HIPC(c, hipMemcpyAsync(h_off.data(), d_offsets, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  for (uint64_t i = 0; i < n_seqs; ++i)
+    if (h_off[i + 1] < h_off[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
+  for (uint64_t j = 0; j < n_ids; ++j) out_off[j + 1] = out_off[j] + (h_off[read_ids[j] + 1] - h_off[read_ids[j]]);
+  const uint64_t need = out_off[n_ids];
+  *n_out_bases = need;
+  if (need > out_bases_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "%llu bases do not fit out_bases_cap %llu", (unsigned long long)need, (unsigned long long)out_bases_cap);
+  if (!d_out_offsets || (need && (!d_out_bases || !d_bases))) return SHK_ERR_BAD_ARG;
+  HIPC(c, hipMemcpyAsync(d_out_offsets, out_off.data(), (n_ids + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (need) {
+    Scratch m{c->misc};
+    const size_t o_ids = m.take<uint64_t>(n_ids);
+    HIPC(c, m.ensure());
+    HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_ids), read_ids, n_ids * 8, hipMemcpyHostToDevice, c->stream));
+    const uint64_t wpb = WG / 64;
+    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_ids + wpb - 1) / wpb, (uint64_t)c->n_cus * 8));
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_gather_reads, dim3((uint32_t)blocks), dim3(WG), 0, c->stream, (const uint8_t *)d_bases, (const uint64_t *)d_offsets,
+                       (const uint64_t *)m.at<uint64_t>(o_ids), n_ids, (const uint64_t *)d_out_offsets, (uint8_t *)d_out_bases);
+  }
+  HIPC(c, hipGetLastError());
+  HIPC(c, hipStreamSynchronize(c->stream));  // (keeps out_off and read_ids alive until their copies ran; the batch is complete on return)
+  return SHK_OK;
 }
 
 int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {

@@ -198,6 +198,7 @@ ABI_SYMBOLS = [
     "shk_unpack_reads_device",
     "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget",
     "shk_thread_reads", "shk_thread_reads_device",
+    "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
 ]
 
 _lib = None
@@ -324,6 +325,9 @@ def load_library():
     L.shk_pcr_node_budget.argtypes = [u64]
     L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
+    L.shk_filter_reads_panel.argtypes = [vp, vp, vp, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
+    L.shk_filter_reads_panel_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
+    L.shk_gather_reads_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
     L.shk_pcr_node_budget.restype = u64
     L.shk_owner_counts.argtypes = [vp, u32, vp]
     L.shk_compact_owners.argtypes = [vp, u32, vp, vp, vp, u64, C.c_int32]
@@ -715,6 +719,60 @@ class KmerEngine:
         self._check(self._L.shk_filter_reads(self._h, bases.ctypes.data, offsets.ctypes.data, n,
                                              pk.ctypes.data, len(pk), out.ctypes.data))
         return out[:n].astype(bool)
+
+    def filter_reads_panel(self, bases, offsets, gene_kmers, device: bool = False) -> list:
+        """PrimerReadFilter::filter_reads (pcr/read_filter.rs:24-55) of one batch against every gene of a panel in one
+        pass (shk_filter_reads_panel): gene_kmers is a sequence of arrays of canonical primer k-mers, one per gene; the
+        answer is one uint64 array per gene, the indices of the reads that match it, ascending.  device=True: bases
+        and offsets are torch tensors on this context's device (shk_filter_reads_panel_device)."""
+        genes = [np.ascontiguousarray(np.atleast_1d(g), dtype=np.uint64).reshape(-1) for g in gene_kmers]
+        goff = np.zeros(len(genes) + 1, dtype=np.uint64)
+        if genes:
+            goff[1:] = np.cumsum([len(g) for g in genes])
+        pk = np.concatenate(genes) if genes else np.zeros(0, dtype=np.uint64)
+        n = len(offsets) - 1
+        if device:
+            args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
+            call = self._L.shk_filter_reads_panel_device
+        else:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            args = (bases.ctypes.data, offsets.ctypes.data, n)
+            call = self._L.shk_filter_reads_panel
+        moff = np.zeros(len(genes) + 1, dtype=np.uint64)
+        # room for every read in up to four genes: a call that finds more says so and is made again, which walks the
+        # reads a second time
+        cap = max(n, 1) * min(max(len(genes), 1), 4)
+        while True:
+            reads = np.zeros(cap, dtype=np.uint64)
+            need = C.c_uint64(0)
+            rcode = call(self._h, *args, pk.ctypes.data, goff.ctypes.data, len(genes), moff.ctypes.data, reads.ctypes.data, cap,
+                         C.byref(need))
+            if rcode == -2 and need.value > cap:  # the list was too small: it says what it needs
+                cap = int(need.value)
+                continue
+            self._check(rcode)
+            return [reads[int(moff[g]):int(moff[g + 1])].copy() for g in range(len(genes))]
+
+    def gather_reads(self, bases_t, offsets_t, read_ids):
+        """The reads read_ids (any order, repeats allowed) of a batch that lies on this context's device, as a batch of
+        their own on the same device (shk_gather_reads_device) → (bases uint8 tensor, offsets int64 tensor): what takes a
+        gene's list from filter_reads_panel to thread_reads(device=True)."""
+        import torch
+        ids = np.ascontiguousarray(read_ids, dtype=np.uint64).reshape(-1)
+        n = offsets_t.numel() - 1
+        out_off = torch.empty(len(ids) + 1, dtype=torch.int64, device=self._tdev)
+        cap = len(ids) * (bases_t.numel() // max(n, 1) + 1)  # the mean read length each; the retry is for longer picks
+        while True:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self._tdev)
+            need = C.c_uint64(0)
+            rcode = self._L.shk_gather_reads_device(self._h, bases_t.data_ptr(), offsets_t.data_ptr(), n, ids.ctypes.data, len(ids),
+                                                    out.data_ptr(), cap, out_off.data_ptr(), C.byref(need))
+            if rcode == -2 and need.value > cap:  # nothing was written: it says what it needs
+                cap = int(need.value)
+                continue
+            self._check(rcode)
+            return out[:int(need.value)], out_off
 
     def kmers_from_reads(self, bases: np.ndarray, offsets: np.ndarray):
         """Batched kmers_from_ascii (kmer/encoding.rs:332-371) in the form thread_reads uses it
