@@ -1614,6 +1614,103 @@ __global__ void __launch_bounds__(WG) k_primer_scan(TableRef tb, uint64_t slot0,
 }
 
 // ==========================================================================================
+// What the read walkers below share (K_FILTER, K_KMERS, K_THREAD, K_FILTER_PANEL): the probe of a lookup set, the key runs
+// behind it, and a read's bytes as canonical k-mers — rolling, one thread per read; as bit planes, one wave per read.
+// ==========================================================================================
+constexpr uint32_t SET_NONE = 0xFFFFFFFFu;         // set_find: the key is not in the set
+// The slot of `key` in an open-addressing set of mask + 1 slots (EMPTY where free; from set_hash(key) on, linear; the
+// host keeps the load ≤ 1/2, so a probe ends), or SET_NONE.  keys may lie in LDS or in global memory.
+__device__ __forceinline__ uint32_t set_find(const uint64_t *keys, uint32_t mask, uint64_t key) {
+  for (uint32_t s = set_hash(key) & mask;; s = (s + 1) & mask) {
+    const uint64_t cur = keys[s];
+    if (cur == key) return s;
+    if (cur == EMPTY) return SET_NONE;
+  }
+}
+
+// KEYRUNS: a lookup set whose every key owns a run of items — the edges that spell a k-mer (K_THREAD), the genes that
+// hold a primer k-mer (K_FILTER_PANEL).  The host builds it (key_runs_build, shk_reads_api.hip.h).
+struct KeyRuns {
+  const uint64_t *keys;   // [mask + 1] canonical k-mer or EMPTY: the set set_find probes
+  const uint32_t *start;  // [mask + 1] the key's first item in items
+  const uint32_t *items;  // [n_items] ascending by (key, item): a key's items lie side by side
+  const uint32_t *last;   // [(n_items + 31) / 32] bit i: items[i] is the last of its key's run (run_ends)
+  uint32_t mask, n_items;
+};
+__device__ __forceinline__ bool run_ends(const uint32_t *last, uint32_t i) { return (last[i >> 5] >> (i & 31u)) & 1u; }
+// Its bytes and its layout in LDS: keys, start, items, last from an 8-byte-aligned base, so the uint64_t array stays
+// 8-byte aligned; a uint4 array goes in FRONT of it at a 16-byte-aligned base (K_THREAD's meta: the keys stay aligned).
+__host__ __device__ inline size_t key_runs_bytes(uint32_t cap, uint32_t n_items) {
+  return (size_t)cap * 12 + (size_t)n_items * 4 + (size_t)((n_items + 31) / 32) * 4;
+}
+// every thread of the workgroup (nt threads) calls it; the caller's __syncthreads() completes the copy
+__device__ __forceinline__ KeyRuns key_runs_to_lds(const KeyRuns &g, uint8_t *base, uint32_t nt) {
+  const uint32_t cap = g.mask + 1, n = g.n_items;
+  uint64_t *lk = (uint64_t *)base;
+  uint32_t *ls = (uint32_t *)(lk + cap), *li = ls + cap, *ll = li + n;
+  for (uint32_t i = threadIdx.x; i < cap; i += nt) lk[i] = g.keys[i], ls[i] = g.start[i];
+  for (uint32_t i = threadIdx.x; i < n; i += nt) li[i] = g.items[i];
+  for (uint32_t i = threadIdx.x; i < (n + 31) / 32; i += nt) ll[i] = g.last[i];
+  return KeyRuns{lk, ls, li, ll, g.mask, n};
+}
+
+// kmers_from_ascii (src/kmer/encoding.rs:332-371) one byte at a time: the one-thread-per-read form of K_FILTER and K_KMERS.
+struct RollingKmer {
+  uint64_t mask, fwd = 0, rev = 0;
+  int k, n_valid = 0;
+  __device__ __forceinline__ explicit RollingKmer(int k_) : mask((1ull << (2 * k_)) - 1), k(k_) {}
+  // → 1: *key = the canonical k-mer that ends at c; 0: none (an N restarts, encoding.rs:346-352); −1: c is outside ACGTN (:353-356)
+  __device__ __forceinline__ int step(uint32_t c, uint64_t *key) {
+    if (c == 'N') return n_valid = 0;
+    if (!byte_is_acgtn(c)) return -1;
+    const uint64_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
+    fwd = ((fwd << 2) | b2) & mask;
+    rev = (rev >> 2) | ((3 - b2) << (2 * (k - 1)));
+    if (++n_valid < k) return 0;
+    *key = fwd < rev ? fwd : rev;
+    return 1;
+  }
+};
+
+// One wave step's bytes rb[p] (p = the step's first byte + lane; beyond len: 'A') as wave-wide bit planes: code bit 0,
+// code bit 1, N, and whether any of them is outside ACGTN.  Ballots: the planes live in scalar registers.
+struct ReadPlanes {
+  uint64_t p0, p1, n;
+  bool bad;
+};
+__device__ __forceinline__ ReadPlanes read_planes(const uint8_t *__restrict__ rb, uint32_t p, uint32_t len) {
+  const uint32_t c = p < len ? rb[p] : (uint32_t)'A';
+  const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
+  return ReadPlanes{__ballot(b2 & 1u), __ballot(b2 >> 1), __ballot(c == 'N'), __ballot(!byte_is_acgtn(c)) != 0};
+}
+// bit i of x → bit 2i
+__device__ __forceinline__ uint64_t spread2(uint32_t x) {
+  uint64_t v = x;
+  v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
+  v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
+  v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
+  v = (v | (v << 2)) & 0x3333333333333333ull;
+  v = (v | (v << 1)) & 0x5555555555555555ull;
+  return v;
+}
+// bits l … l+31 of the 128-bit value hi:lo (l < 64)
+__device__ __forceinline__ uint32_t window32(uint64_t lo, uint64_t hi, uint32_t l) {
+  return (uint32_t)((lo >> l) | ((hi << 1) << (63 - l)));
+}
+// Lane `lane`'s window of the step at s0: bits lane … lane+k−1 of two steps' planes (lo: the bytes from s0 on, hi: the
+// next 64), km = 2^k − 1, k ≤ 31.  → whether it is a list element (one of the read's n_win windows, without an N) and if
+// so *key = its canonical k-mer: the code planes bit-reversed and interleaved, or their complements, not reversed.
+__device__ __forceinline__ bool window_key(const ReadPlanes &lo, const ReadPlanes &hi, uint32_t lane, int k, uint32_t km, uint32_t s0,
+                                           uint32_t n_win, uint64_t *key) {
+  if (s0 + lane >= n_win || (window32(lo.n, hi.n, lane) & km) != 0) return false;
+  const uint32_t w0 = window32(lo.p0, hi.p0, lane) & km, w1 = window32(lo.p1, hi.p1, lane) & km;
+  const uint64_t fwd = spread2(__brev(w0) >> (32 - k)) | (spread2(__brev(w1) >> (32 - k)) << 1);
+  const uint64_t rev = spread2(~w0 & km) | (spread2(~w1 & km) << 1);
+  *key = fwd < rev ? fwd : rev;
+  return true;
+}
+
+// ==========================================================================================
 // K_FILTER: PrimerReadFilter::matches (src/pcr/read_filter.rs:43-49) for a batch of reads: a read
 // matches when kmers_from_ascii accepts it (no byte outside ACGTN — otherwise the reference
 // returns false for the whole read) and at least one of its canonical k-mers is in the set.
@@ -1626,31 +1723,16 @@ __global__ void __launch_bounds__(WG) k_filter_reads(const uint8_t *__restrict__
                                                      uint32_t set_mask, uint8_t *__restrict__ out) {
   const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
   if (i >= n_seqs) return;
-  const uint64_t mask = (1ull << (2 * k)) - 1;
-  uint64_t fwd = 0, rev = 0;
-  int n_valid = 0;
+  RollingKmer roll(k);
+  uint64_t key = 0;
   bool hit = false, ok = true;
   for (uint64_t p = offsets[i], e = offsets[i + 1]; p < e; ++p) {
-    const uint32_t c = bases[p];
-    if (c == 'N') {  // encoding.rs:346-352
-      n_valid = 0;
-      continue;
-    }
-    if (!byte_is_acgtn(c)) {  // encoding.rs:353-356 → Err → matches() is false
+    const int got = roll.step(bases[p], &key);
+    if (got < 0) {  // → Err → matches() is false
       ok = false;
       break;
     }
-    const uint64_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
-    fwd = ((fwd << 2) | b2) & mask;
-    rev = (rev >> 2) | ((3 - b2) << (2 * (k - 1)));
-    if (++n_valid >= k && !hit) {
-      const uint64_t key = fwd < rev ? fwd : rev;
-      for (uint32_t s = set_hash(key) & set_mask;; s = (s + 1) & set_mask) {
-        const uint64_t cur = set_keys[s];
-        if (cur == key) hit = true;
-        if (cur == key || cur == EMPTY) break;
-      }
-    }
+    if (got && !hit) hit = set_find(set_keys, set_mask, key) != SET_NONE;
   }
   out[i] = ok && hit;
 }
@@ -1668,25 +1750,18 @@ __global__ void __launch_bounds__(WG) k_kmers_from_reads(const uint8_t *__restri
                                                          uint8_t *__restrict__ bad_byte) {
   const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
   if (i >= n_seqs) return;
-  const uint64_t mask = (1ull << (2 * k)) - 1;
-  uint64_t fwd = 0, rev = 0;
-  int n_valid = 0;
+  RollingKmer roll(k);
+  uint64_t key = 0;
   uint32_t n = 0, bad = 0;
   uint64_t *dst = out + koff[i];
   for (uint64_t p = offsets[i], e = offsets[i + 1]; p < e; ++p) {
     const uint32_t c = bases[p];
-    if (c == 'N') {  // encoding.rs:346-352
-      n_valid = 0;
-      continue;
-    }
-    if (!byte_is_acgtn(c)) {  // encoding.rs:353-356 → Err for the whole read
+    const int got = roll.step(c, &key);
+    if (got < 0) {  // → Err for the whole read
       bad = c;
       break;
     }
-    const uint64_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
-    fwd = ((fwd << 2) | b2) & mask;
-    rev = (rev >> 2) | ((3 - b2) << (2 * (k - 1)));
-    if (++n_valid >= k) dst[n++] = fwd < rev ? fwd : rev;
+    if (got) dst[n++] = key;
   }
   n_out[i] = bad ? 0u : n;
   bad_byte[i] = (uint8_t)bad;
@@ -1696,14 +1771,11 @@ __global__ void __launch_bounds__(WG) k_kmers_from_reads(const uint8_t *__restri
 // K_THREAD: thread_reads (src/pcr/threading.rs:87-192) for a batch of reads against a graph given as a lookup set
 // the host built (shk_thread_reads).  One WAVE per read, THREAD_TILE = 64 window start positions per
 // step, one per lane:
-//   bases      64 new bytes per step, one per lane, turned into wave-wide bit planes by ballots (code bit 0, code
-//              bit 1, N, invalid) that live in scalar registers; lane l's window is bits l … l+k−1 of two steps'
-//              planes, bit-reversed and interleaved into the k-mer (the complement planes, not reversed, give the
-//              reverse complement).  A window with an N is no list element (kmers_from_ascii drops it and leaves no
-//              gap, encoding.rs:346-352): its lane sits out, and "the previous element" of a lane is the nearest
-//              lower lane that has one — or the carry from the step before.
-//   probe      position-parallel: open addressing over min(x, revcomp(x)) → first candidate (build_edge_lookup,
-//              threading.rs:203-220).  An element with ONE candidate has its edge there and then.
+//   bases      64 new bytes per step as bit planes (read_planes), each lane's window and key from them (window_key).  A
+//              window with an N is no list element (encoding.rs:346-352): its lane sits out, and "the previous element"
+//              of a lane is the nearest lower lane that has one — or the carry from the step before.
+//   probe      position-parallel (set_find) → first candidate (build_edge_lookup, threading.rs:203-220).  An element
+//              with ONE candidate has its edge there and then.
 //   resolve    the only sequential step (resolve_candidates, threading.rs:233-256): elements with more candidates,
 //              in list order (a ballot and a loop over its bits, wave-uniform), each after its predecessor is final.
 //   runs       from the neighbour lanes (find_contiguous_runs, threading.rs:261-315): an element CONTINUES the run
@@ -1727,32 +1799,12 @@ constexpr int THREAD_LDS_EDGES = 2048;             // graphs up to this many edg
 constexpr size_t THREAD_LDS_MAX = 128u << 10;      // … if it fits this much of a CU's 160 KiB (2048 edges: at most 104.3 KiB)
 
 struct ThreadSet {
-  const uint64_t *keys;   // [mask + 1] canonical edge k-mer or EMPTY, open addressing by set_hash, load ≤ 1/2
-  const uint32_t *start;  // [mask + 1] the key's first candidate in cand
-  const uint32_t *cand;   // [n_edges] edges ascending by (key, edge)
-  const uint32_t *last;   // bit i: cand[i] is the last candidate of its key
-  const uint4 *meta;      // [n_edges] {src, tgt, link slot base of the pairs (e, ·) or TH_NONE, rank of e among its source's out-edges}
-  uint32_t mask;
-  uint32_t n_edges;
+  KeyRuns runs;       // canonical edge k-mer → its candidates: the edges, ascending by (key, edge)
+  const uint4 *meta;  // [runs.n_items] {src, tgt, link slot base of the pairs (e, ·) or TH_NONE, rank of e among its source's out-edges}
 };
-// bytes of LDS the set and the two private counters take (the order of k_thread_reads<true>)
+// bytes of LDS of k_thread_reads<true>, in its order: meta, the key runs, the two private counters
 __host__ __device__ inline size_t thread_lds_bytes(uint32_t cap, uint32_t n_edges) {
-  return (size_t)cap * 12 + (size_t)n_edges * 28 + (size_t)((n_edges + 31) / 32) * 4;
-}
-
-// bit i of x → bit 2i
-__device__ __forceinline__ uint64_t spread2(uint32_t x) {
-  uint64_t v = x;
-  v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
-  v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
-  v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  v = (v | (v << 2)) & 0x3333333333333333ull;
-  v = (v | (v << 1)) & 0x5555555555555555ull;
-  return v;
-}
-// bits l … l+31 of the 128-bit value hi:lo (l < 64)
-__device__ __forceinline__ uint32_t window32(uint64_t lo, uint64_t hi, uint32_t l) {
-  return (uint32_t)((lo >> l) | ((hi << 1) << (63 - l)));
+  return (size_t)n_edges * 16 + key_runs_bytes(cap, n_edges) + (size_t)n_edges * 8;
 }
 
 template <bool LDS>
@@ -1762,18 +1814,16 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
                                                             uint32_t *__restrict__ unamb, uint32_t *__restrict__ links,
                                                             uint32_t *__restrict__ read_edges) {
   extern __shared__ __align__(16) uint8_t th_lds[];
-  const uint32_t cap = gs.mask + 1, E = gs.n_edges;
-  uint64_t *lk = (uint64_t *)th_lds;  // (cap ≥ 16: every array below starts 16-byte aligned where it has to)
-  uint4 *lm = (uint4 *)(lk + cap);
-  uint32_t *ls = (uint32_t *)(lm + E), *lc = ls + cap, *ll = lc + E, *lt = ll + (E + 31) / 32, *lu = lt + E;
+  const uint32_t E = gs.runs.n_items;
+  uint4 *lm = (uint4 *)th_lds;  // (the uint4 array first: see key_runs_bytes)
+  uint32_t *lt = (uint32_t *)(th_lds + (size_t)E * 16 + key_runs_bytes(gs.runs.mask + 1, E)), *lu = lt + E;
+  KeyRuns ks = gs.runs;
   if (LDS) {
-    for (uint32_t i = threadIdx.x; i < cap; i += THREAD_WG) lk[i] = gs.keys[i], ls[i] = gs.start[i];
-    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gs.meta[i], lc[i] = gs.cand[i], lt[i] = 0, lu[i] = 0;
-    for (uint32_t i = threadIdx.x; i < (E + 31) / 32; i += THREAD_WG) ll[i] = gs.last[i];
+    ks = key_runs_to_lds(gs.runs, th_lds + (size_t)E * 16, THREAD_WG);
+    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gs.meta[i], lt[i] = 0, lu[i] = 0;
     __syncthreads();
   }
-  const uint64_t *keys = LDS ? lk : gs.keys;
-  const uint32_t *start = LDS ? ls : gs.start, *cand = LDS ? lc : gs.cand, *last = LDS ? ll : gs.last;
+  const uint32_t *cand = ks.items;
   const uint4 *meta = LDS ? lm : gs.meta;
   uint32_t *ctot = LDS ? lt : total, *cun = LDS ? lu : unamb;
 
@@ -1794,38 +1844,25 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
     bool bad = false;
     // ---- sweep 1, first step first: edges, run flags, link slots → scratch
     uint32_t c_hit = 0, c_tgt = 0, c_lbase = TH_NONE, c_pre = 0;  // the last list element so far
-    uint64_t p0lo = 0, p1lo = 0, nlo = 0;
-    if (n_win) {
-      const uint32_t c = lane < len ? rb[lane] : (uint32_t)'A';
-      const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
-      p0lo = __ballot(b2 & 1u), p1lo = __ballot(b2 >> 1), nlo = __ballot(c == 'N');
-      bad = __ballot(!byte_is_acgtn(c)) != 0;
-    }
+    ReadPlanes lo{0, 0, 0, false};
+    if (n_win) lo = read_planes(rb, lane, len);
+    bad = lo.bad;
     for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
-      const uint32_t p = s0 + THREAD_TILE + lane;  // the step's new bytes: the upper half of its windows' span
-      const uint32_t c = p < len ? rb[p] : (uint32_t)'A';
-      const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
-      const uint64_t p0hi = __ballot(b2 & 1u), p1hi = __ballot(b2 >> 1), nhi = __ballot(c == 'N');
-      if (__ballot(!byte_is_acgtn(c)) != 0) {  // encoding.rs:353-356 → Err → the read is skipped whole
+      const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
+      if (hi.bad) {  // encoding.rs:353-356 → Err → the read is skipped whole
         bad = true;
         break;
       }
-      const bool v = s0 + lane < n_win && (window32(nlo, nhi, lane) & km) == 0;  // a list element
+      uint64_t key = 0;
+      const bool v = window_key(lo, hi, lane, k, km, s0, n_win, &key);  // a list element
       uint32_t edge = TH_NONE, src = 0, tgt = 0, lbase = TH_NONE, orank = 0, cstart = 0;
       int hit = 0;
       bool multi = false;
       if (v) {
-        const uint32_t w0 = window32(p0lo, p0hi, lane) & km, w1 = window32(p1lo, p1hi, lane) & km;
-        const uint64_t fwd = spread2(__brev(w0) >> (32 - k)) | (spread2(__brev(w1) >> (32 - k)) << 1);
-        const uint64_t rev = spread2(~w0 & km) | (spread2(~w1 & km) << 1);
-        const uint64_t key = fwd < rev ? fwd : rev;
-        for (uint32_t s = set_hash(key) & gs.mask;; s = (s + 1) & gs.mask) {
-          const uint64_t cur = keys[s];
-          if (cur == key) hit = 1, cstart = start[s];
-          if (cur == key || cur == EMPTY) break;
-        }
-        if (hit) {
-          multi = !((last[cstart >> 5] >> (cstart & 31u)) & 1u);
+        const uint32_t s = set_find(ks.keys, ks.mask, key);
+        if (s != SET_NONE) {
+          hit = 1, cstart = ks.start[s];
+          multi = !run_ends(ks.last, cstart);
           if (!multi) {
             edge = cand[cstart];
             const uint4 m = meta[edge];
@@ -1851,7 +1888,7 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
               pick = e;
               break;
             }
-            if ((last[i >> 5] >> (i & 31u)) & 1u) break;
+            if (run_ends(ks.last, i)) break;
           }
         const uint4 pm = meta[pick];
         if ((int)lane == m) edge = pick, src = pm.x, tgt = pm.y, lbase = pm.z, orank = pm.w;
@@ -1875,7 +1912,7 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
         c_hit = (uint32_t)__shfl(hit, top), c_tgt = __shfl(tgt, top), c_lbase = __shfl(lbase, top);
         c_pre = (uint32_t)__shfl((int)pre, top);
       }
-      p0lo = p0hi, p1lo = p1hi, nlo = nhi;
+      lo = hi;
     }
     if (bad) n_hit = 0;
     if (read_edges && lane == 0) read_edges[r] = n_hit;
@@ -1910,11 +1947,10 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
 // ==========================================================================================
 // K_FILTER_PANEL: PrimerReadFilter::matches (src/pcr/read_filter.rs:43-49) of every read of a batch against every
 // gene of a panel in one walk (shk_filter_reads_panel).  The lookup set the host built maps a canonical
-// k-mer to the genes that hold it.  One WAVE per read, 64 window start positions per step as in K_THREAD:
-//   bases      64 new bytes per step, one per lane, turned into the code, N and invalid bit planes by four ballots
-//              (read_planes); lane l's window is bits l … l+k−1 of two steps' planes, so every byte is loaded once.
-//   probe      position-parallel; a read of a run mostly belongs to no amplicon, so the common step is load, four
-//              ballots and one probe that ends on an EMPTY slot.
+// k-mer to the genes that hold it.  One WAVE per read, THREAD_TILE window start positions per step as in K_THREAD:
+//   bases      as K_THREAD: read_planes and window_key, so every byte is loaded once.
+//   probe      position-parallel (set_find); a read of a run mostly belongs to no amplicon, so the common step is load,
+//              four ballots and one probe that ends on an EMPTY slot.
 //   hit        the lane ORs its key's genes into the wave's bitmap of n_genes bits in LDS.
 //   emit       only behind the read's last byte — a later invalid byte cancels the read (kmers_from_ascii fails as
 //              a whole, encoding.rs:353-356): the lanes walk the bitmap's words, append one (gene, read) record per
@@ -1932,48 +1968,24 @@ constexpr int FILTER_READ_BITS = 52;               // of a record; the gene abov
 static_assert((FILTER_MAX_GENES - 1) >> (64 - FILTER_READ_BITS) == 0, "a gene fits a record's top bits");
 
 struct PanelSet {
-  const uint64_t *keys;   // [mask + 1] canonical primer k-mer or EMPTY, open addressing by set_hash, load ≤ 1/2
-  const uint32_t *start;  // [mask + 1] the key's first entry in genes
-  const uint32_t *genes;  // [n_pairs] gene ids by (key, gene), each (key, gene) once
-  const uint32_t *last;   // bit i: genes[i] is the last gene of its key
-  uint32_t mask, n_pairs, n_genes;
+  KeyRuns runs;  // canonical primer k-mer → the genes that hold it: gene ids by (key, gene), each pair once
+  uint32_t n_genes;
 };
 // bytes of dynamic LDS: the 16 bitmaps first (both variants), then the set (k_filter_panel<true>)
 __host__ __device__ inline size_t filter_bitmap_bytes(uint32_t n_genes) { return (size_t)(FILTER_WG / 64) * ((n_genes + 31) / 32) * 4; }
-__host__ __device__ inline size_t filter_set_bytes(uint32_t cap, uint32_t n_pairs) {
-  return (size_t)cap * 12 + (size_t)n_pairs * 4 + (size_t)((n_pairs + 31) / 32) * 4;
-}
-
-// One step's bytes rb[p0 + lane] (beyond len: 'A') as wave-wide bit planes: code bit 0, code bit 1, N, and whether any
-// of them is outside ACGTN.
-struct ReadPlanes {
-  uint64_t p0, p1, n;
-  bool bad;
-};
-__device__ __forceinline__ ReadPlanes read_planes(const uint8_t *__restrict__ rb, uint32_t p, uint32_t len) {
-  const uint32_t c = p < len ? rb[p] : (uint32_t)'A';
-  const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
-  return ReadPlanes{__ballot(b2 & 1u), __ballot(b2 >> 1), __ballot(c == 'N'), __ballot(!byte_is_acgtn(c)) != 0};
-}
+__host__ __device__ inline size_t filter_set_bytes(uint32_t cap, uint32_t n_pairs) { return key_runs_bytes(cap, n_pairs); }
 
 template <bool LDS>
 __global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
                                                             uint64_t n_seqs, int k, PanelSet gs, unsigned long long *__restrict__ out,
                                                             uint64_t cap, unsigned long long *__restrict__ n_out) {
   extern __shared__ __align__(16) uint8_t fp_lds[];
-  const uint32_t n_words = (gs.n_genes + 31) / 32, scap = gs.mask + 1, P = gs.n_pairs;
+  const uint32_t n_words = (gs.n_genes + 31) / 32;
   uint32_t *bm_all = (uint32_t *)fp_lds;  // (16 · n_words words: a multiple of 64 bytes, so the keys behind stay aligned)
-  uint64_t *lk = (uint64_t *)(bm_all + (FILTER_WG / 64) * n_words);
-  uint32_t *ls = (uint32_t *)(lk + (LDS ? scap : 0)), *lg = ls + (LDS ? scap : 0), *ll = lg + (LDS ? P : 0);
   for (uint32_t i = threadIdx.x; i < (FILTER_WG / 64) * n_words; i += FILTER_WG) bm_all[i] = 0;
-  if (LDS) {
-    for (uint32_t i = threadIdx.x; i < scap; i += FILTER_WG) lk[i] = gs.keys[i], ls[i] = gs.start[i];
-    for (uint32_t i = threadIdx.x; i < P; i += FILTER_WG) lg[i] = gs.genes[i];
-    for (uint32_t i = threadIdx.x; i < (P + 31) / 32; i += FILTER_WG) ll[i] = gs.last[i];
-  }
+  KeyRuns ks = gs.runs;
+  if (LDS) ks = key_runs_to_lds(gs.runs, fp_lds + filter_bitmap_bytes(gs.n_genes), FILTER_WG);
   __syncthreads();
-  const uint64_t *keys = LDS ? lk : gs.keys;
-  const uint32_t *start = LDS ? ls : gs.start, *genes = LDS ? lg : gs.genes, *last = LDS ? ll : gs.last;
 
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1991,29 +2003,23 @@ __global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__res
     const uint8_t *rb = bases + b0;
     ReadPlanes lo = read_planes(rb, lane, len);
     bool bad = lo.bad, any = false;
-    for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += 64) {
-      const ReadPlanes hi = read_planes(rb, s0 + 64 + lane, len);  // the step's new bytes: the upper half of its windows' span
+    for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
+      const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
       if (hi.bad) {  // encoding.rs:353-356 → Err → matches() is false for every gene
         bad = true;
         break;
       }
       bool hit = false;
-      if (s0 + lane < n_win && (window32(lo.n, hi.n, lane) & km) == 0) {  // a window without an N: a k-mer
-        const uint32_t w0 = window32(lo.p0, hi.p0, lane) & km, w1 = window32(lo.p1, hi.p1, lane) & km;
-        const uint64_t fwd = spread2(__brev(w0) >> (32 - k)) | (spread2(__brev(w1) >> (32 - k)) << 1);
-        const uint64_t rev = spread2(~w0 & km) | (spread2(~w1 & km) << 1);
-        const uint64_t key = fwd < rev ? fwd : rev;
-        for (uint32_t s = set_hash(key) & gs.mask;; s = (s + 1) & gs.mask) {
-          const uint64_t cur = keys[s];
-          if (cur == key) {
-            hit = true;
-            for (uint32_t i = start[s];; ++i) {
-              const uint32_t g = genes[i];
-              atomicOr(&bm[g >> 5], 1u << (g & 31u));
-              if ((last[i >> 5] >> (i & 31u)) & 1u) break;
-            }
+      uint64_t key = 0;
+      if (window_key(lo, hi, lane, k, km, s0, n_win, &key)) {  // a window without an N: a k-mer
+        const uint32_t s = set_find(ks.keys, ks.mask, key);
+        if (s != SET_NONE) {
+          hit = true;
+          for (uint32_t i = ks.start[s];; ++i) {
+            const uint32_t g = ks.items[i];
+            atomicOr(&bm[g >> 5], 1u << (g & 31u));
+            if (run_ends(ks.last, i)) break;
           }
-          if (cur == key || cur == EMPTY) break;
         }
       }
       any |= __ballot(hit) != 0;

@@ -3347,3 +3347,5 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 
 // shk_export_table … shk_set_owner_share: the calls that read the table or hand it to a peer
 #include "shk_table_api.hip.h"
+// shk_filter_reads … shk_gather_reads_device: the calls that walk a batch of reads and leave the table alone
+#include "shk_reads_api.hip.h"

@@ -522,596 +522,6 @@ int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, 
   return SHK_OK;
 }
 
-int shk_filter_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
-                     const uint64_t *primer_kmers, uint64_t n_kmers, uint8_t *out_matches) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_filter_reads(c->group->ctx[0], bases, offsets, n_seqs, primer_kmers, n_kmers, out_matches);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || (n_seqs && (!offsets || !out_matches))) return SHK_ERR_BAD_ARG;
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  const uint32_t k = c->cfg.k;
-  // the union of the primer k-mers (read_filter.rs:24-41) as an open-addressing set at load ≤ 1/2
-  uint64_t cap = 16;
-  while (cap < 2 * n_kmers) cap <<= 1;
-  if (cap > (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "primer k-mer set too large");
-  std::vector<uint64_t> set(cap, ~0ull);
-  for (uint64_t j = 0; j < n_kmers; ++j) {
-    const uint64_t key = primer_kmers[j];
-    if (2 * k < 64 && (key >> (2 * k)) != 0)
-      return fail(c, SHK_ERR_BAD_ARG, "primer k-mer %llu does not fit %u bases", (unsigned long long)key, k);
-    for (uint64_t sl = set_hash(key) & (cap - 1);; sl = (sl + 1) & (cap - 1)) {
-      if (set[sl] == key) break;
-      if (set[sl] == ~0ull) {
-        set[sl] = key;
-        break;
-      }
-    }
-  }
-  const uint64_t n_bases = offsets[n_seqs];
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  Scratch m{c->misc};
-  const size_t o_set = m.take<uint64_t>(cap), o_out = m.take<uint8_t>(n_seqs);
-  HIPC(c, m.ensure());
-  uint64_t *dset = m.at<uint64_t>(o_set);
-  uint8_t *dout = m.at<uint8_t>(o_out);
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dset, set.data(), cap * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_filter_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
-                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, n_seqs, (int)k,
-                       (const uint64_t *)dset, (uint32_t)(cap - 1), dout);
-  }
-  HIPC(c, hipMemcpyAsync(out_matches, dout, n_seqs, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `set` alive until its copy ran)
-  return SHK_OK;
-}
-
-int shk_kmers_from_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
-                         uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_kmers_from_reads(c->group->ctx[0], bases, offsets, n_seqs, kmers, kmers_cap, n_kmers, bad_byte);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || (n_seqs && (!offsets || !n_kmers || !bad_byte))) return SHK_ERR_BAD_ARG;
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  const uint32_t k = c->cfg.k;
-  // koff(i): every read gets room for the most k-mers it can yield
-  std::vector<uint64_t> koff(n_seqs + 1);
-  koff[0] = 0;
-  for (uint64_t i = 0; i < n_seqs; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
-    const uint64_t len = offsets[i + 1] - offsets[i];
-    koff[i + 1] = koff[i] + (len >= k ? len - k + 1 : 0);
-  }
-  const uint64_t n_total = koff[n_seqs];
-  if (n_total > kmers_cap || (n_total && !kmers))
-    return fail(c, SHK_ERR_BAD_ARG, "kmers_cap %llu is below the %llu k-mers these reads can yield",
-                (unsigned long long)kmers_cap, (unsigned long long)n_total);
-  const uint64_t n_bases = offsets[n_seqs];
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  Scratch m{c->misc};
-  const size_t o_koff = m.take<uint64_t>(n_seqs + 1), o_kmers = m.take<uint64_t>(n_total + 1), o_n = m.take<uint32_t>(n_seqs),
-               o_bad = m.take<uint8_t>(n_seqs);
-  HIPC(c, m.ensure());
-  uint64_t *dkoff = m.at<uint64_t>(o_koff), *dkm = m.at<uint64_t>(o_kmers);
-  uint32_t *dnk = m.at<uint32_t>(o_n);
-  uint8_t *dbad = m.at<uint8_t>(o_bad);
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
-  HIPC(c, hipStreamSynchronize(c->stream));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(dkoff, koff.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_kmers_from_reads, dim3((uint32_t)((n_seqs + WG - 1) / WG)), dim3(WG), 0, c->stream,
-                       (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p,
-                       (const uint64_t *)dkoff, n_seqs, (int)k, dkm, dnk, dbad);
-  }
-  // a read's span is copied back whole; only its first n_kmers[i] entries mean anything
-  if (n_total) HIPC(c, hipMemcpyAsync(kmers, dkm, n_total * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(n_kmers, dnk, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(bad_byte, dbad, n_seqs, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps `koff` alive until its copy ran)
-  return SHK_OK;
-}
-
-namespace {
-
-// A graph as k_thread_reads wants it: the lookup set of build_edge_lookup (threading.rs:203-220), the
-// per-edge facts find_contiguous_runs / record_branch_links ask the graph for, and a dense slot for every branch link.
-struct ThreadPlan {
-  std::vector<uint64_t> keys;               // open addressing by set_hash, EMPTY where free, load ≤ 1/2
-  std::vector<uint32_t> start, cand, last;  // a key's first candidate; edges by (key, edge); bit i: cand[i] ends its key's run
-  std::vector<uint4> meta;                  // {src, tgt, link base or TH_NONE, out rank}
-  std::vector<uint64_t> out_first;          // CSR of the out-edges by source node, ascending edge index (link decoding)
-  std::vector<uint32_t> out_list;
-  uint64_t n_slots = 0;                     // Σ over branch nodes of in_deg · out_deg
-};
-
-// Everything shk_thread_reads refuses before the device is touched, and the plan of a non-empty graph.
-int thread_plan(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
-                uint64_t n_edges, uint64_t n_seqs, const uint64_t *read_index, const uint8_t *mate, const shk_thread_out *out,
-                ThreadPlan *pl) {
-  const uint32_t k = c->cfg.k;
-  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_thread_reads needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
-  if (n_nodes >= (1ull << 32) || n_edges >= (1ull << 32))
-    return fail(c, SHK_ERR_BAD_ARG, "graph of %llu nodes and %llu edges: both must be below 2^32", (unsigned long long)n_nodes,
-                (unsigned long long)n_edges);
-  if ((n_nodes && !node_sub_kmers) || (n_edges && (!edge_src || !edge_tgt || !out->support_total || !out->support_unambiguous)))
-    return fail(c, SHK_ERR_BAD_ARG, "shk_thread_reads: a graph array or a support array is missing");
-  if ((read_index == nullptr) != (mate == nullptr))
-    return fail(c, SHK_ERR_BAD_ARG, "read_index and mate go together: both (thread_reads_paired) or neither (thread_reads)");
-  for (uint64_t i = 0; mate && i < n_seqs; ++i)
-    if (mate[i] > 2) return fail(c, SHK_ERR_BAD_ARG, "mate[%llu] = %u: 0 unpaired, 1 R1, 2 R2", (unsigned long long)i, mate[i]);
-  const uint64_t nmask = ~0ull >> (64 - 2 * (k - 1));
-  for (uint64_t v = 0; v < n_nodes; ++v)
-    if (node_sub_kmers[v] > nmask) return fail(c, SHK_ERR_BAD_ARG, "node %llu: sub_kmer is not a %u-mer", (unsigned long long)v, k - 1);
-  for (uint64_t e = 0; e < n_edges; ++e)
-    if (edge_src[e] >= n_nodes || edge_tgt[e] >= n_nodes)
-      return fail(c, SHK_ERR_BAD_ARG, "edge %llu: endpoint (%u, %u) outside the %llu nodes", (unsigned long long)e, edge_src[e], edge_tgt[e],
-                  (unsigned long long)n_nodes);
-  if (!n_edges) return SHK_OK;
-  if (n_edges > (1ull << 30)) return fail(c, SHK_ERR_NOMEM, "graph of %llu edges: the lookup set would not fit", (unsigned long long)n_edges);
-  const uint32_t E = (uint32_t)n_edges;
-  auto revcomp = [k](uint64_t x) {
-    uint64_t r = 0;
-    for (uint32_t i = 0; i < k; ++i, x >>= 2) r = (r << 2) | (3 - (x & 3));
-    return r;
-  };
-  // edge k-mer (reconstruct_edge_kmer, graph.rs:127-134) → canonical key; candidates ascending by (key, edge)
-  std::vector<uint64_t> ekey(E);
-  for (uint32_t e = 0; e < E; ++e) {
-    const uint64_t x = (node_sub_kmers[edge_src[e]] << 2) | (node_sub_kmers[edge_tgt[e]] & 3);
-    ekey[e] = std::min(x, revcomp(x));
-  }
-  pl->cand.resize(E);
-  for (uint32_t e = 0; e < E; ++e) pl->cand[e] = e;
-  std::stable_sort(pl->cand.begin(), pl->cand.end(), [&](uint32_t a, uint32_t b) { return ekey[a] < ekey[b]; });
-  uint64_t n_keys = 0;
-  for (uint32_t i = 0; i < E; ++i) n_keys += i == 0 || ekey[pl->cand[i]] != ekey[pl->cand[i - 1]];
-  uint64_t cap = 16;
-  while (cap < 2 * n_keys) cap <<= 1;
-  pl->keys.assign(cap, EMPTY);
-  pl->start.assign(cap, 0);
-  pl->last.assign((E + 31) / 32, 0);
-  for (uint32_t i = 0; i < E; ++i) {
-    const uint64_t key = ekey[pl->cand[i]];
-    if (i + 1 == E || ekey[pl->cand[i + 1]] != key) pl->last[i >> 5] |= 1u << (i & 31);
-    if (i && ekey[pl->cand[i - 1]] == key) continue;
-    uint64_t s = set_hash(key) & (cap - 1);
-    while (pl->keys[s] != EMPTY) s = (s + 1) & (cap - 1);
-    pl->keys[s] = key;
-    pl->start[s] = i;
-  }
-  // degrees as edge counts (neighbors_directed(..).count(), threading.rs:329-330), ranks among a node's in- and out-edges
-  std::vector<uint32_t> in_deg(n_nodes, 0), out_deg(n_nodes, 0), in_rank(E), out_rank(E);
-  for (uint32_t e = 0; e < E; ++e) in_rank[e] = in_deg[edge_tgt[e]]++, out_rank[e] = out_deg[edge_src[e]]++;
-  pl->out_first.assign(n_nodes + 1, 0);
-  for (uint64_t v = 0; v < n_nodes; ++v) pl->out_first[v + 1] = pl->out_first[v] + out_deg[v];
-  pl->out_list.resize(E);
-  for (uint32_t e = 0; e < E; ++e) pl->out_list[pl->out_first[edge_src[e]] + out_rank[e]] = e;
-  // a branch node v (either degree above 1) owns in_deg · out_deg link slots: (a, b) ↦ base[v] + in_rank(a) · out_deg + out_rank(b)
-  std::vector<uint64_t> base(n_nodes, 0);
-  uint64_t n_slots = 0;
-  for (uint64_t v = 0; v < n_nodes; ++v) {
-    if (in_deg[v] <= 1 && out_deg[v] <= 1) continue;
-    base[v] = n_slots;
-    n_slots += (uint64_t)in_deg[v] * out_deg[v];
-    if (n_slots > (1ull << 31))
-      return fail(c, SHK_ERR_BAD_ARG, "the branch nodes of this graph have more than 2^31 (incoming, outgoing) edge pairs");
-  }
-  pl->n_slots = n_slots;
-  pl->meta.resize(E);
-  for (uint32_t e = 0; e < E; ++e) {
-    const uint32_t v = edge_tgt[e];
-    const bool branch = in_deg[v] > 1 || out_deg[v] > 1;
-    pl->meta[e] = make_uint4(edge_src[e], v, branch ? (uint32_t)(base[v] + (uint64_t)in_rank[e] * out_deg[v]) : TH_NONE, out_rank[e]);
-  }
-  return SHK_OK;
-}
-
-void thread_out_zero(shk_thread_out *out, uint64_t n_edges, uint64_t n_seqs) {
-  if (n_edges) std::fill(out->support_total, out->support_total + n_edges, 0u);
-  if (n_edges) std::fill(out->support_unambiguous, out->support_unambiguous + n_edges, 0u);
-  if (out->read_edges) std::fill(out->read_edges, out->read_edges + n_seqs, 0u);
-  out->n_links = out->n_paired_links = 0;
-}
-
-// offsets as a batch of reads over n_bases bytes (a read's length is a 31-bit number in the kernel)
-int thread_check_offsets(shk_ctx *c, const uint64_t *offsets, uint64_t n_seqs, uint64_t n_bases, uint64_t *max_len,
-                         const char *who = "shk_thread_reads") {
-  *max_len = 0;
-  for (uint64_t i = 0; i < n_seqs; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
-    *max_len = std::max(*max_len, offsets[i + 1] - offsets[i]);
-  }
-  if (offsets[n_seqs] > n_bases)
-    return fail(c, SHK_ERR_BAD_ARG, "offsets end at %llu, beyond the %llu bases", (unsigned long long)offsets[n_seqs], (unsigned long long)n_bases);
-  if (*max_len >= (1ull << 31)) return fail(c, SHK_ERR_BAD_ARG, "a read of %llu bases: %s takes reads below 2^31", (unsigned long long)*max_len, who);
-  return SHK_OK;
-}
-
-// The launch and what follows it.  The batch is resident (d_bases, d_offsets), its offsets checked (h_offsets); the
-// context is settled and its stream idle.
-int thread_core(shk_ctx *c, const ThreadPlan &pl, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t max_len, uint64_t n_seqs,
-                const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
-  const uint32_t k = c->cfg.k, E = (uint32_t)pl.cand.size(), cap = (uint32_t)pl.keys.size();
-  const int lds_edges = env_int("SHK_THREAD_LDS_EDGES", THREAD_LDS_EDGES);
-  const size_t lds = thread_lds_bytes(cap, E);
-  const bool use_lds = (int64_t)E <= (int64_t)lds_edges && lds <= THREAD_LDS_MAX;
-  // every wave keeps one (edge, flags) pair per window of the read it is on: the longest read sizes a wave's scratch,
-  // and 256 MiB of scratch bound the waves
-  const uint64_t max_win = max_len >= k ? max_len - k + 1 : 0;
-  const uint64_t stride = std::max<uint64_t>(THREAD_TILE, (max_win + THREAD_TILE - 1) / THREAD_TILE * THREAD_TILE);
-  const uint64_t wpb = THREAD_WG / 64;
-  uint64_t blocks = std::min<uint64_t>((n_seqs + wpb - 1) / wpb, (uint64_t)c->n_cus * (use_lds ? 1 : 2));
-  blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, ((256ull << 20) / 8) / (stride * wpb)));
-  Scratch m{c->misc};
-  const size_t o_keys = m.take<uint64_t>(cap), o_start = m.take<uint32_t>(cap), o_cand = m.take<uint32_t>(E), o_last = m.take<uint32_t>(pl.last.size()),
-               o_meta = m.take<uint4>(E);
-  const size_t n_cnt = 2 * (size_t)E + pl.n_slots + n_seqs;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
-  const size_t o_cnt = m.take<uint32_t>(n_cnt), o_scr = m.take<uint2>(blocks * wpb * stride);
-  HIPC(c, m.ensure());
-  uint32_t *dtot = m.at<uint32_t>(o_cnt), *dun = dtot + E, *dlinks = dun + E, *dre = dlinks + pl.n_slots;
-  HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_keys), pl.keys.data(), (size_t)cap * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_start), pl.start.data(), (size_t)cap * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_cand), pl.cand.data(), (size_t)E * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_last), pl.last.data(), pl.last.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint4>(o_meta), pl.meta.data(), (size_t)E * 16, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
-  if (getenv("SHK_TRACE"))  // (read at each call, like SHK_THREAD_LDS_EDGES: the tests look for this line)
-    fprintf(stderr, "[shk] thread_reads: %u edges, set of %zu bytes in %s, %llu blocks\n", E, lds, use_lds ? "LDS" : "global memory",
-            (unsigned long long)blocks);
-  const ThreadSet set{m.at<uint64_t>(o_keys), m.at<uint32_t>(o_start), m.at<uint32_t>(o_cand), m.at<uint32_t>(o_last), m.at<uint4>(o_meta), cap - 1, E};
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    if (use_lds) {
-      if (!c->lds_attr_thread) {  // > 64 KiB of dynamic LDS has to be asked for
-        HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_thread_reads<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)THREAD_LDS_MAX));
-        c->lds_attr_thread = true;
-      }
-      hipLaunchKernelGGL(k_thread_reads<true>, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, d_bases, d_offsets, n_seqs, (int)k, set,
-                         m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
-    } else {
-      hipLaunchKernelGGL(k_thread_reads<false>, dim3((uint32_t)blocks), dim3(THREAD_WG), 0, c->stream, d_bases, d_offsets, n_seqs, (int)k, set,
-                         m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
-    }
-  }
-  HIPC(c, hipGetLastError());
-  std::vector<uint32_t> slots(pl.n_slots), re_own;
-  uint32_t *re = out->read_edges;
-  if (!re && mate) {
-    re_own.resize(n_seqs);
-    re = re_own.data();
-  }
-  HIPC(c, hipMemcpyAsync(out->support_total, dtot, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(out->support_unambiguous, dun, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
-  if (pl.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pl.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
-  if (re) HIPC(c, hipMemcpyAsync(re, dre, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the plan alive until its copies ran)
-  // paired_links.len() (threading.rs:166-189): pairs of which an R1 and an R2 read each mapped to some edge
-  out->n_paired_links = 0;
-  if (mate) {
-    std::unordered_map<uint64_t, uint8_t> seen;
-    for (uint64_t i = 0; i < n_seqs; ++i)
-      if (mate[i] && re[i]) {
-        uint8_t &s = seen[read_index[i] / 2];
-        if (s != 3 && (s |= mate[i]) == 3) ++out->n_paired_links;
-      }
-  }
-  // the links that were seen, ascending by (in, out): edge a's slots are its target's out-edges in ascending order
-  uint64_t n_links = 0;
-  for (uint32_t s : slots) n_links += s != 0;
-  out->n_links = n_links;
-  if (n_links > out->link_cap || (n_links && (!out->link_in || !out->link_out || !out->link_counts)))
-    return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)out->link_cap);
-  uint64_t at = 0;
-  for (uint32_t a = 0; a < E && at < n_links; ++a) {
-    if (pl.meta[a].z == TH_NONE) continue;
-    const uint64_t o0 = pl.out_first[pl.meta[a].y], o1 = pl.out_first[pl.meta[a].y + 1];
-    for (uint64_t j = o0; j < o1; ++j)
-      if (const uint32_t n = slots[pl.meta[a].z + (j - o0)]) {
-        out->link_in[at] = a, out->link_out[at] = pl.out_list[j], out->link_counts[at] = n;
-        ++at;
-      }
-  }
-  return SHK_OK;
-}
-
-}  // namespace
-
-int shk_thread_reads_device(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
-                            uint64_t n_edges, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
-                            const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_thread_reads_device(c->group->ctx[0], node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, d_bases, d_offsets, n_seqs,
-                                           n_bases, read_index, mate, out);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || !out || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
-  ThreadPlan pl;
-  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
-  thread_out_zero(out, n_edges, n_seqs);
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read)
-  std::vector<uint64_t> h_off(n_seqs + 1);
-  HIPC(c, hipMemcpyAsync(h_off.data(), d_offsets, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  uint64_t max_len = 0;
-  SHK_TRY(thread_check_offsets(c, h_off.data(), n_seqs, n_bases, &max_len));
-  if (n_edges == 0) return SHK_OK;
-  return thread_core(c, pl, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, max_len, n_seqs, read_index, mate, out);
-}
-
-int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
-                     uint64_t n_edges, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *read_index,
-                     const uint8_t *mate, shk_thread_out *out) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_thread_reads(c->group->ctx[0], node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, bases, offsets, n_seqs, read_index,
-                                    mate, out);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || !out || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
-  ThreadPlan pl;
-  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
-  thread_out_zero(out, n_edges, n_seqs);
-  if (n_seqs == 0) return SHK_OK;
-  uint64_t max_len = 0;
-  SHK_TRY(thread_check_offsets(c, offsets, n_seqs, offsets[n_seqs], &max_len));
-  if (n_edges == 0) return SHK_OK;
-  // the device form's launch over the staged batch (its offsets are already here: no copy back)
-  const uint64_t n_bases = offsets[n_seqs];
-  if (n_bases && !bases) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
-  HIPC(c, hipStreamSynchronize(c->stream));
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  return thread_core(c, pl, (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, max_len, n_seqs, read_index, mate, out);
-}
-
-namespace {
-
-// A panel as k_filter_panel wants it: the distinct k-mers of all genes in one open-addressing table,
-// each with the run of genes that hold it — ThreadPlan's keys / start / cand / last without the edge words.
-struct PanelPlan {
-  std::vector<uint64_t> keys;                // open addressing by set_hash, EMPTY where free, load ≤ 1/2
-  std::vector<uint32_t> start, genes, last;  // a key's first gene; gene ids by (key, gene), each pair once; bit i: genes[i] ends its key's run
-  uint64_t n_keys = 0;
-};
-
-// Everything the panel filter refuses before the device is touched, and the plan of a panel that has k-mers.
-int panel_plan(shk_ctx *c, const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes, PanelPlan *pl) {
-  const uint32_t k = c->cfg.k;
-  if (n_genes > FILTER_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u is above the limit of %u", n_genes, FILTER_MAX_GENES);
-  if (!n_genes) return SHK_OK;
-  if (!gene_offsets) return SHK_ERR_BAD_ARG;
-  for (uint32_t g = 0; g < n_genes; ++g)
-    if (gene_offsets[g + 1] < gene_offsets[g]) return fail(c, SHK_ERR_BAD_ARG, "gene_offsets must be non-decreasing");
-  const uint64_t k0 = gene_offsets[0], k1 = gene_offsets[n_genes];
-  if (k1 > k0 && !primer_kmers) return SHK_ERR_BAD_ARG;
-  if (k1 - k0 > (1ull << 30)) return fail(c, SHK_ERR_NOMEM, "panel of %llu k-mers: the lookup set would not fit", (unsigned long long)(k1 - k0));
-  std::vector<std::pair<uint64_t, uint32_t>> pairs;
-  pairs.reserve(k1 - k0);
-  for (uint32_t g = 0; g < n_genes; ++g)
-    for (uint64_t j = gene_offsets[g]; j < gene_offsets[g + 1]; ++j) {
-      const uint64_t key = primer_kmers[j];
-      if ((key >> (2 * k)) != 0)  // (k ≤ 31)
-        return fail(c, SHK_ERR_BAD_ARG, "primer k-mer %llu does not fit %u bases", (unsigned long long)key, k);
-      pairs.emplace_back(key, g);
-    }
-  std::sort(pairs.begin(), pairs.end());
-  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
-  const uint32_t P = (uint32_t)pairs.size();
-  if (!P) return SHK_OK;
-  for (uint32_t i = 0; i < P; ++i) pl->n_keys += i == 0 || pairs[i].first != pairs[i - 1].first;
-  uint64_t cap = 16;
-  while (cap < 2 * pl->n_keys) cap <<= 1;
-  pl->keys.assign(cap, EMPTY);
-  pl->start.assign(cap, 0);
-  pl->genes.resize(P);
-  pl->last.assign((P + 31) / 32, 0);
-  for (uint32_t i = 0; i < P; ++i) {
-    const uint64_t key = pairs[i].first;
-    pl->genes[i] = pairs[i].second;
-    if (i + 1 == P || pairs[i + 1].first != key) pl->last[i >> 5] |= 1u << (i & 31);
-    if (i && pairs[i - 1].first == key) continue;
-    uint64_t s = set_hash(key) & (cap - 1);
-    while (pl->keys[s] != EMPTY) s = (s + 1) & (cap - 1);
-    pl->keys[s] = key;
-    pl->start[s] = i;
-  }
-  return SHK_OK;
-}
-
-// One k_filter_panel pass with room for `room` records: *n_total = the records the batch has; recs = all of them when
-// they fit (else empty).  The batch is resident, its offsets checked; the context is settled and its stream idle.
-int panel_pass(shk_ctx *c, const PanelPlan &pl, uint32_t n_genes, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs,
-               uint64_t room, std::vector<uint64_t> *recs, uint64_t *n_total) {
-  const uint32_t cap = (uint32_t)pl.keys.size(), P = (uint32_t)pl.genes.size();
-  const int lds_keys = env_int("SHK_FILTER_LDS_KEYS", FILTER_LDS_KEYS);
-  const size_t bitmaps = filter_bitmap_bytes(n_genes), lds = bitmaps + filter_set_bytes(cap, P);
-  const bool use_lds = (int64_t)pl.n_keys <= (int64_t)lds_keys && lds <= FILTER_LDS_MAX;
-  const uint64_t wpb = FILTER_WG / 64;
-  const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_seqs + wpb - 1) / wpb, (uint64_t)c->n_cus * (use_lds ? 1 : 2)));
-  Scratch m{c->misc};
-  const size_t o_keys = m.take<uint64_t>(cap), o_start = m.take<uint32_t>(cap), o_genes = m.take<uint32_t>(P), o_last = m.take<uint32_t>(pl.last.size()),
-               o_n = m.take<unsigned long long>(1), o_rec = m.take<unsigned long long>(room);
-  HIPC(c, m.ensure());
-  unsigned long long *dn = m.at<unsigned long long>(o_n), *drec = m.at<unsigned long long>(o_rec);
-  HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_keys), pl.keys.data(), (size_t)cap * 8, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_start), pl.start.data(), (size_t)cap * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_genes), pl.genes.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint32_t>(o_last), pl.last.data(), pl.last.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
-  if (getenv("SHK_TRACE"))  // (read at each call, like SHK_FILTER_LDS_KEYS: the tests look for this line)
-    fprintf(stderr, "[shk] filter_panel: %u genes, %llu keys, set of %zu bytes in %s, room %llu, %llu blocks\n", n_genes,
-            (unsigned long long)pl.n_keys, lds - bitmaps, use_lds ? "LDS" : "global memory", (unsigned long long)room, (unsigned long long)blocks);
-  const PanelSet set{m.at<uint64_t>(o_keys), m.at<uint32_t>(o_start), m.at<uint32_t>(o_genes), m.at<uint32_t>(o_last), cap - 1, P, n_genes};
-  {
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    if (use_lds) {
-      if (!c->lds_attr_filter) {  // > 64 KiB of dynamic LDS has to be asked for
-        HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_filter_panel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FILTER_LDS_MAX));
-        c->lds_attr_filter = true;
-      }
-      hipLaunchKernelGGL(k_filter_panel<true>, dim3((uint32_t)blocks), dim3(FILTER_WG), lds, c->stream, d_bases, d_offsets, n_seqs, (int)c->cfg.k, set,
-                         drec, room, dn);
-    } else {
-      hipLaunchKernelGGL(k_filter_panel<false>, dim3((uint32_t)blocks), dim3(FILTER_WG), bitmaps, c->stream, d_bases, d_offsets, n_seqs, (int)c->cfg.k,
-                         set, drec, room, dn);
-    }
-  }
-  HIPC(c, hipGetLastError());
-  unsigned long long nt = 0;
-  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the plan alive until its copies ran)
-  *n_total = nt;
-  recs->clear();
-  if (nt && nt <= room) {
-    recs->resize(nt);
-    HIPC(c, hipMemcpy(recs->data(), drec, nt * 8, hipMemcpyDeviceToHost));
-  }
-  return SHK_OK;
-}
-
-// The passes and what follows them: the records sorted by (gene, read) are the answer.  Same preconditions as panel_pass.
-int panel_core(shk_ctx *c, const PanelPlan &pl, uint32_t n_genes, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs,
-               uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
-  if (n_seqs >> FILTER_READ_BITS) return fail(c, SHK_ERR_BAD_ARG, "a batch of %llu reads", (unsigned long long)n_seqs);
-  const uint64_t room = (uint64_t)std::max(env_int("SHK_FILTER_CANDIDATES", 1 << 20), 1);
-  std::vector<uint64_t> recs;
-  uint64_t nt = 0;
-  SHK_TRY(panel_pass(c, pl, n_genes, d_bases, d_offsets, n_seqs, room, &recs, &nt));
-  if (nt > room) {  // the list overflowed: the pass counted what there is, so the second one has room for exactly that
-    uint64_t n2 = 0;
-    SHK_TRY(panel_pass(c, pl, n_genes, d_bases, d_offsets, n_seqs, nt, &recs, &n2));
-    if (n2 != nt)
-      return fail(c, SHK_ERR_INVARIANT, "panel filter rerun produced %llu records, expected %llu", (unsigned long long)n2, (unsigned long long)nt);
-  }
-  std::sort(recs.begin(), recs.end());  // arrival order is not part of the result
-  for (const uint64_t r : recs) ++match_offsets[(r >> FILTER_READ_BITS) + 1];
-  for (uint32_t g = 0; g < n_genes; ++g) match_offsets[g + 1] += match_offsets[g];
-  *n_matches = nt;
-  if (nt > match_cap || (nt && !match_reads))
-    return fail(c, SHK_ERR_BAD_ARG, "%llu matches do not fit match_cap %llu", (unsigned long long)nt, (unsigned long long)match_cap);
-  for (uint64_t i = 0; i < nt; ++i) match_reads[i] = recs[i] & ((1ull << FILTER_READ_BITS) - 1);
-  return SHK_OK;
-}
-
-}  // namespace
-
-int shk_filter_reads_panel_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
-                                  const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets,
-                                  uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_filter_reads_panel_device(c->group->ctx[0], d_bases, d_offsets, n_seqs, n_bases, primer_kmers, gene_offsets, n_genes,
-                                                 match_offsets, match_reads, match_cap, n_matches);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || !match_offsets || !n_matches || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
-  PanelPlan pl;
-  SHK_TRY(panel_plan(c, primer_kmers, gene_offsets, n_genes, &pl));
-  std::fill(match_offsets, match_offsets + n_genes + 1, 0ull);
-  *n_matches = 0;
-  if (n_seqs == 0) return SHK_OK;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read)
-  std::vector<uint64_t> h_off(n_seqs + 1);
-  HIPC(c, hipMemcpyAsync(h_off.data(), d_offsets, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  uint64_t max_len = 0;
-  SHK_TRY(thread_check_offsets(c, h_off.data(), n_seqs, n_bases, &max_len, "shk_filter_reads_panel"));
-  if (pl.genes.empty()) return SHK_OK;
-  return panel_core(c, pl, n_genes, (const uint8_t *)d_bases, (const uint64_t *)d_offsets, n_seqs, match_offsets, match_reads, match_cap, n_matches);
-}
-
-int shk_filter_reads_panel(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *primer_kmers,
-                           const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap,
-                           uint64_t *n_matches) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_filter_reads_panel(c->group->ctx[0], bases, offsets, n_seqs, primer_kmers, gene_offsets, n_genes, match_offsets,
-                                          match_reads, match_cap, n_matches);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || !match_offsets || !n_matches || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
-  PanelPlan pl;
-  SHK_TRY(panel_plan(c, primer_kmers, gene_offsets, n_genes, &pl));
-  std::fill(match_offsets, match_offsets + n_genes + 1, 0ull);
-  *n_matches = 0;
-  if (n_seqs == 0) return SHK_OK;
-  uint64_t max_len = 0;
-  SHK_TRY(thread_check_offsets(c, offsets, n_seqs, offsets[n_seqs], &max_len, "shk_filter_reads_panel"));
-  if (pl.genes.empty()) return SHK_OK;
-  // the device form's passes over the staged batch (its offsets are already here: no copy back)
-  const uint64_t n_bases = offsets[n_seqs];
-  if (n_bases && !bases) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(settle(c));  // (not table_read_begin: the table is not read; the staging buffers may still feed a counting launch)
-  HIPC(c, hipStreamSynchronize(c->stream));
-  HIPC(c, c->in_bases.ensure(n_bases + 16));
-  HIPC(c, c->in_offsets.ensure((n_seqs + 2) * 8));
-  if (n_bases) HIPC(c, hipMemcpyAsync(c->in_bases.p, bases, n_bases, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(c->in_offsets.p, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  return panel_core(c, pl, n_genes, (const uint8_t *)c->in_bases.p, (const uint64_t *)c->in_offsets.p, n_seqs, match_offsets, match_reads,
-                    match_cap, n_matches);
-}
-
-int shk_gather_reads_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, const uint64_t *read_ids, uint64_t n_ids,
-                            void *d_out_bases, uint64_t out_bases_cap, void *d_out_offsets, uint64_t *n_out_bases) {
-  if (c && c->group) {  // stateless: any device will do
-    const int rc = shk_gather_reads_device(c->group->ctx[0], d_bases, d_offsets, n_seqs, read_ids, n_ids, d_out_bases, out_bases_cap,
-                                           d_out_offsets, n_out_bases);
-    return rc == SHK_OK ? rc : group_fail(c, c->group, rc, 0);
-  }
-  if (!c || !n_out_bases || (n_ids && !read_ids) || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
-  *n_out_bases = 0;
-  for (uint64_t j = 0; j < n_ids; ++j)
-    if (read_ids[j] >= n_seqs)
-      return fail(c, SHK_ERR_BAD_ARG, "read_ids[%llu] = %llu is outside the %llu reads", (unsigned long long)j, (unsigned long long)read_ids[j],
-                  (unsigned long long)n_seqs);
-  HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(settle(c));  // (the call's scratch and stream are the context's)
-  std::vector<uint64_t> h_off(n_seqs + 1, 0), out_off(n_ids + 1, 0);
-  if (n_seqs) HIPC(c, hipMemcpyAsync(h_off.data(), d_offsets, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  for (uint64_t i = 0; i < n_seqs; ++i)
-    if (h_off[i + 1] < h_off[i]) return fail(c, SHK_ERR_BAD_ARG, "offsets must be non-decreasing");
-  for (uint64_t j = 0; j < n_ids; ++j) out_off[j + 1] = out_off[j] + (h_off[read_ids[j] + 1] - h_off[read_ids[j]]);
-  const uint64_t need = out_off[n_ids];
-  *n_out_bases = need;
-  if (need > out_bases_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "%llu bases do not fit out_bases_cap %llu", (unsigned long long)need, (unsigned long long)out_bases_cap);
-  if (!d_out_offsets || (need && (!d_out_bases || !d_bases))) return SHK_ERR_BAD_ARG;
-  HIPC(c, hipMemcpyAsync(d_out_offsets, out_off.data(), (n_ids + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  if (need) {
-    Scratch m{c->misc};
-    const size_t o_ids = m.take<uint64_t>(n_ids);
-    HIPC(c, m.ensure());
-    HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_ids), read_ids, n_ids * 8, hipMemcpyHostToDevice, c->stream));
-    const uint64_t wpb = WG / 64;
-    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_ids + wpb - 1) / wpb, (uint64_t)c->n_cus * 8));
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_gather_reads, dim3((uint32_t)blocks), dim3(WG), 0, c->stream, (const uint8_t *)d_bases, (const uint64_t *)d_offsets,
-                       (const uint64_t *)m.at<uint64_t>(o_ids), n_ids, (const uint64_t *)d_out_offsets, (uint8_t *)d_out_bases);
-  }
-  HIPC(c, hipGetLastError());
-  HIPC(c, hipStreamSynchronize(c->stream));  // (keeps out_off and read_ids alive until their copies ran; the batch is complete on return)
-  return SHK_OK;
-}
-
 int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {
   SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
