@@ -387,6 +387,62 @@ int shk_thread_reads_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64
                             const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                             const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out);
 
+/* shk_thread_reads for a whole sPCR panel in ONE call: do_pcr threads each gene's filtered reads through that gene's
+ * pruned graph (src/pcr/mod.rs:663-697, src/pcr/threading.rs:87-192); this call takes every graph of the panel, the
+ * per-gene read lists as shk_filter_reads_panel returns them and the batch where it lies, and answers for all genes
+ * from one launch — no gather, no second copy of the reads.
+ * GRAPHS: gene g's graph is nodes node_sub_kmers[node_offsets[g] .. node_offsets[g+1]) and edges
+ *   [edge_offsets[g] .. edge_offsets[g+1]) of edge_src / edge_tgt, whose entries are node positions LOCAL to the gene
+ *   (0 = the gene's first node): n_genes outputs of shk_pcr_extend, or the caller's pruned graphs, concatenate without
+ *   renumbering.  Each graph follows the rules of shk_thread_reads: EDGE K-MER, candidates ascending by edge
+ *   (build_edge_lookup, threading.rs:203-220), degrees as edge counts (threading.rs:329-330).  All three offset arrays
+ *   have n_genes + 1 entries, non-decreasing.
+ * LISTS: gene g's reads are list_reads[list_offsets[g] .. list_offsets[g+1]), indices into the batch — exactly the
+ *   match_offsets / match_reads of shk_filter_reads_panel.  Any order is accepted, a read may be in any number of
+ *   genes, and a repeat inside a list counts twice, as it would in a gathered batch.
+ * RESULT: for every g, what shk_thread_reads gives for gene g's graph over the batch made of its listed reads in list
+ *   order (threading.rs:87-192): support_* at edge_offsets[g] .., the links ascending by (in, out) at
+ *   [link_offsets[g], link_offsets[g+1]) with edge indices LOCAL to the gene, read_edges per list position.  With
+ *   read_index and mate given (indexed by read of the BATCH, n_seqs entries each), n_paired_links[g] = the distinct
+ *   read_index / 2 for which some listed R1 read and some listed R2 read of gene g each mapped to an edge
+ *   (threading.rs:166-189).
+ * DEGENERATE: a gene with no edges: its read_edges are 0; a gene with no reads: its supports are 0; n_genes == 0:
+ *   all zero; a read with a byte outside ACGTN contributes nothing and is no error (threading.rs:98-101).
+ * link_cap too small: SHK_ERR_BAD_ARG with n_links set to the need and link_offsets complete; the other outputs are
+ *   complete too, as in shk_thread_reads.
+ * Errors, SHK_ERR_BAD_ARG with a text that names the gene, all raised before the device is touched (the device form
+ *   has to copy the read offsets back to check them): every graph error of shk_thread_reads; decreasing node_offsets,
+ *   edge_offsets, list_offsets or read offsets; a listed read ≥ n_seqs; n_genes > SHK_THREAD_MAX_GENES; one of
+ *   read_index / mate without the other; mate > 2; a panel with 2^32 edges or more in total; a panel with more than
+ *   2^31 link slots ((incoming, outgoing) pairs at branch nodes) in total.
+ * The context's table is neither read nor written; valid whenever shk_thread_reads is, on owner shares too; a
+ * multi-device context runs it on its first device.  Tuning, all read at each call, none changes the result:
+ * SHK_THREAD_LDS_EDGES decides per gene, as for shk_thread_reads, whether the gene's set goes to LDS;
+ * SHK_THREAD_PANEL_JOB (reads, default 16): every list is cut into slices of at most that many reads, the jobs the
+ * workgroups share out; SHK_THREAD_PANEL_BLOCKS (0 = the rule of shk_thread_reads) caps the workgroups. */
+#define SHK_THREAD_MAX_GENES 4096   /* = SHK_FILTER_MAX_GENES: the lists come from that call */
+typedef struct shk_thread_panel_out {  /* every pointer optional except the two support arrays */
+  uint32_t *support_total;        /* [edge_offsets[n_genes]] gene g's edges at edge_offsets[g] ..            */
+  uint32_t *support_unambiguous;  /* same layout                                                           */
+  uint64_t *link_offsets;         /* [n_genes + 1] gene g's links are [link_offsets[g], link_offsets[g+1])   */
+  uint32_t *link_in, *link_out, *link_counts; uint64_t link_cap, n_links;  /* edge indices LOCAL to the gene */
+  uint32_t *read_edges;           /* [list_offsets[n_genes]] aligned with list_reads                         */
+  uint64_t *n_paired_links;       /* [n_genes]; zeros when mate == NULL                                      */
+} shk_thread_panel_out;
+/* Host buffers (bases / offsets as shk_ingest_reads): stages the batch, then as the device form. */
+int shk_thread_reads_panel(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint64_t *node_offsets,
+                           const uint32_t *edge_src, const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes,
+                           const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
+                           const uint64_t *list_offsets, const uint64_t *list_reads,
+                           const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out);
+/* The batch resident in device memory (d_bases: n_bases bytes, d_offsets: n_seqs + 1 u64, as shk_ingest_reads_device);
+ * everything else on the host.  The offsets are copied back once.  Returns when the annotations are complete. */
+int shk_thread_reads_panel_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint64_t *node_offsets,
+                                  const uint32_t *edge_src, const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes,
+                                  const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                                  const uint64_t *list_offsets, const uint64_t *list_reads,
+                                  const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out);
+
 /* PrimerReadFilter::filter_reads (src/pcr/read_filter.rs:24-55) for a whole sPCR panel in ONE pass over the batch:
  * do_pcr runs once per gene (stats.rs:85-87) and filters every retained read against that gene's primer k-mers
  * (pcr/mod.rs:470-485); this call walks the reads once and answers for all n_genes genes.

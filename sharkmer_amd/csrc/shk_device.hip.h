@@ -1807,6 +1807,119 @@ __host__ __device__ inline size_t thread_lds_bytes(uint32_t cap, uint32_t n_edge
   return (size_t)n_edges * 16 + key_runs_bytes(cap, n_edges) + (size_t)n_edges * 8;
 }
 
+// A graph in front of the walk of one read: its set and meta, in LDS or in global memory, and its counters — the
+// two supports where the kernel keeps them (LDS-private or global), the link slots always global.
+struct ThreadView {
+  KeyRuns runs;
+  const uint4 *meta;
+  uint32_t *total, *unamb, *links;
+};
+
+// The walk of ONE read by one wave — both sweeps, from its first bytes to its last atomic (see K_THREAD above): rb, len
+// the read, scr the wave's scratch (one entry per window of the read) → the edges the read was mapped to (read_edges).
+// The one copy of the walk: k_thread_reads and k_thread_panel both call it, each with its own view.
+__device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const uint8_t *__restrict__ rb, uint32_t len, int k, uint2 *__restrict__ scr,
+                                                uint32_t lane) {
+  const uint32_t km = (1u << k) - 1u;         // k ≤ 31
+  const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
+  const uint64_t upto = below | (1ull << lane);
+  const uint32_t n_win = len >= (uint32_t)k ? len - (uint32_t)k + 1u : 0u;  // (a shorter read has no k-mer, valid or not)
+  uint32_t n_hit = 0;
+  bool bad = false;
+  // ---- sweep 1, first step first: edges, run flags, link slots → scratch
+  uint32_t c_hit = 0, c_tgt = 0, c_lbase = TH_NONE, c_pre = 0;  // the last list element so far
+  ReadPlanes lo{0, 0, 0, false};
+  if (n_win) lo = read_planes(rb, lane, len);
+  bad = lo.bad;
+  for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
+    const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
+    if (hi.bad) {  // encoding.rs:353-356 → Err → the read is skipped whole
+      bad = true;
+      break;
+    }
+    uint64_t key = 0;
+    const bool v = window_key(lo, hi, lane, k, km, s0, n_win, &key);  // a list element
+    uint32_t edge = TH_NONE, src = 0, tgt = 0, lbase = TH_NONE, orank = 0, cstart = 0;
+    int hit = 0;
+    bool multi = false;
+    if (v) {
+      const uint32_t s = set_find(t.runs.keys, t.runs.mask, key);
+      if (s != SET_NONE) {
+        hit = 1, cstart = t.runs.start[s];
+        multi = !run_ends(t.runs.last, cstart);
+        if (!multi) {
+          edge = t.runs.items[cstart];
+          const uint4 m = t.meta[edge];
+          src = m.x, tgt = m.y, lbase = m.z, orank = m.w;
+        }
+      }
+    }
+    const uint64_t vm = __ballot(v);
+    for (uint64_t mm = __ballot(multi); mm; mm &= mm - 1) {  // in list order; everything here is wave-uniform
+      const int m = __ffsll((unsigned long long)mm) - 1;
+      const uint64_t under = vm & ((1ull << m) - 1);
+      const int pl = under ? 63 - __clzll((long long)under) : 0;
+      const int sh = __shfl(hit, pl);
+      const uint32_t st = __shfl(tgt, pl);
+      const bool ph = under ? sh != 0 : c_hit != 0;
+      const uint32_t pt = under ? st : c_tgt;
+      const uint32_t first = __shfl(cstart, m);
+      uint32_t pick = t.runs.items[first];  // no previous edge, or none adjacent: candidate 0 (threading.rs:255)
+      if (ph)
+        for (uint32_t i = first;; ++i) {
+          const uint32_t e = t.runs.items[i];
+          if (t.meta[e].x == pt) {
+            pick = e;
+            break;
+          }
+          if (run_ends(t.runs.last, i)) break;
+        }
+      const uint4 pm = t.meta[pick];
+      if ((int)lane == m) edge = pick, src = pm.x, tgt = pm.y, lbase = pm.z, orank = pm.w;
+    }
+    // my predecessor in the list
+    const uint64_t under = vm & below;
+    const int pl = under ? 63 - __clzll((long long)under) : 0;
+    const int sh = __shfl(hit, pl);
+    const uint32_t st = __shfl(tgt, pl), sl = __shfl(lbase, pl);
+    const bool ph = under ? sh != 0 : c_hit != 0;
+    const uint32_t pt = under ? st : c_tgt, plb = under ? sl : c_lbase;
+    const bool cont = hit && ph && pt == src;
+    const bool bp = cont && plb != TH_NONE;
+    const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
+    const uint64_t s_le = sm & upto;
+    const bool pre = s_le ? (bm & upto & ~((1ull << (63 - __clzll((long long)s_le))) - 1)) != 0 : ((bm & upto) != 0 || c_pre != 0);
+    scr[s0 + lane] = make_uint2(edge, bp ? plb + orank : 0x80000000u | (v ? 4u : 0u) | (pre ? 2u : 0u) | (cont ? 1u : 0u));
+    n_hit += (uint32_t)__popcll(__ballot(hit));
+    if (vm) {
+      const int top = 63 - __clzll((long long)vm);
+      c_hit = (uint32_t)__shfl(hit, top), c_tgt = __shfl(tgt, top), c_lbase = __shfl(lbase, top);
+      c_pre = (uint32_t)__shfl((int)pre, top);
+    }
+    lo = hi;
+  }
+  if (bad) n_hit = 0;
+  if (!n_hit) return 0;
+  // ---- sweep 2, last step first: the atomics
+  __threadfence_block();  // the wave reads what its other lanes wrote
+  uint32_t c_suf = 0;     // a branch pair between the next step's start and the end of the run that enters it
+  for (uint32_t s0 = (n_win - 1) & ~(THREAD_TILE - 1);; s0 -= THREAD_TILE) {
+    const uint2 q = scr[s0 + lane];
+    const bool bp = !(q.y >> 31), v = bp || (q.y & 4u), cont = bp || (q.y & 1u), pre = bp || (q.y & 2u);
+    const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
+    const uint64_t s_gt = sm & ~upto;
+    const bool suf = s_gt ? (bm & ~upto & ((1ull << (__ffsll((unsigned long long)s_gt) - 1)) - 1)) != 0 : ((bm & ~upto) != 0 || c_suf != 0);
+    if (q.x != TH_NONE) {
+      atomicAdd(&t.total[q.x], 1u);
+      if (!pre && !suf) atomicAdd(&t.unamb[q.x], 1u);
+    }
+    if (bp) atomicAdd(&t.links[q.y], 1u);
+    c_suf = sm ? (bm & ((1ull << (__ffsll((unsigned long long)sm) - 1)) - 1)) != 0 : (bm != 0 || c_suf != 0);
+    if (s0 == 0) break;
+  }
+  return n_hit;
+}
+
 template <bool LDS>
 __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
                                                             uint64_t n_seqs, int k, ThreadSet gs, uint2 *__restrict__ scratch,
@@ -1823,117 +1936,17 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
     for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gs.meta[i], lt[i] = 0, lu[i] = 0;
     __syncthreads();
   }
-  const uint32_t *cand = ks.items;
-  const uint4 *meta = LDS ? lm : gs.meta;
-  uint32_t *ctot = LDS ? lt : total, *cun = LDS ? lu : unamb;
+  const ThreadView view{ks, LDS ? lm : gs.meta, LDS ? lt : total, LDS ? lu : unamb, links};
 
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t wave = (uint64_t)blockIdx.x * (THREAD_WG / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t n_waves = (uint64_t)gridDim.x * (THREAD_WG / 64);
   uint2 *scr = scratch + wave * scr_stride;
-  const uint32_t km = (1u << k) - 1u;         // k ≤ 31
-  const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
-  const uint64_t upto = below | (1ull << lane);
 
   for (uint64_t r = wave; r < n_seqs; r += n_waves) {
     const uint64_t b0 = offsets[r];
-    const uint32_t len = (uint32_t)(offsets[r + 1] - b0);
-    const uint32_t n_win = len >= (uint32_t)k ? len - (uint32_t)k + 1u : 0u;  // (a shorter read has no k-mer, valid or not)
-    const uint8_t *rb = bases + b0;
-    uint32_t n_hit = 0;
-    bool bad = false;
-    // ---- sweep 1, first step first: edges, run flags, link slots → scratch
-    uint32_t c_hit = 0, c_tgt = 0, c_lbase = TH_NONE, c_pre = 0;  // the last list element so far
-    ReadPlanes lo{0, 0, 0, false};
-    if (n_win) lo = read_planes(rb, lane, len);
-    bad = lo.bad;
-    for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
-      const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
-      if (hi.bad) {  // encoding.rs:353-356 → Err → the read is skipped whole
-        bad = true;
-        break;
-      }
-      uint64_t key = 0;
-      const bool v = window_key(lo, hi, lane, k, km, s0, n_win, &key);  // a list element
-      uint32_t edge = TH_NONE, src = 0, tgt = 0, lbase = TH_NONE, orank = 0, cstart = 0;
-      int hit = 0;
-      bool multi = false;
-      if (v) {
-        const uint32_t s = set_find(ks.keys, ks.mask, key);
-        if (s != SET_NONE) {
-          hit = 1, cstart = ks.start[s];
-          multi = !run_ends(ks.last, cstart);
-          if (!multi) {
-            edge = cand[cstart];
-            const uint4 m = meta[edge];
-            src = m.x, tgt = m.y, lbase = m.z, orank = m.w;
-          }
-        }
-      }
-      const uint64_t vm = __ballot(v);
-      for (uint64_t mm = __ballot(multi); mm; mm &= mm - 1) {  // in list order; everything here is wave-uniform
-        const int m = __ffsll((unsigned long long)mm) - 1;
-        const uint64_t under = vm & ((1ull << m) - 1);
-        const int pl = under ? 63 - __clzll((long long)under) : 0;
-        const int sh = __shfl(hit, pl);
-        const uint32_t st = __shfl(tgt, pl);
-        const bool ph = under ? sh != 0 : c_hit != 0;
-        const uint32_t pt = under ? st : c_tgt;
-        const uint32_t first = __shfl(cstart, m);
-        uint32_t pick = cand[first];  // no previous edge, or none adjacent: candidate 0 (threading.rs:255)
-        if (ph)
-          for (uint32_t i = first;; ++i) {
-            const uint32_t e = cand[i];
-            if (meta[e].x == pt) {
-              pick = e;
-              break;
-            }
-            if (run_ends(ks.last, i)) break;
-          }
-        const uint4 pm = meta[pick];
-        if ((int)lane == m) edge = pick, src = pm.x, tgt = pm.y, lbase = pm.z, orank = pm.w;
-      }
-      // my predecessor in the list
-      const uint64_t under = vm & below;
-      const int pl = under ? 63 - __clzll((long long)under) : 0;
-      const int sh = __shfl(hit, pl);
-      const uint32_t st = __shfl(tgt, pl), sl = __shfl(lbase, pl);
-      const bool ph = under ? sh != 0 : c_hit != 0;
-      const uint32_t pt = under ? st : c_tgt, plb = under ? sl : c_lbase;
-      const bool cont = hit && ph && pt == src;
-      const bool bp = cont && plb != TH_NONE;
-      const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
-      const uint64_t s_le = sm & upto;
-      const bool pre = s_le ? (bm & upto & ~((1ull << (63 - __clzll((long long)s_le))) - 1)) != 0 : ((bm & upto) != 0 || c_pre != 0);
-      scr[s0 + lane] = make_uint2(edge, bp ? plb + orank : 0x80000000u | (v ? 4u : 0u) | (pre ? 2u : 0u) | (cont ? 1u : 0u));
-      n_hit += (uint32_t)__popcll(__ballot(hit));
-      if (vm) {
-        const int top = 63 - __clzll((long long)vm);
-        c_hit = (uint32_t)__shfl(hit, top), c_tgt = __shfl(tgt, top), c_lbase = __shfl(lbase, top);
-        c_pre = (uint32_t)__shfl((int)pre, top);
-      }
-      lo = hi;
-    }
-    if (bad) n_hit = 0;
+    const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
     if (read_edges && lane == 0) read_edges[r] = n_hit;
-    if (!n_hit) continue;
-    // ---- sweep 2, last step first: the atomics
-    __threadfence_block();  // the wave reads what its other lanes wrote
-    uint32_t c_suf = 0;     // a branch pair between the next step's start and the end of the run that enters it
-    for (uint32_t s0 = (n_win - 1) & ~(THREAD_TILE - 1);; s0 -= THREAD_TILE) {
-      const uint2 q = scr[s0 + lane];
-      const bool bp = !(q.y >> 31), v = bp || (q.y & 4u), cont = bp || (q.y & 1u), pre = bp || (q.y & 2u);
-      const uint64_t sm = __ballot(v && !cont), bm = __ballot(bp);
-      const uint64_t s_gt = sm & ~upto;
-      const bool suf = s_gt ? (bm & ~upto & ((1ull << (__ffsll((unsigned long long)s_gt) - 1)) - 1)) != 0 : ((bm & ~upto) != 0 || c_suf != 0);
-      if (q.x != TH_NONE) {
-        atomicAdd(&ctot[q.x], 1u);
-        if (!pre && !suf) atomicAdd(&cun[q.x], 1u);
-      }
-      if (bp) atomicAdd(&links[q.y], 1u);
-      c_suf = sm ? (bm & ((1ull << (__ffsll((unsigned long long)sm) - 1)) - 1)) != 0 : (bm != 0 || c_suf != 0);
-      if (s0 == 0) break;
-    }
   }
   if (LDS) {
     __syncthreads();
@@ -1941,6 +1954,108 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__res
       if (lt[i]) atomicAdd(&total[i], lt[i]);
       if (lu[i]) atomicAdd(&unamb[i], lu[i]);
     }
+  }
+}
+
+// k_thread_panel: the same walk for a whole sPCR panel in one launch (shk_thread_reads_panel).  The host
+// concatenates every gene's set into one upload and describes each gene in a ThreadGene; the genes' read lists, cut
+// into slices, are the JOBS, in (gene, slice) order.  Workgroups are persistent: each walks a contiguous range of jobs
+// and so holds one gene at a time — its set in LDS with LDS-private supports, or pointers to the global arrays.  At a job
+// of another gene: a barrier (no wave is still walking), the held gene's private supports flushed (one global atomic
+// per touched edge), a barrier (nobody still reads what the load overwrites), the new gene loaded, a barrier.  Inside a
+// job wave w takes the slice's reads w, w + 16, …: list position → list_reads → offsets → bytes; read_edges is written
+// at the list position.  No workgroup reads what another wrote: counters meet in global atomics and the host reads
+// them after the launch.
+struct ThreadGene {              // 64 bytes
+  uint64_t keys, start, items, last, meta;  // byte offsets of the gene's arrays within the upload (16-byte aligned each)
+  uint32_t mask, n_edges;        // of its set: slots − 1; items = edges
+  uint32_t cnt_base, link_base;  // its first edge in total / unamb, its first slot in links
+  uint32_t lds, pad;             // whether its set goes to LDS
+};
+static_assert(sizeof(ThreadGene) == 64, "a gene's descriptor is 64 bytes");
+struct ThreadJob {               // 16 bytes
+  uint64_t first;                // list position of the slice's first read (within list_reads as uploaded)
+  uint32_t gene, n;              // n reads
+};
+static_assert(sizeof(ThreadJob) == 16, "a job is 16 bytes");
+constexpr int THREAD_PANEL_JOB = THREAD_WG / 64;   // reads per job (SHK_THREAD_PANEL_JOB): one per wave of the workgroup — the finest cut that
+                                                   // leaves no wave without a read, so the workgroups' shares differ by at most 16 reads; a job
+                                                   // costs 16 bytes and one scalar load, a gene change depends on the ranges, not on the cut
+static_assert(SHK_THREAD_MAX_GENES == SHK_FILTER_MAX_GENES, "the lists come from shk_filter_reads_panel");
+
+__device__ __forceinline__ ThreadView thread_view_global(const ThreadGene &g, const uint8_t *__restrict__ up, uint32_t *total, uint32_t *unamb,
+                                                         uint32_t *links) {
+  return ThreadView{KeyRuns{(const uint64_t *)(up + g.keys), (const uint32_t *)(up + g.start), (const uint32_t *)(up + g.items),
+                            (const uint32_t *)(up + g.last), g.mask, g.n_edges},
+                    (const uint4 *)(up + g.meta), total + g.cnt_base, unamb + g.cnt_base, links + g.link_base};
+}
+
+__global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                            const uint64_t *__restrict__ list_reads, const ThreadGene *__restrict__ genes,
+                                                            const ThreadJob *__restrict__ jobs, uint32_t n_jobs,
+                                                            const uint8_t *__restrict__ upload, int k, uint2 *__restrict__ scratch,
+                                                            uint32_t scr_stride, uint32_t *__restrict__ total, uint32_t *__restrict__ unamb,
+                                                            uint32_t *__restrict__ links, uint32_t *__restrict__ read_edges) {
+  extern __shared__ __align__(16) uint8_t th_lds[];  // laid out per gene as k_thread_reads<true> lays it out (thread_lds_bytes)
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint2 *scr = scratch + ((uint64_t)blockIdx.x * (THREAD_WG / 64) + wib) * scr_stride;
+  // this workgroup's jobs: a contiguous range, so that it changes gene as rarely as possible
+  const uint32_t j0 = (uint32_t)((uint64_t)n_jobs * blockIdx.x / gridDim.x), j1 = (uint32_t)((uint64_t)n_jobs * (blockIdx.x + 1) / gridDim.x);
+  uint32_t held = TH_NONE;  // the gene this workgroup holds
+  ThreadGene g{};
+  // the held gene's two private supports, flushed: every thread its own indices
+  auto flush = [&]() {
+    const uint32_t E = g.n_edges;
+    const uint32_t *lt = (const uint32_t *)(th_lds + (size_t)E * 16 + key_runs_bytes(g.mask + 1, E)), *lu = lt + E;
+    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) {
+      if (lt[i]) atomicAdd(&total[g.cnt_base + i], lt[i]);
+      if (lu[i]) atomicAdd(&unamb[g.cnt_base + i], lu[i]);
+    }
+  };
+  for (uint32_t j = j0; j < j1; ++j) {
+    const ThreadJob job = jobs[j];
+    if (job.gene != held) {  // (the same for every thread of the workgroup: the barriers are met by all)
+      __syncthreads();
+      if (held != TH_NONE && g.lds) flush();
+      __syncthreads();
+      held = job.gene;
+      g = genes[held];
+      if (g.lds) {
+        const uint32_t E = g.n_edges;
+        const ThreadView gv = thread_view_global(g, upload, total, unamb, links);
+        uint4 *lm = (uint4 *)th_lds;
+        uint32_t *lt = (uint32_t *)(th_lds + (size_t)E * 16 + key_runs_bytes(g.mask + 1, E)), *lu = lt + E;
+        key_runs_to_lds(gv.runs, th_lds + (size_t)E * 16, THREAD_WG);
+        for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gv.meta[i], lt[i] = 0, lu[i] = 0;
+      }
+      __syncthreads();
+    }
+    uint32_t *re = read_edges + job.first;
+    const uint64_t *ids = list_reads + job.first;
+    if (g.lds) {
+      const uint32_t E = g.n_edges, cap = g.mask + 1;
+      uint8_t *kb = th_lds + (size_t)E * 16;  // key_runs_to_lds' layout
+      uint32_t *ls = (uint32_t *)(kb + (size_t)cap * 8), *lt = (uint32_t *)(kb + key_runs_bytes(cap, E));
+      const ThreadView view{KeyRuns{(const uint64_t *)kb, ls, ls + cap, ls + cap + E, g.mask, E}, (const uint4 *)th_lds, lt, lt + E,
+                            links + g.link_base};
+      for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
+        const uint64_t r = ids[i], b0 = offsets[r];
+        const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
+        if (lane == 0) re[i] = n_hit;
+      }
+    } else {
+      const ThreadView view = thread_view_global(g, upload, total, unamb, links);
+      for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
+        const uint64_t r = ids[i], b0 = offsets[r];
+        const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
+        if (lane == 0) re[i] = n_hit;
+      }
+    }
+  }
+  if (held != TH_NONE && g.lds) {
+    __syncthreads();
+    flush();
   }
 }
 

@@ -1,5 +1,5 @@
 // shk_reads_api.hip.h — the read-side calls of the C ABI (included by shk_engine.hip, same translation unit): a batch of
-// reads walked against a lookup set the host builds (shk_filter_reads, shk_filter_reads_panel, shk_thread_reads), decoded
+// reads walked against a lookup set the host builds (shk_filter_reads, shk_filter_reads_panel, shk_thread_reads[_panel]), decoded
 // (shk_kmers_from_reads) or copied (shk_gather_reads_device).  None reads the table.  What they share comes first: the
 // host side of set_find / KeyRuns (shk_device.hip.h), the two openers of a batch, the LDS-or-global launch, the forward.
 namespace {
@@ -286,6 +286,43 @@ void thread_out_zero(shk_thread_out *out, uint64_t n_edges, uint64_t n_seqs) {
   out->n_links = out->n_paired_links = 0;
 }
 
+// What follows a launch, for shk_thread_reads and, per gene, for shk_thread_reads_panel.
+// paired_links.len() (threading.rs:166-189): pairs of which an R1 and an R2 read each mapped to some edge.  Position i
+// of the n walked is read reads[i] of the batch (reads == NULL: read i) and mapped to re[i] edges.
+uint64_t thread_paired_links(const uint64_t *reads, uint64_t n, const uint64_t *read_index, const uint8_t *mate, const uint32_t *re) {
+  std::unordered_map<uint64_t, uint8_t> seen;
+  uint64_t n_pairs = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t r = reads ? reads[i] : i;
+    if (mate[r] && re[i]) {
+      uint8_t &s = seen[read_index[r] / 2];
+      if (s != 3 && (s |= mate[r]) == 3) ++n_pairs;
+    }
+  }
+  return n_pairs;
+}
+// the links that were seen: the slots that are not 0 …
+uint64_t thread_links_count(const uint32_t *slots, uint64_t n_slots) {
+  uint64_t n_links = 0;
+  for (uint64_t i = 0; i < n_slots; ++i) n_links += slots[i] != 0;
+  return n_links;
+}
+// … ascending by (in, out): edge a's slots are its target's out-edges in ascending order
+void thread_links_decode(const ThreadPlan &pl, const uint32_t *slots, uint64_t n_links, uint32_t *link_in, uint32_t *link_out,
+                         uint32_t *link_counts) {
+  const uint32_t E = (uint32_t)pl.meta.size();
+  uint64_t at = 0;
+  for (uint32_t a = 0; a < E && at < n_links; ++a) {
+    if (pl.meta[a].z == TH_NONE) continue;
+    const uint64_t o0 = pl.out_first[pl.meta[a].y], o1 = pl.out_first[pl.meta[a].y + 1];
+    for (uint64_t j = o0; j < o1; ++j)
+      if (const uint32_t n = slots[pl.meta[a].z + (j - o0)]) {
+        link_in[at] = a, link_out[at] = pl.out_list[j], link_counts[at] = n;
+        ++at;
+      }
+  }
+}
+
 // The launch over an opened batch (its offsets checked) and what follows it.
 int thread_core(shk_ctx *c, const ThreadPlan &pl, const ReadBatch &b, const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
   const uint32_t k = c->cfg.k, E = (uint32_t)pl.runs.items.size(), cap = (uint32_t)pl.runs.keys.size();
@@ -329,32 +366,12 @@ int thread_core(shk_ctx *c, const ThreadPlan &pl, const ReadBatch &b, const uint
   if (pl.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pl.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
   if (re) HIPC(c, hipMemcpyAsync(re, dre, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the plan alive until its copies ran)
-  // paired_links.len() (threading.rs:166-189): pairs of which an R1 and an R2 read each mapped to some edge
-  out->n_paired_links = 0;
-  if (mate) {
-    std::unordered_map<uint64_t, uint8_t> seen;
-    for (uint64_t i = 0; i < n_seqs; ++i)
-      if (mate[i] && re[i]) {
-        uint8_t &s = seen[read_index[i] / 2];
-        if (s != 3 && (s |= mate[i]) == 3) ++out->n_paired_links;
-      }
-  }
-  // the links that were seen, ascending by (in, out): edge a's slots are its target's out-edges in ascending order
-  uint64_t n_links = 0;
-  for (uint32_t s : slots) n_links += s != 0;
+  out->n_paired_links = mate ? thread_paired_links(nullptr, n_seqs, read_index, mate, re) : 0;
+  const uint64_t n_links = thread_links_count(slots.data(), pl.n_slots);
   out->n_links = n_links;
   if (n_links > out->link_cap || (n_links && (!out->link_in || !out->link_out || !out->link_counts)))
     return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)out->link_cap);
-  uint64_t at = 0;
-  for (uint32_t a = 0; a < E && at < n_links; ++a) {
-    if (pl.meta[a].z == TH_NONE) continue;
-    const uint64_t o0 = pl.out_first[pl.meta[a].y], o1 = pl.out_first[pl.meta[a].y + 1];
-    for (uint64_t j = o0; j < o1; ++j)
-      if (const uint32_t n = slots[pl.meta[a].z + (j - o0)]) {
-        out->link_in[at] = a, out->link_out[at] = pl.out_list[j], out->link_counts[at] = n;
-        ++at;
-      }
-  }
+  thread_links_decode(pl, slots.data(), n_links, out->link_in, out->link_out, out->link_counts);
   return SHK_OK;
 }
 
@@ -398,6 +415,223 @@ int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_node
   ReadBatch b;
   SHK_TRY(batch_from_host(c, bases, offsets, n_seqs, max_len, &b));
   return thread_core(c, pl, b, read_index, mate, out);
+}
+
+namespace {
+
+// A panel of graphs as k_thread_panel wants it: one ThreadPlan per gene, by thread_plan.
+struct ThreadPanelPlan {
+  std::vector<ThreadPlan> genes;
+  uint64_t e0 = 0, n_edges = 0, l0 = 0, n_listed = 0, n_slots = 0;  // the panel's first edge and list position; its totals
+};
+
+// Everything shk_thread_reads_panel refuses before the device is touched (the read offsets apart), and the genes' plans.
+int thread_panel_plan(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src, const uint32_t *edge_tgt,
+                      const uint64_t *edge_offsets, uint32_t n_genes, uint64_t n_seqs, const uint64_t *list_offsets, const uint64_t *list_reads,
+                      const uint64_t *read_index, const uint8_t *mate, const shk_thread_panel_out *out, ThreadPanelPlan *pp) {
+  if (n_genes > SHK_THREAD_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u is above the limit of %u", n_genes, SHK_THREAD_MAX_GENES);
+  if ((read_index == nullptr) != (mate == nullptr))
+    return fail(c, SHK_ERR_BAD_ARG, "read_index and mate go together: both (thread_reads_paired) or neither (thread_reads)");
+  for (uint64_t i = 0; mate && i < n_seqs; ++i)
+    if (mate[i] > 2) return fail(c, SHK_ERR_BAD_ARG, "mate[%llu] = %u: 0 unpaired, 1 R1, 2 R2", (unsigned long long)i, mate[i]);
+  if (!n_genes) return SHK_OK;
+  if (!node_offsets || !edge_offsets || !list_offsets) return fail(c, SHK_ERR_BAD_ARG, "shk_thread_reads_panel: an offsets array is missing");
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    if (node_offsets[g + 1] < node_offsets[g]) return fail(c, SHK_ERR_BAD_ARG, "gene %u: node_offsets must be non-decreasing", g);
+    if (edge_offsets[g + 1] < edge_offsets[g]) return fail(c, SHK_ERR_BAD_ARG, "gene %u: edge_offsets must be non-decreasing", g);
+    if (list_offsets[g + 1] < list_offsets[g]) return fail(c, SHK_ERR_BAD_ARG, "gene %u: list_offsets must be non-decreasing", g);
+  }
+  pp->e0 = edge_offsets[0], pp->n_edges = edge_offsets[n_genes] - pp->e0;
+  pp->l0 = list_offsets[0], pp->n_listed = list_offsets[n_genes] - pp->l0;
+  if (pp->n_edges >= (1ull << 32))
+    return fail(c, SHK_ERR_BAD_ARG, "a panel of %llu edges (gene 0 to gene %u): the total must be below 2^32", (unsigned long long)pp->n_edges,
+                n_genes - 1);
+  if (pp->n_listed && !list_reads) return fail(c, SHK_ERR_BAD_ARG, "shk_thread_reads_panel: list_reads is missing");
+  for (uint32_t g = 0; g < n_genes; ++g)
+    for (uint64_t p = list_offsets[g]; p < list_offsets[g + 1]; ++p)
+      if (list_reads[p] >= n_seqs)
+        return fail(c, SHK_ERR_BAD_ARG, "gene %u: list_reads[%llu] = %llu is outside the %llu reads", g, (unsigned long long)p,
+                    (unsigned long long)list_reads[p], (unsigned long long)n_seqs);
+  // the graphs, each by shk_thread_reads' own rules (read_index / mate are checked above, once: no reads go in)
+  const shk_thread_out one{out->support_total, out->support_unambiguous, nullptr, nullptr, nullptr, 0, 0, nullptr, 0};
+  pp->genes.resize(n_genes);
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const uint64_t v0 = node_offsets[g], e0 = edge_offsets[g];
+    const int rc = thread_plan(c, node_sub_kmers ? node_sub_kmers + v0 : nullptr, node_offsets[g + 1] - v0, edge_src ? edge_src + e0 : nullptr,
+                               edge_tgt ? edge_tgt + e0 : nullptr, edge_offsets[g + 1] - e0, 0, read_index, mate, &one, &pp->genes[g]);
+    if (rc != SHK_OK) {
+      const std::string why = c->err;
+      return fail(c, rc, "gene %u: %s", g, why.c_str());
+    }
+    pp->n_slots += pp->genes[g].n_slots;
+    if (pp->n_slots > (1ull << 31))
+      return fail(c, SHK_ERR_BAD_ARG, "gene %u: the panel's branch nodes have more than 2^31 (incoming, outgoing) edge pairs up to this gene", g);
+  }
+  return SHK_OK;
+}
+
+void thread_panel_out_zero(shk_thread_panel_out *out, const ThreadPanelPlan &pp, uint32_t n_genes) {
+  if (pp.n_edges) std::fill(out->support_total + pp.e0, out->support_total + pp.e0 + pp.n_edges, 0u);
+  if (pp.n_edges) std::fill(out->support_unambiguous + pp.e0, out->support_unambiguous + pp.e0 + pp.n_edges, 0u);
+  if (out->read_edges && pp.n_listed) std::fill(out->read_edges + pp.l0, out->read_edges + pp.l0 + pp.n_listed, 0u);
+  if (out->link_offsets) std::fill(out->link_offsets, out->link_offsets + n_genes + 1, 0ull);
+  if (out->n_paired_links) std::fill(out->n_paired_links, out->n_paired_links + n_genes, 0ull);
+  out->n_links = 0;
+}
+
+// The launch over an opened batch (its offsets checked) and what follows it.
+int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
+                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+  const uint32_t k = c->cfg.k;
+  const int lds_edges = env_int("SHK_THREAD_LDS_EDGES", THREAD_LDS_EDGES);
+  const uint64_t job_reads = (uint64_t)std::max(env_int("SHK_THREAD_PANEL_JOB", THREAD_PANEL_JOB), 1);
+  const int block_cap = env_int("SHK_THREAD_PANEL_BLOCKS", 0);
+  // the upload: every gene's meta, keys, start, items, last (16-byte aligned each), then the descriptors
+  std::vector<uint8_t> up;
+  std::vector<ThreadGene> desc(n_genes);
+  std::vector<ThreadJob> jobs;
+  auto put = [&up](const void *p, size_t bytes) {
+    const size_t at = up.size();
+    up.resize(at + ((bytes + 15) & ~(size_t)15), 0);
+    if (bytes) memcpy(up.data() + at, p, bytes);
+    return (uint64_t)at;
+  };
+  size_t lds = 0;
+  uint32_t n_lds = 0, n_global = 0;
+  uint64_t e_at = 0, slot_at = 0, n_walked = 0;
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const ThreadPlan &pl = pp.genes[g];
+    const uint32_t E = (uint32_t)pl.runs.items.size();
+    const uint64_t n_list = list_offsets[g + 1] - list_offsets[g];
+    ThreadGene &d = desc[g];
+    d = ThreadGene{};
+    d.cnt_base = (uint32_t)e_at, d.link_base = (uint32_t)slot_at;
+    e_at += E, slot_at += pl.n_slots;
+    if (!E) continue;  // no set, no jobs: its reads map to nothing
+    const uint32_t cap = (uint32_t)pl.runs.keys.size();
+    const size_t gene_lds = thread_lds_bytes(cap, E);
+    d.lds = (int64_t)E <= (int64_t)lds_edges && gene_lds <= THREAD_LDS_MAX;  // thread_core's rule, per gene
+    if (d.lds) lds = std::max(lds, gene_lds);
+    ++(d.lds ? n_lds : n_global);
+    d.meta = put(pl.meta.data(), (size_t)E * 16);
+    d.keys = put(pl.runs.keys.data(), (size_t)cap * 8), d.start = put(pl.runs.start.data(), (size_t)cap * 4);
+    d.items = put(pl.runs.items.data(), (size_t)E * 4), d.last = put(pl.runs.last.data(), pl.runs.last.size() * 4);
+    d.mask = cap - 1, d.n_edges = E;
+    for (uint64_t at = 0; at < n_list; at += job_reads)  // (gene, slice) order
+      jobs.push_back(ThreadJob{list_offsets[g] - pp.l0 + at, g, (uint32_t)std::min(job_reads, n_list - at)});
+    n_walked += n_list;
+  }
+  if (jobs.empty()) return SHK_OK;  // (the outputs are zero already)
+  if (jobs.size() >= (1ull << 32)) return fail(c, SHK_ERR_BAD_ARG, "%zu jobs: raise SHK_THREAD_PANEL_JOB", jobs.size());
+  const size_t o_desc_up = put(desc.data(), desc.size() * sizeof(ThreadGene));
+  // blocks: thread_core's rule — a wave per read up to the device's workgroups (one per CU when a set fills its LDS), the
+  // waves bounded by 256 MiB of scratch, whose stride the longest read of the BATCH sets — and never more than the jobs
+  const uint64_t max_win = b.max_len >= k ? b.max_len - k + 1 : 0;
+  const uint64_t stride = std::max<uint64_t>(THREAD_TILE, (max_win + THREAD_TILE - 1) / THREAD_TILE * THREAD_TILE);
+  const uint64_t wpb = THREAD_WG / 64;
+  uint64_t blocks = std::min<uint64_t>((n_walked + wpb - 1) / wpb, (uint64_t)c->n_cus * (n_lds ? 1 : 2));
+  blocks = std::min<uint64_t>(blocks, ((256ull << 20) / 8) / (stride * wpb));
+  if (block_cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)block_cap);
+  blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, jobs.size()));
+  Scratch m{c->misc};
+  const size_t o_up = m.take<uint8_t>(up.size()), o_jobs = m.take<ThreadJob>(jobs.size()), o_list = m.take<uint64_t>(pp.n_listed);
+  const size_t n_cnt = 2 * (size_t)pp.n_edges + pp.n_slots + pp.n_listed;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
+  const size_t o_cnt = m.take<uint32_t>(n_cnt), o_scr = m.take<uint2>(blocks * wpb * stride);
+  HIPC(c, m.ensure());
+  uint32_t *dtot = m.at<uint32_t>(o_cnt), *dun = dtot + pp.n_edges, *dlinks = dun + pp.n_edges, *dre = dlinks + pp.n_slots;
+  HIPC(c, hipMemcpyAsync(m.at<uint8_t>(o_up), up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(m.at<ThreadJob>(o_jobs), jobs.data(), jobs.size() * sizeof(ThreadJob), hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + pp.l0, pp.n_listed * 8, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
+  if (getenv("SHK_TRACE"))  // (read at each call, like the knobs: the tests look for this line)
+    fprintf(stderr, "[shk] thread_reads_panel: %u genes, %zu jobs, %llu blocks, %u genes in LDS, %u genes in global memory\n", n_genes, jobs.size(),
+            (unsigned long long)blocks, n_lds, n_global);
+  {
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    if (lds > (64u << 10) && !c->lds_attr_thread_panel) {  // > 64 KiB of dynamic LDS has to be asked for once
+      HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_thread_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)THREAD_LDS_MAX));
+      c->lds_attr_thread_panel = true;
+    }
+    hipLaunchKernelGGL(k_thread_panel, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, b.d_bases, b.d_offsets,
+                       (const uint64_t *)m.at<uint64_t>(o_list), (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up),
+                       (const ThreadJob *)m.at<ThreadJob>(o_jobs), (uint32_t)jobs.size(), (const uint8_t *)m.at<uint8_t>(o_up), (int)k,
+                       m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
+  }
+  HIPC(c, hipGetLastError());
+  std::vector<uint32_t> slots(pp.n_slots), re_own;
+  uint32_t *re = out->read_edges ? out->read_edges + pp.l0 : nullptr;
+  if (!re && mate) {
+    re_own.resize(pp.n_listed);
+    re = re_own.data();
+  }
+  HIPC(c, hipMemcpyAsync(out->support_total + pp.e0, dtot, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(out->support_unambiguous + pp.e0, dun, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
+  if (pp.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pp.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
+  if (re) HIPC(c, hipMemcpyAsync(re, dre, pp.n_listed * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the upload and the jobs alive until their copies ran)
+  // per gene, what thread_core does for its one graph
+  std::vector<uint64_t> link_off(n_genes + 1, 0);
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const uint64_t l_at = list_offsets[g] - pp.l0, n_list = list_offsets[g + 1] - list_offsets[g];
+    if (mate && out->n_paired_links) out->n_paired_links[g] = thread_paired_links(list_reads + list_offsets[g], n_list, read_index, mate, re + l_at);
+    link_off[g + 1] = link_off[g] + thread_links_count(slots.data() + desc[g].link_base, pp.genes[g].n_slots);
+  }
+  const uint64_t n_links = link_off[n_genes];
+  if (out->link_offsets) std::copy(link_off.begin(), link_off.end(), out->link_offsets);
+  out->n_links = n_links;
+  if (n_links > out->link_cap || (n_links && (!out->link_in || !out->link_out || !out->link_counts)))
+    return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)out->link_cap);
+  for (uint32_t g = 0; g < n_genes; ++g)
+    thread_links_decode(pp.genes[g], slots.data() + desc[g].link_base, link_off[g + 1] - link_off[g], out->link_in + link_off[g],
+                        out->link_out + link_off[g], out->link_counts + link_off[g]);
+  return SHK_OK;
+}
+
+}  // namespace
+
+int shk_thread_reads_panel_device(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src,
+                                  const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const void *d_bases, const void *d_offsets,
+                                  uint64_t n_seqs, uint64_t n_bases, const uint64_t *list_offsets, const uint64_t *list_reads,
+                                  const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+  if (c && c->group)
+    return on_any_device(c, [&](shk_ctx *d) {
+      return shk_thread_reads_panel_device(d, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, d_bases, d_offsets, n_seqs,
+                                           n_bases, list_offsets, list_reads, read_index, mate, out);
+    });
+  if (!c || !out || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
+  ThreadPanelPlan pp;
+  SHK_TRY(thread_panel_plan(c, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, n_seqs, list_offsets, list_reads, read_index,
+                            mate, out, &pp));
+  thread_panel_out_zero(out, pp, n_genes);
+  if (n_seqs == 0 || n_genes == 0) return SHK_OK;
+  ReadBatch b;
+  SHK_TRY(batch_from_device(c, d_bases, d_offsets, n_seqs, n_bases, "shk_thread_reads_panel", &b));  // (the offsets come back once)
+  return thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
+}
+
+int shk_thread_reads_panel(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src,
+                           const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const uint8_t *bases, const uint64_t *offsets,
+                           uint64_t n_seqs, const uint64_t *list_offsets, const uint64_t *list_reads, const uint64_t *read_index,
+                           const uint8_t *mate, shk_thread_panel_out *out) {
+  if (c && c->group)
+    return on_any_device(c, [&](shk_ctx *d) {
+      return shk_thread_reads_panel(d, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, bases, offsets, n_seqs, list_offsets,
+                                    list_reads, read_index, mate, out);
+    });
+  if (!c || !out || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
+  ThreadPanelPlan pp;
+  SHK_TRY(thread_panel_plan(c, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, n_seqs, list_offsets, list_reads, read_index,
+                            mate, out, &pp));
+  thread_panel_out_zero(out, pp, n_genes);
+  if (n_seqs == 0 || n_genes == 0) return SHK_OK;
+  uint64_t max_len = 0;
+  SHK_TRY(batch_check_offsets(c, offsets, n_seqs, offsets[n_seqs], "shk_thread_reads_panel", &max_len));
+  if (pp.n_edges == 0 || pp.n_listed == 0) return SHK_OK;
+  if (offsets[n_seqs] && !bases) return SHK_ERR_BAD_ARG;
+  // the device form's launch over the staged batch (its offsets are already here: no copy back)
+  ReadBatch b;
+  SHK_TRY(batch_from_host(c, bases, offsets, n_seqs, max_len, &b));
+  return thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
 }
 
 namespace {

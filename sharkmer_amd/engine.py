@@ -157,6 +157,12 @@ class _ThreadOut(C.Structure):
                 ("read_edges", C.c_void_p), ("n_paired_links", C.c_uint64)]
 
 
+class _ThreadPanelOut(C.Structure):
+    _fields_ = [("support_total", C.c_void_p), ("support_unambiguous", C.c_void_p), ("link_offsets", C.c_void_p),
+                ("link_in", C.c_void_p), ("link_out", C.c_void_p), ("link_counts", C.c_void_p), ("link_cap", C.c_uint64),
+                ("n_links", C.c_uint64), ("read_edges", C.c_void_p), ("n_paired_links", C.c_void_p)]
+
+
 @dataclass
 class ThreadingAnnotations:
     """What shk_thread_reads returns: ThreadingAnnotations of pcr/threading.rs:54-62 as arrays."""
@@ -197,7 +203,7 @@ ABI_SYMBOLS = [
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
     "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget",
-    "shk_thread_reads", "shk_thread_reads_device",
+    "shk_thread_reads", "shk_thread_reads_device", "shk_thread_reads_panel", "shk_thread_reads_panel_device",
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
 ]
 
@@ -325,6 +331,9 @@ def load_library():
     L.shk_pcr_node_budget.argtypes = [u64]
     L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
+    L.shk_thread_reads_panel.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(_ThreadPanelOut)]
+    L.shk_thread_reads_panel_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, u64, vp, vp, vp, vp,
+                                                C.POINTER(_ThreadPanelOut)]
     L.shk_filter_reads_panel.argtypes = [vp, vp, vp, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
     L.shk_filter_reads_panel_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
     L.shk_gather_reads_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
@@ -708,6 +717,78 @@ class KmerEngine:
             self._check(rcode)
             return ThreadingAnnotations(tot[:ne].copy(), una[:ne].copy(), np.stack([li[:m], lo[:m]], axis=1), lc[:m].copy(),
                                         re[:n].copy(), int(out.n_paired_links))
+
+    def thread_reads_panel(self, graphs, bases, offsets, lists, read_index=None, mate=None, device: bool = False) -> list:
+        """thread_reads of every gene of a panel in one call (shk_thread_reads_panel): graphs is a sequence of PcrGraph or
+        (node_sub_kmers, edge_src, edge_tgt) tuples, one per gene, edge endpoints local to the gene; lists is what
+        filter_reads_panel returns — per gene the indices of its reads in the batch (any order, repeats count).  The
+        answer is one ThreadingAnnotations per gene: what thread_reads gives for that graph over its listed reads in
+        list order.  read_index and mate (one entry per read of the BATCH) give the paired form.  device=True: bases
+        and offsets are torch tensors on this context's device (shk_thread_reads_panel_device)."""
+        gs = [(g.node_sub_kmers, g.edge_src, g.edge_tgt) if isinstance(g, PcrGraph) else g for g in graphs]
+        ng = len(gs)
+        if len(lists) != ng:
+            raise ValueError("one read list per graph")
+        subs = [np.ascontiguousarray(g[0], dtype=np.uint64).reshape(-1) for g in gs]
+        ess = [np.ascontiguousarray(g[1], dtype=np.uint32).reshape(-1) for g in gs]
+        ets = [np.ascontiguousarray(g[2], dtype=np.uint32).reshape(-1) for g in gs]
+        lss = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in lists]
+        if any(len(a) != len(b) for a, b in zip(ess, ets)):
+            raise ValueError("edge_src and edge_tgt differ in length")
+
+        def cat(parts, dtype):
+            off = np.zeros(ng + 1, dtype=np.uint64)
+            if parts:
+                off[1:] = np.cumsum([len(x) for x in parts])
+            return (np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)), off
+
+        sub, noff = cat(subs, np.uint64)
+        es, eoff = cat(ess, np.uint32)
+        et, _ = cat(ets, np.uint32)
+        lr, loff = cat(lss, np.uint64)
+        n = len(offsets) - 1
+        ne, nl = len(es), len(lr)
+        ri = None if read_index is None else np.ascontiguousarray(read_index, dtype=np.uint64)
+        mt = None if mate is None else np.ascontiguousarray(mate, dtype=np.uint8)
+        for a in (ri, mt):
+            if a is not None and len(a) != n:
+                raise ValueError("read_index and mate take one entry per read of the batch")
+        tot, una = np.zeros(max(ne, 1), dtype=np.uint32), np.zeros(max(ne, 1), dtype=np.uint32)
+        re = np.zeros(max(nl, 1), dtype=np.uint32)
+        koff = np.zeros(ng + 1, dtype=np.uint64)
+        npl = np.zeros(max(ng, 1), dtype=np.uint64)
+        if device:
+            args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
+            call = self._L.shk_thread_reads_panel_device
+        else:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            args = (bases.ctypes.data, offsets.ctypes.data, n)
+            call = self._L.shk_thread_reads_panel
+        # room for every link there can be, per gene as thread_reads sizes it (the retry is for panels beyond 2^22)
+        link_cap = 0
+        for s_, a, b in zip(subs, ess, ets):
+            ind, outd = (np.bincount(x, minlength=len(s_) + 1).astype(np.int64) for x in (b, a))
+            m = min(len(ind), len(outd))
+            link_cap += int((ind[:m] * outd[:m])[(ind[:m] > 1) | (outd[:m] > 1)].sum())
+        link_cap = max(1, min(link_cap, 1 << 22))
+        while True:
+            li, lo, lc = (np.zeros(link_cap, dtype=np.uint32) for _ in range(3))
+            out = _ThreadPanelOut(tot.ctypes.data, una.ctypes.data, koff.ctypes.data, li.ctypes.data, lo.ctypes.data, lc.ctypes.data,
+                                  link_cap, 0, re.ctypes.data, npl.ctypes.data)
+            rcode = call(self._h, sub.ctypes.data, noff.ctypes.data, es.ctypes.data, et.ctypes.data, eoff.ctypes.data, ng, *args,
+                         loff.ctypes.data, lr.ctypes.data, None if ri is None else ri.ctypes.data,
+                         None if mt is None else mt.ctypes.data, C.byref(out))
+            if rcode == -2 and int(out.n_links) > link_cap:  # the link arrays were too small: it says what it needs
+                link_cap = int(out.n_links)
+                continue
+            self._check(rcode)
+            anns = []
+            for g in range(ng):
+                e0, e1, k0, k1, l0, l1 = (int(x) for x in (eoff[g], eoff[g + 1], koff[g], koff[g + 1], loff[g], loff[g + 1]))
+                anns.append(ThreadingAnnotations(tot[e0:e1].copy(), una[e0:e1].copy(), np.stack([li[k0:k1], lo[k0:k1]], axis=1),
+                                                 lc[k0:k1].copy(), re[l0:l1].copy(), int(npl[g])))
+            return anns
 
     def filter_reads(self, bases: np.ndarray, offsets: np.ndarray, primer_kmers) -> np.ndarray:
         """PrimerReadFilter::matches per read (pcr/read_filter.rs:43-55) → bool array."""
