@@ -140,7 +140,7 @@ enum {
   SHK_K_PCOUNT = 12,   /* validate + count k-mers per partition (k_part_count) */
   SHK_K_PSCAN = 13,    /* the two small exclusive scans between count and scatter */
   SHK_K_HISTO_ROWS = 14, /* histograms + totals from the rows the (one) fresh page pass of a job left behind, instead of SHK_K_HISTO's scan */
-  SHK_K_EXTEND = 15    /* shk_neighborhood: seed, narrow and wide level launches */
+  SHK_K_EXTEND = 15    /* shk_neighborhood(_panel): seed, narrow and wide level launches */
 };
 
 /* ---- lifecycle ------------------------------------------------------------ */
@@ -393,10 +393,10 @@ int shk_thread_reads_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64
  * from one launch — no gather, no second copy of the reads.
  * GRAPHS: gene g's graph is nodes node_sub_kmers[node_offsets[g] .. node_offsets[g+1]) and edges
  *   [edge_offsets[g] .. edge_offsets[g+1]) of edge_src / edge_tgt, whose entries are node positions LOCAL to the gene
- *   (0 = the gene's first node): n_genes outputs of shk_pcr_extend, or the caller's pruned graphs, concatenate without
- *   renumbering.  Each graph follows the rules of shk_thread_reads: EDGE K-MER, candidates ascending by edge
- *   (build_edge_lookup, threading.rs:203-220), degrees as edge counts (threading.rs:329-330).  All three offset arrays
- *   have n_genes + 1 entries, non-decreasing.
+ *   (0 = the gene's first node): the output of shk_pcr_extend_panel as it is, n_genes outputs of shk_pcr_extend, or the
+ *   caller's pruned graphs, concatenated without renumbering.  Each graph follows the rules of shk_thread_reads: EDGE
+ *   K-MER, candidates ascending by edge (build_edge_lookup, threading.rs:203-220), degrees as edge counts
+ *   (threading.rs:329-330).  All three offset arrays have n_genes + 1 entries, non-decreasing.
  * LISTS: gene g's reads are list_reads[list_offsets[g] .. list_offsets[g+1]), indices into the batch — exactly the
  *   match_offsets / match_reads of shk_filter_reads_panel.  Any order is accepted, a read may be in any number of
  *   genes, and a repeat inside a list counts twice, as it would in a gathered batch.
@@ -539,6 +539,59 @@ int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_
                    uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes,
                    uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges,
                    uint32_t *found_path, uint32_t *threshold_used, uint32_t *steps_run);
+/* shk_neighborhood for many independent seed sets in ONE call: the table side of shk_pcr_extend_panel, where every gene
+ * of a panel asks for the neighbourhood of its own queue at its own threshold (extend_graph, src/pcr/graph.rs:377-525,
+ * once per gene of stats.rs:85-87).  Each job is carried through its levels by one workgroup of its own (a chain is as
+ * deep as the amplicon is long and about one entry wide), so a panel's chains run side by side in the time of the
+ * longest; a job whose level outgrows a workgroup is finished alone afterwards, as shk_neighborhood would.
+ * LAYOUT: job j's seeds are nodes/dirs[seed_offsets[j] .. seed_offsets[j+1]) (n_jobs + 1 offsets, non-decreasing); its
+ *   k-mers and counts are written from index caps[0] + … + caps[j−1] of kmers/counts, its fringe from index
+ *   fringe_caps[0] + … + fringe_caps[j−1] of fringe_nodes/fringe_dirs; n_out[j], n_fringe[j], levels_done[j].
+ * RESULT: for every j exactly what shk_neighborhood returns on the same table for (j's seeds, min_counts[j],
+ *   max_levels, caps[j], fringe_caps[j]) — the whole-levels rule, both lists sorted.  Jobs share nothing: each has its
+ *   own two sets, entry lists and counters.  A job without seeds returns zeros; n_jobs == 0 is SHK_OK.
+ * Errors, raised before the device is touched, with a text that names the job: every argument error of
+ *   shk_neighborhood, decreasing seed_offsets: SHK_ERR_BAD_ARG; also n_jobs > SHK_PCR_MAX_GENES.  Multi-device
+ *   contexts and owner shares: SHK_ERR_STATE.  Valid whenever shk_lookup is; the table is not touched.  The device
+ *   scratch per job is 8 bytes × (the powers of two above 8·cap + 2·seeds and above 2·cap, for the two sets) plus 24
+ *   bytes per unit of cap and 24 per unit of fringe_cap (lists and their packed copies): 140 to 210 bytes per unit of
+ *   cap when fringe_cap = cap, the upper end at a power-of-two cap.  It is the context's grow-only scratch and stays
+ *   with it; when it cannot be had the call fails with SHK_ERR_NOMEM and the context stays usable. */
+#define SHK_PCR_MAX_GENES 4096   /* = SHK_FILTER_MAX_GENES = SHK_THREAD_MAX_GENES */
+int shk_neighborhood_panel(shk_ctx *ctx, const uint64_t *nodes, const uint8_t *dirs,
+                           const uint64_t *seed_offsets /* n_jobs + 1 */, uint32_t n_jobs,
+                           const uint32_t *min_counts /* n_jobs */, uint32_t max_levels,
+                           const uint64_t *caps, const uint64_t *fringe_caps /* n_jobs each */,
+                           uint64_t *kmers, uint32_t *counts, uint64_t *n_out /* n_jobs */,
+                           uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe /* n_jobs */,
+                           uint32_t *levels_done /* n_jobs */);
+
+/* shk_pcr_extend for a whole sPCR panel in ONE call: do_pcr builds and extends one graph per gene (stats.rs:85-87,
+ * src/pcr/mod.rs:559-619, src/pcr/graph.rs:196-528); this call replays every gene's extension on the host in rounds and
+ * fetches what all of them need from the table with one shk_neighborhood_panel call per round.
+ * IN: primer_kmers / primer_counts / primer_offsets are the kmers / counts / offsets of shk_primer_kmers for primers
+ *   ordered forward, reverse per gene: direction 2g is gene g's forward set, 2g + 1 its reverse set (2·n_genes + 1
+ *   offsets, non-decreasing).  An empty set is no error, as in shk_pcr_extend.  params[g]: gene g's parameters.
+ * OUT: for every g exactly what shk_pcr_extend returns for gene g's two sets and params[g]: nodes in NodeIndex order at
+ *   node_offsets[g] .., edges in EdgeIndex order at edge_offsets[g] .. with endpoints LOCAL to the gene (0 = the gene's
+ *   first node), found_path[g], threshold_used[g], steps_run[g] — the graph arrays are the input form of
+ *   shk_thread_reads_panel and pass straight on.  node_cap / edge_cap too small: SHK_ERR_BAD_ARG with both offset
+ *   arrays complete (their last entries are the need).  n_genes == 0: zero offsets.
+ * Errors, SHK_ERR_BAD_ARG with a text that names the gene and the direction: a primer k-mer that is not a k-mer (before
+ *   the device is touched), decreasing primer_offsets; also n_genes > SHK_PCR_MAX_GENES, k < 2.  Multi-device contexts
+ *   and owner shares: SHK_ERR_STATE.  The table is not touched.
+ * Tuning, all read at each call, none changes the result: SHK_PCR_PANEL_THREADS (default 8, clamped to 1..16) host threads replay
+ *   the genes of a round (1: serial); SHK_PCR_PANEL_FETCH_CAP (k-mers, default 2^22; 140 to 210 bytes of device
+ *   scratch each, see shk_neighborhood_panel: up to 0.9 GB at the default, kept by the context) is shared evenly by the jobs of a launch — a job gets at least 4 × its seeds and at most what its node budget
+ *   leaves, and a round whose minimums exceed the budget is cut into several launches; SHK_PCR_FETCH_CAP, when set, is
+ *   the capacity of every job, as for shk_pcr_extend.  SHK_PCR_PANEL_TRACE (set to anything): one line on stderr per
+ *   call with its rounds and launches. */
+int shk_pcr_extend_panel(shk_ctx *ctx, const uint64_t *primer_kmers, const uint32_t *primer_counts,
+                         const uint64_t *primer_offsets /* 2·n_genes + 1 */, uint32_t n_genes,
+                         const shk_pcr_extend_params *params /* n_genes */,
+                         uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t *node_offsets /* n_genes + 1 */, uint64_t node_cap,
+                         uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t *edge_offsets /* n_genes + 1 */, uint64_t edge_cap,
+                         uint32_t *found_path, uint32_t *threshold_used, uint32_t *steps_run /* n_genes each */);
 /* compute_node_budget (graph.rs:40-52): 100 000 nodes up to 150 Mbp ingested, 500 000 from 750 Mbp, linear between. */
 uint64_t shk_pcr_node_budget(uint64_t n_bases_ingested);
 

@@ -1331,7 +1331,7 @@ constexpr int NB_WG = 1024;            // k_nb_narrow: one workgroup
 constexpr uint32_t NB_NARROW = 1024;   // … carries a level of up to this many entries
 constexpr uint32_t NB_RUN = 0, NB_COMPLETE = 1, NB_LIMIT = 2, NB_OVERFLOW = 3, NB_WIDE = 4;
 
-struct NbCtl {                 // host ↔ device state of one shk_neighborhood call
+struct NbCtl {                 // host ↔ device state of one shk_neighborhood call (of one job of a panel call)
   unsigned long long k_n;      // accepted k-mers appended so far
   unsigned long long next_n;   // entries of the level under construction (counted past fringe_cap)
   unsigned long long cur_n;    // entries of the current (unexpanded) level
@@ -1415,7 +1415,8 @@ __global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ct
 // the two entry lists and the fill counters in LDS, a workgroup barrier between levels, no host round trip.  It
 // stops with ctl->status = why: the neighbourhood is complete, max_levels reached, the next level did not fit the
 // caller's capacities (ctl then describes the level before it), or it is too wide for one workgroup (k_nb_wide's).
-__global__ void __launch_bounds__(NB_WG) k_nb_narrow(TableRef tb, NbRef nb, NbCtl *ctl) {
+// (The level loop itself: k_nb_narrow runs it for the one job of shk_neighborhood, k_nb_narrow_panel for its own job.)
+__device__ __forceinline__ void nb_narrow_levels(const TableRef &tb, const NbRef &nb, NbCtl *ctl) {
   __shared__ uint64_t s_list[2][NB_NARROW];
   __shared__ unsigned long long s_kn, s_kstart, s_nextn, s_curfull;  // s_curfull: the current level's size, s_curn capped
   __shared__ uint32_t s_full, s_status, s_curn, s_sel, s_levels;
@@ -1470,6 +1471,56 @@ __global__ void __launch_bounds__(NB_WG) k_nb_narrow(TableRef tb, NbRef nb, NbCt
     ctl->status = s_status;
     ctl->set_full = s_full;
   }
+}
+
+__global__ void __launch_bounds__(NB_WG) k_nb_narrow(TableRef tb, NbRef nb, NbCtl *ctl) { nb_narrow_levels(tb, nb, ctl); }
+
+// PANEL (shk_neighborhood_panel): many independent jobs side by side, each with its own NbRef (two sets, two entry
+// lists, k-mer list) and NbCtl in device arrays.  Nothing is shared between jobs and no workgroup waits for another:
+// jobs beyond what the card holds at once queue behind the others.
+//
+// Level 0 of every job in one launch: seed i (the jobs' sorted seed lists back to back) belongs to job seed_job[i],
+// whose seeds start at seed_start[job]; it goes into that job's first entry list and visited set.
+__global__ void __launch_bounds__(WG) k_nb_seed_panel(const NbRef *__restrict__ refs, NbCtl *ctls,
+                                                      const uint64_t *__restrict__ seeds,
+                                                      const uint32_t *__restrict__ seed_job,
+                                                      const uint64_t *__restrict__ seed_start, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = seed_job[i];
+  const uint64_t e = seeds[i];
+  refs[j].list[0][i - seed_start[j]] = e;  // (< the job's distinct seeds ≤ its fringe_cap: the host's check)
+  if (nb_set_insert(refs[j].vis, refs[j].vis_mask, e) < 0) atomicOr(&ctls[j].set_full, 1u);
+}
+
+// One workgroup per job, blockIdx.x the job: k_nb_narrow's level loop on the job's own NbRef / NbCtl.  A job that is
+// not there to be run — no seeds (NB_COMPLETE from the host) or a level 0 too wide for a workgroup (NB_WIDE) — is left
+// as it is; the host takes the wide ones on afterwards, one at a time.
+__global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel(TableRef tb, const NbRef *__restrict__ refs, NbCtl *ctls) {
+  NbCtl *ctl = &ctls[blockIdx.x];
+  if (ctl->status != NB_RUN || ctl->cur_n == 0 || ctl->cur_n > NB_NARROW) return;  // (the same for every thread: ctl is written at the end only)
+  nb_narrow_levels(tb, refs[blockIdx.x], ctl);  // (read in place: a private copy, indexed by list, would live in scratch)
+}
+
+// What a job hands back, packed: its k_n k-mers and counts from pack_k, its n_f fringe entries (the unexpanded level,
+// list[sel]) from pack_f — so that the host fetches three arrays for the whole panel whatever the capacities were.
+struct NbPack {
+  unsigned long long k_n, n_f, pack_k, pack_f;
+  uint32_t sel, pad;
+};
+__global__ void __launch_bounds__(WG) k_nb_pack_panel(const NbRef *__restrict__ refs, const NbPack *__restrict__ pk,
+                                                      uint64_t *__restrict__ out_k, uint32_t *__restrict__ out_c,
+                                                      uint64_t *__restrict__ out_f) {
+  const NbPack p = pk[blockIdx.x];
+  const NbRef &nb = refs[blockIdx.x];
+  const uint64_t *kmers = nb.kmers;
+  const uint32_t *counts = nb.counts;
+  for (unsigned long long i = threadIdx.x; i < p.k_n; i += WG) {
+    out_k[p.pack_k + i] = kmers[i];
+    out_c[p.pack_k + i] = counts[i];
+  }
+  const uint64_t *src = (p.sel & 1u) ? nb.list[1] : nb.list[0];
+  for (unsigned long long i = threadIdx.x; i < p.n_f; i += WG) out_f[p.pack_f + i] = src[i];
 }
 
 // ==========================================================================================

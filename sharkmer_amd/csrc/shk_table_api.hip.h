@@ -67,6 +67,105 @@ int compact_owners_launch(shk_ctx *c, uint32_t n_owners, const uint64_t *h_off, 
   return SHK_OK;
 }
 
+// The level loop of shk_neighborhood, and of a job of shk_neighborhood_panel that outgrew its workgroup: from the state
+// h (which dctl holds too) until the job stops — complete, at max_levels, or before a level that does not fit.
+int nb_run_levels(shk_ctx *c, const NbRef &nb, NbCtl *dctl, NbCtl &h) {
+  // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
+  while (h.status == NB_RUN || h.status == NB_WIDE) {
+    if (h.cur_n == 0) {
+      h.status = NB_COMPLETE;
+      break;
+    }
+    if (nb.max_levels && h.levels_done >= nb.max_levels) {
+      h.status = NB_LIMIT;
+      break;
+    }
+    if (h.cur_n <= NB_NARROW) {
+      {
+        ScopedTimer t(c, SHK_K_EXTEND);
+        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
+      }
+      HIPC(c, hipGetLastError());
+      HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+      HIPC(c, hipStreamSynchronize(c->stream));
+      continue;
+    }
+    const unsigned long long k_start = h.k_n;
+    {
+      ScopedTimer t(c, SHK_K_EXTEND);
+      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
+                         dctl, h.cur_sel, (uint64_t)h.cur_n);
+    }
+    HIPC(c, hipGetLastError());
+    NbCtl r{};
+    HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (r.set_full || r.k_n > nb.cap || r.next_n > nb.fringe_cap) {  // the level did not fit: the k-mer list back to its start
+      h.k_n = k_start;
+      h.status = NB_OVERFLOW;
+      break;
+    }
+    h.k_n = r.k_n;
+    h.cur_n = r.next_n;
+    h.cur_sel ^= 1u;
+    h.levels_done += 1;
+    h.next_n = 0;
+    h.status = NB_RUN;
+    HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));  // (h is a pageable source: the copy has read it)
+  }
+  return SHK_OK;
+}
+
+// Sizes of a job's two sets.  An accepted k-mer has two orientations and an orientation one successor per dir: through
+// a level that fits, the visited set never holds more than the seeds and 4·cap entries, the k-mer set cap.  Both at
+// most half full then; a set that fills up (probes are bounded) belongs to a level that does not fit and is dropped.
+uint64_t nb_pow2_above(uint64_t n) {
+  uint64_t s = 16;
+  while (s < n) s <<= 1;
+  return s;
+}
+uint64_t nb_vis_slots(uint64_t n_seeds, uint64_t cap) { return nb_pow2_above(2 * (n_seeds + 4 * cap) + 2); }
+uint64_t nb_kset_slots(uint64_t cap) { return nb_pow2_above(2 * cap + 2); }
+
+// A call's (or a job's) seeds as level 0: the distinct (node, dir) pairs as entries node << 1 | (0 forward, 1 reverse),
+// ascending.  `who`: what an error text starts with ("" or "job 7: ").
+int nb_level0(shk_ctx *c, const char *who, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds, uint32_t k,
+              uint64_t fringe_cap, std::vector<uint64_t> *seeds) {
+  const uint64_t node_mask = (1ull << (2 * (k - 1))) - 1ull;
+  seeds->clear();
+  seeds->reserve(n_seeds);
+  for (uint64_t i = 0; i < n_seeds; ++i) {
+    if (dirs[i] == 0 || dirs[i] > 3) return fail(c, SHK_ERR_BAD_ARG, "%sseed %llu: dir %u is not 1 (forward), 2 (reverse) or 3 (both)", who, (unsigned long long)i, dirs[i]);
+    if (nodes[i] > node_mask) return fail(c, SHK_ERR_BAD_ARG, "%sseed %llu: node 0x%llx is not a %u-mer", who, (unsigned long long)i, (unsigned long long)nodes[i], k - 1);
+    if (dirs[i] & 1) seeds->push_back(nodes[i] << 1);
+    if (dirs[i] & 2) seeds->push_back(nodes[i] << 1 | 1ull);
+  }
+  std::sort(seeds->begin(), seeds->end());
+  seeds->erase(std::unique(seeds->begin(), seeds->end()), seeds->end());
+  if (seeds->size() > fringe_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "%s%llu distinct seeds do not fit fringe_cap %llu", who, (unsigned long long)seeds->size(), (unsigned long long)fringe_cap);
+  return SHK_OK;
+}
+
+// The arrival order of the appends is not part of the result: (hk, hc) ascending by k-mer into (kmers, counts), the
+// entries hf ascending into (fringe_nodes, fringe_dirs).
+void nb_sorted_out(const uint64_t *hk, const uint32_t *hc, uint64_t nk, uint64_t *hf, uint64_t nf, uint64_t *kmers,
+                   uint32_t *counts, uint64_t *fringe_nodes, uint8_t *fringe_dirs) {
+  std::vector<uint32_t> order(nk);
+  for (uint64_t i = 0; i < nk; ++i) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
+  for (uint64_t i = 0; i < nk; ++i) {
+    kmers[i] = hk[order[i]];
+    counts[i] = hc[order[i]];
+  }
+  std::sort(hf, hf + nf);
+  for (uint64_t i = 0; i < nf; ++i) {
+    fringe_nodes[i] = hf[i] >> 1;
+    fringe_dirs[i] = (uint8_t)(1u << (hf[i] & 1ull));
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -138,34 +237,14 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
   if ((cap && (!kmers || !counts)) || (fringe_cap && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
   if (cap > (1ull << 32) || fringe_cap > (1ull << 32))
     return fail(c, SHK_ERR_BAD_ARG, "cap %llu / fringe_cap %llu above 2^32", (unsigned long long)cap, (unsigned long long)fringe_cap);
-  const uint64_t node_mask = (1ull << (2 * (k - 1))) - 1ull;
-  // level 0: the distinct (node, dir) pairs, as entries node << 1 | (0 forward, 1 reverse)
-  std::vector<uint64_t> seeds;
-  seeds.reserve(n_seeds);
-  for (uint64_t i = 0; i < n_seeds; ++i) {
-    if (dirs[i] == 0 || dirs[i] > 3) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: dir %u is not 1 (forward), 2 (reverse) or 3 (both)", (unsigned long long)i, dirs[i]);
-    if (nodes[i] > node_mask) return fail(c, SHK_ERR_BAD_ARG, "seed %llu: node 0x%llx is not a %u-mer", (unsigned long long)i, (unsigned long long)nodes[i], k - 1);
-    if (dirs[i] & 1) seeds.push_back(nodes[i] << 1);
-    if (dirs[i] & 2) seeds.push_back(nodes[i] << 1 | 1ull);
-  }
-  std::sort(seeds.begin(), seeds.end());
-  seeds.erase(std::unique(seeds.begin(), seeds.end()), seeds.end());
-  if (seeds.size() > fringe_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "%llu distinct seeds do not fit fringe_cap %llu", (unsigned long long)seeds.size(), (unsigned long long)fringe_cap);
+  std::vector<uint64_t> seeds;  // level 0
+  SHK_TRY(nb_level0(c, "", nodes, dirs, n_seeds, k, fringe_cap, &seeds));
   *n_out = 0;
   *n_fringe = 0;
   *levels_done = 0;
   if (seeds.empty()) return SHK_OK;
   SHK_TRY(table_read_begin(c));
-  // An accepted k-mer has two orientations and an orientation one successor per dir: through a level that fits, the
-  // visited set never holds more than the seeds and 4·cap entries, the k-mer set cap.  Both at most half full then; a
-  // set that fills up (probes are bounded) belongs to a level that does not fit and is dropped.
-  auto pow2_above = [](uint64_t n) {
-    uint64_t s = 16;
-    while (s < n) s <<= 1;
-    return s;
-  };
-  const uint64_t vis_slots = pow2_above(2 * (seeds.size() + 4 * cap) + 2), kset_slots = pow2_above(2 * cap + 2);
+  const uint64_t vis_slots = nb_vis_slots(seeds.size(), cap), kset_slots = nb_kset_slots(cap);
   const uint64_t fc = std::max<uint64_t>(fringe_cap, 1), kc = std::max<uint64_t>(cap, 1);
   Scratch m{c->misc};
   const size_t o_ctl = m.take<NbCtl>(1), o_vis = m.take<uint64_t>(vis_slots), o_kset = m.take<uint64_t>(kset_slots);  // (vis, kset: adjacent)
@@ -196,51 +275,7 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
     hipLaunchKernelGGL(k_nb_seed, dim3((uint32_t)((seeds.size() + WG - 1) / WG)), dim3(WG), 0, c->stream, nb,
                        (uint64_t)seeds.size(), dctl);
   }
-  // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
-  while (h.status == NB_RUN || h.status == NB_WIDE) {
-    if (h.cur_n == 0) {
-      h.status = NB_COMPLETE;
-      break;
-    }
-    if (max_levels && h.levels_done >= max_levels) {
-      h.status = NB_LIMIT;
-      break;
-    }
-    if (h.cur_n <= NB_NARROW) {
-      {
-        ScopedTimer t(c, SHK_K_EXTEND);
-        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
-      }
-      HIPC(c, hipGetLastError());
-      HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-      HIPC(c, hipStreamSynchronize(c->stream));
-      continue;
-    }
-    const unsigned long long k_start = h.k_n;
-    {
-      ScopedTimer t(c, SHK_K_EXTEND);
-      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
-                         dctl, h.cur_sel, (uint64_t)h.cur_n);
-    }
-    HIPC(c, hipGetLastError());
-    NbCtl r{};
-    HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (r.set_full || r.k_n > cap || r.next_n > fringe_cap) {  // the level did not fit: the k-mer list back to its start
-      h.k_n = k_start;
-      h.status = NB_OVERFLOW;
-      break;
-    }
-    h.k_n = r.k_n;
-    h.cur_n = r.next_n;
-    h.cur_sel ^= 1u;
-    h.levels_done += 1;
-    h.next_n = 0;
-    h.status = NB_RUN;
-    HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));  // (h is a pageable source: the copy has read it)
-  }
-  // the arrival order of the appends is not part of the result: sorted
+  SHK_TRY(nb_run_levels(c, nb, dctl, h));
   const uint64_t nk = h.k_n, nf = h.status == NB_COMPLETE ? 0 : h.cur_n;
   std::vector<uint64_t> hk(nk), hf(nf);
   std::vector<uint32_t> hc(nk);
@@ -249,18 +284,7 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
     HIPC(c, hipMemcpy(hc.data(), nb.counts, nk * 4, hipMemcpyDeviceToHost));
   }
   if (nf) HIPC(c, hipMemcpy(hf.data(), nb.list[h.cur_sel], nf * 8, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> order(nk);
-  for (uint64_t i = 0; i < nk; ++i) order[i] = (uint32_t)i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; });
-  for (uint64_t i = 0; i < nk; ++i) {
-    kmers[i] = hk[order[i]];
-    counts[i] = hc[order[i]];
-  }
-  std::sort(hf.begin(), hf.end());
-  for (uint64_t i = 0; i < nf; ++i) {
-    fringe_nodes[i] = hf[i] >> 1;
-    fringe_dirs[i] = (uint8_t)(1u << (hf[i] & 1ull));
-  }
+  nb_sorted_out(hk.data(), hc.data(), nk, hf.data(), nf, kmers, counts, fringe_nodes, fringe_dirs);
   *n_out = nk;
   *n_fringe = nf;
   *levels_done = h.levels_done;
@@ -302,6 +326,209 @@ int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_co
   std::copy(g.esrc.begin(), g.esrc.end(), edge_src);
   std::copy(g.etgt.begin(), g.etgt.end(), edge_tgt);
   std::copy(g.ecount.begin(), g.ecount.end(), edge_counts);
+  return SHK_OK;
+}
+
+int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
+                           const uint32_t *min_counts, uint32_t max_levels, const uint64_t *caps, const uint64_t *fringe_caps,
+                           uint64_t *kmers, uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs,
+                           uint64_t *n_fringe, uint32_t *levels_done) {
+  using ull = unsigned long long;
+  if (!c) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_neighborhood_panel needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  if (n_jobs > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_jobs %u above SHK_PCR_MAX_GENES (%u)", n_jobs, (unsigned)SHK_PCR_MAX_GENES);
+  if (n_jobs == 0) return SHK_OK;
+  if (!seed_offsets || !min_counts || !caps || !fringe_caps || !n_out || !n_fringe || !levels_done) return SHK_ERR_BAD_ARG;
+  // every job's arguments before the device is touched
+  std::vector<std::vector<uint64_t>> seeds(n_jobs);  // level 0 per job
+  std::vector<uint64_t> out_at(n_jobs + 1, 0), fr_at(n_jobs + 1, 0);  // where a job's outputs start in the caller's arrays
+  uint64_t n_all_seeds = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    char who[32];
+    snprintf(who, sizeof who, "job %u: ", j);
+    if (seed_offsets[j + 1] < seed_offsets[j])
+      return fail(c, SHK_ERR_BAD_ARG, "%sseed_offsets decrease (%llu after %llu)", who, (ull)seed_offsets[j + 1], (ull)seed_offsets[j]);
+    if (caps[j] > (1ull << 32) || fringe_caps[j] > (1ull << 32))
+      return fail(c, SHK_ERR_BAD_ARG, "%scap %llu / fringe_cap %llu above 2^32", who, (ull)caps[j], (ull)fringe_caps[j]);
+    const uint64_t a = seed_offsets[j], n = seed_offsets[j + 1] - a;
+    if (n && (!nodes || !dirs)) return SHK_ERR_BAD_ARG;
+    SHK_TRY(nb_level0(c, who, nodes ? nodes + a : nullptr, dirs ? dirs + a : nullptr, n, k, fringe_caps[j], &seeds[j]));
+    out_at[j + 1] = out_at[j] + caps[j];
+    fr_at[j + 1] = fr_at[j] + fringe_caps[j];
+    n_all_seeds += seeds[j].size();
+  }
+  if ((out_at[n_jobs] && (!kmers || !counts)) || (fr_at[n_jobs] && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
+  std::fill(n_out, n_out + n_jobs, 0ull);
+  std::fill(n_fringe, n_fringe + n_jobs, 0ull);
+  std::fill(levels_done, levels_done + n_jobs, 0u);
+  if (n_all_seeds == 0) return SHK_OK;
+  SHK_TRY(table_read_begin(c));
+  // Device layout: every job's two sets in one region (one clear), then what is uploaded in one copy (NbRef, NbCtl,
+  // seed starts, seeds, their jobs), then the lists.  A job without seeds gets no room: it is not run.
+  std::vector<uint64_t> capj(n_jobs), fcj(n_jobs), set_at(n_jobs + 1, 0), l_at(n_jobs + 1, 0), k_at(n_jobs + 1, 0);
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    const bool live = !seeds[j].empty();
+    capj[j] = live ? caps[j] : 0;
+    fcj[j] = live ? fringe_caps[j] : 0;
+    set_at[j + 1] = set_at[j] + (live ? nb_vis_slots(seeds[j].size(), capj[j]) + nb_kset_slots(capj[j]) : 0);
+    l_at[j + 1] = l_at[j] + std::max<uint64_t>(fcj[j], 1);
+    k_at[j + 1] = k_at[j] + std::max<uint64_t>(capj[j], 1);
+  }
+  Scratch m{c->misc};
+  const size_t o_sets = m.take<uint64_t>(set_at[n_jobs]);
+  const size_t o_refs = m.take<NbRef>(n_jobs), o_ctl = m.take<NbCtl>(n_jobs), o_start = m.take<uint64_t>(n_jobs + 1);
+  const size_t o_seeds = m.take<uint64_t>(n_all_seeds), o_sjob = m.take<uint32_t>(n_all_seeds);
+  const size_t o_pack = m.take<NbPack>(n_jobs);  // (ends the uploaded block)
+  const size_t o_l0 = m.take<uint64_t>(l_at[n_jobs]), o_l1 = m.take<uint64_t>(l_at[n_jobs]);
+  const size_t o_km = m.take<uint64_t>(k_at[n_jobs]), o_ct = m.take<uint32_t>(k_at[n_jobs]);
+  const size_t o_pk = m.take<uint64_t>(k_at[n_jobs]), o_pc = m.take<uint32_t>(k_at[n_jobs]), o_pf = m.take<uint64_t>(l_at[n_jobs]);
+  HIPC(c, m.ensure());
+  std::vector<uint8_t> up(o_pack - o_refs, 0);  // the uploaded block as the device holds it
+  NbRef *href = (NbRef *)up.data();
+  NbCtl *hctl = (NbCtl *)(up.data() + (o_ctl - o_refs));
+  uint64_t *hstart = (uint64_t *)(up.data() + (o_start - o_refs)), *hseeds = (uint64_t *)(up.data() + (o_seeds - o_refs));
+  uint32_t *hsjob = (uint32_t *)(up.data() + (o_sjob - o_refs));
+  uint64_t at = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    NbRef &nb = href[j];
+    const uint64_t vis_slots = seeds[j].empty() ? 0 : nb_vis_slots(seeds[j].size(), capj[j]);
+    nb.vis = m.at<uint64_t>(o_sets) + set_at[j];
+    nb.kset = nb.vis + vis_slots;
+    nb.vis_mask = vis_slots ? vis_slots - 1 : 0;
+    nb.kset_mask = seeds[j].empty() ? 0 : nb_kset_slots(capj[j]) - 1;
+    nb.list[0] = m.at<uint64_t>(o_l0) + l_at[j];
+    nb.list[1] = m.at<uint64_t>(o_l1) + l_at[j];
+    nb.kmers = m.at<uint64_t>(o_km) + k_at[j];
+    nb.counts = m.at<uint32_t>(o_ct) + k_at[j];
+    nb.cap = capj[j];
+    nb.fringe_cap = fcj[j];
+    nb.min_count = std::max(min_counts[j], 1u);
+    nb.max_levels = max_levels;
+    nb.k = (int)k;
+    hctl[j].cur_n = seeds[j].size();
+    hctl[j].status = seeds[j].empty() ? NB_COMPLETE : seeds[j].size() > NB_NARROW ? NB_WIDE : NB_RUN;
+    hstart[j] = at;
+    for (const uint64_t e : seeds[j]) {
+      hseeds[at] = e;
+      hsjob[at++] = j;
+    }
+  }
+  hstart[n_jobs] = at;
+  NbRef *drefs = m.at<NbRef>(o_refs);
+  NbCtl *dctl = m.at<NbCtl>(o_ctl);
+  HIPC(c, hipMemsetAsync(m.at<uint64_t>(o_sets), 0xFF, set_at[n_jobs] * 8, c->stream));  // every set ← EMPTY
+  HIPC(c, hipMemcpyAsync(drefs, up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_seed_panel, dim3((uint32_t)((n_all_seeds + WG - 1) / WG)), dim3(WG), 0, c->stream,
+                       (const NbRef *)drefs, dctl, (const uint64_t *)m.at<uint64_t>(o_seeds),
+                       (const uint32_t *)m.at<uint32_t>(o_sjob), (const uint64_t *)m.at<uint64_t>(o_start), n_all_seeds);
+  }
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_narrow_panel, dim3(n_jobs), dim3(NB_WG), 0, c->stream, c->tb, (const NbRef *)drefs, dctl);
+  }
+  HIPC(c, hipGetLastError());
+  std::vector<NbCtl> h(n_jobs);
+  HIPC(c, hipMemcpyAsync(h.data(), dctl, (size_t)n_jobs * sizeof(NbCtl), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also: `up` has been read)
+  // the exception: a job with a level wider than a workgroup goes on alone, as in shk_neighborhood
+  for (uint32_t j = 0; j < n_jobs; ++j)
+    if (h[j].status == NB_WIDE) SHK_TRY(nb_run_levels(c, href[j], dctl + j, h[j]));
+  std::vector<NbPack> pk(n_jobs);
+  uint64_t tot_k = 0, tot_f = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    pk[j] = NbPack{h[j].k_n, h[j].status == NB_COMPLETE ? 0ull : h[j].cur_n, tot_k, tot_f, h[j].cur_sel, 0};
+    if (pk[j].k_n > capj[j] || pk[j].n_f > std::max<uint64_t>(fcj[j], seeds[j].size()))
+      return fail(c, SHK_ERR_INVARIANT, "job %u: %llu k-mers / %llu fringe entries beyond its capacities", j, pk[j].k_n, pk[j].n_f);
+    tot_k += pk[j].k_n;
+    tot_f += pk[j].n_f;
+  }
+  std::vector<uint64_t> hk(tot_k), hf(tot_f);
+  std::vector<uint32_t> hc(tot_k);
+  if (tot_k || tot_f) {
+    HIPC(c, hipMemcpyAsync(m.at<NbPack>(o_pack), pk.data(), (size_t)n_jobs * sizeof(NbPack), hipMemcpyHostToDevice, c->stream));
+    {
+      ScopedTimer t(c, SHK_K_EXTEND);
+      hipLaunchKernelGGL(k_nb_pack_panel, dim3(n_jobs), dim3(WG), 0, c->stream, (const NbRef *)drefs,
+                         (const NbPack *)m.at<NbPack>(o_pack), m.at<uint64_t>(o_pk), m.at<uint32_t>(o_pc), m.at<uint64_t>(o_pf));
+    }
+    HIPC(c, hipGetLastError());
+    if (tot_k) {
+      HIPC(c, hipMemcpyAsync(hk.data(), m.at<uint64_t>(o_pk), tot_k * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPC(c, hipMemcpyAsync(hc.data(), m.at<uint32_t>(o_pc), tot_k * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (tot_f) HIPC(c, hipMemcpyAsync(hf.data(), m.at<uint64_t>(o_pf), tot_f * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+  }
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    const NbPack &p = pk[j];
+    nb_sorted_out(hk.data() + p.pack_k, hc.data() + p.pack_k, p.k_n, hf.data() + p.pack_f, p.n_f, kmers + out_at[j],
+                  counts + out_at[j], fringe_nodes + fr_at[j], fringe_dirs + fr_at[j]);
+    n_out[j] = p.k_n;
+    n_fringe[j] = p.n_f;
+    levels_done[j] = h[j].levels_done;
+  }
+  return SHK_OK;
+}
+
+int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
+                         uint32_t n_genes, const shk_pcr_extend_params *params, uint64_t *node_sub_kmers, uint8_t *node_flags,
+                         uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts,
+                         uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path, uint32_t *threshold_used,
+                         uint32_t *steps_run) {
+  using ull = unsigned long long;
+  if (!c || !node_offsets || !edge_offsets) return SHK_ERR_BAD_ARG;
+  if (c->group)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)");
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  const uint32_t k = c->cfg.k;
+  if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
+  if (n_genes > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", n_genes, (unsigned)SHK_PCR_MAX_GENES);
+  node_offsets[0] = edge_offsets[0] = 0;
+  if (n_genes == 0) return SHK_OK;
+  if (!primer_offsets || !params || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
+  const uint64_t kmask = ~0ull >> (64 - 2 * k);
+  static const char *const dir_name[2] = {"forward", "reverse"};
+  for (uint32_t d = 0; d < 2 * n_genes; ++d) {
+    if (primer_offsets[d + 1] < primer_offsets[d])
+      return fail(c, SHK_ERR_BAD_ARG, "gene %u, %s set: primer_offsets decrease (%llu after %llu)", d / 2, dir_name[d & 1],
+                  (ull)primer_offsets[d + 1], (ull)primer_offsets[d]);
+    if (primer_offsets[d + 1] > primer_offsets[d] && (!primer_kmers || !primer_counts)) return SHK_ERR_BAD_ARG;
+    for (uint64_t i = primer_offsets[d]; i < primer_offsets[d + 1]; ++i)
+      if (primer_kmers[i] > kmask)
+        return fail(c, SHK_ERR_BAD_ARG, "gene %u: %s primer k-mer %llu is not a %u-mer", d / 2, dir_name[d & 1],
+                    (ull)(i - primer_offsets[d]), k);
+  }
+  std::vector<PcrGraph> gs;
+  std::string msg;
+  const int rc = pcr_extend_panel_run(c, k, primer_kmers, primer_counts, primer_offsets, n_genes, params, &gs, threshold_used,
+                                      steps_run, &msg);
+  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood_panel's own text stands)
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    node_offsets[g + 1] = node_offsets[g] + gs[g].sub_kmer.size();
+    edge_offsets[g + 1] = edge_offsets[g] + gs[g].esrc.size();
+    found_path[g] = gs[g].found_path ? 1u : 0u;
+  }
+  const uint64_t nn = node_offsets[n_genes], ne = edge_offsets[n_genes];
+  if (nn > node_cap || ne > edge_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "panel of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu", (ull)nn,
+                (ull)ne, (ull)node_cap, (ull)edge_cap);
+  if ((nn && (!node_sub_kmers || !node_flags)) || (ne && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const PcrGraph &gr = gs[g];
+    std::copy(gr.sub_kmer.begin(), gr.sub_kmer.end(), node_sub_kmers + node_offsets[g]);
+    std::copy(gr.flags.begin(), gr.flags.end(), node_flags + node_offsets[g]);
+    std::copy(gr.esrc.begin(), gr.esrc.end(), edge_src + edge_offsets[g]);
+    std::copy(gr.etgt.begin(), gr.etgt.end(), edge_tgt + edge_offsets[g]);
+    std::copy(gr.ecount.begin(), gr.ecount.end(), edge_counts + edge_offsets[g]);
+  }
   return SHK_OK;
 }
 

@@ -202,7 +202,7 @@ ABI_SYMBOLS = [
     "shk_stream", "shk_compact_owners_packed", "shk_compact_owners_fixed", "shk_merge_pieces_max", "shk_merge_pieces", "shk_set_owner_share", "shk_finalize_begin", "shk_finalize_end",
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
-    "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget",
+    "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget", "shk_neighborhood_panel", "shk_pcr_extend_panel",
     "shk_thread_reads", "shk_thread_reads_device", "shk_thread_reads_panel", "shk_thread_reads_panel_device",
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
 ]
@@ -329,6 +329,8 @@ def load_library():
     L.shk_pcr_extend.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(_PcrExtendParams), vp, vp, u64, C.POINTER(u64),
                                  vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.shk_pcr_node_budget.argtypes = [u64]
+    L.shk_neighborhood_panel.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.shk_pcr_extend_panel.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
     L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_panel.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(_ThreadPanelOut)]
@@ -670,6 +672,109 @@ class KmerEngine:
             self._check(rcode)
             return PcrGraph(sub[:n].copy(), flags[:n].copy(), es[:e].copy(), et[:e].copy(), ec[:e].copy(),
                             bool(found.value), int(thr.value), int(steps.value))
+
+    def neighborhood_panel(self, jobs, max_levels: int = 0) -> list:
+        """shk_neighborhood_panel: the neighbourhoods of many independent seed sets in one call.  jobs: a sequence of
+        (nodes, dirs, min_count) or (nodes, dirs, min_count, cap, fringe_cap) — the arguments of `neighborhood`, the
+        capacities 2^16 when left out; max_levels holds for all.  → per job the tuple `neighborhood` returns."""
+        jobs = [tuple(j) for j in jobs]
+        nj = len(jobs)
+        ns = [np.ascontiguousarray(np.atleast_1d(j[0]), dtype=np.uint64).reshape(-1) for j in jobs]
+        ds = [np.ascontiguousarray(np.atleast_1d(j[1]), dtype=np.uint8).reshape(-1) for j in jobs]
+        if any(len(a) != len(b) for a, b in zip(ns, ds)):
+            raise ValueError("nodes and dirs differ in length")
+        nodes = np.concatenate(ns) if ns else np.zeros(0, dtype=np.uint64)
+        dirs = np.concatenate(ds) if ds else np.zeros(0, dtype=np.uint8)
+        soff = np.zeros(nj + 1, dtype=np.uint64)
+        if nj:
+            soff[1:] = np.cumsum([len(a) for a in ns])
+        mcs = np.array([j[2] for j in jobs], dtype=np.uint32)
+        caps = np.array([j[3] if len(j) > 3 else 1 << 16 for j in jobs], dtype=np.uint64)
+        fcaps = np.array([j[4] if len(j) > 4 else 1 << 16 for j in jobs], dtype=np.uint64)
+        ka = np.concatenate([[0], np.cumsum(caps, dtype=np.uint64)]).astype(np.uint64)
+        fa = np.concatenate([[0], np.cumsum(fcaps, dtype=np.uint64)]).astype(np.uint64)
+        kmers = np.zeros(max(int(ka[-1]), 1), dtype=np.uint64)
+        counts = np.zeros(max(int(ka[-1]), 1), dtype=np.uint32)
+        fn = np.zeros(max(int(fa[-1]), 1), dtype=np.uint64)
+        fd = np.zeros(max(int(fa[-1]), 1), dtype=np.uint8)
+        n_out, n_fr = np.zeros(max(nj, 1), dtype=np.uint64), np.zeros(max(nj, 1), dtype=np.uint64)
+        lv = np.zeros(max(nj, 1), dtype=np.uint32)
+        self._check(self._L.shk_neighborhood_panel(self._h, nodes.ctypes.data, dirs.ctypes.data, soff.ctypes.data, nj,
+                                                   mcs.ctypes.data, max_levels, caps.ctypes.data, fcaps.ctypes.data,
+                                                   kmers.ctypes.data, counts.ctypes.data, n_out.ctypes.data, fn.ctypes.data,
+                                                   fd.ctypes.data, n_fr.ctypes.data, lv.ctypes.data))
+        out = []
+        for j in range(nj):
+            a, b, n, f = int(ka[j]), int(fa[j]), int(n_out[j]), int(n_fr[j])
+            out.append((kmers[a:a + n].copy(), counts[a:a + n].copy(), fn[b:b + f].copy(), fd[b:b + f].copy(), int(lv[j])))
+        return out
+
+    def pcr_extend_panel(self, primer_results, params=None) -> list:
+        """shk_pcr_extend for every gene of a panel in one call (shk_pcr_extend_panel) → one PcrGraph per gene, a list
+        thread_reads_panel takes as it is.  primer_results: what primer_kmers returns for primers ordered forward,
+        reverse per gene (entry 2g gene g's forward set, 2g + 1 its reverse set; k-mers first, counts second), or the
+        raw arrays (kmers, counts, offsets) of shk_primer_kmers.  params: one dict of pcr_extend's keyword arguments
+        (min_count, table_min_count, high_coverage_ratio, max_num_nodes, sweep) per gene, or one for all;
+        max_num_nodes None = compute_node_budget of the bases this context has ingested."""
+        raw = len(primer_results) == 3 and all(isinstance(x, np.ndarray) and x.ndim == 1 for x in primer_results)
+        if raw:
+            pk = np.ascontiguousarray(primer_results[0], dtype=np.uint64)
+            pc = np.ascontiguousarray(primer_results[1], dtype=np.uint32)
+            po = np.ascontiguousarray(primer_results[2], dtype=np.uint64)
+            if len(po) < 1 or len(po) % 2 != 1:
+                raise ValueError("primer offsets take 2 * n_genes + 1 entries")
+        else:
+            sets = list(primer_results)
+            if len(sets) % 2:
+                raise ValueError("a forward and a reverse set per gene")
+            ks = [np.ascontiguousarray(x[0], dtype=np.uint64).reshape(-1) for x in sets]
+            cs = [np.ascontiguousarray(x[1], dtype=np.uint32).reshape(-1) for x in sets]
+            if any(len(a) != len(b) for a, b in zip(ks, cs)):
+                raise ValueError("k-mers and counts differ in length")
+            pk = np.concatenate(ks) if ks else np.zeros(0, dtype=np.uint64)
+            pc = np.concatenate(cs) if cs else np.zeros(0, dtype=np.uint32)
+            po = np.zeros(len(sets) + 1, dtype=np.uint64)
+            if sets:
+                po[1:] = np.cumsum([len(a) for a in ks])
+        ng = (len(po) - 1) // 2
+        if params is None or isinstance(params, dict):
+            params = [params or {}] * ng
+        if len(params) != ng:
+            raise ValueError("one set of parameters per gene")
+        budget = None
+        prm = (_PcrExtendParams * max(ng, 1))()
+        for g, p in enumerate(params):
+            p = dict(p)
+            mnn = p.get("max_num_nodes")
+            if mnn is None:
+                if budget is None:
+                    budget = pcr_node_budget(self.counters()["n_bases_ingested"])
+                mnn = budget
+            prm[g] = _PcrExtendParams(p.get("min_count", 2), p.get("table_min_count", 2), p.get("high_coverage_ratio", 10.0),
+                                      mnn, 1 if p.get("sweep", True) else 0, 0)
+        noff, eoff = np.zeros(ng + 1, dtype=np.uint64), np.zeros(ng + 1, dtype=np.uint64)
+        found, thr, steps = (np.zeros(max(ng, 1), dtype=np.uint32) for _ in range(3))
+        node_cap, edge_cap = 4096 * max(ng, 1), 8192 * max(ng, 1)
+        for attempt in (0, 1):
+            sub = np.zeros(node_cap, dtype=np.uint64)
+            flags = np.zeros(node_cap, dtype=np.uint8)
+            es, et, ec = (np.zeros(edge_cap, dtype=np.uint32) for _ in range(3))
+            rcode = self._L.shk_pcr_extend_panel(self._h, pk.ctypes.data, pc.ctypes.data, po.ctypes.data, ng, C.cast(prm, C.c_void_p),
+                                                 sub.ctypes.data, flags.ctypes.data, noff.ctypes.data, node_cap, es.ctypes.data,
+                                                 et.ctypes.data, ec.ctypes.data, eoff.ctypes.data, edge_cap, found.ctypes.data,
+                                                 thr.ctypes.data, steps.ctypes.data)
+            n, e = int(noff[ng]), int(eoff[ng])
+            if attempt == 0 and rcode == -2 and (n > node_cap or e > edge_cap):  # too small: the offsets say what it needs
+                node_cap, edge_cap = max(node_cap, n), max(edge_cap, e)
+                continue
+            self._check(rcode)
+            break
+        out = []
+        for g in range(ng):
+            a, b, x, y = int(noff[g]), int(noff[g + 1]), int(eoff[g]), int(eoff[g + 1])
+            out.append(PcrGraph(sub[a:b].copy(), flags[a:b].copy(), es[x:y].copy(), et[x:y].copy(), ec[x:y].copy(),
+                                bool(found[g]), int(thr[g]), int(steps[g])))
+        return out
 
     def thread_reads(self, graph, bases, offsets, read_index=None, mate=None, device: bool = False) -> ThreadingAnnotations:
         """thread_reads / thread_reads_paired (pcr/threading.rs:87-192) of a batch through `graph` — a PcrGraph or a
