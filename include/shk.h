@@ -595,6 +595,65 @@ int shk_pcr_extend_panel(shk_ctx *ctx, const uint64_t *primer_kmers, const uint3
 /* compute_node_budget (graph.rs:40-52): 100 000 nodes up to 150 Mbp ingested, 500 000 from 750 Mbp, linear between. */
 uint64_t shk_pcr_node_budget(uint64_t n_bases_ingested);
 
+/* The pruning stage of do_pcr for a whole sPCR panel in ONE call: remove_low_coverage_tips → reachability_pruning →
+ * annotate_coverage_ratios (src/pcr/mod.rs:631-697; src/pcr/pruning.rs, src/pcr/graph.rs:533-546), between
+ * shk_pcr_extend_panel and shk_thread_reads_panel.  One workgroup per gene on the device.
+ * IN: the output of shk_pcr_extend_panel as it is (n_genes outputs of shk_pcr_extend concatenated will do as well):
+ *   per-gene offsets (n_genes + 1 each, non-decreasing), edge endpoints LOCAL to the gene, flags 1 = is_start,
+ *   2 = is_end.  k is the context's k.  node_sub_kmers is only carried through on the host and may be NULL (the
+ *   output's node_sub_kmers is not written then).  params[g]: gene g's parameters.
+ * SEMANTICS, per gene, exactly the reference:
+ *   Degrees are edge counts (neighbors_directed(..).count() on a StableDiGraph): parallel edges count severally, a
+ *     self-loop counts in both directions.
+ *   Tip stage (stages bit 0; pruning.rs:19-95): median = median_via_select of all edge counts of the INPUT graph, 1.0
+ *     without edges; min_tip = max(median × tip_coverage_fraction, 1.0), computed once.  Rounds run until one removes
+ *     nothing.  In a round every surviving node that is neither start nor end and has out-degree 0 or in-degree 0 is
+ *     judged on the graph as it stood at the START of the round, and all nodes judged removable leave together with
+ *     their edges.  Out-degree 0: removable iff tip_length_backward < k and its largest incoming edge count (0 without
+ *     one), as f64, is < min_tip; in-degree 0: the same with tip_length_forward and its outgoing counts; both degrees
+ *     0: both tests.  tip_length_backward (:99-124) starts at 1; while the current node has exactly one incoming edge
+ *     whose source has out-degree <= 1 and is not a start node, it steps to that source and adds 1.
+ *     tip_length_forward (:128-149) is the mirror image with in-degree and is_end.
+ *   Reachability (stages bit 1; :170-214), on what the tip stage left: keep exactly the nodes reachable forward from
+ *     some surviving start node AND backward from some surviving end node.
+ *   Annotation (graph.rs:533-546): median of the pruned graph's edge counts; coverage_ratio[e] = count / median when
+ *     there is an edge and median > 0, otherwise every ratio is 0.0 (what get_dbedge left).
+ * OUT: node_keep[v] for every input node (index as in the input arrays), always.  The compacted graphs: the surviving
+ *   nodes and edges (an edge survives iff both endpoints do) in ascending original index at out_node_offsets[g] .. /
+ *   out_edge_offsets[g] .., endpoints renumbered to positions in the compacted gene — the input form of
+ *   shk_thread_reads_panel; node_index / edge_index: each survivor's original local index.  tip_rounds counts the
+ *   rounds that removed something.  node_cap / edge_cap too small: SHK_ERR_BAD_ARG with both out-offset arrays (their
+ *   last entries are the need), node_keep, median and the counters complete.  n_genes == 0: zero offsets.  An empty
+ *   gene is valid; a gene without a start or an end prunes to nothing.
+ * Errors, SHK_ERR_BAD_ARG with a text that names the gene, all raised before the device is touched: an endpoint >= the
+ *   gene's node count, decreasing offsets, a flag above 3, a NaN tip_coverage_fraction, stages > 3; also n_genes >
+ *   SHK_PCR_MAX_GENES and 2^32 or more nodes or edges in total.  Scratch that cannot be had: SHK_ERR_NOMEM, the context
+ *   stays usable.
+ * State: the table is neither read nor written; valid in any state of the context and on owner shares; a multi-device
+ *   context runs it on its first device.  The kernel takes no slot of shk_timings: device_ms is the call's own.
+ * Tuning, read at each call, never changes a result: SHK_PRUNE_LDS_NODES (default 2560) — a gene of at most that many
+ *   nodes whose adjacency and state fit 79 KiB (24 bytes per node + 8.25 per edge) is pruned in LDS, larger ones in
+ *   the context's grow-only scratch (16 bytes per node on top of the upload); 0: every gene in global memory. */
+typedef struct shk_pcr_prune_params {
+  double   tip_coverage_fraction; /* PCRParams.tip_coverage_fraction [0.1] */
+  uint32_t stages;                /* bit 0 remove_low_coverage_tips, bit 1 reachability_pruning; 0 is read as 3 */
+  uint32_t reserved;
+} shk_pcr_prune_params;
+
+typedef struct shk_pcr_prune_out {      /* every pointer optional except node_keep */
+  uint8_t  *node_keep;                  /* [node_offsets[n_genes]] 1 = the node survives */
+  uint64_t *out_node_offsets, *out_edge_offsets;  /* [n_genes + 1] */
+  uint64_t *node_sub_kmers; uint8_t *node_flags; uint32_t *node_index; uint64_t node_cap;
+  uint32_t *edge_src, *edge_tgt, *edge_counts, *edge_index; double *coverage_ratio; uint64_t edge_cap;
+  double   *median;                     /* [n_genes] median edge count of the pruned graph, 0.0 when it has no edges */
+  uint32_t *tip_rounds, *tips_removed, *unreachable_removed;  /* [n_genes] each */
+  double    device_ms;                  /* event time of the call's launches */
+} shk_pcr_prune_out;
+
+int shk_pcr_prune_panel(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint8_t *node_flags, const uint64_t *node_offsets,
+                        const uint32_t *edge_src, const uint32_t *edge_tgt, const uint32_t *edge_counts, const uint64_t *edge_offsets,
+                        uint32_t n_genes, const shk_pcr_prune_params *params /* n_genes */, shk_pcr_prune_out *out);
+
 /* ---- multi-GPU hooks (device pointers; exchanged by the caller over RCCL) ---- */
 
 /* Table geometry needed to shard by owner: n_pages (power of two),

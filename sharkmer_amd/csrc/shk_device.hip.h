@@ -2469,6 +2469,224 @@ __global__ void __launch_bounds__(WG) k_synth(SynthSpec sp, uint64_t first_read,
   }
 }
 
+// ==========================================================================================
+// K_PRUNE: the pruning stage of sPCR between extension and threading:
+// remove_low_coverage_tips (src/pcr/pruning.rs:19-149) and reachability_pruning (:170-214) for
+// every gene of a panel, one workgroup per gene, blockIdx.x the gene.  Nothing is shared
+// between genes and no workgroup waits for another; inside a gene the phases are separated by
+// workgroup barriers only, and every loop is bounded by the gene's size.
+//
+// A gene is its two CSR sides as the host's counting sort made them: in_first / out_first
+// (n + 1 entries), in_nbr[j] the SOURCE of the j-th edge into a node, out_nbr[j] the TARGET of
+// the j-th edge out of it (parallel edges and self-loops listed severally), and one bit per
+// list position, "this edge's count, as f64, is >= min_tip_count" (the only thing the tip rule
+// asks of a count).  No answer depends on the order inside a node's list.
+//
+// Working state, 4 words per node:
+//   mark     0 = alive, r = removed by tip round r.  "Alive at the start of round r" is
+//            mark ∈ {0, r}: the decide phase may set r while others still read it.
+//   indeg / outdeg   live edge counts (neighbors_directed(..).count()); after the tip stage the
+//            same words are the two BFS queues (a node enters a queue once: n entries each)
+//   fr       bits 0-1 the node's flags (1 is_start, 2 is_end), bit 2 reached forward from a
+//            start, bit 3 reached backward from an end
+// LDS form: CSR and state live in the workgroup's LDS (copied in first); global form: the CSR
+// is read where the host put it and the state lives in the context's scratch.  Both forms are
+// prune_gene over a PruneView, inlined once with LDS pointers and once with global ones.
+// ==========================================================================================
+constexpr int PRUNE_WG = 1024;                     // one workgroup per gene
+constexpr size_t PRUNE_LDS_MAX = 79u << 10;        // two genes per CU: 2 × (79 KiB + the counters below) within 160 KiB
+constexpr int PRUNE_LDS_NODES = 2560;              // default of SHK_PRUNE_LDS_NODES: 24 B per node + 8.25 B per edge ≤ PRUNE_LDS_MAX at n = e
+
+struct PruneGene {
+  uint64_t in_first, out_first, in_nbr, out_nbr, in_heavy, out_heavy, flags;  // byte offsets into the uploaded block
+  uint64_t work;   // global form: first of the gene's 4 · n state words
+  uint64_t keep;   // the gene's first byte of node_keep
+  uint32_t n, e;
+  uint32_t lds, stages;
+};
+struct PruneCounters { uint32_t tip_rounds, tips_removed, unreachable_removed, pad; };
+
+__host__ __device__ inline size_t prune_lds_bytes(uint64_t n, uint64_t e) {
+  return (size_t)(4 * (2 * (n + 1) + 2 * e + 2 * ((e + 31) / 32) + 4 * n));
+}
+
+struct PruneView {
+  const uint32_t *in_first, *out_first, *in_nbr, *out_nbr, *in_heavy, *out_heavy;
+  uint32_t *mark, *indeg, *outdeg, *fr;
+};
+
+__device__ __forceinline__ bool prune_alive(const uint32_t *mark, uint32_t v, uint32_t r) {
+  const uint32_t m = mark[v];
+  return m == 0 || m == r;
+}
+
+// One side of the tip rule for dead end v at the start of round r: the walk of tip_length_backward (first/nbr/heavy the
+// INCOMING side, deg_same = indeg, deg_other = outdeg, stop = is_start) or of tip_length_forward (the mirror image)
+// stays below k nodes, and no live edge on that side of v is heavy.
+__device__ __forceinline__ bool prune_tip_side(const uint32_t *first, const uint32_t *nbr, const uint32_t *heavy, const uint32_t *mark,
+                                               const uint32_t *deg_same, const uint32_t *deg_other, const uint32_t *fr, uint32_t stop,
+                                               uint32_t v, uint32_t r, uint32_t k) {
+  for (uint32_t j = first[v], j1 = first[v + 1]; j < j1; ++j)
+    if (((heavy[j >> 5] >> (j & 31)) & 1u) && prune_alive(mark, nbr[j], r)) return false;
+  uint32_t cur = v;
+  for (uint32_t len = 1;; ++len) {  // (at most k turns)
+    if (len >= k) return false;
+    if (deg_same[cur] != 1) return true;
+    uint32_t next = ~0u;
+    for (uint32_t j = first[cur], j1 = first[cur + 1]; j < j1; ++j)
+      if (prune_alive(mark, nbr[j], r)) {
+        next = nbr[j];
+        break;
+      }
+    if (next == ~0u || deg_other[next] > 1 || (fr[next] & stop)) return true;
+    cur = next;
+  }
+}
+
+__device__ __forceinline__ void prune_gene(const PruneView &g, uint32_t n, uint32_t stages, uint32_t k, uint8_t *__restrict__ keep,
+                                           PruneCounters *__restrict__ out) {
+  __shared__ uint32_t s_cnt[2], s_fn[3], s_bn[3], s_kept, s_live;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) {
+    s_cnt[0] = s_cnt[1] = 0;
+    s_fn[0] = s_fn[1] = s_fn[2] = s_bn[0] = s_bn[1] = s_bn[2] = 0;
+    s_kept = s_live = 0;
+  }
+  for (uint32_t v = tid; v < n; v += PRUNE_WG) {
+    g.mark[v] = 0;
+    g.indeg[v] = g.in_first[v + 1] - g.in_first[v];
+    g.outdeg[v] = g.out_first[v + 1] - g.out_first[v];
+  }
+  __syncthreads();
+  uint32_t rounds = 0, removed = 0;
+  if (stages & 1u) {
+    // a round that goes on removes a node: at most n of them, and one more that finds nothing
+    for (uint64_t r64 = 1; r64 <= (uint64_t)n + 1; ++r64) {
+      const uint32_t r = (uint32_t)r64;
+      // decide, on the graph as the round found it
+      for (uint32_t v = tid; v < n; v += PRUNE_WG) {
+        if (g.mark[v] != 0 || (g.fr[v] & 3u)) continue;
+        const uint32_t od = g.outdeg[v], id = g.indeg[v];
+        if (od && id) continue;
+        bool rm = true;
+        if (od == 0) rm = prune_tip_side(g.in_first, g.in_nbr, g.in_heavy, g.mark, g.indeg, g.outdeg, g.fr, 1u, v, r, k);
+        if (rm && id == 0) rm = prune_tip_side(g.out_first, g.out_nbr, g.out_heavy, g.mark, g.outdeg, g.indeg, g.fr, 2u, v, r, k);
+        if (rm) {
+          g.mark[v] = r;
+          atomicAdd(&s_cnt[r & 1u], 1u);
+        }
+      }
+      __syncthreads();
+      const uint32_t n_rm = s_cnt[r & 1u];
+      if (n_rm == 0) break;  // (the same for every thread)
+      rounds += 1;
+      removed += n_rm;
+      if (tid == 0) s_cnt[(r + 1) & 1u] = 0;  // (last read behind the previous round's decide barrier)
+      // apply: the marked nodes leave with their edges
+      for (uint32_t v = tid; v < n; v += PRUNE_WG) {
+        if (g.mark[v] != r) continue;
+        for (uint32_t j = g.out_first[v], j1 = g.out_first[v + 1]; j < j1; ++j)
+          if (prune_alive(g.mark, g.out_nbr[j], r)) atomicSub(&g.indeg[g.out_nbr[j]], 1u);
+        for (uint32_t j = g.in_first[v], j1 = g.in_first[v + 1]; j < j1; ++j)
+          if (prune_alive(g.mark, g.in_nbr[j], r)) atomicSub(&g.outdeg[g.in_nbr[j]], 1u);
+      }
+      __syncthreads();
+    }
+  }
+  if (stages & 2u) {
+    // both searches in one level loop; level L counts its new entries in s_fn / s_bn[L % 3] and clears the pair of
+    // level L + 1, which was last read behind the barrier of level L − 2
+    uint32_t *fq = g.indeg, *bq = g.outdeg;
+    __syncthreads();  // (a round that broke off: everyone is past its reads of the degrees)
+    for (uint32_t v = tid; v < n; v += PRUNE_WG) {
+      if (g.mark[v] != 0) continue;
+      const uint32_t f = g.fr[v];
+      if (f & 1u) {
+        g.fr[v] = f | (f & 2u ? 12u : 4u);
+        fq[atomicAdd(&s_fn[0], 1u)] = v;
+      }
+      if (f & 2u) {
+        if (!(f & 1u)) g.fr[v] = f | 8u;
+        bq[atomicAdd(&s_bn[0], 1u)] = v;
+      }
+    }
+    __syncthreads();
+    uint32_t fh = 0, ft = s_fn[0], bh = 0, bt = s_bn[0];
+    // a level that goes on enters a node into a queue: at most 2n of them
+    for (uint64_t lvl = 1; lvl <= 2 * (uint64_t)n + 1; ++lvl) {
+      const uint64_t nf = ft - fh, nb = bt - bh;
+      if (nf + nb == 0) break;  // (the same for every thread)
+      const uint32_t c = (uint32_t)(lvl % 3), cz = (uint32_t)((lvl + 1) % 3);
+      if (tid == 0) s_fn[cz] = s_bn[cz] = 0;
+      for (uint64_t i = tid; i < nf + nb; i += PRUNE_WG) {
+        if (i < nf) {
+          const uint32_t v = fq[fh + (uint32_t)i];
+          for (uint32_t j = g.out_first[v], j1 = g.out_first[v + 1]; j < j1; ++j) {
+            const uint32_t u = g.out_nbr[j];
+            if (g.mark[u] == 0 && !(atomicOr(&g.fr[u], 4u) & 4u)) fq[ft + atomicAdd(&s_fn[c], 1u)] = u;
+          }
+        } else {
+          const uint32_t v = bq[bh + (uint32_t)(i - nf)];
+          for (uint32_t j = g.in_first[v], j1 = g.in_first[v + 1]; j < j1; ++j) {
+            const uint32_t u = g.in_nbr[j];
+            if (g.mark[u] == 0 && !(atomicOr(&g.fr[u], 8u) & 8u)) bq[bt + atomicAdd(&s_bn[c], 1u)] = u;
+          }
+        }
+      }
+      __syncthreads();
+      fh = ft, ft += s_fn[c];
+      bh = bt, bt += s_bn[c];
+    }
+  }
+  uint32_t kept = 0, live = 0;
+  for (uint32_t v = tid; v < n; v += PRUNE_WG) {
+    const bool alive = g.mark[v] == 0;
+    const bool kp = alive && (!(stages & 2u) || (g.fr[v] & 12u) == 12u);
+    keep[v] = kp ? 1 : 0;
+    kept += kp, live += alive;
+  }
+  if (kept) atomicAdd(&s_kept, kept);
+  if (live) atomicAdd(&s_live, live);
+  __syncthreads();
+  if (tid == 0) *out = PruneCounters{rounds, removed, s_live - s_kept, 0};
+}
+
+__global__ void __launch_bounds__(PRUNE_WG) k_prune_panel(const PruneGene *__restrict__ genes, const uint8_t *__restrict__ up,
+                                                          uint32_t *__restrict__ work, uint8_t *__restrict__ keep,
+                                                          PruneCounters *__restrict__ counters, uint32_t k) {
+  extern __shared__ uint32_t s_prune[];
+  const PruneGene d = genes[blockIdx.x];
+  const uint32_t n = d.n, e = d.e, tid = threadIdx.x;
+  PruneCounters *out = counters + blockIdx.x;
+  if (n == 0) {  // (the same for every thread)
+    if (tid == 0) *out = PruneCounters{0, 0, 0, 0};
+    return;
+  }
+  const uint32_t *in_first = (const uint32_t *)(up + d.in_first), *out_first = (const uint32_t *)(up + d.out_first);
+  const uint32_t *in_nbr = (const uint32_t *)(up + d.in_nbr), *out_nbr = (const uint32_t *)(up + d.out_nbr);
+  const uint32_t *in_heavy = (const uint32_t *)(up + d.in_heavy), *out_heavy = (const uint32_t *)(up + d.out_heavy);
+  const uint8_t *flags = up + d.flags;
+  const uint32_t hw = (e + 31) / 32;
+  if (d.lds) {
+    // prune_lds_bytes' layout: in_first, out_first, in_nbr, out_nbr, in_heavy, out_heavy, mark, indeg, outdeg, fr
+    uint32_t *l_in_first = s_prune, *l_out_first = l_in_first + (n + 1), *l_in_nbr = l_out_first + (n + 1), *l_out_nbr = l_in_nbr + e;
+    uint32_t *l_in_heavy = l_out_nbr + e, *l_out_heavy = l_in_heavy + hw, *l_mark = l_out_heavy + hw, *l_indeg = l_mark + n;
+    uint32_t *l_outdeg = l_indeg + n, *l_fr = l_outdeg + n;
+    for (uint32_t i = tid; i <= n; i += PRUNE_WG) l_in_first[i] = in_first[i], l_out_first[i] = out_first[i];
+    for (uint32_t i = tid; i < e; i += PRUNE_WG) l_in_nbr[i] = in_nbr[i], l_out_nbr[i] = out_nbr[i];
+    for (uint32_t i = tid; i < hw; i += PRUNE_WG) l_in_heavy[i] = in_heavy[i], l_out_heavy[i] = out_heavy[i];
+    for (uint32_t i = tid; i < n; i += PRUNE_WG) l_fr[i] = flags[i] & 3u;
+    __syncthreads();
+    prune_gene(PruneView{l_in_first, l_out_first, l_in_nbr, l_out_nbr, l_in_heavy, l_out_heavy, l_mark, l_indeg, l_outdeg, l_fr}, n, d.stages, k,
+               keep + d.keep, out);
+  } else {
+    uint32_t *w = work + d.work;
+    for (uint32_t i = tid; i < n; i += PRUNE_WG) w[3 * (uint64_t)n + i] = flags[i] & 3u;
+    prune_gene(PruneView{in_first, out_first, in_nbr, out_nbr, in_heavy, out_heavy, w, w + n, w + 2 * (uint64_t)n, w + 3 * (uint64_t)n}, n, d.stages,
+               k, keep + d.keep, out);
+  }
+}
+
 }  // namespace shk
 
 // ##########################################################################################

@@ -148,6 +148,37 @@ class PcrGraph:
     steps_run: int
 
 
+class _PcrPruneParams(C.Structure):
+    _fields_ = [("tip_coverage_fraction", C.c_double), ("stages", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _PcrPruneOut(C.Structure):
+    _fields_ = [("node_keep", C.c_void_p), ("out_node_offsets", C.c_void_p), ("out_edge_offsets", C.c_void_p),
+                ("node_sub_kmers", C.c_void_p), ("node_flags", C.c_void_p), ("node_index", C.c_void_p), ("node_cap", C.c_uint64),
+                ("edge_src", C.c_void_p), ("edge_tgt", C.c_void_p), ("edge_counts", C.c_void_p), ("edge_index", C.c_void_p),
+                ("coverage_ratio", C.c_void_p), ("edge_cap", C.c_uint64), ("median", C.c_void_p), ("tip_rounds", C.c_void_p),
+                ("tips_removed", C.c_void_p), ("unreachable_removed", C.c_void_p), ("device_ms", C.c_double)]
+
+
+@dataclass
+class PrunedGraph:
+    """What shk_pcr_prune_panel returns for a gene: the graph after remove_low_coverage_tips, reachability_pruning and
+    annotate_coverage_ratios (pcr/mod.rs:631-697) — the survivors in ascending original index, endpoints renumbered."""
+    node_sub_kmers: np.ndarray  # u64
+    node_flags: np.ndarray      # u8: 1 is_start, 2 is_end
+    edge_src: np.ndarray        # u32, positions in this graph
+    edge_tgt: np.ndarray
+    edge_counts: np.ndarray     # u32
+    node_index: np.ndarray      # u32: each node's index in the graph that went in
+    edge_index: np.ndarray      # u32: each edge's index in the graph that went in
+    coverage_ratio: np.ndarray  # f64 per edge, DBEdge.coverage_ratio
+    median: float               # median edge count of this graph, 0.0 without edges
+    node_keep: np.ndarray       # u8 per node of the graph that went in
+    tip_rounds: int             # tip rounds that removed something
+    tips_removed: int
+    unreachable_removed: int
+
+
 THREAD_TILE = 64  # the list elements one wave step of k_thread_reads covers (THREAD_TILE in csrc/shk_device.hip.h)
 
 
@@ -203,6 +234,7 @@ ABI_SYMBOLS = [
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
     "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget", "shk_neighborhood_panel", "shk_pcr_extend_panel",
+    "shk_pcr_prune_panel",
     "shk_thread_reads", "shk_thread_reads_device", "shk_thread_reads_panel", "shk_thread_reads_panel_device",
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
 ]
@@ -331,6 +363,7 @@ def load_library():
     L.shk_pcr_node_budget.argtypes = [u64]
     L.shk_neighborhood_panel.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.shk_pcr_extend_panel.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
+    L.shk_pcr_prune_panel.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, C.POINTER(_PcrPruneOut)]
     L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_panel.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(_ThreadPanelOut)]
@@ -420,6 +453,9 @@ class KmerEngine:
         if rc != 0:
             raise ShkError(rc, (self._L.shk_last_error(None) or b"").decode("utf-8", "replace"))
         self._h = h
+
+    last_prune_device_ms = 0.0  # shk_pcr_prune_out.device_ms of the last pcr_prune_panel call
+    prune_first_cap = 1 << 22   # pcr_prune_panel's first guess at the room the pruned panel needs, nodes and edges each
 
     # -- plumbing ------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -776,12 +812,86 @@ class KmerEngine:
                                 bool(found[g]), int(thr[g]), int(steps[g])))
         return out
 
+    def pcr_prune_panel(self, graphs, tip_coverage_fraction=0.1, stages=3) -> list:
+        """remove_low_coverage_tips, reachability_pruning and annotate_coverage_ratios for every gene of a panel in one
+        call (shk_pcr_prune_panel) → one PrunedGraph per gene, a list thread_reads_panel takes as it is.  graphs: what
+        pcr_extend_panel returns, or (node_sub_kmers, node_flags, edge_src, edge_tgt, edge_counts) tuples with endpoints
+        local to the gene.  tip_coverage_fraction and stages (bit 0 the tips, bit 1 reachability): one value for all
+        genes or one per gene."""
+        gs = [(g.node_sub_kmers, g.node_flags, g.edge_src, g.edge_tgt, g.edge_counts) if isinstance(g, (PcrGraph, PrunedGraph)) else g
+              for g in graphs]
+        ng = len(gs)
+        subs = [np.ascontiguousarray(g[0], dtype=np.uint64).reshape(-1) for g in gs]
+        fls = [np.ascontiguousarray(g[1], dtype=np.uint8).reshape(-1) for g in gs]
+        ess = [np.ascontiguousarray(g[2], dtype=np.uint32).reshape(-1) for g in gs]
+        ets = [np.ascontiguousarray(g[3], dtype=np.uint32).reshape(-1) for g in gs]
+        ecs = [np.ascontiguousarray(g[4], dtype=np.uint32).reshape(-1) for g in gs]
+        if any(len(a) != len(b) for a, b in zip(subs, fls)):
+            raise ValueError("node_sub_kmers and node_flags differ in length")
+        if any(len(a) != len(b) or len(a) != len(c_) for a, b, c_ in zip(ess, ets, ecs)):
+            raise ValueError("edge_src, edge_tgt and edge_counts differ in length")
+        fracs = list(tip_coverage_fraction) if np.ndim(tip_coverage_fraction) else [tip_coverage_fraction] * ng
+        stgs = list(stages) if np.ndim(stages) else [stages] * ng
+        if len(fracs) != ng or len(stgs) != ng:
+            raise ValueError("one tip_coverage_fraction and one stages value per gene")
+
+        def cat(parts, dtype):
+            off = np.zeros(ng + 1, dtype=np.uint64)
+            if parts:
+                off[1:] = np.cumsum([len(x) for x in parts])
+            return (np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)), off
+
+        sub, noff = cat(subs, np.uint64)
+        fl, _ = cat(fls, np.uint8)
+        es, eoff = cat(ess, np.uint32)
+        et, _ = cat(ets, np.uint32)
+        ec, _ = cat(ecs, np.uint32)
+        prm = (_PcrPruneParams * max(ng, 1))()
+        for g in range(ng):
+            prm[g] = _PcrPruneParams(float(fracs[g]), int(stgs[g]), 0)
+        nn, ne = len(sub), len(es)
+        keep = np.zeros(max(nn, 1), dtype=np.uint8)
+        ono, oeo = np.zeros(ng + 1, dtype=np.uint64), np.zeros(ng + 1, dtype=np.uint64)
+        med = np.zeros(max(ng, 1), dtype=np.float64)
+        rounds, tips, unreach = (np.zeros(max(ng, 1), dtype=np.uint32) for _ in range(3))
+        # a pruned graph is no larger than what went in: room for all of it (pages nothing writes to cost nothing), up to
+        # prune_first_cap entries — a call that keeps more says so and is made again, which prunes a second time
+        node_cap, edge_cap = max(min(nn, self.prune_first_cap), 1), max(min(ne, self.prune_first_cap), 1)
+        for attempt in (0, 1):
+            osub, ofl, oni = np.zeros(node_cap, dtype=np.uint64), np.zeros(node_cap, dtype=np.uint8), np.zeros(node_cap, dtype=np.uint32)
+            oes, oet, oec, oei = (np.zeros(edge_cap, dtype=np.uint32) for _ in range(4))
+            ratio = np.zeros(edge_cap, dtype=np.float64)
+            out = _PcrPruneOut(keep.ctypes.data, ono.ctypes.data, oeo.ctypes.data, osub.ctypes.data, ofl.ctypes.data, oni.ctypes.data,
+                               node_cap, oes.ctypes.data, oet.ctypes.data, oec.ctypes.data, oei.ctypes.data, ratio.ctypes.data, edge_cap,
+                               med.ctypes.data, rounds.ctypes.data, tips.ctypes.data, unreach.ctypes.data, 0.0)
+            rcode = self._L.shk_pcr_prune_panel(self._h, sub.ctypes.data, fl.ctypes.data, noff.ctypes.data, es.ctypes.data, et.ctypes.data,
+                                                ec.ctypes.data, eoff.ctypes.data, ng, C.cast(prm, C.c_void_p), C.byref(out))
+            n, e = int(ono[ng]), int(oeo[ng])
+            if attempt == 0 and rcode == -2 and (n > node_cap or e > edge_cap):  # too small: the offsets say what it needs
+                node_cap, edge_cap = max(node_cap, n), max(edge_cap, e)
+                continue
+            self._check(rcode)
+            break
+        self.last_prune_device_ms = float(out.device_ms)
+        res = []
+        for g in range(ng):
+            a, b, x, y = (int(v) for v in (ono[g], ono[g + 1], oeo[g], oeo[g + 1]))
+            v0, v1 = int(noff[g]), int(noff[g + 1])
+            res.append(PrunedGraph(osub[a:b].copy(), ofl[a:b].copy(), oes[x:y].copy(), oet[x:y].copy(), oec[x:y].copy(), oni[a:b].copy(),
+                                   oei[x:y].copy(), ratio[x:y].copy(), float(med[g]), keep[v0:v1].copy(), int(rounds[g]), int(tips[g]),
+                                   int(unreach[g])))
+        return res
+
+    def pcr_prune(self, graph, tip_coverage_fraction: float = 0.1, stages: int = 3) -> PrunedGraph:
+        """pcr_prune_panel for one gene."""
+        return self.pcr_prune_panel([graph], tip_coverage_fraction, stages)[0]
+
     def thread_reads(self, graph, bases, offsets, read_index=None, mate=None, device: bool = False) -> ThreadingAnnotations:
         """thread_reads / thread_reads_paired (pcr/threading.rs:87-192) of a batch through `graph` — a PcrGraph or a
         (node_sub_kmers, edge_src, edge_tgt) tuple, any graph at all — on the device (shk_thread_reads).  read_index
         and mate (0 unpaired, 1 R1, 2 R2) together give the paired form.  device=True: bases and offsets are torch
         tensors on this context's device (shk_thread_reads_device)."""
-        if isinstance(graph, PcrGraph):
+        if isinstance(graph, (PcrGraph, PrunedGraph)):
             graph = (graph.node_sub_kmers, graph.edge_src, graph.edge_tgt)
         sub = np.ascontiguousarray(graph[0], dtype=np.uint64)
         es = np.ascontiguousarray(graph[1], dtype=np.uint32)
@@ -830,7 +940,7 @@ class KmerEngine:
         answer is one ThreadingAnnotations per gene: what thread_reads gives for that graph over its listed reads in
         list order.  read_index and mate (one entry per read of the BATCH) give the paired form.  device=True: bases
         and offsets are torch tensors on this context's device (shk_thread_reads_panel_device)."""
-        gs = [(g.node_sub_kmers, g.edge_src, g.edge_tgt) if isinstance(g, PcrGraph) else g for g in graphs]
+        gs = [(g.node_sub_kmers, g.edge_src, g.edge_tgt) if isinstance(g, (PcrGraph, PrunedGraph)) else g for g in graphs]
         ng = len(gs)
         if len(lists) != ng:
             raise ValueError("one read list per graph")
