@@ -251,6 +251,11 @@ int shk_histograms(shk_ctx *ctx, uint64_t *out);
 int shk_get_counters(shk_ctx *ctx, shk_counters *out);
 int shk_get_timings(shk_ctx *ctx, shk_timings *out);
 int shk_reset_timings(shk_ctx *ctx);
+/* The materialising page pass of a context whose last counting launch left its table unwritten (a histogram job's
+ * fresh fused page pass writes no table; the first reader or writer of the table has it written then): device time and
+ * timed launches since shk_reset_timings, under SHK_FLAG_TIMING like the slots of shk_timings — whose layout is fixed
+ * by this ABI version, hence a call of its own.  Either pointer may be null. */
+int shk_get_lazy_table_timing(shk_ctx *ctx, double *ms, uint64_t *launches);
 
 /* ---- merged-table read API (counting.rs:205-260) --------------------------------- */
 

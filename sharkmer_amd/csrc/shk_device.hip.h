@@ -4389,10 +4389,17 @@ struct FusedHist {
   unsigned long long histo_max;
   uint32_t n_cols;
   uint32_t pad;
+  unsigned long long *pspill;    // [page]: records this page's workgroup put on the spill list (TABLE = false only)
 };
 // (HIST = 2: the launch covers ONE chunk lane — no running sums to carry across a lane loop: the fold's sixteen
 // registers and what they cost the record loop's code are not there)
-template <bool FRESH, int HIST = 0>
+//
+// TABLE = false (with HIST): the histogram-only form.  Identical up to the end of a lane's record loop; then neither
+// the lane's counts nor, at the end, the rebuilt keys are stored — the histogram rows, the totals, the spills and
+// n_distinct are what the pass leaves.  The table is then DEFINED by the regions and cursors the launch read
+// (shk_ctx::tb_virtual): whoever needs it runs k_pages32<true, 0> over them again.  A page's own spills are counted
+// (pspill): that second pass spills for itself, so the host takes these off the list and keeps the scatter's.
+template <bool FRESH, int HIST = 0, bool TABLE = true>
 __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane_lo, uint32_t lane_hi,
                                                       uint32_t lane_stride, uint32_t n_regions_,
                                                       const unsigned int *__restrict__ cursor, uint32_t cap_p,
@@ -4400,6 +4407,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
                                                       DevStats *__restrict__ stats, SpillRef sp, uint32_t page0 = 0,
                                                       FusedHist fh = FusedHist{}) {
   static_assert(!HIST || FRESH, "the fused histogram is a fresh pass's");
+  static_assert(TABLE || HIST, "a pass that writes no table leaves the histogram");
   static_assert(FH_BINS == MQ32, "a wave bins into its own miss queue");
   __shared__ __attribute__((aligned(16))) uint32_t tags[PAGE_SLOTS];
   __shared__ __attribute__((aligned(16))) uint32_t dl[PAGE_SLOTS];  // this pass's count per slot
@@ -4463,8 +4471,10 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
     for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off, 64);
     may_insert = w < room;
   };
+  uint32_t n_sp = 0;    // per thread (TABLE = false)
   auto spill = [&](uint32_t rec) {
     const uint64_t key = unmix_key((gpage << R) | rec, bits);
+    if (!TABLE) ++n_sp;
     unsigned long long i = atomicAdd(&stats->spill_count, 1ull);
     if (i < sp.cap) {
       sp.keys[i] = key;
@@ -4581,7 +4591,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
     }
     gv = tb.vals + (uint64_t)lane * tb.cap + ((uint64_t)page << PAGE_LOG);
     if (n == 0) {  // (uniform across the workgroup)
-      if (FRESH) {
+      if (FRESH && TABLE) {
 #pragma unroll
         for (int u = 0; u < PAGE_SLOTS / 4 / PG_WG; ++u)
           reinterpret_cast<uint4 *>(gv)[threadIdx.x + u * PG_WG] = make_uint4(0u, 0u, 0u, 0u);
@@ -4684,7 +4694,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
       if (FRESH) {  // counts start at zero: every quad is written, none is read
 #pragma unroll
         for (int u = 0; u < WB; ++u) {
-          reinterpret_cast<uint4 *>(gv)[threadIdx.x + u * PG_WG] = d[u];
+          if (TABLE) reinterpret_cast<uint4 *>(gv)[threadIdx.x + u * PG_WG] = d[u];
           if (d[u].x | d[u].y | d[u].z | d[u].w)
             reinterpret_cast<uint4 *>(dl)[threadIdx.x + u * PG_WG] = make_uint4(0u, 0u, 0u, 0u);
         }
@@ -4710,7 +4720,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
     lds_barrier();  // (the counts on their way to HBM are nobody's business in here: the next lane's are elsewhere)
   }
   __syncthreads();
-  if (FRESH) {  // the page's keys, rebuilt from the tags: home bucket = bucket - d, fingerprint = the tag's upper bits
+  if (FRESH && TABLE) {  // the page's keys, rebuilt from the tags: home bucket = bucket - d, fingerprint = the tag's upper bits
 #pragma unroll
     for (int u = 0; u < LD; ++u) {
       const uint32_t i = threadIdx.x + u * PG_WG;
@@ -4735,6 +4745,10 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
   }
   const uint32_t nnew = pg_wg_sum(n_new, dl);
   if (nnew && threadIdx.x == 0) atomicAdd(&stats->n_distinct, (unsigned long long)nnew);
+  if (!TABLE) {
+    const uint32_t nsp = pg_wg_sum(n_sp, dl);
+    if (threadIdx.x == 0) fh.pspill[page] = nsp;
+  }
   if (HIST) {  // the page's share of the totals (k_histo's HistoTotals), one row of ptot
     unsigned long long t4[4] = {0, 0, fh_lane, 0};
     if (HIST == 1) {

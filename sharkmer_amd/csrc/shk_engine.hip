@@ -28,12 +28,13 @@
 using namespace shk;
 
 struct shk_ctx;
-static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, bool prezeroed);
+static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, bool prezeroed, bool more_follow);
 static int prepare_cursors(shk_ctx *c, bool multi, bool defer, uint32_t *n_words);
 static int acc_prepare(shk_ctx *c, uint64_t kmers_ub, int64_t lane_one, uint64_t lane_add_exact = 0);
 static bool first_launch_defers(shk_ctx *c, uint64_t kmers_ub, bool multi);
 static int settle(shk_ctx *c);
 static int settle_light(shk_ctx *c);
+static int tb_materialise(shk_ctx *c);
 static int flush_acc(shk_ctx *c);
 static int replay_held_spills(shk_ctx *c);
 static uint64_t acc_records_est(const shk_ctx *c, uint64_t kmers_ub);
@@ -227,6 +228,7 @@ struct HostBuf {  // grow-only pinned host scratch
   }
 };
 
+constexpr int K_MATERIALISE = SHK_N_KERNELS;  // the materialising page pass (tb_materialise): timed beside shk_timings
 struct TimedEvent {
   int kid;
   hipEvent_t a, b;
@@ -307,6 +309,21 @@ struct shk_ctx {
   // shk_reset does not clear the table: the first page pass that covers every page and lane writes it whole
   // (k_pages32<true>); anything else that touches the table first clears it then (tb_fresh)
   bool tb_stale = false;
+  // The table is VIRTUAL: the last counting launch's page pass left the histogram and wrote no table (k_pages32<true,
+  // HIST, false>).  What the table holds is defined by that launch's page regions and cursors, which are still where
+  // they were; tb_fresh — anybody's first touch of the table — runs the ordinary fresh pass over them (tb_materialise,
+  // timed as lazy_ms / lazy_launches), and a reset drops the state with the table.  A context that has materialised
+  // once writes its tables eagerly from then on (lazy_off; SHK_LAZY_TABLE: 0 never virtual, 1 this, 2 always virtual).
+  bool tb_virtual = false, lazy_off = false;
+  bool more_slices = false;  // the launch being planned is a slice of a host batch, and not its last: no virtual table
+  struct {
+    uint32_t n_pages, l_lo, l_hi, lane_stride, n_regions, cap;
+    const unsigned int *cursor;
+    const uint32_t *buf;
+    uint64_t spill_cap;
+  } vt{};
+  double lazy_ms = 0;          // the materialising passes: a slot beside shk_timings (whose layout is ABI 2's)
+  uint64_t lazy_launches = 0;
   // the histogram and totals on the device still hold what the last finalize read back: cleared by the next
   // reset, by the next ingest's k_mark_starts on its way, or by the next scan itself — not by a launch per finalize
   bool hist_dirty = false;
@@ -456,8 +473,13 @@ void resolve_timings(shk_ctx *c) {
     (void)hipEventSynchronize(ev.b);
     float ms = 0;
     if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
-      c->timings.ms[ev.kid] += ms;
-      c->timings.launches[ev.kid] += 1;
+      if (ev.kid == K_MATERIALISE) {
+        c->lazy_ms += ms;
+        c->lazy_launches += 1;
+      } else {
+        c->timings.ms[ev.kid] += ms;
+        c->timings.launches[ev.kid] += 1;
+      }
     }
     if (!ev.a_shared) c->event_pool.push_back(ev.a);
     c->event_pool.push_back(ev.b);
@@ -502,6 +524,7 @@ static void fused_drop(shk_ctx *c) {
 }
 int tb_fresh(shk_ctx *c) {
   fused_drop(c);
+  if (c->tb_virtual) return tb_materialise(c);
   if (!c->tb_stale) return SHK_OK;
   c->tb_stale = false;
   return fill_state(c, c->tb, false);
@@ -574,6 +597,10 @@ int grow_to(shk_ctx *c, uint32_t new_log_pages) {
     int rcf = settle(c);
     if (rcf != SHK_OK) return rcf;
     if (new_log_pages <= c->tb.log_pages) return SHK_OK;
+  }
+  if (c->tb_virtual) {  // a virtual table is written before it is rehashed
+    SHK_TRY(tb_fresh(c));
+    if (new_log_pages <= c->tb.log_pages) return SHK_OK;  // (the materialising pass's own settle may have grown it)
   }
   fused_drop(c);
   TableRef nt{};
@@ -679,6 +706,11 @@ int drain_spill(shk_ctx *c, uint64_t spill_cap) {
 }
 
 constexpr uint64_t MAX_SUB_BASES = 1ull << 28;  // bases per counting launch (bounds scratch)
+// (SHK_SUB_KB, test hook: fewer — a small batch as several counting launches; whole tiles, never more than the bound)
+static uint64_t max_sub_bases() {
+  const uint64_t kb = (uint64_t)std::max(env_int("SHK_SUB_KB", (int)(MAX_SUB_BASES >> 10)), TILE_T >> 10);
+  return std::min(MAX_SUB_BASES, (kb << 10) / TILE_T * TILE_T);
+}
 
 // Core ingest over device-resident input.  lane_fixed >= 0: every read to that chunk lane
 // (drain_batch, io.rs:356-358); lane_fixed < 0: stripe by running read index
@@ -687,6 +719,7 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
                 uint64_t n_bases, int64_t lane_fixed, XchgOut *xo = nullptr, uint64_t off_bias = 0) {
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   if (!(xo && xo->late_settle)) SHK_TRY(settle_light(c));  // the previous launch's spill list / scratch must be done with
+  if (c->tb_virtual) SHK_TRY(tb_fresh(c));  // (this batch's records and cursors go where the ones that define the table are)
   c->finalized = c->hist_ready = false;
   c->chain_from_mark = false;
   const uint64_t g0 = c->n_reads_read;
@@ -725,7 +758,8 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
   // the truth is).
   // (a batch of at most MAX_SUB_BASES bases is ONE counting launch even when the partial tiles at its 1000-read
   // block boundaries take the tile count past MAX_SUB_BASES / TILE_T: a second launch would be a second page pass)
-  const uint64_t tiles_per_sub = n_bases <= MAX_SUB_BASES ? std::max<uint64_t>(MAX_SUB_BASES / TILE_T, n_tiles_ub) : MAX_SUB_BASES / TILE_T;
+  const uint64_t sub_bases = max_sub_bases();
+  const uint64_t tiles_per_sub = n_bases <= sub_bases ? std::max<uint64_t>(sub_bases / TILE_T, n_tiles_ub) : sub_bases / TILE_T;
   {
     const uint64_t first_kmers_ub = std::min(tiles_per_sub, n_tiles_ub) * TILE_T;
     int rc = ensure_capacity(c, c->cfg.table_capacity_hint ? 0 : (first_kmers_ub / 4) >> c->owner_bits);
@@ -738,10 +772,10 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
   }
   uint32_t n_cursor_words = 0;
   if (xo && xo->wide) {  // the wide exchange round: no partition cursors at all
-    if (n_tiles_ub > tiles_per_sub) return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)MAX_SUB_BASES);
+    if (n_tiles_ub > tiles_per_sub) return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)sub_bases);
     HIPC(c, c->part_meta.ensure(64));
   } else if (xo) {  // exchange round: level-1 scatter only, every owner's records (shk_xchg_scatter_device)
-    if (n_tiles_ub > tiles_per_sub) return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)MAX_SUB_BASES);
+    if (n_tiles_ub > tiles_per_sub) return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)sub_bases);
     int rc = xchg_prepare_cursors(c, &n_cursor_words);
     if (rc != SHK_OK) return rc;
   } else {
@@ -788,7 +822,9 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
     if (ta) SHK_TRY(settle_light(c));
     int rc = ta ? ensure_capacity(c, c->cfg.table_capacity_hint ? 0 : (sub_kmers_ub / 4) >> c->owner_bits) : SHK_OK;
     if (rc != SHK_OK) return rc;
-    rc = count_tiles(c, b, sub_kmers_ub, /*prezeroed=*/ta == 0);
+    // (a launch that another one of this ingest — or another slice of its host batch — follows writes its table: the
+    // next launch's scatter takes the regions and cursors that would define a virtual one)
+    rc = count_tiles(c, b, sub_kmers_ub, /*prezeroed=*/ta == 0, /*more_follow=*/c->more_slices || ta + tiles_per_sub < n_tiles_ub);
     if (rc != SHK_OK) return rc;
   }
   return SHK_OK;
@@ -1540,12 +1576,20 @@ static bool fused_hist_wanted(const shk_ctx *c) {
   if (rows_bytes > (4ull << 30)) return false;
   return !c->own_set && !c->zero_count_keys && !c->fused_off && env_int("SHK_FUSED_HIST", 1) != 0;
 }
+// The fresh fused pass may leave the table unwritten (tb_virtual): not on a context that has had to write one after
+// all — it goes on writing them with the pass, as fused_off leaves the histogram to the scan.  SHK_LAZY_TABLE, read at
+// every launch: 0 = never, 1 = that, 2 = wherever the pass is fused.
+static bool lazy_table_wanted(const shk_ctx *c) {
+  const int mode = env_int("SHK_LAZY_TABLE", 1);
+  return mode == 2 || (mode != 0 && !c->lazy_off);
+}
 static int fused_hist_prepare(shk_ctx *c, uint32_t n_pages, FusedHist *fh) {
   const uint32_t n_cols = c->cfg.chunks;
   HIPC(c, c->fh_partial.ensure((size_t)n_pages * std::max<uint32_t>(n_cols, 1) * FH_BINS * 4));
-  HIPC(c, c->fh_tot.ensure((size_t)n_pages * 4 * 8));
+  HIPC(c, c->fh_tot.ensure((size_t)n_pages * 5 * 8));  // (+ a word per page: its own spills, histogram-only form)
   fh->partial = (uint32_t *)c->fh_partial.p;
   fh->ptot = (unsigned long long *)c->fh_tot.p;
+  fh->pspill = fh->ptot + (size_t)n_pages * 4;
   fh->hist = c->d_hist;
   fh->histo_max = c->cfg.histo_max;
   fh->n_cols = n_cols;
@@ -1568,19 +1612,28 @@ static void launch_scatter_sorted(shk_ctx *c, bool rec32, uint32_t G, const Batc
 // k_pages32 on the context's stream: `n_blocks` pages from page0 on, chunk lanes [l_lo, l_hi) of each.  fresh: the
 // table's first pass, which writes every page whole; fuse: it leaves the histogram behind (fresh passes only) — over
 // a lane loop (HIST = 1) or, the launch covering ONE lane, without the loop's running sums (HIST = 2).
+// hist_only (with fuse): the form that writes no table (the caller makes the table virtual).
 static void launch_pages32(shk_ctx *c, bool fresh, bool fuse, uint32_t n_blocks, uint32_t page0, uint32_t l_lo, uint32_t l_hi, uint32_t lane_stride,
-                           uint32_t n_regions, const unsigned int *cursor, uint32_t cap, const uint32_t *buf, SpillRef sp, const FusedHist &fh) {
-#define SHK_PG(F, H)                                                                                                                       \
-  hipLaunchKernelGGL((k_pages32<F, H>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, n_regions, cursor, cap, \
+                           uint32_t n_regions, const unsigned int *cursor, uint32_t cap, const uint32_t *buf, SpillRef sp, const FusedHist &fh,
+                           bool hist_only = false) {
+#define SHK_PG(F, H, T)                                                                                                                       \
+  hipLaunchKernelGGL((k_pages32<F, H, T>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, n_regions, cursor, cap, \
                      buf, c->d_stats, sp, page0, fh)
   if (!fresh)
-    SHK_PG(false, 0);
+    SHK_PG(false, 0, true);
   else if (!fuse)
-    SHK_PG(true, 0);
-  else if (l_hi - l_lo == 1)
-    SHK_PG(true, 2);
-  else
-    SHK_PG(true, 1);
+    SHK_PG(true, 0, true);
+  else if (l_hi - l_lo == 1) {
+    if (hist_only)
+      SHK_PG(true, 2, false);
+    else
+      SHK_PG(true, 2, true);
+  } else {
+    if (hist_only)
+      SHK_PG(true, 1, false);
+    else
+      SHK_PG(true, 1, true);
+  }
 #undef SHK_PG
 }
 // k_pages (8-byte records) on the context's stream.  fresh: the table's first page pass — nothing is read, keys and
@@ -1595,7 +1648,7 @@ static void launch_pages64(shk_ctx *c, bool fresh, uint32_t n_blocks, uint32_t p
                        (uint64_t *)c->part2.p, c->d_stats, sp, page0);
 }
 
-static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed, bool defer) {
+static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, SpillRef sp, bool prezeroed, bool defer, bool more_follow) {
   const PartGeom pg = part_geom(c);
   const bool multi = b.tiles != nullptr;
   const PagedRoute r = paged_route(c, pg, multi, defer);
@@ -1695,14 +1748,20 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
       FusedHist fh{};
       const bool fuse = rec32 && fresh && fused_hist_wanted(c);
       if (fuse) SHK_TRY(fused_hist_prepare(c, n_pages, &fh));
+      // (the table holds nothing — it is stale — so the pass's new keys are all the job's: what tb_materialise starts from)
+      const bool lazy = fuse && !more_follow && lazy_table_wanted(c) && c->h_stats->n_distinct == 0;
       ScopedTimer t(c, SHK_K_PAGES, /*chain=*/true);
       if (rec32) {
         launch_pages32(c, fresh, fuse, n_pages, 0u, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cursor, dpg.cap,
-                       (const uint32_t *)dpg.buf, sp, fh);
+                       (const uint32_t *)dpg.buf, sp, fh, lazy);
         if (fresh) {
           c->tb_stale = false;
           c->fused_valid = fuse;
           c->fused_pages = n_pages;
+        }
+        if (lazy) {
+          c->tb_virtual = true;
+          c->vt = {n_pages, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cap, dpg.cursor, (const uint32_t *)dpg.buf, sp.cap};
         }
       } else
         launch_pages64(c, false, n_pages, 0u, lane, lane + 1, 0u, dpg.cursor, dpg.cap, (const uint64_t *)dpg.buf, sp);
@@ -1739,7 +1798,9 @@ static uint64_t acc_records_est(const shk_ctx *c, uint64_t kmers_ub) {
   return std::min<uint64_t>(kmers_ub, share + share / 8 + 65536);
 }
 
-static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, bool prezeroed) {
+static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, bool prezeroed, bool more_follow) {
+  // (whoever plans a launch has been through tb_fresh: this one's scatter overwrites what defines a virtual table)
+  if (c->tb_virtual) return fail(c, SHK_ERR_INVARIANT, "a counting launch behind a virtual table");
   CountPath path = count_path(c, sub_kmers_ub, b.tiles != nullptr);
   if (path == PATH_DEFER) {  // (the first launch of an ingest was planned before k_mark_starts)
     int rc = acc_prepare(c, acc_records_est(c, sub_kmers_ub), b.tiles ? -1 : (int64_t)b.lane0);
@@ -1756,7 +1817,7 @@ static int count_tiles(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, boo
   if (!prezeroed)
     HIPC(c, hipMemsetAsync(&c->d_stats->spill_count, 0, sizeof(unsigned long long), c->stream));
   if (path != PATH_DIRECT) {
-    int rc = paged_count(c, b, sub_kmers_ub, sp, prezeroed, path == PATH_DEFER);
+    int rc = paged_count(c, b, sub_kmers_ub, sp, prezeroed, path == PATH_DEFER, more_follow);
     if (rc != SHK_OK) return rc;
     if (path == PATH_DEFER) {
       c->acc_active = true;
@@ -1962,6 +2023,58 @@ static int settle_light(shk_ctx *c) {
   }
   c->unsettled = false;  // a clean partition launch: nothing to repair, the table was not touched
   return SHK_OK;
+}
+
+// A virtual table written after all: the ordinary fresh pass over the regions and cursors of the launch that left it
+// virtual, and that launch looked at and repaired — the table is then what an eager pass and its settle leave.
+//  - n_distinct: the first pass counted the job's new keys, this one counts them again: back to zero in between (the
+//    table was empty before; which keys spill instead may differ between the two passes — probe races).
+//  - the spill list: the scatter's entries stay (first on the list: the scatter had finished), the first page pass's
+//    go — this pass spills for itself; the counter restarts behind the scatter's.
+// The state changes once the table's contents are on the stream, not before: a step that fails on the way leaves the
+// table virtual, its records and cursors untouched, and the next caller at the door tries again.
+static int tb_materialise(shk_ctx *c) {
+  const auto v = c->vt;
+  if (c->unsettled) SHK_TRY(read_stats(c));
+  if (c->h_stats->bad != ~0ull) {  // the pass counted nothing (an invalid byte: the settle that follows poisons the context)
+    SHK_TRY(fill_state(c, c->tb, false));
+    c->tb_virtual = c->tb_stale = false;
+    c->lazy_off = true;
+    return SHK_OK;
+  }
+  if (c->spillA.cap < v.spill_cap * 16) return fail(c, SHK_ERR_INVARIANT, "spill list of a virtual table's launch missing");
+  unsigned long long keep = 0;
+  if (c->h_stats->spill_count > 0) {
+    std::vector<unsigned long long> ps(v.n_pages);
+    HIPC(c, hipMemcpyAsync(ps.data(), (const unsigned long long *)c->fh_tot.p + (size_t)v.n_pages * 4, (size_t)v.n_pages * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    unsigned long long own = 0;
+    for (auto x : ps) own += x;
+    if (own > c->h_stats->spill_count) return fail(c, SHK_ERR_INVARIANT, "a virtual table's pages spilled %llu of %llu records", own, (unsigned long long)c->h_stats->spill_count);
+    keep = c->h_stats->spill_count - own;
+  }
+  // (from here on the device's counters are no longer the first pass's: a failure leaves a context that neither has
+  // its table nor can have it written again, and says so to every later call)
+  const int rc = [&]() -> int {
+    const unsigned long long w[2] = {0ull, keep};  // DevStats: n_distinct, spill_count
+    static_assert(offsetof(DevStats, spill_count) == offsetof(DevStats, n_distinct) + 8, "one copy for the two");
+    HIPC(c, hipMemcpyAsync(&c->d_stats->n_distinct, w, sizeof w, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));  // (`w` lives on this stack)
+    ScopedTimer t(c, K_MATERIALISE);
+    launch_pages32(c, true, false, v.n_pages, 0u, v.l_lo, v.l_hi, v.lane_stride, v.n_regions, v.cursor, v.cap, v.buf, spill_ref(c->spillA, v.spill_cap), FusedHist{});
+    HIPC(c, hipGetLastError());
+    return SHK_OK;
+  }();
+  if (rc != SHK_OK) {
+    c->poisoned = true;
+    c->poison_code = rc;
+    return rc;
+  }
+  c->tb_virtual = false;
+  c->lazy_off = true;
+  c->unsettled = true;
+  c->unsettled_spill_cap = v.spill_cap;
+  return settle(c);
 }
 
 #include "shk_group.hip.h"
@@ -2192,6 +2305,7 @@ int shk_reset(shk_ctx *c) {
     int rc = fill_state(c, env_int("SHK_NO_FRESH", 0) ? c->tb : none, true);
     if (rc != SHK_OK) return rc;
     c->tb_stale = !env_int("SHK_NO_FRESH", 0);
+    c->tb_virtual = false;  // (the job's records are never replayed: the table they define goes with the job)
     c->hist_dirty = false;
     c->fused_valid = false;
   }
@@ -2522,8 +2636,10 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
                          (const uint8_t *)c->pk_stage[bsel].p, (uint32_t)(o0 & 3), (const uint32_t *)c->nm_stage[bsel].p,
                          (uint32_t)(o0 & 31), nb, (uint8_t *)db.p);
     }
+    c->more_slices = i + 1 < n_slices;  // (a table the next slice is about to need is written by this slice's pass)
     rc = ingest_core(c, (const uint8_t *)db.p, (const uint64_t *)dof.p, r1 - r0, offsets[r1] - offsets[r0],
                      lane_fixed, nullptr, offsets[r0]);
+    c->more_slices = false;
     if (rc != SHK_OK) {
       (void)hipStreamSynchronize(c->copy_stream);  // do not leave a copy reading `rebased` behind
       return rc;
@@ -2932,6 +3048,7 @@ int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, cons
   SHK_TRY(single_device_only(c));
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   HIPC(c, hipSetDevice(c->cfg.device));
+  if (c->tb_virtual) SHK_TRY(tb_fresh(c));  // (the list's level-1 pass takes the buffers that define a virtual table)
   if (d_kmers && insert_list_paged_ok(c, d_counts, n) && (d_lanes || c->n_lanes == 1)) {
     fused_drop(c);
     c->finalized = c->hist_ready = false;
@@ -3242,6 +3359,27 @@ int shk_get_timings(shk_ctx *c, shk_timings *o) {
   return SHK_OK;
 }
 
+int shk_get_lazy_table_timing(shk_ctx *c, double *ms, uint64_t *launches) {
+  if (!c) return SHK_ERR_BAD_ARG;
+  double m = 0;
+  uint64_t n = 0;
+  if (c->group) {  // summed over the devices
+    for (uint32_t d = 0; d < c->group->D; ++d) {
+      double md = 0;
+      uint64_t nd = 0;
+      (void)shk_get_lazy_table_timing(c->group->ctx[d], &md, &nd);
+      m += md, n += nd;
+    }
+  } else {
+    (void)hipSetDevice(c->cfg.device);
+    resolve_timings(c);
+    m = c->lazy_ms, n = c->lazy_launches;
+  }
+  if (ms) *ms = m;
+  if (launches) *launches = n;
+  return SHK_OK;
+}
+
 int shk_reset_timings(shk_ctx *c) {
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) {
@@ -3251,6 +3389,8 @@ int shk_reset_timings(shk_ctx *c) {
   (void)hipSetDevice(c->cfg.device);
   resolve_timings(c);
   memset(&c->timings, 0, sizeof c->timings);
+  c->lazy_ms = 0;
+  c->lazy_launches = 0;
   c->job_idx = 0;
   c->timing_now = true;
   return SHK_OK;

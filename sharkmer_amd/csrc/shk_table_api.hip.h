@@ -861,6 +861,8 @@ int shk_compact_owners_fixed(shk_ctx *c, uint32_t n_owners, uint64_t capacity, v
   // (Otherwise nothing is waited for: a counting launch nobody has looked at yet may have spilled records, in which
   // case the table read here is incomplete — k_piece_headers sees that on the device and poisons every header, no
   // rank merges anything, and the finalize that follows repairs the table before the exchange is repeated.)
+  // (One exception: a table left virtual by the last launch is written here, and that does wait — the launch is looked
+  // at, the materialising pass runs and is settled.  Once per context at the most: it writes its tables eagerly after.)
   SHK_TRY(tb_fresh(c));
   HIPC(c, c->h_rebased[0].ensure((size_t)n_owners * 16));
   uint64_t *h = (uint64_t *)c->h_rebased[0].p;
@@ -907,7 +909,7 @@ int shk_merge_pieces(shk_ctx *c, const void *d_buf, uint32_t n_pieces, uint64_t 
 static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride,
                         uint64_t piece_cap, uint32_t skip_piece) {
   HIPC(c, hipSetDevice(c->cfg.device));
-  SHK_TRY(tb_fresh(c));
+  SHK_TRY(tb_fresh(c));  // (a virtual table is written and settled here: a host round trip, once per context at the most)
   // (Not table_read_begin: the settle depends on ride_on.)
   // Fixed-capacity pieces behind a counting launch nobody has looked at yet: nothing is waited for.  If that
   // launch spilled, the senders' headers are poisoned and k_merge touches nothing; if not, what the merge spills

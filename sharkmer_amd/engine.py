@@ -220,7 +220,7 @@ class _Synth(C.Structure):
 ABI_SYMBOLS = [
     "shk_abi_version", "shk_create", "shk_destroy", "shk_reset", "shk_last_error", "shk_ingest_batch",
     "shk_ingest_reads", "shk_set_read_index", "shk_ingest_reads_device", "shk_insert_counts", "shk_sync", "shk_finalize",
-    "shk_histograms", "shk_get_counters", "shk_get_timings", "shk_reset_timings",
+    "shk_histograms", "shk_get_counters", "shk_get_timings", "shk_reset_timings", "shk_get_lazy_table_timing",
     "shk_export_table", "shk_lookup", "shk_find_oligos", "shk_primer_compile", "shk_primer_kmers", "shk_filter_reads", "shk_kmers_from_reads", "shk_table_geometry", "shk_table_reserve_pages", "shk_owner_counts", "shk_compact_owners",
     "shk_merge_entries",
     "shk_table_device_ptrs", "shk_merge_pages", "shk_set_owned_pages", "shk_alloc_pinned",
@@ -348,6 +348,7 @@ def load_library():
     L.shk_get_counters.argtypes = [vp, C.POINTER(_Counters)]
     L.shk_get_timings.argtypes = [vp, C.POINTER(_Timings)]
     L.shk_reset_timings.argtypes = [vp]
+    L.shk_get_lazy_table_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.shk_export_table.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.shk_lookup.argtypes = [vp, vp, vp, u64, C.c_int]
     L.shk_find_oligos.argtypes = [vp, vp, u32, u32, u32, vp, vp, u64, C.POINTER(u64)]
@@ -586,8 +587,13 @@ class KmerEngine:
     def timings(self) -> dict:
         t = _Timings()
         self._check(self._L.shk_get_timings(self._h, C.byref(t)))
-        return {KERNEL_NAMES[i]: (float(t.ms[i]), int(t.launches[i]))
-                for i in range(len(KERNEL_NAMES)) if t.launches[i]}
+        out = {KERNEL_NAMES[i]: (float(t.ms[i]), int(t.launches[i]))
+               for i in range(len(KERNEL_NAMES)) if t.launches[i]}
+        ms, n = C.c_double(0), C.c_uint64(0)   # the materialising pass of a lazily written table: beside shk_timings
+        self._check(self._L.shk_get_lazy_table_timing(self._h, C.byref(ms), C.byref(n)))
+        if n.value:
+            out["materialise"] = (float(ms.value), int(n.value))
+        return out
 
     def reset_timings(self):
         self._check(self._L.shk_reset_timings(self._h))
