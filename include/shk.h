@@ -140,7 +140,7 @@ enum {
   SHK_K_PCOUNT = 12,   /* validate + count k-mers per partition (k_part_count) */
   SHK_K_PSCAN = 13,    /* the two small exclusive scans between count and scatter */
   SHK_K_HISTO_ROWS = 14, /* histograms + totals from the rows the (one) fresh page pass of a job left behind, instead of SHK_K_HISTO's scan */
-  SHK_K_EXTEND = 15    /* shk_neighborhood(_panel): seed, narrow and wide level launches */
+  SHK_K_EXTEND = 15    /* shk_neighborhood(_panel): seed, narrow and wide level launches, a panel's pack */
 };
 
 /* ---- lifecycle ------------------------------------------------------------ */
@@ -369,9 +369,11 @@ int shk_kmers_from_reads(shk_ctx *ctx, const uint8_t *bases, const uint64_t *off
  *   graph whose branch nodes have more than 2^31 (incoming, outgoing) pairs between them — every such pair has a
  *   counter of its own on the device.
  * The context's table is neither read nor written; valid whenever shk_filter_reads is, on owner shares too; a
- * multi-device context runs it on its first device.  Tuning: SHK_THREAD_LDS_EDGES (edges, read at each call; default
- * 2048): graphs up to that size keep their lookup set in LDS, larger ones in global memory; the result does not depend
- * on it. */
+ * multi-device context runs it on its first device.  The call is shk_thread_reads_panel (below) for one gene that lists
+ * every read of the batch in the batch's order — the same launch, with no list uploaded.  Tuning, all read at each
+ * call, none changes the result: SHK_THREAD_LDS_EDGES (edges; default 2048): graphs up to that size keep their lookup
+ * set in LDS, larger ones in global memory; SHK_THREAD_PANEL_JOB and SHK_THREAD_PANEL_BLOCKS cut this call's batch and
+ * cap its workgroups as they do a panel's.  With SHK_TRACE set the launch prints the panel's line (1 genes). */
 typedef struct shk_thread_out {   /* every pointer optional except the two support arrays */
   uint32_t *support_total;        /* [n_edges] EdgeReadSupport.read_support_total        */
   uint32_t *support_unambiguous;  /* [n_edges] EdgeReadSupport.read_support_unambiguous  */
@@ -424,7 +426,8 @@ int shk_thread_reads_device(shk_ctx *ctx, const uint64_t *node_sub_kmers, uint64
  * multi-device context runs it on its first device.  Tuning, all read at each call, none changes the result:
  * SHK_THREAD_LDS_EDGES decides per gene, as for shk_thread_reads, whether the gene's set goes to LDS;
  * SHK_THREAD_PANEL_JOB (reads, default 16): every list is cut into slices of at most that many reads, the jobs the
- * workgroups share out; SHK_THREAD_PANEL_BLOCKS (0 = the rule of shk_thread_reads) caps the workgroups. */
+ * workgroups share out; SHK_THREAD_PANEL_BLOCKS (0 = a wave per listed read up to the device's workgroups) caps the
+ * workgroups.  Both hold for shk_thread_reads[_device] too, which is this call with one gene. */
 #define SHK_THREAD_MAX_GENES 4096   /* = SHK_FILTER_MAX_GENES: the lists come from that call */
 typedef struct shk_thread_panel_out {  /* every pointer optional except the two support arrays */
   uint32_t *support_total;        /* [edge_offsets[n_genes]] gene g's edges at edge_offsets[g] ..            */
@@ -510,7 +513,9 @@ int shk_gather_reads_device(shk_ctx *ctx, const void *d_bases, const void *d_off
  * report k-mers and entries again that an earlier call reported).  A deterministic function of table and arguments.
  * Errors: dir 0 or > 3, a node > mask, more distinct seeds than fringe_cap: SHK_ERR_BAD_ARG; a multi-device context
  * or an owner share (a neighbour's count may live on another share): SHK_ERR_STATE.  Valid whenever shk_lookup is;
- * the table is not touched.  cap, fringe_cap ≤ 2^32; the device scratch is about 100 bytes per unit of cap. */
+ * the table is not touched.  cap, fringe_cap ≤ 2^32; the device scratch is about 100 bytes per unit of cap.  The call
+ * is one job of shk_neighborhood_panel (below): the same kernels and scratch layout, its lists fetched from the job's
+ * own arrays instead of a packed copy. */
 int shk_neighborhood(shk_ctx *ctx, const uint64_t *nodes, const uint8_t *dirs, uint64_t n_seeds,
                      uint32_t min_count, uint32_t max_levels,
                      uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
@@ -536,8 +541,10 @@ typedef struct shk_pcr_extend_params {
  * an error (do_pcr returns before, mod.rs:446-468): the other set's seeds are extended and no path is found.
  * node_cap / edge_cap too small: SHK_ERR_BAD_ARG with *n_nodes / *n_edges set to what is needed.  A k-mer counts
  * when its merged count ≥ max(threshold, table_min_count, 1).  Multi-device contexts and owner shares:
- * SHK_ERR_STATE, as shk_neighborhood.  Tuning: SHK_PCR_FETCH_CAP (k-mers, read at each call) bounds one
- * shk_neighborhood fetch; the result does not depend on it. */
+ * SHK_ERR_STATE, as shk_neighborhood.  The call is shk_pcr_extend_panel (below) for one gene, replayed on the calling
+ * thread; a host allocation that fails in the replay is SHK_ERR_NOMEM.  Tuning: SHK_PCR_FETCH_CAP (k-mers, read at
+ * each call) bounds one neighbourhood fetch; the result does not depend on it.  The panel's own knobs
+ * (SHK_PCR_PANEL_FETCH_CAP, SHK_PCR_PANEL_THREADS, SHK_PCR_PANEL_TRACE) do not apply to this call. */
 int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
                    const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev,
                    const shk_pcr_extend_params *p,
@@ -548,7 +555,7 @@ int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_
  * of a panel asks for the neighbourhood of its own queue at its own threshold (extend_graph, src/pcr/graph.rs:377-525,
  * once per gene of stats.rs:85-87).  Each job is carried through its levels by one workgroup of its own (a chain is as
  * deep as the amplicon is long and about one entry wide), so a panel's chains run side by side in the time of the
- * longest; a job whose level outgrows a workgroup is finished alone afterwards, as shk_neighborhood would.
+ * longest; a job whose level outgrows a workgroup is finished alone afterwards, a wide launch per level.
  * LAYOUT: job j's seeds are nodes/dirs[seed_offsets[j] .. seed_offsets[j+1]) (n_jobs + 1 offsets, non-decreasing); its
  *   k-mers and counts are written from index caps[0] + … + caps[j−1] of kmers/counts, its fringe from index
  *   fringe_caps[0] + … + fringe_caps[j−1] of fringe_nodes/fringe_dirs; n_out[j], n_fringe[j], levels_done[j].

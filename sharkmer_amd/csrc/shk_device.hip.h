@@ -1316,7 +1316,8 @@ __global__ void __launch_bounds__(WG) k_export(TableRef tb, uint64_t slot0, uint
 }
 
 // ==========================================================================================
-// K_EXTEND: the bulk neighbourhood of a seed set (shk_neighborhood), the table side of sPCR's graph extension
+// K_EXTEND: the bulk neighbourhoods of many seed sets side by side (shk_neighborhood_panel; shk_neighborhood is its
+// one-job case and runs the same kernels), the table side of sPCR's graph extension
 // (extend_graph, src/pcr/graph.rs:377-525): breadth-first over (node, dir) entries — a node is a (k−1)-mer, dir 0
 // extends it forward ((node << 2) | b), dir 1 backward ((b << 2(k−1)) | node) — where an entry's four candidate
 // k-mers are looked up in the merged table and the accepted ones (merged count ≥ min_count) lead to the next level.
@@ -1327,11 +1328,11 @@ __global__ void __launch_bounds__(WG) k_export(TableRef tb, uint64_t slot0, uint
 // Fills past a list's capacity are counted but not written; the level then did not fit and the host drops it (the
 // k-mer list is cut back to its fill at the level's start, the entry list of the level itself is untouched).
 // ==========================================================================================
-constexpr int NB_WG = 1024;            // k_nb_narrow: one workgroup
+constexpr int NB_WG = 1024;            // k_nb_narrow_panel: one workgroup per job
 constexpr uint32_t NB_NARROW = 1024;   // … carries a level of up to this many entries
 constexpr uint32_t NB_RUN = 0, NB_COMPLETE = 1, NB_LIMIT = 2, NB_OVERFLOW = 3, NB_WIDE = 4;
 
-struct NbCtl {                 // host ↔ device state of one shk_neighborhood call (of one job of a panel call)
+struct NbCtl {                 // host ↔ device state of one job
   unsigned long long k_n;      // accepted k-mers appended so far
   unsigned long long next_n;   // entries of the level under construction (counted past fringe_cap)
   unsigned long long cur_n;    // entries of the current (unexpanded) level
@@ -1364,8 +1365,8 @@ __device__ __forceinline__ int nb_set_insert(uint64_t *set, uint64_t mask, uint6
   return -1;
 }
 
-// One (entry, base) pair of the current level.  k_n / next_n: the two fill counters (LDS in k_nb_narrow, the control
-// block in k_nb_wide); lds_next: where k_nb_narrow keeps the first NB_NARROW entries of the next level.
+// One (entry, base) pair of the current level.  k_n / next_n: the two fill counters (LDS in k_nb_narrow_panel, the control
+// block in k_nb_wide); lds_next: where k_nb_narrow_panel keeps the first NB_NARROW entries of the next level.
 __device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, uint64_t entry, uint32_t b,
                                           uint64_t *next_list, unsigned long long *k_n, unsigned long long *next_n,
                                           uint32_t *set_full, uint64_t *lds_next) {
@@ -1396,13 +1397,6 @@ __device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, u
   if (lds_next && at < NB_NARROW) lds_next[at] = succ;
 }
 
-// Level 0 into the visited set.
-__global__ void __launch_bounds__(WG) k_nb_seed(NbRef nb, uint64_t n, NbCtl *ctl) {
-  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
-  if (i >= n) return;
-  if (nb_set_insert(nb.vis, nb.vis_mask, nb.list[0][i]) < 0) atomicOr(&ctl->set_full, 1u);
-}
-
 // WIDE: one level per launch, one thread per (entry, base); the host reads the two fills back and decides.
 __global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ctl, uint32_t cur_sel, uint64_t cur_n) {
   const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
@@ -1415,7 +1409,7 @@ __global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ct
 // the two entry lists and the fill counters in LDS, a workgroup barrier between levels, no host round trip.  It
 // stops with ctl->status = why: the neighbourhood is complete, max_levels reached, the next level did not fit the
 // caller's capacities (ctl then describes the level before it), or it is too wide for one workgroup (k_nb_wide's).
-// (The level loop itself: k_nb_narrow runs it for the one job of shk_neighborhood, k_nb_narrow_panel for its own job.)
+// (The level loop itself; k_nb_narrow_panel runs it for its job.)
 __device__ __forceinline__ void nb_narrow_levels(const TableRef &tb, const NbRef &nb, NbCtl *ctl) {
   __shared__ uint64_t s_list[2][NB_NARROW];
   __shared__ unsigned long long s_kn, s_kstart, s_nextn, s_curfull;  // s_curfull: the current level's size, s_curn capped
@@ -1433,12 +1427,13 @@ __device__ __forceinline__ void nb_narrow_levels(const TableRef &tb, const NbRef
   }
   __syncthreads();
   const uint32_t sel0 = s_sel;
-  for (uint32_t i = tid; i < s_curn; i += NB_WG) s_list[sel0][i] = nb.list[sel0][i];
+  const uint64_t *list0 = sel0 ? nb.list[1] : nb.list[0];  // (a select, not an index: nb stays in registers)
+  for (uint32_t i = tid; i < s_curn; i += NB_WG) s_list[sel0][i] = list0[i];
   __syncthreads();
   while (true) {
     const uint32_t sel = s_sel, cur_n = s_curn;
     for (uint32_t t = tid; t < cur_n * 4; t += NB_WG)
-      nb_expand(tb, nb, s_list[sel][t >> 2], t & 3, nb.list[sel ^ 1], &s_kn, &s_nextn, &s_full, s_list[sel ^ 1]);
+      nb_expand(tb, nb, s_list[sel][t >> 2], t & 3, sel ? nb.list[0] : nb.list[1], &s_kn, &s_nextn, &s_full, s_list[sel ^ 1]);
     __syncthreads();
     if (tid == 0) {
       if (s_full || s_kn > nb.cap || s_nextn > nb.fringe_cap) {
@@ -1473,10 +1468,8 @@ __device__ __forceinline__ void nb_narrow_levels(const TableRef &tb, const NbRef
   }
 }
 
-__global__ void __launch_bounds__(NB_WG) k_nb_narrow(TableRef tb, NbRef nb, NbCtl *ctl) { nb_narrow_levels(tb, nb, ctl); }
-
-// PANEL (shk_neighborhood_panel): many independent jobs side by side, each with its own NbRef (two sets, two entry
-// lists, k-mer list) and NbCtl in device arrays.  Nothing is shared between jobs and no workgroup waits for another:
+// The jobs: many independent ones side by side, each with its own NbRef (two sets, two entry lists, k-mer list) and
+// NbCtl in device arrays.  Nothing is shared between jobs and no workgroup waits for another:
 // jobs beyond what the card holds at once queue behind the others.
 //
 // Level 0 of every job in one launch: seed i (the jobs' sorted seed lists back to back) belongs to job seed_job[i],
@@ -1493,13 +1486,15 @@ __global__ void __launch_bounds__(WG) k_nb_seed_panel(const NbRef *__restrict__ 
   if (nb_set_insert(refs[j].vis, refs[j].vis_mask, e) < 0) atomicOr(&ctls[j].set_full, 1u);
 }
 
-// One workgroup per job, blockIdx.x the job: k_nb_narrow's level loop on the job's own NbRef / NbCtl.  A job that is
+// One workgroup per job, blockIdx.x the job: the narrow level loop on the job's own NbRef / NbCtl.  A job that is
 // not there to be run — no seeds (NB_COMPLETE from the host) or a level 0 too wide for a workgroup (NB_WIDE) — is left
-// as it is; the host takes the wide ones on afterwards, one at a time.
+// as it is; the host takes the wide ones on afterwards, one at a time (k_nb_wide per level, and this kernel with a grid
+// of 1 on the job's own pair when a level fits a workgroup again).
 __global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel(TableRef tb, const NbRef *__restrict__ refs, NbCtl *ctls) {
   NbCtl *ctl = &ctls[blockIdx.x];
   if (ctl->status != NB_RUN || ctl->cur_n == 0 || ctl->cur_n > NB_NARROW) return;  // (the same for every thread: ctl is written at the end only)
-  nb_narrow_levels(tb, refs[blockIdx.x], ctl);  // (read in place: a private copy, indexed by list, would live in scratch)
+  const NbRef nb = refs[blockIdx.x];  // (a private copy: scalar loads once, not after every atomic of the level loop)
+  nb_narrow_levels(tb, nb, ctl);
 }
 
 // What a job hands back, packed: its k_n k-mers and counts from pack_k, its n_f fringe entries (the unexpanded level,
@@ -1820,7 +1815,7 @@ __global__ void __launch_bounds__(WG) k_kmers_from_reads(const uint8_t *__restri
 
 // ==========================================================================================
 // K_THREAD: thread_reads (src/pcr/threading.rs:87-192) for a batch of reads against a graph given as a lookup set
-// the host built (shk_thread_reads).  One WAVE per read, THREAD_TILE = 64 window start positions per
+// the host built (shk_thread_reads; the kernel is k_thread_panel below).  One WAVE per read, THREAD_TILE = 64 window start positions per
 // step, one per lane:
 //   bases      64 new bytes per step as bit planes (read_planes), each lane's window and key from them (window_key).  A
 //              window with an N is no list element (encoding.rs:346-352): its lane sits out, and "the previous element"
@@ -1839,8 +1834,9 @@ __global__ void __launch_bounds__(WG) k_kmers_from_reads(const uint8_t *__restri
 // sweep only writes (edge, flags | link slot) per position to the wave's scratch, and a second sweep, last step
 // first, carrying "a branch pair between here and the run's end" (suf) the other way, does every atomic: support_total
 // per element, support_unambiguous when neither pre nor suf, the link's slot per branch pair.
-// LDS = true: the whole set lies in LDS (copied by every workgroup once; it then walks many reads) and the two
-// support counters are LDS-private, flushed at the end; false: the same code over the global arrays.
+// A graph's set lies in LDS (copied by a workgroup once; it then walks many reads) with the two support counters
+// LDS-private, flushed when the workgroup lets go of the graph — or it stays in global memory: the same code over the
+// global arrays.
 // ==========================================================================================
 constexpr int THREAD_WG = 1024;                    // 16 waves: one workgroup per CU when the set fills its LDS
 constexpr uint32_t THREAD_TILE = 64;               // list elements per wave step (engine.py mirrors it as THREAD_TILE)
@@ -1849,11 +1845,7 @@ static_assert(THREAD_TILE == 64, "one window per lane of a wave");
 constexpr int THREAD_LDS_EDGES = 2048;             // graphs up to this many edges keep their set in LDS (SHK_THREAD_LDS_EDGES) …
 constexpr size_t THREAD_LDS_MAX = 128u << 10;      // … if it fits this much of a CU's 160 KiB (2048 edges: at most 104.3 KiB)
 
-struct ThreadSet {
-  KeyRuns runs;       // canonical edge k-mer → its candidates: the edges, ascending by (key, edge)
-  const uint4 *meta;  // [runs.n_items] {src, tgt, link slot base of the pairs (e, ·) or TH_NONE, rank of e among its source's out-edges}
-};
-// bytes of LDS of k_thread_reads<true>, in its order: meta, the key runs, the two private counters
+// bytes of LDS of a graph whose set k_thread_panel keeps there, in its order: meta, the key runs, the two private counters
 __host__ __device__ inline size_t thread_lds_bytes(uint32_t cap, uint32_t n_edges) {
   return (size_t)n_edges * 16 + key_runs_bytes(cap, n_edges) + (size_t)n_edges * 8;
 }
@@ -1861,14 +1853,14 @@ __host__ __device__ inline size_t thread_lds_bytes(uint32_t cap, uint32_t n_edge
 // A graph in front of the walk of one read: its set and meta, in LDS or in global memory, and its counters — the
 // two supports where the kernel keeps them (LDS-private or global), the link slots always global.
 struct ThreadView {
-  KeyRuns runs;
-  const uint4 *meta;
+  KeyRuns runs;       // canonical edge k-mer → its candidates: the edges, ascending by (key, edge)
+  const uint4 *meta;  // [runs.n_items] {src, tgt, link slot base of the pairs (e, ·) or TH_NONE, rank of e among its source's out-edges}
   uint32_t *total, *unamb, *links;
 };
 
 // The walk of ONE read by one wave — both sweeps, from its first bytes to its last atomic (see K_THREAD above): rb, len
 // the read, scr the wave's scratch (one entry per window of the read) → the edges the read was mapped to (read_edges).
-// The one copy of the walk: k_thread_reads and k_thread_panel both call it, each with its own view.
+// k_thread_panel calls it with the view of the gene it holds.
 __device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const uint8_t *__restrict__ rb, uint32_t len, int k, uint2 *__restrict__ scr,
                                                 uint32_t lane) {
   const uint32_t km = (1u << k) - 1u;         // k ≤ 31
@@ -1971,51 +1963,15 @@ __device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const uint8
   return n_hit;
 }
 
-template <bool LDS>
-__global__ void __launch_bounds__(THREAD_WG) k_thread_reads(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
-                                                            uint64_t n_seqs, int k, ThreadSet gs, uint2 *__restrict__ scratch,
-                                                            uint32_t scr_stride, uint32_t *__restrict__ total,
-                                                            uint32_t *__restrict__ unamb, uint32_t *__restrict__ links,
-                                                            uint32_t *__restrict__ read_edges) {
-  extern __shared__ __align__(16) uint8_t th_lds[];
-  const uint32_t E = gs.runs.n_items;
-  uint4 *lm = (uint4 *)th_lds;  // (the uint4 array first: see key_runs_bytes)
-  uint32_t *lt = (uint32_t *)(th_lds + (size_t)E * 16 + key_runs_bytes(gs.runs.mask + 1, E)), *lu = lt + E;
-  KeyRuns ks = gs.runs;
-  if (LDS) {
-    ks = key_runs_to_lds(gs.runs, th_lds + (size_t)E * 16, THREAD_WG);
-    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) lm[i] = gs.meta[i], lt[i] = 0, lu[i] = 0;
-    __syncthreads();
-  }
-  const ThreadView view{ks, LDS ? lm : gs.meta, LDS ? lt : total, LDS ? lu : unamb, links};
-
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (uint64_t)blockIdx.x * (THREAD_WG / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t n_waves = (uint64_t)gridDim.x * (THREAD_WG / 64);
-  uint2 *scr = scratch + wave * scr_stride;
-
-  for (uint64_t r = wave; r < n_seqs; r += n_waves) {
-    const uint64_t b0 = offsets[r];
-    const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
-    if (read_edges && lane == 0) read_edges[r] = n_hit;
-  }
-  if (LDS) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < E; i += THREAD_WG) {
-      if (lt[i]) atomicAdd(&total[i], lt[i]);
-      if (lu[i]) atomicAdd(&unamb[i], lu[i]);
-    }
-  }
-}
-
-// k_thread_panel: the same walk for a whole sPCR panel in one launch (shk_thread_reads_panel).  The host
+// k_thread_panel: the walk for a whole sPCR panel in one launch (shk_thread_reads_panel; shk_thread_reads
+// is the panel of one gene that lists every read).  The host
 // concatenates every gene's set into one upload and describes each gene in a ThreadGene; the genes' read lists, cut
 // into slices, are the JOBS, in (gene, slice) order.  Workgroups are persistent: each walks a contiguous range of jobs
 // and so holds one gene at a time — its set in LDS with LDS-private supports, or pointers to the global arrays.  At a job
 // of another gene: a barrier (no wave is still walking), the held gene's private supports flushed (one global atomic
 // per touched edge), a barrier (nobody still reads what the load overwrites), the new gene loaded, a barrier.  Inside a
-// job wave w takes the slice's reads w, w + 16, …: list position → list_reads → offsets → bytes; read_edges is written
-// at the list position.  No workgroup reads what another wrote: counters meet in global atomics and the host reads
+// job wave w takes the slice's reads w, w + 16, …: list position → list_reads → offsets → bytes (list_reads == nullptr:
+// list position i is read i); read_edges is written at the list position.  No workgroup reads what another wrote: counters meet in global atomics and the host reads
 // them after the launch.
 struct ThreadGene {              // 64 bytes
   uint64_t keys, start, items, last, meta;  // byte offsets of the gene's arrays within the upload (16-byte aligned each)
@@ -2047,7 +2003,7 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__res
                                                             const uint8_t *__restrict__ upload, int k, uint2 *__restrict__ scratch,
                                                             uint32_t scr_stride, uint32_t *__restrict__ total, uint32_t *__restrict__ unamb,
                                                             uint32_t *__restrict__ links, uint32_t *__restrict__ read_edges) {
-  extern __shared__ __align__(16) uint8_t th_lds[];  // laid out per gene as k_thread_reads<true> lays it out (thread_lds_bytes)
+  extern __shared__ __align__(16) uint8_t th_lds[];  // the held gene's meta, key runs and two private supports (thread_lds_bytes)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint2 *scr = scratch + ((uint64_t)blockIdx.x * (THREAD_WG / 64) + wib) * scr_stride;
@@ -2083,7 +2039,6 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__res
       __syncthreads();
     }
     uint32_t *re = read_edges + job.first;
-    const uint64_t *ids = list_reads + job.first;
     if (g.lds) {
       const uint32_t E = g.n_edges, cap = g.mask + 1;
       uint8_t *kb = th_lds + (size_t)E * 16;  // key_runs_to_lds' layout
@@ -2091,14 +2046,14 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__res
       const ThreadView view{KeyRuns{(const uint64_t *)kb, ls, ls + cap, ls + cap + E, g.mask, E}, (const uint4 *)th_lds, lt, lt + E,
                             links + g.link_base};
       for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
-        const uint64_t r = ids[i], b0 = offsets[r];
+        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i, b0 = offsets[r];
         const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
         if (lane == 0) re[i] = n_hit;
       }
     } else {
       const ThreadView view = thread_view_global(g, upload, total, unamb, links);
       for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
-        const uint64_t r = ids[i], b0 = offsets[r];
+        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i, b0 = offsets[r];
         const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
         if (lane == 0) re[i] = n_hit;
       }

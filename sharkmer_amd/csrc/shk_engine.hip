@@ -290,7 +290,7 @@ struct shk_ctx {
   hipEvent_t copy_done[NST] = {};
   int stage_last = -1;            // the staging set the last slice of the previous host-buffer ingest took (its count may still be in flight)
   bool zero_count_keys = false;   // some key may have been inserted with count 0 (shk_insert_counts, merges): k_histo reads the keys
-  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter64 = false, lds_attr_thread = false, lds_attr_thread_panel = false, lds_attr_filter = false, lds_attr_prune = false;  // hipFuncSetAttribute done for this context's device
+  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter64 = false, lds_attr_thread_panel = false, lds_attr_filter = false, lds_attr_prune = false;  // hipFuncSetAttribute done for this context's device
   HostBuf h_rebased[NST];           // pinned staging of a slice's re-based offsets (a pageable source would make the copy synchronous)
   DevBuf in_bases, in_offsets, st_bases[NST], st_offsets[NST], startbits, tiles, spillA, spillB, misc, part, part2, part3, part_meta;
   DevBuf pk_stage[NST], nm_stage[NST], nz_dev[NST], pk_ascii;

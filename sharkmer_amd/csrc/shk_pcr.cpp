@@ -1,4 +1,4 @@
-// shk_pcr.cpp — sPCR's graph extension replayed on the host over counts fetched in bulk (shk_neighborhood).
+// shk_pcr.cpp — sPCR's graph extension replayed on the host over counts fetched in bulk (shk_neighborhood_panel).
 //
 // extend_graph (src/pcr/graph.rs:321-528) asks the table for four k-mer counts per node and decides in FIFO order:
 // the decisions depend on the order, the counts do not.  So the counts are fetched ahead — the neighbourhood of
@@ -8,9 +8,9 @@
 // treats like absence.  When the loop reaches an entry whose expansion it does not hold yet (the fetch was cut by its
 // capacities, or a cap was small), it fetches again from what is in the queue then.
 //
-// The loop is a state object (Extension) that stops where it needs a fetch and is taken up again after it: one gene
-// fetches with shk_neighborhood and goes on; a panel's genes run side by side, and what they need goes to the device
-// in one shk_neighborhood_panel call per round.
+// The loop is a state object (Extension) that stops where it needs a fetch and is taken up again after it: a panel's
+// genes run side by side, and what they need goes to the device in one shk_neighborhood_panel call per round.  One gene
+// (shk_pcr_extend) is a panel of one, replayed on the calling thread.
 #include "shk_pcr.h"
 
 #include <algorithm>
@@ -308,43 +308,6 @@ std::vector<uint32_t> pcr_coverage_thresholds(uint32_t primer_count, uint32_t mi
   return t;
 }
 
-int pcr_extend_run(shk_ctx *ctx, uint32_t k, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
-                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev,
-                   const shk_pcr_extend_params &p, PcrGraph *out, uint32_t *threshold_used, uint32_t *steps_run,
-                   std::string *err) {
-  GeneSweep gs;
-  gs.init(k, fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev, p);
-  const uint64_t fetch_cap = env_u64("SHK_PCR_FETCH_CAP", 0);  // 0: sized by the replay's room
-  std::vector<uint64_t> nodes, kmers, fnodes;
-  std::vector<uint8_t> dirs, fdirs;
-  std::vector<uint32_t> counts;
-  for (gs.advance(); !gs.done; gs.advance()) {
-    const std::vector<uint64_t> &seeds = gs.ex.seeds;
-    const uint64_t n = seeds.size();
-    // level 0 always fits 4 k-mers and 4 successors per entry: every fetch gets at least one level further
-    const uint64_t cap = std::max<uint64_t>(fetch_cap ? fetch_cap : gs.ex.room, 4 * n);
-    nodes.resize(n), dirs.resize(n), kmers.resize(cap), counts.resize(cap), fnodes.resize(cap), fdirs.resize(cap);
-    for (uint64_t i = 0; i < n; ++i) {
-      nodes[i] = seeds[i] >> 1;
-      dirs[i] = (uint8_t)(1u << (seeds[i] & 1));
-    }
-    uint64_t n_out = 0, n_fringe = 0;
-    uint32_t levels = 0;
-    const int rc = shk_neighborhood(ctx, nodes.data(), dirs.data(), n, gs.ex.cn.accept, 0, kmers.data(), counts.data(), cap,
-                                    &n_out, fnodes.data(), fdirs.data(), cap, &n_fringe, &levels);
-    if (rc != SHK_OK) return rc;
-    if (levels == 0) {
-      *err = "shk_pcr_extend: a neighbourhood fetch made no progress";
-      return SHK_ERR_INVARIANT;
-    }
-    gs.answer(kmers.data(), counts.data(), n_out, levels);
-  }
-  *out = std::move(gs.out);
-  *threshold_used = gs.threshold_used;
-  *steps_run = gs.steps_run;
-  return SHK_OK;
-}
-
 namespace {
 
 // A grow-only array that is never value-initialised (the panel's output arrays are as large as its capacities).
@@ -361,17 +324,18 @@ struct Raw {
   }
 };
 
-int panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint32_t *primer_counts,
-              const uint64_t *primer_offsets, uint32_t n_genes, const shk_pcr_extend_params *params,
-              std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
-  const uint64_t fetch_cap = env_u64("SHK_PCR_FETCH_CAP", 0);
-  const uint64_t budget = env_u64("SHK_PCR_PANEL_FETCH_CAP", 1ull << 22);
-  const char *env_threads = getenv("SHK_PCR_PANEL_THREADS");  // default 8; whatever is given is clamped to 1..16
+// who: the public call, for its error texts.  The panel-only knobs (SHK_PCR_PANEL_*) are the panel's: the single call
+// has no launch budget to share, one thread, and no trace line.
+int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params, bool panel,
+              const char *who, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
+  const uint64_t fetch_cap = env_u64("SHK_PCR_FETCH_CAP", 0);  // 0: sized by the replay's room
+  const uint64_t budget = panel ? env_u64("SHK_PCR_PANEL_FETCH_CAP", 1ull << 22) : ~0ull;
+  const char *env_threads = panel ? getenv("SHK_PCR_PANEL_THREADS") : "1";  // default 8; whatever is given is clamped to 1..16
   const uint32_t n_threads = (uint32_t)std::min<long long>(std::max<long long>(env_threads ? atoll(env_threads) : 8, 1), 16);
   std::vector<GeneSweep> genes(n_genes);
   for (uint32_t g = 0; g < n_genes; ++g) {
-    const uint64_t f0 = primer_offsets[2 * g], r0 = primer_offsets[2 * g + 1], r1 = primer_offsets[2 * g + 2];
-    genes[g].init(k, primer_kmers + f0, primer_counts + f0, r0 - f0, primer_kmers + r0, primer_counts + r0, r1 - r0, params[g]);
+    const PcrPrimers &pr = primers[g];
+    genes[g].init(k, pr.fwd_kmers, pr.fwd_counts, pr.n_fwd, pr.rev_kmers, pr.rev_counts, pr.n_rev, params[g]);
   }
   std::vector<uint32_t> active(n_genes);
   for (uint32_t g = 0; g < n_genes; ++g) active[g] = g;
@@ -412,7 +376,7 @@ int panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint
       for (std::thread &th : pool) th.join();
     }
     if (std::find(failed.begin(), failed.end(), 1) != failed.end()) {
-      *err = "shk_pcr_extend_panel: out of host memory in a gene's replay";
+      *err = std::string(who) + ": out of host memory in a gene's replay";
       return SHK_ERR_NOMEM;
     }
     launches_used = 0;
@@ -454,7 +418,7 @@ int panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint
       uint64_t at = 0;
       for (uint32_t j = 0; j < n_jobs; ++j) {
         if (L.levels[j] == 0) {
-          *err = "shk_pcr_extend_panel: gene " + std::to_string(active[a + j]) + ": a neighbourhood fetch made no progress";
+          *err = std::string(who) + (panel ? ": gene " + std::to_string(active[a + j]) : "") + ": a neighbourhood fetch made no progress";
           return SHK_ERR_INVARIANT;
         }
         genes[active[a + j]].answer(L.kmers.p.get() + at, L.counts.p.get() + at, L.n_out[j], L.levels[j]);
@@ -463,7 +427,7 @@ int panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint
       a = b;
     }
   }
-  if (getenv("SHK_PCR_PANEL_TRACE"))
+  if (panel && getenv("SHK_PCR_PANEL_TRACE"))
     fprintf(stderr, "shk_pcr_extend_panel: genes %u rounds %llu launches %llu threads %u\n", n_genes, (unsigned long long)n_rounds,
             (unsigned long long)n_launches, n_threads);
   out->resize(n_genes);
@@ -477,13 +441,13 @@ int panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint
 
 }  // namespace
 
-int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint32_t *primer_counts,
-                         const uint64_t *primer_offsets, uint32_t n_genes, const shk_pcr_extend_params *params,
-                         std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
+int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params,
+                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
+  const char *who = panel ? "shk_pcr_extend_panel" : "shk_pcr_extend";
   try {
-    return panel_run(ctx, k, primer_kmers, primer_counts, primer_offsets, n_genes, params, out, threshold_used, steps_run, err);
+    return panel_run(ctx, k, primers, n_genes, params, panel, who, out, threshold_used, steps_run, err);
   } catch (const std::exception &e) {  // bad_alloc on the calling thread: an error code, not an exception across the C ABI
-    *err = std::string("shk_pcr_extend_panel: ") + e.what();
+    *err = std::string(who) + ": " + e.what();
     return SHK_ERR_NOMEM;
   }
 }

@@ -1,7 +1,7 @@
 // shk_pcr.h — host side of sPCR's graph extension (create_seed_graph + extend_graph, src/pcr/graph.rs:196-528, under
 // the threshold sweep of do_pcr, src/pcr/mod.rs:559-619): the reference's order-dependent logic replayed statement for
-// statement over counts fetched in bulk by shk_neighborhood / shk_neighborhood_panel (plain C++: no HIP; the device is
-// reached through those entry points only).
+// statement over counts fetched in bulk by shk_neighborhood_panel (plain C++: no HIP; the device is reached through
+// that entry point only).
 #pragma once
 
 #include <cstdint>
@@ -22,18 +22,21 @@ double pcr_median_u32(std::vector<uint32_t> counts, double dflt);
 // compute_coverage_thresholds (mod.rs:403-428)
 std::vector<uint32_t> pcr_coverage_thresholds(uint32_t primer_count, uint32_t min_count);
 
-// The sweep over a context of k-mer length k.  *threshold_used / *steps_run describe the last step run, whose graph is
-// *out.  Returns SHK_OK or the code of a failed shk_neighborhood (its text is the context's last error); *err is set
-// for failures of its own.
-int pcr_extend_run(shk_ctx *ctx, uint32_t k, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
-                   const uint64_t *rev_kmers, const uint32_t *rev_counts, uint64_t n_rev,
-                   const shk_pcr_extend_params &p, PcrGraph *out, uint32_t *threshold_used, uint32_t *steps_run,
-                   std::string *err);
+struct PcrPrimers {  // one gene's two primer sets
+  const uint64_t *fwd_kmers;
+  const uint32_t *fwd_counts;
+  uint64_t n_fwd;
+  const uint64_t *rev_kmers;
+  const uint32_t *rev_counts;
+  uint64_t n_rev;
+};
 
-// The same for every gene of a panel (shk_pcr_extend_panel): gene g's forward set is direction 2g of (primer_kmers,
-// primer_counts, primer_offsets), its reverse set 2g + 1, its parameters params[g].  The genes' replays run in rounds
-// on a few host threads (SHK_PCR_PANEL_THREADS); what they need from the table goes into one shk_neighborhood_panel
-// call per round, made by the calling thread.  out, threshold_used, steps_run: per gene, as above.
-int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const uint64_t *primer_kmers, const uint32_t *primer_counts,
-                         const uint64_t *primer_offsets, uint32_t n_genes, const shk_pcr_extend_params *params,
-                         std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err);
+// The sweep of every gene of a panel over a context of k-mer length k: gene g from primers[g] under params[g].  Per
+// gene, threshold_used / steps_run describe the last step run, whose graph is (*out)[g].  The genes' replays run in
+// rounds on a few host threads (SHK_PCR_PANEL_THREADS); what they need from the table goes into one
+// shk_neighborhood_panel call per round, made by the calling thread.  panel: shk_pcr_extend_panel's call; else
+// shk_pcr_extend's, one gene on the calling thread, which the SHK_PCR_PANEL_* knobs do not govern.  Returns SHK_OK or
+// the code of a failed shk_neighborhood_panel (its text is the context's last error); *err is set for failures of its
+// own, a failed host allocation among them (SHK_ERR_NOMEM).
+int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params,
+                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err);

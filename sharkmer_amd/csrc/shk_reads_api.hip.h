@@ -204,7 +204,7 @@ int shk_kmers_from_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offse
 
 namespace {
 
-// A graph as k_thread_reads wants it: the lookup set of build_edge_lookup (threading.rs:203-220), the
+// A graph as k_thread_panel wants it: the lookup set of build_edge_lookup (threading.rs:203-220), the
 // per-edge facts find_contiguous_runs / record_branch_links ask the graph for, and a dense slot for every branch link.
 struct ThreadPlan {
   HostKeyRuns runs;                 // canonical edge k-mer → its candidates, edges ascending
@@ -286,7 +286,7 @@ void thread_out_zero(shk_thread_out *out, uint64_t n_edges, uint64_t n_seqs) {
   out->n_links = out->n_paired_links = 0;
 }
 
-// What follows a launch, for shk_thread_reads and, per gene, for shk_thread_reads_panel.
+// What follows a launch, per gene.
 // paired_links.len() (threading.rs:166-189): pairs of which an R1 and an R2 read each mapped to some edge.  Position i
 // of the n walked is read reads[i] of the batch (reads == NULL: read i) and mapped to re[i] edges.
 uint64_t thread_paired_links(const uint64_t *reads, uint64_t n, const uint64_t *read_index, const uint8_t *mate, const uint32_t *re) {
@@ -322,102 +322,6 @@ void thread_links_decode(const ThreadPlan &pl, const uint32_t *slots, uint64_t n
       }
   }
 }
-
-// The launch over an opened batch (its offsets checked) and what follows it.
-int thread_core(shk_ctx *c, const ThreadPlan &pl, const ReadBatch &b, const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
-  const uint32_t k = c->cfg.k, E = (uint32_t)pl.runs.items.size(), cap = (uint32_t)pl.runs.keys.size();
-  const uint64_t n_seqs = b.n_seqs, max_len = b.max_len;
-  const int lds_edges = env_int("SHK_THREAD_LDS_EDGES", THREAD_LDS_EDGES);
-  const size_t lds = thread_lds_bytes(cap, E);
-  const bool use_lds = (int64_t)E <= (int64_t)lds_edges && lds <= THREAD_LDS_MAX;
-  // every wave keeps one (edge, flags) pair per window of the read it is on: the longest read sizes a wave's scratch,
-  // and 256 MiB of scratch bound the waves
-  const uint64_t max_win = max_len >= k ? max_len - k + 1 : 0;
-  const uint64_t stride = std::max<uint64_t>(THREAD_TILE, (max_win + THREAD_TILE - 1) / THREAD_TILE * THREAD_TILE);
-  const uint64_t wpb = THREAD_WG / 64;
-  uint64_t blocks = std::min<uint64_t>((n_seqs + wpb - 1) / wpb, (uint64_t)c->n_cus * (use_lds ? 1 : 2));
-  blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, ((256ull << 20) / 8) / (stride * wpb)));
-  Scratch m{c->misc};
-  const KeyRunsAt o_runs = key_runs_take(m, pl.runs);
-  const size_t o_meta = m.take<uint4>(E);
-  const size_t n_cnt = 2 * (size_t)E + pl.n_slots + n_seqs;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
-  const size_t o_cnt = m.take<uint32_t>(n_cnt), o_scr = m.take<uint2>(blocks * wpb * stride);
-  HIPC(c, m.ensure());
-  uint32_t *dtot = m.at<uint32_t>(o_cnt), *dun = dtot + E, *dlinks = dun + E, *dre = dlinks + pl.n_slots;
-  ThreadSet set{{}, m.at<uint4>(o_meta)};
-  SHK_TRY(key_runs_upload(c, m, o_runs, pl.runs, &set.runs));
-  HIPC(c, hipMemcpyAsync(m.at<uint4>(o_meta), pl.meta.data(), (size_t)E * 16, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
-  if (getenv("SHK_TRACE"))  // (read at each call, like SHK_THREAD_LDS_EDGES: the tests look for this line)
-    fprintf(stderr, "[shk] thread_reads: %u edges, set of %zu bytes in %s, %llu blocks\n", E, lds, use_lds ? "LDS" : "global memory",
-            (unsigned long long)blocks);
-  SHK_TRY(launch_lds_or_global(c, &k_thread_reads<true>, &k_thread_reads<false>, use_lds, &c->lds_attr_thread, THREAD_LDS_MAX, blocks, THREAD_WG,
-                               use_lds ? lds : 0, b.d_bases, b.d_offsets, n_seqs, (int)k, set, m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks,
-                               dre));
-  HIPC(c, hipGetLastError());
-  std::vector<uint32_t> slots(pl.n_slots), re_own;
-  uint32_t *re = out->read_edges;
-  if (!re && mate) {
-    re_own.resize(n_seqs);
-    re = re_own.data();
-  }
-  HIPC(c, hipMemcpyAsync(out->support_total, dtot, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(out->support_unambiguous, dun, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
-  if (pl.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pl.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
-  if (re) HIPC(c, hipMemcpyAsync(re, dre, n_seqs * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the plan alive until its copies ran)
-  out->n_paired_links = mate ? thread_paired_links(nullptr, n_seqs, read_index, mate, re) : 0;
-  const uint64_t n_links = thread_links_count(slots.data(), pl.n_slots);
-  out->n_links = n_links;
-  if (n_links > out->link_cap || (n_links && (!out->link_in || !out->link_out || !out->link_counts)))
-    return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)out->link_cap);
-  thread_links_decode(pl, slots.data(), n_links, out->link_in, out->link_out, out->link_counts);
-  return SHK_OK;
-}
-
-}  // namespace
-
-int shk_thread_reads_device(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
-                            uint64_t n_edges, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
-                            const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
-  if (c && c->group)
-    return on_any_device(c, [&](shk_ctx *d) {
-      return shk_thread_reads_device(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, d_bases, d_offsets, n_seqs, n_bases, read_index, mate, out);
-    });
-  if (!c || !out || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
-  ThreadPlan pl;
-  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
-  thread_out_zero(out, n_edges, n_seqs);
-  if (n_seqs == 0) return SHK_OK;
-  ReadBatch b;
-  SHK_TRY(batch_from_device(c, d_bases, d_offsets, n_seqs, n_bases, "shk_thread_reads", &b));
-  if (n_edges == 0) return SHK_OK;
-  return thread_core(c, pl, b, read_index, mate, out);
-}
-
-int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
-                     uint64_t n_edges, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *read_index,
-                     const uint8_t *mate, shk_thread_out *out) {
-  if (c && c->group)
-    return on_any_device(c, [&](shk_ctx *d) {
-      return shk_thread_reads(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, bases, offsets, n_seqs, read_index, mate, out);
-    });
-  if (!c || !out || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
-  ThreadPlan pl;
-  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
-  thread_out_zero(out, n_edges, n_seqs);
-  if (n_seqs == 0) return SHK_OK;
-  uint64_t max_len = 0;
-  SHK_TRY(batch_check_offsets(c, offsets, n_seqs, offsets[n_seqs], "shk_thread_reads", &max_len));
-  if (n_edges == 0) return SHK_OK;
-  if (offsets[n_seqs] && !bases) return SHK_ERR_BAD_ARG;
-  // the device form's launch over the staged batch (its offsets are already here: no copy back)
-  ReadBatch b;
-  SHK_TRY(batch_from_host(c, bases, offsets, n_seqs, max_len, &b));
-  return thread_core(c, pl, b, read_index, mate, out);
-}
-
-namespace {
 
 // A panel of graphs as k_thread_panel wants it: one ThreadPlan per gene, by thread_plan.
 struct ThreadPanelPlan {
@@ -479,10 +383,33 @@ void thread_panel_out_zero(shk_thread_panel_out *out, const ThreadPanelPlan &pp,
   out->n_links = 0;
 }
 
-// The launch over an opened batch (its offsets checked) and what follows it.
+// What thread_panel_core leaves, for shk_thread_reads_panel's shk_thread_panel_out and shk_thread_reads' shk_thread_out
+// alike.  The large arrays are written where the caller wants them: the supports of the panel's edges (gene after gene)
+// and, where asked for, read_edges by list position.
+struct ThreadPanelResult {
+  uint32_t *support_total, *support_unambiguous, *read_edges;  // in: the destinations (read_edges: or nullptr)
+  std::vector<uint32_t> link_in, link_out, link_counts;        // the links seen, gene after gene: gene g's from link_off[g]
+  std::vector<uint64_t> link_off, n_paired;                    // n_genes + 1; n_genes (zero without mates)
+};
+
+// The links of a result into a caller's arrays of link_cap entries.
+int thread_links_out(shk_ctx *c, const ThreadPanelResult &res, uint64_t link_cap, uint32_t *link_in, uint32_t *link_out, uint32_t *link_counts) {
+  const uint64_t n_links = res.link_off.back();
+  if (n_links > link_cap || (n_links && (!link_in || !link_out || !link_counts)))
+    return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)link_cap);
+  std::copy(res.link_in.begin(), res.link_in.end(), link_in);
+  std::copy(res.link_out.begin(), res.link_out.end(), link_out);
+  std::copy(res.link_counts.begin(), res.link_counts.end(), link_counts);
+  return SHK_OK;
+}
+
+// The launch over an opened batch (its offsets checked) and what follows it.  list_reads == nullptr: list position i (from
+// pp.l0) is read i — the one gene of shk_thread_reads, which lists every read.
 int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
-                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, ThreadPanelResult *res) {
   const uint32_t k = c->cfg.k;
+  res->link_off.assign(n_genes + 1, 0);
+  res->n_paired.assign(n_genes, 0);
   const int lds_edges = env_int("SHK_THREAD_LDS_EDGES", THREAD_LDS_EDGES);
   const uint64_t job_reads = (uint64_t)std::max(env_int("SHK_THREAD_PANEL_JOB", THREAD_PANEL_JOB), 1);
   const int block_cap = env_int("SHK_THREAD_PANEL_BLOCKS", 0);
@@ -510,7 +437,7 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
     if (!E) continue;  // no set, no jobs: its reads map to nothing
     const uint32_t cap = (uint32_t)pl.runs.keys.size();
     const size_t gene_lds = thread_lds_bytes(cap, E);
-    d.lds = (int64_t)E <= (int64_t)lds_edges && gene_lds <= THREAD_LDS_MAX;  // thread_core's rule, per gene
+    d.lds = (int64_t)E <= (int64_t)lds_edges && gene_lds <= THREAD_LDS_MAX;
     if (d.lds) lds = std::max(lds, gene_lds);
     ++(d.lds ? n_lds : n_global);
     d.meta = put(pl.meta.data(), (size_t)E * 16);
@@ -524,7 +451,7 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   if (jobs.empty()) return SHK_OK;  // (the outputs are zero already)
   if (jobs.size() >= (1ull << 32)) return fail(c, SHK_ERR_BAD_ARG, "%zu jobs: raise SHK_THREAD_PANEL_JOB", jobs.size());
   const size_t o_desc_up = put(desc.data(), desc.size() * sizeof(ThreadGene));
-  // blocks: thread_core's rule — a wave per read up to the device's workgroups (one per CU when a set fills its LDS), the
+  // blocks: a wave per read up to the device's workgroups (one per CU when a set fills its LDS), the
   // waves bounded by 256 MiB of scratch, whose stride the longest read of the BATCH sets — and never more than the jobs
   const uint64_t max_win = b.max_len >= k ? b.max_len - k + 1 : 0;
   const uint64_t stride = std::max<uint64_t>(THREAD_TILE, (max_win + THREAD_TILE - 1) / THREAD_TILE * THREAD_TILE);
@@ -534,14 +461,15 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   if (block_cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)block_cap);
   blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, jobs.size()));
   Scratch m{c->misc};
-  const size_t o_up = m.take<uint8_t>(up.size()), o_jobs = m.take<ThreadJob>(jobs.size()), o_list = m.take<uint64_t>(pp.n_listed);
+  const size_t o_up = m.take<uint8_t>(up.size()), o_jobs = m.take<ThreadJob>(jobs.size()), o_list = m.take<uint64_t>(list_reads ? pp.n_listed : 0);
   const size_t n_cnt = 2 * (size_t)pp.n_edges + pp.n_slots + pp.n_listed;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
   const size_t o_cnt = m.take<uint32_t>(n_cnt), o_scr = m.take<uint2>(blocks * wpb * stride);
   HIPC(c, m.ensure());
   uint32_t *dtot = m.at<uint32_t>(o_cnt), *dun = dtot + pp.n_edges, *dlinks = dun + pp.n_edges, *dre = dlinks + pp.n_slots;
   HIPC(c, hipMemcpyAsync(m.at<uint8_t>(o_up), up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemcpyAsync(m.at<ThreadJob>(o_jobs), jobs.data(), jobs.size() * sizeof(ThreadJob), hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + pp.l0, pp.n_listed * 8, hipMemcpyHostToDevice, c->stream));
+  const uint64_t *dlist = list_reads ? m.at<uint64_t>(o_list) : nullptr;
+  if (list_reads) HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + pp.l0, pp.n_listed * 8, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
   if (getenv("SHK_TRACE"))  // (read at each call, like the knobs: the tests look for this line)
     fprintf(stderr, "[shk] thread_reads_panel: %u genes, %zu jobs, %llu blocks, %u genes in LDS, %u genes in global memory\n", n_genes, jobs.size(),
@@ -553,41 +481,105 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
       c->lds_attr_thread_panel = true;
     }
     hipLaunchKernelGGL(k_thread_panel, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, b.d_bases, b.d_offsets,
-                       (const uint64_t *)m.at<uint64_t>(o_list), (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up),
+                       dlist, (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up),
                        (const ThreadJob *)m.at<ThreadJob>(o_jobs), (uint32_t)jobs.size(), (const uint8_t *)m.at<uint8_t>(o_up), (int)k,
                        m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
   }
   HIPC(c, hipGetLastError());
   std::vector<uint32_t> slots(pp.n_slots), re_own;
-  uint32_t *re = out->read_edges ? out->read_edges + pp.l0 : nullptr;
+  uint32_t *re = res->read_edges;
   if (!re && mate) {
     re_own.resize(pp.n_listed);
     re = re_own.data();
   }
-  HIPC(c, hipMemcpyAsync(out->support_total + pp.e0, dtot, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(out->support_unambiguous + pp.e0, dun, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(res->support_total, dtot, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(res->support_unambiguous, dun, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
   if (pp.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pp.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
   if (re) HIPC(c, hipMemcpyAsync(re, dre, pp.n_listed * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the upload and the jobs alive until their copies ran)
-  // per gene, what thread_core does for its one graph
-  std::vector<uint64_t> link_off(n_genes + 1, 0);
   for (uint32_t g = 0; g < n_genes; ++g) {
     const uint64_t l_at = list_offsets[g] - pp.l0, n_list = list_offsets[g + 1] - list_offsets[g];
-    if (mate && out->n_paired_links) out->n_paired_links[g] = thread_paired_links(list_reads + list_offsets[g], n_list, read_index, mate, re + l_at);
-    link_off[g + 1] = link_off[g] + thread_links_count(slots.data() + desc[g].link_base, pp.genes[g].n_slots);
+    if (mate)
+      res->n_paired[g] = list_reads ? thread_paired_links(list_reads + list_offsets[g], n_list, read_index, mate, re + l_at)
+                                    : thread_paired_links(nullptr, n_list, read_index + l_at, mate + l_at, re + l_at);
+    res->link_off[g + 1] = res->link_off[g] + thread_links_count(slots.data() + desc[g].link_base, pp.genes[g].n_slots);
   }
-  const uint64_t n_links = link_off[n_genes];
-  if (out->link_offsets) std::copy(link_off.begin(), link_off.end(), out->link_offsets);
-  out->n_links = n_links;
-  if (n_links > out->link_cap || (n_links && (!out->link_in || !out->link_out || !out->link_counts)))
-    return fail(c, SHK_ERR_BAD_ARG, "%llu branch links do not fit link_cap %llu", (unsigned long long)n_links, (unsigned long long)out->link_cap);
+  const uint64_t n_links = res->link_off[n_genes];
+  res->link_in.resize(n_links), res->link_out.resize(n_links), res->link_counts.resize(n_links);
   for (uint32_t g = 0; g < n_genes; ++g)
-    thread_links_decode(pp.genes[g], slots.data() + desc[g].link_base, link_off[g + 1] - link_off[g], out->link_in + link_off[g],
-                        out->link_out + link_off[g], out->link_counts + link_off[g]);
+    thread_links_decode(pp.genes[g], slots.data() + desc[g].link_base, res->link_off[g + 1] - res->link_off[g],
+                        res->link_in.data() + res->link_off[g], res->link_out.data() + res->link_off[g], res->link_counts.data() + res->link_off[g]);
   return SHK_OK;
 }
 
+// shk_thread_reads[_device] after their checks and early returns: the panel of one gene that lists every read of the
+// opened batch, in the batch's order (no list is uploaded).
+int thread_one_gene(shk_ctx *c, ThreadPlan &&pl, uint64_t n_edges, const ReadBatch &b, const uint64_t *read_index, const uint8_t *mate,
+                    shk_thread_out *out) {
+  ThreadPanelPlan pp;
+  pp.n_edges = n_edges, pp.n_listed = b.n_seqs, pp.n_slots = pl.n_slots;
+  pp.genes.push_back(std::move(pl));
+  const uint64_t list_offsets[2] = {0, b.n_seqs};
+  ThreadPanelResult res{out->support_total, out->support_unambiguous, out->read_edges, {}, {}, {}, {}, {}};
+  SHK_TRY(thread_panel_core(c, pp, 1, b, list_offsets, nullptr, read_index, mate, &res));
+  out->n_paired_links = res.n_paired[0];
+  out->n_links = res.link_off[1];
+  return thread_links_out(c, res, out->link_cap, out->link_in, out->link_out, out->link_counts);
+}
+
+// shk_thread_reads_panel[_device] after theirs.
+int thread_panel_run(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
+                     const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+  ThreadPanelResult res{out->support_total + pp.e0, out->support_unambiguous + pp.e0, out->read_edges ? out->read_edges + pp.l0 : nullptr,
+                        {}, {}, {}, {}, {}};
+  SHK_TRY(thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, &res));
+  if (out->n_paired_links) std::copy(res.n_paired.begin(), res.n_paired.end(), out->n_paired_links);
+  if (out->link_offsets) std::copy(res.link_off.begin(), res.link_off.end(), out->link_offsets);
+  out->n_links = res.link_off[n_genes];
+  return thread_links_out(c, res, out->link_cap, out->link_in, out->link_out, out->link_counts);
+}
+
 }  // namespace
+
+int shk_thread_reads_device(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
+                            uint64_t n_edges, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                            const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
+  if (c && c->group)
+    return on_any_device(c, [&](shk_ctx *d) {
+      return shk_thread_reads_device(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, d_bases, d_offsets, n_seqs, n_bases, read_index, mate, out);
+    });
+  if (!c || !out || (n_seqs && !d_offsets)) return SHK_ERR_BAD_ARG;
+  ThreadPlan pl;
+  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
+  thread_out_zero(out, n_edges, n_seqs);
+  if (n_seqs == 0) return SHK_OK;
+  ReadBatch b;
+  SHK_TRY(batch_from_device(c, d_bases, d_offsets, n_seqs, n_bases, "shk_thread_reads", &b));
+  if (n_edges == 0) return SHK_OK;
+  return thread_one_gene(c, std::move(pl), n_edges, b, read_index, mate, out);
+}
+
+int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
+                     uint64_t n_edges, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *read_index,
+                     const uint8_t *mate, shk_thread_out *out) {
+  if (c && c->group)
+    return on_any_device(c, [&](shk_ctx *d) {
+      return shk_thread_reads(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, bases, offsets, n_seqs, read_index, mate, out);
+    });
+  if (!c || !out || (n_seqs && !offsets)) return SHK_ERR_BAD_ARG;
+  ThreadPlan pl;
+  SHK_TRY(thread_plan(c, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, n_seqs, read_index, mate, out, &pl));
+  thread_out_zero(out, n_edges, n_seqs);
+  if (n_seqs == 0) return SHK_OK;
+  uint64_t max_len = 0;
+  SHK_TRY(batch_check_offsets(c, offsets, n_seqs, offsets[n_seqs], "shk_thread_reads", &max_len));
+  if (n_edges == 0) return SHK_OK;
+  if (offsets[n_seqs] && !bases) return SHK_ERR_BAD_ARG;
+  // the device form's launch over the staged batch (its offsets are already here: no copy back)
+  ReadBatch b;
+  SHK_TRY(batch_from_host(c, bases, offsets, n_seqs, max_len, &b));
+  return thread_one_gene(c, std::move(pl), n_edges, b, read_index, mate, out);
+}
 
 int shk_thread_reads_panel_device(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src,
                                   const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const void *d_bases, const void *d_offsets,
@@ -606,7 +598,7 @@ int shk_thread_reads_panel_device(shk_ctx *c, const uint64_t *node_sub_kmers, co
   if (n_seqs == 0 || n_genes == 0) return SHK_OK;
   ReadBatch b;
   SHK_TRY(batch_from_device(c, d_bases, d_offsets, n_seqs, n_bases, "shk_thread_reads_panel", &b));  // (the offsets come back once)
-  return thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
+  return thread_panel_run(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
 }
 
 int shk_thread_reads_panel(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src,
@@ -631,7 +623,7 @@ int shk_thread_reads_panel(shk_ctx *c, const uint64_t *node_sub_kmers, const uin
   // the device form's launch over the staged batch (its offsets are already here: no copy back)
   ReadBatch b;
   SHK_TRY(batch_from_host(c, bases, offsets, n_seqs, max_len, &b));
-  return thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
+  return thread_panel_run(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, out);
 }
 
 namespace {

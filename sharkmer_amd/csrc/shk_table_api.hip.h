@@ -67,9 +67,12 @@ int compact_owners_launch(shk_ctx *c, uint32_t n_owners, const uint64_t *h_off, 
   return SHK_OK;
 }
 
-// The level loop of shk_neighborhood, and of a job of shk_neighborhood_panel that outgrew its workgroup: from the state
-// h (which dctl holds too) until the job stops — complete, at max_levels, or before a level that does not fit.
-int nb_run_levels(shk_ctx *c, const NbRef &nb, NbCtl *dctl, NbCtl &h) {
+// The level loop of a neighbourhood job that outgrew its workgroup (nb_panel_core: status NB_WIDE): from the state h
+// (which dctl holds too; nb is the host's copy of *dref) until the job stops — complete, at max_levels, or before a
+// level that does not fit.  A narrow launch is k_nb_narrow_panel on this job alone.  Its guard (status NB_RUN, 0 <
+// cur_n <= NB_NARROW) holds at each: the loop comes in with a level wider than NB_NARROW, so a narrow launch always
+// follows a wide level, after which the host uploaded h with status NB_RUN and the cur_n tested here.
+int nb_run_levels(shk_ctx *c, const NbRef &nb, const NbRef *dref, NbCtl *dctl, NbCtl &h) {
   // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
   while (h.status == NB_RUN || h.status == NB_WIDE) {
     if (h.cur_n == 0) {
@@ -83,7 +86,7 @@ int nb_run_levels(shk_ctx *c, const NbRef &nb, NbCtl *dctl, NbCtl &h) {
     if (h.cur_n <= NB_NARROW) {
       {
         ScopedTimer t(c, SHK_K_EXTEND);
-        hipLaunchKernelGGL(k_nb_narrow, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, nb, dctl);
+        hipLaunchKernelGGL(k_nb_narrow_panel, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, dref, dctl);
       }
       HIPC(c, hipGetLastError());
       HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -166,6 +169,173 @@ void nb_sorted_out(const uint64_t *hk, const uint32_t *hc, uint64_t nk, uint64_t
   }
 }
 
+// The device part of shk_neighborhood_panel, and of shk_neighborhood as its one-job case, after every job's arguments
+// were checked: job j starts from level 0 seeds[j] (nb_level0's) under min_counts[j], caps[j] and fringe_caps[j]; its
+// k-mers go to (kmers, counts) + out_at[j], its fringe to (fringe_nodes, fringe_dirs) + fr_at[j], its figures to
+// n_out[j], n_fringe[j] and levels_done[j].
+int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
+                  const uint64_t *caps, const uint64_t *fringe_caps, const uint64_t *out_at, const uint64_t *fr_at, uint64_t *kmers,
+                  uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
+                  uint32_t *levels_done) {
+  const uint32_t k = c->cfg.k;
+  uint64_t n_all_seeds = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) n_all_seeds += seeds[j].size();
+  std::fill(n_out, n_out + n_jobs, 0ull);
+  std::fill(n_fringe, n_fringe + n_jobs, 0ull);
+  std::fill(levels_done, levels_done + n_jobs, 0u);
+  if (n_all_seeds == 0) return SHK_OK;
+  SHK_TRY(table_read_begin(c));
+  // Device layout: every job's two sets in one region (one clear), then what is uploaded in one copy (NbRef, NbCtl,
+  // seed starts, seeds, their jobs), then the lists.  A job without seeds gets no room: it is not run.  The packed
+  // copies are for a panel: one job's lists are fetched from where they are.
+  const bool packed = n_jobs > 1;
+  std::vector<uint64_t> capj(n_jobs), fcj(n_jobs), set_at(n_jobs + 1, 0), l_at(n_jobs + 1, 0), k_at(n_jobs + 1, 0);
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    const bool live = !seeds[j].empty();
+    capj[j] = live ? caps[j] : 0;
+    fcj[j] = live ? fringe_caps[j] : 0;
+    set_at[j + 1] = set_at[j] + (live ? nb_vis_slots(seeds[j].size(), capj[j]) + nb_kset_slots(capj[j]) : 0);
+    l_at[j + 1] = l_at[j] + std::max<uint64_t>(fcj[j], 1);
+    k_at[j + 1] = k_at[j] + std::max<uint64_t>(capj[j], 1);
+  }
+  const uint64_t n_pk = packed ? k_at[n_jobs] : 0, n_pf = packed ? l_at[n_jobs] : 0;
+  Scratch m{c->misc};
+  const size_t o_sets = m.take<uint64_t>(set_at[n_jobs]);
+  const size_t o_refs = m.take<NbRef>(n_jobs), o_ctl = m.take<NbCtl>(n_jobs), o_start = m.take<uint64_t>(n_jobs + 1);
+  const size_t o_seeds = m.take<uint64_t>(n_all_seeds), o_sjob = m.take<uint32_t>(n_all_seeds);
+  const size_t o_pack = m.take<NbPack>(n_jobs);  // (ends the uploaded block)
+  const size_t o_l0 = m.take<uint64_t>(l_at[n_jobs]), o_l1 = m.take<uint64_t>(l_at[n_jobs]);
+  const size_t o_km = m.take<uint64_t>(k_at[n_jobs]), o_ct = m.take<uint32_t>(k_at[n_jobs]);
+  const size_t o_pk = m.take<uint64_t>(n_pk), o_pc = m.take<uint32_t>(n_pk), o_pf = m.take<uint64_t>(n_pf);
+  HIPC(c, m.ensure());
+  std::vector<uint8_t> up(o_pack - o_refs, 0);  // the uploaded block as the device holds it
+  NbRef *href = (NbRef *)up.data();
+  NbCtl *hctl = (NbCtl *)(up.data() + (o_ctl - o_refs));
+  uint64_t *hstart = (uint64_t *)(up.data() + (o_start - o_refs)), *hseeds = (uint64_t *)(up.data() + (o_seeds - o_refs));
+  uint32_t *hsjob = (uint32_t *)(up.data() + (o_sjob - o_refs));
+  uint64_t at = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    NbRef &nb = href[j];
+    const uint64_t vis_slots = seeds[j].empty() ? 0 : nb_vis_slots(seeds[j].size(), capj[j]);
+    nb.vis = m.at<uint64_t>(o_sets) + set_at[j];
+    nb.kset = nb.vis + vis_slots;
+    nb.vis_mask = vis_slots ? vis_slots - 1 : 0;
+    nb.kset_mask = seeds[j].empty() ? 0 : nb_kset_slots(capj[j]) - 1;
+    nb.list[0] = m.at<uint64_t>(o_l0) + l_at[j];
+    nb.list[1] = m.at<uint64_t>(o_l1) + l_at[j];
+    nb.kmers = m.at<uint64_t>(o_km) + k_at[j];
+    nb.counts = m.at<uint32_t>(o_ct) + k_at[j];
+    nb.cap = capj[j];
+    nb.fringe_cap = fcj[j];
+    nb.min_count = std::max(min_counts[j], 1u);
+    nb.max_levels = max_levels;
+    nb.k = (int)k;
+    hctl[j].cur_n = seeds[j].size();
+    hctl[j].status = seeds[j].empty() ? NB_COMPLETE : seeds[j].size() > NB_NARROW ? NB_WIDE : NB_RUN;
+    hstart[j] = at;
+    for (const uint64_t e : seeds[j]) {
+      hseeds[at] = e;
+      hsjob[at++] = j;
+    }
+  }
+  hstart[n_jobs] = at;
+  NbRef *drefs = m.at<NbRef>(o_refs);
+  NbCtl *dctl = m.at<NbCtl>(o_ctl);
+  HIPC(c, hipMemsetAsync(m.at<uint64_t>(o_sets), 0xFF, set_at[n_jobs] * 8, c->stream));  // every set ← EMPTY
+  HIPC(c, hipMemcpyAsync(drefs, up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_seed_panel, dim3((uint32_t)((n_all_seeds + WG - 1) / WG)), dim3(WG), 0, c->stream,
+                       (const NbRef *)drefs, dctl, (const uint64_t *)m.at<uint64_t>(o_seeds),
+                       (const uint32_t *)m.at<uint32_t>(o_sjob), (const uint64_t *)m.at<uint64_t>(o_start), n_all_seeds);
+  }
+  {
+    ScopedTimer t(c, SHK_K_EXTEND);
+    hipLaunchKernelGGL(k_nb_narrow_panel, dim3(n_jobs), dim3(NB_WG), 0, c->stream, c->tb, (const NbRef *)drefs, dctl);
+  }
+  HIPC(c, hipGetLastError());
+  std::vector<NbCtl> h(n_jobs);
+  HIPC(c, hipMemcpyAsync(h.data(), dctl, (size_t)n_jobs * sizeof(NbCtl), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also: `up` has been read)
+  // the exception: a job with a level wider than a workgroup goes on alone
+  for (uint32_t j = 0; j < n_jobs; ++j)
+    if (h[j].status == NB_WIDE) SHK_TRY(nb_run_levels(c, href[j], drefs + j, dctl + j, h[j]));
+  std::vector<NbPack> pk(n_jobs);
+  uint64_t tot_k = 0, tot_f = 0;
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    pk[j] = NbPack{h[j].k_n, h[j].status == NB_COMPLETE ? 0ull : h[j].cur_n, tot_k, tot_f, h[j].cur_sel, 0};
+    if (pk[j].k_n > capj[j] || pk[j].n_f > std::max<uint64_t>(fcj[j], seeds[j].size()))
+      return fail(c, SHK_ERR_INVARIANT, "job %u: %llu k-mers / %llu fringe entries beyond its capacities", j, pk[j].k_n, pk[j].n_f);
+    tot_k += pk[j].k_n;
+    tot_f += pk[j].n_f;
+  }
+  std::vector<uint64_t> hk(tot_k), hf(tot_f);
+  std::vector<uint32_t> hc(tot_k);
+  if (tot_k || tot_f) {
+    const uint64_t *dk = href[0].kmers, *df = href[0].list[pk[0].sel & 1u];  // one job: its own arrays
+    const uint32_t *dc = href[0].counts;
+    if (packed) {
+      dk = m.at<uint64_t>(o_pk), dc = m.at<uint32_t>(o_pc), df = m.at<uint64_t>(o_pf);
+      HIPC(c, hipMemcpyAsync(m.at<NbPack>(o_pack), pk.data(), (size_t)n_jobs * sizeof(NbPack), hipMemcpyHostToDevice, c->stream));
+      {
+        ScopedTimer t(c, SHK_K_EXTEND);
+        hipLaunchKernelGGL(k_nb_pack_panel, dim3(n_jobs), dim3(WG), 0, c->stream, (const NbRef *)drefs,
+                           (const NbPack *)m.at<NbPack>(o_pack), m.at<uint64_t>(o_pk), m.at<uint32_t>(o_pc), m.at<uint64_t>(o_pf));
+      }
+      HIPC(c, hipGetLastError());
+    }
+    // (one job: the stream is idle here, and plain copies are what the single call always made; a panel's queue behind the pack)
+    auto fetch = [&](void *dst, const void *src, size_t bytes) {
+      return packed ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    if (tot_k) {
+      HIPC(c, fetch(hk.data(), dk, tot_k * 8));
+      HIPC(c, fetch(hc.data(), dc, tot_k * 4));
+    }
+    if (tot_f) HIPC(c, fetch(hf.data(), df, tot_f * 8));
+    if (packed) HIPC(c, hipStreamSynchronize(c->stream));
+  }
+  for (uint32_t j = 0; j < n_jobs; ++j) {
+    const NbPack &p = pk[j];
+    nb_sorted_out(hk.data() + p.pack_k, hc.data() + p.pack_k, p.k_n, hf.data() + p.pack_f, p.n_f, kmers + out_at[j],
+                  counts + out_at[j], fringe_nodes + fr_at[j], fringe_dirs + fr_at[j]);
+    n_out[j] = p.k_n;
+    n_fringe[j] = p.n_f;
+    levels_done[j] = h[j].levels_done;
+  }
+  return SHK_OK;
+}
+
+// The graphs of shk_pcr_extend_panel, and of shk_pcr_extend as a panel of one, into the caller's arrays: gene g's nodes
+// from node_offsets[g], its edges from edge_offsets[g] (both filled here, as is found_path, before anything is refused).
+// what: "graph" or "panel", as the text of a refusal calls them.
+int pcr_graphs_out(shk_ctx *c, const char *what, const std::vector<PcrGraph> &gs, uint64_t *node_sub_kmers, uint8_t *node_flags,
+                   uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts,
+                   uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path) {
+  using ull = unsigned long long;
+  const size_t n_genes = gs.size();
+  node_offsets[0] = edge_offsets[0] = 0;
+  for (size_t g = 0; g < n_genes; ++g) {
+    node_offsets[g + 1] = node_offsets[g] + gs[g].sub_kmer.size();
+    edge_offsets[g + 1] = edge_offsets[g] + gs[g].esrc.size();
+    found_path[g] = gs[g].found_path ? 1u : 0u;
+  }
+  const uint64_t nn = node_offsets[n_genes], ne = edge_offsets[n_genes];
+  if (nn > node_cap || ne > edge_cap)
+    return fail(c, SHK_ERR_BAD_ARG, "%s of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu", what, (ull)nn,
+                (ull)ne, (ull)node_cap, (ull)edge_cap);
+  if ((nn && (!node_sub_kmers || !node_flags)) || (ne && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
+  for (size_t g = 0; g < n_genes; ++g) {
+    const PcrGraph &gr = gs[g];
+    std::copy(gr.sub_kmer.begin(), gr.sub_kmer.end(), node_sub_kmers + node_offsets[g]);
+    std::copy(gr.flags.begin(), gr.flags.end(), node_flags + node_offsets[g]);
+    std::copy(gr.esrc.begin(), gr.esrc.end(), edge_src + edge_offsets[g]);
+    std::copy(gr.etgt.begin(), gr.etgt.end(), edge_tgt + edge_offsets[g]);
+    std::copy(gr.ecount.begin(), gr.ecount.end(), edge_counts + edge_offsets[g]);
+  }
+  return SHK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,56 +409,10 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
     return fail(c, SHK_ERR_BAD_ARG, "cap %llu / fringe_cap %llu above 2^32", (unsigned long long)cap, (unsigned long long)fringe_cap);
   std::vector<uint64_t> seeds;  // level 0
   SHK_TRY(nb_level0(c, "", nodes, dirs, n_seeds, k, fringe_cap, &seeds));
-  *n_out = 0;
-  *n_fringe = 0;
-  *levels_done = 0;
-  if (seeds.empty()) return SHK_OK;
-  SHK_TRY(table_read_begin(c));
-  const uint64_t vis_slots = nb_vis_slots(seeds.size(), cap), kset_slots = nb_kset_slots(cap);
-  const uint64_t fc = std::max<uint64_t>(fringe_cap, 1), kc = std::max<uint64_t>(cap, 1);
-  Scratch m{c->misc};
-  const size_t o_ctl = m.take<NbCtl>(1), o_vis = m.take<uint64_t>(vis_slots), o_kset = m.take<uint64_t>(kset_slots);  // (vis, kset: adjacent)
-  const size_t o_l0 = m.take<uint64_t>(fc), o_l1 = m.take<uint64_t>(fc), o_km = m.take<uint64_t>(kc), o_ct = m.take<uint32_t>(kc);
-  HIPC(c, m.ensure());
-  NbCtl *dctl = m.at<NbCtl>(o_ctl);
-  NbRef nb{};
-  nb.vis = m.at<uint64_t>(o_vis);
-  nb.kset = m.at<uint64_t>(o_kset);
-  nb.vis_mask = vis_slots - 1;
-  nb.kset_mask = kset_slots - 1;
-  nb.list[0] = m.at<uint64_t>(o_l0);
-  nb.list[1] = m.at<uint64_t>(o_l1);
-  nb.kmers = m.at<uint64_t>(o_km);
-  nb.counts = m.at<uint32_t>(o_ct);
-  nb.cap = cap;
-  nb.fringe_cap = fringe_cap;
-  nb.min_count = std::max(min_count, 1u);
-  nb.max_levels = max_levels;
-  nb.k = (int)k;
-  NbCtl h{};
-  h.cur_n = seeds.size();
-  HIPC(c, hipMemsetAsync(nb.vis, 0xFF, (o_l0 - o_vis), c->stream));  // both sets ← EMPTY
-  HIPC(c, hipMemcpyAsync(dctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemcpyAsync(nb.list[0], seeds.data(), seeds.size() * 8, hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_EXTEND);
-    hipLaunchKernelGGL(k_nb_seed, dim3((uint32_t)((seeds.size() + WG - 1) / WG)), dim3(WG), 0, c->stream, nb,
-                       (uint64_t)seeds.size(), dctl);
-  }
-  SHK_TRY(nb_run_levels(c, nb, dctl, h));
-  const uint64_t nk = h.k_n, nf = h.status == NB_COMPLETE ? 0 : h.cur_n;
-  std::vector<uint64_t> hk(nk), hf(nf);
-  std::vector<uint32_t> hc(nk);
-  if (nk) {
-    HIPC(c, hipMemcpy(hk.data(), nb.kmers, nk * 8, hipMemcpyDeviceToHost));
-    HIPC(c, hipMemcpy(hc.data(), nb.counts, nk * 4, hipMemcpyDeviceToHost));
-  }
-  if (nf) HIPC(c, hipMemcpy(hf.data(), nb.list[h.cur_sel], nf * 8, hipMemcpyDeviceToHost));
-  nb_sorted_out(hk.data(), hc.data(), nk, hf.data(), nf, kmers, counts, fringe_nodes, fringe_dirs);
-  *n_out = nk;
-  *n_fringe = nf;
-  *levels_done = h.levels_done;
-  return SHK_OK;
+  // one job of the panel's core: its outputs at the start of the caller's arrays
+  const uint64_t at0 = 0;
+  return nb_panel_core(c, &seeds, 1, &min_count, max_levels, &cap, &fringe_cap, &at0, &at0, kmers, counts, n_out, fringe_nodes,
+                       fringe_dirs, n_fringe, levels_done);
 }
 
 int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
@@ -309,24 +433,18 @@ int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_co
     if (fwd_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "forward primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
   for (uint64_t i = 0; i < n_rev; ++i)
     if (rev_kmers[i] > kmask) return fail(c, SHK_ERR_BAD_ARG, "reverse primer k-mer %llu is not a %u-mer", (unsigned long long)i, k);
-  PcrGraph g;
+  // a panel of one gene
+  const PcrPrimers primers{fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev};
+  std::vector<PcrGraph> gs;
   std::string msg;
-  const int rc = pcr_extend_run(c, k, fwd_kmers, fwd_counts, n_fwd, rev_kmers, rev_counts, n_rev, *p, &g, threshold_used,
-                                steps_run, &msg);
-  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood's own text stands)
-  *n_nodes = g.sub_kmer.size();
-  *n_edges = g.esrc.size();
-  *found_path = g.found_path ? 1u : 0u;
-  if (*n_nodes > node_cap || *n_edges > edge_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "graph of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu",
-                (unsigned long long)*n_nodes, (unsigned long long)*n_edges, (unsigned long long)node_cap, (unsigned long long)edge_cap);
-  if ((*n_nodes && (!node_sub_kmers || !node_flags)) || (*n_edges && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
-  std::copy(g.sub_kmer.begin(), g.sub_kmer.end(), node_sub_kmers);
-  std::copy(g.flags.begin(), g.flags.end(), node_flags);
-  std::copy(g.esrc.begin(), g.esrc.end(), edge_src);
-  std::copy(g.etgt.begin(), g.etgt.end(), edge_tgt);
-  std::copy(g.ecount.begin(), g.ecount.end(), edge_counts);
-  return SHK_OK;
+  const int rc = pcr_extend_panel_run(c, k, &primers, 1, p, false, &gs, threshold_used, steps_run, &msg);
+  if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else the neighbourhood fetch's own text stands)
+  uint64_t node_offsets[2], edge_offsets[2];
+  const int rc_out = pcr_graphs_out(c, "graph", gs, node_sub_kmers, node_flags, node_offsets, node_cap, edge_src, edge_tgt, edge_counts,
+                                    edge_offsets, edge_cap, found_path);
+  *n_nodes = node_offsets[1];
+  *n_edges = edge_offsets[1];
+  return rc_out;
 }
 
 int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
@@ -347,7 +465,6 @@ int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dir
   // every job's arguments before the device is touched
   std::vector<std::vector<uint64_t>> seeds(n_jobs);  // level 0 per job
   std::vector<uint64_t> out_at(n_jobs + 1, 0), fr_at(n_jobs + 1, 0);  // where a job's outputs start in the caller's arrays
-  uint64_t n_all_seeds = 0;
   for (uint32_t j = 0; j < n_jobs; ++j) {
     char who[32];
     snprintf(who, sizeof who, "job %u: ", j);
@@ -360,121 +477,10 @@ int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dir
     SHK_TRY(nb_level0(c, who, nodes ? nodes + a : nullptr, dirs ? dirs + a : nullptr, n, k, fringe_caps[j], &seeds[j]));
     out_at[j + 1] = out_at[j] + caps[j];
     fr_at[j + 1] = fr_at[j] + fringe_caps[j];
-    n_all_seeds += seeds[j].size();
   }
   if ((out_at[n_jobs] && (!kmers || !counts)) || (fr_at[n_jobs] && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
-  std::fill(n_out, n_out + n_jobs, 0ull);
-  std::fill(n_fringe, n_fringe + n_jobs, 0ull);
-  std::fill(levels_done, levels_done + n_jobs, 0u);
-  if (n_all_seeds == 0) return SHK_OK;
-  SHK_TRY(table_read_begin(c));
-  // Device layout: every job's two sets in one region (one clear), then what is uploaded in one copy (NbRef, NbCtl,
-  // seed starts, seeds, their jobs), then the lists.  A job without seeds gets no room: it is not run.
-  std::vector<uint64_t> capj(n_jobs), fcj(n_jobs), set_at(n_jobs + 1, 0), l_at(n_jobs + 1, 0), k_at(n_jobs + 1, 0);
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    const bool live = !seeds[j].empty();
-    capj[j] = live ? caps[j] : 0;
-    fcj[j] = live ? fringe_caps[j] : 0;
-    set_at[j + 1] = set_at[j] + (live ? nb_vis_slots(seeds[j].size(), capj[j]) + nb_kset_slots(capj[j]) : 0);
-    l_at[j + 1] = l_at[j] + std::max<uint64_t>(fcj[j], 1);
-    k_at[j + 1] = k_at[j] + std::max<uint64_t>(capj[j], 1);
-  }
-  Scratch m{c->misc};
-  const size_t o_sets = m.take<uint64_t>(set_at[n_jobs]);
-  const size_t o_refs = m.take<NbRef>(n_jobs), o_ctl = m.take<NbCtl>(n_jobs), o_start = m.take<uint64_t>(n_jobs + 1);
-  const size_t o_seeds = m.take<uint64_t>(n_all_seeds), o_sjob = m.take<uint32_t>(n_all_seeds);
-  const size_t o_pack = m.take<NbPack>(n_jobs);  // (ends the uploaded block)
-  const size_t o_l0 = m.take<uint64_t>(l_at[n_jobs]), o_l1 = m.take<uint64_t>(l_at[n_jobs]);
-  const size_t o_km = m.take<uint64_t>(k_at[n_jobs]), o_ct = m.take<uint32_t>(k_at[n_jobs]);
-  const size_t o_pk = m.take<uint64_t>(k_at[n_jobs]), o_pc = m.take<uint32_t>(k_at[n_jobs]), o_pf = m.take<uint64_t>(l_at[n_jobs]);
-  HIPC(c, m.ensure());
-  std::vector<uint8_t> up(o_pack - o_refs, 0);  // the uploaded block as the device holds it
-  NbRef *href = (NbRef *)up.data();
-  NbCtl *hctl = (NbCtl *)(up.data() + (o_ctl - o_refs));
-  uint64_t *hstart = (uint64_t *)(up.data() + (o_start - o_refs)), *hseeds = (uint64_t *)(up.data() + (o_seeds - o_refs));
-  uint32_t *hsjob = (uint32_t *)(up.data() + (o_sjob - o_refs));
-  uint64_t at = 0;
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    NbRef &nb = href[j];
-    const uint64_t vis_slots = seeds[j].empty() ? 0 : nb_vis_slots(seeds[j].size(), capj[j]);
-    nb.vis = m.at<uint64_t>(o_sets) + set_at[j];
-    nb.kset = nb.vis + vis_slots;
-    nb.vis_mask = vis_slots ? vis_slots - 1 : 0;
-    nb.kset_mask = seeds[j].empty() ? 0 : nb_kset_slots(capj[j]) - 1;
-    nb.list[0] = m.at<uint64_t>(o_l0) + l_at[j];
-    nb.list[1] = m.at<uint64_t>(o_l1) + l_at[j];
-    nb.kmers = m.at<uint64_t>(o_km) + k_at[j];
-    nb.counts = m.at<uint32_t>(o_ct) + k_at[j];
-    nb.cap = capj[j];
-    nb.fringe_cap = fcj[j];
-    nb.min_count = std::max(min_counts[j], 1u);
-    nb.max_levels = max_levels;
-    nb.k = (int)k;
-    hctl[j].cur_n = seeds[j].size();
-    hctl[j].status = seeds[j].empty() ? NB_COMPLETE : seeds[j].size() > NB_NARROW ? NB_WIDE : NB_RUN;
-    hstart[j] = at;
-    for (const uint64_t e : seeds[j]) {
-      hseeds[at] = e;
-      hsjob[at++] = j;
-    }
-  }
-  hstart[n_jobs] = at;
-  NbRef *drefs = m.at<NbRef>(o_refs);
-  NbCtl *dctl = m.at<NbCtl>(o_ctl);
-  HIPC(c, hipMemsetAsync(m.at<uint64_t>(o_sets), 0xFF, set_at[n_jobs] * 8, c->stream));  // every set ← EMPTY
-  HIPC(c, hipMemcpyAsync(drefs, up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
-  {
-    ScopedTimer t(c, SHK_K_EXTEND);
-    hipLaunchKernelGGL(k_nb_seed_panel, dim3((uint32_t)((n_all_seeds + WG - 1) / WG)), dim3(WG), 0, c->stream,
-                       (const NbRef *)drefs, dctl, (const uint64_t *)m.at<uint64_t>(o_seeds),
-                       (const uint32_t *)m.at<uint32_t>(o_sjob), (const uint64_t *)m.at<uint64_t>(o_start), n_all_seeds);
-  }
-  {
-    ScopedTimer t(c, SHK_K_EXTEND);
-    hipLaunchKernelGGL(k_nb_narrow_panel, dim3(n_jobs), dim3(NB_WG), 0, c->stream, c->tb, (const NbRef *)drefs, dctl);
-  }
-  HIPC(c, hipGetLastError());
-  std::vector<NbCtl> h(n_jobs);
-  HIPC(c, hipMemcpyAsync(h.data(), dctl, (size_t)n_jobs * sizeof(NbCtl), hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also: `up` has been read)
-  // the exception: a job with a level wider than a workgroup goes on alone, as in shk_neighborhood
-  for (uint32_t j = 0; j < n_jobs; ++j)
-    if (h[j].status == NB_WIDE) SHK_TRY(nb_run_levels(c, href[j], dctl + j, h[j]));
-  std::vector<NbPack> pk(n_jobs);
-  uint64_t tot_k = 0, tot_f = 0;
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    pk[j] = NbPack{h[j].k_n, h[j].status == NB_COMPLETE ? 0ull : h[j].cur_n, tot_k, tot_f, h[j].cur_sel, 0};
-    if (pk[j].k_n > capj[j] || pk[j].n_f > std::max<uint64_t>(fcj[j], seeds[j].size()))
-      return fail(c, SHK_ERR_INVARIANT, "job %u: %llu k-mers / %llu fringe entries beyond its capacities", j, pk[j].k_n, pk[j].n_f);
-    tot_k += pk[j].k_n;
-    tot_f += pk[j].n_f;
-  }
-  std::vector<uint64_t> hk(tot_k), hf(tot_f);
-  std::vector<uint32_t> hc(tot_k);
-  if (tot_k || tot_f) {
-    HIPC(c, hipMemcpyAsync(m.at<NbPack>(o_pack), pk.data(), (size_t)n_jobs * sizeof(NbPack), hipMemcpyHostToDevice, c->stream));
-    {
-      ScopedTimer t(c, SHK_K_EXTEND);
-      hipLaunchKernelGGL(k_nb_pack_panel, dim3(n_jobs), dim3(WG), 0, c->stream, (const NbRef *)drefs,
-                         (const NbPack *)m.at<NbPack>(o_pack), m.at<uint64_t>(o_pk), m.at<uint32_t>(o_pc), m.at<uint64_t>(o_pf));
-    }
-    HIPC(c, hipGetLastError());
-    if (tot_k) {
-      HIPC(c, hipMemcpyAsync(hk.data(), m.at<uint64_t>(o_pk), tot_k * 8, hipMemcpyDeviceToHost, c->stream));
-      HIPC(c, hipMemcpyAsync(hc.data(), m.at<uint32_t>(o_pc), tot_k * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (tot_f) HIPC(c, hipMemcpyAsync(hf.data(), m.at<uint64_t>(o_pf), tot_f * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-  }
-  for (uint32_t j = 0; j < n_jobs; ++j) {
-    const NbPack &p = pk[j];
-    nb_sorted_out(hk.data() + p.pack_k, hc.data() + p.pack_k, p.k_n, hf.data() + p.pack_f, p.n_f, kmers + out_at[j],
-                  counts + out_at[j], fringe_nodes + fr_at[j], fringe_dirs + fr_at[j]);
-    n_out[j] = p.k_n;
-    n_fringe[j] = p.n_f;
-    levels_done[j] = h[j].levels_done;
-  }
-  return SHK_OK;
+  return nb_panel_core(c, seeds.data(), n_jobs, min_counts, max_levels, caps, fringe_caps, out_at.data(), fr_at.data(), kmers, counts,
+                       n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
 }
 
 int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
@@ -506,30 +512,17 @@ int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_
         return fail(c, SHK_ERR_BAD_ARG, "gene %u: %s primer k-mer %llu is not a %u-mer", d / 2, dir_name[d & 1],
                     (ull)(i - primer_offsets[d]), k);
   }
+  std::vector<PcrPrimers> primers(n_genes);
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const uint64_t f0 = primer_offsets[2 * g], r0 = primer_offsets[2 * g + 1], r1 = primer_offsets[2 * g + 2];
+    primers[g] = PcrPrimers{primer_kmers + f0, primer_counts + f0, r0 - f0, primer_kmers + r0, primer_counts + r0, r1 - r0};
+  }
   std::vector<PcrGraph> gs;
   std::string msg;
-  const int rc = pcr_extend_panel_run(c, k, primer_kmers, primer_counts, primer_offsets, n_genes, params, &gs, threshold_used,
-                                      steps_run, &msg);
+  const int rc = pcr_extend_panel_run(c, k, primers.data(), n_genes, params, true, &gs, threshold_used, steps_run, &msg);
   if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood_panel's own text stands)
-  for (uint32_t g = 0; g < n_genes; ++g) {
-    node_offsets[g + 1] = node_offsets[g] + gs[g].sub_kmer.size();
-    edge_offsets[g + 1] = edge_offsets[g] + gs[g].esrc.size();
-    found_path[g] = gs[g].found_path ? 1u : 0u;
-  }
-  const uint64_t nn = node_offsets[n_genes], ne = edge_offsets[n_genes];
-  if (nn > node_cap || ne > edge_cap)
-    return fail(c, SHK_ERR_BAD_ARG, "panel of %llu nodes and %llu edges does not fit node_cap %llu / edge_cap %llu", (ull)nn,
-                (ull)ne, (ull)node_cap, (ull)edge_cap);
-  if ((nn && (!node_sub_kmers || !node_flags)) || (ne && (!edge_src || !edge_tgt || !edge_counts))) return SHK_ERR_BAD_ARG;
-  for (uint32_t g = 0; g < n_genes; ++g) {
-    const PcrGraph &gr = gs[g];
-    std::copy(gr.sub_kmer.begin(), gr.sub_kmer.end(), node_sub_kmers + node_offsets[g]);
-    std::copy(gr.flags.begin(), gr.flags.end(), node_flags + node_offsets[g]);
-    std::copy(gr.esrc.begin(), gr.esrc.end(), edge_src + edge_offsets[g]);
-    std::copy(gr.etgt.begin(), gr.etgt.end(), edge_tgt + edge_offsets[g]);
-    std::copy(gr.ecount.begin(), gr.ecount.end(), edge_counts + edge_offsets[g]);
-  }
-  return SHK_OK;
+  return pcr_graphs_out(c, "panel", gs, node_sub_kmers, node_flags, node_offsets, node_cap, edge_src, edge_tgt, edge_counts, edge_offsets,
+                        edge_cap, found_path);
 }
 
 int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,

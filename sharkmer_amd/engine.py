@@ -179,7 +179,7 @@ class PrunedGraph:
     unreachable_removed: int
 
 
-THREAD_TILE = 64  # the list elements one wave step of k_thread_reads covers (THREAD_TILE in csrc/shk_device.hip.h)
+THREAD_TILE = 64  # the list elements one wave step of the read walk (k_thread_panel) covers (THREAD_TILE in csrc/shk_device.hip.h)
 
 
 class _ThreadOut(C.Structure):

@@ -121,6 +121,13 @@ def rising():
     return _chain_case("rising", [4] * 1023, ((0, 1, 2), (1, 2, 1)), [1023, 1023, 1024, 1025], 3)
 
 
+def zigzag():
+    """One seed without a k-mer, 1023 chains of 5 levels and one of 4; the first chain forks at level 1 into a branch of
+    one node: 1025, 1024, 1025, 1024, 1023 — level 0 is the wide kernel's, level 1 fits a workgroup, level 2 is wide
+    again and level 3 goes back: the hand-over in both directions, twice."""
+    return _chain_case("zigzag", [1] + [5] * 1023 + [4], ((1, 1, 1),), [1025, 1024, 1025, 1024, 1023], 2)
+
+
 # ---- 2. complete de Bruijn graphs ---------------------------------------------------------------------------------
 
 def canonical_kmers(k):
@@ -194,6 +201,6 @@ def _lanes_case(i):
 
 # name → builder (built when asked for: a test module's collection stays cheap)
 CASES = {"flat%d" % n: (lambda n=n: flat(n)) for n in (1023, 1024, 1025, 2049)}
-CASES.update(falling=falling, rising=rising)
+CASES.update(falling=falling, rising=rising, zigzag=zigzag)
 CASES.update({"dense%d_%s" % (k, "all" if e else "one"): (lambda k=k, e=e: dense(k, e)) for k in (2, 3, 4, 5, 6, 7) for e in (False, True)})
 CASES.update({"lanes%d" % i: _lanes_case(i) for i in range(7)})

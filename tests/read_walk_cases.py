@@ -1,4 +1,4 @@
-"""One small batch per k that all four read walkers are held to — k_filter_reads, k_kmers_from_reads, k_thread_reads and
+"""One small batch per k that all four read walkers are held to — k_filter_reads, k_kmers_from_reads, k_thread_panel and
 k_filter_panel — shared by the CPU test of the batch itself (test_read_walk_cases_cpu.py) and the GPU test
 (test_gpu_read_walk.py).  The reads sit where the pieces the walkers share can go wrong: the 64-window step of the two
 wave-per-read kernels, an N or an invalid byte either side of it, the first and the last window of a read.
@@ -17,7 +17,7 @@ from __future__ import annotations
 import random
 from collections import namedtuple
 
-T = 64  # windows per wave step of k_thread_reads and k_filter_panel
+T = 64  # windows per wave step of k_thread_panel and k_filter_panel
 KS = (3, 21, 31)
 LONG = 200
 COMP = bytes.maketrans(b"ACGTN", b"TGCAN")

@@ -1,5 +1,5 @@
 """shk_neighborhood and shk_pcr_extend on the crafted tables of tests/nb_cases.py: levels of exactly 1023, 1024, 1025 and
-2049 entries and the cuts (max_levels, cap, fringe_cap) on the level where k_nb_narrow and k_nb_wide hand over, complete
+2049 entries and the cuts (max_levels, cap, fringe_cap) on the level where k_nb_narrow_panel and k_nb_wide hand over, complete
 de Bruijn graphs at k 2..7, thresholds met only by the saturating sum over lanes, a table grown under the graph.  Every
 table goes in through `insert` — no reads, no finalize — and every answer is compared with tests/pcr_ref.py over the
 same inserts merged in Python, arrays and order included.  tests/test_pcr_ref_cpu.py checks without a GPU that each
@@ -71,10 +71,11 @@ class Walk:
 
 # ---- 1. the hand-over sizes -------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", ["flat1023", "flat1024", "flat1025", "flat2049", "falling", "rising"])
+@pytest.mark.parametrize("name", ["flat1023", "flat1024", "flat1025", "flat2049", "falling", "rising", "zigzag"])
 def test_levels_at_the_hand_over_sizes(name):
     """Levels of exactly NB_NARROW − 1, NB_NARROW, NB_NARROW + 1 entries (and two workgroups' worth), flat, falling
-    through the hand-over and rising through it; fringe_cap at the three sizes (fewer than the seeds: refused), and on
+    through the hand-over, rising through it, and wide → narrow → wide → narrow (zigzag: the one-workgroup kernel launched
+    on the single job from the host's level loop, and handing back to it); fringe_cap at the three sizes (fewer than the seeds: refused), and on
     the hand-over level L every cut there is: max_levels L − 1, L, L + 1, cap |K_L| and |K_{L+1}| and one less each."""
     case = nb_cases.CASES[name]()
     table = nb_cases.merged_table(case.inserts)
@@ -93,6 +94,31 @@ def test_levels_at_the_hand_over_sizes(name):
             cut = w.check(cap=cap)
             assert cut[4] == (L + 1 if cap == w.ksz[L + 1] else L if cap >= w.ksz[L] else L - 1)
         assert w.resume(max_levels=2) == (len(case.sizes) + 1) // 2
+
+
+@pytest.mark.parametrize("name", ["rising", "zigzag", "dense5_one", "dense7_one"])
+def test_single_calls_around_a_panel_call(name):
+    """shk_neighborhood lays its scratch out as the panel does (it is the panel's one-job case): on one context a single
+    call, a panel of three jobs with other seeds and capacities, and the single call again with a smaller cap — each
+    against the model, so nothing of the layout before shows in the call after."""
+    case = nb_cases.CASES[name]()
+    table = nb_cases.merged_table(case.inserts)
+    with engine_for(case) as eng:
+        w = Walk(eng, case, table)
+        whole = w.check()
+        assert len(whole[0]) == len(table)
+        last = case.seeds[-1:]
+        jobs = [(case.seeds, case.dirs, w.mc, w.big["cap"], w.big["fringe_cap"]),   # the same job inside a panel
+                (last, [3], w.mc, 8, 64),                                           # one seed both ways, cut by its cap
+                (case.seeds[:7], case.dirs[:7], w.mc + 1, w.ksz[2], w.big["fringe_cap"])]
+        got = eng.neighborhood_panel(jobs, max_levels=3)
+        for j, (job, g) in enumerate(zip(jobs, got)):
+            want = ref.neighborhood(job[0], job[1], table, case.k, job[2], max_levels=3, cap=job[3], fringe_cap=job[4])
+            assert_neighborhood(g, want, (name, "job", j))
+        cut = w.check(cap=w.ksz[2] - 1)
+        assert cut[4] == 1 and len(cut[0]) < len(whole[0])
+        w.check(max_levels=2, cap=w.ksz[2])
+        w.check()
 
 
 # ---- 2. complete de Bruijn graphs -------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU tests of sPCR's graph extension over the device-resident table: shk_neighborhood (k_nb_narrow, k_nb_wide) and
+"""GPU tests of sPCR's graph extension over the device-resident table: shk_neighborhood (k_nb_narrow_panel, k_nb_wide) and
 shk_pcr_extend against tests/pcr_ref.py — the reference's create_seed_graph / extend_graph / threshold sweep and the
 level-by-level definition of the neighbourhood, restated literally over the CPU oracle's merged table.  Everything is
 compared as arrays, order included."""
@@ -79,6 +79,33 @@ def test_18s_end_to_end(orc, min_count, sweep):
     assert_graph(got, want, used, steps)
     assert_neighborhood(nb, ref.neighborhood(want.sub_kmer[:2], [1, 2], table, 21, 5))
     assert nb[4] > 1700 and len(nb[2]) == 0
+
+
+def test_18s_single_call_under_the_fetch_caps(orc, monkeypatch):
+    """shk_pcr_extend is shk_pcr_extend_panel's replay with one gene: SHK_PCR_FETCH_CAP sizes its fetches as it sizes the
+    panel's, the panel-only SHK_PCR_PANEL_FETCH_CAP does not touch it, and either way its graph is the model's and the
+    one pcr_extend_panel gives for that gene."""
+    bases, offsets, table = case_18s(orc)
+    a = dict(min_count=5, table_min_count=1, sweep=False, max_num_nodes=ref.DEFAULT_MAX_NUM_NODES)
+    for name in ("SHK_PCR_FETCH_CAP", "SHK_PCR_PANEL_FETCH_CAP", "SHK_PCR_PANEL_THREADS"):
+        monkeypatch.delenv(name, raising=False)
+    with sa.KmerEngine(21, 1, 100) as eng:
+        eng.ingest_reads(bases, offsets)
+        eng.finalize()
+        fwd, rev = eng.primer_pair_kmers(FWD_18S, REV_18S, trim=15, mismatches=2, min_count=3)
+        want, used, steps = ref.pcr_extend(fwd[:2], rev[:2], table, 21, 5, 1, 10.0, ref.DEFAULT_MAX_NUM_NODES, False)
+        assert want.found_path and len(want.sub_kmer) > 1700
+        for fetch_cap in (None, "64"):
+            for panel_cap in (None, "64"):
+                for env, value in (("SHK_PCR_FETCH_CAP", fetch_cap), ("SHK_PCR_PANEL_FETCH_CAP", panel_cap)):
+                    if value is None:
+                        monkeypatch.delenv(env, raising=False)
+                    else:
+                        monkeypatch.setenv(env, value)
+                what = (fetch_cap, panel_cap)
+                assert_graph(eng.pcr_extend(fwd, rev, **a), want, used, steps, what)
+                (one,) = eng.pcr_extend_panel([fwd, rev], a)
+                assert_graph(one, want, used, steps, what + ("panel",))
 
 
 # ---- 2. neighborhood on synthetic reads ---------------------------------------------------------------------------

@@ -78,11 +78,11 @@ def test_thread_reads_over_a_chain_cut_from_a_read(orc, k, where, monkeypatch, c
              np.array([e[1] for e in edges], dtype=np.uint32))
     with sa.KmerEngine(k, 1, 10) as eng:
         bases, offsets = eng._pack(b.reads)
-        trace(capfd, "thread_reads:")
+        trace(capfd, "thread_reads_panel:")
         got = eng.thread_reads(graph, bases, offsets)
-        lines = trace(capfd, "thread_reads:")
+        lines = trace(capfd, "thread_reads_panel:")  # (the single call is the panel of one gene, and says so)
         flags = eng.filter_reads(bases, offsets, canon)
-    assert len(lines) == 1 and "bytes in " + SET_WHERE[where] + "," in lines[0], lines
+    assert len(lines) == 1 and " 1 genes, " in lines[0] and " 1 genes in " + SET_WHERE[where] in lines[0], lines
     tot, una, links, counts, read_edges = ref.as_arrays(ref.thread_reads(g, b.reads, k), len(edges))
     assert got.read_edges.tolist() == read_edges
     assert got.support_total.tolist() == tot

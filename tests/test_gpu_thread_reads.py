@@ -1,7 +1,10 @@
-"""GPU tests of sPCR's read threading on the device: shk_thread_reads (k_thread_reads) against tests/thread_ref.py — the
-reference's thread_reads / thread_reads_paired restated literally.  Everything is integers and compared for equality, order
-included: support_total, support_unambiguous, the links, their counts, read_edges (and n_paired_links where mates are
-given).  Every test runs twice: with the lookup set in LDS and in global memory (SHK_THREAD_LDS_EDGES)."""
+"""GPU tests of sPCR's read threading on the device: shk_thread_reads — the one-gene case of shk_thread_reads_panel, run by
+k_thread_panel over the batch's reads in their order — against tests/thread_ref.py, the reference's thread_reads /
+thread_reads_paired restated literally.  Everything is integers and compared for equality, order included: support_total,
+support_unambiguous, the links, their counts, read_edges (and n_paired_links where mates are given).  Every test runs
+twice: with the lookup set in LDS and in global memory (SHK_THREAD_LDS_EDGES).  The panel's cuts (SHK_THREAD_PANEL_JOB,
+SHK_THREAD_PANEL_BLOCKS) apply to the single call too: section 6 runs it with job tails on both sides of a workgroup's 16
+waves."""
 import os
 
 import numpy as np
@@ -14,7 +17,7 @@ import thread_ref as ref
 
 pytestmark = pytest.mark.gpu
 
-T = THREAD_TILE  # list elements one wave step of k_thread_reads covers: a read's state crosses steps at multiples of it
+T = THREAD_TILE  # list elements one wave step of the read walk covers: a read's state crosses steps at multiples of it
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FWD_18S, REV_18S = "AACCTGGTTGATCCTGCCAGT", "TGATCCTTCTGCAGGTTCACCTAC"
 _cache = {}
@@ -27,20 +30,35 @@ _run = {}
 def variant(request, monkeypatch, capfd):
     """Graphs up to SHK_THREAD_LDS_EDGES edges keep their set in LDS (if it fits): 0 sends every graph to global memory,
     a large number every graph that fits to LDS (all of this file's do: the 18S graph is the largest).  With SHK_TRACE
-    set a launch says on stderr where its set lies; `launched` checks that it was where the test meant it to be."""
+    set a launch says on stderr how many genes' sets lie where (the single call is a panel of one gene); `launched` checks
+    that the one set was where the test meant it to be."""
     monkeypatch.setenv("SHK_THREAD_LDS_EDGES", "0" if request.param == "global" else "1000000")
     monkeypatch.setenv("SHK_TRACE", "1")
-    _run.update(capfd=capfd, where="set of %d bytes in " + ("global memory" if request.param == "global" else "LDS"))
+    for name in ("SHK_THREAD_PANEL_BLOCKS", "SHK_THREAD_PANEL_JOB"):
+        monkeypatch.delenv(name, raising=False)
+    _run.update(capfd=capfd, where="1 genes, %d jobs, %d blocks, " + ("0 genes in LDS, 1 genes in global memory" if request.param == "global"
+                                                                      else "1 genes in LDS, 0 genes in global memory"))
     return request.param
 
 
 def launched(n):
-    """The launches since the last look: n of them, each with its set where the variant puts it."""
-    lines = [x for x in _run["capfd"].readouterr().err.splitlines() if "thread_reads:" in x]
+    """The launches since the last look: n of them, each of one gene with its set where the variant puts it → [(jobs, blocks)]."""
+    lines = [x for x in _run["capfd"].readouterr().err.splitlines() if "thread_reads_panel:" in x]
     assert len(lines) == n, lines
+    cuts = []
     for x in lines:
-        size = int(x.split("set of ")[1].split()[0])
-        assert _run["where"] % size in x, x
+        jobs, blocks = int(x.split(" genes, ")[1].split()[0]), int(x.split(" jobs, ")[1].split()[0])
+        assert x.endswith(_run["where"] % (jobs, blocks)), x
+        cuts.append((jobs, blocks))
+    return cuts
+
+
+def to_device(bases, offsets):
+    import torch
+    db = torch.from_numpy(np.ascontiguousarray(bases, dtype=np.uint8).copy()).to("cuda:0")
+    do = torch.from_numpy(np.ascontiguousarray(offsets).astype(np.int64)).to("cuda:0")
+    torch.cuda.synchronize()
+    return db, do
 
 
 def graph_arrays(g):
@@ -48,12 +66,17 @@ def graph_arrays(g):
             np.array([e[1] for e in g.edges], dtype=np.uint32))
 
 
-def check(eng, g, reads, k, read_index=None, mate=None, what=None):
+def check(eng, g, reads, k, read_index=None, mate=None, what=None, want=None, device=False):
+    """want: the model's answer where the caller keeps it (the same batch under several cuts); device: the device form."""
     bases, offsets = eng._pack(reads)
+    if device:
+        bases, offsets = to_device(bases, offsets)
     launched(0)
-    got = eng.thread_reads(graph_arrays(g), bases, offsets, read_index, mate)
-    launched(1 if g.edges and reads else 0)
-    if mate is None:
+    got = eng.thread_reads(graph_arrays(g), bases, offsets, read_index, mate, device=device)
+    _run["cuts"] = launched(1 if g.edges and reads else 0)
+    if want is not None:
+        pass
+    elif mate is None:
         want = ref.thread_reads(g, reads, k)
     else:
         want = ref.thread_reads_paired(g, reads, read_index, mate, k)
@@ -280,3 +303,56 @@ def test_argument_errors_and_link_cap():
             eng.thread_reads((np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint32)),
                              *eng._pack([b"ACGT"]))
         assert e.value.code == -2 and "k >= 2" in e.value.msg
+
+
+# ---- 6. the panel's cuts under the single call -------------------------------------------------------------------------------
+
+TAIL_SIZES = (1, 15, 16, 17, 33)  # a job tail on both sides of the 16 waves of a workgroup; 33: two full slices and one read
+_tails, _paired = {}, {}
+
+
+def tail_batches():
+    """Per crafted k = 3 case that has edges and reads, and per size: the case's reads taken round and round up to that
+    many, and the model's answer — computed once, the same under every cut."""
+    if not _tails:
+        for name, g, reads in tc.crafted_cases():
+            if g.edges and reads:
+                for n in TAIL_SIZES:
+                    batch = [reads[i % len(reads)] for i in range(n)]
+                    _tails[name, n] = (g, batch, ref.thread_reads(g, batch, 3))
+    return _tails
+
+
+def paired_batch():
+    """Mates 0 / 1 / 2 mixed over the branch graph; a read of fewer than k bases and an empty one as somebody's mate.  Pair
+    p is reads 2p and 2p + 1: only pair 0 has an R1 and an R2 that both map."""
+    if not _paired:
+        g = tc.branch_graph()
+        reads = [b"AACG", b"ACG", b"AA", b"AACGG", b"TTTT", b"AAC", b"AACG", tc.rc_bytes(b"AACG"), b"AAC", b"", b"ACG", b"AACG", b"AACGG"]
+        mate = [1, 2, 1, 2, 1, 2, 0, 0, 1, 2, 2, 2, 0]
+        read_index = list(range(len(reads)))
+        want = ref.thread_reads_paired(g, reads, read_index, mate, 3)
+        assert want.n_paired_links == 1 and want.read_edges[2] == 0 and sum(1 for x in want.read_edges if x) >= 8
+        _paired["batch"] = (g, reads, read_index, mate, want)
+    return _paired["batch"]
+
+
+@pytest.mark.parametrize("blocks", ["1", "2", None])
+@pytest.mark.parametrize("job", ["1", "5", None])
+def test_job_tails_and_block_caps_under_the_single_call(monkeypatch, job, blocks):
+    """SHK_THREAD_PANEL_JOB and SHK_THREAD_PANEL_BLOCKS cut the single call as they cut a panel: every batch of
+    tail_batches and the paired batch (host and device form) under job sizes 1, 5 and the default 16 and 1, 2 and
+    unbounded workgroups, against the model, every array."""
+    if blocks:
+        monkeypatch.setenv("SHK_THREAD_PANEL_BLOCKS", blocks)
+    if job:
+        monkeypatch.setenv("SHK_THREAD_PANEL_JOB", job)
+    per_job = int(job or 16)
+    with sa.KmerEngine(3, 1, 100) as eng:
+        for (name, n), (g, batch, want) in tail_batches().items():
+            check(eng, g, batch, 3, what=(name, n, job, blocks), want=want)
+            ((n_jobs, n_blocks),) = _run["cuts"]
+            assert n_jobs == (n + per_job - 1) // per_job and 1 <= n_blocks <= min(n_jobs, int(blocks or n_jobs))
+        g, reads, read_index, mate, want = paired_batch()
+        for device in (False, True):
+            check(eng, g, reads, 3, read_index, mate, what=("paired", job, blocks, device), want=want, device=device)
