@@ -666,6 +666,106 @@ int shk_pcr_prune_panel(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint
                         const uint32_t *edge_src, const uint32_t *edge_tgt, const uint32_t *edge_counts, const uint64_t *edge_offsets,
                         uint32_t n_genes, const shk_pcr_prune_params *params /* n_genes */, shk_pcr_prune_out *out);
 
+/* ---- the last stage of do_pcr: paths, sequences, scores, dedup (src/pcr/mod.rs:699-813) ---- */
+
+/* A panel's pruned graphs with their optional threading annotations, as the earlier stages emit them. */
+typedef struct shk_pcr_graphs {
+  uint32_t n_genes; uint32_t reserved;
+  /* the output layout of shk_pcr_prune_panel: offsets n_genes + 1 each, endpoints LOCAL to the gene */
+  const uint64_t *node_sub_kmers; const uint8_t *node_flags; const uint64_t *node_offsets;
+  const uint32_t *edge_src, *edge_tgt, *edge_counts; const double *coverage_ratio; const uint64_t *edge_offsets;
+  /* the layout of shk_thread_panel_out; all may be NULL (no gene has annotations then).  has_threading[g] != 0: gene g
+   * was threaded (its read list was not empty, mod.rs:664-697); NULL with annotations present: every gene was. */
+  const uint32_t *support_total, *support_unambiguous; const uint64_t *link_offsets;
+  const uint32_t *link_in, *link_out, *link_counts; const uint8_t *has_threading;
+} shk_pcr_graphs;
+
+typedef struct shk_pcr_paths_params {  /* PCRParams, with the reference's defaults */
+  uint64_t min_length, max_length;     /* [0] [10000] */
+  uint64_t max_dfs_states;             /* [100000] */
+  uint64_t max_paths_per_pair;         /* [20], counted per start node */
+  uint64_t max_node_visits;            /* [2] */
+} shk_pcr_paths_params;
+
+#define SHK_PCR_SCORE_FIELDS 6  /* kmer_min_count, coverage_cv, max_coverage_ratio, zero_support_edges,
+                                   median_unambiguous_support, edge_support_fraction; NaN stands for None */
+typedef struct shk_pcr_records {        /* every pointer optional except record_offsets */
+  uint64_t *record_offsets;             /* [n_genes + 1] gene g's records are [record_offsets[g], record_offsets[g+1]) */
+  uint64_t *seq_offsets;                /* [record_cap + 1] record r's bases are seqs[seq_offsets[r] .. seq_offsets[r+1]) */
+  uint8_t  *seqs;                       /* ASCII */
+  uint64_t  record_cap, seq_cap;
+  uint64_t  n_records, n_seq_bytes;     /* OUT: what the call produced — the need when a capacity was too small */
+  uint32_t *start_node;                 /* per record: the path's first node, local to the gene */
+  uint64_t *path_nodes;                 /* per record: nodes on the path */
+  double   *count_mean, *count_median; uint64_t *count_min, *count_max;
+  double   *score;                      /* PathScore::composite */
+  double   *score_fields;               /* [SHK_PCR_SCORE_FIELDS per record] */
+  uint64_t *paths_found, *generated, *states_explored;  /* [n_genes]: paths of get_assembly_paths, records of
+                                           generate_sequences_from_paths, DFS pops summed over the gene's start nodes */
+} shk_pcr_records;
+
+/* resolve_bubbles → get_assembly_paths → generate_sequences_from_paths (pcr/bubble.rs:52-275, pcr/paths.rs:78-356) for
+ * every gene of a panel, on the host (no context, no device: the search is one dependent chain), on a
+ * few threads over genes (SHK_PCR_PANEL_THREADS, default 8, clamped to 1..16).
+ * SEMANTICS, per gene, exactly the reference.  A node's outgoing (incoming) edges are taken newest first, i.e. in
+ *   DESCENDING edge index: petgraph links a new edge at the head of its node's list and the pruning only removes.
+ *   sorted_children visits by count × preference descending, equal scores in ASCENDING edge index (stable ascending
+ *   sort, popped from the back).  Bubble preferences exist only for a gene with annotations: sources in ascending node
+ *   index, branches along single-out-edge nodes for at most 50 steps, evidence = Σ support_total + Σ link_counts of
+ *   (edge into the source, first edge) in wrapping u32, ranked by evidence descending then edge k-mer ascending,
+ *   preference evidence / max (1.0 when max is 0), later writes replace earlier ones.  One search per start node in
+ *   ascending node index; states_explored counts every pop; an end node at >= min_path_nodes is recorded and not
+ *   extended, below it is walked through; the start node itself is never tested.  Records: the start node's (k-1)-mer
+ *   plus one base per step; shorter than min_length or without edges: skipped.  Without annotations the three
+ *   read-support fields are NaN (None) and the composite takes no read-support factor.
+ * OUT: per gene the records in enumeration order.  record_cap / seq_cap too small: SHK_ERR_BAD_ARG with n_records,
+ *   n_seq_bytes, record_offsets and the per-gene counters complete.
+ * Errors, SHK_ERR_BAD_ARG with a text in err that names the gene: an endpoint >= the gene's node count, decreasing
+ *   offsets, a flag above 3, k < 2 or k > 31, a sub-k-mer above the (k-1)-base mask, a link edge >= the gene's edge
+ *   count, n_genes > SHK_PCR_MAX_GENES.  Host memory that cannot be had: SHK_ERR_NOMEM. */
+int shk_pcr_paths_panel(uint32_t k, const shk_pcr_graphs *graphs, const shk_pcr_paths_params *params /* n_genes */,
+                        shk_pcr_records *out, char *err, size_t err_cap);
+
+/* 1 when the Levenshtein distance of a[0..la) and b[0..lb) is <= t, else 0: what bounded_levenshtein(a, b, t).is_some()
+ * answers (paths.rs:388-391).  Banded two-row DP over bytes, any alphabet, any lengths, any t. */
+int shk_edit_within(const uint8_t *a, uint64_t la, const uint8_t *b, uint64_t lb, uint32_t t);
+
+#define SHK_PCR_MAX_AMPLICONS 20  /* MAX_NUM_AMPLICONS, paths.rs:20 */
+typedef struct shk_pcr_dedup_out {      /* every pointer optional */
+  uint32_t *kept;                       /* [SHK_PCR_MAX_AMPLICONS * n_genes] gene g's kept records at 20 g ..: indices
+                                           into the gene's input records, in final order; returned[g] of them */
+  uint32_t *generated, *retained, *returned;  /* [n_genes]: records in, kept before truncation, kept */
+  uint32_t *order;                      /* [record_offsets[n_genes]] per gene: sorted position -> input index */
+  uint64_t *pair_words;                 /* the within-t bits of all pairs i < j of the SORTED order, gene g's at word
+                                           pair_offsets[g]: pair (i, j) of m records is bit i(2m-i-1)/2 + j-i-1 */
+  uint64_t *pair_offsets;               /* [n_genes + 1], in 64-bit words */
+  uint64_t  pair_cap;                   /* words of pair_words */
+  uint64_t  pairs_device, pairs_host, pairs_prefiltered;  /* OUT: how the pairs were decided */
+  double    device_ms;                  /* event time of the call's launch */
+} shk_pcr_dedup_out;
+
+/* sort_and_deduplicate (paths.rs:360-427) for every gene of a panel.  IN: gene g's records are
+ * [record_offsets[g], record_offsets[g+1]); record r is the ACGT bytes seqs[seq_offsets[r] .. seq_offsets[r+1]) with
+ * scores[r]; thresholds[g] is the gene's dedup_edit_threshold.  The host sorts each gene by score descending
+ * (total_cmp) then bytes ascending; the within-t relation of ALL pairs of the sorted order is computed — by K_DEDUP on
+ * the device (one lane per pair, Landau-Vishkin over 2-bit packed words), or by shk_edit_within on the
+ * host for a gene with t > 31 or a record of 2^30 bases or more, and for the whole call when its pairs that need an
+ * alignment number fewer than SHK_DEDUP_DEVICE_PAIRS (read at each call; 0 = always the device; never changes a
+ * result).  Pairs with |la - lb| > t (0) or t >= max(la, lb) (1) need none.  Then greedily: a record is kept exactly
+ * when no earlier KEPT record is within t; at most SHK_PCR_MAX_AMPLICONS are returned.  With SHK_TRACE set the call
+ * prints one line to stderr: genes, pairs on the device, on the host, decided by the prefilters.
+ * Errors: SHK_ERR_BAD_ARG naming the gene or record for decreasing offsets, a byte outside ACGT, n_genes >
+ * SHK_PCR_MAX_GENES, pair_cap too small (pair_offsets complete).  Scratch that cannot be had: SHK_ERR_NOMEM, the context
+ * stays usable.  State: as shk_pcr_prune_panel — the table is not touched, any state, owner shares, first device. */
+int shk_pcr_dedup_panel(shk_ctx *ctx, const uint8_t *seqs, const uint64_t *seq_offsets, const uint64_t *record_offsets,
+                        const double *scores, const uint32_t *thresholds, uint32_t n_genes, shk_pcr_dedup_out *out);
+
+/* shk_pcr_paths_panel, then shk_pcr_dedup_panel with thresholds[g], then the renumbering of mod.rs:785-813: out holds
+ * the final products per gene in product order 0, 1, .. (record_offsets[g+1] - record_offsets[g] of them); generated[g]
+ * counts the records before the dedup, retained[g] (optional) those kept before the truncation.  k is the context's. */
+int shk_pcr_products_panel(shk_ctx *ctx, const shk_pcr_graphs *graphs, const shk_pcr_paths_params *params,
+                           const uint32_t *thresholds, shk_pcr_records *out, uint32_t *retained, double *device_ms);
+
 /* ---- multi-GPU hooks (device pointers; exchanged by the caller over RCCL) ---- */
 
 /* Table geometry needed to shard by owner: n_pages (power of two),

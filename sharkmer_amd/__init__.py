@@ -10,6 +10,7 @@ from .engine import (  # noqa: F401
     KmerEngine, ShkError, N_READS_PER_BATCH, lib_path, load_library,
     FLAG_TIMING, FLAG_FORCE_DIRECT, FLAG_FORCE_PAGED, FLAG_DEFER_ERRORS, FLAG_TIMING_SAMPLED, KERNEL_NAMES, RESERVE_NONE,
     Primer, primer_compile, PRIMER_LEVELS, PcrGraph, PrunedGraph, pcr_node_budget,
+    PcrProducts, DedupResult, pcr_paths_panel, edit_within, PCR_SCORE_FIELDS, PCR_MAX_AMPLICONS,
     PackedReads, pack_reads, release_cached_memory, FastqReader, write_histo, write_final_histo, write_stats_yaml, validate_args, run_files,
 )
 from .synth import SynthSpec, synth_reads  # noqa: F401

@@ -11,6 +11,8 @@
 #include "shk_front.h"
 #include "shk_primer.h"
 #include "shk_pcr.h"
+#include "shk_products.h"
+#include "shk_dedup_core.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3491,3 +3493,6 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 #include "shk_reads_api.hip.h"
 // shk_pcr_prune_panel: the graphs of a panel pruned between extension and threading; the table is left alone
 #include "shk_prune_api.hip.h"
+// shk_pcr_dedup_panel, shk_pcr_products_panel: the dedup's pair matrix on the device, the products of a panel; the table
+// is left alone
+#include "shk_products_api.hip.h"

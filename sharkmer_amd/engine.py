@@ -205,6 +205,215 @@ class ThreadingAnnotations:
     n_paired_links: int              # paired_links.len(); 0 for the unpaired form
 
 
+class _PcrGraphs(C.Structure):
+    _fields_ = [("n_genes", C.c_uint32), ("reserved", C.c_uint32), ("node_sub_kmers", C.c_void_p), ("node_flags", C.c_void_p),
+                ("node_offsets", C.c_void_p), ("edge_src", C.c_void_p), ("edge_tgt", C.c_void_p), ("edge_counts", C.c_void_p),
+                ("coverage_ratio", C.c_void_p), ("edge_offsets", C.c_void_p), ("support_total", C.c_void_p),
+                ("support_unambiguous", C.c_void_p), ("link_offsets", C.c_void_p), ("link_in", C.c_void_p), ("link_out", C.c_void_p),
+                ("link_counts", C.c_void_p), ("has_threading", C.c_void_p)]
+
+
+class _PcrPathsParams(C.Structure):
+    _fields_ = [("min_length", C.c_uint64), ("max_length", C.c_uint64), ("max_dfs_states", C.c_uint64),
+                ("max_paths_per_pair", C.c_uint64), ("max_node_visits", C.c_uint64)]
+
+
+class _PcrRecords(C.Structure):
+    _fields_ = [("record_offsets", C.c_void_p), ("seq_offsets", C.c_void_p), ("seqs", C.c_void_p), ("record_cap", C.c_uint64),
+                ("seq_cap", C.c_uint64), ("n_records", C.c_uint64), ("n_seq_bytes", C.c_uint64), ("start_node", C.c_void_p),
+                ("path_nodes", C.c_void_p), ("count_mean", C.c_void_p), ("count_median", C.c_void_p), ("count_min", C.c_void_p),
+                ("count_max", C.c_void_p), ("score", C.c_void_p), ("score_fields", C.c_void_p), ("paths_found", C.c_void_p),
+                ("generated", C.c_void_p), ("states_explored", C.c_void_p)]
+
+
+class _PcrDedupOut(C.Structure):
+    _fields_ = [("kept", C.c_void_p), ("generated", C.c_void_p), ("retained", C.c_void_p), ("returned", C.c_void_p),
+                ("order", C.c_void_p), ("pair_words", C.c_void_p), ("pair_offsets", C.c_void_p), ("pair_cap", C.c_uint64),
+                ("pairs_device", C.c_uint64), ("pairs_host", C.c_uint64), ("pairs_prefiltered", C.c_uint64),
+                ("device_ms", C.c_double)]
+
+
+PCR_SCORE_FIELDS = ("kmer_min_count", "coverage_cv", "max_coverage_ratio", "zero_support_edges", "median_unambiguous_support",
+                    "edge_support_fraction")  # SHK_PCR_SCORE_FIELDS; NaN stands for None
+PCR_MAX_AMPLICONS = 20  # SHK_PCR_MAX_AMPLICONS = MAX_NUM_AMPLICONS (pcr/paths.rs:20)
+
+
+def _fmt_f64(x: float) -> str:
+    """Rust's `{}` of an f64 for the values a median takes: 12, 12.5 (never 12.0)."""
+    x = float(x)
+    return str(int(x)) if x == int(x) else repr(x)
+
+
+@dataclass
+class PcrProducts:
+    """A gene's records: what generate_sequences_from_paths made, in enumeration order (pcr_paths_panel), or the final
+    products after sort_and_deduplicate in product order 0, 1, .. (pcr_products_panel); one entry per record."""
+    sequences: list             # str, ACGT
+    start_node: np.ndarray      # u32: the path's first node
+    path_nodes: np.ndarray      # u64: nodes on the path
+    count_mean: np.ndarray      # f64
+    count_median: np.ndarray    # f64
+    count_min: np.ndarray       # u64
+    count_max: np.ndarray       # u64
+    score: np.ndarray           # f64, PathScore::composite
+    score_fields: np.ndarray    # n × 6 f64 in the order of PCR_SCORE_FIELDS, NaN = None
+    paths_found: int            # get_assembly_paths' paths
+    generated: int              # records before the dedup
+    states_explored: int        # DFS pops, summed over the start nodes
+    retained: int | None = None  # records the dedup kept before the truncation to 20 (pcr_products_panel only)
+
+    def fasta(self, sample: str, gene_name: str) -> str:
+        """The reference's FASTA records (pcr/paths.rs:331-343 with product = the record's position, as mod.rs:785-813
+        renumbers them), each one header line and one sequence line."""
+        out = []
+        for i, seq in enumerate(self.sequences):
+            out.append(f">{sample}_{gene_name}_{i} sample={sample} gene={gene_name} product={i} length={len(seq)} "
+                       f"kmer_count_mean={float(self.count_mean[i]):.2f} kmer_count_median={_fmt_f64(self.count_median[i])} "
+                       f"kmer_count_min={int(self.count_min[i])} kmer_count_max={int(self.count_max[i])} "
+                       f"score={float(self.score[i]):.2f}\n{seq}\n")
+        return "".join(out)
+
+
+@dataclass
+class DedupResult:
+    """A gene's answer of pcr_dedup_panel."""
+    kept: np.ndarray            # u32: the records kept, indices into the gene's input, in final order (at most 20)
+    generated: int
+    retained: int               # kept before the truncation
+    order: np.ndarray           # u32: sorted position -> input index
+    pair_bits: np.ndarray | None  # bool per pair i < j of the sorted order, row-major upper triangle (want_pairs=True)
+
+
+def _per_gene(value, ng: int, name: str) -> list:
+    vals = list(value) if np.ndim(value) else [value] * ng
+    if len(vals) != ng:
+        raise ValueError(f"one {name} for all genes or one per gene")
+    return vals
+
+
+def _cat(parts, dtype):
+    off = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        off[1:] = np.cumsum([len(x) for x in parts])
+    return (np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(0, dtype=dtype)), off
+
+
+def _pcr_graphs(graphs, annotations):
+    """(shk_pcr_graphs, the arrays it points into) from the list pcr_prune_panel returns — or (node_sub_kmers, node_flags,
+    edge_src, edge_tgt, edge_counts, coverage_ratio) tuples — and the list thread_reads_panel returns, None entries
+    allowed."""
+    gs = [(g.node_sub_kmers, g.node_flags, g.edge_src, g.edge_tgt, g.edge_counts, g.coverage_ratio) if isinstance(g, PrunedGraph) else g
+          for g in graphs]
+    ng = len(gs)
+    cols = [[np.ascontiguousarray(g[i], dtype=dt).reshape(-1) for g in gs]
+            for i, dt in enumerate((np.uint64, np.uint8, np.uint32, np.uint32, np.uint32, np.float64))]
+    if any(len(a) != len(b) for a, b in zip(cols[0], cols[1])):
+        raise ValueError("node_sub_kmers and node_flags differ in length")
+    if any(len({len(c[g]) for c in cols[2:]}) != 1 for g in range(ng)):
+        raise ValueError("edge_src, edge_tgt, edge_counts and coverage_ratio differ in length")
+    sub, noff = _cat(cols[0], np.uint64)
+    fl, _ = _cat(cols[1], np.uint8)
+    es, eoff = _cat(cols[2], np.uint32)
+    et, _ = _cat(cols[3], np.uint32)
+    ec, _ = _cat(cols[4], np.uint32)
+    ratio, _ = _cat(cols[5], np.float64)
+    keep = [sub, fl, noff, es, et, ec, ratio, eoff]
+    G = _PcrGraphs(ng, 0, sub.ctypes.data, fl.ctypes.data, noff.ctypes.data, es.ctypes.data, et.ctypes.data, ec.ctypes.data,
+                   ratio.ctypes.data, eoff.ctypes.data, None, None, None, None, None, None, None)
+    if annotations is not None and any(a is not None for a in annotations):
+        if len(annotations) != ng:
+            raise ValueError("one annotations entry (or None) per graph")
+        tot, una, lks, lcs = [], [], [], []
+        for g, a in enumerate(annotations):
+            ne = len(cols[2][g])
+            if a is None:
+                tot.append(np.zeros(ne, dtype=np.uint32)), una.append(np.zeros(ne, dtype=np.uint32))
+                lks.append(np.zeros((0, 2), dtype=np.uint32)), lcs.append(np.zeros(0, dtype=np.uint32))
+                continue
+            if len(a.support_total) != ne or len(a.support_unambiguous) != ne:
+                raise ValueError("annotations take one support entry per edge")
+            tot.append(np.ascontiguousarray(a.support_total, dtype=np.uint32))
+            una.append(np.ascontiguousarray(a.support_unambiguous, dtype=np.uint32))
+            lks.append(np.ascontiguousarray(a.links, dtype=np.uint32).reshape(-1, 2))
+            lcs.append(np.ascontiguousarray(a.link_counts, dtype=np.uint32).reshape(-1))
+        st, _ = _cat(tot, np.uint32)
+        su, _ = _cat(una, np.uint32)
+        li, loff = _cat([np.ascontiguousarray(x[:, 0]) for x in lks], np.uint32)
+        lo, _ = _cat([np.ascontiguousarray(x[:, 1]) for x in lks], np.uint32)
+        lc, _ = _cat(lcs, np.uint32)
+        has = np.array([a is not None for a in annotations], dtype=np.uint8)
+        keep += [st, su, loff, li, lo, lc, has]
+        G.support_total, G.support_unambiguous, G.link_offsets = st.ctypes.data, su.ctypes.data, loff.ctypes.data
+        G.link_in, G.link_out, G.link_counts, G.has_threading = li.ctypes.data, lo.ctypes.data, lc.ctypes.data, has.ctypes.data
+    return G, keep
+
+
+def _pcr_params(ng, min_length, max_length, max_dfs_states, max_paths_per_pair, max_node_visits):
+    cols = [_per_gene(v, ng, n) for v, n in ((min_length, "min_length"), (max_length, "max_length"), (max_dfs_states, "max_dfs_states"),
+                                             (max_paths_per_pair, "max_paths_per_pair"), (max_node_visits, "max_node_visits"))]
+    prm = (_PcrPathsParams * max(ng, 1))()
+    for g in range(ng):
+        prm[g] = _PcrPathsParams(*(int(c[g]) for c in cols))
+    return prm
+
+
+def _pcr_records_call(ng, call, retained=None):
+    """Runs call(records struct) with room that grows once to what the call says it needs; one PcrProducts per gene."""
+    roff = np.zeros(ng + 1, dtype=np.uint64)
+    found, gen, states = (np.zeros(max(ng, 1), dtype=np.uint64) for _ in range(3))
+    rcap, scap = max(64 * ng, 1), max(1 << 16, 1)
+    for attempt in (0, 1):
+        soff = np.zeros(rcap + 1, dtype=np.uint64)
+        seqs = np.zeros(scap, dtype=np.uint8)
+        start = np.zeros(rcap, dtype=np.uint32)
+        nodes, cmin, cmax = (np.zeros(rcap, dtype=np.uint64) for _ in range(3))
+        mean, med, score = (np.zeros(rcap, dtype=np.float64) for _ in range(3))
+        fields = np.zeros((rcap, len(PCR_SCORE_FIELDS)), dtype=np.float64)
+        R = _PcrRecords(roff.ctypes.data, soff.ctypes.data, seqs.ctypes.data, rcap, scap, 0, 0, start.ctypes.data, nodes.ctypes.data,
+                        mean.ctypes.data, med.ctypes.data, cmin.ctypes.data, cmax.ctypes.data, score.ctypes.data, fields.ctypes.data,
+                        found.ctypes.data, gen.ctypes.data, states.ctypes.data)
+        rcode, check = call(R)
+        if attempt == 0 and rcode == -2 and (R.n_records > rcap or R.n_seq_bytes > scap):  # too small: it says what it needs
+            rcap, scap = max(rcap, int(R.n_records)), max(scap, int(R.n_seq_bytes))
+            continue
+        check(rcode)
+        break
+    res = []
+    for g in range(ng):
+        a, b = int(roff[g]), int(roff[g + 1])
+        ss = [seqs[int(soff[r]):int(soff[r + 1])].tobytes().decode("ascii") for r in range(a, b)]
+        res.append(PcrProducts(ss, start[a:b].copy(), nodes[a:b].copy(), mean[a:b].copy(), med[a:b].copy(), cmin[a:b].copy(),
+                               cmax[a:b].copy(), score[a:b].copy(), fields[a:b].copy(), int(found[g]), int(gen[g]), int(states[g]),
+                               None if retained is None else int(retained[g])))
+    return res
+
+
+def pcr_paths_panel(k: int, graphs, annotations=None, min_length=0, max_length=10000, max_dfs_states=100000, max_paths_per_pair=20,
+                    max_node_visits=2) -> list:
+    """resolve_bubbles, get_assembly_paths and generate_sequences_from_paths (pcr/bubble.rs, pcr/paths.rs:78-356) for
+    every gene of a panel on the host, no device (shk_pcr_paths_panel) → one PcrProducts per gene, records in
+    enumeration order.  graphs: the list pcr_prune_panel returns; annotations: the list thread_reads_panel returns, with
+    None for a gene that had no reads; each parameter one value for all genes or one per gene."""
+    L = load_library()
+    G, keep = _pcr_graphs(graphs, annotations)
+    ng = G.n_genes
+    prm = _pcr_params(ng, min_length, max_length, max_dfs_states, max_paths_per_pair, max_node_visits)
+    err = C.create_string_buffer(1024)
+
+    def check(rc):
+        if rc != 0:
+            raise ShkError(rc, err.value.decode("utf-8", "replace"))
+
+    return _pcr_records_call(ng, lambda R: (L.shk_pcr_paths_panel(k, C.byref(G), prm, C.byref(R), err, len(err)), check))
+
+
+def edit_within(a, b, t: int) -> bool:
+    """Levenshtein distance of two byte strings <= t (shk_edit_within): bounded_levenshtein(a, b, t).is_some()."""
+    a = a.encode("latin-1") if isinstance(a, str) else bytes(a)
+    b = b.encode("latin-1") if isinstance(b, str) else bytes(b)
+    return bool(load_library().shk_edit_within(a, len(a), b, len(b), t))
+
+
 def pcr_node_budget(n_bases_ingested: int) -> int:
     """compute_node_budget (pcr/graph.rs:40-52)."""
     return int(load_library().shk_pcr_node_budget(n_bases_ingested))
@@ -234,7 +443,7 @@ ABI_SYMBOLS = [
     "shk_packed_sizes", "shk_pack_reads", "shk_ingest_packed", "shk_ingest_packed_device", "shk_pack_reads_device",
     "shk_unpack_reads_device",
     "shk_neighborhood", "shk_pcr_extend", "shk_pcr_node_budget", "shk_neighborhood_panel", "shk_pcr_extend_panel",
-    "shk_pcr_prune_panel",
+    "shk_pcr_prune_panel", "shk_pcr_paths_panel", "shk_edit_within", "shk_pcr_dedup_panel", "shk_pcr_products_panel",
     "shk_thread_reads", "shk_thread_reads_device", "shk_thread_reads_panel", "shk_thread_reads_panel_device",
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
 ]
@@ -365,6 +574,10 @@ def load_library():
     L.shk_neighborhood_panel.argtypes = [vp, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.shk_pcr_extend_panel.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
     L.shk_pcr_prune_panel.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, C.POINTER(_PcrPruneOut)]
+    L.shk_pcr_paths_panel.argtypes = [u32, C.POINTER(_PcrGraphs), vp, C.POINTER(_PcrRecords), C.c_char_p, C.c_size_t]
+    L.shk_edit_within.argtypes = [C.c_char_p, u64, C.c_char_p, u64, u32]
+    L.shk_pcr_dedup_panel.argtypes = [vp, vp, vp, vp, vp, vp, u32, C.POINTER(_PcrDedupOut)]
+    L.shk_pcr_products_panel.argtypes = [vp, C.POINTER(_PcrGraphs), vp, vp, C.POINTER(_PcrRecords), vp, C.POINTER(C.c_double)]
     L.shk_thread_reads.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_device.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, u64, u64, vp, vp, C.POINTER(_ThreadOut)]
     L.shk_thread_reads_panel.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(_ThreadPanelOut)]
@@ -886,6 +1099,71 @@ class KmerEngine:
             res.append(PrunedGraph(osub[a:b].copy(), ofl[a:b].copy(), oes[x:y].copy(), oet[x:y].copy(), oec[x:y].copy(), oni[a:b].copy(),
                                    oei[x:y].copy(), ratio[x:y].copy(), float(med[g]), keep[v0:v1].copy(), int(rounds[g]), int(tips[g]),
                                    int(unreach[g])))
+        return res
+
+    def pcr_dedup_panel(self, records, scores, dedup_edit_threshold=10, want_pairs: bool = False) -> list:
+        """sort_and_deduplicate (pcr/paths.rs:360-427) for every gene of a panel (shk_pcr_dedup_panel): records is per
+        gene a list of ACGT strings, scores per gene their composite scores, dedup_edit_threshold one value or one per
+        gene → one DedupResult per gene.  want_pairs: also the within-threshold bit of every pair of the sorted order.
+        How the pairs were decided and the kernel's time are left in self.last_dedup."""
+        ng = len(records)
+        if len(scores) != ng:
+            raise ValueError("one score list per gene")
+        thr = np.array(_per_gene(dedup_edit_threshold, ng, "dedup_edit_threshold"), dtype=np.uint32).reshape(-1)
+        flat = [r.encode("ascii") if isinstance(r, str) else bytes(r) for g in records for r in g]
+        roff = np.zeros(ng + 1, dtype=np.uint64)
+        if ng:
+            roff[1:] = np.cumsum([len(g) for g in records])
+        soff = np.zeros(len(flat) + 1, dtype=np.uint64)
+        if flat:
+            soff[1:] = np.cumsum([len(r) for r in flat])
+        seqs = np.frombuffer(b"".join(flat), dtype=np.uint8) if flat else np.zeros(0, dtype=np.uint8)
+        sc = np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in scores]) if ng else np.zeros(0)
+        sc = np.ascontiguousarray(sc, dtype=np.float64)
+        if len(sc) != len(flat):
+            raise ValueError("one score per record")
+        kept = np.zeros(PCR_MAX_AMPLICONS * max(ng, 1), dtype=np.uint32)
+        gen, ret, rtd = (np.zeros(max(ng, 1), dtype=np.uint32) for _ in range(3))
+        order = np.zeros(max(len(flat), 1), dtype=np.uint32)
+        poff = np.zeros(ng + 1, dtype=np.uint64)
+        n_words = sum((len(g) * (len(g) - 1) // 2 + 63) // 64 for g in records) if want_pairs else 0
+        words = np.zeros(max(n_words, 1), dtype=np.uint64)
+        out = _PcrDedupOut(kept.ctypes.data, gen.ctypes.data, ret.ctypes.data, rtd.ctypes.data, order.ctypes.data,
+                           words.ctypes.data if want_pairs else None, poff.ctypes.data, n_words, 0, 0, 0, 0.0)
+        rcode = self._L.shk_pcr_dedup_panel(self._h, seqs.ctypes.data, soff.ctypes.data, roff.ctypes.data, sc.ctypes.data,
+                                            thr.ctypes.data, ng, C.byref(out))
+        self._check(rcode)
+        self.last_dedup = {"device_ms": float(out.device_ms), "pairs_device": int(out.pairs_device), "pairs_host": int(out.pairs_host),
+                           "pairs_prefiltered": int(out.pairs_prefiltered)}
+        res = []
+        for g in range(ng):
+            a, b, m = int(roff[g]), int(roff[g + 1]), len(records[g])
+            bits = None
+            if want_pairs:
+                w = words[int(poff[g]):int(poff[g + 1])]
+                bits = np.unpackbits(w.view(np.uint8), bitorder="little")[:m * (m - 1) // 2].astype(bool)
+            res.append(DedupResult(kept[PCR_MAX_AMPLICONS * g:PCR_MAX_AMPLICONS * g + int(rtd[g])].copy(), int(gen[g]), int(ret[g]),
+                                   order[a:b].copy(), bits))
+        return res
+
+    def pcr_products_panel(self, graphs, annotations=None, min_length=0, max_length=10000, max_dfs_states=100000,
+                           max_paths_per_pair=20, max_node_visits=2, dedup_edit_threshold=10) -> list:
+        """The last stage of do_pcr (pcr/mod.rs:699-813) for every gene of a panel in one call (shk_pcr_products_panel):
+        bubble preferences, the path search, sequences and scores on the host, the dedup's pair matrix on the device,
+        the products renumbered 0, 1, .. → one PcrProducts per gene.  graphs: the list pcr_prune_panel returns;
+        annotations: the list thread_reads_panel returns, None entries allowed; each parameter one value for all genes
+        or one per gene.  The kernel's time is left in self.last_products_device_ms."""
+        G, keep = _pcr_graphs(graphs, annotations)
+        ng = G.n_genes
+        prm = _pcr_params(ng, min_length, max_length, max_dfs_states, max_paths_per_pair, max_node_visits)
+        thr = np.array(_per_gene(dedup_edit_threshold, ng, "dedup_edit_threshold"), dtype=np.uint32).reshape(-1)
+        if not ng:
+            thr = np.zeros(1, dtype=np.uint32)
+        retained = np.zeros(max(ng, 1), dtype=np.uint32)
+        ms = C.c_double(0.0)
+        res = _pcr_records_call(ng, lambda R: (self._L.shk_pcr_products_panel(self._h, C.byref(G), prm, thr.ctypes.data, C.byref(R),
+                                                                              retained.ctypes.data, C.byref(ms)), self._check), retained)
+        self.last_products_device_ms = float(ms.value)
         return res
 
     def pcr_prune(self, graph, tip_coverage_fraction: float = 0.1, stages: int = 3) -> PrunedGraph:
