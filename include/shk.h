@@ -495,6 +495,41 @@ int shk_gather_reads_device(shk_ctx *ctx, const void *d_bases, const void *d_off
                             const uint64_t *read_ids, uint64_t n_ids,
                             void *d_out_bases, uint64_t out_bases_cap, void *d_out_offsets, uint64_t *n_out_bases);
 
+/* RETAINED READS: the reads of a job kept in device memory as they are ingested, so that sPCR's read pass (the two
+ * _retained calls below) needs no second pass over the input — the reference re-opens its files and collects every
+ * sequence on the host (reread_sequences, src/io.rs:769-943, from src/main.rs:134).  The store holds three bit planes
+ * (code bit 0, code bit 1, N: 0.375 bytes per base) and one u64 offset per read.
+ * on = 1 (capacity_bases_hint sizes the first allocation; 0: the first batch does): accepted only while the context
+ *   holds no reads — freshly created or after shk_reset — otherwise SHK_ERR_STATE.  A retained read's index is its
+ *   ordinal among the reads handed to the context since then, whatever shk_set_read_index says.  on = 0 frees the
+ *   store, at any time.  shk_reset empties the store, keeps its allocation and leaves retention on; shk_destroy frees
+ *   it.  Off by default.  A multi-device context refuses the call (SHK_ERR_STATE).
+ * WHAT IS RETAINED: every batch of shk_ingest_reads / _batch / _packed / _reads_device / _packed_device, on owner
+ *   shares too (whole reads, not the share's k-mers), appended on the context's stream.  The exchange rounds (the
+ *   shk_xchg_ scatter calls) retain nothing; shk_insert_counts and shk_insert_device add no reads.  The store grows
+ *   geometrically; when room for a batch cannot be had the ingest returns SHK_ERR_NOMEM with nothing counted and
+ *   nothing retained from that call.  An invalid byte poisons the context as without retention, and every retained
+ *   call on a poisoned context returns that error. */
+int shk_retain_reads(shk_ctx *ctx, int on, uint64_t capacity_bases_hint);
+/* Reads and bases retained so far, and the device memory the store holds (0, 0, 0 with retention off). */
+int shk_retained_info(shk_ctx *ctx, uint64_t *n_reads, uint64_t *n_bases, uint64_t *device_bytes);
+/* Retained reads first_read .. first_read + n_reads as ASCII on the host (N where the read had one): offsets gets
+ * n_reads + 1 entries from 0, *n_bases the total.  bases_cap too small: SHK_ERR_BAD_ARG with *n_bases set to the need
+ * and nothing written.  Also SHK_ERR_BAD_ARG: a range beyond the retained reads; SHK_ERR_STATE: retention is off. */
+int shk_retained_export(shk_ctx *ctx, uint64_t first_read, uint64_t n_reads, uint8_t *bases, uint64_t bases_cap,
+                        uint64_t *offsets, uint64_t *n_bases);
+/* shk_filter_reads_panel_device and shk_thread_reads_panel_device with the batch being every read retained so far, in
+ * retention order: the same outputs, match_cap / link_cap protocol, limits, tuning and errors; read_index and mate take
+ * one entry per retained read.  The walks read the planes as they lie — no byte loads, no ballots.  SHK_ERR_STATE
+ * with retention off; zero retained reads: all-zero outputs.  They wait for every queued append, may be called in the
+ * middle of a job (later ingests go on appending) and neither read nor write the table. */
+int shk_filter_reads_panel_retained(shk_ctx *ctx, const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes,
+                                    uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches);
+int shk_thread_reads_panel_retained(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint64_t *node_offsets,
+                                    const uint32_t *edge_src, const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes,
+                                    const uint64_t *list_offsets, const uint64_t *list_reads,
+                                    const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out);
+
 /* The bulk neighbourhood of a seed set in sPCR's extension graph: every table lookup extend_graph
  * (src/pcr/graph.rs:377-525) can make from these seeds at this threshold, fetched breadth-first on the device, many
  * levels per launch.  For a context of k-mer length k ≥ 2, mask = (1 << 2(k−1)) − 1:

@@ -18,6 +18,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "shk_retain_core.h"
+
 namespace shk {
 
 constexpr uint64_t EMPTY = 0xFFFFFFFFFFFFFFFFull;  // never a k-mer: k<32 ⇒ key < 2^62
@@ -1729,6 +1731,48 @@ __device__ __forceinline__ ReadPlanes read_planes(const uint8_t *__restrict__ rb
   const uint32_t b2 = ((c >> 1) ^ (c >> 2)) & 3u;
   return ReadPlanes{__ballot(b2 & 1u), __ballot(b2 >> 1), __ballot(c == 'N'), __ballot(!byte_is_acgtn(c)) != 0};
 }
+// Where the wave-per-read walks (K_THREAD, K_FILTER_PANEL) take a read's planes from.  A batch source opens read r as
+// a read source and gives its length; planes(s, lane, len) are the 64 positions from s on, lane l's at s + l.
+//   AsciiReads / AsciiRead     the batch as ASCII plus offsets in HBM: a byte load per lane and four ballots per step.
+//   PlaneReads / PlaneRead     the retained store (K_RETAIN below): the planes lie there as bits, so a step
+//                              is six wave-uniform 8-byte loads and three funnel shifts (retain_plane).  The addresses are
+//                              formed through readfirstlane: the loads are the scalar unit's.  No read of the store has an
+//                              invalid byte (the ingest that found one poisoned the context): bad is constant false.
+struct AsciiRead {
+  const uint8_t *rb;
+  __device__ __forceinline__ ReadPlanes planes(uint32_t s, uint32_t lane, uint32_t len) const { return read_planes(rb, s + lane, len); }
+};
+struct AsciiReads {
+  const uint8_t *bases;
+  const uint64_t *offsets;
+  __device__ __forceinline__ AsciiRead open(uint64_t r, uint32_t *len) const {
+    const uint64_t b0 = offsets[r];
+    *len = (uint32_t)(offsets[r + 1] - b0);
+    return AsciiRead{bases + b0};
+  }
+};
+__device__ __forceinline__ uint64_t uniform64(uint64_t x) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+}
+struct PlaneRead {
+  const uint64_t *p0, *p1, *nn;
+  uint64_t b0;  // the read's first bit (wave-uniform)
+  __device__ __forceinline__ ReadPlanes planes(uint32_t s, uint32_t, uint32_t len) const {
+    const uint32_t su = (uint32_t)__builtin_amdgcn_readfirstlane((int)s), lu = (uint32_t)__builtin_amdgcn_readfirstlane((int)len);
+    return ReadPlanes{retain_plane(p0, b0, su, lu), retain_plane(p1, b0, su, lu), retain_plane(nn, b0, su, lu), false};
+  }
+};
+struct PlaneReads {
+  const uint64_t *p0, *p1, *nn;
+  const uint64_t *offsets;  // [n_reads + 1] first bit of every read, the store's end last
+  __device__ __forceinline__ PlaneRead open(uint64_t r, uint32_t *len) const {
+    const uint64_t ru = uniform64(r), b0 = offsets[ru];
+    *len = (uint32_t)(offsets[ru + 1] - b0);
+    return PlaneRead{p0, p1, nn, b0};
+  }
+};
+
 // bit i of x → bit 2i
 __device__ __forceinline__ uint64_t spread2(uint32_t x) {
   uint64_t v = x;
@@ -1858,11 +1902,11 @@ struct ThreadView {
   uint32_t *total, *unamb, *links;
 };
 
-// The walk of ONE read by one wave — both sweeps, from its first bytes to its last atomic (see K_THREAD above): rb, len
-// the read, scr the wave's scratch (one entry per window of the read) → the edges the read was mapped to (read_edges).
-// k_thread_panel calls it with the view of the gene it holds.
-__device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const uint8_t *__restrict__ rb, uint32_t len, int k, uint2 *__restrict__ scr,
-                                                uint32_t lane) {
+// The walk of ONE read by one wave — both sweeps, from its first bytes to its last atomic (see K_THREAD above): rd, len
+// the read as its source opened it (AsciiRead or PlaneRead), scr the wave's scratch (one entry per window of the read) →
+// the edges the read was mapped to (read_edges).  thread_panel_body calls it with the view of the gene it holds.
+template <class Read>
+__device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const Read &rd, uint32_t len, int k, uint2 *__restrict__ scr, uint32_t lane) {
   const uint32_t km = (1u << k) - 1u;         // k ≤ 31
   const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
   const uint64_t upto = below | (1ull << lane);
@@ -1872,10 +1916,10 @@ __device__ __forceinline__ uint32_t thread_walk(const ThreadView &t, const uint8
   // ---- sweep 1, first step first: edges, run flags, link slots → scratch
   uint32_t c_hit = 0, c_tgt = 0, c_lbase = TH_NONE, c_pre = 0;  // the last list element so far
   ReadPlanes lo{0, 0, 0, false};
-  if (n_win) lo = read_planes(rb, lane, len);
+  if (n_win) lo = rd.planes(0, lane, len);
   bad = lo.bad;
   for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
-    const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
+    const ReadPlanes hi = rd.planes(s0 + THREAD_TILE, lane, len);  // the step's new bytes: the upper half of its windows' span
     if (hi.bad) {  // encoding.rs:353-356 → Err → the read is skipped whole
       bad = true;
       break;
@@ -1997,13 +2041,14 @@ __device__ __forceinline__ ThreadView thread_view_global(const ThreadGene &g, co
                     (const uint4 *)(up + g.meta), total + g.cnt_base, unamb + g.cnt_base, links + g.link_base};
 }
 
-__global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
-                                                            const uint64_t *__restrict__ list_reads, const ThreadGene *__restrict__ genes,
-                                                            const ThreadJob *__restrict__ jobs, uint32_t n_jobs,
-                                                            const uint8_t *__restrict__ upload, int k, uint2 *__restrict__ scratch,
-                                                            uint32_t scr_stride, uint32_t *__restrict__ total, uint32_t *__restrict__ unamb,
-                                                            uint32_t *__restrict__ links, uint32_t *__restrict__ read_edges) {
-  extern __shared__ __align__(16) uint8_t th_lds[];  // the held gene's meta, key runs and two private supports (thread_lds_bytes)
+// (the body of k_thread_panel and k_thread_panel_retained: th_lds is the kernel's dynamic LDS — the held gene's meta, key
+// runs and two private supports, thread_lds_bytes)
+template <class Reads>
+__device__ __forceinline__ void thread_panel_body(uint8_t *th_lds, const Reads &rs, const uint64_t *__restrict__ list_reads,
+                                                  const ThreadGene *__restrict__ genes, const ThreadJob *__restrict__ jobs, uint32_t n_jobs,
+                                                  const uint8_t *__restrict__ upload, int k, uint2 *__restrict__ scratch, uint32_t scr_stride,
+                                                  uint32_t *__restrict__ total, uint32_t *__restrict__ unamb, uint32_t *__restrict__ links,
+                                                  uint32_t *__restrict__ read_edges) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint2 *scr = scratch + ((uint64_t)blockIdx.x * (THREAD_WG / 64) + wib) * scr_stride;
@@ -2046,15 +2091,19 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__res
       const ThreadView view{KeyRuns{(const uint64_t *)kb, ls, ls + cap, ls + cap + E, g.mask, E}, (const uint4 *)th_lds, lt, lt + E,
                             links + g.link_base};
       for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
-        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i, b0 = offsets[r];
-        const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
+        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i;
+        uint32_t len;
+        const auto rd = rs.open(r, &len);
+        const uint32_t n_hit = thread_walk(view, rd, len, k, scr, lane);
         if (lane == 0) re[i] = n_hit;
       }
     } else {
       const ThreadView view = thread_view_global(g, upload, total, unamb, links);
       for (uint32_t i = wib; i < job.n; i += THREAD_WG / 64) {
-        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i, b0 = offsets[r];
-        const uint32_t n_hit = thread_walk(view, bases + b0, (uint32_t)(offsets[r + 1] - b0), k, scr, lane);
+        const uint64_t r = list_reads ? list_reads[job.first + i] : job.first + i;
+        uint32_t len;
+        const auto rd = rs.open(r, &len);
+        const uint32_t n_hit = thread_walk(view, rd, len, k, scr, lane);
         if (lane == 0) re[i] = n_hit;
       }
     }
@@ -2063,6 +2112,27 @@ __global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__res
     __syncthreads();
     flush();
   }
+}
+
+__global__ void __launch_bounds__(THREAD_WG) k_thread_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                            const uint64_t *__restrict__ list_reads, const ThreadGene *__restrict__ genes,
+                                                            const ThreadJob *__restrict__ jobs, uint32_t n_jobs,
+                                                            const uint8_t *__restrict__ upload, int k, uint2 *__restrict__ scratch,
+                                                            uint32_t scr_stride, uint32_t *__restrict__ total, uint32_t *__restrict__ unamb,
+                                                            uint32_t *__restrict__ links, uint32_t *__restrict__ read_edges) {
+  extern __shared__ __align__(16) uint8_t th_lds[];
+  thread_panel_body(th_lds, AsciiReads{bases, offsets}, list_reads, genes, jobs, n_jobs, upload, k, scratch, scr_stride, total, unamb, links,
+                    read_edges);
+}
+// … over the retained store (shk_thread_reads_panel_retained): list_reads are retained read indices
+__global__ void __launch_bounds__(THREAD_WG) k_thread_panel_retained(PlaneReads rs, const uint64_t *__restrict__ list_reads,
+                                                                     const ThreadGene *__restrict__ genes, const ThreadJob *__restrict__ jobs,
+                                                                     uint32_t n_jobs, const uint8_t *__restrict__ upload, int k,
+                                                                     uint2 *__restrict__ scratch, uint32_t scr_stride,
+                                                                     uint32_t *__restrict__ total, uint32_t *__restrict__ unamb,
+                                                                     uint32_t *__restrict__ links, uint32_t *__restrict__ read_edges) {
+  extern __shared__ __align__(16) uint8_t th_lds[];
+  thread_panel_body(th_lds, rs, list_reads, genes, jobs, n_jobs, upload, k, scratch, scr_stride, total, unamb, links, read_edges);
 }
 
 // ==========================================================================================
@@ -2096,11 +2166,10 @@ struct PanelSet {
 __host__ __device__ inline size_t filter_bitmap_bytes(uint32_t n_genes) { return (size_t)(FILTER_WG / 64) * ((n_genes + 31) / 32) * 4; }
 __host__ __device__ inline size_t filter_set_bytes(uint32_t cap, uint32_t n_pairs) { return key_runs_bytes(cap, n_pairs); }
 
-template <bool LDS>
-__global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
-                                                            uint64_t n_seqs, int k, PanelSet gs, unsigned long long *__restrict__ out,
-                                                            uint64_t cap, unsigned long long *__restrict__ n_out) {
-  extern __shared__ __align__(16) uint8_t fp_lds[];
+// (the body of k_filter_panel and k_filter_panel_retained: fp_lds is the kernel's dynamic LDS)
+template <bool LDS, class Reads>
+__device__ __forceinline__ void filter_panel_body(uint8_t *fp_lds, const Reads &rs, uint64_t n_seqs, int k, const PanelSet &gs,
+                                                  unsigned long long *__restrict__ out, uint64_t cap, unsigned long long *__restrict__ n_out) {
   const uint32_t n_words = (gs.n_genes + 31) / 32;
   uint32_t *bm_all = (uint32_t *)fp_lds;  // (16 · n_words words: a multiple of 64 bytes, so the keys behind stay aligned)
   for (uint32_t i = threadIdx.x; i < (FILTER_WG / 64) * n_words; i += FILTER_WG) bm_all[i] = 0;
@@ -2117,15 +2186,14 @@ __global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__res
   const uint64_t below = (1ull << lane) - 1;  // the lanes under mine
 
   for (uint64_t r = wave; r < n_seqs; r += n_waves) {
-    const uint64_t b0 = offsets[r];
-    const uint32_t len = (uint32_t)(offsets[r + 1] - b0);
+    uint32_t len;
+    const auto rd = rs.open(r, &len);
     if (len < (uint32_t)k) continue;  // no k-mer, valid or not: matches nothing
     const uint32_t n_win = len - (uint32_t)k + 1u;
-    const uint8_t *rb = bases + b0;
-    ReadPlanes lo = read_planes(rb, lane, len);
+    ReadPlanes lo = rd.planes(0, lane, len);
     bool bad = lo.bad, any = false;
     for (uint32_t s0 = 0; s0 < n_win && !bad; s0 += THREAD_TILE) {
-      const ReadPlanes hi = read_planes(rb, s0 + THREAD_TILE + lane, len);  // the step's new bytes: the upper half of its windows' span
+      const ReadPlanes hi = rd.planes(s0 + THREAD_TILE, lane, len);  // the step's new bytes: the upper half of its windows' span
       if (hi.bad) {  // encoding.rs:353-356 → Err → matches() is false for every gene
         bad = true;
         break;
@@ -2167,6 +2235,89 @@ __global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__res
     }
     __threadfence_block();  // the cleared words, before the next read's hits
   }
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(FILTER_WG) k_filter_panel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offsets,
+                                                            uint64_t n_seqs, int k, PanelSet gs, unsigned long long *__restrict__ out,
+                                                            uint64_t cap, unsigned long long *__restrict__ n_out) {
+  extern __shared__ __align__(16) uint8_t fp_lds[];
+  filter_panel_body<LDS>(fp_lds, AsciiReads{bases, offsets}, n_seqs, k, gs, out, cap, n_out);
+}
+// … over the retained store (shk_filter_reads_panel_retained): read r is retained read r
+template <bool LDS>
+__global__ void __launch_bounds__(FILTER_WG) k_filter_panel_retained(PlaneReads rs, uint64_t n_seqs, int k, PanelSet gs,
+                                                                     unsigned long long *__restrict__ out, uint64_t cap,
+                                                                     unsigned long long *__restrict__ n_out) {
+  extern __shared__ __align__(16) uint8_t fp_lds[];
+  filter_panel_body<LDS>(fp_lds, rs, n_seqs, k, gs, out, cap, n_out);
+}
+
+// ==========================================================================================
+// K_RETAIN: a batch of ASCII reads appended to the retained store (shk_retain_reads; layout and
+// invariant in shk_retain_core.h).  The batch's first base goes to absolute bit S, wherever in a word that is.  One
+// WAVE per RETAIN_WAVE_WORDS destination words (of the words the batch touches, from S / 64), its byte loads issued
+// together: for word w lane l looks at source byte 64·w + l − S if that lies inside the batch, three ballots make the
+// word's planes, lane 0 stores them.  The store's end word is
+// shared with the batch before when S % 64 != 0: its bits from S % 64 on are zero (the invariant), the wave that owns
+// it is its only writer and ORs; every other word is written whole, with zeros behind the batch's end, which keeps the
+// invariant.  The read offsets follow rebased: entry i + 1 of st_offsets (the store's, from its last read's end on) =
+// offsets[i + 1] − off_bias + S, held to the batch.
+// ==========================================================================================
+constexpr uint32_t RETAIN_WAVE_WORDS = 4;
+__global__ void __launch_bounds__(WG) k_retain(const uint8_t *__restrict__ bases, uint64_t n_bases, const uint64_t *__restrict__ offsets,
+                                               uint64_t n_seqs, uint64_t off_bias, uint64_t S, uint64_t n_words, uint64_t *__restrict__ p0,
+                                               uint64_t *__restrict__ p1, uint64_t *__restrict__ nn, uint64_t *__restrict__ st_offsets) {
+  const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (t < n_seqs) {  // (offsets[0] − off_bias is the batch's first byte: the entry of the store's end stays as it is)
+    const uint64_t o = offsets[t + 1] - off_bias;
+    st_offsets[t + 1] = S + (o < n_bases ? o : n_bases);
+  }
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t i0 = (t >> 6) * RETAIN_WAVE_WORDS;  // the wave's first word among the batch's (the same for its 64 lanes)
+  if (i0 >= n_words) return;
+  uint32_t c[RETAIN_WAVE_WORDS];
+#pragma unroll
+  for (uint32_t j = 0; j < RETAIN_WAVE_WORDS; ++j) {
+    const uint64_t p = ((S >> 6) + i0 + j) * 64 + lane;  // absolute bit
+    const bool in = i0 + j < n_words && p >= S && p - S < n_bases;
+    c[j] = in ? bases[p - S] : (uint32_t)'A';
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < RETAIN_WAVE_WORDS; ++j) {
+    const uint64_t i = i0 + j, w = (S >> 6) + i;
+    if (i >= n_words) break;  // (wave-uniform)
+    const bool isn = c[j] == 'N';
+    const uint32_t b2 = isn ? 0u : retain_code(c[j]);
+    const uint64_t w0 = __ballot(b2 & 1u), w1 = __ballot(b2 >> 1), wn = __ballot(isn);
+    if (lane == 0) {
+      if (i == 0 && (S & 63u)) {
+        p0[w] |= w0, p1[w] |= w1, nn[w] |= wn;
+      } else {
+        p0[w] = w0, p1[w] = w1, nn[w] = wn;
+      }
+    }
+  }
+}
+
+// K_RETAINED_EXPORT: the inverse — bases [B0, B0 + n) of the store back to ASCII, N where nn is set: 16 bases per
+// thread and one 16-byte store, as k_unpack (out is padded to a multiple of 16 bytes).
+__global__ void __launch_bounds__(WG) k_retained_export(const uint64_t *__restrict__ p0, const uint64_t *__restrict__ p1,
+                                                        const uint64_t *__restrict__ nn, uint64_t B0, uint64_t n, uint8_t *__restrict__ out) {
+  const uint64_t q = ((uint64_t)blockIdx.x * WG + threadIdx.x) * 16;
+  if (q >= n) return;
+  const uint64_t A = B0 + q, w = A >> 6;
+  const uint32_t sh = (uint32_t)(A & 63u);
+  const uint32_t a0 = (uint32_t)retain_window(p0[w], p0[w + 1], sh) & 0xFFFFu, a1 = (uint32_t)retain_window(p1[w], p1[w + 1], sh) & 0xFFFFu,
+                 an = (uint32_t)retain_window(nn[w], nn[w + 1], sh) & 0xFFFFu;
+  uint32_t o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    o[j] = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) o[j] |= (uint32_t)retain_ascii(a0, a1, an, 4 * j + b) << (8 * b);
+  }
+  *reinterpret_cast<uint4 *>(out + q) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
 // K_GATHER_READS: reads ids[j] of a batch copied back to back into a batch of their own (shk_gather_reads_device):

@@ -13,6 +13,7 @@
 #include "shk_pcr.h"
 #include "shk_products.h"
 #include "shk_dedup_core.h"
+#include "shk_retain_core.h"
 
 #include <algorithm>
 #include <chrono>
@@ -230,6 +231,20 @@ struct HostBuf {  // grow-only pinned host scratch
   }
 };
 
+// The retained reads of a context (shk_retain_reads; layout in shk_retain_core.h): three planes of
+// cap_words words each in one allocation, and the reads' first bits.  Nothing here exists while retention is off.
+struct RetainStore {
+  bool on = false;
+  uint64_t *planes = nullptr, *offsets = nullptr;  // device: p0 | p1 | nn at a stride of cap_words; [cap_reads + 1], entry 0 is 0
+  size_t planes_alloc = 0, offsets_alloc = 0;      // bytes, as dev_alloc gave them
+  uint64_t cap_words = 0, cap_reads = 0;
+  uint64_t n_reads = 0, n_bases = 0;               // appended so far (the appends may still be queued on the stream)
+  uint64_t hint_bases = 0;                         // sizes the first allocation
+  uint64_t *p0() const { return planes; }
+  uint64_t *p1() const { return planes + cap_words; }
+  uint64_t *nn() const { return planes + 2 * cap_words; }
+};
+
 constexpr int K_MATERIALISE = SHK_N_KERNELS;  // the materialising page pass (tb_materialise): timed beside shk_timings
 struct TimedEvent {
   int kid;
@@ -292,7 +307,7 @@ struct shk_ctx {
   hipEvent_t copy_done[NST] = {};
   int stage_last = -1;            // the staging set the last slice of the previous host-buffer ingest took (its count may still be in flight)
   bool zero_count_keys = false;   // some key may have been inserted with count 0 (shk_insert_counts, merges): k_histo reads the keys
-  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter64 = false, lds_attr_thread_panel = false, lds_attr_filter = false, lds_attr_prune = false;  // hipFuncSetAttribute done for this context's device
+  bool lds_attr_scatter = false, lds_attr_rescatter = false, lds_attr_scatter64 = false, lds_attr_thread_panel = false, lds_attr_filter = false, lds_attr_prune = false, lds_attr_thread_retained = false, lds_attr_filter_retained = false;  // hipFuncSetAttribute done for this context's device
   HostBuf h_rebased[NST];           // pinned staging of a slice's re-based offsets (a pageable source would make the copy synchronous)
   DevBuf in_bases, in_offsets, st_bases[NST], st_offsets[NST], startbits, tiles, spillA, spillB, misc, part, part2, part3, part_meta;
   DevBuf pk_stage[NST], nm_stage[NST], nz_dev[NST], pk_ascii;
@@ -302,6 +317,7 @@ struct shk_ctx {
   DevBuf xbuf, xspill;            // owner layout: the level-1 records of a launch by [owner][lane][super-page]; the foreign spill list
   DevBuf xbuf_alt, part_meta_alt;  // the OTHER exchange buffer and cursor block: shk_xchg_scatter_device takes the two in turn
   uint64_t xspill_cap = 0;
+  RetainStore retain;             // the reads kept at ingest (off unless shk_retain_reads switched it on)
   // host counters
   std::vector<uint64_t> lane_reads;
   uint64_t n_reads_read = 0, n_bases_read = 0;
@@ -714,6 +730,64 @@ static uint64_t max_sub_bases() {
   return std::min(MAX_SUB_BASES, (kb << 10) / TILE_T * TILE_T);
 }
 
+// Retention (shk_retain_reads), the two halves of an append.  Room for n_seqs reads of n_bases bases behind what the
+// store holds: growth is geometric, the old content moves device to device on the context's stream, and the old
+// allocation is given back behind it (dev_free waits for the device).  On failure the store is as it was.
+int retain_reserve(shk_ctx *c, uint64_t n_seqs, uint64_t n_bases) {
+  RetainStore &st = c->retain;
+  const uint64_t need_w = retain_words(st.n_bases + n_bases), need_r = st.n_reads + n_seqs;
+  if (need_w > st.cap_words) {
+    uint64_t cap = std::max(std::max(need_w, 2 * st.cap_words), retain_words(st.hint_bases));
+    void *np = nullptr;
+    size_t got = 0;
+    if (dev_alloc(&np, cap * 24, &got) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, SHK_ERR_NOMEM, "out of device memory growing the retained reads to %llu bases", (unsigned long long)(st.n_bases + n_bases));
+    }
+    cap = got / 24;
+    uint64_t *q = (uint64_t *)np;
+    const uint64_t used = (st.n_bases + 63) / 64;
+    hipError_t e = hipMemsetAsync(q, 0, cap * 24, c->stream);  // (the slack and everything behind the end: zero)
+    for (int pl = 0; pl < 3 && used && e == hipSuccess; ++pl)
+      e = hipMemcpyAsync(q + pl * cap, st.planes + pl * st.cap_words, used * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) {
+      dev_free(np, got);
+      return fail(c, SHK_ERR_HIP, "HIP error %s moving the retained reads", hipGetErrorString(e));
+    }
+    dev_free(st.planes, st.planes_alloc);
+    st.planes = q, st.planes_alloc = got, st.cap_words = cap;
+  }
+  if (need_r > st.cap_reads || !st.offsets) {
+    uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need_r, 2 * st.cap_reads), 1024);
+    void *np = nullptr;
+    size_t got = 0;
+    if (dev_alloc(&np, (cap + 1) * 8, &got) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, SHK_ERR_NOMEM, "out of device memory growing the retained reads to %llu reads", (unsigned long long)need_r);
+    }
+    cap = got / 8 - 1;
+    hipError_t e = hipMemsetAsync(np, 0, (cap + 1) * 8, c->stream);  // (entry 0 is 0 and stays so)
+    if (st.offsets && e == hipSuccess) e = hipMemcpyAsync(np, st.offsets, (st.n_reads + 1) * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess) {
+      dev_free(np, got);
+      return fail(c, SHK_ERR_HIP, "HIP error %s moving the retained reads' offsets", hipGetErrorString(e));
+    }
+    dev_free(st.offsets, st.offsets_alloc);
+    st.offsets = (uint64_t *)np, st.offsets_alloc = got, st.cap_reads = cap;
+  }
+  return SHK_OK;
+}
+// The batch (as ingest_core has it; room reserved) appended once, on the context's stream.
+void retain_append(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, uint64_t off_bias) {
+  RetainStore &st = c->retain;
+  const uint64_t S = st.n_bases, n_words = ((S & 63) + n_bases + 63) / 64;
+  const uint64_t threads = std::max(n_seqs, (n_words + RETAIN_WAVE_WORDS - 1) / RETAIN_WAVE_WORDS * 64);
+  if (threads)
+    hipLaunchKernelGGL(k_retain, dim3((uint32_t)((threads + WG - 1) / WG)), dim3(WG), 0, c->stream, d_bases, n_bases, d_offsets, n_seqs, off_bias, S,
+                       n_words, st.p0(), st.p1(), st.nn(), st.offsets + st.n_reads);
+  st.n_reads += n_seqs, st.n_bases += n_bases;
+}
+
 // Core ingest over device-resident input.  lane_fixed >= 0: every read to that chunk lane
 // (drain_batch, io.rs:356-358); lane_fixed < 0: stripe by running read index
 // (read i → chunk (i/1000) % n_chunks, io.rs:340-343,355-361).
@@ -722,6 +796,8 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   if (!(xo && xo->late_settle)) SHK_TRY(settle_light(c));  // the previous launch's spill list / scratch must be done with
   if (c->tb_virtual) SHK_TRY(tb_fresh(c));  // (this batch's records and cursors go where the ones that define the table are)
+  const bool retain = c->retain.on && !xo;  // (the exchange rounds retain nothing)
+  if (retain) SHK_TRY(retain_reserve(c, n_seqs, n_bases));  // before anything is counted: a failure leaves the call undone
   c->finalized = c->hist_ready = false;
   c->chain_from_mark = false;
   const uint64_t g0 = c->n_reads_read;
@@ -742,6 +818,7 @@ int ingest_core(shk_ctx *c, const uint8_t *d_bases, const uint64_t *d_offsets, u
   }
   if (lane_fixed < 0) c->n_reads_read += n_seqs;  // explicit-lane batches do not advance striping
   c->n_bases_read += n_bases;
+  if (retain) retain_append(c, d_bases, d_offsets, n_seqs, n_bases, off_bias);  // one append, however many counting launches follow
   if (n_seqs == 0 || n_bases == 0) return xo ? (xo->wide ? xw_scatter_launch(c, BatchRef{}, 0, xo) : xchg_scatter_launch(c, BatchRef{}, 0, xo)) : SHK_OK;
 
   // 1. read-start bitmap (+ tile list when the batch spans several chunk lanes)
@@ -2275,6 +2352,8 @@ void shk_destroy(shk_ctx *c) {
   c->fh_tot.release();
   for (int i = 0; i < shk_ctx::NST; ++i) c->pk_stage[i].release(), c->nm_stage[i].release(), c->nz_dev[i].release(), c->nz_host[i].release(), c->hp_pk[i].release(), c->hp_nm[i].release();
   c->pk_ascii.release();
+  dev_free(c->retain.planes, c->retain.planes_alloc);
+  dev_free(c->retain.offsets, c->retain.offsets_alloc);
   lap("scratch given back");
   if (c->stream) stream_give(c->stream);  // (synchronised at the top)
   lap("stream destroyed");
@@ -2319,6 +2398,7 @@ int shk_reset(shk_ctx *c) {
   // re-read (read_stats) before the host looks at it again
   std::fill(c->lane_reads.begin(), c->lane_reads.end(), 0);
   c->n_reads_read = c->n_bases_read = 0;
+  c->retain.n_reads = c->retain.n_bases = 0;  // (emptied, its allocation kept, retention as it was)
   c->n_inserted = 0;
   c->own_set = false;
   c->own_share_n = 0;
@@ -3491,6 +3571,8 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 #include "shk_table_api.hip.h"
 // shk_filter_reads … shk_gather_reads_device: the calls that walk a batch of reads and leave the table alone
 #include "shk_reads_api.hip.h"
+// the retained reads: the switch, the export and the read-side calls over the store
+#include "shk_retain_api.hip.h"
 // shk_pcr_prune_panel: the graphs of a panel pruned between extension and threading; the table is left alone
 #include "shk_prune_api.hip.h"
 // shk_pcr_dedup_panel, shk_pcr_products_panel: the dedup's pair matrix on the device, the products of a panel; the table

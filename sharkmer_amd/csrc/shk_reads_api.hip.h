@@ -62,9 +62,11 @@ int key_runs_upload(shk_ctx *c, const Scratch &m, const KeyRunsAt &at, const Hos
 }
 
 // A batch of reads in front of a kernel: resident, the context settled, its stream idle but for the batch's own copies.
+// Either ASCII plus offsets, or (planes.p0 set) every read of the retained store (batch_from_retained, shk_retain_api.hip.h).
 struct ReadBatch {
   const uint8_t *d_bases; const uint64_t *d_offsets;
   uint64_t n_seqs, n_bases, max_len;  // (max_len: 0 where the caller never looked)
+  PlaneReads planes;
 };
 
 // offsets as a batch of reads over n_bases bytes (a read's length is a 31-bit number in the wave-per-read kernels)
@@ -472,18 +474,28 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   if (list_reads) HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + pp.l0, pp.n_listed * 8, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
   if (getenv("SHK_TRACE"))  // (read at each call, like the knobs: the tests look for this line)
-    fprintf(stderr, "[shk] thread_reads_panel: %u genes, %zu jobs, %llu blocks, %u genes in LDS, %u genes in global memory\n", n_genes, jobs.size(),
-            (unsigned long long)blocks, n_lds, n_global);
+    fprintf(stderr, "[shk] thread_reads_panel: %u genes, %zu jobs, %llu blocks, %u genes in LDS, %u genes in global memory%s\n", n_genes, jobs.size(),
+            (unsigned long long)blocks, n_lds, n_global, b.planes.p0 ? ", retained reads" : "");
   {
     ScopedTimer t(c, SHK_K_LOOKUP);
     if (lds > (64u << 10) && !c->lds_attr_thread_panel) {  // > 64 KiB of dynamic LDS has to be asked for once
       HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_thread_panel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)THREAD_LDS_MAX));
       c->lds_attr_thread_panel = true;
     }
-    hipLaunchKernelGGL(k_thread_panel, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, b.d_bases, b.d_offsets,
-                       dlist, (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up),
-                       (const ThreadJob *)m.at<ThreadJob>(o_jobs), (uint32_t)jobs.size(), (const uint8_t *)m.at<uint8_t>(o_up), (int)k,
-                       m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
+    if (lds > (64u << 10) && b.planes.p0 && !c->lds_attr_thread_retained) {
+      HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_thread_panel_retained), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)THREAD_LDS_MAX));
+      c->lds_attr_thread_retained = true;
+    }
+    if (b.planes.p0)
+      hipLaunchKernelGGL(k_thread_panel_retained, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, b.planes, dlist,
+                         (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up), (const ThreadJob *)m.at<ThreadJob>(o_jobs), (uint32_t)jobs.size(),
+                         (const uint8_t *)m.at<uint8_t>(o_up), (int)k, m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
+    else
+      hipLaunchKernelGGL(k_thread_panel, dim3((uint32_t)blocks), dim3(THREAD_WG), lds, c->stream, b.d_bases, b.d_offsets,
+                         dlist, (const ThreadGene *)(m.at<uint8_t>(o_up) + o_desc_up),
+                         (const ThreadJob *)m.at<ThreadJob>(o_jobs), (uint32_t)jobs.size(), (const uint8_t *)m.at<uint8_t>(o_up), (int)k,
+                         m.at<uint2>(o_scr), (uint32_t)stride, dtot, dun, dlinks, dre);
   }
   HIPC(c, hipGetLastError());
   std::vector<uint32_t> slots(pp.n_slots), re_own;
@@ -675,10 +687,15 @@ int panel_pass(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBa
   SHK_TRY(key_runs_upload(c, m, o_runs, pl, &set.runs));
   HIPC(c, hipMemsetAsync(dn, 0, 8, c->stream));
   if (getenv("SHK_TRACE"))  // (read at each call, like SHK_FILTER_LDS_KEYS: the tests look for this line)
-    fprintf(stderr, "[shk] filter_panel: %u genes, %llu keys, set of %zu bytes in %s, room %llu, %llu blocks\n", n_genes,
-            (unsigned long long)pl.n_keys, lds - bitmaps, use_lds ? "LDS" : "global memory", (unsigned long long)room, (unsigned long long)blocks);
-  SHK_TRY(launch_lds_or_global(c, &k_filter_panel<true>, &k_filter_panel<false>, use_lds, &c->lds_attr_filter, FILTER_LDS_MAX, blocks, FILTER_WG,
-                               use_lds ? lds : bitmaps, b.d_bases, b.d_offsets, n_seqs, (int)c->cfg.k, set, drec, room, dn));
+    fprintf(stderr, "[shk] filter_panel: %u genes, %llu keys, set of %zu bytes in %s, room %llu, %llu blocks%s\n", n_genes,
+            (unsigned long long)pl.n_keys, lds - bitmaps, use_lds ? "LDS" : "global memory", (unsigned long long)room, (unsigned long long)blocks,
+            b.planes.p0 ? ", retained reads" : "");
+  if (b.planes.p0)
+    SHK_TRY(launch_lds_or_global(c, &k_filter_panel_retained<true>, &k_filter_panel_retained<false>, use_lds, &c->lds_attr_filter_retained,
+                                 FILTER_LDS_MAX, blocks, FILTER_WG, use_lds ? lds : bitmaps, b.planes, n_seqs, (int)c->cfg.k, set, drec, room, dn));
+  else
+    SHK_TRY(launch_lds_or_global(c, &k_filter_panel<true>, &k_filter_panel<false>, use_lds, &c->lds_attr_filter, FILTER_LDS_MAX, blocks, FILTER_WG,
+                                 use_lds ? lds : bitmaps, b.d_bases, b.d_offsets, n_seqs, (int)c->cfg.k, set, drec, room, dn));
   HIPC(c, hipGetLastError());
   unsigned long long nt = 0;
   HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));

@@ -446,6 +446,8 @@ ABI_SYMBOLS = [
     "shk_pcr_prune_panel", "shk_pcr_paths_panel", "shk_edit_within", "shk_pcr_dedup_panel", "shk_pcr_products_panel",
     "shk_thread_reads", "shk_thread_reads_device", "shk_thread_reads_panel", "shk_thread_reads_panel_device",
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
+    "shk_retain_reads", "shk_retained_info", "shk_retained_export", "shk_filter_reads_panel_retained",
+    "shk_thread_reads_panel_retained",
 ]
 
 _lib = None
@@ -586,6 +588,11 @@ def load_library():
     L.shk_filter_reads_panel.argtypes = [vp, vp, vp, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
     L.shk_filter_reads_panel_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
     L.shk_gather_reads_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
+    L.shk_retain_reads.argtypes = [vp, C.c_int, u64]
+    L.shk_retained_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.shk_retained_export.argtypes = [vp, u64, u64, vp, u64, vp, C.POINTER(u64)]
+    L.shk_filter_reads_panel_retained.argtypes = [vp, vp, vp, u32, vp, vp, u64, C.POINTER(u64)]
+    L.shk_thread_reads_panel_retained.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, C.POINTER(_ThreadPanelOut)]
     L.shk_pcr_node_budget.restype = u64
     L.shk_owner_counts.argtypes = [vp, u32, vp]
     L.shk_compact_owners.argtypes = [vp, u32, vp, vp, vp, u64, C.c_int32]
@@ -1224,6 +1231,20 @@ class KmerEngine:
         answer is one ThreadingAnnotations per gene: what thread_reads gives for that graph over its listed reads in
         list order.  read_index and mate (one entry per read of the BATCH) give the paired form.  device=True: bases
         and offsets are torch tensors on this context's device (shk_thread_reads_panel_device)."""
+        n = len(offsets) - 1
+        if device:
+            args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
+            call = self._L.shk_thread_reads_panel_device
+        else:
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            args = (bases.ctypes.data, offsets.ctypes.data, n)
+            call = self._L.shk_thread_reads_panel
+        return self._thread_panel(call, args, n, graphs, lists, read_index, mate)
+
+    def _thread_panel(self, call, args, n, graphs, lists, read_index, mate) -> list:
+        """thread_reads_panel and thread_reads_retained behind their batch: `args` are the call's arguments between
+        n_genes and list_offsets, n the reads of the batch."""
         gs = [(g.node_sub_kmers, g.edge_src, g.edge_tgt) if isinstance(g, (PcrGraph, PrunedGraph)) else g for g in graphs]
         ng = len(gs)
         if len(lists) != ng:
@@ -1245,7 +1266,6 @@ class KmerEngine:
         es, eoff = cat(ess, np.uint32)
         et, _ = cat(ets, np.uint32)
         lr, loff = cat(lss, np.uint64)
-        n = len(offsets) - 1
         ne, nl = len(es), len(lr)
         ri = None if read_index is None else np.ascontiguousarray(read_index, dtype=np.uint64)
         mt = None if mate is None else np.ascontiguousarray(mate, dtype=np.uint8)
@@ -1256,14 +1276,6 @@ class KmerEngine:
         re = np.zeros(max(nl, 1), dtype=np.uint32)
         koff = np.zeros(ng + 1, dtype=np.uint64)
         npl = np.zeros(max(ng, 1), dtype=np.uint64)
-        if device:
-            args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
-            call = self._L.shk_thread_reads_panel_device
-        else:
-            bases = np.ascontiguousarray(bases, dtype=np.uint8)
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            args = (bases.ctypes.data, offsets.ctypes.data, n)
-            call = self._L.shk_thread_reads_panel
         # room for every link there can be, per gene as thread_reads sizes it (the retry is for panels beyond 2^22)
         link_cap = 0
         for s_, a, b in zip(subs, ess, ets):
@@ -1305,11 +1317,6 @@ class KmerEngine:
         pass (shk_filter_reads_panel): gene_kmers is a sequence of arrays of canonical primer k-mers, one per gene; the
         answer is one uint64 array per gene, the indices of the reads that match it, ascending.  device=True: bases
         and offsets are torch tensors on this context's device (shk_filter_reads_panel_device)."""
-        genes = [np.ascontiguousarray(np.atleast_1d(g), dtype=np.uint64).reshape(-1) for g in gene_kmers]
-        goff = np.zeros(len(genes) + 1, dtype=np.uint64)
-        if genes:
-            goff[1:] = np.cumsum([len(g) for g in genes])
-        pk = np.concatenate(genes) if genes else np.zeros(0, dtype=np.uint64)
         n = len(offsets) - 1
         if device:
             args = (bases.data_ptr(), offsets.data_ptr(), n, bases.numel())
@@ -1319,6 +1326,16 @@ class KmerEngine:
             offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
             args = (bases.ctypes.data, offsets.ctypes.data, n)
             call = self._L.shk_filter_reads_panel
+        return self._filter_panel(call, args, n, gene_kmers)
+
+    def _filter_panel(self, call, args, n, gene_kmers) -> list:
+        """filter_reads_panel and filter_reads_retained behind their batch: `args` are the call's arguments in front of
+        primer_kmers, n the reads of the batch."""
+        genes = [np.ascontiguousarray(np.atleast_1d(g), dtype=np.uint64).reshape(-1) for g in gene_kmers]
+        goff = np.zeros(len(genes) + 1, dtype=np.uint64)
+        if genes:
+            goff[1:] = np.cumsum([len(g) for g in genes])
+        pk = np.concatenate(genes) if genes else np.zeros(0, dtype=np.uint64)
         moff = np.zeros(len(genes) + 1, dtype=np.uint64)
         # room for every read in up to four genes: a call that finds more says so and is made again, which walks the
         # reads a second time
@@ -1333,6 +1350,47 @@ class KmerEngine:
                 continue
             self._check(rcode)
             return [reads[int(moff[g]):int(moff[g + 1])].copy() for g in range(len(genes))]
+
+    # ---- retained reads: the job's reads kept in device memory at ingest (shk_retain_reads) ------------------------------
+    def retain_reads(self, on: bool = True, capacity_bases: int = 0):
+        """Keep every read ingested from now on in device memory (three bit planes, 0.375 bytes per base) for
+        filter_reads_retained and thread_reads_retained.  Switching on takes a context that holds no reads (new, or
+        after reset); capacity_bases sizes the first allocation.  on=False frees the store."""
+        self._check(self._L.shk_retain_reads(self._h, 1 if on else 0, int(capacity_bases)))
+
+    def retained_info(self) -> dict:
+        """→ {"reads", "bases", "device_bytes"} of the retained store."""
+        r, b, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.shk_retained_info(self._h, C.byref(r), C.byref(b), C.byref(d)))
+        return {"reads": int(r.value), "bases": int(b.value), "device_bytes": int(d.value)}
+
+    def retained_reads(self, first: int = 0, n: int | None = None):
+        """Retained reads first .. first + n (n=None: to the last) back as ASCII → (bases uint8, offsets uint64 from 0)."""
+        if n is None:
+            n = max(self.retained_info()["reads"] - first, 0)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        cap = 150 * n  # (a guess; the retry is for longer reads)
+        while True:
+            bases = np.zeros(max(cap, 1), dtype=np.uint8)
+            need = C.c_uint64(0)
+            rcode = self._L.shk_retained_export(self._h, first, n, bases.ctypes.data, cap, offsets.ctypes.data, C.byref(need))
+            if rcode == -2 and need.value > cap:  # nothing was written: it says what it needs
+                cap = int(need.value)
+                continue
+            self._check(rcode)
+            return bases[:int(need.value)].copy(), offsets
+
+    def filter_reads_retained(self, gene_kmers) -> list:
+        """filter_reads_panel with the batch being every read retained so far, in retention order
+        (shk_filter_reads_panel_retained): no batch crosses anything, the walk reads the store's planes."""
+        n = self.retained_info()["reads"]
+        return self._filter_panel(self._L.shk_filter_reads_panel_retained, (), n, gene_kmers)
+
+    def thread_reads_retained(self, graphs, lists, read_index=None, mate=None) -> list:
+        """thread_reads_panel over the retained reads (shk_thread_reads_panel_retained): lists name retained reads — what
+        filter_reads_retained returns — and read_index / mate take one entry per retained read."""
+        n = self.retained_info()["reads"]
+        return self._thread_panel(self._L.shk_thread_reads_panel_retained, (), n, graphs, lists, read_index, mate)
 
     def gather_reads(self, bases_t, offsets_t, read_ids):
         """The reads read_ids (any order, repeats allowed) of a batch that lies on this context's device, as a batch of
