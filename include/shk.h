@@ -256,6 +256,9 @@ int shk_reset_timings(shk_ctx *ctx);
  * timed launches since shk_reset_timings, under SHK_FLAG_TIMING like the slots of shk_timings — whose layout is fixed
  * by this ABI version, hence a call of its own.  Either pointer may be null. */
 int shk_get_lazy_table_timing(shk_ctx *ctx, double *ms, uint64_t *launches);
+/* Cursor segments per page region of the context's last paged counting launch (0: there has been none; a group: its
+ * first device's): 1 everywhere but where k_scatter32 writes straight into the regions k_pages32 reads. */
+int shk_get_scatter_segments(shk_ctx *ctx, uint32_t *segs);
 
 /* ---- merged-table read API (counting.rs:205-260) --------------------------------- */
 

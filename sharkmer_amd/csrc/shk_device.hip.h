@@ -3174,12 +3174,16 @@ __device__ __forceinline__ void place_entries(uint32_t *__restrict__ sorted, con
 // records' worth of regions and their cursor words — is ONE contiguous piece of each array (what crosses
 // the link in a multi-GPU run).  keep = an owner id: records of every other owner are dropped in the walk
 // and there is a single segment (seg_recs = 0); keep = ~0: all owners' records are kept.
+// Cursor SEGMENTS (without OWN; own.segs = S): a partition's region is S segments, each with its own cursor word and
+// its own capacity cap_p — segment s of partition p of lane l is region (l·S + s)·P + p of lanes·S·P block-interleaved
+// regions, its cursor word at the same index.  A workgroup reserves in segment blockIdx.x % S for its whole life, so
+// the cursor lines the workgroups meet on are S × 64 instead of 64; k_pages32 reads a lane's S segments in turn.
 constexpr uint32_t SC32_MAX_LANES = 128;  // chunk lanes one all-lanes pass of k_scatter32 takes (its per-lane base counts: 1 KiB of static LDS)
 struct OwnerCfg {
   uint32_t log_w;     // owner bits (≤ log_parts)
   uint32_t keep;      // owner id to keep, or ~0 = all
   uint32_t seg_recs;  // records per owner segment (0: one segment only)
-  uint32_t pad;
+  uint32_t segs;      // without OWN: cursor segments per region (a power of two; 0 = 1), see k_scatter32
 };
 template <int NT, int TT, bool WIDE, int LOGP = 0, bool ALL = false, bool OWN = false>
 __global__ void __launch_bounds__(NT, 4) k_scatter32(
@@ -3221,7 +3225,9 @@ __global__ void __launch_bounds__(NT, 4) k_scatter32(
   const uint32_t per = P / NT ? P / NT : 1;
   const uint32_t rbits = 2u * (uint32_t)k - log_parts;  // ≤ 32: bits of a record
   const uint32_t rmask = (uint32_t)(0xFFFFFFFFull >> (32 - rbits));
-  const uint32_t n_regions = (all_lanes ? n_region_lanes : 1u) * P;
+  const uint32_t segs = OWN || own.segs == 0u ? 1u : own.segs;
+  const uint32_t seg = blockIdx.x & (segs - 1u);
+  const uint32_t n_regions = (all_lanes ? n_region_lanes : 1u) * segs * P;
   // owner layout
   const uint32_t log_p1w = OWN ? log_parts - own.log_w : 0u;  // super-page bits inside an owner's share
   const uint32_t p1w_mask = (1u << log_p1w) - 1u;
@@ -3466,7 +3472,7 @@ __global__ void __launch_bounds__(NT, 4) k_scatter32(
           run += (cnt[lo + i] + 1u) & ~1u;
         }
     }
-    const uint32_t rbase = all_lanes ? lane * P : 0u;  // first region of this tile's lane
+    const uint32_t rbase = ((all_lanes ? lane * segs : 0u) + seg) * P;  // first region of this tile's lane, in this workgroup's segment
     // reserve this sub-tile's run in every page's region: one returning device-scope add per
     // non-empty (sub-tile, page); the results are parked in registers over the place phase
     uint32_t gres[MAX_PARTS / NT > 0 ? MAX_PARTS / NT : 1];
@@ -3520,6 +3526,14 @@ __global__ void __launch_bounds__(NT, 4) k_scatter32(
         return reinterpret_cast<uint32_t *>(base + rec_slot(rbase + pc, n_regions, at) * 4u);
       };
       const uint32_t cap4 = cap_p << 2;
+      // LOGP, one lane: the region count goes into the multiplier and the segment into the base — whole as long as it
+      // fits __umul24's 24 bits (S ≤ 4 at LOGP = 10), in blocks beyond (wave-uniform: one of two copies of the loop)
+      const uint32_t nreg_m1 = n_regions - 1u;
+      constexpr bool FOLDED = !OWN && !WIDE && !ALL && LOGP != 0;  // (the variant that folds; every other one has ONE copy of the loop)
+      const bool f24 = !FOLDED || nreg_m1 < (1u << (24 - (RB_LOG + 2)));
+      const uint32_t fac = f24 ? nreg_m1 << (RB_LOG + 2) : nreg_m1;
+      char *const base_seg = base + ((size_t)(seg * P) << (RB_LOG + 2));
+      auto write_out = [&](auto f24_t) {
 #pragma unroll 2
       for (uint32_t i = threadIdx.x; 2 * i < n_ent; i += NT) {
         const uint2 ee = sorted2[i];
@@ -3533,8 +3547,9 @@ __global__ void __launch_bounds__(NT, 4) k_scatter32(
           const uint2 rec2 = make_uint2(r0, r1);  // (both records in one block: one 8-byte store)
           if (!OWN && !WIDE && !ALL && LOGP) {
             // 2^LOGP regions of one lane: byte offset = at·4 + (at >> 10)·(regions - 1)·4096 + region·4096
-            const uint32_t off = __umul24(at4 >> (RB_LOG + 2), (uint32_t)(((1u << LOGP) - 1u) << (RB_LOG + 2))) + at4 + (pcb << RB_LOG);
-            __builtin_memcpy(base + off, &rec2, 8);
+            const uint32_t m = __umul24(at4 >> (RB_LOG + 2), fac);
+            const uint32_t off = (decltype(f24_t)::value ? m : m << (RB_LOG + 2)) + at4 + (pcb << RB_LOG);
+            __builtin_memcpy(base_seg + off, &rec2, 8);
           } else if (!OWN && !WIDE && ALL) {
             // the same with the regions of all lanes block-interleaved together (their number is a wave-uniform
             // run-time value; a lane's buffer stays below 4 GiB or the launch is a WIDE one)
@@ -3552,6 +3567,13 @@ __global__ void __launch_bounds__(NT, 4) k_scatter32(
             else spill_rec(pc, r1);
           }
         }
+      }
+      };
+      if constexpr (FOLDED) {
+        if (f24) write_out(std::true_type{});
+        else write_out(std::false_type{});
+      } else {
+        write_out(std::true_type{});
       }
     }
     STAMP(5);
@@ -4511,7 +4533,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
                                                       const unsigned int *__restrict__ cursor, uint32_t cap_p,
                                                       const uint32_t *__restrict__ part_buf,
                                                       DevStats *__restrict__ stats, SpillRef sp, uint32_t page0 = 0,
-                                                      FusedHist fh = FusedHist{}) {
+                                                      FusedHist fh = FusedHist{}, uint32_t segs = 1) {
   static_assert(!HIST || FRESH, "the fused histogram is a fresh pass's");
   static_assert(TABLE || HIST, "a pass that writes no table leaves the histogram");
   static_assert(FH_BINS == MQ32, "a wave bins into its own miss queue");
@@ -4520,9 +4542,14 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
   __shared__ __attribute__((aligned(16))) uint32_t mqs[(PG_WG / 64) * MQ32];
   if (stats->bad != ~0ull) return;
   const uint32_t page = blockIdx.x + page0;
+  // (lane l, segment s) of this page: region and cursor word (l·segs + s)·pages + page (k_scatter32's cursor segments;
+  // lane_stride = pages or — one lane's regions — 0; segs = 1: l·lane_stride + page)
+  const uint32_t seg_stride = segs > 1 ? 1u << tb.log_pages : 0u;
+  auto region_of = [&](uint32_t l, uint32_t s) -> uint32_t { return l * lane_stride * segs + s * seg_stride + page; };
   if (!FRESH) {
     uint32_t any = 0;
-    for (uint32_t l = lane_lo; l < lane_hi; ++l) any |= cursor[l * lane_stride + page];
+    for (uint32_t l = lane_lo; l < lane_hi; ++l)
+      for (uint32_t s = 0; s < segs; ++s) any |= cursor[region_of(l, s)];
     if (any == 0) return;  // nothing for this page in any lane: leave it untouched in HBM
   }
   uint32_t lane = lane_lo;
@@ -4564,8 +4591,7 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
   const uint32_t room = occ0 < PAGE_FILL_CAP ? (PAGE_FILL_CAP - occ0) / (PG_WG / 64) : 0u;
   for (uint32_t i = threadIdx.x; i < PAGE_SLOTS; i += PG_WG) dl[i] = 0;
   __syncthreads();
-  uint32_t n = 0;        // records of the current lane's region (set per lane below)
-  uint64_t region = 0;   // … and its index among the block-interleaved regions (rec_slot)
+  uint32_t n = 0;        // records of the current lane's segments together (set per lane below)
   const uint64_t n_regions = n_regions_;
   const uint32_t wave = threadIdx.x >> 6, lane_id = threadIdx.x & 63;
   uint32_t *mq = mqs + wave * MQ32;
@@ -4691,10 +4717,16 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
     }
   };
   for (lane = lane_lo; lane < lane_hi; ++lane) {
-    {
-      const uint32_t filled = cursor[lane * lane_stride + page];
-      n = filled < cap_p ? filled : cap_p;  // beyond cap_p: spilled
-    }
+    // (segment 0's fill level is read once; with one segment it is the region's, and the loop below is the single-region one)
+    const uint32_t filled0 = cursor[region_of(lane, 0u)];
+    const uint32_t fill0 = filled0 < cap_p ? filled0 : cap_p;
+    auto seg_fill = [&](uint32_t s) -> uint32_t {  // records in segment s (wave-uniform)
+      if (s == 0u) return fill0;
+      const uint32_t filled = cursor[region_of(lane, s)];
+      return filled < cap_p ? filled : cap_p;  // beyond cap_p: spilled
+    };
+    n = fill0;
+    for (uint32_t s = 1; s < segs; ++s) n += seg_fill(s);
     gv = tb.vals + (uint64_t)lane * tb.cap + ((uint64_t)page << PAGE_LOG);
     if (n == 0) {  // (uniform across the workgroup)
       if (FRESH && TABLE) {
@@ -4710,7 +4742,6 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
       }
       continue;
     }
-    region = (uint64_t)lane * lane_stride + page;
     // this lane's counts of the page: asked for NOW, needed when the lane's records have been counted — the
     // HBM round trip hides behind the record loop instead of standing between two lanes.  (A deeper pipeline —
     // every lane's fill level asked for up front, the next lane's first records in flight over this lane's drain
@@ -4726,12 +4757,16 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
     // Main loop: one 16-B load = four records per thread per step, the next step's load in flight.
     // No barrier in here: queues are per wave, and a slot's count of this pass is a full 32-bit word
     // (a page sees < 2^31 records), so nothing has to be folded away mid-pass.
-    const uint32_t n_steps = n / (P32_RPS * PG_WG);
+    // The lane's segments go into the same counts one after the other, ONE pipeline across them: first every segment's
+    // whole steps (the load in flight may be the next segment's first), then what is left of all of them as one dense
+    // run of quads — a thread finds its quad's (segment, offset) from the prefix sums — so that a page pays about as
+    // many partial steps as there are records for, not one per segment.
+    constexpr uint32_t STEP = P32_RPS * PG_WG;
     // (a region of at most two steps — a chunk lane's share of a page on a many-lane table — fits the miss queue
     // whole: one drain at the end instead of three, each of which is a chain of LDS round trips)
     const bool early = n > 2 * P32_RPS * PG_WG;
-    auto load4 = [&](uint32_t step) {  // this lane's four records of a step (they share a block)
-      return *reinterpret_cast<const uint4 *>(part_buf + rec_slot64(region, n_regions, (step * PG_WG + threadIdx.x) * 4u));
+    auto load4 = [&](uint32_t s, uint32_t j) {  // four records from record j of segment s on (they share a block)
+      return *reinterpret_cast<const uint4 *>(part_buf + rec_slot64(region_of(lane, s), n_regions, j));
     };
     // `nv` = how many of the lane's four records exist (4 in every step but a page's last, partial one)
     auto body = [&](uint32_t step, const uint4 &cur, uint32_t nv, auto partial) {
@@ -4774,20 +4809,75 @@ __global__ void __launch_bounds__(PG_WG, 4) k_pages32(TableRef tb, uint32_t lane
       // repeats until it is inserted (measured: 4 early drains 0.232 ms, 0 → 0.240, 16 → 0.257)
       if (n_miss > MQ32 - 64 * P32_RPS || (step < P32_EARLY && early)) drain();
     };
-    uint4 nxt;
-    if (n_steps) nxt = load4(0);
-    // the last, partial step's records are asked for now as well (a short region is two loads: both in flight)
-    const uint32_t tail_j = (n_steps * PG_WG + threadIdx.x) * 4u;
-    const uint32_t tail_nv = tail_j < n ? (n - tail_j < 4u ? n - tail_j : 4u) : 0u;
-    uint4 tailv = make_uint4(0u, 0u, 0u, 0u);
-    if (tail_nv) tailv = load4(n_steps);  // (a quad never straddles a block; its tail past n is ignored)
-    for (uint32_t step = 0; step < n_steps; ++step) {
-      const uint4 cur = nxt;
-      if (step + 1 < n_steps) nxt = load4(step + 1);
-      body(step, cur, 4u, std::false_type{});
+    if (segs == 1) {  // one region per (lane, page): the loop as it has always been (every lane of a many-lane table comes through here)
+      const uint32_t n_steps = n / STEP;
+      uint4 nxt;
+      if (n_steps) nxt = load4(0u, threadIdx.x * 4u);
+      // the last, partial step's records are asked for now as well (a short region is two loads: both in flight)
+      const uint32_t tail_j = (n_steps * PG_WG + threadIdx.x) * 4u;
+      const uint32_t tail_nv = tail_j < n ? (n - tail_j < 4u ? n - tail_j : 4u) : 0u;
+      uint4 tailv = make_uint4(0u, 0u, 0u, 0u);
+      if (tail_nv) tailv = load4(0u, tail_j);  // (a quad never straddles a block; its tail past n is ignored)
+      for (uint32_t step = 0; step < n_steps; ++step) {
+        const uint4 cur = nxt;
+        if (step + 1 < n_steps) nxt = load4(0u, ((step + 1) * PG_WG + threadIdx.x) * 4u);
+        body(step, cur, 4u, std::false_type{});
+      }
+      if (n_steps * STEP < n)  // the page's last, partial step: lanes past the end sit it out
+        body(n_steps, tailv, tail_nv, std::true_type{});
+    } else {
+      auto next_seg = [&](uint32_t s) -> uint32_t {  // the first segment from s on that has a whole step
+        while (s < segs && seg_fill(s) < STEP) ++s;
+        return s;
+      };
+      // this thread's quad of partial step t: its records (0: none), where they are
+      auto tail_quad = [&](uint32_t t, uint32_t &qs, uint32_t &qj) -> uint32_t {
+        const uint32_t q = t * PG_WG + threadIdx.x;
+        uint32_t acc = 0, nv = 0;
+        for (uint32_t s = 0; s < segs; ++s) {
+          const uint32_t ns = seg_fill(s), left = ns & (STEP - 1u), quads = (left + 3u) >> 2;
+          if (q - acc < quads) {  // (q < acc wraps: no)
+            const uint32_t o = (q - acc) * 4u;
+            nv = left - o < 4u ? left - o : 4u;
+            qs = s;
+            qj = (ns & ~(STEP - 1u)) + o;
+          }
+          acc += quads;
+        }
+        return nv;
+      };
+      uint32_t tail_quads = 0;
+      for (uint32_t s = 0; s < segs; ++s) tail_quads += ((seg_fill(s) & (STEP - 1u)) + 3u) >> 2;
+      const uint32_t tail_steps = (tail_quads + PG_WG - 1u) / PG_WG;
+      uint4 nxt;
+      uint32_t ls = next_seg(0), lj = 0;  // the load in flight: segment, step inside it
+      uint32_t lw = ls < segs ? seg_fill(ls) / STEP : 0u;  // … and that segment's whole steps (no cursor is read inside the loop)
+      if (ls < segs) nxt = load4(ls, threadIdx.x * 4u);
+      // the first partial step's records are asked for now as well (a short region is two loads: both in flight)
+      uint32_t qs = 0, qj = 0;
+      uint32_t tail_nv = tail_quad(0, qs, qj);
+      uint4 tailv = make_uint4(0u, 0u, 0u, 0u);
+      if (tail_nv) tailv = load4(qs, qj);  // (a quad never straddles a block; its tail past the segment's end is ignored)
+      uint32_t step = 0;  // steps of this lane so far (the early drains are for a page's first steps)
+      while (ls < segs) {
+        const uint4 cur = nxt;
+        if (++lj == lw) {
+          ls = next_seg(ls + 1), lj = 0;
+          lw = ls < segs ? seg_fill(ls) / STEP : 0u;
+        }
+        if (ls < segs) nxt = load4(ls, (lj * PG_WG + threadIdx.x) * 4u);
+        body(step++, cur, 4u, std::false_type{});
+      }
+      for (uint32_t t = 0; t < tail_steps; ++t) {  // partial steps: lanes past the end sit them out
+        const uint4 cur = tailv;
+        const uint32_t nv = tail_nv;
+        if (t + 1 < tail_steps) {
+          tail_nv = tail_quad(t + 1, qs, qj);
+          if (tail_nv) tailv = load4(qs, qj);
+        }
+        body(step++, cur, nv, std::true_type{});
+      }
     }
-    if (n_steps * P32_RPS * PG_WG < n)  // the page's last, partial step: lanes past the end sit it out
-      body(n_steps, tailv, tail_nv, std::true_type{});
     drain();
     lds_barrier();
     // this pass's counts → the page's counts (saturating), four slots per lane and step; all of a

@@ -339,7 +339,9 @@ struct shk_ctx {
     const unsigned int *cursor;
     const uint32_t *buf;
     uint64_t spill_cap;
+    uint32_t segs;  // cursor segments per (lane, page) region
   } vt{};
+  uint32_t last_segs = 0;  // cursor segments of the last paged counting launch (shk_get_scatter_segments)
   double lazy_ms = 0;          // the materialising passes: a slot beside shk_timings (whose layout is ABI 2's)
   uint64_t lazy_launches = 0;
   // the histogram and totals on the device still hold what the last finalize read back: cleared by the next
@@ -979,6 +981,18 @@ static bool use_rec32(const shk_ctx *c, const PartGeom &g) {
 #ifndef SHK_SC32_WGS
 #define SHK_SC32_WGS 1
 #endif
+// (SHK_SC32_SEGS: cursor segments of k_scatter32's page regions on the immediate one-level route — 1, 2, 4, 8 or 16;
+// the build's default for ONE lane's regions, and a run-time test hook of the same name, read where the route is
+// resolved, which holds for all-lanes launches too.  Those stay at one segment by default: a (lane, page) region of a
+// many-lane job is a step or two of the page pass, and S partial regions in its place cost 40 and 100 lanes 17–20 %)
+#ifndef SHK_SC32_SEGS
+#define SHK_SC32_SEGS 4
+#endif
+static uint32_t sc32_segs(bool all_lanes) {
+  const uint32_t dflt = all_lanes ? 1u : (uint32_t)SHK_SC32_SEGS;
+  const int s = env_int("SHK_SC32_SEGS", (int)dflt);
+  return s == 1 || s == 2 || s == 4 || s == 8 || s == 16 ? (uint32_t)s : dflt;
+}
 constexpr int SC32_NT = SHK_SC32_NT, SC32_TT = 16 * SHK_SC32_NT;  // k_scatter32: 64 KiB of records + 64 KiB of entries in LDS,
 constexpr size_t SC32_LDS_MAX = 160 * 1024 - 2048;  // one workgroup per CU (its static LDS is < 2 KiB: per-lane base counts of up to 128 chunk lanes)
 static size_t scatter32_lds(uint32_t P1) {
@@ -1038,10 +1052,12 @@ struct PagedRoute {
   bool two_level;
   bool all_lanes;         // ALL-LANES mode (immediate passes only; deferred: always (lane, page) regions)
   bool one_pass;          // every lane's tiles in a single scatter launch
+  uint32_t segs;          // cursor segments per page region (k_scatter32 straight into the regions k_pages32 reads: immediate, one level)
   uint32_t cursor_words;  // per-launch cursor words, from the start of part_meta
 };
 static PagedRoute paged_route(const shk_ctx *c, const PartGeom &g, bool multi, bool defer) {
   PagedRoute r{};
+  r.segs = 1;
   r.two_level = g.two_level;
   r.owner = xl_route(c, g, multi, defer) ? XL_REC32 : defer && xl64_route(c, g) ? XL_REC64 : XL_NONE;
   if (r.owner != XL_NONE) {  // one segment's cursors: [lane][super-page of the share]
@@ -1062,7 +1078,8 @@ static PagedRoute paged_route(const shk_ctx *c, const PartGeom &g, bool multi, b
   r.all_lanes = use_all_lanes(c, g, multi) && !defer;
   r.one_pass = r.all_lanes || (defer && !g.two_level && rec32);
   // deferred: page regions and cursors are the accumulation ones and persist; only a level-1 pass has cursors of its own
-  r.cursor_words = defer ? (g.two_level ? g.P1 : 0) : (r.all_lanes ? c->n_lanes : 1) * g.P1 + (g.two_level ? g.n_pages : 0);
+  if (!defer && !g.two_level && r.scatter == SCATTER_32) r.segs = sc32_segs(r.all_lanes);
+  r.cursor_words = defer ? (g.two_level ? g.P1 : 0) : (r.all_lanes ? c->n_lanes : 1) * r.segs * g.P1 + (g.two_level ? g.n_pages : 0);
   return r;
 }
 
@@ -1260,7 +1277,7 @@ static bool first_launch_defers(shk_ctx *c, uint64_t kmers_ub, bool multi) { ret
 // must not be reallocated between k_mark_starts (which clears cursors in it) and the partition launch.
 static size_t cursor_buf_bytes(const shk_ctx *c, const PartGeom &g, const PagedRoute &r) {
   const bool lanes = r.all_lanes || r.owner != XL_NONE;  // (the owner layouts: n_lanes · P1 words, whatever the number of segments)
-  return ((size_t)(lanes ? c->n_lanes : 1) * g.P1 + g.n_pages) * 4 + 64;
+  return ((size_t)(lanes ? c->n_lanes : 1) * r.segs * g.P1 + g.n_pages) * 4 + 64;
 }
 
 // Room for the partition cursors of the next paged pass; *n_words = how many k_mark_starts clears.
@@ -1290,10 +1307,11 @@ static hipError_t scatter32_variant(shk_ctx *c, bool set_attr, uint32_t G, size_
 }
 static int launch_scatter32(shk_ctx *c, bool wide, uint32_t G, size_t lds, const BatchRef &b, uint32_t log_p1,
                             uint32_t lane_filter, unsigned int *cursor, uint32_t cap, uint32_t *buf, SpillRef sp,
-                            unsigned long long *dbg, uint32_t NL, const OwnerCfg *own = nullptr) {
+                            unsigned long long *dbg, uint32_t NL, const OwnerCfg *own = nullptr, uint32_t segs = 1) {
   const bool all = lane_filter == 0xFFFFFFFFu, p10 = log_p1 == 10;
   if (own && (wide || !all)) return fail(c, SHK_ERR_INVARIANT, "the owner layout's scatter takes every lane and 32-bit offsets");
-  const OwnerCfg oc = own ? *own : OwnerCfg{};
+  if (segs > 1 && (own || wide)) return fail(c, SHK_ERR_INVARIANT, "cursor segments are the immediate one-level route's");
+  const OwnerCfg oc = own ? *own : OwnerCfg{0u, 0u, 0u, segs};
   auto each = [&](bool set_attr, bool w, bool p, bool a, bool o) -> hipError_t {
 #define SHK_V(W, LP, A, O) scatter32_variant<W, LP, A, O>(c, set_attr, G, lds, b, log_p1, lane_filter, cursor, cap, buf, sp, dbg, NL, oc)
     if (o) return p ? SHK_V(false, 10, true, true) : SHK_V(false, 0, true, true);
@@ -1694,10 +1712,10 @@ static void launch_scatter_sorted(shk_ctx *c, bool rec32, uint32_t G, const Batc
 // hist_only (with fuse): the form that writes no table (the caller makes the table virtual).
 static void launch_pages32(shk_ctx *c, bool fresh, bool fuse, uint32_t n_blocks, uint32_t page0, uint32_t l_lo, uint32_t l_hi, uint32_t lane_stride,
                            uint32_t n_regions, const unsigned int *cursor, uint32_t cap, const uint32_t *buf, SpillRef sp, const FusedHist &fh,
-                           bool hist_only = false) {
+                           bool hist_only = false, uint32_t segs = 1) {
 #define SHK_PG(F, H, T)                                                                                                                       \
   hipLaunchKernelGGL((k_pages32<F, H, T>), dim3(n_blocks), dim3(PG_WG), 0, c->stream, c->tb, l_lo, l_hi, lane_stride, n_regions, cursor, cap, \
-                     buf, c->d_stats, sp, page0, fh)
+                     buf, c->d_stats, sp, page0, fh, segs)
   if (!fresh)
     SHK_PG(false, 0, true);
   else if (!fuse)
@@ -1731,6 +1749,7 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
   const PartGeom pg = part_geom(c);
   const bool multi = b.tiles != nullptr;
   const PagedRoute r = paged_route(c, pg, multi, defer);
+  c->last_segs = r.segs;
   if (r.owner != XL_NONE) return xl_count(c, r.rec_bytes, b, pg, sub_kmers_ub, sp, prezeroed);
   if (pg.lw) return fail(c, SHK_ERR_INVARIANT, "an owner share has no paged path besides the owner layout");
   const uint32_t lp = pg.lp, n_pages = pg.n_pages, log_p1 = pg.log_p1, log_sub = pg.log_sub, P1 = pg.P1;
@@ -1756,11 +1775,19 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
   const uint32_t cap1_unit = r.scatter == SCATTER_64_INTERLEAVED ? (uint32_t)RS_TILE : 1u << RB_LOG;
   bool all_lanes = r.all_lanes, one_pass = r.one_pass;
   uint32_t n_cursor_words = r.cursor_words;
-  uint32_t cap1 = (region_cap(all_lanes ? striped_lane_ub(c, sub_kmers_ub) : sub_kmers_ub, P1, pads) + cap1_unit - 1u) & ~(cap1_unit - 1u);
-  if (all_lanes && (uint64_t)NL * P1 * cap1 * 4 > 0xFFFFFFFFull) {  // 32-bit byte offsets: fall back to a pass per lane
+  // (cursor segments: cap1 is a SEGMENT's capacity and level 1 has segs regions per partition.  A segment gets its
+  // share of what the region would get, slack included, in whole blocks: S times region_cap's 1024 records of slack
+  // would let a skewed batch that overflows a region today pass without a spill)
+  const uint32_t S = r.segs;
+  auto seg_cap = [&](uint64_t records_ub) -> uint32_t {
+    const uint32_t whole = region_cap(records_ub, P1, pads);
+    return ((S > 1 ? (whole + S - 1u) / S : whole) + cap1_unit - 1u) & ~(cap1_unit - 1u);
+  };
+  uint32_t cap1 = seg_cap(all_lanes ? striped_lane_ub(c, sub_kmers_ub) : sub_kmers_ub);
+  if (all_lanes && (uint64_t)NL * S * P1 * cap1 * 4 > 0xFFFFFFFFull) {  // 32-bit byte offsets: fall back to a pass per lane
     all_lanes = one_pass = false;
-    n_cursor_words = P1;
-    cap1 = (region_cap(sub_kmers_ub, P1, pads) + cap1_unit - 1u) & ~(cap1_unit - 1u);
+    n_cursor_words = S * P1;
+    cap1 = seg_cap(sub_kmers_ub);
   }
   if (n_cursor_words > r.cursor_words)  // (k_mark_starts cleared the route's words, and no more, for a prezeroed launch)
     return fail(c, SHK_ERR_INVARIANT, "a paged launch wants %u cursor words, its route has %u", n_cursor_words, r.cursor_words);
@@ -1772,9 +1799,9 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
 
   const bool to_acc1 = defer && !two_level;  // level 1 fills the waiting page regions itself
   if (!to_acc1) {
-    if ((uint64_t)region_lanes * P1 * cap1 * r.rec_bytes > 0xFFFFFFFFull)  // 32-bit byte offsets in the scatter
+    if ((uint64_t)region_lanes * S * P1 * cap1 * r.rec_bytes > 0xFFFFFFFFull)  // 32-bit byte offsets in the scatter
       return fail(c, SHK_ERR_INVARIANT, "partition buffer of one launch exceeds 4 GiB");
-    HIPC(c, c->part.ensure((uint64_t)region_lanes * P1 * cap1 * r.rec_bytes));
+    HIPC(c, c->part.ensure((uint64_t)region_lanes * S * P1 * cap1 * r.rec_bytes));
   }
   if (two_level && !defer) HIPC(c, c->part3.ensure((uint64_t)n_pages * cap_pg * r.rec_bytes));
   if (!rec32 && !defer)
@@ -1803,7 +1830,7 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
       int rcl = SHK_OK;
       if (r.scatter == SCATTER_32)
         rcl = launch_scatter32(c, wide1, std::min<uint32_t>(G, c->n_cus_scatter * SHK_SC32_WGS), scatter32_lds(P1), b, log_p1,
-                               one_pass ? 0xFFFFFFFFu : lane, d1.cursor, d1.cap, (uint32_t *)d1.buf, sp, dbg, NL);
+                               one_pass ? 0xFFFFFFFFu : lane, d1.cursor, d1.cap, (uint32_t *)d1.buf, sp, dbg, NL, nullptr, S);
       else if (r.scatter == SCATTER_SORTED)
         launch_scatter_sorted(c, rec32, G, b, log_p1, lane, d1.cursor_of(lane), d1.cap, rec32 ? d1.buf : d1.buf64_of(lane), sp, dbg);
       else  // 8-byte records, k_scatter32's machine
@@ -1831,8 +1858,8 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
       const bool lazy = fuse && !more_follow && lazy_table_wanted(c) && c->h_stats->n_distinct == 0;
       ScopedTimer t(c, SHK_K_PAGES, /*chain=*/true);
       if (rec32) {
-        launch_pages32(c, fresh, fuse, n_pages, 0u, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cursor, dpg.cap,
-                       (const uint32_t *)dpg.buf, sp, fh, lazy);
+        launch_pages32(c, fresh, fuse, n_pages, 0u, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * S * n_pages, dpg.cursor, dpg.cap,
+                       (const uint32_t *)dpg.buf, sp, fh, lazy, S);
         if (fresh) {
           c->tb_stale = false;
           c->fused_valid = fuse;
@@ -1840,7 +1867,7 @@ static int paged_count(shk_ctx *c, const BatchRef &b, uint64_t sub_kmers_ub, Spi
         }
         if (lazy) {
           c->tb_virtual = true;
-          c->vt = {n_pages, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * n_pages, dpg.cap, dpg.cursor, (const uint32_t *)dpg.buf, sp.cap};
+          c->vt = {n_pages, l_lo, l_hi, (uint32_t)dpg.lane_stride, region_lanes * S * n_pages, dpg.cap, dpg.cursor, (const uint32_t *)dpg.buf, sp.cap, S};
         }
       } else
         launch_pages64(c, false, n_pages, 0u, lane, lane + 1, 0u, dpg.cursor, dpg.cap, (const uint64_t *)dpg.buf, sp);
@@ -2140,7 +2167,7 @@ static int tb_materialise(shk_ctx *c) {
     HIPC(c, hipMemcpyAsync(&c->d_stats->n_distinct, w, sizeof w, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));  // (`w` lives on this stack)
     ScopedTimer t(c, K_MATERIALISE);
-    launch_pages32(c, true, false, v.n_pages, 0u, v.l_lo, v.l_hi, v.lane_stride, v.n_regions, v.cursor, v.cap, v.buf, spill_ref(c->spillA, v.spill_cap), FusedHist{});
+    launch_pages32(c, true, false, v.n_pages, 0u, v.l_lo, v.l_hi, v.lane_stride, v.n_regions, v.cursor, v.cap, v.buf, spill_ref(c->spillA, v.spill_cap), FusedHist{}, false, v.segs);
     HIPC(c, hipGetLastError());
     return SHK_OK;
   }();
@@ -3459,6 +3486,12 @@ int shk_get_lazy_table_timing(shk_ctx *c, double *ms, uint64_t *launches) {
   }
   if (ms) *ms = m;
   if (launches) *launches = n;
+  return SHK_OK;
+}
+
+int shk_get_scatter_segments(shk_ctx *c, uint32_t *segs) {
+  if (!c || !segs) return SHK_ERR_BAD_ARG;
+  *segs = c->group ? (c->group->D ? c->group->ctx[0]->last_segs : 0u) : c->last_segs;
   return SHK_OK;
 }
 

@@ -429,7 +429,7 @@ class _Synth(C.Structure):
 ABI_SYMBOLS = [
     "shk_abi_version", "shk_create", "shk_destroy", "shk_reset", "shk_last_error", "shk_ingest_batch",
     "shk_ingest_reads", "shk_set_read_index", "shk_ingest_reads_device", "shk_insert_counts", "shk_sync", "shk_finalize",
-    "shk_histograms", "shk_get_counters", "shk_get_timings", "shk_reset_timings", "shk_get_lazy_table_timing",
+    "shk_histograms", "shk_get_counters", "shk_get_timings", "shk_reset_timings", "shk_get_lazy_table_timing", "shk_get_scatter_segments",
     "shk_export_table", "shk_lookup", "shk_find_oligos", "shk_primer_compile", "shk_primer_kmers", "shk_filter_reads", "shk_kmers_from_reads", "shk_table_geometry", "shk_table_reserve_pages", "shk_owner_counts", "shk_compact_owners",
     "shk_merge_entries",
     "shk_table_device_ptrs", "shk_merge_pages", "shk_set_owned_pages", "shk_alloc_pinned",
@@ -560,6 +560,7 @@ def load_library():
     L.shk_get_timings.argtypes = [vp, C.POINTER(_Timings)]
     L.shk_reset_timings.argtypes = [vp]
     L.shk_get_lazy_table_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.shk_get_scatter_segments.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.shk_export_table.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.shk_lookup.argtypes = [vp, vp, vp, u64, C.c_int]
     L.shk_find_oligos.argtypes = [vp, vp, u32, u32, u32, vp, vp, u64, C.POINTER(u64)]
@@ -814,6 +815,12 @@ class KmerEngine:
         if n.value:
             out["materialise"] = (float(ms.value), int(n.value))
         return out
+
+    def scatter_segments(self) -> int:
+        """Cursor segments per page region of the last paged counting launch (0: none yet)."""
+        s = C.c_uint32(0)
+        self._check(self._L.shk_get_scatter_segments(self._h, C.byref(s)))
+        return int(s.value)
 
     def reset_timings(self):
         self._check(self._L.shk_reset_timings(self._h))
