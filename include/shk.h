@@ -804,6 +804,108 @@ int shk_pcr_dedup_panel(shk_ctx *ctx, const uint8_t *seqs, const uint64_t *seq_o
 int shk_pcr_products_panel(shk_ctx *ctx, const shk_pcr_graphs *graphs, const shk_pcr_paths_params *params,
                            const uint32_t *thresholds, shk_pcr_records *out, uint32_t *retained, double *device_ms);
 
+/* ---- do_pcr / run_pcr: the stages above as one call over a panel (src/pcr/mod.rs:431-819, src/stats.rs:49-183;
+ *      DESIGN.md §18) ---- */
+
+typedef struct shk_pcr_gene {          /* PCRParams as do_pcr reads it; reference defaults in brackets */
+  const char *gene_name, *forward_seq, *reverse_seq;   /* primers upper case IUPAC, as parse_pcr_primers_string leaves them */
+  uint64_t min_length /*0*/, max_length /*10000*/;
+  uint32_t min_count /*2*/, mismatches /*2*/, trim /*15*/, dedup_edit_threshold /*10*/;
+  uint64_t max_dfs_states /*100000*/, max_paths_per_pair /*20*/, max_node_visits /*2*/;
+  uint32_t max_primer_kmers /*40*/, reserved;
+  double   high_coverage_ratio /*10.0*/, tip_coverage_fraction /*0.1*/;
+} shk_pcr_gene;
+/* The defaults of parse_pcr_primers_string (cli.rs:17-27, 131-136): everything but the three strings, which are left. */
+void shk_pcr_gene_defaults(shk_pcr_gene *g);
+
+/* parse_pcr_primers_string (cli.rs:12-140): "key=value,key=value,..." into *out (defaults first).  Items are split on
+ * commas, each at its first '=', keys lower-cased; name, forward, reverse (upper-cased), max-length, min-length,
+ * min-count, mismatches, trim, dedup-edit-threshold; citation and notes are accepted and dropped.  The three strings
+ * are stored NUL-terminated in `strings` (strings_cap bytes; strlen(spec) + 3 always suffice) and *out points into it.
+ * SHK_ERR_BAD_ARG with the reference's text in err (at most err_cap bytes with the NUL): "Invalid empty primer
+ * specification", "Invalid parameter (should be key=value): '…'…", "Duplicate parameter '…' in primer specification
+ * '…'. Each key may appear at most once.", "Unexpected parameter: …", and for a number that does not parse "Invalid
+ * value for {key}: {value}" (the context anyhow prints first; its cause line is Rust's ParseIntError text and is not
+ * reproduced). */
+int shk_pcr_parse_primers(const char *spec, shk_pcr_gene *out, char *strings, size_t strings_cap, char *err, size_t err_cap);
+/* validate_pcr_params (mod.rs:295-399): the number of (error, suggestion) pairs found, 0 for a valid gene; they are
+ * written to buf as "error\nsuggestion\n" per pair in the reference's order (at most buf_cap bytes with the NUL; buf may
+ * be NULL).  Host only, no context. */
+int shk_pcr_validate_gene(const shk_pcr_gene *g, char *buf, size_t buf_cap);
+/* The bail! text of collect_pcr_params (cli.rs:528-554) over n genes: returns the total number of errors (0: nothing
+ * written), "Primer validation failed (N error[s]):\n" and per failing gene "\n  {name} ({source}):\n" with
+ * "    - {error}\n      Suggestion: {suggestion}\n" lines.  sources[g] NULL (or sources NULL): "--pcr-primers". */
+int shk_pcr_validation_report(const shk_pcr_gene *genes, uint32_t n, const char *const *sources, char *buf, size_t buf_cap);
+
+#define SHK_PCR_SUCCESS 0u
+#define SHK_PCR_NO_FORWARD 1u   /* "forward primer not found" (mod.rs:449-467) */
+#define SHK_PCR_NO_REVERSE 2u   /* "reverse primer not found" */
+#define SHK_PCR_NO_PRIMERS 3u   /* "forward and reverse primers not found" */
+#define SHK_PCR_NO_PATH 4u      /* "no path found" (mod.rs:567) */
+#define SHK_PCR_NODE_BUDGET 5u  /* "node budget exceeded" (mod.rs:621-623) */
+/* PcrOutcome.failure_reason for a status: NULL for SHK_PCR_SUCCESS (and for a number that is no status). */
+const char *shk_pcr_failure_reason(uint32_t status);
+
+#define SHK_PCR_READS_NONE 0u      /* reads = None: k-mer-only scoring */
+#define SHK_PCR_READS_RETAINED 1u  /* every read retained so far (shk_retain_reads) */
+#define SHK_PCR_READS_HOST 2u      /* bases / offsets / n_seqs below, as shk_ingest_reads */
+typedef struct shk_pcr_run_params {
+  uint32_t min_kmer_count;   /* cli --min-kmer-count [2]: FilteredKmerCounts' floor; 0 is read as 1 */
+  uint32_t reads;            /* SHK_PCR_READS_* */
+  uint32_t paired;           /* RETAINED or HOST without read_index/mate: reads alternate R1, R2, index = ordinal
+                                (reread_sequences, io.rs:831-898); 0: every read Unpaired */
+  uint32_t reserved;
+  uint64_t max_num_nodes;    /* 0: shk_pcr_node_budget(n_bases_ingested of the context) (main.rs:147-165) */
+  const uint8_t *bases; const uint64_t *offsets; uint64_t n_seqs;
+  const uint64_t *read_index; const uint8_t *mate;   /* HOST only, both or neither; given, they override `paired` */
+  uint64_t reserved2[4];
+} shk_pcr_run_params;
+
+typedef struct shk_pcr_run_out {   /* every pointer optional except records.record_offsets and status; [n_genes] each */
+  shk_pcr_records records;         /* the final products of all genes in gene order: the layout and the capacity
+                                      protocol of shk_pcr_products_panel (a gene without products has none) */
+  uint32_t *status;                /* SHK_PCR_* */
+  uint32_t *n_fwd_kmers, *n_rev_kmers;       /* sizes of the two primer k-mer sets */
+  uint32_t *max_fwd_count, *max_rev_count;   /* get_max_count of each (mod.rs:542-543); 0 for an empty set */
+  uint32_t *median_primer_count;   /* min of the two get_median_count (mod.rs:546-548, counting.rs:275-298) */
+  uint32_t *threshold_used, *steps_run, *found_path;  /* shk_pcr_extend_panel's; 0 for a gene that returned before */
+  uint64_t *n_nodes, *n_edges;     /* of the extended graph (the last step run) */
+  uint64_t *n_pruned_nodes, *n_pruned_edges;  /* of the pruned graph; 0 without a found path */
+  uint64_t *n_reads_matched;       /* the gene's filter list length; 0 without reads */
+  uint8_t  *threaded;              /* 1: the gene's reads were threaded through its pruned graph (mod.rs:664-697) */
+  uint64_t *n_paired_links;        /* thread_reads_paired's paired_links.len() */
+  uint8_t  *low_primer_counts;     /* 1: either max count below 5 (mod.rs:752-759) */
+  uint64_t reserved[4];
+} shk_pcr_run_out;
+
+/* run_pcr's loop over do_pcr (stats.rs:84-98, mod.rs:431-819) for a panel, the genes side by side: every stage above is
+ * called ONCE for all genes still alive, and not at all when none is left.  Needs a finalized context, as
+ * shk_primer_kmers.  Per gene, in this order:
+ *   1. min_count <- max(min_count, min_kmer_count) (collect_pcr_params, cli.rs:556-570).
+ *   2. shk_primer_kmers for the whole panel (forward then reverse per gene; min_count the clamped one, max_kmers =
+ *      max_primer_kmers).  An empty set: status 1 / 2 / 3 and nothing more for the gene (mod.rs:446-468).
+ *   3. With reads: the gene's filter set is the canonical forms of both sets (from_primer_kmers, read_filter.rs:24-41);
+ *      one panel filter pass for the genes that got this far.
+ *   4. shk_pcr_extend_panel with min_count, table_min_count = min_kmer_count, high_coverage_ratio, max_num_nodes, sweep.
+ *   5. The reason starts as NO_PATH; the last step's graph with n_nodes >= max_num_nodes makes it NODE_BUDGET
+ *      (mod.rs:621, path or not).
+ *   6. Only with found_path: prune (tip_coverage_fraction); thread iff reads were given and the gene's list is not empty
+ *      (mod.rs:664-697), paired iff some listed read has mate != 0 (mod.rs:671); shk_pcr_products_panel with annotations
+ *      exactly for the threaded genes.  At least one generated record: SUCCESS; otherwise the reason of step 5 stays.
+ * READS: a HOST batch is staged once for both read-side stages; RETAINED runs both over the planes (SHK_ERR_STATE with
+ *   retention off); with `paired` and no arrays the mate of read i is 1 + (i & 1) and its index i, looked up for listed
+ *   reads only.  Zero reads behave like an empty list for every gene.
+ * ERRORS, the first gene in gene order that has one, with a text that names the gene, all before the device is touched;
+ *   within a gene: its first shk_pcr_validate_gene failure, then "Duplicate gene name '…'" when an earlier gene has the
+ *   name (cli.rs:572-581), both SHK_ERR_BAD_ARG; then get_primer_kmers' errors in its order — too many variants
+ *   forward, reverse, invalid character forward, reverse (primers.rs:440-478; the validation lets no character through
+ *   that the conversion refuses).  Multi-device contexts and owner shares: SHK_ERR_STATE, as shk_pcr_extend_panel.
+ *   records.record_cap / seq_cap too small: SHK_ERR_BAD_ARG with n_records / n_seq_bytes the need and every per-gene
+ *   array complete.  n_genes == 0: SHK_OK, nothing launched.
+ * With SHK_TRACE set: one line per gene on stderr after the run. */
+int shk_pcr_run(shk_ctx *ctx, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params,
+                shk_pcr_run_out *out);
+
 /* ---- multi-GPU hooks (device pointers; exchanged by the caller over RCCL) ---- */
 
 /* Table geometry needed to shard by owner: n_pages (power of two),
@@ -1013,7 +1115,7 @@ int shk_write_histo(const char *path, const char *version, uint32_t k, uint32_t 
 int shk_write_final_histo(const char *path, const char *version, uint32_t k, uint32_t chunks,
                           uint64_t histo_max, const uint64_t *histo);
 
-/* RunStats (stats.rs:27-45) as filled at main.rs:182-197; pcr_results is always empty here. */
+/* RunStats (stats.rs:27-45) as filled at main.rs:182-197; pcr_results goes beside it (shk_write_stats_yaml_pcr). */
 typedef struct shk_run_stats {
   const char *sharkmer_version;
   const char *command;
@@ -1039,7 +1141,7 @@ int shk_validate_args(uint32_t k, uint64_t histo_max, const char *sample);
 const char *shk_run_error(void);
 
 /* ingest_reads + consolidate_and_histogram + write_stats over local files (main.rs:74-78,
- * 112-197 without sPCR): the flags -k --chunks --histo-max -m -s -o --validate-every. */
+ * 112-197 without sPCR; with it: shk_run_files_pcr below): the flags -k --chunks --histo-max -m -s -o --validate-every. */
 typedef struct shk_run_config {
   const char *const *inputs; /* FASTQ(.gz) paths; n_inputs == 0 ⇒ stdin */
   uint32_t n_inputs;
@@ -1061,6 +1163,43 @@ typedef struct shk_run_config {
   const int32_t *device_ids;
 } shk_run_config;
 int shk_run_files(const shk_run_config *cfg, shk_run_stats *out_stats);
+
+/* write_fasta_record (io.rs:144-158) for records first .. first + n of recs (the layout shk_pcr_run fills), the i-th of
+ * them as product i: ">{sample}_{gene}_{i} sample={sample} gene={gene} product={i} length=… kmer_count_mean=…
+ * kmer_count_median=… kmer_count_min=… kmer_count_max=… score=…" (paths.rs:331-343 as renumbered at mod.rs:785-813),
+ * then the sequence wrapped at 80 columns (FASTA_LINE_WIDTH, io.rs:14).  The file is created or truncated. */
+int shk_write_fasta(const char *path, const char *sample, const shk_pcr_gene *gene, const shk_pcr_records *recs,
+                    uint64_t first, uint64_t n);
+
+/* PcrGeneResult (stats.rs:11-23) as run_pcr fills it (stats.rs:102-145): status "success" for SHK_PCR_SUCCESS and
+ * "fail" otherwise, failure_reason = shk_pcr_failure_reason(status); output_file is always None there. */
+typedef struct shk_pcr_gene_stat {
+  const char *gene_name;
+  uint32_t status;                 /* SHK_PCR_* */
+  uint32_t n_products;
+  const uint64_t *product_lengths; /* [n_products]; the key is omitted when n_products == 0 */
+} shk_pcr_gene_stat;
+/* shk_write_stats_yaml plus pcr_results (stats.rs:43-44); n == 0 omits the key: the bytes of shk_write_stats_yaml. */
+int shk_write_stats_yaml_pcr(const char *path, const shk_run_stats *st, const shk_pcr_gene_stat *results, uint32_t n);
+
+/* The sPCR side of a file run: what --pcr-primers, --min-kmer-count, --read-threading and --node-budget-global set
+ * (main.rs:133-178). */
+typedef struct shk_pcr_file_config {
+  const shk_pcr_gene *genes;
+  uint32_t n_genes;
+  uint32_t min_kmer_count;      /* [2]; 0 is read as 1 */
+  uint32_t read_threading;      /* 1: retain the reads at ingest and thread them; stdin input: k-mer-only scoring
+                                   (main.rs:136-139) */
+  uint32_t dump;                /* reserved, 0 (--dump-graph is not built) */
+  uint64_t node_budget_global;  /* 0 = shk_pcr_node_budget(n_bases_ingested) */
+  uint64_t reserved[4];
+} shk_pcr_file_config;
+/* shk_run_files with main.rs:133-199: after the histograms, shk_pcr_run over pcr->genes, {sample}_{gene}.fasta for every
+ * gene with products in gene order (stats.rs:102-125), then the stats file with pcr_results.  A run that fails leaves no
+ * stats file.  pcr NULL or without genes: shk_run_files.  out (optional) is handed to shk_pcr_run as it is: the caller's
+ * arrays and capacities; NULL: the call keeps the products to itself.  n_devices > 1 with genes: SHK_ERR_STATE. */
+int shk_run_files_pcr(const shk_run_config *cfg, const shk_pcr_file_config *pcr, shk_run_stats *out_stats,
+                      shk_pcr_run_out *out);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,8 @@ from .engine import (  # noqa: F401
     FLAG_TIMING, FLAG_FORCE_DIRECT, FLAG_FORCE_PAGED, FLAG_DEFER_ERRORS, FLAG_TIMING_SAMPLED, KERNEL_NAMES, RESERVE_NONE,
     Primer, primer_compile, PRIMER_LEVELS, PcrGraph, PrunedGraph, pcr_node_budget,
     PcrProducts, DedupResult, pcr_paths_panel, edit_within, PCR_SCORE_FIELDS, PCR_MAX_AMPLICONS,
+    PcrGene, PcrOutcome, parse_pcr_primers, validate_pcr_gene, pcr_validation_report, pcr_failure_reason, write_fasta,
+    PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET,
     PackedReads, pack_reads, release_cached_memory, FastqReader, write_histo, write_final_histo, write_stats_yaml, validate_args, run_files,
 )
 from .synth import SynthSpec, synth_reads  # noqa: F401

@@ -3,7 +3,11 @@
 // Flags mirror the reference's clap definitions (src/cli.rs:165-232): -k (default 19), --chunks
 // (0), --histo-max (10000), -m/--max-reads, -s/--sample, -o/--outdir ("./"), -t/--threads
 // (accepted; counting was single-threaded in the reference and is on the GPU here),
-// --validate-every (0).  Exit status and "Error: …" on stderr follow anyhow's main().
+// --validate-every (0).  sPCR (cli.rs:12-140, 234-330; main.rs:33-56, 133-199): --pcr-primers SPEC (repeatable),
+// --min-kmer-count (2), --read-threading, --node-budget-global, and the six global tuning flags that overwrite every
+// gene's values as the reference does: --max-dfs-states, --max-paths-per-pair, --max-node-visits, --max-primer-kmers,
+// --high-coverage-ratio, --tip-coverage-fraction.  With a gene, {sample}_{gene}.fasta is written for every gene with
+// products and the stats file carries pcr_results.  Exit status and "Error: …" on stderr follow anyhow's main().
 #include "../../include/shk.h"
 
 #include <cstdio>
@@ -26,6 +30,11 @@ int main(int argc, char **argv) {
   const char *sample = nullptr, *outdir = "./";
   std::vector<int32_t> devices;  // --devices 0,1,2,3: one multi-device context (not a reference flag)
   std::vector<const char *> inputs;
+  std::vector<const char *> specs;  // --pcr-primers, in order
+  bool read_threading = false;
+  unsigned long long min_kmer_count = 2, node_budget = 0, max_dfs_states = 100000, max_paths_per_pair = 20, max_node_visits = 2,
+                     max_primer_kmers = 40;
+  double high_coverage_ratio = 10.0, tip_coverage_fraction = 0.1;
   std::string command;
   for (int i = 0; i < argc; ++i) {
     if (i) command += ' ';
@@ -55,7 +64,26 @@ int main(int argc, char **argv) {
         exit(2);
       }
     };
+    auto real = [&](double *dst) {
+      const char *v = val ? val : need(i, key.c_str());
+      char *end = nullptr;
+      *dst = strtod(v, &end);
+      if (!*v || !end || *end) {
+        fprintf(stderr, "error: invalid value '%s' for '%s'\n", v, key.c_str());
+        exit(2);
+      }
+    };
     if (key == "-k") num(&k);
+    else if (key == "--pcr-primers") specs.push_back(val ? argv[i] + eq + 1 : need(i, key.c_str()));
+    else if (key == "--min-kmer-count") num(&min_kmer_count);
+    else if (key == "--read-threading") read_threading = true;
+    else if (key == "--node-budget-global") num(&node_budget);
+    else if (key == "--max-dfs-states") num(&max_dfs_states);
+    else if (key == "--max-paths-per-pair") num(&max_paths_per_pair);
+    else if (key == "--max-node-visits") num(&max_node_visits);
+    else if (key == "--max-primer-kmers") num(&max_primer_kmers);
+    else if (key == "--high-coverage-ratio") real(&high_coverage_ratio);
+    else if (key == "--tip-coverage-fraction") real(&tip_coverage_fraction);
     else if (key == "--chunks") num(&chunks);
     else if (key == "--histo-max") num(&histo_max);
     else if (key == "-m" || key == "--max-reads") num(&max_reads);
@@ -80,7 +108,8 @@ int main(int argc, char **argv) {
     else if (key == "-o" || key == "--outdir") outdir = val ? argv[i] + eq + 1 : need(i, key.c_str());
     else if (key == "-h" || key == "--help") {
       printf("Usage: shk_count [-k K] [--chunks N] [--histo-max M] [-m READS] -s SAMPLE [-o OUTDIR] "
-             "[--validate-every N] [--gzip-all-members] [FASTQ[.gz] ...]\n");
+             "[--validate-every N] [--gzip-all-members] [--pcr-primers \"forward=...,reverse=...,name=...\"]... "
+             "[--min-kmer-count N] [--read-threading] [--node-budget-global N] [FASTQ[.gz] ...]\n");
       return 0;
     } else if (a.size() > 1 && a[0] == '-' && a != "-") {
       fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str());
@@ -89,6 +118,30 @@ int main(int argc, char **argv) {
       inputs.push_back(argv[i]);
     }
   }
+  // collect_pcr_params (cli.rs:521-554) and the global tuning flags (main.rs:49-56)
+  std::vector<shk_pcr_gene> genes(specs.size());
+  std::vector<std::vector<char>> strings(specs.size());
+  for (size_t g = 0; g < specs.size(); ++g) {
+    char err[1024];
+    strings[g].resize(strlen(specs[g]) + 3);
+    if (shk_pcr_parse_primers(specs[g], &genes[g], strings[g].data(), strings[g].size(), err, sizeof err) != SHK_OK) {
+      fprintf(stderr, "Error: Could not parse primer specification: \"%s\"\n\nCaused by:\n    %s\n", specs[g], err);
+      return 1;
+    }
+    genes[g].max_dfs_states = max_dfs_states, genes[g].max_paths_per_pair = max_paths_per_pair, genes[g].max_node_visits = max_node_visits;
+    genes[g].max_primer_kmers = (uint32_t)max_primer_kmers;
+    genes[g].high_coverage_ratio = high_coverage_ratio, genes[g].tip_coverage_fraction = tip_coverage_fraction;
+  }
+  if (min_kmer_count < 1) {  // cli.rs validate_args
+    fprintf(stderr, "Error: min-kmer-count must be at least 1\n");
+    return 1;
+  }
+  shk_pcr_file_config pcr{};
+  pcr.genes = genes.data();
+  pcr.n_genes = (uint32_t)genes.size();
+  pcr.min_kmer_count = (uint32_t)min_kmer_count;
+  pcr.read_threading = read_threading;
+  pcr.node_budget_global = node_budget;
   shk_run_config rc{};
   rc.inputs = inputs.data();
   rc.n_inputs = (uint32_t)inputs.size();
@@ -106,7 +159,7 @@ int main(int argc, char **argv) {
   rc.n_devices = (uint32_t)devices.size();
   rc.device_ids = devices.empty() ? nullptr : devices.data();
   shk_run_stats st{};
-  int rcode = shk_run_files(&rc, &st);
+  int rcode = genes.empty() ? shk_run_files(&rc, &st) : shk_run_files_pcr(&rc, &pcr, &st, nullptr);
   if (rcode != SHK_OK) {
     fprintf(stderr, "Error: %s\n", shk_run_error());
     return 1;

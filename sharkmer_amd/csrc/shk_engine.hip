@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -3611,3 +3612,5 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 // shk_pcr_dedup_panel, shk_pcr_products_panel: the dedup's pair matrix on the device, the products of a panel; the table
 // is left alone
 #include "shk_products_api.hip.h"
+// shk_pcr_run: do_pcr for a panel, the stage calls above chained with the reference's control flow; no kernel of its own
+#include "shk_pcr_run_api.hip.h"

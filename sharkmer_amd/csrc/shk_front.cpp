@@ -2273,8 +2273,12 @@ static std::string yaml_str(const std::string &s) {
   return q;
 }
 
-int shk_write_stats_yaml(const char *path, const shk_run_stats *st) {
-  if (!path || !st) return SHK_ERR_BAD_ARG;
+int shk_write_stats_yaml(const char *path, const shk_run_stats *st) { return shk_write_stats_yaml_pcr(path, st, nullptr, 0); }
+
+int shk_write_stats_yaml_pcr(const char *path, const shk_run_stats *st, const shk_pcr_gene_stat *results, uint32_t n) {
+  if (!path || !st || (n && !results)) return SHK_ERR_BAD_ARG;
+  for (uint32_t g = 0; g < n; ++g)
+    if (results[g].n_products && !results[g].product_lengths) return SHK_ERR_BAD_ARG;
   FILE *f = fopen(path, "w");
   if (!f) return SHK_ERR_IO;
   // RunStats field order, stats.rs:27-45; Option fields skipped when None, pcr_results when empty
@@ -2293,6 +2297,227 @@ int shk_write_stats_yaml(const char *path, const shk_run_stats *st) {
     fprintf(f, "n_singleton_kmers: %llu\n", (unsigned long long)st->n_singleton_kmers);
   }
   fprintf(f, "peak_memory_bytes: %llu\n", (unsigned long long)st->peak_memory_bytes);
+  // pcr_results (stats.rs:11-23, 43-44), skipped when empty: a block sequence of mappings, the dash at the parent key's
+  // indentation (serde_yaml_ng's emitter, read — no recorded output); output_file is None in every PcrGeneResult
+  // run_pcr builds (stats.rs:123, 141)
+  if (n) fprintf(f, "pcr_results:\n");
+  for (uint32_t g = 0; g < n; ++g) {
+    const shk_pcr_gene_stat &r = results[g];
+    const char *reason = shk_pcr_failure_reason(r.status);
+    fprintf(f, "- gene_name: %s\n", yaml_str(r.gene_name ? r.gene_name : "").c_str());
+    fprintf(f, "  status: %s\n", r.status == SHK_PCR_SUCCESS ? "success" : "fail");
+    fprintf(f, "  n_products: %u\n", r.n_products);
+    if (r.n_products) fprintf(f, "  product_lengths:\n");
+    for (uint32_t i = 0; i < r.n_products; ++i) fprintf(f, "  - %llu\n", (unsigned long long)r.product_lengths[i]);
+    if (r.status != SHK_PCR_SUCCESS)  // (stats.rs:133-135: never None on a fail)
+      fprintf(f, "  failure_reason: %s\n", yaml_str(reason ? reason : "unknown (no reason reported by PCR pipeline)").c_str());
+  }
+  return fclose(f) == 0 ? SHK_OK : SHK_ERR_IO;
+}
+
+// ---- sPCR's host side: the primer specification, its validation, the FASTA writer (cli.rs:12-140, 528-554;
+// pcr/mod.rs:295-399; io.rs:144-158) -----------------------------------------------------------------------------------
+
+void shk_pcr_gene_defaults(shk_pcr_gene *g) {
+  if (!g) return;
+  g->min_length = 0, g->max_length = 10000;
+  g->min_count = 2, g->mismatches = 2, g->trim = 15, g->dedup_edit_threshold = 10;
+  g->max_dfs_states = 100000, g->max_paths_per_pair = 20, g->max_node_visits = 2;
+  g->max_primer_kmers = 40, g->reserved = 0;
+  g->high_coverage_ratio = 10.0, g->tip_coverage_fraction = 0.1;
+}
+
+const char *shk_pcr_failure_reason(uint32_t status) {
+  switch (status) {
+    case SHK_PCR_NO_FORWARD: return "forward primer not found";
+    case SHK_PCR_NO_REVERSE: return "reverse primer not found";
+    case SHK_PCR_NO_PRIMERS: return "forward and reverse primers not found";
+    case SHK_PCR_NO_PATH: return "no path found";
+    case SHK_PCR_NODE_BUDGET: return "node budget exceeded";
+    default: return nullptr;
+  }
+}
+
+static void put_text(char *dst, size_t cap, const std::string &s) {
+  if (!dst || !cap) return;
+  const size_t n = std::min(cap - 1, s.size());
+  memcpy(dst, s.data(), n);
+  dst[n] = 0;
+}
+
+// str::parse::<uN>(): an optional '+', then decimal digits only, no overflow
+static bool parse_uint(const std::string &s, uint64_t max, uint64_t *out) {
+  size_t i = !s.empty() && s[0] == '+' ? 1 : 0;
+  if (i == s.size()) return false;
+  uint64_t v = 0;
+  for (; i < s.size(); ++i) {
+    if (s[i] < '0' || s[i] > '9') return false;
+    const uint64_t d = (uint64_t)(s[i] - '0');
+    if (v > (max - d) / 10) return false;
+    v = v * 10 + d;
+  }
+  *out = v;
+  return true;
+}
+
+int shk_pcr_parse_primers(const char *spec, shk_pcr_gene *out, char *strings, size_t strings_cap, char *err, size_t err_cap) {
+  put_text(err, err_cap, "");
+  if (!spec || !out || !strings) return SHK_ERR_BAD_ARG;
+  auto bail = [&](const std::string &why) {
+    put_text(err, err_cap, why);
+    return SHK_ERR_BAD_ARG;
+  };
+  const std::string s = spec;
+  if (s.empty()) return bail("Invalid empty primer specification");
+  std::string name, fwd, rev;
+  shk_pcr_gene g{};
+  shk_pcr_gene_defaults(&g);
+  std::vector<std::string> seen;
+  for (size_t at = 0;;) {  // split(','): an empty item between two commas is an item too
+    const size_t comma = s.find(',', at);
+    const std::string item = s.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+    const size_t eq = item.find('=');
+    if (eq == std::string::npos)
+      return bail("Invalid parameter (should be key=value): '" + item +
+                  "'\nCommas are not allowed in field values. Use --pcr-panel-file with a YAML panel for complex metadata.");
+    std::string key = item.substr(0, eq);
+    const std::string value = item.substr(eq + 1);
+    for (char &ch : key)
+      if (ch >= 'A' && ch <= 'Z') ch = (char)(ch - 'A' + 'a');
+    if (std::find(seen.begin(), seen.end(), key) != seen.end())
+      return bail("Duplicate parameter '" + key + "' in primer specification '" + s + "'. Each key may appear at most once.");
+    seen.push_back(key);
+    auto upper = [](std::string v) {
+      for (char &ch : v)
+        if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 'a' + 'A');
+      return v;
+    };
+    uint64_t v = 0;
+    auto number = [&](uint64_t max) { return parse_uint(value, max, &v); };
+    const std::string bad = "Invalid value for " + key + ": " + value;
+    if (key == "name") name = value;
+    else if (key == "forward") fwd = upper(value);
+    else if (key == "reverse") rev = upper(value);
+    else if (key == "max-length") { if (!number(~0ull)) return bail(bad); g.max_length = v; }
+    else if (key == "min-length") { if (!number(~0ull)) return bail(bad); g.min_length = v; }
+    else if (key == "min-count") { if (!number(0xFFFFFFFFull)) return bail(bad); g.min_count = (uint32_t)v; }
+    else if (key == "mismatches") { if (!number(0xFFFFFFFFull)) return bail(bad); g.mismatches = (uint32_t)v; }
+    else if (key == "trim") { if (!number(0xFFFFFFFFull)) return bail(bad); g.trim = (uint32_t)v; }
+    else if (key == "dedup-edit-threshold") { if (!number(0xFFFFFFFFull)) return bail(bad); g.dedup_edit_threshold = (uint32_t)v; }
+    else if (key == "citation" || key == "notes") {}  // accepted, not part of shk_pcr_gene
+    else return bail("Unexpected parameter: " + key);
+    if (comma == std::string::npos) break;
+    at = comma + 1;
+  }
+  const size_t need = name.size() + fwd.size() + rev.size() + 3;
+  if (need > strings_cap) return bail(fmt("the strings of the specification take %zu bytes, strings_cap is %zu", need, strings_cap));
+  char *p = strings;
+  auto store = [&](const std::string &v) {
+    char *at = p;
+    memcpy(p, v.c_str(), v.size() + 1);
+    p += v.size() + 1;
+    return (const char *)at;
+  };
+  g.gene_name = store(name), g.forward_seq = store(fwd), g.reverse_seq = store(rev);
+  *out = g;
+  return SHK_OK;
+}
+
+namespace {
+
+// the chars of s that is_valid_nucleotide (primers.rs:11-30) refuses, each as its UTF-8 bytes, joined by ", "
+std::string invalid_nucleotides(const std::string &s) {
+  std::string out;
+  for (size_t i = 0; i < s.size();) {
+    const unsigned char b = (unsigned char)s[i];
+    size_t len = b < 0x80 ? 1 : b >= 0xF0 ? 4 : b >= 0xE0 ? 3 : b >= 0xC0 ? 2 : 1;
+    len = std::min(len, s.size() - i);
+    if (!(len == 1 && b && strchr("ACGTRYSWKMBDHVN", (char)b))) {
+      if (!out.empty()) out += ", ";
+      out.append(s, i, len);
+    }
+    i += len;
+  }
+  return out;
+}
+
+std::vector<std::pair<std::string, std::string>> pcr_gene_errors(const shk_pcr_gene *g) {
+  std::vector<std::pair<std::string, std::string>> e;
+  const std::string f = g->forward_seq ? g->forward_seq : "", r = g->reverse_seq ? g->reverse_seq : "", name = g->gene_name ? g->gene_name : "";
+  if (f.size() < 2) e.emplace_back("Forward primer sequence is too short: '" + f + "'", "Primer sequences must be at least 2 bases");
+  if (r.size() < 2) e.emplace_back("Reverse primer sequence is too short: '" + r + "'", "Primer sequences must be at least 2 bases");
+  if (f.size() >= 2)
+    if (const std::string bad = invalid_nucleotides(f); !bad.empty())
+      e.emplace_back("Invalid nucleotide(s) " + bad + " in forward primer " + f, "Valid characters: A C G T R Y W S M K B D H V N");
+  if (r.size() >= 2)
+    if (const std::string bad = invalid_nucleotides(r); !bad.empty())
+      e.emplace_back("Invalid nucleotide(s) " + bad + " in reverse primer " + r, "Valid characters: A C G T R Y W S M K B D H V N");
+  if (g->min_length > g->max_length)
+    e.emplace_back(fmt("min-length (%llu) is greater than max-length (%llu)", (unsigned long long)g->min_length, (unsigned long long)g->max_length),
+                   "Swap the values or adjust the range");
+  if (g->min_count < 2) e.emplace_back(fmt("min-count is %u, must be at least 2", g->min_count), "Set min-count to at least 2");
+  if (g->max_length == 0) e.emplace_back("max-length is 0", "Set max-length to a positive value");
+  if (name.empty()) e.emplace_back("Gene name is empty", "Provide a unique name for the primer pair via the 'name' field");
+  if (f == r && f.size() >= 2)
+    e.emplace_back("Forward and reverse primers are identical: " + f, "Check that forward and reverse sequences are not swapped");
+  return e;
+}
+
+// Rust's `{}` of an f64 that is a median of integers: 12, 12.5; anything else by its shortest round-trip digits
+std::string f64_display(double x) {
+  if (x == (double)(long long)x && x > -1e15 && x < 1e15) return fmt("%lld", (long long)x);
+  for (int p = 1; p < 17; ++p) {
+    const std::string s = fmt("%.*g", p, x);
+    if (strtod(s.c_str(), nullptr) == x) return s;
+  }
+  return fmt("%.17g", x);
+}
+
+}  // namespace
+
+int shk_pcr_validate_gene(const shk_pcr_gene *g, char *buf, size_t buf_cap) {
+  put_text(buf, buf_cap, "");
+  if (!g) return SHK_ERR_BAD_ARG;
+  const auto errors = pcr_gene_errors(g);
+  std::string text;
+  for (const auto &e : errors) text += e.first + "\n" + e.second + "\n";
+  put_text(buf, buf_cap, text);
+  return (int)errors.size();
+}
+
+int shk_pcr_validation_report(const shk_pcr_gene *genes, uint32_t n, const char *const *sources, char *buf, size_t buf_cap) {
+  put_text(buf, buf_cap, "");
+  if (n && !genes) return SHK_ERR_BAD_ARG;
+  size_t total = 0;
+  std::string report;
+  for (uint32_t g = 0; g < n; ++g) {
+    const auto errors = pcr_gene_errors(genes + g);
+    if (errors.empty()) continue;
+    total += errors.size();
+    report += fmt("\n  %s (%s):\n", genes[g].gene_name ? genes[g].gene_name : "", sources && sources[g] ? sources[g] : "--pcr-primers");
+    for (const auto &e : errors) report += "    - " + e.first + "\n      Suggestion: " + e.second + "\n";
+  }
+  if (total) put_text(buf, buf_cap, fmt("Primer validation failed (%zu error%s):\n", total, total == 1 ? "" : "s") + report);
+  return (int)total;
+}
+
+int shk_write_fasta(const char *path, const char *sample, const shk_pcr_gene *gene, const shk_pcr_records *recs, uint64_t first, uint64_t n) {
+  if (!path || !sample || !gene || !gene->gene_name || !recs) return SHK_ERR_BAD_ARG;
+  if (n && (!recs->seq_offsets || !recs->seqs || !recs->count_mean || !recs->count_median || !recs->count_min || !recs->count_max || !recs->score))
+    return SHK_ERR_BAD_ARG;
+  FILE *f = fopen(path, "w");
+  if (!f) return SHK_ERR_IO;
+  const char *name = gene->gene_name;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t r = first + i, a = recs->seq_offsets[r], b = recs->seq_offsets[r + 1];
+    fprintf(f, ">%s_%s_%llu sample=%s gene=%s product=%llu length=%llu kmer_count_mean=%.2f kmer_count_median=%s kmer_count_min=%llu kmer_count_max=%llu score=%.2f\n",
+            sample, name, (unsigned long long)i, sample, name, (unsigned long long)i, (unsigned long long)(b - a), recs->count_mean[r],
+            f64_display(recs->count_median[r]).c_str(), (unsigned long long)recs->count_min[r], (unsigned long long)recs->count_max[r], recs->score[r]);
+    for (uint64_t at = a; at < b; at += 80) {  // seq.chunks(FASTA_LINE_WIDTH): an empty sequence has no line
+      fwrite(recs->seqs + at, 1, (size_t)std::min<uint64_t>(80, b - at), f);
+      fputc('\n', f);
+    }
+  }
   return fclose(f) == 0 ? SHK_OK : SHK_ERR_IO;
 }
 

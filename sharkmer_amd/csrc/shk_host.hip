@@ -1,5 +1,5 @@
-// shk_host.hip — shk_run_files: ingest_reads + consolidate_and_histogram + write_stats for local files
-// (src/main.rs:74-78, 112-197 without sPCR), feeding libshk's device path in super-batches through pinned buffers.
+// shk_host.hip — shk_run_files[_pcr]: ingest_reads + consolidate_and_histogram (+ run_pcr) + write_stats for local files
+// (src/main.rs:74-78, 112-199), feeding libshk's device path in super-batches through pinned buffers.
 // The FASTQ front-end, the writers and the packer it drives are plain C++ (shk_front.cpp, shk_inflate.cpp — also
 // built under sanitizers, `make san`); only what touches HIP (pinned buffers, device memory in use) lives here.
 #include "../../include/shk.h"
@@ -20,10 +20,12 @@
 using shk::fmt;
 #define g_run_error (shk::run_error())
 
-extern "C" {
+namespace {
 
-int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
+// shk_run_files (pcr == nullptr or without genes: not a byte of its output differs) and shk_run_files_pcr
+int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk_run_stats *out_stats, shk_pcr_run_out *pcr_out) {
   if (!rc) return SHK_ERR_BAD_ARG;
+  const uint32_t n_genes = pcr ? pcr->n_genes : 0;
   const bool trace = getenv("SHK_TRACE") != nullptr;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
@@ -38,6 +40,24 @@ int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
   g_run_error.clear();
   int v = shk_validate_args(rc->k, rc->histo_max, rc->sample);
   if (v != SHK_OK) return v;
+  if (n_genes) {  // collect_pcr_params (cli.rs:528-581), before a read is read
+    if (!pcr->genes) return SHK_ERR_BAD_ARG;
+    std::vector<char> report(4096 + 2048 * (size_t)n_genes);
+    if (shk_pcr_validation_report(pcr->genes, n_genes, nullptr, report.data(), report.size()) != 0) {
+      g_run_error = report.data();
+      return SHK_ERR_BAD_ARG;
+    }
+    for (uint32_t g = 0; g < n_genes; ++g)
+      for (uint32_t h = 0; h < g; ++h)
+        if (!strcmp(pcr->genes[g].gene_name, pcr->genes[h].gene_name)) {
+          g_run_error = fmt("Duplicate gene name '%s' (from --pcr-primers)", pcr->genes[g].gene_name);
+          return SHK_ERR_BAD_ARG;
+        }
+    if (rc->n_devices > 1) {
+      g_run_error = "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)";
+      return SHK_ERR_STATE;
+    }
+  }
   std::string dir = rc->outdir ? rc->outdir : "./";  // main.rs:74-78
   if (dir.empty() || dir.back() != '/') dir += '/';
   {  // create_dir_all (main.rs:80-84)
@@ -74,6 +94,15 @@ int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
   v = shk_create(&cfg, &ctx);
   if (v != SHK_OK) {
     g_run_error = shk_last_error(nullptr);
+    shk_fastq_close(rd);
+    return v;
+  }
+  // --read-threading: the reads stay in HBM as they are ingested, where the reference reads its files a second time
+  // (main.rs:133-144); stdin cannot be read twice there, so it is not threaded here either (main.rs:136-139)
+  const bool threading = n_genes && pcr->read_threading && rc->n_inputs > 0;
+  if (threading && (v = shk_retain_reads(ctx, 1, 0)) != SHK_OK) {
+    g_run_error = shk_last_error(ctx);
+    shk_destroy(ctx);
     shk_fastq_close(rd);
     return v;
   }
@@ -244,6 +273,61 @@ int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
       return v;
     }
   }
+  // run_pcr (stats.rs:49-145): the panel, then one FASTA file per gene with products, in gene order
+  std::vector<shk_pcr_gene_stat> gene_stats(n_genes);
+  std::vector<uint64_t> product_lengths;
+  if (n_genes) {
+    shk_pcr_run_params pp{};
+    pp.min_kmer_count = pcr->min_kmer_count;
+    pp.reads = threading ? SHK_PCR_READS_RETAINED : SHK_PCR_READS_NONE;
+    pp.max_num_nodes = pcr->node_budget_global;
+    // the call's own record arrays where the caller brought none: at most SHK_PCR_MAX_AMPLICONS records per gene
+    std::vector<uint32_t> status(n_genes);
+    std::vector<uint64_t> roff(n_genes + 1), soff, cmin, cmax;
+    std::vector<uint8_t> seqs;
+    std::vector<double> mean, median, score;
+    shk_pcr_run_out own{};
+    shk_pcr_run_out *po = pcr_out ? pcr_out : &own;
+    uint64_t seq_cap = 1ull << 20;
+    for (int attempt = 0;; ++attempt) {
+      if (!pcr_out) {
+        const uint64_t cap = (uint64_t)SHK_PCR_MAX_AMPLICONS * n_genes;
+        soff.assign(cap + 1, 0), cmin.assign(cap, 0), cmax.assign(cap, 0), mean.assign(cap, 0), median.assign(cap, 0), score.assign(cap, 0);
+        seqs.assign(seq_cap, 0);
+        own.status = status.data();
+        own.records.record_offsets = roff.data(), own.records.seq_offsets = soff.data(), own.records.seqs = seqs.data();
+        own.records.record_cap = cap, own.records.seq_cap = seq_cap;
+        own.records.count_mean = mean.data(), own.records.count_median = median.data(), own.records.count_min = cmin.data();
+        own.records.count_max = cmax.data(), own.records.score = score.data();
+      }
+      v = shk_pcr_run(ctx, pcr->genes, n_genes, &pp, po);
+      if (v == SHK_ERR_BAD_ARG && !pcr_out && attempt == 0 && own.records.n_seq_bytes > seq_cap) {  // products beyond a megabase: once more
+        seq_cap = own.records.n_seq_bytes;
+        continue;
+      }
+      break;
+    }
+    if (v != SHK_OK) {
+      g_run_error = shk_last_error(ctx);
+      cleanup();
+      return v;
+    }
+    mark("sPCR");
+    const shk_pcr_records &R = po->records;
+    product_lengths.resize(R.record_offsets[n_genes]);
+    for (uint32_t g = 0; g < n_genes; ++g) {
+      const uint64_t a = R.record_offsets[g], b = R.record_offsets[g + 1];
+      for (uint64_t r = a; r < b; ++r) product_lengths[r] = R.seq_offsets[r + 1] - R.seq_offsets[r];
+      gene_stats[g] = shk_pcr_gene_stat{pcr->genes[g].gene_name, po->status[g], (uint32_t)(b - a), product_lengths.data() + a};
+      if (b == a) continue;
+      const std::string path = dir + sample + "_" + pcr->genes[g].gene_name + ".fasta";  // stats.rs:106
+      if ((v = shk_write_fasta(path.c_str(), sample.c_str(), &pcr->genes[g], &R, a, b - a)) != SHK_OK) {
+        g_run_error = fmt("Failed to create FASTA file: %s", path.c_str());
+        cleanup();
+        return v;
+      }
+    }
+  }
   shk_run_stats st{};
   st.sharkmer_version = version;
   st.command = rc->command ? rc->command : "";
@@ -260,7 +344,7 @@ int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
   st.n_multi_kmers = cn.n_kmers_ingested >= cn.n_singleton_kmers ? cn.n_kmers_ingested - cn.n_singleton_kmers : 0;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) st.peak_memory_bytes = total_b - free_b;  // device bytes in use
-  v = shk_write_stats_yaml((dir + sample + ".stats.yaml").c_str(), &st);
+  v = shk_write_stats_yaml_pcr((dir + sample + ".stats.yaml").c_str(), &st, gene_stats.data(), n_genes);
   if (out_stats) *out_stats = st;
   if (out_stats) {  // strings owned by the caller's config, not by us
     out_stats->sharkmer_version = nullptr;
@@ -272,6 +356,16 @@ int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) {
   mark("cleanup");
   if (v != SHK_OK) g_run_error = "Failed to create stats file";
   return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shk_run_files(const shk_run_config *rc, shk_run_stats *out_stats) { return run_files_impl(rc, nullptr, out_stats, nullptr); }
+
+int shk_run_files_pcr(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk_run_stats *out_stats, shk_pcr_run_out *out) {
+  return run_files_impl(rc, pcr, out_stats, out);
 }
 
 }  // extern "C"

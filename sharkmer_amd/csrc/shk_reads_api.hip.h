@@ -291,14 +291,17 @@ void thread_out_zero(shk_thread_out *out, uint64_t n_edges, uint64_t n_seqs) {
 // What follows a launch, per gene.
 // paired_links.len() (threading.rs:166-189): pairs of which an R1 and an R2 read each mapped to some edge.  Position i
 // of the n walked is read reads[i] of the batch (reads == NULL: read i) and mapped to re[i] edges.
+// mate == NULL: the rule of interleaved pairs (reread_sequences, io.rs:831-898) — read r is R1 when r is even, R2 when
+// odd, its index r — so that nothing the size of the batch has to exist (shk_pcr_run over retained reads).
 uint64_t thread_paired_links(const uint64_t *reads, uint64_t n, const uint64_t *read_index, const uint8_t *mate, const uint32_t *re) {
   std::unordered_map<uint64_t, uint8_t> seen;
   uint64_t n_pairs = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const uint64_t r = reads ? reads[i] : i;
-    if (mate[r] && re[i]) {
-      uint8_t &s = seen[read_index[r] / 2];
-      if (s != 3 && (s |= mate[r]) == 3) ++n_pairs;
+    const uint8_t m = mate ? mate[r] : (uint8_t)(1 + (r & 1));
+    if (m && re[i]) {
+      uint8_t &s = seen[(mate ? read_index[r] : r) / 2];
+      if (s != 3 && (s |= m) == 3) ++n_pairs;
     }
   }
   return n_pairs;
@@ -408,7 +411,8 @@ int thread_links_out(shk_ctx *c, const ThreadPanelResult &res, uint64_t link_cap
 // The launch over an opened batch (its offsets checked) and what follows it.  list_reads == nullptr: list position i (from
 // pp.l0) is read i — the one gene of shk_thread_reads, which lists every read.
 int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
-                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, ThreadPanelResult *res) {
+                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, ThreadPanelResult *res,
+                      bool mate_rule = false /* no arrays: pairs by thread_paired_links' rule (needs list_reads) */) {
   const uint32_t k = c->cfg.k;
   res->link_off.assign(n_genes + 1, 0);
   res->n_paired.assign(n_genes, 0);
@@ -500,7 +504,7 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   HIPC(c, hipGetLastError());
   std::vector<uint32_t> slots(pp.n_slots), re_own;
   uint32_t *re = res->read_edges;
-  if (!re && mate) {
+  if (!re && (mate || mate_rule)) {
     re_own.resize(pp.n_listed);
     re = re_own.data();
   }
@@ -511,7 +515,9 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the upload and the jobs alive until their copies ran)
   for (uint32_t g = 0; g < n_genes; ++g) {
     const uint64_t l_at = list_offsets[g] - pp.l0, n_list = list_offsets[g + 1] - list_offsets[g];
-    if (mate)
+    if (mate_rule && !mate)
+      res->n_paired[g] = thread_paired_links(list_reads + list_offsets[g], n_list, nullptr, nullptr, re + l_at);
+    else if (mate)
       res->n_paired[g] = list_reads ? thread_paired_links(list_reads + list_offsets[g], n_list, read_index, mate, re + l_at)
                                     : thread_paired_links(nullptr, n_list, read_index + l_at, mate + l_at, re + l_at);
     res->link_off[g + 1] = res->link_off[g] + thread_links_count(slots.data() + desc[g].link_base, pp.genes[g].n_slots);

@@ -419,6 +419,167 @@ def pcr_node_budget(n_bases_ingested: int) -> int:
     return int(load_library().shk_pcr_node_budget(n_bases_ingested))
 
 
+class _PcrGene(C.Structure):
+    _fields_ = [("gene_name", C.c_char_p), ("forward_seq", C.c_char_p), ("reverse_seq", C.c_char_p), ("min_length", C.c_uint64),
+                ("max_length", C.c_uint64), ("min_count", C.c_uint32), ("mismatches", C.c_uint32), ("trim", C.c_uint32),
+                ("dedup_edit_threshold", C.c_uint32), ("max_dfs_states", C.c_uint64), ("max_paths_per_pair", C.c_uint64),
+                ("max_node_visits", C.c_uint64), ("max_primer_kmers", C.c_uint32), ("reserved", C.c_uint32),
+                ("high_coverage_ratio", C.c_double), ("tip_coverage_fraction", C.c_double)]
+
+
+class _PcrRunParams(C.Structure):
+    _fields_ = [("min_kmer_count", C.c_uint32), ("reads", C.c_uint32), ("paired", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_num_nodes", C.c_uint64), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("n_seqs", C.c_uint64),
+                ("read_index", C.c_void_p), ("mate", C.c_void_p), ("reserved2", C.c_uint64 * 4)]
+
+
+_PCR_RUN_U32 = ("status", "n_fwd_kmers", "n_rev_kmers", "max_fwd_count", "max_rev_count", "median_primer_count", "threshold_used",
+                "steps_run", "found_path")
+_PCR_RUN_U64A = ("n_nodes", "n_edges", "n_pruned_nodes", "n_pruned_edges", "n_reads_matched")
+
+
+class _PcrRunOut(C.Structure):
+    _fields_ = ([("records", _PcrRecords)] + [(f, C.c_void_p) for f in _PCR_RUN_U32 + _PCR_RUN_U64A]
+                + [("threaded", C.c_void_p), ("n_paired_links", C.c_void_p), ("low_primer_counts", C.c_void_p), ("reserved", C.c_uint64 * 4)])
+
+
+class _PcrGeneStat(C.Structure):
+    _fields_ = [("gene_name", C.c_char_p), ("status", C.c_uint32), ("n_products", C.c_uint32), ("product_lengths", C.c_void_p)]
+
+
+class _PcrFileConfig(C.Structure):
+    _fields_ = [("genes", C.POINTER(_PcrGene)), ("n_genes", C.c_uint32), ("min_kmer_count", C.c_uint32), ("read_threading", C.c_uint32),
+                ("dump", C.c_uint32), ("node_budget_global", C.c_uint64), ("reserved", C.c_uint64 * 4)]
+
+
+PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET = range(6)  # SHK_PCR_* (include/shk.h)
+PCR_READS_NONE, PCR_READS_RETAINED, PCR_READS_HOST = range(3)
+
+
+@dataclass
+class PcrGene:
+    """PCRParams as do_pcr reads it (src/pcr/mod.rs), with the reference's defaults: shk_pcr_gene."""
+    gene_name: str = ""
+    forward_seq: str = ""
+    reverse_seq: str = ""
+    min_length: int = 0
+    max_length: int = 10000
+    min_count: int = 2
+    mismatches: int = 2
+    trim: int = 15
+    dedup_edit_threshold: int = 10
+    max_dfs_states: int = 100000
+    max_paths_per_pair: int = 20
+    max_node_visits: int = 2
+    max_primer_kmers: int = 40
+    high_coverage_ratio: float = 10.0
+    tip_coverage_fraction: float = 0.1
+
+    def _c(self) -> _PcrGene:
+        return _PcrGene(self.gene_name.encode(), self.forward_seq.encode(), self.reverse_seq.encode(), self.min_length, self.max_length,
+                        self.min_count, self.mismatches, self.trim, self.dedup_edit_threshold, self.max_dfs_states,
+                        self.max_paths_per_pair, self.max_node_visits, self.max_primer_kmers, 0, self.high_coverage_ratio,
+                        self.tip_coverage_fraction)
+
+
+def _pcr_genes(genes):
+    arr = (_PcrGene * max(len(genes), 1))()
+    for i, g in enumerate(genes):
+        arr[i] = g._c()
+    return arr
+
+
+def parse_pcr_primers(spec: str) -> PcrGene:
+    """parse_pcr_primers_string (cli.rs:12-140): "forward=…,reverse=…,name=…[,max-length=…]" → PcrGene; ShkError with
+    the reference's text otherwise (shk_pcr_parse_primers)."""
+    L = load_front_library()
+    raw = spec.encode()
+    g = _PcrGene()
+    strings, err = C.create_string_buffer(len(raw) + 3), C.create_string_buffer(2048 + 2 * len(raw))
+    rc = L.shk_pcr_parse_primers(raw, C.byref(g), strings, len(strings), err, len(err))
+    if rc != 0:
+        raise ShkError(rc, err.value.decode("utf-8", "replace"))
+    return PcrGene(g.gene_name.decode(), g.forward_seq.decode(), g.reverse_seq.decode(), int(g.min_length), int(g.max_length),
+                   int(g.min_count), int(g.mismatches), int(g.trim), int(g.dedup_edit_threshold), int(g.max_dfs_states),
+                   int(g.max_paths_per_pair), int(g.max_node_visits), int(g.max_primer_kmers), float(g.high_coverage_ratio),
+                   float(g.tip_coverage_fraction))
+
+
+def validate_pcr_gene(gene: PcrGene) -> list:
+    """validate_pcr_params (pcr/mod.rs:295-399): the (error, suggestion) pairs, [] for a valid gene."""
+    buf = C.create_string_buffer(8192 + 4 * (len(gene.forward_seq.encode()) + len(gene.reverse_seq.encode())))
+    c = gene._c()
+    n = load_front_library().shk_pcr_validate_gene(C.byref(c), buf, len(buf))
+    lines = buf.value.decode("utf-8", "replace").split("\n")
+    return [(lines[2 * i], lines[2 * i + 1]) for i in range(n)]
+
+
+def pcr_validation_report(genes, sources=None) -> str:
+    """The bail! text of collect_pcr_params (cli.rs:528-554) over the genes; "" when all are valid."""
+    arr = _pcr_genes(genes)
+    src = None
+    if sources is not None:
+        src = (C.c_char_p * max(len(genes), 1))(*[None if s is None else s.encode() for s in sources])
+    buf = C.create_string_buffer(4096 + 4096 * len(genes))
+    load_front_library().shk_pcr_validation_report(arr, len(genes), src, buf, len(buf))
+    return buf.value.decode("utf-8", "replace")
+
+
+def pcr_failure_reason(status: int):
+    r = load_front_library().shk_pcr_failure_reason(status)
+    return None if r is None else r.decode()
+
+
+@dataclass
+class PcrOutcome:
+    """do_pcr's PcrOutcome for one gene (pcr/mod.rs:286-291) with the diagnostics shk_pcr_run keeps."""
+    gene_name: str
+    status: int                 # PCR_SUCCESS .. PCR_NODE_BUDGET
+    failure_reason: str | None  # the reference's text; None on success
+    products: PcrProducts       # the final products in product order (empty on a fail)
+    n_fwd_kmers: int
+    n_rev_kmers: int
+    max_fwd_count: int
+    max_rev_count: int
+    median_primer_count: int
+    threshold_used: int
+    steps_run: int
+    found_path: bool
+    n_nodes: int
+    n_edges: int
+    n_pruned_nodes: int
+    n_pruned_edges: int
+    n_reads_matched: int
+    threaded: bool
+    n_paired_links: int
+    low_primer_counts: bool
+
+
+def _records_struct(recs: PcrProducts):
+    """One gene's PcrProducts as a shk_pcr_records (and the arrays it points into)."""
+    n = len(recs.sequences)
+    seqs = np.frombuffer("".join(recs.sequences).encode("ascii"), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
+    soff = np.zeros(n + 1, dtype=np.uint64)
+    soff[1:] = np.cumsum([len(s) for s in recs.sequences])
+    roff = np.array([0, n], dtype=np.uint64)
+    cols = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((recs.count_mean, np.float64), (recs.count_median, np.float64),
+                                                            (recs.count_min, np.uint64), (recs.count_max, np.uint64),
+                                                            (recs.score, np.float64))]
+    R = _PcrRecords(roff.ctypes.data, soff.ctypes.data, seqs.ctypes.data, n, len(seqs), n, int(soff[n]), None, None, cols[0].ctypes.data,
+                    cols[1].ctypes.data, cols[2].ctypes.data, cols[3].ctypes.data, cols[4].ctypes.data, None, None, None, None)
+    return R, [seqs, soff, roff] + cols
+
+
+def write_fasta(path: str, sample: str, gene_name: str, products: PcrProducts):
+    """write_fasta_record (io.rs:144-158) for a gene's products: the headers of PcrProducts.fasta, sequences wrapped at
+    80 columns (shk_write_fasta)."""
+    R, keep = _records_struct(products)
+    g = PcrGene(gene_name=gene_name)._c()
+    rc = load_front_library().shk_write_fasta(os.fsencode(path), sample.encode(), C.byref(g), C.byref(R), 0, len(products.sequences))
+    if rc != 0:
+        raise ShkError(rc, "shk_write_fasta failed")
+
+
 class _Synth(C.Structure):
     _fields_ = [("seed_genome", C.c_uint64), ("seed_reads", C.c_uint64), ("genome_len", C.c_uint64),
                 ("read_len", C.c_uint32), ("sub_per_64k", C.c_uint32), ("n_per_64k", C.c_uint32),
@@ -448,6 +609,8 @@ ABI_SYMBOLS = [
     "shk_filter_reads_panel", "shk_filter_reads_panel_device", "shk_gather_reads_device",
     "shk_retain_reads", "shk_retained_info", "shk_retained_export", "shk_filter_reads_panel_retained",
     "shk_thread_reads_panel_retained",
+    "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
+    "shk_pcr_run", "shk_write_fasta", "shk_write_stats_yaml_pcr", "shk_run_files_pcr",
 ]
 
 _lib = None
@@ -481,6 +644,8 @@ FRONT_SYMBOLS = [
     "shk_fastq_open", "shk_fastq_open_ex", "shk_fastq_close", "shk_fastq_error", "shk_fastq_next_batch", "shk_fastq_next_batch_packed", "shk_fastq_stats",
     "shk_write_histo", "shk_write_final_histo", "shk_write_stats_yaml", "shk_validate_args", "shk_run_error",
     "shk_packed_sizes", "shk_pack_reads",
+    "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
+    "shk_write_fasta", "shk_write_stats_yaml_pcr",
 ]
 
 
@@ -505,6 +670,15 @@ def _type_front(L):
     L.shk_validate_args.argtypes = [u32, u64, C.c_char_p]
     L.shk_run_error.argtypes = []
     L.shk_run_error.restype = C.c_char_p
+    L.shk_pcr_gene_defaults.argtypes = [C.POINTER(_PcrGene)]
+    L.shk_pcr_gene_defaults.restype = None
+    L.shk_pcr_parse_primers.argtypes = [C.c_char_p, C.POINTER(_PcrGene), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+    L.shk_pcr_validate_gene.argtypes = [C.POINTER(_PcrGene), C.c_char_p, C.c_size_t]
+    L.shk_pcr_validation_report.argtypes = [C.POINTER(_PcrGene), u32, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t]
+    L.shk_pcr_failure_reason.argtypes = [u32]
+    L.shk_pcr_failure_reason.restype = C.c_char_p
+    L.shk_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(_PcrGene), C.POINTER(_PcrRecords), u64, u64]
+    L.shk_write_stats_yaml_pcr.argtypes = [C.c_char_p, C.POINTER(_RunStats), C.POINTER(_PcrGeneStat), u32]
 
 
 _front = None
@@ -640,6 +814,8 @@ def load_library():
     L.shk_synth_reads_device.argtypes = [vp, C.POINTER(_Synth), u64, u64, vp, vp]
     _type_front(L)
     L.shk_run_files.argtypes = [C.POINTER(_RunConfig), C.POINTER(_RunStats)]
+    L.shk_run_files_pcr.argtypes = [C.POINTER(_RunConfig), C.POINTER(_PcrFileConfig), C.POINTER(_RunStats), C.POINTER(_PcrRunOut)]
+    L.shk_pcr_run.argtypes = [vp, C.POINTER(_PcrGene), u32, C.POINTER(_PcrRunParams), C.POINTER(_PcrRunOut)]
     for name in ABI_SYMBOLS:
         getattr(L, name)  # AttributeError here = the .so is stale
     _lib = L
@@ -1399,6 +1575,66 @@ class KmerEngine:
         n = self.retained_info()["reads"]
         return self._thread_panel(self._L.shk_thread_reads_panel_retained, (), n, graphs, lists, read_index, mate)
 
+    def pcr_run(self, genes, reads=None, paired: bool = False, min_kmer_count: int = 2, max_num_nodes: int = 0,
+                record_cap: int | None = None, seq_cap: int | None = None) -> list:
+        """do_pcr for every gene of a panel in one call (shk_pcr_run; pcr/mod.rs:431-819 under stats.rs:84-98) → one
+        PcrOutcome per gene.  genes: PcrGene or specification strings.  reads: None (k-mer-only scoring), "retained"
+        (every read retained so far) or (bases, offsets[, read_index, mate]), a host batch as ingest_reads takes it.
+        paired: without read_index / mate the reads alternate R1, R2.  max_num_nodes 0: compute_node_budget of the bases
+        ingested.  record_cap / seq_cap: fixed capacities (no second call when they are too small)."""
+        genes = [g if isinstance(g, PcrGene) else parse_pcr_primers(g) for g in genes]
+        ng = len(genes)
+        arr = _pcr_genes(genes)
+        prm = _PcrRunParams(min_kmer_count, PCR_READS_NONE, 1 if paired else 0, 0, max_num_nodes, None, None, 0, None, None)
+        keep = []
+        if isinstance(reads, str):
+            if reads != "retained":
+                raise ValueError('reads: None, "retained" or (bases, offsets[, read_index, mate])')
+            prm.reads = PCR_READS_RETAINED
+        elif reads is not None:
+            bases = np.ascontiguousarray(reads[0], dtype=np.uint8)
+            offsets = np.ascontiguousarray(reads[1], dtype=np.uint64)
+            keep += [bases, offsets]
+            prm.reads, prm.bases, prm.offsets, prm.n_seqs = PCR_READS_HOST, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1
+            if len(reads) > 2 and (reads[2] is not None or reads[3] is not None):
+                ri = None if reads[2] is None else np.ascontiguousarray(reads[2], dtype=np.uint64)
+                mt = None if reads[3] is None else np.ascontiguousarray(reads[3], dtype=np.uint8)
+                if any(x is not None and len(x) != prm.n_seqs for x in (ri, mt)):
+                    raise ValueError("read_index and mate take one entry per read")
+                keep += [ri, mt]
+                prm.read_index = None if ri is None else ri.ctypes.data
+                prm.mate = None if mt is None else mt.ctypes.data
+        n1 = max(ng, 1)
+        cols = {f: np.zeros(n1, dtype=np.uint32) for f in _PCR_RUN_U32}
+        cols.update({f: np.zeros(n1, dtype=np.uint64) for f in _PCR_RUN_U64A + ("n_paired_links",)})
+        cols.update({f: np.zeros(n1, dtype=np.uint8) for f in ("threaded", "low_primer_counts")})
+        O = _PcrRunOut()
+        for f, a in cols.items():
+            setattr(O, f, a.ctypes.data)
+
+        def call(R):
+            R.record_cap = R.record_cap if record_cap is None else record_cap
+            R.seq_cap = R.seq_cap if seq_cap is None else seq_cap
+            O.records = R
+            rc = self._L.shk_pcr_run(self._h, arr, ng, C.byref(prm), C.byref(O))
+            R.n_records, R.n_seq_bytes = O.records.n_records, O.records.n_seq_bytes
+            if rc != 0 and (record_cap is not None or seq_cap is not None):  # (no second call with room)
+                try:
+                    self._check(rc)
+                except ShkError as e:  # what the call left: the needs and the per-gene arrays, which are complete
+                    e.needs = (int(R.n_records), int(R.n_seq_bytes))
+                    e.per_gene = {f: a[:ng].copy() for f, a in cols.items()}
+                    raise
+            return rc, self._check
+
+        prods = _pcr_records_call(ng, call)
+        out = []
+        for g in range(ng):
+            v = {f: int(a[g]) for f, a in cols.items()}
+            v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
+            out.append(PcrOutcome(gene_name=genes[g].gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
+        return out
+
     def gather_reads(self, bases_t, offsets_t, read_ids):
         """The reads read_ids (any order, repeats allowed) of a batch that lies on this context's device, as a batch of
         their own on the same device (shk_gather_reads_device) → (bases uint8 tensor, offsets int64 tensor): what takes a
@@ -1850,7 +2086,16 @@ def write_stats_yaml(path: str, **f):
                    n_multi_kmers=f.get("n_multi_kmers", 0), n_singleton_kmers=f.get("n_singleton_kmers", 0),
                    peak_memory_bytes=f.get("peak_memory_bytes", 0),
                    has_histogram=1 if f.get("has_histogram", f["chunks"] > 0) else 0)
-    rc = load_front_library().shk_write_stats_yaml(os.fsencode(path), C.byref(st))
+    results = f.get("pcr_results")  # [(gene_name, status, product_lengths)]: stats.rs:11-23, 43-44
+    if results is None:
+        rc = load_front_library().shk_write_stats_yaml(os.fsencode(path), C.byref(st))
+    else:
+        arr, keep = (_PcrGeneStat * max(len(results), 1))(), []
+        for i, (name, status, lengths) in enumerate(results):
+            ln = np.asarray(list(lengths), dtype=np.uint64)
+            keep.append(ln)
+            arr[i] = _PcrGeneStat(name.encode(), int(status), len(ln), ln.ctypes.data if len(ln) else None)
+        rc = load_front_library().shk_write_stats_yaml_pcr(os.fsencode(path), C.byref(st), arr, len(results))
     if rc != 0:
         raise ShkError(rc, "shk_write_stats_yaml failed")
 
@@ -1865,9 +2110,16 @@ def validate_args(k: int, histo_max: int, sample):
 
 def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", histo_max: int = 10000,
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
-              command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False) -> dict:
-    """main.rs:112-197 without sPCR: FASTQ files → counts → .histo/.final.histo/.stats.yaml.
+              command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
+              pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
+    """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
+    strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
+    tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
+    max_primer_kmers, high_coverage_ratio, tip_coverage_fraction), which overwrite every gene's values.
     device_ids: run on one multi-device context (shk_run_config.n_devices).  gzip_all_members: see FastqReader."""
+    known = ("max_dfs_states", "max_paths_per_pair", "max_node_visits", "max_primer_kmers", "high_coverage_ratio", "tip_coverage_fraction")
+    if set(tuning) - set(known):
+        raise TypeError(f"unexpected arguments {sorted(set(tuning) - set(known))}")
     L = load_library()
     arr = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     cfg = _RunConfig(inputs=arr, n_inputs=len(inputs), k=k, chunks=chunks, device=device,
@@ -1880,7 +2132,23 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
         cfg.n_devices = len(device_ids)
         cfg.device_ids = C.cast(ids, C.POINTER(C.c_int32))
     st = _RunStats()
-    rc = L.shk_run_files(C.byref(cfg), C.byref(st))
+    if pcr_primers:
+        genes = []
+        for spec in pcr_primers:
+            try:
+                g = spec if isinstance(spec, PcrGene) else parse_pcr_primers(spec)
+            except ShkError as e:
+                raise ShkError(e.code, f'Could not parse primer specification: "{spec}"\n\nCaused by:\n    {e.msg}') from None
+            for name, value in tuning.items():
+                setattr(g, name, value)
+            genes.append(g)
+        if min_kmer_count < 1:
+            raise ShkError(-2, "min-kmer-count must be at least 1")
+        arr = _pcr_genes(genes)
+        pcfg = _PcrFileConfig(arr, len(genes), min_kmer_count, 1 if read_threading else 0, 0, node_budget_global)
+        rc = L.shk_run_files_pcr(C.byref(cfg), C.byref(pcfg), C.byref(st), None)
+    else:
+        rc = L.shk_run_files(C.byref(cfg), C.byref(st))
     if rc != 0:
         raise ShkError(rc, (L.shk_run_error() or b"").decode("utf-8", "replace"))
     return {f: int(getattr(st, f)) for f, t in _RunStats._fields_ if t in (C.c_uint32, C.c_uint64)}
