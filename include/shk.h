@@ -1092,6 +1092,29 @@ int shk_fastq_open(const char *const *paths, uint32_t n_paths, uint64_t max_read
 #define SHK_FASTQ_GZIP_ALL_MEMBERS 1u
 int shk_fastq_open_ex(const char *const *paths, uint32_t n_paths, uint64_t max_reads,
                       uint64_t validate_every, uint32_t flags, shk_fastq **out);
+/* BGZF (bgzip) input decoded in batches: NOT defaults, and both imply SHK_FASTQ_GZIP_ALL_MEMBERS' semantics.  A bgzip'd
+ * file is thousands of gzip members of at most 64 KiB whose headers carry their compressed size (the BC subfield) and
+ * whose trailers carry their decoded size, so the members are independent jobs with known extents before a bit is
+ * decoded.  Consecutive members with that framing (FLG exactly FEXTRA, a BC subfield, body and text ≤ 65536 bytes) are
+ * decoded side by side — SHK_FASTQ_BGZF_BATCH: on the reader's host threads; SHK_FASTQ_BGZF_DEVICE: on a HIP device,
+ * one wave per member (the text comes back to the host parser).  Every member's CRC-32 and ISIZE are checked before a
+ * byte of it is parsed.  At the first member that is not framed so, or whose decode, CRC-32 or ISIZE fails, the
+ * one-after-the-other decoder of SHK_FASTQ_GZIP_ALL_MEMBERS takes over from that member's header on: reads, order,
+ * errors and their texts are that flag's, whatever the file holds.  Flags 0 and 1 behave, and run, as before. */
+#define SHK_FASTQ_BGZF_BATCH 2u
+#define SHK_FASTQ_BGZF_DEVICE 4u
+/* shk_fastq_open_ex with the device the SHK_FASTQ_BGZF_DEVICE route runs on (shk_fastq_open_ex: device 0).  With that
+ * flag set and no such device to open — or in a build of the front-end alone — the call fails with SHK_ERR_NO_DEVICE
+ * and a text in shk_run_error(); it never decodes on the host instead. */
+int shk_fastq_open_device(const char *const *paths, uint32_t n_paths, uint64_t max_reads,
+                          uint64_t validate_every, uint32_t flags, int device_id, shk_fastq **out);
+/* gzip members decoded so far, by route: on the device, in host batches, one after the other (any may be NULL).  Ahead
+ * of what has been handed out: the decoders run in front of the parse. */
+int shk_fastq_member_stats(const shk_fastq *r, uint64_t *n_members_device, uint64_t *n_members_host_batch,
+                           uint64_t *n_members_sequential);
+/* Process-wide totals of the device route since the library was loaded (for measurements): members decoded, the
+ * decode kernel's time in nanoseconds (hipEvents around its launches), bytes uploaded and bytes downloaded. */
+int shk_bgzf_device_totals(uint64_t *n_members, uint64_t *kernel_ns, uint64_t *bytes_up, uint64_t *bytes_down);
 void shk_fastq_close(shk_fastq *r);
 const char *shk_fastq_error(const shk_fastq *r);
 /* Up to max_seqs sequences / bases_cap bytes, in input order; offsets[0] = 0.  A sequence that

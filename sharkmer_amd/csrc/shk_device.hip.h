@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "shk_inflate_core.h"
 #include "shk_retain_core.h"
 
 namespace shk {
@@ -5009,6 +5010,31 @@ __global__ void __launch_bounds__(WG) k_hist_reduce(const uint32_t *__restrict__
       if (threadIdx.x == 3) atomicAdd(&tot->any_saturated, v);  // (low half: saturated sums — non-zero is what counts; high half: adds past the LDS bins)
     }
   }
+}
+
+// ---- K_INFLATE: the members of a BGZF batch, one wave each ------------------------------------------
+// comp: the batch's compressed bytes (4-byte aligned, INFLATE_PAD bytes allocated behind them); jobs[m]: where member
+// m's raw DEFLATE body lies in comp and where its text goes in out (the host's prefix sum of ISIZE); status[m]: an
+// InfCoreStatus.  A wave's work depends on no other wave's: nothing here waits, and a corrupt stream is a status.  The
+// decode itself is shk_inflate_core.h — symbol decode the same in every lane, bytes moved by all 64.
+// LDS: sizeof(InfCoreScratch) = 4384 bytes per wave, 17536 per workgroup of INFLATE_WAVES = 4 waves: nine workgroups —
+// 36 waves — fit a CU's 160 KiB, so the tables do not hold occupancy under the 8 waves per CU asked for; the 140 VGPRs
+// do, at 3 waves per SIMD: 12 waves per CU.
+constexpr int INFLATE_WAVES = 4;
+constexpr uint32_t INFLATE_PAD = 8;
+struct InflateJob {
+  unsigned long long in_offset, out_offset;
+  uint32_t in_len, out_len;
+};
+__global__ __launch_bounds__(INFLATE_WAVES * 64) void k_inflate_members(const uint8_t *__restrict__ comp, const InflateJob *__restrict__ jobs,
+                                                                         uint32_t n_members, uint8_t *out, uint32_t *__restrict__ status) {
+  __shared__ InfCoreScratch scratch[INFLATE_WAVES];
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;  // (w: the same in the wave)
+  const uint32_t m = blockIdx.x * INFLATE_WAVES + w;
+  if (m >= n_members) return;  // (the whole wave)
+  const InflateJob j = jobs[m];
+  const uint32_t st = inflate_member<64>(scratch[w], lane, comp, j.in_offset, j.in_len, out + j.out_offset, j.out_len);
+  if (lane == 0) status[m] = st;
 }
 
 }  // namespace shk

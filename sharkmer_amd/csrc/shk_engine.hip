@@ -16,6 +16,7 @@
 #include "shk_retain_core.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -3614,3 +3615,5 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 #include "shk_products_api.hip.h"
 // shk_pcr_run: do_pcr for a panel, the stage calls above chained with the reference's control flow; no kernel of its own
 #include "shk_pcr_run_api.hip.h"
+// the device backend of the BGZF batched route: K_INFLATE behind the front-end's member decoder hook; no context
+#include "shk_inflate_api.hip.h"

@@ -120,6 +120,10 @@ void Pool::parallel_for(uint32_t n, std::function<void(uint32_t)> f) {
   n_jobs = 0;
 }
 
+// the device backend of the BGZF batched route (shk_front.h), if the library has one
+static std::atomic<const MemberDecoderOps *> g_device_decoder{nullptr};
+void shk_front_set_member_decoder(const MemberDecoderOps *ops) { g_device_decoder.store(ops); }
+
 }  // namespace shk
 
 using namespace shk;
@@ -497,6 +501,58 @@ struct PgzGate {
 // is consumed.  With a process-wide gate a second reader on a large .gz waited for the first to be drained — one thread
 // taking two readers in lockstep, as read_fastq_paired does with R1 / R2 (io.rs:629-700), never came back.)
 
+// ---- BGZF members decoded in batches --------------------------------------------------------------
+// What decodes a batch sits behind MemberDecoderOps (shk_front.h).  The device backend is on the HIP side of libshk.so
+// and registers itself when the library is loaded; this file has the host one: a member per task on the reader's pool,
+// each with an Inflater of its own and an empty history.
+struct HostMemberDecoder {
+  Pool *pool;
+  struct Slot {
+    const uint8_t *comp = nullptr;
+    const MemberJob *jobs = nullptr;
+    uint32_t n = 0;
+  } slot[2];
+};
+// one member into dst[0, out_len): the statuses of shk_inflate_core.h
+static uint32_t inflate_member_host(const uint8_t *body, uint32_t in_len, uint8_t *dst, uint32_t out_len) {
+  // (Inflater::run writes up to OUT_SLACK bytes past what it has decoded — into a scratch block, not into the next
+  // member's slot, which another task is filling)
+  thread_local std::vector<uint8_t> tmp(65536 + 2 * Inflater::OUT_SLACK);
+  Inflater inf;
+  inf.reset(body, body + in_len);
+  inf.history_bytes = 0;
+  size_t pos = 0;
+  const InflateStatus st = inf.run(tmp.data(), &pos, (size_t)out_len + Inflater::OUT_SLACK);
+  if (st == INF_CORRUPT) return 1;                   // INFC_CORRUPT
+  if (st == INF_TRUNCATED) return 2;                 // INFC_INPUT_EXHAUSTED
+  if (st == INF_OUTPUT_FULL || pos > out_len) return 3;  // INFC_OUTPUT_OVER (decoding stops once pos > out_len)
+  if (pos < out_len) return 4;                       // INFC_OUTPUT_SHORT
+  if (inf.input_after_stream() != body + in_len) return 5;  // INFC_INPUT_LEFT
+  memcpy(dst, tmp.data(), out_len);
+  return 0;
+}
+static bool host_dec_probe(int, std::string *) { return true; }
+static void *host_dec_open(int) { return nullptr; }  // (made by its user: it needs the reader's pool)
+static int host_dec_submit(void *d, int s, const uint8_t *comp, size_t, const MemberJob *jobs, uint32_t n, uint64_t) {
+  auto &sl = ((HostMemberDecoder *)d)->slot[s];
+  sl.comp = comp;
+  sl.jobs = jobs;
+  sl.n = n;
+  return 0;
+}
+static int host_dec_collect(void *d, int s, uint8_t *dst, uint32_t *status) {
+  auto *hd = (HostMemberDecoder *)d;
+  const auto sl = hd->slot[s];
+  if (!dst) return 0;  // (a batch nobody wants any more: nothing was started for it)
+  hd->pool->parallel_for(sl.n, [&](uint32_t i) {
+    const MemberJob &j = sl.jobs[i];
+    status[i] = inflate_member_host(sl.comp + j.in_offset, j.in_len, dst + j.out_offset, j.out_len);
+  });
+  return 0;
+}
+static void host_dec_close(void *d) { delete (HostMemberDecoder *)d; }
+static const MemberDecoderOps HOST_DECODER = {host_dec_probe, host_dec_open, host_dec_submit, host_dec_collect, host_dec_close};
+
 struct GzSource final : Source {
   GzMember gz;
   PgzGate *gate;            // the reader's gate
@@ -522,6 +578,11 @@ struct GzSource final : Source {
   // ends (by this thread: wants_crc() is then false), its error is the stream's.
   bool all_members = false;
   IoError members_err;
+  // the batched route over BGZF members (run_members): 0 off, SHK_FASTQ_BGZF_BATCH, SHK_FASTQ_BGZF_DEVICE
+  uint32_t bgzf_mode = 0;
+  int bgzf_device = 0;
+  Pool *pool = nullptr;                           // the reader's (host decode, CRC-32s)
+  std::atomic<uint64_t> *member_stats = nullptr;  // the reader's counts: [0] device, [1] host batch, [2] one after the other
   static constexpr size_t DEPTH = 3;
   const uint8_t *file_base;  // the file's first byte (file offsets decide where flate2's reads begin)
   GzSource(const uint8_t *p, const uint8_t *e, std::shared_ptr<void> own, PgzGate *gt, uint64_t turn) : gate(gt), ticket(turn), owner(std::move(own)), file_base(p) {
@@ -1161,16 +1222,149 @@ struct GzSource final : Source {
     uint64_t member_out = 0;
     uint64_t gone = 0;                        // bytes of the stream that have left the buffer's front
     const uint8_t *deflate0 = gz.inf.in;      // where the member being decoded begins
+    // ---- the batched route (bgzf_mode): BGZF members decoded side by side, in front of this loop -----------------------
+    // While the members at `member_hdr` are batchable (bgzf_scan), a batch of them is decoded into the buffer behind
+    // `pos` by the decoder — two batches in flight: the next one is scanned and submitted before this one is waited
+    // for — and every member's CRC-32 is checked here, on the pool.  The members in front of the first one that fails
+    // (status, CRC-32; a wrong ISIZE is a status) stay; at that member's header, or at the first member that is not
+    // batchable, this loop goes on the way it always has, with the state it would have there: a fresh member, nothing
+    // of it decoded.  What it then reports — error, text, the reference_has_seen cut — is its own.
+    const uint8_t *member_hdr = file_base;  // the header of the member the loop stands in front of
+    const uint8_t *const file_end = gz.file_end;
+    bool batching = bgzf_mode != 0;
+    const MemberDecoderOps *ops = nullptr;
+    void *dec = nullptr;
+    if (batching) {
+      if (bgzf_mode & SHK_FASTQ_BGZF_DEVICE) {
+        ops = g_device_decoder.load();
+        dec = ops ? ops->open(bgzf_device) : nullptr;
+      } else {
+        ops = &HOST_DECODER;
+        auto *hd = new HostMemberDecoder();
+        hd->pool = pool;
+        dec = hd;
+      }
+      if (!dec) batching = false;  // (the device went away after the reader was opened: one after the other)
+    }
+    struct DecClose {
+      const MemberDecoderOps *&ops;
+      void *&dec;
+      ~DecClose() {
+        if (dec) ops->close(dec);
+      }
+    } dec_close{ops, dec};
+    // a batch's decoded bytes: 64 MiB keeps 16 host threads busy and the text in cache-sized steps (2.9 against 2.5
+    // Gbases/s with 128); the device wants the ≈2000 members of 128 MiB — two batches fill its 4096 wave slots — and
+    // gives 2.5-2.8 against 2.1-2.4 Gbases/s with 64
+    const uint64_t budget = [this] {
+      const char *e = getenv("SHK_BGZF_BATCH_KB");  // test hook: batch borders in tiny files
+      return e ? std::max<uint64_t>(1, (uint64_t)atoll(e)) << 10 : (uint64_t)((bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 128 : 64) << 20;
+    }();
+    struct Batch {
+      std::vector<BgzfMember> ms;
+      std::vector<MemberJob> jobs;
+      const uint8_t *begin = nullptr, *end = nullptr;
+      uint64_t out_bytes = 0;
+      int slot = 0;
+      bool live = false;  // submitted, not collected
+    } batch[2];
+    int cur = 0;
+    auto scan_submit = [&](Batch &B, const uint8_t *from, int slot_) {  // false: no batchable member there (or the decoder failed)
+      B.ms.clear();
+      B.jobs.clear();
+      B.begin = from;
+      B.end = bgzf_scan(from, file_end, budget, &B.ms);
+      B.out_bytes = 0;
+      B.slot = slot_;
+      for (const BgzfMember &x : B.ms) {
+        B.jobs.push_back(MemberJob{(uint64_t)(x.header - from) + x.body_off, B.out_bytes, x.body_len, x.isize});
+        B.out_bytes += x.isize;
+      }
+      if (B.ms.empty()) return false;
+      B.live = ops->submit(dec, slot_, from, (size_t)(B.end - from), B.jobs.data(), (uint32_t)B.jobs.size(), B.out_bytes) == 0;
+      return B.live;
+    };
+    auto drop_batch = [&](Batch &B) {
+      if (B.live) (void)ops->collect(dec, B.slot, nullptr, nullptr);
+      B.live = false;
+    };
+    // room for `need` more bytes behind pos: whole lines in front of it leave as a window (held back as below)
+    auto make_room = [&](size_t need) {
+      if (b->v.size() - pos >= need + Inflater::OUT_SLACK) return;
+      const size_t held = std::min(pos - line0, HOLD_BACK);
+      const void *nl = memrchr(b->v.data() + line0, '\n', pos - held - line0);
+      const size_t cut = nl ? (size_t)((const uint8_t *)nl - b->v.data()) + 1 : line0;
+      const size_t keep = std::min(pos, std::max<size_t>(32768, pos - cut));
+      auto nb = std::make_shared<Buf>();
+      // (sizes in steps of 8 MiB: Buf keeps blocks for reuse by their exact size)
+      nb->v.resize(std::max(cap, (keep + std::max(need, window) + Inflater::OUT_SLACK + (8u << 20) - 1) & ~(size_t)((8u << 20) - 1)));
+      memcpy(nb->v.data(), b->v.data() + pos - keep, keep);
+      if (cut > line0) emit(Window{b, (const char *)b->v.data() + line0, cut - line0, false});
+      line0 = keep - (pos - cut);
+      gone += pos - keep;
+      pos = keep;
+      crc_from = keep;
+      b = std::move(nb);
+    };
+    std::vector<uint32_t> status;
     for (;;) {
       {
         std::lock_guard<std::mutex> lk(m);
         if (stop) break;
+      }
+      if (batching) {  // (in front of a member: crc = 0, member_out = 0, crc_from = pos)
+        Batch &B = batch[cur], &N = batch[cur ^ 1];
+        if (!B.live && !scan_submit(B, member_hdr, cur)) {
+          batching = false;
+          continue;
+        }
+        if (B.end < file_end) (void)scan_submit(N, B.end, cur ^ 1);
+        make_room((size_t)B.out_bytes);
+        const uint32_t n = (uint32_t)B.ms.size();
+        status.assign(n, ~0u);
+        const bool came = ops->collect(dec, B.slot, b->v.data() + pos, status.data()) == 0;
+        B.live = false;
+        uint8_t *const text = b->v.data() + pos;
+        if (came)
+          pool->parallel_for(n, [&](uint32_t i) {
+            if (status[i] == 0 && crc32_update(0, text + B.jobs[i].out_offset, B.jobs[i].out_len) != B.ms[i].crc) status[i] = ~0u - 1;
+          });
+        uint32_t k = 0;
+        while (k < n && status[k] == 0) ++k;
+        const size_t good = k < n ? (size_t)B.jobs[k].out_offset : (size_t)B.out_bytes;
+        pos += good;
+        crc_from = pos;
+        if (member_stats) member_stats[(bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 0 : 1] += k;
+        member_hdr = k < n ? B.ms[k].header : B.end;
+        if (k == n && member_hdr >= file_end) {  // the file's end, clean: what INF_STREAM_END of the last member does below
+          emit(Window{b, (const char *)b->v.data() + line0, pos - line0, true});
+          break;
+        }
+        if (k == n && N.live) {
+          cur ^= 1;
+          continue;
+        }
+        // hand over: a member that failed, or one that is not batchable
+        drop_batch(N);
+        batching = false;
+        gz = GzMember();
+        gz.open(member_hdr, file_end);
+        members_err = gz.header_error;
+        crc = 0;
+        member_out = 0;
+        deflate0 = gz.inf.in;
+        if (members_err.kind != IO_NONE) {
+          emit(Window{b, (const char *)b->v.data() + line0, pos - line0, true});
+          break;
+        }
+        continue;
       }
       gz.inf.history_bytes = member_out;  // (a member's matches reach back into that member only)
       const InflateStatus st = gz.inf.run(b->v.data(), &pos, b->v.size());
       crc = crc32_update(crc, b->v.data() + crc_from, pos - crc_from);
       member_out += pos - crc_from;
       crc_from = pos;
+      if (st != INF_OUTPUT_FULL && member_stats) member_stats[2] += 1;
       if (st == INF_STREAM_END) {
         members_err = gz.finish(st, crc, member_out);
         const uint8_t *nxt = gz.inf.input_after_stream() + 8, *fe = gz.file_end;
@@ -1357,6 +1551,9 @@ struct Producer {
   FileEnd end;
   static constexpr size_t Q_MAX = 256u << 20;  // bytes buffered ahead per file
   bool gz_all_members = false;  // (shk_fastq_open_ex: not the reference's behaviour)
+  uint32_t bgzf_mode = 0;       // SHK_FASTQ_BGZF_BATCH / _DEVICE: BGZF members in batches (GzSource::run_members)
+  int bgzf_device = 0;
+  std::atomic<uint64_t> *member_stats = nullptr;
   PgzGate *gate = nullptr;      // the reader's gate (shk_fastq::gate)
   uint64_t pgz_ticket = 0;      // this file's turn at the many-thread gzip decoder (drawn in file order by the reader)
   bool ticket_given = false;    // … handed to a GzSource; otherwise given back as soon as the source is known
@@ -1440,6 +1637,10 @@ struct Producer {
           auto *g = new GzSource((const uint8_t *)data, (const uint8_t *)data + size, nullptr, gate, pgz_ticket);
           ticket_given = true;
           g->all_members = gz_all_members;
+          g->bgzf_mode = bgzf_mode;
+          g->bgzf_device = bgzf_device;
+          g->pool = pool;
+          g->member_stats = member_stats;
           return with_window(g);
         }
         return with_window(new MappedSource(data, size));
@@ -1473,6 +1674,10 @@ struct Producer {
     auto *g = new GzSource(all->data(), all->data() + all->size(), all, gate, pgz_ticket);
     ticket_given = true;
     g->all_members = gz_all_members;
+    g->bgzf_mode = bgzf_mode;
+    g->bgzf_device = bgzf_device;
+    g->pool = pool;
+    g->member_stats = member_stats;
     return with_window(g);
   }
 
@@ -1816,6 +2021,9 @@ struct shk_fastq {
   uint32_t T = 1;
   uint64_t max_reads = 0, validate_every = 0;
   bool gz_all_members = false;
+  uint32_t bgzf_mode = 0;  // SHK_FASTQ_BGZF_BATCH / SHK_FASTQ_BGZF_DEVICE
+  int bgzf_device = 0;
+  std::atomic<uint64_t> member_stats[3] = {{0}, {0}, {0}};  // gzip members decoded: device, host batch, one after the other
   // -- the scout: what is known about the input ahead of what has been handed out
   struct Held {
     SeqChunk c;
@@ -1867,6 +2075,9 @@ struct shk_fastq {
       p->pool = pool.get();
       p->T = T;
       p->gz_all_members = gz_all_members;
+      p->bgzf_mode = bgzf_mode;
+      p->bgzf_device = bgzf_device;
+      p->member_stats = member_stats;
       p->gate = &gate;
       p->pgz_ticket = gate.draw();
       Producer *pp = p.get();
@@ -2002,14 +2213,38 @@ int shk_fastq_open(const char *const *paths, uint32_t n_paths, uint64_t max_read
 
 int shk_fastq_open_ex(const char *const *paths, uint32_t n_paths, uint64_t max_reads, uint64_t validate_every, uint32_t flags,
                       shk_fastq **out) {
+  return shk_fastq_open_device(paths, n_paths, max_reads, validate_every, flags, 0, out);
+}
+
+int shk_fastq_open_device(const char *const *paths, uint32_t n_paths, uint64_t max_reads, uint64_t validate_every, uint32_t flags,
+                          int device_id, shk_fastq **out) {
   if (!out) return SHK_ERR_BAD_ARG;
+  *out = nullptr;
+  if (flags & SHK_FASTQ_BGZF_DEVICE) {  // never quietly on the host instead
+    const MemberDecoderOps *ops = g_device_decoder.load();
+    std::string why = "this build of the front-end has no device decoder";
+    if (!ops || !ops->probe(device_id, &why)) {
+      run_error() = fmt("SHK_FASTQ_BGZF_DEVICE: no HIP device %d to decode on: %s", device_id, why.c_str());
+      return SHK_ERR_NO_DEVICE;
+    }
+  }
   auto *r = new shk_fastq();
-  r->gz_all_members = (flags & SHK_FASTQ_GZIP_ALL_MEMBERS) != 0;
+  r->bgzf_mode = flags & (SHK_FASTQ_BGZF_BATCH | SHK_FASTQ_BGZF_DEVICE);
+  r->bgzf_device = device_id;
+  r->gz_all_members = (flags & SHK_FASTQ_GZIP_ALL_MEMBERS) != 0 || r->bgzf_mode != 0;
   for (uint32_t i = 0; i < n_paths; ++i) r->paths.emplace_back(paths[i]);
   if (n_paths == 0) r->paths.emplace_back("-");  // stdin, io.rs:517-537
   r->max_reads = max_reads;
   r->validate_every = validate_every;
   *out = r;
+  return SHK_OK;
+}
+
+int shk_fastq_member_stats(const shk_fastq *r, uint64_t *n_members_device, uint64_t *n_members_host_batch, uint64_t *n_members_sequential) {
+  if (!r) return SHK_ERR_BAD_ARG;
+  if (n_members_device) *n_members_device = r->member_stats[0].load();
+  if (n_members_host_batch) *n_members_host_batch = r->member_stats[1].load();
+  if (n_members_sequential) *n_members_sequential = r->member_stats[2].load();
   return SHK_OK;
 }
 

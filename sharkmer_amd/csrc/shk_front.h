@@ -44,4 +44,26 @@ struct Pool {
   uint32_t size() const { return (uint32_t)th.size(); }
 };
 
+// ---- the seam between the BGZF batched route (shk_front.cpp, no HIP) and what decodes a batch ----------
+// A batch: consecutive BGZF members, their compressed bytes `comp[0, comp_len)` in one piece (headers and trailers
+// included), and per member where its raw DEFLATE body lies in that and where its text goes in the batch's output.
+struct MemberJob {
+  uint64_t in_offset, out_offset;  // out_offset: the prefix sum of ISIZE
+  uint32_t in_len, out_len;        // both ≤ 65536
+};
+// A decoder takes up to two batches at a time (slots 0 and 1: the next one goes up while this one comes back).
+// submit() queues a batch; collect() waits for it, writes its text to dst[0, out_bytes) and one InfCoreStatus word per
+// member to status[].  Both return 0, or an error that ends the batched route for the stream (the one-after-the-other
+// decoder takes over; nothing is lost).  No ABI promise: the struct is the library's own.
+struct MemberDecoderOps {
+  bool (*probe)(int device, std::string *why);  // can a decoder be opened there at all (asked by shk_fastq_open_device)
+  void *(*open)(int device);
+  int (*submit)(void *dec, int slot, const uint8_t *comp, size_t comp_len, const MemberJob *jobs, uint32_t n, uint64_t out_bytes);
+  int (*collect)(void *dec, int slot, uint8_t *dst, uint32_t *status);
+  void (*close)(void *dec);
+};
+// The device backend registers itself here when libshk.so is loaded (shk_inflate_api.hip.h); a build of the front-end
+// alone has none, and the device flag then fails at open.
+void shk_front_set_member_decoder(const MemberDecoderOps *ops);
+
 }  // namespace shk

@@ -76,7 +76,9 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
     }
   }
   shk_fastq *rd = nullptr;
-  v = shk_fastq_open_ex(rc->inputs, rc->n_inputs, rc->max_reads, rc->validate_every, rc->fastq_flags, &rd);
+  // (SHK_FASTQ_BGZF_DEVICE decodes on the context's first device)
+  const int first_device = rc->n_devices >= 1 && rc->device_ids ? rc->device_ids[0] : rc->device;
+  v = shk_fastq_open_device(rc->inputs, rc->n_inputs, rc->max_reads, rc->validate_every, rc->fastq_flags, first_device, &rd);
   if (v != SHK_OK) return v;
   shk_config cfg{};
   cfg.k = rc->k;

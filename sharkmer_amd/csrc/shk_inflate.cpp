@@ -951,4 +951,48 @@ IoError GzMember::finish(InflateStatus last, uint32_t crc, uint64_t total_out) c
   return IoError();
 }
 
+// ---- BGZF framing ------------------------------------------------------------------------------------------------
+static bool bgzf_member_at(const uint8_t *p, const uint8_t *e, BgzfMember *m) {
+  if (e - p < 12 + 6 + 8) return false;  // (the smallest: a header with the BC subfield alone, an empty body's trailer)
+  if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return false;
+  const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
+  if ((size_t)(e - p) < 12 + xlen + 8) return false;
+  const uint8_t *x = p + 12, *const xe = x + xlen;
+  uint32_t bsize = 0;
+  bool found = false;
+  while (xe - x >= 4) {  // subfields: SI1 SI2 SLEN data
+    const size_t slen = (size_t)x[2] | ((size_t)x[3] << 8);
+    if ((size_t)(xe - x) < 4 + slen) return false;
+    if (x[0] == 'B' && x[1] == 'C' && slen == 2 && !found) {
+      bsize = (uint32_t)x[4] | ((uint32_t)x[5] << 8);
+      found = true;
+    }
+    x += 4 + slen;
+  }
+  if (!found || x != xe) return false;
+  const size_t size = (size_t)bsize + 1, head = 12 + xlen;
+  if (size < head + 8 || size > (size_t)(e - p)) return false;
+  const size_t body_len = size - head - 8;
+  if (body_len > 65536) return false;
+  const uint8_t *t = p + size - 8;
+  m->header = p;
+  m->size = (uint32_t)size;
+  m->body_off = (uint32_t)head;
+  m->body_len = (uint32_t)body_len;
+  m->crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+  m->isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+  return m->isize <= 65536;
+}
+const uint8_t *bgzf_scan(const uint8_t *p, const uint8_t *file_end, uint64_t out_budget, std::vector<BgzfMember> *out) {
+  uint64_t sum = 0;
+  BgzfMember m;
+  while (p < file_end && bgzf_member_at(p, file_end, &m)) {
+    if (!out->empty() && sum + m.isize > out_budget) break;
+    sum += m.isize;
+    out->push_back(m);
+    p += m.size;
+  }
+  return p;
+}
+
 }  // namespace shk

@@ -13,6 +13,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace shk {
 
@@ -89,5 +90,20 @@ struct GzMember {
   // written) after INF_STREAM_END, or the error a short or corrupt body turns into.  IO_NONE = clean end of stream.
   IoError finish(InflateStatus last, uint32_t crc, uint64_t total_out) const;
 };
+
+// ---- BGZF framing ------------------------------------------------------------------------------------------------
+// A gzip member the batched route can take without decoding a bit of it: ID1 ID2 CM = 1f 8b 08, FLG exactly FEXTRA, a
+// BC subfield of length 2 in the extra field (BSIZE: the member's size − 1), the member inside the file, header + 8 ≤
+// its size, a body of at most 65536 bytes and ISIZE ≤ 65536.  (bgzip's 28-byte end-of-file member is one: 0 bytes out.)
+struct BgzfMember {
+  const uint8_t *header;  // the member's first byte
+  uint32_t size;          // BSIZE + 1: header, body and trailer
+  uint32_t body_off, body_len;
+  uint32_t crc, isize;    // the trailer's words
+};
+// Lists the consecutive batchable members from `p` on while their ISIZEs sum to at most `out_budget` (the first one is
+// taken whatever its size) and returns the first byte behind them — `p` itself when the member there is not batchable
+// (anything else that may follow a trailer, a member cut short by the file's end).  Decodes nothing.
+const uint8_t *bgzf_scan(const uint8_t *p, const uint8_t *file_end, uint64_t out_budget, std::vector<BgzfMember> *out);
 
 }  // namespace shk

@@ -26,6 +26,16 @@ FLAG_FORCE_PAGED = 4
 FLAG_TIMING_SAMPLED = 16  # with FLAG_TIMING: only every 4th job's launches are bracketed (include/shk.h)
 RESERVE_NONE = 0xFFFFFFFF  # shk_config.reserve_cus: every compute unit (include/shk.h)
 FASTQ_GZIP_ALL_MEMBERS = 1  # shk_fastq_open_ex / shk_run_config.fastq_flags (include/shk.h)
+FASTQ_BGZF_BATCH = 2        # BGZF members decoded in batches on host threads …
+FASTQ_BGZF_DEVICE = 4       # … or on the device (both imply every member)
+
+
+def _bgzf_flags(bgzf) -> int:
+    if bgzf is None:
+        return 0
+    if bgzf not in ("host", "device"):
+        raise ValueError(f"bgzf must be None, 'host' or 'device', not {bgzf!r}")
+    return FASTQ_BGZF_BATCH if bgzf == "host" else FASTQ_BGZF_DEVICE
 FLAG_DEFER_ERRORS = 8  # host-buffer ingests return once queued; errors surface at the next call (include/shk.h)
 
 KERNEL_NAMES = ["mark", "scan", "direct", "scatter", "pages", "histo", "grow", "insert",
@@ -596,6 +606,7 @@ ABI_SYMBOLS = [
     "shk_table_device_ptrs", "shk_merge_pages", "shk_set_owned_pages", "shk_alloc_pinned",
     "shk_free_pinned", "shk_alloc_device", "shk_free_device", "shk_release_cached_memory", "shk_synth_reads_device",
     "shk_fastq_open", "shk_fastq_open_ex", "shk_fastq_close", "shk_fastq_error", "shk_fastq_next_batch", "shk_fastq_next_batch_packed", "shk_fastq_stats",
+    "shk_fastq_open_device", "shk_fastq_member_stats", "shk_bgzf_device_totals",
     "shk_write_histo", "shk_write_final_histo", "shk_write_stats_yaml", "shk_validate_args",
     "shk_run_error", "shk_run_files",
     "shk_xchg_scatter_device", "shk_xchg_absorb", "shk_xchg_spill", "shk_xchg_spill_clear", "shk_insert_device",
@@ -642,6 +653,7 @@ def _share_hip_runtime_with_torch():
 
 FRONT_SYMBOLS = [
     "shk_fastq_open", "shk_fastq_open_ex", "shk_fastq_close", "shk_fastq_error", "shk_fastq_next_batch", "shk_fastq_next_batch_packed", "shk_fastq_stats",
+    "shk_fastq_open_device", "shk_fastq_member_stats",
     "shk_write_histo", "shk_write_final_histo", "shk_write_stats_yaml", "shk_validate_args", "shk_run_error",
     "shk_packed_sizes", "shk_pack_reads",
     "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
@@ -664,6 +676,8 @@ def _type_front(L):
     L.shk_fastq_next_batch.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.shk_fastq_next_batch_packed.argtypes = [vp, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.shk_fastq_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.shk_fastq_open_device.argtypes = [C.POINTER(C.c_char_p), u32, u64, u64, u32, C.c_int, C.POINTER(vp)]
+    L.shk_fastq_member_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.shk_write_histo.argtypes = [C.c_char_p, C.c_char_p, u32, u32, u64, vp]
     L.shk_write_final_histo.argtypes = [C.c_char_p, C.c_char_p, u32, u32, u64, vp]
     L.shk_write_stats_yaml.argtypes = [C.c_char_p, C.POINTER(_RunStats)]
@@ -2010,13 +2024,18 @@ class FastqReader:
     """read_fastq / open_fastq_reader (io.rs:271-352, 598-625) through libshk's C++ host.
     Parses only (no GPU needed)."""
 
-    def __init__(self, paths, max_reads: int = 0, validate_every: int = 0, gzip_all_members: bool = False):
+    def __init__(self, paths, max_reads: int = 0, validate_every: int = 0, gzip_all_members: bool = False, bgzf=None, device: int = 0):
         """gzip_all_members: NOT the reference (a gzip file is read up to the end of its first member, io.rs:606-617) —
-        every member (bgzip, concatenated files), shk_fastq_open_ex's SHK_FASTQ_GZIP_ALL_MEMBERS."""
+        every member (bgzip, concatenated files), shk_fastq_open_ex's SHK_FASTQ_GZIP_ALL_MEMBERS.
+        bgzf: "host" or "device" — every member too, BGZF members decoded in batches on the reader's threads or on HIP
+        device `device` (SHK_FASTQ_BGZF_BATCH / SHK_FASTQ_BGZF_DEVICE, shk_fastq_open_device); the same reads and errors."""
         self._L = load_front_library()
         arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
         h = C.c_void_p()
-        rc = self._L.shk_fastq_open_ex(arr, len(paths), max_reads, validate_every, FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0, C.byref(h))
+        flags = (FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0) | _bgzf_flags(bgzf)
+        rc = self._L.shk_fastq_open_device(arr, len(paths), max_reads, validate_every, flags, device, C.byref(h))
+        if rc != 0 and flags & FASTQ_BGZF_DEVICE:
+            raise ShkError(rc, (self._L.shk_run_error() or b"").decode("utf-8", "replace"))
         if rc != 0:
             raise ShkError(rc, "shk_fastq_open failed")
         self._h = h
@@ -2059,6 +2078,13 @@ class FastqReader:
         self._L.shk_fastq_stats(self._h, C.byref(a), C.byref(b), C.byref(m), C.byref(d))
         return {"n_reads_read": int(a.value), "n_bases_read": int(b.value),
                 "reached_max": bool(m.value), "done": bool(d.value)}
+
+    def member_stats(self) -> dict:
+        """gzip members decoded so far, by route (shk_fastq_member_stats): on the device, in host batches, one after the
+        other.  The decoders run ahead of what has been handed out."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._L.shk_fastq_member_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
+        return {"device": int(a.value), "host_batch": int(b.value), "sequential": int(c.value)}
 
 
 def write_histo(path: str, histo: np.ndarray, k: int, histo_max: int, version: str = "3.1.0"):
@@ -2111,12 +2137,13 @@ def validate_args(k: int, histo_max: int, sample):
 def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", histo_max: int = 10000,
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
               command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
-              pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
+              bgzf=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
     """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
     strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
     tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
     max_primer_kmers, high_coverage_ratio, tip_coverage_fraction), which overwrite every gene's values.
-    device_ids: run on one multi-device context (shk_run_config.n_devices).  gzip_all_members: see FastqReader."""
+    device_ids: run on one multi-device context (shk_run_config.n_devices).  gzip_all_members, bgzf: see FastqReader
+    (bgzf="device" decodes on the context's first device)."""
     known = ("max_dfs_states", "max_paths_per_pair", "max_node_visits", "max_primer_kmers", "high_coverage_ratio", "tip_coverage_fraction")
     if set(tuning) - set(known):
         raise TypeError(f"unexpected arguments {sorted(set(tuning) - set(known))}")
@@ -2126,7 +2153,7 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
                      histo_max=histo_max, max_reads=max_reads, validate_every=validate_every,
                      sample=None if sample is None else sample.encode(), outdir=os.fsencode(outdir),
                      command=command.encode(), version=None, table_capacity_hint=capacity_hint,
-                     batch_reads=batch_reads, batch_bases=batch_bases, fastq_flags=FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0)
+                     batch_reads=batch_reads, batch_bases=batch_bases, fastq_flags=(FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0) | _bgzf_flags(bgzf))
     if device_ids is not None:
         ids = (C.c_int32 * len(device_ids))(*device_ids)
         cfg.n_devices = len(device_ids)
