@@ -1097,8 +1097,8 @@ int shk_fastq_open_ex(const char *const *paths, uint32_t n_paths, uint64_t max_r
  * whose trailers carry their decoded size, so the members are independent jobs with known extents before a bit is
  * decoded.  Consecutive members with that framing (FLG exactly FEXTRA, a BC subfield, body and text ≤ 65536 bytes) are
  * decoded side by side — SHK_FASTQ_BGZF_BATCH: on the reader's host threads; SHK_FASTQ_BGZF_DEVICE: on a HIP device,
- * one wave per member (the text comes back to the host parser).  Every member's CRC-32 and ISIZE are checked before a
- * byte of it is parsed.  At the first member that is not framed so, or whose decode, CRC-32 or ISIZE fails, the
+ * one wave per member (the text comes back to the host parser — unless SHK_FASTQ_DEVICE_PARSE, below, keeps it in device
+ * memory and frames the records there).  Every member's CRC-32 and ISIZE are checked before a byte of it is parsed.  At the first member that is not framed so, or whose decode, CRC-32 or ISIZE fails, the
  * one-after-the-other decoder of SHK_FASTQ_GZIP_ALL_MEMBERS takes over from that member's header on: reads, order,
  * errors and their texts are that flag's, whatever the file holds.  Flags 0 and 1 behave, and run, as before. */
 #define SHK_FASTQ_BGZF_BATCH 2u
@@ -1115,6 +1115,85 @@ int shk_fastq_member_stats(const shk_fastq *r, uint64_t *n_members_device, uint6
 /* Process-wide totals of the device route since the library was loaded (for measurements): members decoded, the
  * decode kernel's time in nanoseconds (hipEvents around its launches), bytes uploaded and bytes downloaded. */
 int shk_bgzf_device_totals(uint64_t *n_members, uint64_t *kernel_ns, uint64_t *bytes_up, uint64_t *bytes_down);
+
+/* ---- FASTQ text parsed on the device ----
+ * shk_fastq_parse_device frames the records of n_bytes (at most 2^31) of FASTQ text that lies in device memory, at any
+ * alignment, the way read_fastq / BufRead::lines / validate_fastq_record do (io.rs:161-198, 271-352): a line ends with
+ * '\n', a '\r' directly in front of it is not part of the line; with `last` an unterminated rest is a line too (and
+ * keeps a '\r' at its end); record j is lines 4j .. 4j+3.  The sequences go, concatenated, to d_bases and their offsets
+ * to d_offsets[n_records + 1] — what shk_ingest_reads_device takes.  An ANOMALY is a record the host must decide about:
+ * a byte >= 0x80 in one of its four lines, a sequence byte outside ACGTN, or, when the record's global index g =
+ * first_record + j is validated (g == 0 || (validate_every && g % validate_every == 0)): a header that does not start
+ * with '@', a separator that does not start with '+', a quality line of another length than the sequence.  The call
+ * looks at records [0, min(whole records, max_records)) and emits those in front of the first anomaly among them;
+ * bytes_consumed is where the last emitted record ends: what lies behind is the caller's (a partial record, fewer than
+ * four lines, or the anomaly).  Synchronous.  SHK_ERR_BAD_ARG when a capacity is too small: out->n_records and
+ * out->n_bases then say what the text needs (nothing is written beyond a capacity). */
+#define SHK_FASTQ_ANOMALY_HIGH_BYTE 1u
+#define SHK_FASTQ_ANOMALY_HEADER 2u
+#define SHK_FASTQ_ANOMALY_SEPARATOR 3u
+#define SHK_FASTQ_ANOMALY_QUALITY_LEN 4u
+#define SHK_FASTQ_ANOMALY_BASE 5u   /* of several kinds in one record the lowest is reported */
+typedef struct shk_fastq_text_params {
+  uint64_t first_record;    /* global index of the text's first record (validation cadence) */
+  uint64_t validate_every;
+  uint64_t max_records;     /* emit at most this many; 0 = no limit */
+  uint32_t last;            /* the text ends its file: an unterminated last line is a line */
+  uint32_t reserved;
+} shk_fastq_text_params;
+typedef struct shk_fastq_text_result {
+  uint64_t n_records, n_bases, bytes_consumed;
+  uint64_t anomaly_record;  /* UINT64_MAX: none among the records looked at */
+  uint32_t anomaly_kind, reserved;
+} shk_fastq_text_result;
+int shk_fastq_parse_device(shk_ctx *ctx, const void *d_text, uint64_t n_bytes, const shk_fastq_text_params *params,
+                           void *d_bases, uint64_t bases_cap, void *d_offsets, uint64_t offsets_cap,
+                           shk_fastq_text_result *out);
+/* CRC-32 (gzip's) of n extents of d_text, one wave each: d_jobs[n] of shk_crc_job, d_crc[n] words (device pointers; an
+ * extent of 0 bytes gives 0).  Synchronous. */
+typedef struct shk_crc_job {
+  uint64_t offset;
+  uint32_t len, reserved;
+} shk_crc_job;
+int shk_crc32_members_device(shk_ctx *ctx, const void *d_text, const void *d_jobs, uint32_t n, void *d_crc);
+/* The bytes of text one wave takes in the framing passes (tests put line ends on its borders). */
+void shk_fastq_parse_geometry(uint32_t *tile_bytes);
+/* The route: bgzip'd FASTQ files → the context, the text never leaving device memory.  Per batch of BGZF members the
+ * compressed bytes go up, K_INFLATE decodes them, the members' CRC-32 are computed on the device and come down with the
+ * statuses (8 bytes per member), the records are framed over carry + text, and the sequences are ingested
+ * (shk_ingest_reads_device; retained if retention is on).  The read index, the cadence and max_reads run across the
+ * files.  A single-device context that holds no reads (else SHK_ERR_STATE).
+ * gave_up == 2: the input is not this route's (no path, a path that is no regular file, a first member that is not
+ * BGZF, a multi-device context) — nothing was touched.  gave_up == 1: a member that is not BGZF, a decode status, a
+ * CRC-32 or an anomaly in front of max_reads, a file that ends inside a record or without a final '\n', or a failure of
+ * the route's own: the context
+ * has been shk_reset (retention as it was) and the caller reads the whole input through shk_fastq_open*, whose reads,
+ * errors and texts are then the outcome.  Both come with SHK_OK.  The route never decodes or parses on the host. */
+typedef struct shk_fastq_device_stats {
+  uint64_t n_batches, n_members;
+  uint64_t n_records, n_bases;      /* framed on the device and ingested (= the context's reads when gave_up == 0) */
+  uint64_t bytes_up, bytes_down;    /* the route's own traffic: compressed bytes and jobs up; statuses, CRCs, result words down */
+  uint64_t kernel_ns;               /* the framing and CRC-32 kernels (hipEvents round their launches) */
+  uint32_t gave_up, give_up_reason; /* reason: SHK_FASTQ_GIVEUP_* */
+} shk_fastq_device_stats;
+#define SHK_FASTQ_GIVEUP_NOT_ELIGIBLE 1u
+#define SHK_FASTQ_GIVEUP_MEMBER 2u      /* a member that is not batchable BGZF */
+#define SHK_FASTQ_GIVEUP_DECODE 3u      /* a decode status (a wrong ISIZE is one) */
+#define SHK_FASTQ_GIVEUP_CRC 4u
+#define SHK_FASTQ_GIVEUP_ANOMALY 5u
+#define SHK_FASTQ_GIVEUP_TEXT_LEFT 6u   /* a file ends inside a record, or its last line has no '\n' */
+#define SHK_FASTQ_GIVEUP_OWN 7u         /* a HIP error, an allocation, an ingest that failed, a carry beyond its room */
+int shk_ingest_fastq_files_device(shk_ctx *ctx, const char *const *paths, uint32_t n_paths, uint64_t max_reads,
+                                  uint64_t validate_every, shk_fastq_device_stats *out);
+/* Process-wide totals of the route and of shk_fastq_parse_device / shk_crc32_members_device since the library was
+ * loaded (any may be NULL): batches, records framed on the device, give-ups (gave_up != 0), bytes up, bytes down, the
+ * framing and CRC-32 kernels' nanoseconds. */
+int shk_fastq_device_totals(uint64_t *n_batches, uint64_t *n_records, uint64_t *n_give_ups, uint64_t *bytes_up,
+                            uint64_t *bytes_down, uint64_t *kernel_ns);
+/* shk_run_config.fastq_flags only, and only together with SHK_FASTQ_BGZF_DEVICE (alone: SHK_ERR_BAD_ARG): the run tries
+ * shk_ingest_fastq_files_device first and, when that gives up, reads the input from the start with the flag cleared.
+ * shk_fastq_open* refuse it (SHK_ERR_BAD_ARG): a reader hands out host batches. */
+#define SHK_FASTQ_DEVICE_PARSE 8u
 void shk_fastq_close(shk_fastq *r);
 const char *shk_fastq_error(const shk_fastq *r);
 /* Up to max_seqs sequences / bases_cap bytes, in input order; offsets[0] = 0.  A sequence that

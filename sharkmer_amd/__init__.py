@@ -14,6 +14,7 @@ from .engine import (  # noqa: F401
     PcrGene, PcrOutcome, parse_pcr_primers, validate_pcr_gene, pcr_validation_report, pcr_failure_reason, write_fasta,
     PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET,
     PackedReads, pack_reads, release_cached_memory, FastqReader, write_histo, write_final_histo, write_stats_yaml, validate_args, run_files,
+    fastq_parse_geometry, fastq_device_totals, FASTQ_NO_ANOMALY,
 )
 from .synth import SynthSpec, synth_reads  # noqa: F401
 

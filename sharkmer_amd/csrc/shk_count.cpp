@@ -92,6 +92,7 @@ int main(int argc, char **argv) {
     else if (key == "--gzip-all-members") gzip_all = true;  // (not a sharkmer flag: sharkmer reads a gzip file's first member)
     else if (key == "--bgzf-batch") bgzf_flags |= SHK_FASTQ_BGZF_BATCH;    // (nor these: every member, BGZF members in batches on host threads …
     else if (key == "--bgzf-device") bgzf_flags |= SHK_FASTQ_BGZF_DEVICE;  //  … or on the device)
+    else if (key == "--device-parse") bgzf_flags |= SHK_FASTQ_DEVICE_PARSE;  // (with --bgzf-device: the text stays on the device and is framed there)
     else if (key == "-t" || key == "--threads") num(&threads);
     else if (key == "--device") num(&device);
     else if (key == "--capacity-hint") num(&hint);
@@ -111,7 +112,7 @@ int main(int argc, char **argv) {
     else if (key == "-o" || key == "--outdir") outdir = val ? argv[i] + eq + 1 : need(i, key.c_str());
     else if (key == "-h" || key == "--help") {
       printf("Usage: shk_count [-k K] [--chunks N] [--histo-max M] [-m READS] -s SAMPLE [-o OUTDIR] "
-             "[--validate-every N] [--gzip-all-members] [--bgzf-batch | --bgzf-device] [--pcr-primers \"forward=...,reverse=...,name=...\"]... "
+             "[--validate-every N] [--gzip-all-members] [--bgzf-batch | --bgzf-device [--device-parse]] [--pcr-primers \"forward=...,reverse=...,name=...\"]... "
              "[--min-kmer-count N] [--read-threading] [--node-budget-global N] [FASTQ[.gz] ...]\n");
       return 0;
     } else if (a.size() > 1 && a[0] == '-' && a != "-") {

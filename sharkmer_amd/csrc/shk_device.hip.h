@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "shk_inflate_core.h"
+#include "shk_fastq_text_core.h"
 #include "shk_retain_core.h"
 
 namespace shk {
@@ -5036,5 +5037,167 @@ __global__ __launch_bounds__(INFLATE_WAVES * 64) void k_inflate_members(const ui
   const uint32_t st = inflate_member<64>(scratch[w], lane, comp, j.in_offset, j.in_len, out + j.out_offset, j.out_len);
   if (lane == 0) status[m] = st;
 }
+
+// ---- K_FASTQ: FASTQ framing and CRC-32 over decoded text in HBM --------------------------------------
+// The passes of shk_fastq_text_core.h, one launch each; every launch is done before the next one starts (one stream),
+// no workgroup waits for another, plain vector stores, no inline assembly.  The control block is cleared by the host
+// (anomaly: all ones) before the first launch.
+struct FqCtrl {
+  unsigned long long n_nl;     // '\n' in the text (the tile counts' total)
+  unsigned long long anomaly;  // fq_anomaly_pack's minimum over the records looked at
+  unsigned int any_high;       // a byte >= 0x80 somewhere in the text
+  unsigned int ends_nl;        // the text's last byte is '\n'
+  unsigned long long n_bases_look;  // the sequence lengths' total over the records looked at
+  FqResultWords res;
+};
+constexpr int FQ_WAVES = 4;       // tiles per workgroup in the tile passes
+constexpr int FQ_REC_WG = 256;    // records per workgroup in the record passes
+constexpr int FQ_SCAN_WG = 1024;
+
+// Pass 1.  tile_cnt[t]: the '\n' of tile t.
+__global__ __launch_bounds__(FQ_WAVES * 64) void k_fq_count(const uint8_t *__restrict__ text, unsigned long long n, unsigned long long n_tiles,
+                                                            unsigned long long *__restrict__ tile_cnt, FqCtrl *ctrl) {
+  const unsigned long long t = (unsigned long long)blockIdx.x * FQ_WAVES + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;  // (the whole wave)
+  const FqWave<64> W{threadIdx.x & 63u};
+  bool high;
+  const uint32_t cnt = fq_tile_count(W, text, n, t, &high);
+  if (W.lane == 0) {
+    tile_cnt[t] = cnt;
+    if (high) atomicOr(&ctrl->any_high, 1u);
+    if (t == n_tiles - 1) ctrl->ends_nl = text[n - 1] == '\n';
+  }
+}
+
+// Exclusive scan of in[0, n) into out[0, n) and the total into *total, by ONE workgroup (n is a text's tiles, or a
+// batch's records / FQ_REC_WG: tens of thousands at most).  out may be in.
+__global__ __launch_bounds__(FQ_SCAN_WG) void k_fq_scan64(const unsigned long long *in, unsigned long long *out, unsigned long long n,
+                                                          unsigned long long *total) {
+  __shared__ unsigned long long wsum[FQ_SCAN_WG / 64];
+  __shared__ unsigned long long carry_s;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (unsigned long long i0 = 0; i0 < n; i0 += FQ_SCAN_WG) {
+    const unsigned long long i = i0 + threadIdx.x;
+    const unsigned long long v = i < n ? in[i] : 0ull;
+    unsigned long long inc = v;  // inclusive within the wave
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned long long u = __shfl_up(inc, off, 64);
+      if ((int)lane >= off) inc += u;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    unsigned long long before = carry_s;
+    for (uint32_t k = 0; k < w; ++k) before += wsum[k];
+    if (i < n) out[i] = before + inc - v;
+    __syncthreads();
+    if (threadIdx.x == FQ_SCAN_WG - 1) carry_s = before + inc;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *total = carry_s;
+}
+
+// Pass 3.  line_end[L]: the position of the '\n' that ends line L.
+__global__ __launch_bounds__(FQ_WAVES * 64) void k_fq_lines(const uint8_t *__restrict__ text, unsigned long long n, unsigned long long n_tiles,
+                                                            const unsigned long long *__restrict__ tile_base, uint32_t *__restrict__ line_end,
+                                                            unsigned long long n_lines_cap) {
+  const unsigned long long t = (unsigned long long)blockIdx.x * FQ_WAVES + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;
+  const FqWave<64> W{threadIdx.x & 63u};
+  fq_tile_lines(W, text, n, t, tile_base[t], line_end, n_lines_cap);
+}
+
+// Pass 4.  Per record its sequence's start and length, the anomalies that need no look at the bases, and per workgroup
+// the lengths' sum.
+__global__ __launch_bounds__(FQ_REC_WG) void k_fq_records(const uint8_t *__restrict__ text, unsigned long long n, const uint32_t *__restrict__ line_end,
+                                                          unsigned long long n_nl, unsigned long long n_look, unsigned long long first_record,
+                                                          unsigned long long validate_every, FqCtrl *ctrl, uint32_t *__restrict__ seq_start,
+                                                          uint32_t *__restrict__ seq_len, unsigned long long *__restrict__ blk_sum) {
+  __shared__ unsigned long long wsum[FQ_REC_WG / 64];
+  const unsigned long long j = (unsigned long long)blockIdx.x * FQ_REC_WG + threadIdx.x;
+  uint32_t len = 0;
+  if (j < n_look) {
+    uint64_t s;
+    const uint32_t kind = fq_record(text, n, line_end, n_nl, j, fq_validates(first_record + j, validate_every), ctrl->any_high != 0, &s, &len);
+    seq_start[j] = (uint32_t)s;
+    seq_len[j] = len;
+    if (kind) atomicMin(&ctrl->anomaly, (unsigned long long)fq_anomaly_pack(j, kind));
+  }
+  unsigned long long v = len;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long s = 0;
+    for (int k = 0; k < FQ_REC_WG / 64; ++k) s += wsum[k];
+    blk_sum[blockIdx.x] = s;
+  }
+}
+
+// offsets[j] = blk_base[workgroup] + the lengths in front of j within it; offsets[n_look]: the total.  (n_look == 0:
+// one workgroup, which writes offsets[0] = 0.)
+__global__ __launch_bounds__(FQ_REC_WG) void k_fq_offsets(const uint32_t *__restrict__ seq_len, const unsigned long long *__restrict__ blk_base,
+                                                          unsigned long long n_look, unsigned long long *__restrict__ offsets) {
+  __shared__ unsigned long long wsum[FQ_REC_WG / 64];
+  const unsigned long long j = (unsigned long long)blockIdx.x * FQ_REC_WG + threadIdx.x;
+  if (n_look == 0) {
+    if (j == 0) offsets[0] = 0;
+    return;  // (the whole grid)
+  }
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const unsigned long long v = j < n_look ? seq_len[j] : 0u;
+  unsigned long long inc = v;
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long u = __shfl_up(inc, off, 64);
+    if ((int)lane >= off) inc += u;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  unsigned long long before = blk_base[blockIdx.x];
+  for (uint32_t k = 0; k < w; ++k) before += wsum[k];
+  if (j < n_look) {
+    offsets[j] = before + inc - v;
+    if (j == n_look - 1) offsets[n_look] = before + inc;
+  }
+}
+
+// Pass 5.  FQ_COPY_LANES lanes per record copy its sequence and check its bases.
+__global__ __launch_bounds__(256) void k_fq_copy(const uint8_t *__restrict__ text, const uint32_t *__restrict__ seq_start,
+                                                 const uint32_t *__restrict__ seq_len, const unsigned long long *__restrict__ offsets,
+                                                 unsigned long long n_look, uint8_t *__restrict__ bases, unsigned long long bases_cap, FqCtrl *ctrl) {
+  const unsigned long long j = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) / FQ_COPY_LANES;
+  if (j >= n_look) return;
+  const bool bad = fq_copy_sequence<FQ_COPY_LANES>(text, seq_start[j], seq_len[j], bases, offsets[j], bases_cap, threadIdx.x % FQ_COPY_LANES);
+  if (bad) atomicMin(&ctrl->anomaly, (unsigned long long)fq_anomaly_pack(j, FQ_ANOMALY_BASE));
+}
+
+// Pass 6.
+__global__ void k_fq_finish(unsigned long long n, const uint32_t *__restrict__ line_end, unsigned long long n_nl, unsigned long long n_look,
+                            const unsigned long long *__restrict__ offsets, FqCtrl *ctrl) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctrl->n_bases_look = offsets[n_look];
+    ctrl->res = fq_result(n, line_end, n_nl, n_look, (const uint64_t *)offsets, ctrl->anomaly);
+  }
+}
+
+// CRC-32 of the members of a batch's decoded text, one wave each: crc[m] over text[jobs[m].offset, + jobs[m].len).
+struct FqCrcJob {
+  unsigned long long offset;
+  uint32_t len, reserved;
+};
+__global__ __launch_bounds__(FQ_WAVES * 64) void k_crc_members(const uint8_t *__restrict__ text, const FqCrcJob *__restrict__ jobs, uint32_t n_members,
+                                                               uint32_t *__restrict__ crc) {
+  __shared__ uint32_t tab[256];
+  tab[threadIdx.x] = fq_crc_table_entry(threadIdx.x);  // (FQ_WAVES * 64 == 256 threads: an entry each)
+  __syncthreads();
+  const uint32_t m = blockIdx.x * FQ_WAVES + (threadIdx.x >> 6);
+  if (m >= n_members) return;  // (the whole wave)
+  const FqWave<64> W{threadIdx.x & 63u};
+  const FqCrcJob j = jobs[m];
+  const uint32_t raw = W.bit_xor(fq_crc_share(tab, text + j.offset, j.len, W.lane));
+  if (W.lane == 0) crc[m] = fq_crc_condition(raw, j.len);
+}
+static_assert(FQ_WAVES * 64 == 256 && FQ_CRC_SHARES == 64, "k_crc_members: a table entry per thread, a share per lane");
 
 }  // namespace shk

@@ -320,6 +320,11 @@ struct shk_ctx {
   DevBuf xbuf_alt, part_meta_alt;  // the OTHER exchange buffer and cursor block: shk_xchg_scatter_device takes the two in turn
   uint64_t xspill_cap = 0;
   RetainStore retain;             // the reads kept at ingest (off unless shk_retain_reads switched it on)
+  // shk_fastq_parse_device's working set (K_FASTQ): tile counts and bases, the line table, the records' extents, the
+  // control block with its pinned mirror, offsets for a call whose caller brought too few; timing events
+  DevBuf fq_tiles, fq_lines, fq_recs, fq_ctrl, fq_offs;
+  HostBuf fq_hctrl;
+  hipEvent_t fq_ev[4] = {};
   // host counters
   std::vector<uint64_t> lane_reads;
   uint64_t n_reads_read = 0, n_bases_read = 0;
@@ -2381,6 +2386,9 @@ void shk_destroy(shk_ctx *c) {
   c->fh_tot.release();
   for (int i = 0; i < shk_ctx::NST; ++i) c->pk_stage[i].release(), c->nm_stage[i].release(), c->nz_dev[i].release(), c->nz_host[i].release(), c->hp_pk[i].release(), c->hp_nm[i].release();
   c->pk_ascii.release();
+  c->fq_tiles.release(), c->fq_lines.release(), c->fq_recs.release(), c->fq_ctrl.release(), c->fq_offs.release(), c->fq_hctrl.release();
+  for (hipEvent_t e : c->fq_ev)
+    if (e) (void)hipEventDestroy(e);
   dev_free(c->retain.planes, c->retain.planes_alloc);
   dev_free(c->retain.offsets, c->retain.offsets_alloc);
   lap("scratch given back");
@@ -3617,3 +3625,6 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 #include "shk_pcr_run_api.hip.h"
 // the device backend of the BGZF batched route: K_INFLATE behind the front-end's member decoder hook; no context
 #include "shk_inflate_api.hip.h"
+// shk_fastq_parse_device, shk_crc32_members_device, shk_ingest_fastq_files_device: K_FASTQ over decoded text in HBM and
+// the file-to-ingest route built on it and on K_INFLATE
+#include "shk_fastq_api.hip.h"

@@ -2220,6 +2220,10 @@ int shk_fastq_open_device(const char *const *paths, uint32_t n_paths, uint64_t m
                           int device_id, shk_fastq **out) {
   if (!out) return SHK_ERR_BAD_ARG;
   *out = nullptr;
+  if (flags & SHK_FASTQ_DEVICE_PARSE) {  // (a reader hands out host batches)
+    run_error() = "SHK_FASTQ_DEVICE_PARSE is a flag of shk_run_files (shk_ingest_fastq_files_device), not of a reader";
+    return SHK_ERR_BAD_ARG;
+  }
   if (flags & SHK_FASTQ_BGZF_DEVICE) {  // never quietly on the host instead
     const MemberDecoderOps *ops = g_device_decoder.load();
     std::string why = "this build of the front-end has no device decoder";

@@ -76,9 +76,16 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
     }
   }
   shk_fastq *rd = nullptr;
+  // SHK_FASTQ_DEVICE_PARSE: the route that keeps the text on the device is tried first (below); the reader, opened
+  // without the flag, is what reads the input when that route gives up
+  const bool device_parse = (rc->fastq_flags & SHK_FASTQ_DEVICE_PARSE) != 0;
+  if (device_parse && !(rc->fastq_flags & SHK_FASTQ_BGZF_DEVICE)) {
+    g_run_error = "SHK_FASTQ_DEVICE_PARSE needs SHK_FASTQ_BGZF_DEVICE: the text it parses is what the device decoded";
+    return SHK_ERR_BAD_ARG;
+  }
   // (SHK_FASTQ_BGZF_DEVICE decodes on the context's first device)
   const int first_device = rc->n_devices >= 1 && rc->device_ids ? rc->device_ids[0] : rc->device;
-  v = shk_fastq_open_device(rc->inputs, rc->n_inputs, rc->max_reads, rc->validate_every, rc->fastq_flags, first_device, &rd);
+  v = shk_fastq_open_device(rc->inputs, rc->n_inputs, rc->max_reads, rc->validate_every, rc->fastq_flags & ~SHK_FASTQ_DEVICE_PARSE, first_device, &rd);
   if (v != SHK_OK) return v;
   shk_config cfg{};
   cfg.k = rc->k;
@@ -148,9 +155,10 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
   // reader is closed in the background as soon as its last batch is out (close_reader_early).
   std::thread close_th;
   uint64_t nrr = 0, nbr = 0;
+  bool routed = false;  // the device route took the whole input: nrr / nbr are its counts, the reader has read nothing
   auto close_reader_early = [&]() {
     if (!rd) return;
-    shk_fastq_stats(rd, &nrr, &nbr, nullptr, nullptr);
+    if (!routed) shk_fastq_stats(rd, &nrr, &nbr, nullptr, nullptr);
     shk_fastq *r0 = rd;
     rd = nullptr;
     close_th = std::thread([r0, trace, now] {
@@ -179,7 +187,19 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
     if (close_th.joinable()) close_th.join();
     mark("  buffers unpinned, context destroyed, reader closed");
   };
-  if (!alloc_buf(bb2[0], true)) {
+  if (device_parse) {
+    shk_fastq_device_stats ds{};
+    v = shk_ingest_fastq_files_device(ctx, rc->inputs, rc->n_inputs, rc->max_reads, rc->validate_every, &ds);
+    if (v != SHK_OK) {
+      g_run_error = shk_last_error(ctx);
+      cleanup();
+      return v;
+    }
+    routed = ds.gave_up == 0;  // (given up: the context is empty again and the loop below reads the input from its start)
+    if (routed) nrr = ds.n_records, nbr = ds.n_bases;
+    mark(routed ? "device route: decoded, framed, ingested" : "device route: gave up");
+  }
+  if (!routed && !alloc_buf(bb2[0], true)) {
     cleanup();
     g_run_error = "pinned buffer allocation failed";
     return SHK_ERR_NOMEM;
@@ -188,8 +208,8 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
     return ascii ? shk_fastq_next_batch(rd, b.data, cap_bases, b.offs, max_seqs, n)
                  : shk_fastq_next_batch_packed(rd, b.data, b.nmask, cap_bases, b.offs, max_seqs, n);
   };
-  mark("first pinned buffers");
-  for (int cur = 0;; cur ^= 1) {  // any batch size keeps the striping: the engine counts reads itself
+  if (!routed) mark("first pinned buffers");
+  for (int cur = 0; !routed; cur ^= 1) {  // any batch size keeps the striping: the engine counts reads itself
     if (!bb2[cur].data) {  // (the second pair is only allocated when there is a second batch)
       if (!alloc_buf(bb2[cur], true)) {
         cleanup();

@@ -28,6 +28,8 @@ RESERVE_NONE = 0xFFFFFFFF  # shk_config.reserve_cus: every compute unit (include
 FASTQ_GZIP_ALL_MEMBERS = 1  # shk_fastq_open_ex / shk_run_config.fastq_flags (include/shk.h)
 FASTQ_BGZF_BATCH = 2        # BGZF members decoded in batches on host threads …
 FASTQ_BGZF_DEVICE = 4       # … or on the device (both imply every member)
+FASTQ_DEVICE_PARSE = 8      # run_files only, with FASTQ_BGZF_DEVICE: the decoded text stays on the device and is framed there
+FASTQ_NO_ANOMALY = (1 << 64) - 1  # shk_fastq_text_result.anomaly_record: none among the records looked at
 
 
 def _bgzf_flags(bgzf) -> int:
@@ -596,6 +598,22 @@ class _Synth(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _FastqTextParams(C.Structure):  # shk_fastq_text_params
+    _fields_ = [("first_record", C.c_uint64), ("validate_every", C.c_uint64), ("max_records", C.c_uint64),
+                ("last", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _FastqTextResult(C.Structure):  # shk_fastq_text_result
+    _fields_ = [("n_records", C.c_uint64), ("n_bases", C.c_uint64), ("bytes_consumed", C.c_uint64),
+                ("anomaly_record", C.c_uint64), ("anomaly_kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _FastqDeviceStats(C.Structure):  # shk_fastq_device_stats
+    _fields_ = [("n_batches", C.c_uint64), ("n_members", C.c_uint64), ("n_records", C.c_uint64), ("n_bases", C.c_uint64),
+                ("bytes_up", C.c_uint64), ("bytes_down", C.c_uint64), ("kernel_ns", C.c_uint64),
+                ("gave_up", C.c_uint32), ("give_up_reason", C.c_uint32)]
+
+
 # every symbol include/shk.h declares (tests check the .so exports them all)
 ABI_SYMBOLS = [
     "shk_abi_version", "shk_create", "shk_destroy", "shk_reset", "shk_last_error", "shk_ingest_batch",
@@ -607,6 +625,7 @@ ABI_SYMBOLS = [
     "shk_free_pinned", "shk_alloc_device", "shk_free_device", "shk_release_cached_memory", "shk_synth_reads_device",
     "shk_fastq_open", "shk_fastq_open_ex", "shk_fastq_close", "shk_fastq_error", "shk_fastq_next_batch", "shk_fastq_next_batch_packed", "shk_fastq_stats",
     "shk_fastq_open_device", "shk_fastq_member_stats", "shk_bgzf_device_totals",
+    "shk_fastq_parse_device", "shk_crc32_members_device", "shk_fastq_parse_geometry", "shk_ingest_fastq_files_device", "shk_fastq_device_totals",
     "shk_write_histo", "shk_write_final_histo", "shk_write_stats_yaml", "shk_validate_args",
     "shk_run_error", "shk_run_files",
     "shk_xchg_scatter_device", "shk_xchg_absorb", "shk_xchg_spill", "shk_xchg_spill_clear", "shk_insert_device",
@@ -740,6 +759,12 @@ def load_library():
     L.shk_ingest_batch.argtypes = [vp, u32, vp, vp, u64]
     L.shk_ingest_reads.argtypes = [vp, vp, vp, u64]
     L.shk_ingest_reads_device.argtypes = [vp, vp, vp, u64, u64]
+    L.shk_fastq_parse_device.argtypes = [vp, vp, u64, C.POINTER(_FastqTextParams), vp, u64, vp, u64, C.POINTER(_FastqTextResult)]
+    L.shk_crc32_members_device.argtypes = [vp, vp, vp, u32, vp]
+    L.shk_fastq_parse_geometry.argtypes = [C.POINTER(u32)]
+    L.shk_fastq_parse_geometry.restype = None
+    L.shk_ingest_fastq_files_device.argtypes = [vp, C.POINTER(C.c_char_p), u32, u64, u64, C.POINTER(_FastqDeviceStats)]
+    L.shk_fastq_device_totals.argtypes = [C.POINTER(u64)] * 6
     L.shk_insert_counts.argtypes = [vp, u32, vp, vp, u64]
     L.shk_sync.argtypes = [vp]
     L.shk_finalize.argtypes = [vp]
@@ -946,6 +971,41 @@ class KmerEngine:
 
     def ingest_reads_device(self, d_bases: int, d_offsets: int, n_seqs: int, n_bases: int):
         self._check(self._L.shk_ingest_reads_device(self._h, d_bases, d_offsets, n_seqs, n_bases))
+
+    # -- FASTQ text on the device ------------------------------------------
+    def parse_fastq_text(self, d_text: int, n_bytes: int, d_bases: int, bases_cap: int, d_offsets: int, offsets_cap: int,
+                         first_record: int = 0, validate_every: int = 0, max_records: int = 0, last: bool = True) -> dict:
+        """shk_fastq_parse_device: the records of n_bytes of FASTQ text at device pointer d_text (any alignment) framed
+        into d_bases / d_offsets (what ingest_reads_device takes).  A capacity that is too small raises ShkError whose
+        .needed says what the text needs."""
+        p = _FastqTextParams(first_record, validate_every, max_records, 1 if last else 0, 0)
+        r = _FastqTextResult()
+        rc = self._L.shk_fastq_parse_device(self._h, d_text, n_bytes, C.byref(p), d_bases, bases_cap, d_offsets, offsets_cap, C.byref(r))
+        out = {f: int(getattr(r, f)) for f, _ in _FastqTextResult._fields_ if f != "reserved"}
+        if rc != 0:
+            e = ShkError(rc, (self._L.shk_last_error(self._h) or b"").decode("utf-8", "replace"))
+            e.needed = out
+            raise e
+        return out
+
+    def crc32_members(self, d_text: int, d_jobs: int, n: int, d_crc: int):
+        """shk_crc32_members_device: gzip's CRC-32 of n extents of d_text (d_jobs: n × (u64 offset, u32 len, u32 0)),
+        one wave each, into d_crc[n] u32."""
+        self._check(self._L.shk_crc32_members_device(self._h, d_text, d_jobs, n, d_crc))
+
+    def ingest_fastq_files(self, paths, max_reads: int = 0, validate_every: int = 0) -> dict:
+        """shk_ingest_fastq_files_device: bgzip'd FASTQ files into this (empty) engine with the text never leaving the
+        device.  The dict is shk_fastq_device_stats; gave_up != 0: nothing of the files is in the engine (1: it has
+        been reset) and the caller reads them through FastqReader."""
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        st = _FastqDeviceStats()
+        self._check(self._L.shk_ingest_fastq_files_device(self._h, arr, len(paths), max_reads, validate_every, C.byref(st)))
+        return {f: int(getattr(st, f)) for f, _ in _FastqDeviceStats._fields_}
+
+    @staticmethod
+    def fastq_device_totals() -> dict:
+        """shk_fastq_device_totals (process-wide): batches, records, give_ups, bytes_up, bytes_down, kernel_ns."""
+        return fastq_device_totals()
 
     def insert(self, kmers, counts, chunk_id: int = 0):
         """KmerCounts::insert (counting.rs:152-154)."""
@@ -2126,6 +2186,20 @@ def write_stats_yaml(path: str, **f):
         raise ShkError(rc, "shk_write_stats_yaml failed")
 
 
+def fastq_parse_geometry() -> int:
+    """The bytes of text one wave takes in the framing passes (shk_fastq_parse_geometry)."""
+    t = C.c_uint32(0)
+    load_library().shk_fastq_parse_geometry(C.byref(t))
+    return int(t.value)
+
+
+def fastq_device_totals() -> dict:
+    """shk_fastq_device_totals: process-wide, since the library was loaded."""
+    v = [C.c_uint64(0) for _ in range(6)]
+    load_library().shk_fastq_device_totals(*[C.byref(x) for x in v])
+    return dict(zip(("batches", "records", "give_ups", "bytes_up", "bytes_down", "kernel_ns"), (int(x.value) for x in v)))
+
+
 def validate_args(k: int, histo_max: int, sample):
     """cli.rs:659-673 + 645-652; raises ShkError with the reference's message."""
     L = load_front_library()
@@ -2137,13 +2211,17 @@ def validate_args(k: int, histo_max: int, sample):
 def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", histo_max: int = 10000,
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
               command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
-              bgzf=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
+              bgzf=None, parse=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
     """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
     strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
     tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
     max_primer_kmers, high_coverage_ratio, tip_coverage_fraction), which overwrite every gene's values.
     device_ids: run on one multi-device context (shk_run_config.n_devices).  gzip_all_members, bgzf: see FastqReader
-    (bgzf="device" decodes on the context's first device)."""
+    (bgzf="device" decodes on the context's first device).  parse="device" (with bgzf="device" only): the decoded text
+    stays on the device and is framed there (SHK_FASTQ_DEVICE_PARSE); a file the route gives up on is read the
+    bgzf="device" way from its start."""
+    if parse not in (None, "device"):
+        raise ValueError(f"parse must be None or 'device', not {parse!r}")
     known = ("max_dfs_states", "max_paths_per_pair", "max_node_visits", "max_primer_kmers", "high_coverage_ratio", "tip_coverage_fraction")
     if set(tuning) - set(known):
         raise TypeError(f"unexpected arguments {sorted(set(tuning) - set(known))}")
@@ -2153,7 +2231,7 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
                      histo_max=histo_max, max_reads=max_reads, validate_every=validate_every,
                      sample=None if sample is None else sample.encode(), outdir=os.fsencode(outdir),
                      command=command.encode(), version=None, table_capacity_hint=capacity_hint,
-                     batch_reads=batch_reads, batch_bases=batch_bases, fastq_flags=(FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0) | _bgzf_flags(bgzf))
+                     batch_reads=batch_reads, batch_bases=batch_bases, fastq_flags=(FASTQ_GZIP_ALL_MEMBERS if gzip_all_members else 0) | _bgzf_flags(bgzf) | (FASTQ_DEVICE_PARSE if parse else 0))
     if device_ids is not None:
         ids = (C.c_int32 * len(device_ids))(*device_ids)
         cfg.n_devices = len(device_ids)

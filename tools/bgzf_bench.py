@@ -1,15 +1,20 @@
 #!/usr/bin/env python
-"""bgzip'd FASTQ, file → histograms, over the three routes that read every member:
-  sequential   run_files(gzip_all_members=True): one thread, a member after the other — the yardstick
-  host         run_files(bgzf="host"): BGZF members in batches on the reader's threads
-  device       run_files(bgzf="device"): K_INFLATE, one wave per member
+"""bgzip'd FASTQ, file → histograms, over the four routes that read every member:
+  sequential    run_files(gzip_all_members=True): one thread, a member after the other — the yardstick
+  host          run_files(bgzf="host"): BGZF members in batches on the reader's threads
+  device        run_files(bgzf="device"): K_INFLATE, one wave per member; the text comes back to the host parser
+  device_parse  run_files(bgzf="device", parse="device"): K_INFLATE, then CRC-32 and the FASTQ framing on the device
+                (K_FASTQ); the text stays in device memory
 
 Writes N synthetic reads of L bases as FASTQ, bgzips the text itself (level 6, 65280-byte members) once, outside the
-timed part, checks that the three routes write the same histograms, then times them alternately: SAMPLES samples each
+timed part, checks that the four routes write the same histograms, then times them alternately: SAMPLES samples each
 after one warm-up, median and range in Gbases/s.  For the device route also the kernel's own time and members per
-second (hipEvents, shk_bgzf_device_totals) and the bytes moved each way.
+second (hipEvents, shk_bgzf_device_totals) and the bytes moved each way; for the device_parse route the bytes moved
+each way per run and the CRC-32 and framing kernels' time (shk_fastq_device_totals), and that it never gave up.
+Beside the protocol (--alone N, default 10): each batched route N times in a row on its own, and the device_parse
+route over batch budgets from 8 MiB to one batch for the whole file.
 
-  python tools/bgzf_bench.py [--reads 1000000] [--length 150] [--samples 5] [--out profiles/bgzf_device.json]
+  python tools/bgzf_bench.py [--reads 1000000] [--length 150] [--samples 5] [--out profiles/bgzf_device_parse.json]
 """
 import argparse
 import ctypes as C
@@ -100,11 +105,13 @@ def main():
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--length", type=int, default=150)
     ap.add_argument("--samples", type=int, default=5)
+    ap.add_argument("--alone", type=int, default=10, help="runs in a row of each batched route on its own, after the protocol (0: none, and no batch sweep)")
     ap.add_argument("--k", type=int, default=21)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_device.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_device_parse.json"))
     a = ap.parse_args()
     L = sa.engine.load_library()
-    routes = {"sequential": dict(gzip_all_members=True), "host": dict(bgzf="host"), "device": dict(bgzf="device")}
+    routes = {"sequential": dict(gzip_all_members=True), "host": dict(bgzf="host"), "device": dict(bgzf="device"),
+              "device_parse": dict(bgzf="device", parse="device")}
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "reads.fastq.gz")
         t0 = time.time()
@@ -128,12 +135,32 @@ def main():
         n_bases = warm["sequential"][1]["n_bases_read"]
         assert warm["sequential"][1]["n_reads_read"] == a.reads
         times = {r: [] for r in routes}
-        dev0 = device_totals(L)
+        assert sa.fastq_device_totals()["give_ups"] == 0, "the device_parse route gave up in its warm-up: that run was the device route's"
+        dev0, fq0 = device_totals(L), sa.fastq_device_totals()
         for _ in range(a.samples):
-            for r in routes:   # (alternating: drift of the machine lands on all three alike)
+            for r in routes:   # (alternating: drift of the machine lands on all of them alike)
                 times[r].append(run(r)[0])
                 print(f"  {r:10s} {n_bases / times[r][-1] / 1e9:.3f} Gbases/s", flush=True)
-        dev1 = device_totals(L)
+        dev1, fq1 = device_totals(L), sa.fastq_device_totals()
+        # beside the protocol: each batched route on its own, --alone runs in a row (no other route in between) …
+        alone = {}
+        for r in ("host", "device", "device_parse"):
+            run(r)
+            alone[r] = [run(r)[0] for _ in range(a.alone)]
+            print(f"  {r:12s} alone: median {statistics.median(alone[r]) * 1e3:.1f} ms", flush=True)
+        # … and the device_parse route over batch budgets (SHK_BGZF_BATCH_KB; unset: the default of 128 MiB)
+        sweep = {}
+        for kb in (8192, 16384, 32768, 65536, 0, 1048576) if a.alone else ():
+            if kb:
+                os.environ["SHK_BGZF_BATCH_KB"] = str(kb)
+            else:
+                os.environ.pop("SHK_BGZF_BATCH_KB", None)
+            run("device_parse")
+            f0 = sa.fastq_device_totals()
+            sweep[str(kb) if kb else "default"] = {"seconds": [run("device_parse")[0] for _ in range(5)],
+                                                   "batches_per_run": (sa.fastq_device_totals()["batches"] - f0["batches"]) // 5}
+        os.environ.pop("SHK_BGZF_BATCH_KB", None)
+        assert sa.fastq_device_totals()["give_ups"] == 0
     members, kernel_ns, up, down = [b - a_ for a_, b in zip(dev0, dev1)]
     res = {"workload": {"reads": a.reads, "read_length": a.length, "k": a.k, "members": n_members, "text_bytes": n_text,
                         "bases": n_bases, "level": 6, "member_payload": 65280, "cpus": usable_cpus()},
@@ -146,12 +173,22 @@ def main():
                             "members_per_second": members / (kernel_ns / 1e9) if kernel_ns else None,
                             "text_gbytes_per_second": n_text * a.samples / kernel_ns if kernel_ns else None,
                             "bytes_up_per_run": up // max(a.samples, 1), "bytes_down_per_run": down // max(a.samples, 1)}
+    fq = {f: fq1[f] - fq0[f] for f in fq1}
+    assert fq["give_ups"] == 0 and fq["records"] == a.reads * a.samples, fq   # every record of every run framed on the device
+    n = max(a.samples, 1)
+    res["device_parse"] = {"batches_per_run": fq["batches"] // n, "records_per_run": fq["records"] // n, "give_ups": fq["give_ups"],
+                           "bytes_up_per_run": fq["bytes_up"] // n, "bytes_down_per_run": fq["bytes_down"] // n,
+                           "crc_and_framing_kernel_seconds_per_run": fq["kernel_ns"] / 1e9 / n}
+    res["alone"] = {r: {"seconds": t, "seconds_median": statistics.median(t), "gbases_per_s_median": n_bases / statistics.median(t) / 1e9}
+                    for r, t in alone.items() if t}
+    res["device_parse_batch_kb_sweep"] = {kb: dict(v, seconds_median=statistics.median(v["seconds"])) for kb, v in sweep.items()}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res["routes"], indent=1))
     print(json.dumps(res["device_kernel"], indent=1))
+    print(json.dumps(res["device_parse"], indent=1))
 
 
 if __name__ == "__main__":
