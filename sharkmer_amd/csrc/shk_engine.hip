@@ -194,21 +194,18 @@ static void host_free(void *p, size_t bytes) {
 
 struct DevBuf {  // grow-only device scratch
   void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
+  size_t cap = 0;  // (what the allocator handed out: the cache may give a larger block than was asked)
+  hipError_t take(size_t bytes, size_t ask) {
     if (bytes <= cap) return hipSuccess;
     release();
-    hipError_t e = dev_alloc(&p, bytes + bytes / 8 + 4096, &cap);
+    hipError_t e = dev_alloc(&p, ask, &cap);
     if (e != hipSuccess) p = nullptr, cap = 0;
     return e;
   }
-  hipError_t ensure_exact(size_t bytes) {  // (a buffer that is planned once from the free memory: no eighth on top)
-    if (bytes <= cap) return hipSuccess;
-    release();
-    hipError_t e = dev_alloc(&p, bytes + 4096, &cap);
-    if (e != hipSuccess) p = nullptr, cap = 0;
-    return e;
-  }
+  hipError_t ensure(size_t bytes) { return take(bytes, bytes + bytes / 8 + 4096); }
+  hipError_t ensure_exact(size_t bytes) { return take(bytes, bytes + 4096); }  // (planned once from the free memory: no eighth on top)
+  // sizes asked in whole steps, for blocks that come and go: the cache matches sizes.  (A grow goes through dev_free's device-wide wait.)
+  hipError_t ensure_step(size_t bytes, size_t step) { return take(bytes, (bytes + step - 1) / step * step); }
   void release() {
     dev_free(p, cap);
     p = nullptr;
@@ -219,13 +216,15 @@ struct DevBuf {  // grow-only device scratch
 struct HostBuf {  // grow-only pinned host scratch
   void *p = nullptr;
   size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
+  hipError_t take(size_t bytes, size_t ask) {
     if (bytes <= cap) return hipSuccess;
     release();
-    hipError_t e = host_alloc(&p, bytes + bytes / 8 + 4096, &cap);
+    hipError_t e = host_alloc(&p, ask, &cap);
     if (e != hipSuccess) p = nullptr, cap = 0;
     return e;
   }
+  hipError_t ensure(size_t bytes) { return take(bytes, bytes + bytes / 8 + 4096); }
+  hipError_t ensure_step(size_t bytes, size_t step) { return take(bytes, (bytes + step - 1) / step * step); }  // (as DevBuf's)
   void release() {
     host_free(p, cap);
     p = nullptr;
@@ -3623,6 +3622,8 @@ int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_rea
 #include "shk_products_api.hip.h"
 // shk_pcr_run: do_pcr for a panel, the stage calls above chained with the reference's control flow; no kernel of its own
 #include "shk_pcr_run_api.hip.h"
+// the decode stage under the two BGZF files below: a slot's stream and blocks, a batch laid out, uploaded and inflated
+#include "shk_bgzf_stage.hip.h"
 // the device backend of the BGZF batched route: K_INFLATE behind the front-end's member decoder hook; no context
 #include "shk_inflate_api.hip.h"
 // shk_fastq_parse_device, shk_crc32_members_device, shk_ingest_fastq_files_device: K_FASTQ over decoded text in HBM and

@@ -31,10 +31,12 @@ struct FqOut {
 };
 
 // The passes over d_text on the context's stream; returns once the result words are back.  get_out is called between
-// the two halves, with the number of records that will be looked at.
+// the two halves, with the number of records that will be looked at.  *down and *kernel_ns: the bytes this call brought
+// down and its kernels' time, also where it fails — added to fq_totals() here, to a caller's own statistics by the caller.
 template <typename GetOut>
 static int fq_parse_core(shk_ctx *c, const uint8_t *d_text, uint64_t n, const shk_fastq_text_params &p, GetOut get_out, shk_fastq_text_result *res,
-                         uint64_t *n_look_out, bool *ends_nl_out = nullptr) {
+                         uint64_t *n_look_out, uint64_t *down, uint64_t *kernel_ns, bool *ends_nl_out = nullptr) {
+  *down = *kernel_ns = 0;
   if (n > FQ_TEXT_MAX) return fail(c, SHK_ERR_BAD_ARG, "shk_fastq_parse_device takes at most %llu bytes of text", (unsigned long long)FQ_TEXT_MAX);
   hipStream_t st = c->stream;
   for (hipEvent_t &e : c->fq_ev)
@@ -57,6 +59,7 @@ static int fq_parse_core(shk_ctx *c, const uint8_t *d_text, uint64_t n, const sh
   HIPC(c, hipMemcpyAsync(h, ctrl, offsetof(FqCtrl, n_bases_look), hipMemcpyDeviceToHost, st));
   HIPC(c, hipStreamSynchronize(st));
   fq_totals().down += offsetof(FqCtrl, n_bases_look);
+  *down = offsetof(FqCtrl, n_bases_look);
   const uint64_t n_nl = h->n_nl;
   const uint64_t n_lines = fq_n_lines(n, n_nl, p.last != 0, h->ends_nl != 0);
   uint64_t n_look = n_lines / 4;
@@ -90,9 +93,10 @@ static int fq_parse_core(shk_ctx *c, const uint8_t *d_text, uint64_t n, const sh
   HIPC(c, hipMemcpyAsync(&h->res, &ctrl->res, sizeof(FqResultWords), hipMemcpyDeviceToHost, st));
   HIPC(c, hipStreamSynchronize(st));
   fq_totals().down += sizeof(FqResultWords);
+  *down += sizeof(FqResultWords);
   float ms0 = 0, ms1 = 0;
   if (hipEventElapsedTime(&ms0, c->fq_ev[0], c->fq_ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, c->fq_ev[2], c->fq_ev[3]) == hipSuccess)
-    fq_totals().kernel_ns += (uint64_t)(((double)ms0 + (double)ms1) * 1e6);
+    fq_totals().kernel_ns += *kernel_ns = (uint64_t)(((double)ms0 + (double)ms1) * 1e6);
   else
     (void)hipGetLastError();
   memcpy(res, &h->res, sizeof *res);
@@ -110,116 +114,183 @@ struct MappedFile {
   }
 };
 
+// The route's run over its files: two slots, and the batches of all files as one sequence — the next one is planned and
+// queued before this one is waited for.  Each step answers a give-up reason, 0: go on.
 struct FastqRoute {
-  struct Slot {
-    hipStream_t st = nullptr;
-    hipEvent_t k0 = nullptr, k1 = nullptr, passed = nullptr;  // round the CRC kernel; the engine stream behind this slot's ingest
+  struct Slot : DecodeSlot {  // up: [inflate jobs | crc jobs | compressed bytes | pad]; down: [n statuses | n crcs], 8 bytes per member and no more
+    hipEvent_t passed = nullptr;  // the engine stream behind this slot's ingest (k0, k1: round the CRC kernel)
     bool passed_set = false;
-    // up: [inflate jobs | crc jobs | compressed bytes | pad]; down: [n statuses | n crcs], 8 bytes per member and no more
-    uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr, *d_text = nullptr, *d_bases = nullptr, *d_offs = nullptr;
-    size_t h_in_cap = 0, d_in_cap = 0, h_out_cap = 0, d_out_cap = 0, d_text_cap = 0, d_bases_cap = 0, d_offs_cap = 0;
-    std::vector<shk::BgzfMember> ms;
-    uint64_t out_bytes = 0;
-    bool live = false, last_of_file = false;
+    DevBuf d_text, d_bases, d_offs;
+    shk::BgzfBatch b;
+    bool last_of_file = false;
+    ~Slot() {  // (the caller has waited for the engine stream where it had been given any of these)
+      if (st) (void)hipStreamSynchronize(st);
+      d_text.release();
+      d_bases.release();
+      d_offs.release();
+      if (passed) (void)hipEventDestroy(passed);
+    }
   } slot[2];
-  bool grow(uint8_t **p, size_t *cap, size_t need, bool pinned) {  // (as InflateDecoder::grow: steps of 4 MiB, the block cache matches sizes)
-    if (*cap >= need) return true;
-    if (*p) pinned ? host_free(*p, *cap) : dev_free(*p, *cap);
-    *p = nullptr;
-    *cap = 0;
-    const size_t ask = (need + (((size_t)4 << 20) - 1)) & ~(((size_t)4 << 20) - 1);
-    size_t got = 0;
-    void *q = nullptr;
-    if ((pinned ? host_alloc(&q, ask, &got) : dev_alloc(&q, ask, &got)) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    *p = (uint8_t *)q;
-    *cap = ask;
-    return true;
+  shk_ctx *c;
+  const std::vector<MappedFile> &files;
+  uint64_t budget, max_reads, validate_every;
+  shk_fastq_device_stats *stats;
+  uint32_t f_next = 0;
+  const uint8_t *p_next;
+  bool input_done = false, reached_max = false;
+  uint64_t carry = 0;  // bytes of text in front of the current slot's own, already in its carry room
+  uint64_t n_reads = 0, n_bases = 0;
+
+  static uint32_t own(hipError_t e) {  // a HIP call of the route's own: 0, or the reason with the error taken off
+    if (e == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return SHK_FASTQ_GIVEUP_OWN;
   }
-  bool open() {
+  uint32_t open() {
     for (Slot &s : slot)
-      if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s.k0) != hipSuccess || hipEventCreate(&s.k1) != hipSuccess ||
-          hipEventCreateWithFlags(&s.passed, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
-    return true;
+      if (!s.open() || own(hipEventCreateWithFlags(&s.passed, hipEventDisableTiming))) return SHK_FASTQ_GIVEUP_OWN;
+    return 0;
   }
-  ~FastqRoute() {  // (the caller has waited for the engine stream where it had been given any of these)
-    for (Slot &s : slot) {
-      if (s.st) (void)hipStreamSynchronize(s.st);
-      host_free(s.h_in, s.h_in_cap);
-      host_free(s.h_out, s.h_out_cap);
-      dev_free(s.d_in, s.d_in_cap);
-      dev_free(s.d_out, s.d_out_cap);
-      dev_free(s.d_text, s.d_text_cap);
-      dev_free(s.d_bases, s.d_bases_cap);
-      dev_free(s.d_offs, s.d_offs_cap);
-      if (s.k0) (void)hipEventDestroy(s.k0);
-      if (s.k1) (void)hipEventDestroy(s.k1);
-      if (s.passed) (void)hipEventDestroy(s.passed);
-      if (s.st) (void)hipStreamDestroy(s.st);
+
+  // The batch feed: the next batch of the next file into s — upload, K_INFLATE, the CRCs, statuses and CRCs down, queued
+  // on the slot's stream behind the engine stream's last use of the slot.  At the input's end: input_done, nothing queued.
+  uint32_t feed(Slot &s) {
+    while (f_next < files.size() && p_next == files[f_next].p + files[f_next].n)
+      if (++f_next < files.size()) p_next = files[f_next].p;
+    if (f_next >= files.size()) {
+      input_done = true;
+      return 0;
     }
+    const uint8_t *file_end = files[f_next].p + files[f_next].n;
+    if (!shk::bgzf_plan_batch(p_next, file_end, budget, &s.b)) return SHK_FASTQ_GIVEUP_MEMBER;
+    s.last_of_file = s.b.end == file_end;
+    const uint32_t n = (uint32_t)s.b.ms.size();
+    const size_t down = (size_t)n * 8;
+    if (!s.ensure_down(down) || own(s.d_text.ensure_step(FQ_CARRY_ROOM + s.b.out_bytes + 16, STAGE_STEP))) return SHK_FASTQ_GIVEUP_OWN;
+    uint8_t *text = (uint8_t *)s.d_text.p + FQ_CARRY_ROOM;
+    uint32_t *d_status = (uint32_t *)s.d_down.p;
+    // (the ingest that read this slot's buffers last, and the carry copied out of it)
+    if (s.passed_set && hipStreamWaitEvent(s.st, s.passed, 0) != hipSuccess) {
+      s.drain();
+      return SHK_FASTQ_GIVEUP_OWN;
+    }
+    auto crc_jobs = [&](uint8_t *h) {
+      for (uint32_t i = 0; i < n; ++i) ((FqCrcJob *)h)[i] = FqCrcJob{s.b.jobs[i].out_offset, s.b.jobs[i].out_len, 0};
+    };
+    const uint8_t *d_cj = nullptr;
+    const size_t up = stage_queue_inflate(s, s.b.begin, (size_t)(s.b.end - s.b.begin), s.b.jobs.data(), n, s.b.out_bytes, stage_round256((size_t)n * sizeof(FqCrcJob)),
+                                          crc_jobs, &d_cj, text, d_status, down, false);  // (0xFF: INFC_NOT_RUN; no CRC yet)
+    if (!up) return SHK_FASTQ_GIVEUP_OWN;
+    bool ok = hipEventRecord(s.k0, s.st) == hipSuccess;
+    if (ok) {
+      k_crc_members<<<dim3((n + FQ_WAVES - 1) / FQ_WAVES), dim3(FQ_WAVES * 64), 0, s.st>>>(text, (const FqCrcJob *)d_cj, n, d_status + n);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipEventRecord(s.k1, s.st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(s.h_down.p, d_status, down, hipMemcpyDeviceToHost, s.st) == hipSuccess;
+    if (!ok) {
+      s.drain();
+      return SHK_FASTQ_GIVEUP_OWN;
+    }
+    s.queued = true;
+    p_next = s.b.end;
+    stats->bytes_up += up;
+    stats->bytes_down += down;  // (exactly what the copy above brings down)
+    stats->n_members += n;
+    stats->n_batches += 1;
+    return 0;
+  }
+
+  // The slot's stream waited for; every member's status and CRC-32.
+  uint32_t wait_and_check(Slot &s) {
+    s.queued = false;
+    if (own(hipStreamSynchronize(s.st))) return SHK_FASTQ_GIVEUP_OWN;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, s.k0, s.k1) == hipSuccess) {
+      stats->kernel_ns += (uint64_t)((double)ms * 1e6);
+      fq_totals().kernel_ns += (uint64_t)((double)ms * 1e6);
+    }
+    const uint32_t n = (uint32_t)s.b.ms.size();
+    const uint32_t *status = (const uint32_t *)s.h_down.p, *crc = status + n;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (status[i] != INFC_OK) return SHK_FASTQ_GIVEUP_DECODE;
+      if (crc[i] != s.b.ms[i].crc) return SHK_FASTQ_GIVEUP_CRC;
+    }
+    return 0;
+  }
+
+  // The framing over carry + text and the ingest, on the engine stream (the slot's stream has been waited for), and the
+  // text behind the last record to the front of nx's.
+  uint32_t frame_ingest_carry(Slot &s, Slot &nx) {
+    const uint64_t n_text = carry + s.b.out_bytes;
+    const uint8_t *text = (const uint8_t *)s.d_text.p + FQ_CARRY_ROOM - carry;
+    shk_fastq_text_params p{};
+    p.first_record = n_reads;
+    p.validate_every = validate_every;
+    p.max_records = max_reads ? max_reads - n_reads : 0;
+    p.last = s.last_of_file;
+    auto get_out = [&](uint64_t n_look, FqOut *o) -> int {
+      if (own(s.d_bases.ensure_step(n_text + 64, STAGE_STEP)) || own(s.d_offs.ensure_step((n_look + 1) * 8, STAGE_STEP))) return SHK_ERR_NOMEM;
+      *o = FqOut{(uint8_t *)s.d_bases.p, n_text, (uint64_t *)s.d_offs.p};  // (the sequences are part of the text: never more bytes than it has)
+      return SHK_OK;
+    };
+    shk_fastq_text_result r{};
+    uint64_t n_look = 0;
+    uint64_t down = 0, ns = 0;
+    bool ends_nl = false;
+    const int prc = fq_parse_core(c, text, n_text, p, get_out, &r, &n_look, &down, &ns, &ends_nl);
+    stats->bytes_down += down;
+    stats->kernel_ns += ns;
+    if (prc != SHK_OK) return SHK_FASTQ_GIVEUP_OWN;
+    if (r.anomaly_record != FQ_NO_ANOMALY) return SHK_FASTQ_GIVEUP_ANOMALY;
+    // a file whose last line is not terminated ends inside a record, or may: the host decides
+    if (s.last_of_file && n_text && !ends_nl) return SHK_FASTQ_GIVEUP_TEXT_LEFT;
+    if (r.n_records && shk_ingest_reads_device(c, s.d_bases.p, s.d_offs.p, r.n_records, r.n_bases) != SHK_OK) return SHK_FASTQ_GIVEUP_OWN;
+    n_reads += r.n_records;
+    n_bases += r.n_bases;
+    reached_max = max_reads && n_reads >= max_reads;
+    if (reached_max) return 0;
+    const uint64_t left = n_text - r.bytes_consumed;
+    if (s.last_of_file) {
+      carry = 0;
+      return left ? SHK_FASTQ_GIVEUP_TEXT_LEFT : 0;
+    }
+    if (left > FQ_CARRY_ROOM || !nx.queued) return SHK_FASTQ_GIVEUP_OWN;  // (a batch that does not end its file has one behind it)
+    if (left && own(hipMemcpyAsync((uint8_t *)nx.d_text.p + FQ_CARRY_ROOM - left, text + r.bytes_consumed, left, hipMemcpyDeviceToDevice, c->stream)))
+      return SHK_FASTQ_GIVEUP_OWN;
+    carry = left;
+    return 0;
+  }
+
+  // The hand-back: this slot's buffers are free again once the engine stream has passed the ingest (and the copy of the carry).
+  uint32_t hand_back(Slot &s) {
+    if (own(hipEventRecord(s.passed, c->stream))) return SHK_FASTQ_GIVEUP_OWN;
+    s.passed_set = true;
+    return 0;
   }
 };
 
-// Upload, K_INFLATE, the CRCs, statuses and CRCs down: queued on the slot's stream behind the engine stream's last use
-// of the slot.  false: a failure of the route's own.
-static bool fq_route_submit(FastqRoute &R, FastqRoute::Slot &s, const uint8_t *from, const uint8_t *end, shk_fastq_device_stats *stats) {
-  const uint32_t n = (uint32_t)s.ms.size();
-  const size_t comp_len = (size_t)(end - from);
-  const size_t jobs_bytes = ((size_t)n * sizeof(InflateJob) + 255) & ~(size_t)255, cjobs_bytes = ((size_t)n * sizeof(FqCrcJob) + 255) & ~(size_t)255;
-  const size_t up = jobs_bytes + cjobs_bytes + ((comp_len + 3) & ~(size_t)3) + INFLATE_PAD, down = (size_t)n * 8;
-  uint64_t out_bytes = 0;
-  for (const shk::BgzfMember &x : s.ms) out_bytes += x.isize;
-  s.out_bytes = out_bytes;
-  if (!R.grow(&s.h_in, &s.h_in_cap, up, true) || !R.grow(&s.d_in, &s.d_in_cap, up, false) || !R.grow(&s.h_out, &s.h_out_cap, down, true) ||
-      !R.grow(&s.d_out, &s.d_out_cap, down, false) || !R.grow(&s.d_text, &s.d_text_cap, FQ_CARRY_ROOM + out_bytes + 16, false))
-    return false;
-  InflateJob *ij = (InflateJob *)s.h_in;
-  FqCrcJob *cj = (FqCrcJob *)(s.h_in + jobs_bytes);
-  uint64_t at = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const shk::BgzfMember &x = s.ms[i];
-    // every job inside the batch: the kernels read and write what the jobs say (bgzf_scan has held body and ISIZE to 65536)
-    const uint64_t in_off = (uint64_t)(x.header - from) + x.body_off;
-    if (x.body_len > INFC_MEMBER_MAX || x.isize > INFC_MEMBER_MAX || in_off + x.body_len > comp_len) return false;
-    ij[i] = InflateJob{in_off, at, x.body_len, x.isize};
-    cj[i] = FqCrcJob{at, x.isize, 0};
-    at += x.isize;
+// Maps the files; every one a regular, non-empty file whose first member is a BGZF one.  0, or NOT_ELIGIBLE.
+static uint32_t fq_route_map(const char *const *paths, uint32_t n_paths, std::vector<MappedFile> *files) {
+  files->resize(n_paths);
+  for (uint32_t f = 0; f < n_paths; ++f) {
+    struct stat sb;
+    const int fd = paths[f] ? open(paths[f], O_RDONLY | O_CLOEXEC) : -1;
+    if (fd < 0) return SHK_FASTQ_GIVEUP_NOT_ELIGIBLE;
+    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size <= 0) {
+      close(fd);
+      return SHK_FASTQ_GIVEUP_NOT_ELIGIBLE;
+    }
+    void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) return SHK_FASTQ_GIVEUP_NOT_ELIGIBLE;
+    MappedFile &mf = (*files)[f];
+    mf.p = (const uint8_t *)m;
+    mf.n = (size_t)sb.st_size;
+    std::vector<shk::BgzfMember> first;
+    if (shk::bgzf_scan(mf.p, mf.p + mf.n, 0, &first) == mf.p) return SHK_FASTQ_GIVEUP_NOT_ELIGIBLE;
   }
-  memcpy(s.h_in + jobs_bytes + cjobs_bytes, from, comp_len);
-  memset(s.h_in + jobs_bytes + cjobs_bytes + comp_len, 0, up - jobs_bytes - cjobs_bytes - comp_len);
-  uint8_t *text = s.d_text + FQ_CARRY_ROOM;
-  bool ok = true;
-  if (s.passed_set) ok = hipStreamWaitEvent(s.st, s.passed, 0) == hipSuccess;  // (the ingest that read this slot's buffers last, and the carry copied out of it)
-  ok = ok && hipMemcpyAsync(s.d_in, s.h_in, up, hipMemcpyHostToDevice, s.st) == hipSuccess;
-  ok = ok && hipMemsetAsync(s.d_out, 0xFF, down, s.st) == hipSuccess;  // INFC_NOT_RUN; no CRC yet
-  if (ok) {
-    k_inflate_members<<<dim3((n + INFLATE_WAVES - 1) / INFLATE_WAVES), dim3(INFLATE_WAVES * 64), 0, s.st>>>(s.d_in + jobs_bytes + cjobs_bytes, (const InflateJob *)s.d_in, n,
-                                                                                                        text, (uint32_t *)s.d_out);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = ok && hipEventRecord(s.k0, s.st) == hipSuccess;
-  if (ok) {
-    k_crc_members<<<dim3((n + FQ_WAVES - 1) / FQ_WAVES), dim3(FQ_WAVES * 64), 0, s.st>>>(text, (const FqCrcJob *)(s.d_in + jobs_bytes), n, (uint32_t *)s.d_out + n);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = ok && hipEventRecord(s.k1, s.st) == hipSuccess;
-  ok = ok && hipMemcpyAsync(s.h_out, s.d_out, down, hipMemcpyDeviceToHost, s.st) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(s.st);
-    return false;
-  }
-  s.live = true;
-  stats->bytes_up += up;
-  stats->bytes_down += down;  // (exactly what the copy above brings down)
-  stats->n_members += n;
-  stats->n_batches += 1;
-  return true;
+  return 0;
 }
 
 }  // namespace
@@ -258,7 +329,8 @@ int shk_fastq_parse_device(shk_ctx *c, const void *d_text, uint64_t n_bytes, con
     return SHK_OK;
   };
   uint64_t n_look = 0;
-  SHK_TRY(fq_parse_core(c, (const uint8_t *)d_text, n_bytes, *params, get_out, out, &n_look));
+  uint64_t down = 0, ns = 0;
+  SHK_TRY(fq_parse_core(c, (const uint8_t *)d_text, n_bytes, *params, get_out, out, &n_look, &down, &ns));
   fq_totals().records += out->n_records;
   if (short_offsets) {
     const uint64_t need = out->n_records;
@@ -300,162 +372,29 @@ int shk_ingest_fastq_files_device(shk_ctx *c, const char *const *paths, uint32_t
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   if (c->n_reads_read || c->n_bases_read || c->n_inserted || c->retain.n_reads)
     return fail(c, SHK_ERR_STATE, "shk_ingest_fastq_files_device: the context holds reads already; the route starts on an empty one (shk_create or shk_reset)");
-  std::vector<MappedFile> files(n_paths);
-  for (uint32_t f = 0; f < n_paths; ++f) {
-    struct stat sb;
-    const int fd = paths[f] ? open(paths[f], O_RDONLY | O_CLOEXEC) : -1;
-    if (fd < 0) return not_eligible();
-    if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size <= 0) {
-      close(fd);
-      return not_eligible();
-    }
-    void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-    close(fd);
-    if (m == MAP_FAILED) return not_eligible();
-    files[f].p = (const uint8_t *)m;
-    files[f].n = (size_t)sb.st_size;
-    std::vector<shk::BgzfMember> first;
-    if (shk::bgzf_scan(files[f].p, files[f].p + files[f].n, 0, &first) == files[f].p) return not_eligible();
-  }
+  std::vector<MappedFile> files;
+  if (fq_route_map(paths, n_paths, &files)) return not_eligible();
   HIPC(c, hipSetDevice(c->cfg.device));
-  const uint64_t budget = [] {
-    const char *e = getenv("SHK_BGZF_BATCH_KB");  // (the BGZF routes' test hook: batch borders in tiny files)
-    const uint64_t b = e ? std::max<uint64_t>(1, (uint64_t)atoll(e)) << 10 : (uint64_t)128 << 20;
-    return std::min<uint64_t>(b, (uint64_t)1 << 30);
-  }();
+  const uint64_t budget = std::min<uint64_t>(shk::bgzf_batch_budget((uint64_t)128 << 20), (uint64_t)1 << 30);
   uint32_t reason = 0;
   uint64_t n_reads = 0, n_bases = 0;
   {
-    FastqRoute R;
-    if (!R.open()) reason = SHK_FASTQ_GIVEUP_OWN;
-    // the batches of all files as one sequence: the next one is scanned and submitted before this one is waited for
-    uint32_t f_next = 0;
-    const uint8_t *p_next = files[0].p;
-    bool input_done = false;
-    auto submit_next = [&](FastqRoute::Slot &s) {  // false with reason == 0: the input's end
-      while (f_next < n_paths && p_next == files[f_next].p + files[f_next].n) {
-        ++f_next;
-        if (f_next < n_paths) p_next = files[f_next].p;
-      }
-      if (f_next >= n_paths) {
-        input_done = true;
-        return false;
-      }
-      const uint8_t *file_end = files[f_next].p + files[f_next].n;
-      s.ms.clear();
-      const uint8_t *end = shk::bgzf_scan(p_next, file_end, budget, &s.ms);
-      if (end == p_next || s.ms.empty()) {
-        reason = SHK_FASTQ_GIVEUP_MEMBER;
-        return false;
-      }
-      s.last_of_file = end == file_end;
-      if (!fq_route_submit(R, s, p_next, end, out)) {
-        reason = SHK_FASTQ_GIVEUP_OWN;
-        return false;
-      }
-      p_next = end;
-      return true;
-    };
-    int cur = 0;
-    uint64_t carry = 0;  // bytes of text in front of slot[cur]'s own, already in its carry room
-    bool reached_max = false;
-    if (!reason) (void)submit_next(R.slot[0]);
-    while (!reason && R.slot[cur].live) {
+    FastqRoute R{{}, c, files, budget, max_reads, validate_every, out};
+    R.p_next = files[0].p;
+    reason = R.open();
+    if (!reason) reason = R.feed(R.slot[0]);
+    for (int cur = 0; !reason && R.slot[cur].queued; cur ^= 1) {
       FastqRoute::Slot &s = R.slot[cur], &nx = R.slot[cur ^ 1];
-      if (!input_done) (void)submit_next(nx);
-      if (reason) break;
-      s.live = false;
-      if (hipStreamSynchronize(s.st) != hipSuccess) {
-        (void)hipGetLastError();
-        reason = SHK_FASTQ_GIVEUP_OWN;
-        break;
-      }
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, s.k0, s.k1) == hipSuccess) {
-        out->kernel_ns += (uint64_t)((double)ms * 1e6);
-        fq_totals().kernel_ns += (uint64_t)((double)ms * 1e6);
-      }
-      const uint32_t n = (uint32_t)s.ms.size();
-      const uint32_t *status = (const uint32_t *)s.h_out, *crc = status + n;
-      for (uint32_t i = 0; i < n && !reason; ++i) {
-        if (status[i] != INFC_OK) reason = SHK_FASTQ_GIVEUP_DECODE;
-        else if (crc[i] != s.ms[i].crc) reason = SHK_FASTQ_GIVEUP_CRC;
-      }
-      if (reason) break;
-      // the framing over carry + text, on the engine stream (the slot's stream has been waited for)
-      const uint64_t n_text = carry + s.out_bytes;
-      const uint8_t *text = s.d_text + FQ_CARRY_ROOM - carry;
-      shk_fastq_text_params p{};
-      p.first_record = n_reads;
-      p.validate_every = validate_every;
-      p.max_records = max_reads ? max_reads - n_reads : 0;
-      p.last = s.last_of_file;
-      auto get_out = [&](uint64_t n_look, FqOut *o) -> int {
-        if (!R.grow(&s.d_bases, &s.d_bases_cap, n_text + 64, false) || !R.grow(&s.d_offs, &s.d_offs_cap, (n_look + 1) * 8, false)) return SHK_ERR_NOMEM;
-        *o = FqOut{s.d_bases, n_text, (uint64_t *)s.d_offs};  // (the sequences are part of the text: never more bytes than it has)
-        return SHK_OK;
-      };
-      shk_fastq_text_result r{};
-      uint64_t n_look = 0;
-      const uint64_t down0 = fq_totals().down.load(), ns0 = fq_totals().kernel_ns.load();
-      bool ends_nl = false;
-      const int prc = fq_parse_core(c, text, n_text, p, get_out, &r, &n_look, &ends_nl);
-      out->bytes_down += fq_totals().down.load() - down0;
-      out->kernel_ns += fq_totals().kernel_ns.load() - ns0;
-      if (prc != SHK_OK) {
-        reason = SHK_FASTQ_GIVEUP_OWN;
-        break;
-      }
-      if (r.anomaly_record != FQ_NO_ANOMALY) {
-        reason = SHK_FASTQ_GIVEUP_ANOMALY;
-        break;
-      }
-      if (s.last_of_file && n_text && !ends_nl) {  // a file whose last line is not terminated ends inside a record, or may: the host decides
-        reason = SHK_FASTQ_GIVEUP_TEXT_LEFT;
-        break;
-      }
-      if (r.n_records && shk_ingest_reads_device(c, s.d_bases, s.d_offs, r.n_records, r.n_bases) != SHK_OK) {
-        reason = SHK_FASTQ_GIVEUP_OWN;
-        break;
-      }
-      n_reads += r.n_records;
-      n_bases += r.n_bases;
-      reached_max = max_reads && n_reads >= max_reads;
-      const uint64_t left = n_text - r.bytes_consumed;
-      if (reached_max) break;
-      if (s.last_of_file) {
-        if (left) {
-          reason = SHK_FASTQ_GIVEUP_TEXT_LEFT;
-          break;
-        }
-        carry = 0;
-      } else {
-        if (left > FQ_CARRY_ROOM || !nx.live) {  // (a batch that does not end its file has one behind it)
-          reason = SHK_FASTQ_GIVEUP_OWN;
-          break;
-        }
-        // the text behind the last record, to the front of the next batch's text
-        if (left && hipMemcpyAsync(nx.d_text + FQ_CARRY_ROOM - left, text + r.bytes_consumed, left, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
-          (void)hipGetLastError();
-          reason = SHK_FASTQ_GIVEUP_OWN;
-          break;
-        }
-        carry = left;
-      }
-      // this slot's buffers are free again once the engine stream has passed the ingest (and the copy of the carry)
-      if (hipEventRecord(s.passed, c->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        reason = SHK_FASTQ_GIVEUP_OWN;
-        break;
-      }
-      s.passed_set = true;
-      cur ^= 1;
+      if (!R.input_done) reason = R.feed(nx);
+      if (!reason) reason = R.wait_and_check(s);
+      if (!reason) reason = R.frame_ingest_carry(s, nx);
+      if (reason || R.reached_max) break;
+      reason = R.hand_back(s);
     }
+    n_reads = R.n_reads;
+    n_bases = R.n_bases;
     // the engine stream may still read a slot's buffers (the last ingests): it is waited for before they go back
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (!reason) reason = SHK_FASTQ_GIVEUP_OWN;
-    }
+    if (FastqRoute::own(hipStreamSynchronize(c->stream)) && !reason) reason = SHK_FASTQ_GIVEUP_OWN;
   }
   fq_totals().batches += out->n_batches;
   fq_totals().up += out->bytes_up;

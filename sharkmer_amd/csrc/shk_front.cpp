@@ -1256,31 +1256,15 @@ struct GzSource final : Source {
     // a batch's decoded bytes: 64 MiB keeps 16 host threads busy and the text in cache-sized steps (2.9 against 2.5
     // Gbases/s with 128); the device wants the ≈2000 members of 128 MiB — two batches fill its 4096 wave slots — and
     // gives 2.5-2.8 against 2.1-2.4 Gbases/s with 64
-    const uint64_t budget = [this] {
-      const char *e = getenv("SHK_BGZF_BATCH_KB");  // test hook: batch borders in tiny files
-      return e ? std::max<uint64_t>(1, (uint64_t)atoll(e)) << 10 : (uint64_t)((bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 128 : 64) << 20;
-    }();
-    struct Batch {
-      std::vector<BgzfMember> ms;
-      std::vector<MemberJob> jobs;
-      const uint8_t *begin = nullptr, *end = nullptr;
-      uint64_t out_bytes = 0;
+    const uint64_t budget = bgzf_batch_budget((uint64_t)((bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 128 : 64) << 20);
+    struct Batch : BgzfBatch {
       int slot = 0;
       bool live = false;  // submitted, not collected
     } batch[2];
     int cur = 0;
     auto scan_submit = [&](Batch &B, const uint8_t *from, int slot_) {  // false: no batchable member there (or the decoder failed)
-      B.ms.clear();
-      B.jobs.clear();
-      B.begin = from;
-      B.end = bgzf_scan(from, file_end, budget, &B.ms);
-      B.out_bytes = 0;
       B.slot = slot_;
-      for (const BgzfMember &x : B.ms) {
-        B.jobs.push_back(MemberJob{(uint64_t)(x.header - from) + x.body_off, B.out_bytes, x.body_len, x.isize});
-        B.out_bytes += x.isize;
-      }
-      if (B.ms.empty()) return false;
+      if (!bgzf_plan_batch(from, file_end, budget, &B)) return false;
       B.live = ops->submit(dec, slot_, from, (size_t)(B.end - from), B.jobs.data(), (uint32_t)B.jobs.size(), B.out_bytes) == 0;
       return B.live;
     };

@@ -9,6 +9,8 @@
 #include <thread>
 #include <vector>
 
+#include "shk_inflate.h"
+
 namespace shk {
 
 std::string fmt(const char *f, ...) __attribute__((format(printf, 1, 2)));
@@ -46,11 +48,7 @@ struct Pool {
 
 // ---- the seam between the BGZF batched route (shk_front.cpp, no HIP) and what decodes a batch ----------
 // A batch: consecutive BGZF members, their compressed bytes `comp[0, comp_len)` in one piece (headers and trailers
-// included), and per member where its raw DEFLATE body lies in that and where its text goes in the batch's output.
-struct MemberJob {
-  uint64_t in_offset, out_offset;  // out_offset: the prefix sum of ISIZE
-  uint32_t in_len, out_len;        // both ≤ 65536
-};
+// included), and a MemberJob per member (shk_inflate.h: bgzf_plan_batch makes them).
 // A decoder takes up to two batches at a time (slots 0 and 1: the next one goes up while this one comes back).
 // submit() queues a batch; collect() waits for it, writes its text to dst[0, out_bytes) and one InfCoreStatus word per
 // member to status[].  Both return 0, or an error that ends the batched route for the stream (the one-after-the-other

@@ -8,6 +8,7 @@
 
 #include <immintrin.h>
 
+#include <cstdlib>
 #include <cstring>
 
 namespace shk {
@@ -993,6 +994,31 @@ const uint8_t *bgzf_scan(const uint8_t *p, const uint8_t *file_end, uint64_t out
     p += m.size;
   }
   return p;
+}
+bool bgzf_plan_batch(const uint8_t *from, const uint8_t *file_end, uint64_t budget, BgzfBatch *b) {
+  b->ms.clear();
+  b->jobs.clear();
+  b->begin = from;
+  b->end = bgzf_scan(from, file_end, budget, &b->ms);
+  b->out_bytes = 0;
+  for (const BgzfMember &x : b->ms) {
+    b->jobs.push_back(MemberJob{(uint64_t)(x.header - from) + x.body_off, b->out_bytes, x.body_len, x.isize});
+    b->out_bytes += x.isize;
+  }
+  return !b->ms.empty();
+}
+bool bgzf_jobs_inside(const MemberJob *jobs, uint32_t n, size_t comp_len, uint64_t out_bytes) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const MemberJob &j = jobs[i];
+    if (j.in_len > 65536 || j.out_len > 65536 || j.in_offset > comp_len || j.in_len > comp_len - j.in_offset || j.out_offset > out_bytes ||
+        j.out_len > out_bytes - j.out_offset)
+      return false;
+  }
+  return true;
+}
+uint64_t bgzf_batch_budget(uint64_t default_bytes) {
+  const char *e = getenv("SHK_BGZF_BATCH_KB");
+  return e ? std::max<uint64_t>(1, (uint64_t)atoll(e)) << 10 : default_bytes;
 }
 
 }  // namespace shk

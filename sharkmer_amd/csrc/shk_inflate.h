@@ -106,4 +106,26 @@ struct BgzfMember {
 // (anything else that may follow a trailer, a member cut short by the file's end).  Decodes nothing.
 const uint8_t *bgzf_scan(const uint8_t *p, const uint8_t *file_end, uint64_t out_budget, std::vector<BgzfMember> *out);
 
+// ---- a batch of members, planned -----------------------------------------------------------------
+// What a decoder is told per member of a batch: where its raw DEFLATE body lies in the batch's compressed bytes
+// `comp[0, comp_len)` (one piece, headers and trailers included) and where its text goes in the batch's output.
+struct MemberJob {
+  uint64_t in_offset, out_offset;  // out_offset: the prefix sum of ISIZE
+  uint32_t in_len, out_len;        // both ≤ 65536
+};
+struct BgzfBatch {
+  std::vector<BgzfMember> ms;
+  std::vector<MemberJob> jobs;  // one per member, offsets from `begin`
+  const uint8_t *begin = nullptr, *end = nullptr;
+  uint64_t out_bytes = 0;       // the members' ISIZEs summed
+};
+// bgzf_scan from `from` under `budget`, and the jobs of what it lists.  false: no batchable member stands at `from`.
+bool bgzf_plan_batch(const uint8_t *from, const uint8_t *file_end, uint64_t budget, BgzfBatch *b);
+// Every job inside the batch — lengths ≤ 65536, [in_offset, + in_len) in comp_len, [out_offset, + out_len) in
+// out_bytes: what a decoder checks before it reads and writes what the jobs say.
+bool bgzf_jobs_inside(const MemberJob *jobs, uint32_t n, size_t comp_len, uint64_t out_bytes);
+// A batch's budget of decoded bytes: SHK_BGZF_BATCH_KB (test hook: batch borders in tiny files; KiB, at least 1) where
+// it is set, default_bytes otherwise.
+uint64_t bgzf_batch_budget(uint64_t default_bytes);
+
 }  // namespace shk

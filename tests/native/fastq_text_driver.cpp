@@ -7,6 +7,11 @@
 //   fastq_text_driver crc SEED N    N random extents of 0..70000 bytes (and the lengths round the shares' borders) at
 //                                   random alignments: the 64 shares' parts, combined and conditioned, against
 //                                   crc32_update
+//   fastq_text_driver plan FILE BUDGET...   bgzf_plan_batch over FILE, batch after batch to the file's end or to the first
+//                                   member it does not take, once per budget (bytes): per batch the member count,
+//                                   out_bytes, where it begins and ends in the file, the first and the last job
+//   fastq_text_driver inside        bgzf_jobs_inside on jobs at the batch's edges and near UINT64_MAX
+//   fastq_text_driver budget DEFAULT   bgzf_batch_budget(DEFAULT) under the environment it is started in
 // The text lies at the case's alignment in an allocation that ends with its last byte, the line table has exactly
 // the text's lines, and bases and offsets have exactly the expected sizes between guard bytes: a read or a write
 // outside any of them is the sanitizer's, or a guard's, to report.
@@ -174,9 +179,76 @@ static int run_crc(uint64_t seed, size_t n_random) {
   return 0;
 }
 
+static int run_plan(const char *path, int n_budgets, char **budgets) {
+  const std::vector<uint8_t> file = slurp(path);
+  const uint8_t *const p0 = file.data(), *const pe = p0 + file.size();
+  for (int k = 0; k < n_budgets; ++k) {
+    const uint64_t budget = strtoull(budgets[k], nullptr, 10);
+    printf("budget %llu\n", (unsigned long long)budget);
+    BgzfBatch b;
+    const uint8_t *p = p0;
+    while (p < pe && bgzf_plan_batch(p, pe, budget, &b)) {
+      if (b.begin != p || b.end <= p || b.jobs.size() != b.ms.size() || !bgzf_jobs_inside(b.jobs.data(), (uint32_t)b.jobs.size(), (size_t)(b.end - b.begin), b.out_bytes)) {
+        fprintf(stderr, "a batch at %zu that is not one\n", (size_t)(p - p0));
+        return 1;
+      }
+      const MemberJob &f = b.jobs.front(), &l = b.jobs.back();
+      printf("batch %zu %llu %zu %zu %llu %llu %u %u %llu %llu %u %u\n", b.ms.size(), (unsigned long long)b.out_bytes, (size_t)(b.begin - p0), (size_t)(b.end - p0),
+             (unsigned long long)f.in_offset, (unsigned long long)f.out_offset, f.in_len, f.out_len, (unsigned long long)l.in_offset,
+             (unsigned long long)l.out_offset, l.in_len, l.out_len);
+      p = b.end;
+    }
+    if (p < pe)
+      printf("stop %zu\n", (size_t)(p - p0));
+    else
+      printf("end\n");
+  }
+  return 0;
+}
+
+static int run_inside() {
+  const uint64_t M = ~0ull;
+  struct {
+    MemberJob j;
+    size_t comp_len;
+    uint64_t out_bytes;
+    bool want;
+  } cases[] = {
+      {{0, 0, 0, 0}, 0, 0, true},
+      {{10, 20, 90, 80}, 100, 100, true},
+      {{10, 20, 91, 80}, 100, 100, false},
+      {{10, 20, 90, 81}, 100, 100, false},
+      {{101, 0, 0, 0}, 100, 100, false},
+      {{0, 101, 0, 0}, 100, 100, false},
+      {{0, 0, 65536, 65536}, 65536, 65536, true},
+      {{0, 0, 65537, 1}, 1 << 20, 1 << 20, false},
+      {{0, 0, 1, 65537}, 1 << 20, 1 << 20, false},
+      {{M, 0, 1, 0}, 100, 100, false},       // (in_offset + in_len wraps to 0)
+      {{M - 5, 0, 10, 0}, 100, 100, false},  // (… to 4)
+      {{0, M, 0, 1}, 100, 100, false},
+      {{0, M - 5, 0, 10}, 100, 100, false},
+      {{M, M, 65536, 65536}, (size_t)M, M, false},
+      {{M - 65536, M - 65536, 65536, 65536}, (size_t)M, M, true},
+  };
+  for (const auto &c : cases)
+    if (bgzf_jobs_inside(&c.j, 1, c.comp_len, c.out_bytes) != c.want) {
+      fprintf(stderr, "bgzf_jobs_inside({%llu, %llu, %u, %u}, %zu, %llu) is not %d\n", (unsigned long long)c.j.in_offset, (unsigned long long)c.j.out_offset, c.j.in_len,
+              c.j.out_len, c.comp_len, (unsigned long long)c.out_bytes, (int)c.want);
+      return 1;
+    }
+  // one job outside among good ones
+  const MemberJob three[3] = {{0, 0, 10, 10}, {M - 1, 10, 10, 10}, {20, 20, 10, 10}};
+  if (bgzf_jobs_inside(three, 3, 100, 100) || !bgzf_jobs_inside(three, 1, 100, 100) || !bgzf_jobs_inside(three, 0, 0, 0)) return 1;
+  printf("inside ok: %zu jobs\n", sizeof cases / sizeof cases[0]);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc >= 4 && !strcmp(argv[1], "plan")) return run_plan(argv[2], argc - 3, argv + 3);
+  if (argc == 2 && !strcmp(argv[1], "inside")) return run_inside();
+  if (argc == 3 && !strcmp(argv[1], "budget")) return printf("%llu\n", (unsigned long long)bgzf_batch_budget(strtoull(argv[2], nullptr, 10))) < 0;
   if (argc == 3 && !strcmp(argv[1], "parse")) return run_parse(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "crc")) return run_crc(strtoull(argv[2], nullptr, 10), strtoull(argv[3], nullptr, 10));
-  fprintf(stderr, "usage: %s parse FILE | crc SEED N\n", argv[0]);
+  fprintf(stderr, "usage: %s parse FILE | crc SEED N | plan FILE BUDGET... | inside | budget DEFAULT\n", argv[0]);
   return 2;
 }

@@ -168,13 +168,16 @@ def write_case(tmp_path, monkeypatch, name):
 @pytest.mark.parametrize("name", sorted(n for n in CLEAN if n not in ("payload1", "payload2")))
 def test_route_counts_what_the_reader_route_counts(orc, tmp_path, monkeypatch, name):
     p, n_members = write_case(tmp_path, monkeypatch, name)
+    before = sa.fastq_device_totals()
     hist, cnt, st = device_run([p])
+    down = sa.fastq_device_totals()["bytes_down"] - before["bytes_down"]
     assert st["gave_up"] == 0, st
     want_hist, want_cnt, n_reads, n_bases = reference_run([p])
     assert st["n_records"] == n_reads and st["n_bases"] == n_bases and st["n_members"] == n_members   # every record framed on the device
     assert np.array_equal(hist, want_hist) and cnt == want_cnt
     assert ("ok", hist.tobytes(), st["n_records"], st["n_bases"]) == oracle_counts(orc, p)
-    assert st["bytes_down"] <= 64 * st["n_members"] + 256 * st["n_batches"], st
+    # two status/CRC words per member; per framed batch the control words in front of n_bases_look and the result words
+    assert st["bytes_down"] == 8 * st["n_members"] + 64 * st["n_batches"] == down, st
     assert st["bytes_up"] >= os.path.getsize(p) - 28 * n_members and st["kernel_ns"] > 0
 
 
@@ -213,6 +216,43 @@ def test_route_gives_up_and_leaves_an_empty_engine(tmp_path, monkeypatch):
     want = reference_run([p])
     assert np.array_equal(eng.histograms(), want[0]) and results(eng.counters()) == want[1]
     eng.close()
+
+
+@pytest.fixture(scope="module")
+def growing_file(tmp_path_factory):
+    """≈ 12 MiB of text in level-6 members, then ≈ 12 MiB in stored ones: with 6000 KiB batches the compressed bytes of a
+    batch go from well under 4 MiB to about 6 MiB, so both slots' upload blocks step from 4 to 8 MiB after use."""
+    reps = -(-(12 << 20) // len(bc.TEXT))
+    part = {level: b"".join(bc.bgzf(bc.TEXT, level=level, eof=False)) for level in (6, 0)}
+    assert len(part[6]) * 6000 * 1024 < 3 * (1 << 20) * len(bc.TEXT) and len(part[0]) > len(bc.TEXT)
+    p = tmp_path_factory.mktemp("bgzf_grow") / "reads.fastq.gz"
+    p.write_bytes(part[6] * reps + part[0] * reps + bc.EOF_MEMBER)
+    return str(p)
+
+
+def test_route_slot_blocks_grow_while_the_other_slot_is_in_flight(growing_file, monkeypatch):
+    monkeypatch.setenv("SHK_BGZF_BATCH_KB", "6000")
+    hist, cnt, st = device_run([growing_file])
+    assert st["gave_up"] == 0 and st["n_batches"] >= 4, st
+    want_hist, want_cnt, n_reads, n_bases = reference_run([growing_file])
+    assert st["n_records"] == n_reads and st["n_bases"] == n_bases
+    assert np.array_equal(hist, want_hist) and cnt == want_cnt
+    # the same file through the reader whose batches the device decodes: the all-members reader's reads, none one by one
+    got, want = [], []
+    for out, kw in ((got, dict(bgzf="device")), (want, dict(gzip_all_members=True))):
+        r = sa.FastqReader([growing_file], **kw)
+        try:
+            while True:
+                b, o = r.next_batch(max_seqs=1 << 20, max_bases=64 << 20)
+                out.append((b.copy(), o.copy()))
+                if r.stats()["done"]:
+                    break
+            if out is got:
+                assert r.member_stats()["sequential"] == 0 and r.member_stats()["device"] > 0
+        finally:
+            r.close()
+    assert np.array_equal(np.concatenate([b for b, _ in got]), np.concatenate([b for b, _ in want]))
+    assert np.array_equal(np.concatenate([np.diff(o.astype(np.int64)) for _, o in got]), np.concatenate([np.diff(o.astype(np.int64)) for _, o in want]))
 
 
 def test_route_two_files_max_reads_and_cadence(tmp_path, monkeypatch):
