@@ -58,6 +58,20 @@ extern "C" {
                                    * the NEXT call on the context (ingest, sync, finalize), and that call's first
                                    * host-to-device copies overlap this one's counting */
 
+#define SHK_FLAG_GROUP_GRAPH 32u   /* a multi-device context (n_devices > 1) answers sPCR's graph extension —
+                                   * shk_neighborhood[_panel], shk_pcr_extend[_panel], shk_pcr_run — instead of refusing:
+                                   * the search runs on the first device and each table probe reads the arrays of the
+                                   * share that owns the key.  Opt-in because of what it has never been
+                                   * run on: no run on more than one physical GPU has been possible where this was built,
+                                   * and until this flag only copy engines (hipMemcpyPeerAsync) crossed devices.  With it a
+                                   * kernel on one device dereferences another device's HBM.  On distinct cards two
+                                   * things are written from the documentation and UNVERIFIED: whether the first device
+                                   * sees the peers' latest table writes after the host-side stream synchronisations, and
+                                   * what a dependent remote probe per level costs over xGMI.  Where peer access between
+                                   * the first device and a distinct other one is missing the context is still created
+                                   * and the graph calls answer SHK_ERR_STATE naming the two devices.  On a one-device
+                                   * context the flag does nothing; owner shares (n_owners > 1) keep refusing. */
+
 typedef struct shk_ctx shk_ctx;
 
 typedef struct shk_config {
@@ -550,7 +564,9 @@ int shk_thread_reads_panel_retained(shk_ctx *ctx, const uint64_t *node_sub_kmers
  * neighbourhood is complete), *levels_done = L.  Calling again with the fringe as seeds continues the search (it may
  * report k-mers and entries again that an earlier call reported).  A deterministic function of table and arguments.
  * Errors: dir 0 or > 3, a node > mask, more distinct seeds than fringe_cap: SHK_ERR_BAD_ARG; a multi-device context
- * or an owner share (a neighbour's count may live on another share): SHK_ERR_STATE.  Valid whenever shk_lookup is;
+ * or an owner share (a neighbour's count may live on another share): SHK_ERR_STATE.  A multi-device context created
+ * with SHK_FLAG_GROUP_GRAPH answers instead: the same search on its first device, every probe into the share that owns
+ * the key; the result is that of one context holding the union of the shares.  Valid whenever shk_lookup is;
  * the table is not touched.  cap, fringe_cap ≤ 2^32; the device scratch is about 100 bytes per unit of cap.  The call
  * is one job of shk_neighborhood_panel (below): the same kernels and scratch layout, its lists fetched from the job's
  * own arrays instead of a packed copy. */
@@ -579,8 +595,8 @@ typedef struct shk_pcr_extend_params {
  * an error (do_pcr returns before, mod.rs:446-468): the other set's seeds are extended and no path is found.
  * node_cap / edge_cap too small: SHK_ERR_BAD_ARG with *n_nodes / *n_edges set to what is needed.  A k-mer counts
  * when its merged count ≥ max(threshold, table_min_count, 1).  Multi-device contexts and owner shares:
- * SHK_ERR_STATE, as shk_neighborhood.  The call is shk_pcr_extend_panel (below) for one gene, replayed on the calling
- * thread; a host allocation that fails in the replay is SHK_ERR_NOMEM.  Tuning: SHK_PCR_FETCH_CAP (k-mers, read at
+ * SHK_ERR_STATE, as shk_neighborhood; a multi-device context with SHK_FLAG_GROUP_GRAPH answers, as shk_neighborhood.
+ * The call is shk_pcr_extend_panel (below) for one gene, replayed on the calling thread; a host allocation that fails in the replay is SHK_ERR_NOMEM.  Tuning: SHK_PCR_FETCH_CAP (k-mers, read at
  * each call) bounds one neighbourhood fetch; the result does not depend on it.  The panel's own knobs
  * (SHK_PCR_PANEL_FETCH_CAP, SHK_PCR_PANEL_THREADS, SHK_PCR_PANEL_TRACE) do not apply to this call. */
 int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_counts, uint64_t n_fwd,
@@ -602,7 +618,8 @@ int shk_pcr_extend(shk_ctx *ctx, const uint64_t *fwd_kmers, const uint32_t *fwd_
  *   own two sets, entry lists and counters.  A job without seeds returns zeros; n_jobs == 0 is SHK_OK.
  * Errors, raised before the device is touched, with a text that names the job: every argument error of
  *   shk_neighborhood, decreasing seed_offsets: SHK_ERR_BAD_ARG; also n_jobs > SHK_PCR_MAX_GENES.  Multi-device
- *   contexts and owner shares: SHK_ERR_STATE.  Valid whenever shk_lookup is; the table is not touched.  The device
+ *   contexts and owner shares: SHK_ERR_STATE; a multi-device context with SHK_FLAG_GROUP_GRAPH answers, with the
+ *   launches of the one-device call (the share directory rides in the call's one upload).  Valid whenever shk_lookup is; the table is not touched.  The device
  *   scratch per job is 8 bytes × (the powers of two above 8·cap + 2·seeds and above 2·cap, for the two sets) plus 24
  *   bytes per unit of cap and 24 per unit of fringe_cap (lists and their packed copies): 140 to 210 bytes per unit of
  *   cap when fringe_cap = cap, the upper end at a power-of-two cap.  It is the context's grow-only scratch and stays
@@ -629,7 +646,8 @@ int shk_neighborhood_panel(shk_ctx *ctx, const uint64_t *nodes, const uint8_t *d
  *   arrays complete (their last entries are the need).  n_genes == 0: zero offsets.
  * Errors, SHK_ERR_BAD_ARG with a text that names the gene and the direction: a primer k-mer that is not a k-mer (before
  *   the device is touched), decreasing primer_offsets; also n_genes > SHK_PCR_MAX_GENES, k < 2.  Multi-device contexts
- *   and owner shares: SHK_ERR_STATE.  The table is not touched.
+ *   and owner shares: SHK_ERR_STATE; a multi-device context with SHK_FLAG_GROUP_GRAPH answers, as
+ *   shk_neighborhood_panel.  The table is not touched.
  * Tuning, all read at each call, none changes the result: SHK_PCR_PANEL_THREADS (default 8, clamped to 1..16) host threads replay
  *   the genes of a round (1: serial); SHK_PCR_PANEL_FETCH_CAP (k-mers, default 2^22; 140 to 210 bytes of device
  *   scratch each, see shk_neighborhood_panel: up to 0.9 GB at the default, kept by the context) is shared evenly by the jobs of a launch — a job gets at least 4 × its seeds and at most what its node budget
@@ -900,11 +918,21 @@ typedef struct shk_pcr_run_out {   /* every pointer optional except records.reco
  *   name (cli.rs:572-581), both SHK_ERR_BAD_ARG; then get_primer_kmers' errors in its order — too many variants
  *   forward, reverse, invalid character forward, reverse (primers.rs:440-478; the validation lets no character through
  *   that the conversion refuses).  Multi-device contexts and owner shares: SHK_ERR_STATE, as shk_pcr_extend_panel.
+ *   A multi-device context with SHK_FLAG_GROUP_GRAPH answers for SHK_PCR_READS_NONE and SHK_PCR_READS_HOST: the primer
+ *   scan over its shares, the extension as shk_pcr_extend_panel, the host batch staged once on its first device, where
+ *   the filter, the threading, the prune and the products run; it retains no reads (SHK_PCR_READS_RETAINED: "reads are
+ *   not retained").  The result is the one-device context's, array for array.
  *   records.record_cap / seq_cap too small: SHK_ERR_BAD_ARG with n_records / n_seq_bytes the need and every per-gene
  *   array complete.  n_genes == 0: SHK_OK, nothing launched.
  * With SHK_TRACE set: one line per gene on stderr after the run. */
 int shk_pcr_run(shk_ctx *ctx, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params,
                 shk_pcr_run_out *out);
+
+/* The owner of a canonical k-mer among n_owners shares, as the engine assigns it (shk_config.n_owners, the shares of a
+ * multi-device context): the top log2(n_owners) bits of the key mix of the 2k-bit value.  Host only, no context: what a
+ * multi-process job routes a query by.  n_owners: a power of two ≤ 64 (1: always 0).  ~0u for k = 0, k ≥ 32 or an
+ * n_owners that is none. */
+uint32_t shk_key_owner(uint32_t k, uint32_t n_owners, uint64_t canonical_kmer);
 
 /* ---- multi-GPU hooks (device pointers; exchanged by the caller over RCCL) ---- */
 
@@ -1294,12 +1322,16 @@ typedef struct shk_pcr_file_config {
                                    (main.rs:136-139) */
   uint32_t dump;                /* reserved, 0 (--dump-graph is not built) */
   uint64_t node_budget_global;  /* 0 = shk_pcr_node_budget(n_bases_ingested) */
-  uint64_t reserved[4];
+  uint64_t context_flags;       /* SHK_FLAG_* for the run's context: SHK_FLAG_GROUP_GRAPH or 0, anything else is
+                                   SHK_ERR_BAD_ARG (the first of what were four reserved words: same size and offsets) */
+  uint64_t reserved[3];
 } shk_pcr_file_config;
 /* shk_run_files with main.rs:133-199: after the histograms, shk_pcr_run over pcr->genes, {sample}_{gene}.fasta for every
  * gene with products in gene order (stats.rs:102-125), then the stats file with pcr_results.  A run that fails leaves no
  * stats file.  pcr NULL or without genes: shk_run_files.  out (optional) is handed to shk_pcr_run as it is: the caller's
- * arrays and capacities; NULL: the call keeps the products to itself.  n_devices > 1 with genes: SHK_ERR_STATE. */
+ * arrays and capacities; NULL: the call keeps the products to itself.  n_devices > 1 with genes: SHK_ERR_STATE, unless
+ * context_flags has SHK_FLAG_GROUP_GRAPH: then the run proceeds over the multi-device context — without read_threading,
+ * which is SHK_ERR_STATE before a read is read (a multi-device context keeps no reads). */
 int shk_run_files_pcr(const shk_run_config *cfg, const shk_pcr_file_config *pcr, shk_run_stats *out_stats,
                       shk_pcr_run_out *out);
 

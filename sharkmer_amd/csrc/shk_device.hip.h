@@ -21,6 +21,7 @@
 #include "shk_inflate_core.h"
 #include "shk_fastq_text_core.h"
 #include "shk_retain_core.h"
+#include "shk_mix.h"
 
 namespace shk {
 
@@ -95,38 +96,7 @@ struct SpillRef {
 // tools/hash_eval.py: page occupancy and slot collisions match a Poisson process on random,
 // AT-rich, tandem-repeat and sequential keys (without the finaliser sequential keys collide).
 constexpr uint32_t MAX_LOG_PAGES = 20;  // page bits + the 11 home-bucket bits ≤ 32 hash bits; 2^33 slots ≈ 103 GB
-// mix_key: a BIJECTION of the 2k-bit key space — ONE multiplication by an odd constant mod 2^2k — so the
-// position of a key in the table (page = top log_pages bits of the product, home bucket = the next 11
-// bits) together with the remaining low bits identifies the key.  The 4-byte-record path of the paged
-// counter ships only those low bits and rebuilds a key with unmix_key (the inverse multiplication) when
-// it has to.  Everything the engine reads off the mixed key it reads off its TOP bits (owner, partition,
-// page, bucket), and the top bits of a product depend on every bit of the key; the low bits, which depend
-// on the key's low bits only, are just carried along as the fingerprint.  Up to 42 key bits (k ≤ 21: the
-// 4-byte-record path, k_scatter32, which is bound by VALU issue) the multiplier is a 32-bit constant — a
-// 64-bit product by it is one v_mad_u64_u32 + one v_mul_lo_u32 — beyond that a 64-bit one (longer keys need
-// the wider constant for keys that differ in their low bits only to reach the top).  tools/hash_eval.py:
-// page occupancy and bucket overflow match a Poisson process on random, AT-rich, tandem-repeat and
-// sequential keys for k = 9…31 (round 1 used multiply–fold–multiply; one multiply measures the same
-// spread and takes five instructions fewer per k-mer in the scatter's walk).
-#ifndef SHK_MIX_M32
-#define SHK_MIX_M32 0xC2B2AE35ull
-#define SHK_MIX_M32_INV 0xD16E308E7ED1B41Dull
-#endif
-constexpr uint64_t MIX_M32 = SHK_MIX_M32, MIX_M64 = 0x9E3779B97F4A7C15ull;
-constexpr uint64_t MIX_M32_INV = SHK_MIX_M32_INV, MIX_M64_INV = 0xF1DE83E19937733Dull;  // mod 2^64
-static_assert((MIX_M32 * MIX_M32_INV) == 1ull && (MIX_M64 * MIX_M64_INV) == 1ull, "inverses mod 2^64");
-#ifndef SHK_MIX_NARROW_BITS
-#define SHK_MIX_NARROW_BITS 42
-#endif
-constexpr uint32_t MIX_NARROW_BITS = SHK_MIX_NARROW_BITS;
-__host__ __device__ __forceinline__ uint64_t mix_key(uint64_t x, uint32_t bits) {
-  const uint64_t mask = ~0ull >> (64 - bits);
-  return (x * (bits <= MIX_NARROW_BITS ? MIX_M32 : MIX_M64)) & mask;
-}
-__host__ __device__ __forceinline__ uint64_t unmix_key(uint64_t y, uint32_t bits) {
-  const uint64_t mask = ~0ull >> (64 - bits);
-  return (y * (bits <= MIX_NARROW_BITS ? MIX_M32_INV : MIX_M64_INV)) & mask;
-}
+// mix_key / unmix_key, the bijective key mix everything below reads its geometry from: shk_mix.h (shared with the host side).
 // the 32 hash bits the table geometry is read from: the top of the mixed key
 __device__ __forceinline__ uint32_t hash64(uint64_t key, uint32_t bits) {
   return (uint32_t)((mix_key(key, bits) << (64 - bits)) >> 32);
@@ -1288,6 +1258,15 @@ __device__ __forceinline__ uint32_t merged_count(const TableRef &tb, uint64_t ke
   return cum;
 }
 
+// merged_count over the shares of a multi-device context (SHK_FLAG_GROUP_GRAPH): dir[d] is share d's table, 2^owner_bits
+// of them (owner_bits >= 1), all of one key length.  Exactly one share owns a key — the top owner_bits of its hash, the
+// bits home_of tests — so the probe is merged_count on that share's arrays: plain loads, nothing is written during the call.
+__device__ __forceinline__ uint32_t merged_count_sharded(const TableRef *dir, uint32_t owner_bits, uint64_t key) {
+  const uint32_t owner = hash64(key, dir[0].key_bits) >> (32 - owner_bits);
+  const TableRef tb = dir[owner];  // (the descriptor once: 48 bytes)
+  return merged_count(tb, key);    // (.owned holds by construction)
+}
+
 __global__ void __launch_bounds__(WG) k_lookup(TableRef tb, const uint64_t *__restrict__ kmers,
                                                uint32_t *__restrict__ out, uint64_t n, int canonical,
                                                int k) {
@@ -1369,9 +1348,22 @@ __device__ __forceinline__ int nb_set_insert(uint64_t *set, uint64_t mask, uint6
   return -1;
 }
 
+// What the table-probing kernels below take as "the table": a context's own TableRef, or the share directory of a
+// multi-device context — a template parameter of the kernels, so that the one-table instantiation is the code it was.
+struct NbShards {
+  const TableRef *dir;  // TableRef[2^owner_bits]: device memory (k_nb_wide), or the workgroup's LDS copy (k_nb_narrow_panel)
+  uint32_t owner_bits;
+};
+constexpr uint32_t NB_MAX_SHARES = 64;  // shares of a multi-device context at most (group_create)
+template <bool SHARDED>
+using NbTable = std::conditional_t<SHARDED, NbShards, TableRef>;
+__device__ __forceinline__ uint32_t nb_count(const TableRef &tb, uint64_t key) { return merged_count(tb, key); }
+__device__ __forceinline__ uint32_t nb_count(const NbShards &sh, uint64_t key) { return merged_count_sharded(sh.dir, sh.owner_bits, key); }
+
 // One (entry, base) pair of the current level.  k_n / next_n: the two fill counters (LDS in k_nb_narrow_panel, the control
 // block in k_nb_wide); lds_next: where k_nb_narrow_panel keeps the first NB_NARROW entries of the next level.
-__device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, uint64_t entry, uint32_t b,
+template <class Table>
+__device__ __forceinline__ void nb_expand(const Table &tb, const NbRef &nb, uint64_t entry, uint32_t b,
                                           uint64_t *next_list, unsigned long long *k_n, unsigned long long *next_n,
                                           uint32_t *set_full, uint64_t *lds_next) {
   const uint64_t node = entry >> 1, dir = entry & 1ull;
@@ -1379,7 +1371,7 @@ __device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, u
   const uint64_t x = dir ? ((uint64_t)b << sh) | node : (node << 2) | b;
   const uint64_t rc = revcomp(x, nb.k);
   const uint64_t cn = x < rc ? x : rc;
-  const uint32_t cnt = merged_count(tb, cn);
+  const uint32_t cnt = nb_count(tb, cn);
   if (cnt < nb.min_count) return;
   const int ins = nb_set_insert(nb.kset, nb.kset_mask, cn);
   if (ins < 0) {
@@ -1401,8 +1393,10 @@ __device__ __forceinline__ void nb_expand(const TableRef &tb, const NbRef &nb, u
   if (lds_next && at < NB_NARROW) lds_next[at] = succ;
 }
 
-// WIDE: one level per launch, one thread per (entry, base); the host reads the two fills back and decides.
-__global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ctl, uint32_t cur_sel, uint64_t cur_n) {
+// WIDE: one level per launch, one thread per (entry, base); the host reads the two fills back and decides.  SHARDED: a
+// thread makes one probe, so it reads its share's descriptor from the directory in device memory, once.
+template <bool SHARDED>
+__global__ void __launch_bounds__(WG) k_nb_wide(NbTable<SHARDED> tb, NbRef nb, NbCtl *ctl, uint32_t cur_sel, uint64_t cur_n) {
   const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
   if (t >= cur_n * 4) return;
   nb_expand(tb, nb, nb.list[cur_sel][t >> 2], (uint32_t)(t & 3), nb.list[cur_sel ^ 1], &ctl->k_n, &ctl->next_n,
@@ -1414,7 +1408,8 @@ __global__ void __launch_bounds__(WG) k_nb_wide(TableRef tb, NbRef nb, NbCtl *ct
 // stops with ctl->status = why: the neighbourhood is complete, max_levels reached, the next level did not fit the
 // caller's capacities (ctl then describes the level before it), or it is too wide for one workgroup (k_nb_wide's).
 // (The level loop itself; k_nb_narrow_panel runs it for its job.)
-__device__ __forceinline__ void nb_narrow_levels(const TableRef &tb, const NbRef &nb, NbCtl *ctl) {
+template <class Table>
+__device__ __forceinline__ void nb_narrow_levels(const Table &tb, const NbRef &nb, NbCtl *ctl) {
   __shared__ uint64_t s_list[2][NB_NARROW];
   __shared__ unsigned long long s_kn, s_kstart, s_nextn, s_curfull;  // s_curfull: the current level's size, s_curn capped
   __shared__ uint32_t s_full, s_status, s_curn, s_sel, s_levels;
@@ -1494,11 +1489,26 @@ __global__ void __launch_bounds__(WG) k_nb_seed_panel(const NbRef *__restrict__ 
 // not there to be run — no seeds (NB_COMPLETE from the host) or a level 0 too wide for a workgroup (NB_WIDE) — is left
 // as it is; the host takes the wide ones on afterwards, one at a time (k_nb_wide per level, and this kernel with a grid
 // of 1 on the job's own pair when a level fits a workgroup again).
-__global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel(TableRef tb, const NbRef *__restrict__ refs, NbCtl *ctls) {
+// SHARDED: which share a probe goes to differs from lane to lane, so the directory is staged into LDS once per workgroup
+// (at most 64 × 48 B = 3 KiB beside the 16 KiB of entry lists) and choosing the owner is one LDS read, not a chain of
+// dependent global loads per probe.
+template <bool SHARDED>
+__global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel(NbTable<SHARDED> tb, const NbRef *__restrict__ refs, NbCtl *ctls) {
   NbCtl *ctl = &ctls[blockIdx.x];
   if (ctl->status != NB_RUN || ctl->cur_n == 0 || ctl->cur_n > NB_NARROW) return;  // (the same for every thread: ctl is written at the end only)
   const NbRef nb = refs[blockIdx.x];  // (a private copy: scalar loads once, not after every atomic of the level loop)
-  nb_narrow_levels(tb, nb, ctl);
+  if constexpr (SHARDED) {
+    static_assert(sizeof(TableRef) % 8 == 0, "the directory is copied in 8-byte words");
+    __shared__ TableRef s_dir[NB_MAX_SHARES];
+    constexpr uint32_t W = sizeof(TableRef) / 8;
+    const uint32_t n8 = (1u << (tb.owner_bits < 6 ? tb.owner_bits : 6)) * W;  // (≤ NB_MAX_SHARES entries whatever the argument says)
+    for (uint32_t i = threadIdx.x; i < n8; i += NB_WG)
+      reinterpret_cast<uint64_t *>(s_dir)[i] = reinterpret_cast<const uint64_t *>(tb.dir)[i];
+    __syncthreads();
+    nb_narrow_levels(NbShards{s_dir, tb.owner_bits}, nb, ctl);
+  } else {
+    nb_narrow_levels(tb, nb, ctl);
+  }
 }
 
 // What a job hands back, packed: its k_n k-mers and counts from pack_k, its n_f fringe entries (the unexpanded level,

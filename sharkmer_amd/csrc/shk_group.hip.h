@@ -66,6 +66,10 @@ struct shk_group {
   bool finalized = false, hist_ready = false;
   std::vector<uint64_t> hist;
   shk_counters tot{};
+  // SHK_FLAG_GROUP_GRAPH: the graph extension's kernels run on the lead share's device (share 0) and read every share's
+  // table there.  graph_peer: a distinct device the lead cannot reach — no hipDeviceCanAccessPeer, or enabling it
+  // failed — (−1: none; found at group_create, answered by the graph calls).
+  int32_t graph_peer = -1;
 
   // Returns whether any worker had failed WHEN THE LAST ONE ARRIVED — one answer for all of them, taken inside the
   // barrier, so that either every worker leaves the round early or none does (a worker that looked at status[] on its
@@ -141,6 +145,16 @@ int group_fail(shk_ctx *top, shk_group *g, int code, uint32_t who) {
   return code;
 }
 
+// How a graph call (shk_neighborhood[_panel], shk_pcr_extend[_panel], shk_pcr_run) opens on a multi-device context
+// created with SHK_FLAG_GROUP_GRAPH (without the flag the call has refused before).
+int group_graph_begin(shk_ctx *top) {
+  const shk_group *g = top->group;
+  if (g->graph_peer >= 0)
+    return fail(top, SHK_ERR_STATE, "SHK_FLAG_GROUP_GRAPH: device %d cannot access the memory of device %d (no peer access): the graph extension reads every share's table from the first device",
+                g->dev_ids[0], g->graph_peer);
+  return SHK_OK;
+}
+
 int group_create(const shk_config *cfg, shk_ctx **out) {
   const uint32_t D = cfg->n_devices;
   if (D > 64 || (D & (D - 1))) return fail(nullptr, SHK_ERR_BAD_ARG, "n_devices must be a power of two ≤ 64, got %u", D);
@@ -186,11 +200,15 @@ int group_create(const shk_config *cfg, shk_ctx **out) {
     for (uint32_t b = 0; b < D; ++b)
       if (g->dev_ids[a] != g->dev_ids[b]) {
         int can = 0;
+        bool on = false;
         if (hipDeviceCanAccessPeer(&can, g->dev_ids[a], g->dev_ids[b]) == hipSuccess && can) {
           (void)hipSetDevice(g->dev_ids[a]);
-          (void)hipDeviceEnablePeerAccess(g->dev_ids[b], 0);  // (already enabled: an error we ignore)
+          const hipError_t e = hipDeviceEnablePeerAccess(g->dev_ids[b], 0);  // (already enabled: an error we ignore)
           (void)hipGetLastError();
+          on = e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled;
         }
+        // what SHK_FLAG_GROUP_GRAPH needs: the lead device's kernels dereference every other share's table
+        if (a == 0 && !on && g->graph_peer < 0) g->graph_peer = g->dev_ids[b];
       }
   g->in_bases.resize(D);
   g->in_offsets.resize(D);

@@ -53,8 +53,16 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
           g_run_error = fmt("Duplicate gene name '%s' (from --pcr-primers)", pcr->genes[g].gene_name);
           return SHK_ERR_BAD_ARG;
         }
-    if (rc->n_devices > 1) {
+    if (pcr->context_flags & ~(uint64_t)SHK_FLAG_GROUP_GRAPH) {
+      g_run_error = fmt("shk_pcr_file_config.context_flags 0x%llx: only SHK_FLAG_GROUP_GRAPH is taken", (unsigned long long)pcr->context_flags);
+      return SHK_ERR_BAD_ARG;
+    }
+    if (rc->n_devices > 1 && !(pcr->context_flags & SHK_FLAG_GROUP_GRAPH)) {
       g_run_error = "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)";
+      return SHK_ERR_STATE;
+    }
+    if (rc->n_devices > 1 && pcr->read_threading) {
+      g_run_error = "a multi-device context keeps no reads: --read-threading needs one device";
       return SHK_ERR_STATE;
     }
   }
@@ -93,6 +101,7 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
   cfg.histo_max = rc->histo_max;
   cfg.device = rc->device;
   cfg.table_capacity_hint = rc->table_capacity_hint;
+  if (n_genes) cfg.flags = (uint32_t)pcr->context_flags;
   if (rc->n_devices > 1) {  // one context over several devices; a single device id is just that device
     cfg.n_devices = rc->n_devices;
     cfg.device_ids = rc->device_ids;

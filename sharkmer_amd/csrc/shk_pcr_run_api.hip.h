@@ -84,10 +84,12 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
     const int code = rf == SHK_ERR_BAD_ARG ? rf : rr == SHK_ERR_BAD_ARG ? rr : rf != SHK_OK ? rf : rr;
     if (why) return fail(c, code, "gene %u '%s': %s", g, genes[g].gene_name, why);
   }
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
+  // A multi-device context (SHK_FLAG_GROUP_GRAPH): the calls that take the context take it as it is — the primer scan
+  // goes over the shares, the extension through the share directory, prune and products on the first device — and the
+  // read-side cores run on the lead share rd, the device the public read calls use; on0: their error text to the context.
+  shk_ctx *rd = c->group ? c->group->ctx[0] : c;
+  auto on0 = [&](int rc) { return rc == SHK_OK || !c->group ? rc : group_fail(c, c->group, rc, 0); };
   const bool host = p->reads == SHK_PCR_READS_HOST, retained = p->reads == SHK_PCR_READS_RETAINED;
   if (retained && !c->retain.on) return fail(c, SHK_ERR_STATE, "shk_pcr_run: reads are not retained (shk_retain_reads)");
   const uint64_t *read_index = host ? p->read_index : nullptr;
@@ -143,7 +145,7 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   std::unique_ptr<uint64_t[]> mreads;
   if (na && p->reads != SHK_PCR_READS_NONE) {
     if (host && p->n_seqs) {
-      SHK_TRY(batch_from_host(c, p->bases, p->offsets, p->n_seqs, host_max_len, &batch));  // the one upload of the batch
+      SHK_TRY(on0(batch_from_host(rd, p->bases, p->offsets, p->n_seqs, host_max_len, &batch)));  // the one upload of the batch
       have_batch = true;
     } else if (retained) {
       SHK_TRY(retained_begin(c, "shk_pcr_run"));
@@ -161,12 +163,12 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       foff[a + 1] = fk.size();
     }
     HostKeyRuns pl;
-    SHK_TRY(panel_plan(c, fk.data(), foff.data(), na, &pl));
+    SHK_TRY(on0(panel_plan(rd, fk.data(), foff.data(), na, &pl)));
     uint64_t cap = std::min<uint64_t>(batch.n_seqs * na, 1ull << 22), n_matches = 0;
     for (int attempt = 0; attempt < 2 && !pl.items.empty(); ++attempt) {
       mreads.reset(new uint64_t[std::max<uint64_t>(cap, 1)]);
       std::fill(moff.begin(), moff.end(), 0ull);
-      const int rc = panel_core(c, pl, na, batch, moff.data(), mreads.get(), cap, &n_matches);
+      const int rc = on0(panel_core(rd, pl, na, batch, moff.data(), mreads.get(), cap, &n_matches));
       if (rc == SHK_ERR_BAD_ARG && attempt == 0 && n_matches > cap) {  // (a panel whose lists outgrow 2^22 entries: once more, with room)
         cap = n_matches;
         continue;
@@ -261,10 +263,10 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       shk_thread_panel_out shape{};
       shape.support_total = ttot.data(), shape.support_unambiguous = tuna.data();
       ThreadPanelPlan tp;
-      SHK_TRY(thread_panel_plan(c, tsub.data(), tnoff.data(), tes.data(), tet.data(), teoff.data(), nt, batch.n_seqs, tloff.data(), tlist.data(),
-                                read_index, mate, &shape, &tp));
+      SHK_TRY(on0(thread_panel_plan(rd, tsub.data(), tnoff.data(), tes.data(), tet.data(), teoff.data(), nt, batch.n_seqs, tloff.data(), tlist.data(),
+                                read_index, mate, &shape, &tp)));
       ThreadPanelResult res{ttot.data(), tuna.data(), nullptr, {}, {}, {}, {}, {}};
-      SHK_TRY(thread_panel_core(c, tp, nt, batch, tloff.data(), tlist.data(), read_index, mate, &res, mate_rule));
+      SHK_TRY(on0(thread_panel_core(rd, tp, nt, batch, tloff.data(), tlist.data(), read_index, mate, &res, mate_rule)));
       for (uint32_t t = 0, f = 0; f < nf; ++f) {  // into the layout of the pruned panel
         loff[f + 1] = loff[f];
         if (t == nt || thr[t] != f) continue;

@@ -5,6 +5,7 @@
 // i where the base is not in allowed(P[i]): one bit mask per base and position describes every level at once
 // (tests/test_primer_kmers_cpu.py pins this against literal enumeration).
 #include "shk_primer.h"
+#include "shk_mix.h"
 
 #include <cstdio>
 #include <cstring>
@@ -104,4 +105,17 @@ extern "C" int shk_primer_compile(const shk_primer *p, uint32_t k, uint32_t *tri
   if (n_variants) memcpy(n_variants, pl.level_size, sizeof pl.level_size);
   if (err && err_len) snprintf(err, err_len, "%s", rc == SHK_OK ? "" : msg.c_str());
   return rc;
+}
+
+// The owner share of a canonical k-mer: the top log2(n_owners) bits of its mixed key, which is what home_of reads off
+// hash64 on the device (shk_device.hip.h).
+extern "C" uint32_t shk_key_owner(uint32_t k, uint32_t n_owners, uint64_t canonical_kmer) {
+  if (k == 0 || k >= 32 || n_owners == 0 || n_owners > 64 || (n_owners & (n_owners - 1))) return ~0u;
+  uint32_t owner_bits = 0;
+  while ((1u << owner_bits) < n_owners) ++owner_bits;
+  if (!owner_bits) return 0;
+  const uint32_t bits = 2 * k;
+  const uint64_t kmer = canonical_kmer & (~0ull >> (64 - bits));
+  if (owner_bits > bits) return ~0u;  // (k = 1, 2 with more owners than keys have bits: the engine makes no such context)
+  return (uint32_t)(shk::mix_key(kmer, bits) >> (bits - owner_bits));
 }

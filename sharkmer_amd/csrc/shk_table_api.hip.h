@@ -67,12 +67,40 @@ int compact_owners_launch(shk_ctx *c, uint32_t n_owners, const uint64_t *h_off, 
   return SHK_OK;
 }
 
+// "The table" of a neighbourhood call: the context's own TableRef, or — a multi-device context under
+// SHK_FLAG_GROUP_GRAPH — the share directory, TableRef[2^owner_bits] in the lead share's scratch (rebuilt at every call:
+// shares grow on their own).
+struct NbTableArg {
+  TableRef one{};
+  NbShards shards{nullptr, 0};
+  bool sharded() const { return shards.dir != nullptr; }
+};
+
+// The one launch site of the two kernels that probe the table.  wide == nullptr: k_nb_narrow_panel, one workgroup for
+// each of the n_jobs jobs at (drefs, dctl); else k_nb_wide, the level of h->cur_n entries in list h->cur_sel of job
+// (*wide, dctl).
+void nb_launch(shk_ctx *c, const NbTableArg &tb, const NbRef *drefs, NbCtl *dctl, uint32_t n_jobs, const NbRef *wide, const NbCtl *h) {
+  ScopedTimer t(c, SHK_K_EXTEND);
+  const dim3 grid(wide ? (uint32_t)((h->cur_n * 4 + WG - 1) / WG) : n_jobs), block(wide ? WG : NB_WG);
+  if (wide) {
+    if (tb.sharded())
+      hipLaunchKernelGGL(k_nb_wide<true>, grid, block, 0, c->stream, tb.shards, *wide, dctl, h->cur_sel, (uint64_t)h->cur_n);
+    else
+      hipLaunchKernelGGL(k_nb_wide<false>, grid, block, 0, c->stream, tb.one, *wide, dctl, h->cur_sel, (uint64_t)h->cur_n);
+  } else {
+    if (tb.sharded())
+      hipLaunchKernelGGL(k_nb_narrow_panel<true>, grid, block, 0, c->stream, tb.shards, drefs, dctl);
+    else
+      hipLaunchKernelGGL(k_nb_narrow_panel<false>, grid, block, 0, c->stream, tb.one, drefs, dctl);
+  }
+}
+
 // The level loop of a neighbourhood job that outgrew its workgroup (nb_panel_core: status NB_WIDE): from the state h
 // (which dctl holds too; nb is the host's copy of *dref) until the job stops — complete, at max_levels, or before a
 // level that does not fit.  A narrow launch is k_nb_narrow_panel on this job alone.  Its guard (status NB_RUN, 0 <
 // cur_n <= NB_NARROW) holds at each: the loop comes in with a level wider than NB_NARROW, so a narrow launch always
 // follows a wide level, after which the host uploaded h with status NB_RUN and the cur_n tested here.
-int nb_run_levels(shk_ctx *c, const NbRef &nb, const NbRef *dref, NbCtl *dctl, NbCtl &h) {
+int nb_run_levels(shk_ctx *c, const NbTableArg &tb, const NbRef &nb, const NbRef *dref, NbCtl *dctl, NbCtl &h) {
   // level after level: the narrow kernel while a level fits one workgroup, else one wide launch and a look at its fills
   while (h.status == NB_RUN || h.status == NB_WIDE) {
     if (h.cur_n == 0) {
@@ -84,21 +112,14 @@ int nb_run_levels(shk_ctx *c, const NbRef &nb, const NbRef *dref, NbCtl *dctl, N
       break;
     }
     if (h.cur_n <= NB_NARROW) {
-      {
-        ScopedTimer t(c, SHK_K_EXTEND);
-        hipLaunchKernelGGL(k_nb_narrow_panel, dim3(1), dim3(NB_WG), 0, c->stream, c->tb, dref, dctl);
-      }
+      nb_launch(c, tb, dref, dctl, 1, nullptr, nullptr);
       HIPC(c, hipGetLastError());
       HIPC(c, hipMemcpyAsync(&h, dctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
       HIPC(c, hipStreamSynchronize(c->stream));
       continue;
     }
     const unsigned long long k_start = h.k_n;
-    {
-      ScopedTimer t(c, SHK_K_EXTEND);
-      hipLaunchKernelGGL(k_nb_wide, dim3((uint32_t)((h.cur_n * 4 + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, nb,
-                         dctl, h.cur_sel, (uint64_t)h.cur_n);
-    }
+    nb_launch(c, tb, nullptr, dctl, 1, &nb, &h);
     HIPC(c, hipGetLastError());
     NbCtl r{};
     HIPC(c, hipMemcpyAsync(&r, dctl, sizeof r, hipMemcpyDeviceToHost, c->stream));
@@ -173,7 +194,11 @@ void nb_sorted_out(const uint64_t *hk, const uint32_t *hc, uint64_t nk, uint64_t
 // were checked: job j starts from level 0 seeds[j] (nb_level0's) under min_counts[j], caps[j] and fringe_caps[j]; its
 // k-mers go to (kmers, counts) + out_at[j], its fringe to (fringe_nodes, fringe_dirs) + fr_at[j], its figures to
 // n_out[j], n_fringe[j] and levels_done[j].
-int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
+// g == nullptr: c is the context and the table its own.  Else c is the lead share (share 0) of the multi-device context
+// g: every share is settled on its own device and its stream drained, the directory of their tables goes up with the
+// call's one upload, and the job logic runs as it is on c — its scratch, stream and timing slots; *who: the share whose
+// error text is the call's.
+int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
                   const uint64_t *caps, const uint64_t *fringe_caps, const uint64_t *out_at, const uint64_t *fr_at, uint64_t *kmers,
                   uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
                   uint32_t *levels_done) {
@@ -184,7 +209,20 @@ int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_job
   std::fill(n_fringe, n_fringe + n_jobs, 0ull);
   std::fill(levels_done, levels_done + n_jobs, 0u);
   if (n_all_seeds == 0) return SHK_OK;
-  SHK_TRY(table_read_begin(c));
+  const uint32_t n_shares = g ? g->D : 0;
+  std::vector<TableRef> shares(n_shares);
+  if (g) {
+    for (uint32_t d = 0; d < n_shares; ++d) {  // (a share's table is final once its stream is idle; nothing writes it during the call)
+      *who = d;
+      SHK_TRY(table_read_begin(g->ctx[d]));
+      HIPC(g->ctx[d], hipStreamSynchronize(g->ctx[d]->stream));
+      shares[d] = g->ctx[d]->tb;
+    }
+    *who = 0;
+    HIPC(c, hipSetDevice(c->cfg.device));
+  } else {
+    SHK_TRY(table_read_begin(c));
+  }
   // Device layout: every job's two sets in one region (one clear), then what is uploaded in one copy (NbRef, NbCtl,
   // seed starts, seeds, their jobs), then the lists.  A job without seeds gets no room: it is not run.  The packed
   // copies are for a panel: one job's lists are fetched from where they are.
@@ -203,6 +241,7 @@ int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_job
   const size_t o_sets = m.take<uint64_t>(set_at[n_jobs]);
   const size_t o_refs = m.take<NbRef>(n_jobs), o_ctl = m.take<NbCtl>(n_jobs), o_start = m.take<uint64_t>(n_jobs + 1);
   const size_t o_seeds = m.take<uint64_t>(n_all_seeds), o_sjob = m.take<uint32_t>(n_all_seeds);
+  const size_t o_dir = m.take<TableRef>(n_shares);  // the share directory (a multi-device context's)
   const size_t o_pack = m.take<NbPack>(n_jobs);  // (ends the uploaded block)
   const size_t o_l0 = m.take<uint64_t>(l_at[n_jobs]), o_l1 = m.take<uint64_t>(l_at[n_jobs]);
   const size_t o_km = m.take<uint64_t>(k_at[n_jobs]), o_ct = m.take<uint32_t>(k_at[n_jobs]);
@@ -239,6 +278,14 @@ int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_job
     }
   }
   hstart[n_jobs] = at;
+  NbTableArg tb;
+  tb.one = c->tb;
+  if (g) {
+    std::copy(shares.begin(), shares.end(), (TableRef *)(up.data() + (o_dir - o_refs)));
+    uint32_t owner_bits = 0;
+    while ((1u << owner_bits) < n_shares) ++owner_bits;
+    tb.shards = NbShards{m.at<TableRef>(o_dir), owner_bits};
+  }
   NbRef *drefs = m.at<NbRef>(o_refs);
   NbCtl *dctl = m.at<NbCtl>(o_ctl);
   HIPC(c, hipMemsetAsync(m.at<uint64_t>(o_sets), 0xFF, set_at[n_jobs] * 8, c->stream));  // every set ← EMPTY
@@ -249,17 +296,14 @@ int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_job
                        (const NbRef *)drefs, dctl, (const uint64_t *)m.at<uint64_t>(o_seeds),
                        (const uint32_t *)m.at<uint32_t>(o_sjob), (const uint64_t *)m.at<uint64_t>(o_start), n_all_seeds);
   }
-  {
-    ScopedTimer t(c, SHK_K_EXTEND);
-    hipLaunchKernelGGL(k_nb_narrow_panel, dim3(n_jobs), dim3(NB_WG), 0, c->stream, c->tb, (const NbRef *)drefs, dctl);
-  }
+  nb_launch(c, tb, drefs, dctl, n_jobs, nullptr, nullptr);
   HIPC(c, hipGetLastError());
   std::vector<NbCtl> h(n_jobs);
   HIPC(c, hipMemcpyAsync(h.data(), dctl, (size_t)n_jobs * sizeof(NbCtl), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));  // (also: `up` has been read)
   // the exception: a job with a level wider than a workgroup goes on alone
   for (uint32_t j = 0; j < n_jobs; ++j)
-    if (h[j].status == NB_WIDE) SHK_TRY(nb_run_levels(c, href[j], drefs + j, dctl + j, h[j]));
+    if (h[j].status == NB_WIDE) SHK_TRY(nb_run_levels(c, tb, href[j], drefs + j, dctl + j, h[j]));
   std::vector<NbPack> pk(n_jobs);
   uint64_t tot_k = 0, tot_f = 0;
   for (uint32_t j = 0; j < n_jobs; ++j) {
@@ -303,6 +347,27 @@ int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_job
     n_fringe[j] = p.n_f;
     levels_done[j] = h[j].levels_done;
   }
+  return SHK_OK;
+}
+
+int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
+                  const uint64_t *caps, const uint64_t *fringe_caps, const uint64_t *out_at, const uint64_t *fr_at, uint64_t *kmers,
+                  uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
+                  uint32_t *levels_done) {
+  shk_group *g = c->group;
+  uint32_t who = 0;
+  const int rc = nb_panel_run(g ? g->ctx[0] : c, g, &who, seeds, n_jobs, min_counts, max_levels, caps, fringe_caps, out_at, fr_at, kmers, counts,
+                              n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
+  return rc == SHK_OK || !g ? rc : group_fail(c, g, rc, who);
+}
+
+// How the four graph calls refuse or open on a multi-device context (`name`: the call's) — and refuse an owner share.
+int graph_call_begin(shk_ctx *c, const char *name) {
+  if (c->group && !(c->cfg.flags & SHK_FLAG_GROUP_GRAPH))
+    return fail(c, SHK_ERR_STATE, "%s needs the whole table on one device: this is a multi-device context (n_devices > 1)", name);
+  if (c->group) return group_graph_begin(c);
+  if (c->n_owners > 1)
+    return fail(c, SHK_ERR_STATE, "%s needs the whole table on one device: this context is an owner share (n_owners > 1)", name);
   return SHK_OK;
 }
 
@@ -398,10 +463,7 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
                      uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
                      uint32_t *levels_done) {
   if (!c || !n_out || !n_fringe || !levels_done || (n_seeds && (!nodes || !dirs))) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  SHK_TRY(graph_call_begin(c, "shk_neighborhood"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
   if ((cap && (!kmers || !counts)) || (fringe_cap && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
@@ -422,10 +484,7 @@ int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_co
                    uint32_t *threshold_used, uint32_t *steps_run) {
   if (!c || !p || !n_nodes || !n_edges || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
   if ((n_fwd && (!fwd_kmers || !fwd_counts)) || (n_rev && (!rev_kmers || !rev_counts))) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  SHK_TRY(graph_call_begin(c, "shk_pcr_extend"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
   const uint64_t kmask = ~0ull >> (64 - 2 * k);
@@ -453,10 +512,7 @@ int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dir
                            uint64_t *n_fringe, uint32_t *levels_done) {
   using ull = unsigned long long;
   if (!c) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_neighborhood_panel needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  SHK_TRY(graph_call_begin(c, "shk_neighborhood_panel"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
   if (n_jobs > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_jobs %u above SHK_PCR_MAX_GENES (%u)", n_jobs, (unsigned)SHK_PCR_MAX_GENES);
@@ -490,10 +546,7 @@ int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_
                          uint32_t *steps_run) {
   using ull = unsigned long long;
   if (!c || !node_offsets || !edge_offsets) return SHK_ERR_BAD_ARG;
-  if (c->group)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)");
-  if (c->n_owners > 1)
-    return fail(c, SHK_ERR_STATE, "shk_pcr_extend_panel needs the whole table on one device: this context is an owner share (n_owners > 1)");
+  SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
   if (n_genes > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", n_genes, (unsigned)SHK_PCR_MAX_GENES);

@@ -39,6 +39,7 @@ def _bgzf_flags(bgzf) -> int:
         raise ValueError(f"bgzf must be None, 'host' or 'device', not {bgzf!r}")
     return FASTQ_BGZF_BATCH if bgzf == "host" else FASTQ_BGZF_DEVICE
 FLAG_DEFER_ERRORS = 8  # host-buffer ingests return once queued; errors surface at the next call (include/shk.h)
+FLAG_GROUP_GRAPH = 32  # a multi-device context answers the graph extension calls and pcr_run (opt-in; include/shk.h)
 
 KERNEL_NAMES = ["mark", "scan", "direct", "scatter", "pages", "histo", "grow", "insert",
                 "lookup", "export", "synth", "merge", "pcount", "pscan", "histo_rows", "extend"]
@@ -461,7 +462,7 @@ class _PcrGeneStat(C.Structure):
 
 class _PcrFileConfig(C.Structure):
     _fields_ = [("genes", C.POINTER(_PcrGene)), ("n_genes", C.c_uint32), ("min_kmer_count", C.c_uint32), ("read_threading", C.c_uint32),
-                ("dump", C.c_uint32), ("node_budget_global", C.c_uint64), ("reserved", C.c_uint64 * 4)]
+                ("dump", C.c_uint32), ("node_budget_global", C.c_uint64), ("context_flags", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
 PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET = range(6)  # SHK_PCR_* (include/shk.h)
@@ -641,6 +642,7 @@ ABI_SYMBOLS = [
     "shk_thread_reads_panel_retained",
     "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
     "shk_pcr_run", "shk_write_fasta", "shk_write_stats_yaml_pcr", "shk_run_files_pcr",
+    "shk_key_owner",
 ]
 
 _lib = None
@@ -2211,12 +2213,14 @@ def validate_args(k: int, histo_max: int, sample):
 def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", histo_max: int = 10000,
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
               command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
-              bgzf=None, parse=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0, **tuning) -> dict:
+              bgzf=None, parse=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0,
+              group_graph: bool = False, **tuning) -> dict:
     """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
     strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
     tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
     max_primer_kmers, high_coverage_ratio, tip_coverage_fraction), which overwrite every gene's values.
-    device_ids: run on one multi-device context (shk_run_config.n_devices).  gzip_all_members, bgzf: see FastqReader
+    device_ids: run on one multi-device context (shk_run_config.n_devices); with pcr_primers that needs group_graph=True
+    (SHK_FLAG_GROUP_GRAPH) and no read_threading.  gzip_all_members, bgzf: see FastqReader
     (bgzf="device" decodes on the context's first device).  parse="device" (with bgzf="device" only): the decoded text
     stays on the device and is framed there (SHK_FASTQ_DEVICE_PARSE); a file the route gives up on is read the
     bgzf="device" way from its start."""
@@ -2250,7 +2254,8 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
         if min_kmer_count < 1:
             raise ShkError(-2, "min-kmer-count must be at least 1")
         arr = _pcr_genes(genes)
-        pcfg = _PcrFileConfig(arr, len(genes), min_kmer_count, 1 if read_threading else 0, 0, node_budget_global)
+        pcfg = _PcrFileConfig(arr, len(genes), min_kmer_count, 1 if read_threading else 0, 0, node_budget_global,
+                              FLAG_GROUP_GRAPH if group_graph else 0)
         rc = L.shk_run_files_pcr(C.byref(cfg), C.byref(pcfg), C.byref(st), None)
     else:
         rc = L.shk_run_files(C.byref(cfg), C.byref(st))
