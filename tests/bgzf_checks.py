@@ -81,3 +81,58 @@ def check_damaged(tmp_path, monkeypatch, name, route, stat):
     monkeypatch.setenv("SHK_BGZF_BATCH_KB", "7")
     got = read_all(p, bgzf=route)
     assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2] and got[3][stat] == n_front
+
+
+LENIENT = bc.lenient_cases()
+
+
+def check_lenient(tmp_path, monkeypatch, name, route, stat):
+    """A stream zlib refuses and our decoders take by one shared rule: the batched route hands out what the
+    all-members reader hands out — the same reads, or the same error — and where the stream decodes, it decodes in the
+    batch, to the bytes its tokens expand to (the trailer's CRC-32 is theirs)."""
+    data, at, decodes = LENIENT[name]
+    monkeypatch.delenv("SHK_BGZF_BATCH_KB", raising=False)
+    p = str(tmp_path / "lenient.fastq.gz")
+    open(p, "wb").write(data)
+    want = read_all(p, gzip_all_members=True)
+    got = read_all(p, bgzf=route)
+    assert got[:3] == want[:3]
+    assert (want[1] is None) == decodes
+    if decodes:
+        assert want[3]["sequential"] == at + 2 and got[3] == {"device": 0, "host_batch": 0, "sequential": 0, stat: at + 2}
+    else:
+        assert got[3][stat] == at and got[3]["sequential"] == want[3]["sequential"] - at
+
+
+def interleaved_file():
+    """(file bytes, n_members): every crafted valid member among ordinary ones of one record each — neighbouring
+    waves of a workgroup on very different streams."""
+    recs = [r + b"\n" for r in bc.SMALL.split(b"\n@")]
+    recs = [recs[0]] + [b"@" + r for r in recs[1:]]
+    recs[-1] = recs[-1][:-1]
+    assert b"".join(recs) == bc.SMALL
+    plain = [bc.bgzf_member(r, level=(1, 6, 9)[i % 3]) for i, r in enumerate(recs)]
+    crafted = [m for name, (ms, _t) in bc.crafted_members().items() if name != "craft_alignment" for m in ms]
+    every = len(plain) // len(crafted)
+    out = []
+    for i, m in enumerate(plain):
+        out.append(m)
+        if i % every == every - 1 and crafted:
+            out.append(crafted.pop(0))
+    out += crafted + [bc.EOF_MEMBER]
+    return b"".join(out), len(out)
+
+
+def check_interleaved(orc, tmp_path, monkeypatch, route, stat, batch_kb):
+    data, n_members = interleaved_file()
+    assert n_members <= 300
+    monkeypatch.delenv("SHK_BGZF_BATCH_KB", raising=False)
+    if batch_kb:
+        monkeypatch.setenv("SHK_BGZF_BATCH_KB", str(batch_kb))
+    p = str(tmp_path / "mix.fastq.gz")
+    open(p, "wb").write(data)
+    want = read_all(p, gzip_all_members=True)
+    got = read_all(p, bgzf=route)
+    assert want[1] is None and got[:3] == want[:3]
+    assert got[3] == {"device": 0, "host_batch": 0, "sequential": 0, stat: n_members}
+    assert product_counts(orc, p, *got[:3]) == oracle_counts(orc, p)

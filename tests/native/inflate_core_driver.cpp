@@ -5,6 +5,8 @@
 //   inflate_core_driver damage SEED N FILE   every truncation length of the first, a middle and the last non-empty
 //                                            member, then N single-bit flips and N random-byte overwrites of members
 //                                            drawn with SEED: each must return a status
+//   inflate_core_driver expect LIST          LIST: lines "path member_index status"; that member, at each of the four
+//                                            alignments, must return exactly that status (all are printed)
 // Every decode runs with the compressed bytes in an allocation that ends where the stated slack ends, the output slot
 // between guard bytes, and a step count held against STEP_FACTOR · (in_len + out_len) + STEP_FLOOR.  Damage may decode
 // "ok" to wrong bytes (a member's CRC-32 catches that, not the decoder): asserted are memory safety, termination, and
@@ -181,6 +183,37 @@ int main(int argc, char **argv) {
            max_steps_per_byte_x100 / 100.0);
     return 0;
   }
-  fprintf(stderr, "usage: %s clean FILE... | damage SEED N FILE\n", argv[0]);
+  if (argc == 3 && !strcmp(argv[1], "expect")) {
+    FILE *lf = fopen(argv[2], "r");
+    if (!lf) return 2;
+    char path[4096];
+    unsigned index, want;
+    size_t n_lines = 0, n_bad = 0;
+    while (fscanf(lf, "%4095s %u %u", path, &index, &want) == 3) {
+      const std::vector<uint8_t> f = slurp(path);
+      const std::vector<Member> ms = members_of(f);
+      if (index >= ms.size()) {
+        fprintf(stderr, "%s has no member %u\n", path, index);
+        return 2;
+      }
+      const Member &m = ms[index];
+      printf("%s %u want %u got", path, index, want);
+      for (uint32_t align = 0; align < 4; ++align) {
+        const Result r = decode(f.data() + m.body, m.body_len, m.isize, align);
+        printf(" %u", r.status);
+        n_bad += r.status != want;
+      }
+      printf("\n");
+      ++n_lines;
+    }
+    fclose(lf);
+    if (n_bad) {
+      fprintf(stderr, "%zu statuses are not the expected ones\n", n_bad);
+      return 1;
+    }
+    printf("expect ok: %zu members at 4 alignments, at most %.2f steps per byte\n", n_lines, max_steps_per_byte_x100 / 100.0);
+    return 0;
+  }
+  fprintf(stderr, "usage: %s clean FILE... | damage SEED N FILE | expect LIST\n", argv[0]);
   return 2;
 }

@@ -12,7 +12,7 @@ import pytest
 import sharkmer_amd as sa
 
 import bgzf_cases as bc
-from bgzf_checks import CLEAN, DAMAGED, check_clean, check_damaged, read_all
+from bgzf_checks import CLEAN, DAMAGED, LENIENT, check_clean, check_damaged, check_interleaved, check_lenient, read_all
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROUTE, STAT = "host", "host_batch"
@@ -75,3 +75,13 @@ def test_new_symbols_are_exported_and_listed():
     hdr = open(os.path.join(os.path.dirname(G), "..", "include", "shk.h")).read()
     assert "#define SHK_FASTQ_BGZF_BATCH 2u" in hdr and "#define SHK_FASTQ_BGZF_DEVICE 4u" in hdr
     assert sa.engine.FASTQ_BGZF_BATCH == 2 and sa.engine.FASTQ_BGZF_DEVICE == 4
+
+
+@pytest.mark.parametrize("name", sorted(LENIENT))
+def test_lenient_stream_reads_the_same_in_host_batches(tmp_path, monkeypatch, name):
+    check_lenient(tmp_path, monkeypatch, name, ROUTE, STAT)
+
+
+@pytest.mark.parametrize("batch_kb", [7, None])
+def test_crafted_members_among_ordinary_ones_in_host_batches(orc, tmp_path, monkeypatch, batch_kb):
+    check_interleaved(orc, tmp_path, monkeypatch, ROUTE, STAT, batch_kb)

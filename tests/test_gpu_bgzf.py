@@ -13,7 +13,7 @@ import yaml
 
 import bgzf_cases as bc
 import sharkmer_amd as sa
-from bgzf_checks import CLEAN, DAMAGED, check_clean, check_damaged, read_all
+from bgzf_checks import CLEAN, DAMAGED, LENIENT, check_clean, check_damaged, check_interleaved, check_lenient, read_all
 
 pytestmark = pytest.mark.gpu
 
@@ -140,3 +140,32 @@ def test_retained_reads_see_the_same_reads(tmp_path, orc):
     assert (tmp_path / "dev" / "s_18s.fasta").read_bytes() == (tmp_path / "all" / "s_18s.fasta").read_bytes()
     assert len((tmp_path / "dev" / "s_18s.fasta").read_bytes()) > 100
     assert outputs(tmp_path / "dev", "s") == outputs(tmp_path / "all", "s")
+
+
+def test_crafted_members_at_every_alignment_decode_on_the_device(orc, tmp_path, monkeypatch):
+    """bgzf_cases.alignment_members: the deep-code and the block-mix member at file offsets ≡ 0, 1, 2, 3 (mod 4) in one
+    batch.  bgzf_plan_batch does not re-align bodies — a job's in_offset is the body's offset from the batch's first
+    byte — so these offsets are what the kernel's dword loads and its seek after a stored block see."""
+    data, n_members, _env, _text = CLEAN["craft_alignment"]
+    offs, at = set(), 0
+    for m in bc.alignment_members()[0]:
+        if len(m) > 600:
+            offs.add((len(m) > 5000, at % 4))
+        at += len(m)
+    assert offs == {(big, r) for big in (False, True) for r in range(4)}
+    p = str(tmp_path / "alignment.fastq.gz")
+    open(p, "wb").write(data)
+    monkeypatch.delenv("SHK_BGZF_BATCH_KB", raising=False)
+    got = read_all(p, bgzf="device")
+    assert got[1] is None and got[3]["device"] == n_members and got[3]["sequential"] == 0
+    check_clean(orc, tmp_path, monkeypatch, "craft_alignment", ROUTE, STAT)
+
+
+@pytest.mark.parametrize("name", sorted(LENIENT))
+def test_lenient_stream_reads_the_same_on_the_device(tmp_path, monkeypatch, name):
+    check_lenient(tmp_path, monkeypatch, name, ROUTE, STAT)
+
+
+@pytest.mark.parametrize("batch_kb", [7, None])
+def test_crafted_members_among_ordinary_ones_on_the_device(orc, tmp_path, monkeypatch, batch_kb):
+    check_interleaved(orc, tmp_path, monkeypatch, ROUTE, STAT, batch_kb)

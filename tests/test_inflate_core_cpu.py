@@ -49,3 +49,36 @@ def test_damaged_members_give_a_status(driver, tmp_path, level, strategy):
     p.write_bytes(b"".join(ms))
     out = run(driver, "damage", "20261020", "1500", str(p))
     assert out.startswith("damage ok:"), out
+
+
+def test_rejected_crafted_members_give_their_status(driver, tmp_path):
+    """bgzf_cases.rejected_members(): every one the status it was built for, at all four alignments — and the lenient
+    members, which the core takes or refuses as the table says."""
+    lines = []
+    for name, (member, status) in bc.rejected_members().items():
+        p = tmp_path / f"{name}.gz"
+        p.write_bytes(member)
+        lines.append(f"{p} 0 {status}")
+    for name, (data, at, decodes) in bc.lenient_cases().items():
+        p = tmp_path / f"lenient_{name}.gz"
+        p.write_bytes(data)
+        lines.append(f"{p} {at} {bc.INFC_OK if decodes else bc.INFC_CORRUPT}")
+    lst = tmp_path / "expect.txt"
+    lst.write_text("\n".join(lines) + "\n")
+    out = run(driver, "expect", str(lst))
+    assert out.splitlines()[-1].startswith(f"expect ok: {len(lines)} members"), out
+    for want, n in ((bc.INFC_CORRUPT, 14), (bc.INFC_INPUT_EXHAUSTED, 2), (bc.INFC_OUTPUT_OVER, 3), (bc.INFC_OUTPUT_SHORT, 1), (bc.INFC_INPUT_LEFT, 1)):
+        assert sum(1 for _m, s in bc.rejected_members().values() if s == want) == n
+
+
+def test_damaged_crafted_members_give_a_status(driver, tmp_path):
+    """Truncations, bit flips and overwrites of the crafted valid members: the damage lands in 15-bit code words, maximal
+    headers and chains of stored blocks.  Small members only for the every-truncation part (the driver takes the first,
+    a middle and the last member of the file)."""
+    order = ["craft_max_header", "craft_no_dist_code", "craft_one_dist_code", "craft_stage_borders", "craft_overlap", "craft_block_mix",
+             "craft_all_symbols", "craft_deep_codes"]
+    ms = [m for name in order for m in bc.crafted_members()[name][0]]
+    p = tmp_path / "crafted.gz"
+    p.write_bytes(b"".join(ms))
+    out = run(driver, "damage", "20261020", "600", str(p))
+    assert out.startswith("damage ok:"), out
