@@ -14,6 +14,7 @@
 #include "shk_products.h"
 #include "shk_dedup_core.h"
 #include "shk_retain_core.h"
+#include "shk_ingest_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -25,6 +26,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -313,7 +315,7 @@ struct shk_ctx {
   DevBuf in_bases, in_offsets, st_bases[NST], st_offsets[NST], startbits, tiles, spillA, spillB, misc, part, part2, part3, part_meta;
   DevBuf pk_stage[NST], nm_stage[NST], nz_dev[NST], pk_ascii;
   DevBuf xw_kmers, xw_lanes, xw_count;  // the wide exchange round's output (shk_xchg_wide_scatter_device)
-  HostBuf hp_pk[NST], hp_nm[NST];  // ASCII host batches packed on the host (ingest_host): a slice's 2-bit stream and N mask, pinned
+  HostBuf hp_pk, hp_nm;  // ASCII host batches packed on the host (ingest_host): the 2-bit streams and N masks of a call's slices, pinned
   HostBuf nz_host[NST];             // … and the non-zero words of a slice's N mask, when they are few (index, word)  // packed input: the staged streams of a slice; a whole batch unpacked (device-resident packed ingest)
   DevBuf xbuf, xspill;            // owner layout: the level-1 records of a launch by [owner][lane][super-page]; the foreign spill list
   DevBuf xbuf_alt, part_meta_alt;  // the OTHER exchange buffer and cursor block: shk_xchg_scatter_device takes the two in turn
@@ -2383,7 +2385,8 @@ void shk_destroy(shk_ctx *c) {
   c->xw_count.release();
   c->fh_partial.release();
   c->fh_tot.release();
-  for (int i = 0; i < shk_ctx::NST; ++i) c->pk_stage[i].release(), c->nm_stage[i].release(), c->nz_dev[i].release(), c->nz_host[i].release(), c->hp_pk[i].release(), c->hp_nm[i].release();
+  for (int i = 0; i < shk_ctx::NST; ++i) c->pk_stage[i].release(), c->nm_stage[i].release(), c->nz_dev[i].release(), c->nz_host[i].release();
+  c->hp_pk.release(), c->hp_nm.release();
   c->pk_ascii.release();
   c->fq_tiles.release(), c->fq_lines.release(), c->fq_recs.release(), c->fq_ctrl.release(), c->fq_offs.release(), c->fq_hctrl.release();
   for (hipEvent_t e : c->fq_ev)
@@ -2459,46 +2462,14 @@ int shk_reset(shk_ctx *c) {
 // overlap").  Striping is unaffected: ingest_core advances the running read index per slice.
 // packed != nullptr: the batch comes as the 2-bit stream + N mask of shk_pack_reads (offsets count BASES of
 // that stream); every slice's share of both crosses PCIe instead of its ASCII bytes and is unpacked in HBM.
-// The non-zero words of an N mask as (index, word) pairs — on a few threads: the caller is between two slices of
-// a host-buffer ingest, with the link busy and nothing else to do.  Returns the number of pairs, or ~0 when
-// there are more than `cap` (the mask then crosses the link as it is).
-static size_t nmask_nonzero(const uint32_t *w, size_t n, uint32_t *pairs, size_t cap) {
-  const unsigned T = (unsigned)std::max(1, std::min(8, (int)(n >> 18)));  // ≥ 1 MiB of mask per thread
-  std::vector<size_t> cnt(T, 0);
-  const size_t seg = cap / T;
-  auto work = [&](unsigned t) {
-    const size_t a = n * t / T, b = n * (t + 1) / T;
-    uint32_t *out = pairs + 2 * seg * t;
-    size_t k = 0;
-    size_t i = a;
-    for (; i < b && (i & 1); ++i)
-      if (w[i]) { if (k < seg) out[2 * k] = (uint32_t)i, out[2 * k + 1] = w[i]; ++k; }
-    for (; i + 8 <= b; i += 8) {  // (64-bit loads: the mask is 4-byte aligned, i is even here — and the host tolerates the rest)
-      uint64_t q[4];
-      memcpy(q, w + i, 32);
-      if ((q[0] | q[1] | q[2] | q[3]) == 0) continue;
-      for (size_t j = i; j < i + 8; ++j)
-        if (w[j]) { if (k < seg) out[2 * k] = (uint32_t)j, out[2 * k + 1] = w[j]; ++k; }
-    }
-    for (; i < b; ++i)
-      if (w[i]) { if (k < seg) out[2 * k] = (uint32_t)i, out[2 * k + 1] = w[i]; ++k; }
-    cnt[t] = k;
-  };
-  if (T == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < T; ++t) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
-  }
-  size_t total = 0;
-  for (unsigned t = 0; t < T; ++t) {
-    if (cnt[t] > seg) return ~(size_t)0;
-    if (t && cnt[t]) memmove(pairs + 2 * total, pairs + 2 * seg * t, cnt[t] * 8);
-    total += cnt[t];
-  }
-  return total;
+// What is arithmetic or threading in it — the slice cuts, the ring of staging sets, a slice's extents in the packed
+// streams, the packer thread, the list form of a sparse N mask — is shk_ingest_plan.h, which runs without a device.
+// The kind of memory a pointer of the caller's names (ordinary host memory, which HIP may not know at all: not an error).
+static hipMemoryType pointer_kind(const void *p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) == hipSuccess) return at.type;
+  (void)hipGetLastError();
+  return hipMemoryTypeUnregistered;
 }
 
 static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
@@ -2517,9 +2488,9 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
   // quarter of that.
   // An ASCII batch is PACKED ON THE HOST, slice by slice, when the host has the cores for it (2-bit stream + N mask by
   // shk_pack_reads' AVX2 converter, ≈ 77 Gbases/s on 16 cores, into pinned staging, by a thread of its own that runs
-  // ahead of the copies and the counting): the link moves 52 GB/s = 52 Gbases/s of ASCII out of pinned memory and 41
-  // out of pageable memory, and 0.3 B per base of a packed slice — and an invalid byte is found, and reported with the
-  // same text, before anything of its slice is copied.  SHK_HOST_PACK=0 / 1 pins the choice.
+  // ahead of the copies and the counting — HostPacker): the link moves 52 GB/s = 52 Gbases/s of ASCII out of pinned
+  // memory and 41 out of pageable memory, and 0.3 B per base of a packed slice — and an invalid byte is found, and
+  // reported with the same text, before anything of its slice is copied.  SHK_HOST_PACK=0 / 1 pins the choice.
   const int hp_env = env_int("SHK_HOST_PACK", -1);
   bool hp = false;
   if (!packed && bases && n_bases_all) {
@@ -2530,34 +2501,13 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
       // for a batch in PAGEABLE memory — 41 → 50-52 Gbases/s; out of pinned memory the gain over the link's 52 is small
       // (55; config 3's stream 43.6 against 41.7: in line the packing runs at ≈ 55, not 77 — it shares the host's
       // memory bus with the copies) and a busy host would turn it into a loss
-      hipPointerAttribute_t at{};
-      if (hipPointerGetAttributes(&at, bases) == hipSuccess) hp = at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged && at.type != hipMemoryTypeDevice;
-      else (void)hipGetLastError(), hp = true;  // (ordinary host memory: not an error)
+      const hipMemoryType kind = pointer_kind(bases);
+      hp = kind != hipMemoryTypeHost && kind != hipMemoryTypeManaged && kind != hipMemoryTypeDevice;
     }
   }
   const uint64_t slice_kb = (uint64_t)env_int("SHK_SLICE_KB", packed ? 256 << 10 : 128 << 10);  // test hook: tiny slices
-  const uint64_t slice_bases = slice_kb << 10;
-  // slice boundaries at read boundaries, ≈ slice_bases each
-  std::vector<uint64_t> cut{0};
-  while (cut.back() < n_seqs) {
-    uint64_t lo = cut.back(), hi = n_seqs;
-    const uint64_t limit = offsets[lo] + (lo == 0 && (packed || hp) ? std::max<uint64_t>(slice_bases / 4, 1) : slice_bases);
-    if (offsets[n_seqs] > limit) {  // largest hi with offsets[hi] ≤ limit, at least one read
-      hi = (uint64_t)(std::upper_bound(offsets + lo, offsets + n_seqs + 1, limit) - offsets) - 1;
-      if (hi <= lo) hi = lo + 1;
-    }
-    cut.push_back(hi);
-  }
+  const std::vector<uint64_t> cut = slice_cuts(offsets, n_seqs, slice_kb << 10, packed || hp);
   const size_t n_slices = cut.size() - 1;
-  if (!c->copy_stream) HIPC(c, stream_take(&c->copy_stream));
-  if (!c->copy_done[0])
-    for (int i = 0; i < shk_ctx::NST; ++i) HIPC(c, hipEventCreateWithFlags(&c->copy_done[i], hipEventDisableTiming));
-  bool offsets_pinned = false;
-  {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, offsets) == hipSuccess) offsets_pinned = at.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();  // (ordinary host memory: not an error)
-  }
   // NST staging sets, taken in turn across slices and across calls: while slice i is counted, the copies of slices
   // i+1 … i+NST−1 are queued on the copy stream, so the link does not wait for the host to come back from a counting
   // launch — nor from a deferred page pass of a large table, which holds the host for several slices' worth of copy
@@ -2566,101 +2516,58 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
   // A call of few slices takes few sets (at least two: one may still be read by the previous call's last launch):
   // a stream of one-slice calls — shk_run_files' 64 M-base batches — allocates two sets, not six (and frees two:
   // tearing the context down was 14 ms of an 80 ms job with all six in use).
-  const int NST = (int)std::min<size_t>(shk_ctx::NST, std::max<size_t>(n_slices + 1, 2));
-  const uint32_t s0 = c->stage_last >= 0 ? (uint32_t)(c->stage_last + 1) % (uint32_t)NST : 0u;
-  auto set_of = [&](size_t i) { return (int)((s0 + i) % (uint32_t)NST); };
-  auto bases_of = [&](int sel) -> DevBuf & { return c->st_bases[sel]; };
-  auto offs_of = [&](int sel) -> DevBuf & { return c->st_offsets[sel]; };
-  // Host packing: ONE thread of its own packs the call's slices, in order, each into its own stretch of the call's
-  // pinned staging (shk_pack_reads: all the host's cores per slice), and says how far it has come; this thread sends
-  // what is packed and counts what has arrived — a deferred page pass that holds it up does not hold the packing up.
-  std::vector<size_t> hp_pk_off, hp_nm_off;
-  std::mutex hp_m;
-  std::condition_variable hp_cv;
-  size_t hp_done = 0;      // slices packed so far
-  int hp_rc = SHK_OK;      // … or the packer's error (an invalid byte: the run is over)
-  std::string hp_err;
-  bool hp_quit = false;
-  std::thread hp_thread;
-  struct HpJoin {  // (every way out of this function goes past the packer)
-    std::thread &t;
-    std::mutex &m;
-    bool &quit;
-    ~HpJoin() {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        quit = true;
-      }
-      if (t.joinable()) t.join();
+  const StageRing ring(n_slices, c->stage_last, shk_ctx::NST);
+  const size_t NST = (size_t)ring.nst;
+  // (sets s0 … s0+NST−2 were last read by launches that a later launch of the previous call has waited for)
+  HostPackLayout lay;
+  std::optional<HostPacker> packer;
+  // The one way out with an error, a HIP error included: no copy is left behind that reads `h_rebased` or the packer's
+  // staging — the copy stream is drained, then the packer is stopped.
+  struct Drain {
+    shk_ctx *c;
+    bool armed = true;
+    ~Drain() {
+      if (armed && c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     }
-  } hp_join{hp_thread, hp_m, hp_quit};
+  } drain{c};
+  if (!c->copy_stream) HIPC(c, stream_take(&c->copy_stream));
+  if (!c->copy_done[0])
+    for (int i = 0; i < shk_ctx::NST; ++i) HIPC(c, hipEventCreateWithFlags(&c->copy_done[i], hipEventDisableTiming));
+  const bool offsets_pinned = pointer_kind(offsets) == hipMemoryTypeHost;
   if (hp) {
-    size_t pk_total = 0, nm_total = 0;
-    for (size_t j = 0; j < n_slices; ++j) {
-      const uint64_t nb = offsets[cut[j + 1]] - offsets[cut[j]];
-      hp_pk_off.push_back(pk_total);
-      hp_nm_off.push_back(nm_total);
-      pk_total += (size_t)((nb / 4 + 64 + 63) & ~63ull);
-      nm_total += (size_t)(((nb / 32 + 2) * 4 + 63) & ~63ull);
-    }
-    HIPC(c, c->hp_pk[0].ensure(pk_total));  // (free: every copy out of them was waited for before the call that made it returned)
-    HIPC(c, c->hp_nm[0].ensure(nm_total));
-    hp_thread = std::thread([&] {
-      for (size_t j = 0; j < n_slices; ++j) {
-        {
-          std::lock_guard<std::mutex> lk(hp_m);
-          if (hp_quit) return;
-        }
-        const uint64_t o0 = offsets[cut[j]], nb = offsets[cut[j + 1]] - o0;
-        int prc = SHK_OK;
-        if (nb) prc = shk_pack_reads(bases + o0, nb, (uint8_t *)c->hp_pk[0].p + hp_pk_off[j], (uint32_t *)((uint8_t *)c->hp_nm[0].p + hp_nm_off[j]), 0);
-        std::lock_guard<std::mutex> lk(hp_m);
-        if (prc != SHK_OK) {
-          hp_rc = prc;
-          hp_err = shk_run_error();  // (this thread's own message buffer)
-          hp_cv.notify_all();
-          return;
-        }
-        hp_done = j + 1;
-        hp_cv.notify_all();
-      }
-    });
+    lay = HostPackLayout(offsets, cut);
+    HIPC(c, c->hp_pk.ensure(lay.pk_total));  // (free: every copy out of them was waited for before the call that made it returned)
+    HIPC(c, c->hp_nm.ensure(lay.nm_total));
+    packer.emplace(bases, offsets, cut, lay, (uint8_t *)c->hp_pk.p, (uint8_t *)c->hp_nm.p);
   }
-  // slices [0, n) packed?  block: wait for slice n − 1 (or the packer's error, which is this call's)
-  auto hp_packed = [&](bool block, size_t need) -> size_t {
-    std::unique_lock<std::mutex> lk(hp_m);
-    if (block) hp_cv.wait(lk, [&] { return hp_done >= need || hp_rc != SHK_OK; });
-    return hp_done;
-  };
-  size_t hp_issued = 0;  // slices whose copies have been queued (host packing)
   auto issue_copy = [&](size_t i) -> int {
-    const int bsel = set_of(i);
+    const int bsel = ring.set_of(i);
     const uint64_t r0 = cut[i], r1 = cut[i + 1];
     const uint64_t o0 = offsets[r0], nb = offsets[r1] - o0, ns = r1 - r0;
-    DevBuf &db = bases_of(bsel);
-    DevBuf &dof = offs_of(bsel);
+    DevBuf &db = c->st_bases[bsel];
+    DevBuf &dof = c->st_offsets[bsel];
     HIPC(c, db.ensure(nb + 64));
     HIPC(c, dof.ensure((ns + 1) * 8));
     const uint8_t *pk_src = packed;
     const uint32_t *nm_src = nmask;
     uint64_t o_rel = o0;  // the slice's first base in the packed streams
     if (nb && hp) {  // (the packer thread has finished this slice: the caller checked)
-      pk_src = (const uint8_t *)c->hp_pk[0].p + hp_pk_off[i];
-      nm_src = (const uint32_t *)((const uint8_t *)c->hp_nm[0].p + hp_nm_off[i]);
+      pk_src = (const uint8_t *)c->hp_pk.p + lay.pk_off[i];
+      nm_src = (const uint32_t *)((const uint8_t *)c->hp_nm.p + lay.nm_off[i]);
       o_rel = 0;
     }
     if (nb && pk_src) {  // the slice's bytes of the 2-bit stream and words of the N mask (+ pad: k_unpack reads a few bytes on)
-      const uint64_t b0 = o_rel >> 2, b1 = (o_rel + nb + 3) >> 2, w0 = o_rel >> 5, w1 = (o_rel + nb + 31) >> 5;
-      HIPC(c, c->pk_stage[bsel].ensure(b1 - b0 + 16));
-      HIPC(c, c->nm_stage[bsel].ensure((w1 - w0 + 2) * 4));
-      HIPC(c, hipMemcpyAsync(c->pk_stage[bsel].p, pk_src + b0, b1 - b0, hipMemcpyHostToDevice, c->copy_stream));
+      const PackedExtent x(o_rel, nb);
+      HIPC(c, c->pk_stage[bsel].ensure(x.b1 - x.b0 + 16));
+      HIPC(c, c->nm_stage[bsel].ensure((x.w1 - x.w0 + 2) * 4));
+      HIPC(c, hipMemcpyAsync(c->pk_stage[bsel].p, pk_src + x.b0, x.b1 - x.b0, hipMemcpyHostToDevice, c->copy_stream));
       // the N mask: a bit per base, a third of the slice's bytes — and nearly all zeros on most data.  When at
       // most 1/16 of its words are non-zero they cross the link as a list and the rest is cleared on the device.
-      const size_t nw = (size_t)(w1 - w0), list_cap = nw / 16 + 64;
+      const size_t nw = (size_t)(x.w1 - x.w0), list_cap = nw / 16 + 64;
       size_t nz = ~(size_t)0;
       if (nw >= (1u << 16) && env_int("SHK_NMASK_SPARSE", 1)) {
         HIPC(c, c->nz_host[bsel].ensure(list_cap * 8));
-        nz = nmask_nonzero(nm_src + w0, nw, (uint32_t *)c->nz_host[bsel].p, list_cap);
+        nz = nmask_nonzero(nm_src + x.w0, nw, (uint32_t *)c->nz_host[bsel].p, list_cap);
       }
       if (nz != ~(size_t)0) {
         HIPC(c, hipMemsetAsync(c->nm_stage[bsel].p, 0, nw * 4, c->copy_stream));
@@ -2671,7 +2578,7 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
                              (uint32_t *)c->nm_stage[bsel].p, (const uint2 *)c->nz_dev[bsel].p, (uint32_t)nz);
         }
       } else {
-        HIPC(c, hipMemcpyAsync(c->nm_stage[bsel].p, nm_src + w0, nw * 4, hipMemcpyHostToDevice, c->copy_stream));
+        HIPC(c, hipMemcpyAsync(c->nm_stage[bsel].p, nm_src + x.w0, nw * 4, hipMemcpyHostToDevice, c->copy_stream));
       }
     } else if (nb)
       HIPC(c, hipMemcpyAsync(db.p, bases + o0, nb, hipMemcpyHostToDevice, c->copy_stream));
@@ -2688,64 +2595,39 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
     HIPC(c, hipEventRecord(c->copy_done[bsel], c->copy_stream));
     return SHK_OK;
   };
-  // (sets s0 … s0+NST−2 were last read by launches that a later launch of the previous call has waited for)
-  int rc = SHK_OK;
-  // host packing: queue the copies of the slices that are packed, in order, up to slice max_j (what the staging sets
-  // allow at this point); need > 0: wait until `need` slices are packed first
-  auto hp_issue = [&](size_t max_j, size_t need) -> int {
-    const size_t have = hp_packed(need > 0, need);
+  // The one copy schedule: queue the copies of the slices that are packed, in order, up to slice max_j (what the
+  // staging sets allow at this point); need > 0: wait until `need` slices are packed first.  Without a packer every
+  // slice counts as packed, and this is "NST − 1 copies ahead of the count": slices 0 … NST−2 before the first wait,
+  // slice i + NST − 1 once slice i − 1's count has let go of its set.
+  size_t issued = 0;  // slices whose copies have been queued
+  auto issue_upto = [&](size_t max_j, size_t need) -> int {
+    const size_t have = packer ? packer->packed(need) : n_slices;
     if (have < need) {  // the packer gave up: encoding.rs:353-356, the run is over
       c->poisoned = true;
-      c->poison_code = hp_rc;
-      return fail(c, hp_rc, "%s", hp_err.c_str());
+      c->poison_code = packer->code();
+      return fail(c, c->poison_code, "%s", packer->text().c_str());
     }
-    while (hp_issued < have && hp_issued < n_slices && hp_issued <= max_j) {
-      const int r = issue_copy(hp_issued);
-      if (r != SHK_OK) return r;
-      ++hp_issued;
-    }
+    for (; issued < have && issued <= max_j; ++issued) SHK_TRY(issue_copy(issued));
     return SHK_OK;
   };
-  for (size_t i = 0; !hp && i < std::min<size_t>(n_slices, (size_t)NST - 1) && rc == SHK_OK; ++i) rc = issue_copy(i);
-  if (rc != SHK_OK) {
-    (void)hipStreamSynchronize(c->copy_stream);
-    return rc;
-  }
   const bool trace = env_int("SHK_HOST_TRACE", 0) != 0;
   const auto t_begin = std::chrono::steady_clock::now();
   auto now_us = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); };
   for (size_t i = 0; i < n_slices; ++i) {
-    const int bsel = set_of(i);
-    if (hp) {  // slice i must be on its way; slice i − 1's count may still be reading set (i − 1) % NST = slice i + NST − 1's
-      rc = hp_issue(i + (size_t)NST - 2, i + 1);
-      if (rc != SHK_OK) {
-        (void)hipStreamSynchronize(c->copy_stream);
-        return rc;
-      }
-    }
+    const int bsel = ring.set_of(i);
+    // slice i must be on its way; slice i − 1's count may still be reading set (i − 1) % NST = slice i + NST − 1's
+    SHK_TRY(issue_upto(i + NST - 2, i + 1));
     const double ta = now_us();
     HIPC(c, hipEventSynchronize(c->copy_done[bsel]));  // `rebased[bsel]` consumed; data resident
     if (trace) fprintf(stderr, "[slice %zu] copy waited %.0f us (at %.0f)", i, now_us() - ta, now_us());
     // slice i-1 (launched without a host sync) read the set that slice i+NST-1 is about to overwrite
-    rc = settle_light(c);
-    if (rc != SHK_OK) {
-      (void)hipStreamSynchronize(c->copy_stream);
-      return rc;
-    }
+    SHK_TRY(settle_light(c));
     HIPC(c, hipStreamSynchronize(c->stream));
     if (trace) fprintf(stderr, " count(i-1) done at %.0f\n", now_us());
-    if (hp) {
-      rc = hp_issue(i + (size_t)NST - 1, 0);  // (whatever else is packed by now)
-    } else if (i + NST - 1 < n_slices) {
-      rc = issue_copy(i + NST - 1);
-    }
-    if (rc != SHK_OK) {
-      (void)hipStreamSynchronize(c->copy_stream);
-      return rc;
-    }
+    SHK_TRY(issue_upto(i + NST - 1, 0));  // (whatever else is packed by now)
     const uint64_t r0 = cut[i], r1 = cut[i + 1];
-    DevBuf &db = bases_of(bsel);
-    DevBuf &dof = offs_of(bsel);
+    DevBuf &db = c->st_bases[bsel];
+    DevBuf &dof = c->st_offsets[bsel];
     if ((packed || hp) && offsets[r1] > offsets[r0]) {  // 2-bit stream + N mask → the slice's ASCII bytes, in HBM
       const uint64_t o0 = hp ? 0 : offsets[r0], nb = offsets[r1] - offsets[r0];
       // (the staged copies start at byte o0/4 resp. word o0/32 of the streams; what k_unpack reads past their
@@ -2755,22 +2637,14 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
                          (uint32_t)(o0 & 31), nb, (uint8_t *)db.p);
     }
     c->more_slices = i + 1 < n_slices;  // (a table the next slice is about to need is written by this slice's pass)
-    rc = ingest_core(c, (const uint8_t *)db.p, (const uint64_t *)dof.p, r1 - r0, offsets[r1] - offsets[r0],
-                     lane_fixed, nullptr, offsets[r0]);
+    const int rc = ingest_core(c, (const uint8_t *)db.p, (const uint64_t *)dof.p, r1 - r0, offsets[r1] - offsets[r0],
+                               lane_fixed, nullptr, offsets[r0]);
     c->more_slices = false;
-    if (rc != SHK_OK) {
-      (void)hipStreamSynchronize(c->copy_stream);  // do not leave a copy reading `rebased` behind
-      return rc;
-    }
-    if (hp) {  // (and what has been packed while this slice was launched)
-      rc = hp_issue(i + (size_t)NST - 1, 0);
-      if (rc != SHK_OK) {
-        (void)hipStreamSynchronize(c->copy_stream);
-        return rc;
-      }
-    }
+    SHK_TRY(rc);
+    SHK_TRY(issue_upto(i + NST - 1, 0));  // (and what has been packed while this slice was launched)
   }
-  c->stage_last = set_of(n_slices - 1);
+  drain.armed = false;  // (every slice's copies were waited for above)
+  c->stage_last = ring.set_of(n_slices - 1);
   // A host-buffer ingest reports its errors (an invalid byte) before returning — unless the caller asked for
   // the device-buffer behaviour (SHK_FLAG_DEFER_ERRORS): then the last slice's launch is looked at by the next
   // call, whose first copies run under it.

@@ -400,9 +400,7 @@ int group_ingest(shk_ctx *top, const uint8_t *bases, const uint64_t *offsets, ui
     for (uint32_t d = 0; d < D; ++d) {
       uint64_t a = cut[d], b = a;
       if (a < n_seqs) {
-        const uint64_t limit = offsets[a] + target;  // largest b with offsets[b] ≤ limit, at least one read
-        b = (uint64_t)(std::upper_bound(offsets + a, offsets + n_seqs + 1, limit) - offsets) - 1;
-        if (b <= a) b = a + 1;
+        b = reads_within(offsets, a, n_seqs, target);
         if (offsets[b] - offsets[a] > SHK_XCHG_MAX_BASES)
           return fail(top, SHK_ERR_BAD_ARG, "a single read of %llu bases exceeds what one exchange round takes", (unsigned long long)(offsets[b] - offsets[a]));
       }

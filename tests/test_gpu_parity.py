@@ -384,16 +384,18 @@ def test_config2_full_size(orc, flags):
 # ---- BASELINE.json config 3 semantics: host input streamed in slices, copy/compute overlap ------------
 
 @pytest.mark.parametrize("host_pack", ["0", "1"])
-@pytest.mark.parametrize("k,chunks", [(31, 1), (21, 4)])
-def test_streamed_slices_match_oracle(orc, monkeypatch, k, chunks, host_pack):
+@pytest.mark.parametrize("k,chunks,empty", [pytest.param(31, 1, False, id="31-1"), pytest.param(21, 4, False, id="21-4"),
+                                            pytest.param(21, 1, True, id="200-empty-reads")])
+def test_streamed_slices_match_oracle(orc, monkeypatch, k, chunks, empty, host_pack):
     """A large host batch crosses PCIe in slices of whole reads (the next slices copying while the current one is
     counted); forcing 64 KiB slices exercises many slice boundaries, including ones inside a 1000-read block.
     host_pack: the slices as ASCII (0), or packed 2-bit on the host first — what a batch of some size gets on a host
-    with the cores for it (SHK_HOST_PACK pins either)."""
-    monkeypatch.setenv("SHK_SLICE_KB", "64")
+    with the cores for it (SHK_HOST_PACK pins either).
+    empty: a call of 200 reads without a base between them — one slice that copies offsets alone, whatever its size."""
+    monkeypatch.setenv("SHK_SLICE_KB", "16" if empty else "64")
     monkeypatch.setenv("SHK_HOST_PACK", host_pack)
     rng = np.random.default_rng(99)
-    bases, offsets = ragged_reads(rng, 20_000, max_len=160, p_n=0.01)
+    bases, offsets = pack([b""] * 200) if empty else ragged_reads(rng, 20_000, max_len=160, p_n=0.01)
     check_against_oracle(orc, bases, offsets, k, chunks, 60, check_table=False)
 
 
