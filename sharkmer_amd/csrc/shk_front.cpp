@@ -12,6 +12,7 @@
 //     (stats.rs:27-45,186-193; field order of RunStats); validate_args (cli.rs:645-677).
 #include "../../include/shk.h"
 #include "shk_front.h"
+#include "shk_gz_source.h"
 #include "shk_inflate.h"
 
 #include <immintrin.h>
@@ -127,6 +128,7 @@ void shk_front_set_member_decoder(const MemberDecoderOps *ops) { g_device_decode
 }  // namespace shk
 
 using namespace shk;
+using namespace shk::gzsrc;  // Buf, Window, Source, LineWindows, ParallelInflate (shk_gz_source.h)
 
 // ---- FASTQ reader --------------------------------------------------------------------------------
 // Front-end at speed, order-preserving.  Every input file has a PRODUCER: a SOURCE turns the
@@ -147,74 +149,6 @@ using namespace shk;
 // what it hands out: reads are delivered up to the last thousand known to have been read whole, everything once the
 // input is known to end cleanly.
 namespace {
-
-// A window's bytes when they are not the mapped file's: a block that is neither zero-filled (std::vector would: 16 MiB
-// per inflated window, a tenth of the inflate thread's time) nor handed back to the allocator after every window (a block
-// this large comes from mmap: thousands of page faults each time) — a few blocks of each size in use are kept for reuse.
-struct Buf {
-  struct Bytes {
-    uint8_t *p = nullptr;
-    size_t n = 0;
-    uint8_t *data() const { return p; }
-    size_t size() const { return n; }
-    void resize(size_t m) {  // (contents are NOT kept: every caller copies what it needs itself)
-      release(p, n);
-      p = acquire(m);
-      n = m;
-    }
-    ~Bytes() { release(p, n); }
-    Bytes() = default;
-    Bytes(const Bytes &) = delete;
-    Bytes &operator=(const Bytes &) = delete;
-  } v;
-
- private:
-  struct Cache {
-    std::mutex m;
-    std::vector<std::pair<size_t, uint8_t *>> blocks;
-    ~Cache() {
-      for (auto &b : blocks) free(b.second);
-    }
-  };
-  static Cache &cache() {
-    static Cache c;
-    return c;
-  }
-  static uint8_t *acquire(size_t n) {
-    if (!n) return nullptr;
-    {
-      Cache &c = cache();
-      std::lock_guard<std::mutex> lk(c.m);
-      for (size_t i = 0; i < c.blocks.size(); ++i)
-        if (c.blocks[i].first == n) {
-          uint8_t *p = c.blocks[i].second;
-          c.blocks.erase(c.blocks.begin() + (long)i);
-          return p;
-        }
-    }
-    uint8_t *p = (uint8_t *)malloc(n);
-    if (!p) throw std::bad_alloc();
-    return p;
-  }
-  static void release(uint8_t *p, size_t n) {
-    if (!p) return;
-    Cache &c = cache();
-    {
-      std::lock_guard<std::mutex> lk(c.m);
-      if (c.blocks.size() < 12) {
-        c.blocks.emplace_back(n, p);
-        return;
-      }
-    }
-    free(p);
-  }
-};
-struct Window {
-  std::shared_ptr<Buf> hold;  // what keeps the bytes alive (null: the producer's mapping)
-  const char *p = nullptr;
-  size_t n = 0;
-  bool last = false;  // the file's last window (any other ends with '\n')
-};
 
 // Rust's str::from_utf8 (Unicode Table 3-7: no overlong forms, no surrogates, nothing above U+10FFFF)
 static bool valid_utf8(const uint8_t *s, size_t n) {
@@ -257,25 +191,6 @@ static bool any_high_bit(const uint8_t *s, size_t n) {
   return ((acc & 0x8080808080808080ull) | (a & 0x80)) != 0;
 }
 
-// An array that is not value-initialised (the line tables of a 128 MiB window are megabytes: zero-filling them, by one
-// thread, was a third of the window's parse).
-template <class T>
-struct UBuf {
-  std::unique_ptr<T[]> p;
-  size_t n = 0, cap = 0;
-  void resize_discard(size_t m) {  // (contents are lost when it has to grow)
-    if (m > cap) {
-      p.reset(new T[m]);
-      cap = m;
-    }
-    n = m;
-  }
-  T *data() { return p.get(); }
-  const T *data() const { return p.get(); }
-  size_t size() const { return n; }
-  T &operator[](size_t i) { return p[i]; }
-  const T &operator[](size_t i) const { return p[i]; }
-};
 constexpr uint32_t NL_POS = 0x7FFFFFFFu, NL_CR = 0x80000000u;  // a line-table entry: position of the '\n' | "the byte before it is '\r'"
 
 // One pass over a share [a, b) of a window of n bytes: for every '\n' in it an entry (its position relative to `base`,
@@ -349,17 +264,6 @@ static bool scan_share(const char *base, size_t n, size_t a, size_t b, std::vect
 }
 
 // ---- sources ---------------------------------------------------------------------------------------------------
-struct Source {
-  size_t window = 128u << 20;
-  virtual ~Source() {}
-  virtual bool next(Window *w) = 0;  // false: no window is left
-  // What reading on behind the last byte reports (IO_NONE: a clean end of file), given the CRC-32 and the length of
-  // all the windows' bytes.  Valid once the window with `last` set has been handed out.
-  virtual IoError finish(uint32_t, uint64_t) { return IoError(); }
-  virtual bool wants_crc() const { return false; }
-  virtual void cancel() {}
-};
-
 struct MappedSource final : Source {  // a regular file, not gzip: slices of the mapping, cut at line ends
   const char *data;
   size_t size, pos = 0;
@@ -402,10 +306,8 @@ struct FdSource final : Source {  // a pipe, stdin, anything that cannot be mapp
   }
   bool next(Window *w) override {
     if (eof) return false;
-    auto b = std::make_shared<Buf>();
     size_t cap = carry.size() + window;
-    b->v.resize(cap);
-    if (!carry.empty()) memcpy(b->v.data(), carry.data(), carry.size());
+    auto b = Buf::block(cap, carry.data(), carry.size());
     size_t have = carry.size();
     carry.clear();
     for (;;) {
@@ -435,12 +337,7 @@ struct FdSource final : Source {  // a pipe, stdin, anything that cannot be mapp
         return true;
       }
       cap *= 2;  // a line longer than the buffer
-      {
-        auto nb = std::make_shared<Buf>();
-        nb->v.resize(cap);
-        memcpy(nb->v.data(), b->v.data(), have);
-        b = std::move(nb);
-      }
+      b = Buf::block(cap, b->v.data(), have);
     }
   }
   IoError finish(uint32_t, uint64_t) override { return err; }
@@ -553,7 +450,9 @@ static int host_dec_collect(void *d, int s, uint8_t *dst, uint32_t *status) {
 static void host_dec_close(void *d) { delete (HostMemberDecoder *)d; }
 static const MemberDecoderOps HOST_DECODER = {host_dec_probe, host_dec_open, host_dec_submit, host_dec_collect, host_dec_close};
 
-struct GzSource final : Source {
+// The decoders' windows go through emit() into a queue of DEPTH; the buffer they are cut from is a LineWindows, the
+// many-thread decoder of one large member a ParallelInflate (shk_gz_source.h).
+struct GzSource final : Source, WindowSink {
   GzMember gz;
   PgzGate *gate;            // the reader's gate
   uint64_t ticket;          // this source's turn at the many-thread decoder
@@ -578,7 +477,7 @@ struct GzSource final : Source {
   // ends (by this thread: wants_crc() is then false), its error is the stream's.
   bool all_members = false;
   IoError members_err;
-  // the batched route over BGZF members (run_members): 0 off, SHK_FASTQ_BGZF_BATCH, SHK_FASTQ_BGZF_DEVICE
+  // the batched route over BGZF members (run_batches): 0 off, SHK_FASTQ_BGZF_BATCH, SHK_FASTQ_BGZF_DEVICE
   uint32_t bgzf_mode = 0;
   int bgzf_device = 0;
   Pool *pool = nullptr;                           // the reader's (host decode, CRC-32s)
@@ -596,9 +495,8 @@ struct GzSource final : Source {
   // 8 KiB were full, when the 32 KiB of compressed input ran out, or at a member's end — so of the `n_ok` bytes in
   // front of the damage the reference's line reader gets
   //     seen = o + 8192 · ⌊(n_ok − o) / 8192⌋,   o = the output in front of the last such input (or member) boundary.
-  // HOLD_BACK: no window is handed on while fewer than this many decoded bytes lie behind its end, so that the cut
-  // never has to take back anything (the reader parses, and hands out, what the windows hold).
-  static constexpr size_t HOLD_BACK = 8192;
+  // LineWindows::HOLD_BACK: no window is handed on while fewer than this many decoded bytes lie behind its end, so that
+  // the cut never has to take back anything (the reader parses, and hands out, what the windows hold).
   // bytes a decoder gets out of [from, to) alone (a stream cut short at `to`: everything whose bits lie in front of it)
   static uint64_t output_of_prefix(const uint8_t *from, const uint8_t *to) {
     Inflater inf;
@@ -640,767 +538,208 @@ struct GzSource final : Source {
     gate->poke();
   }
   bool wants_crc() const override { return !all_members; }
-  void emit(Window &&w) {
+  void emit(Window &&w) override {
     std::unique_lock<std::mutex> lk(m);
     cv.wait(lk, [&] { return stop || q.size() < DEPTH; });
     if (stop) return;
     q.emplace_back(std::move(w));
     cv.notify_all();
   }
-  // ---- one member, many threads -------------------------------------------------------------------------------------
-  // A DEFLATE stream is one long dependency chain (every block's matches reach into the 32 KiB before it), and one
-  // thread inflates ≈1.2 GB/s of FASTQ — 0.6 Gbases/s, three orders of magnitude under the counting rate.  The
-  // two-pass scheme of parallel gzip readers (pugz, rapidgzip) breaks the chain:
-  //   1. the compressed bytes are cut into chunks; a worker per chunk FINDS a block boundary behind its cut (a bit
-  //      position where a dynamic-Huffman header parses, its block decodes and another header follows) and decodes from
-  //      there SPECULATIVELY into 16-bit symbols — a byte, or "byte w of the 32 KiB in front of my entry point, which I
-  //      do not know" (Inflater::run_symbols) — up to the first block boundary behind the next cut;
-  //   2. this thread goes through the chunks in order.  A chunk's result counts only if its entry point is EXACTLY
-  //      where the verified decoding before it ended; what lies between (a stored or fixed block the finder does not
-  //      look for, a chunk whose speculation failed) is decoded here, the ordinary way.  With the window in front of a
-  //      chunk known, its symbols become bytes — any of them independently of the others, so the last 32 KiB (the next
-  //      chunk's window) at once, here, and all of them by the workers, chunks side by side.
-  // What comes out — bytes, their order, the final status and where the stream ended — is the sequential decoder's:
-  // nothing speculative is ever handed on unverified, and an error is only ever reported by a verified position.
-  struct SpecResult {
-    UBuf<uint16_t> sym;
-    size_t n = 0;
-    bool found = false, ready = false;
-    uint64_t start_bit = 0, end_bit = 0;
-    InflateStatus status = INF_CORRUPT;
-    const uint8_t *after = nullptr;
-    double seconds = 0, find_seconds = 0;  // (debug: the worker's time on this chunk, and of it the search for the entry point)
-  };
-  struct Workers {  // a small two-priority pool of the decoder's own
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<std::function<void()>> hi, lo;
-    bool quit = false;
-    // n threads take whatever there is, urgent work first; n_urgent more take urgent work only — a chunk's bytes are
-    // wanted NOW (the windows go out in order), and a worker deep in a 10 ms speculative decode is no help with that
-    Workers(uint32_t n, uint32_t n_urgent) {
-      for (uint32_t i = 0; i < n + n_urgent; ++i)
-        th.emplace_back([this, only_urgent = i >= n] {
-          for (;;) {
-            std::function<void()> f;
-            {
-              std::unique_lock<std::mutex> lk(m);
-              cv.wait(lk, [&] { return quit || !hi.empty() || (!only_urgent && !lo.empty()); });
-              if (hi.empty() && (only_urgent || lo.empty())) {
-                if (quit) return;
-                continue;
-              }
-              auto &q = hi.empty() ? lo : hi;
-              f = std::move(q.front());
-              q.pop_front();
-            }
-            f();
-          }
-        });
-    }
-    void post(bool urgent, std::function<void()> f) {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        (urgent ? hi : lo).emplace_back(std::move(f));
-      }
-      cv.notify_all();
-    }
-    ~Workers() {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        quit = true;
-        lo.clear();  // (speculation nobody will look at)
-      }
-      cv.notify_all();
-      for (auto &t : th) t.join();
-    }
-  };
-  static bool plausible_header_at(const uint8_t *origin, const uint8_t *end, uint64_t bit) {
-    // BFINAL = 0, BTYPE = 2 (bits 0, 0, 1), HLIT ≤ 29, HDIST ≤ 29: what an encoder's dynamic, non-final block starts with
-    const uint8_t *p = origin + (bit >> 3);
-    if (end - p < 4) return false;
-    uint32_t w;
-    memcpy(&w, p, 4);
-    w >>= (uint32_t)(bit & 7);
-    return (w & 7u) == 4u && ((w >> 3) & 31u) <= 29u && ((w >> 8) & 31u) <= 29u;
-  }
-  // The speculative decode of chunk `i`: entry point at or behind bit lo, output up to the first block boundary at or
-  // behind bit hi.
-  static void speculate(SpecResult *r, const uint8_t *origin, const uint8_t *end, uint64_t lo, uint64_t hi, size_t guess) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    struct Note {
-      SpecResult *r;
-      std::chrono::steady_clock::time_point t0;
-      ~Note() { r->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-    } note{r, t_begin};
-    Inflater inf;
-    size_t cap = guess + 65536;
-    r->sym.resize_discard(cap);
-    auto grow = [&](size_t keep) {
-      UBuf<uint16_t> nb;
-      nb.resize_discard(cap * 2);
-      memcpy(nb.data(), r->sym.data(), keep * 2);
-      r->sym = std::move(nb);
-      cap *= 2;
-    };
-    const uint64_t total_bits = (uint64_t)(end - origin) * 8;
-    for (uint64_t p = lo; p < hi && p + 64 < total_bits; ++p) {
-      if (!plausible_header_at(origin, end, p)) continue;
-      inf.seek(origin, end, p);
-      if (inf.read_block_header() != INF_OUTPUT_FULL || inf.state != 2 || inf.last_block || !inf.hdr_plausible) continue;
-      // its block must decode, and a header must follow it
-      size_t pos = 0;
-      bool between = false;
-      InflateStatus st;
-      for (;;) {
-        st = inf.run_symbols(r->sym.data(), &pos, cap, origin, p + 1, &between);
-        if (st == INF_OUTPUT_FULL && !between) {
-          grow(pos);
-          continue;
-        }
-        break;
-      }
-      if (st != INF_OUTPUT_FULL || !between) continue;
-      {
-        Inflater peek = inf;
-        const InflateStatus hs = peek.read_block_header();
-        if (hs == INF_CORRUPT) continue;
-      }
-      // accepted: go on to the first block boundary at or behind `hi`
-      r->found = true;
-      r->start_bit = p;
-      r->find_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-      for (;;) {
-        st = inf.run_symbols(r->sym.data(), &pos, cap, origin, hi, &between);
-        if (st == INF_OUTPUT_FULL && !between) {
-          grow(pos);
-          continue;
-        }
-        break;
-      }
-      r->n = pos;
-      r->status = st;
-      r->end_bit = inf.bit_position(origin);
-      if (st == INF_STREAM_END) r->after = inf.input_after_stream();
-      return;
-    }
+  bool stopped() override {
+    std::lock_guard<std::mutex> lk(m);
+    return stop;
   }
 
-  void run_parallel(uint32_t n_threads, size_t chunk_bytes) {
-    const uint8_t *origin = gz.inf.in, *end = gz.inf.in_end;
-    const size_t n_chunks = ((size_t)(end - origin) + chunk_bytes - 1) / chunk_bytes;
-    std::vector<SpecResult> spec(n_chunks);
-    std::mutex rm;
-    std::condition_variable rcv;
-    Workers pool(n_threads, std::max(2u, n_threads / 4));
-    size_t issued = 1;  // (chunk 0 starts at the stream's start: decoded here, the ordinary way)
-    const size_t ahead = (size_t)n_threads + 2;
-    const size_t guess = chunk_bytes * 6;
-    auto issue_up_to = [&](size_t upto) {
-      for (; issued < n_chunks && issued <= upto; ++issued) {
-        const size_t i = issued;
-        pool.post(false, [&, i] {
-          speculate(&spec[i], origin, end, (uint64_t)i * chunk_bytes * 8, (uint64_t)(i + 1) * chunk_bytes * 8, guess);
-          {
-            std::lock_guard<std::mutex> lk(rm);
-            spec[i].ready = true;
-          }
-          rcv.notify_all();
-        });
-      }
-    };
-    issue_up_to(ahead);
-
-    // a piece of output on its way out: [window w_len][n bytes] in one block; `pending` jobs still write into it
-    // (a count the workers take down and this thread sleeps on — it used to spin with yield())
-    struct Pending {
-      std::mutex m;
-      std::condition_variable cv;
-      int n = 0;
-      void set(int k) {
-        std::lock_guard<std::mutex> lk(m);
-        n = k;
-      }
-      void done() {
-        std::lock_guard<std::mutex> lk(m);
-        if (--n <= 0) cv.notify_all();
-      }
-      void wait() {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return n <= 0; });
-      }
-    };
-    struct Piece {
-      std::shared_ptr<Buf> buf;
-      size_t w_len = 0, n = 0;
-      std::shared_ptr<Pending> pending;
-    };
-    std::deque<Piece> out_q;
-    std::vector<uint8_t> W;       // the last ≤ 32 KiB of everything decoded so far
-    std::vector<uint8_t> carry;   // the bytes of the last, unfinished line (they are also the tail of W when they fit)
-    uint64_t verified = 0;        // bit position everything in front of which has been decoded and checked
-    InflateStatus status = INF_OUTPUT_FULL;
-    const uint8_t *after = nullptr;
-    uint64_t emitted_out = 0;  // bytes of the pieces that have left out_q
-    bool cancelled = false;
-    size_t n_spec_used = 0, n_here = 0;  // chunks taken from the workers / stretches decoded by this thread
-    uint64_t bytes_spec = 0, bytes_here = 0;
-    double t_workers = 0, t_find = 0, t_wait_spec = 0, t_wait_resolve = 0, t_emit = 0;
-    auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-
-    auto is_stopped = [&] {
-      std::lock_guard<std::mutex> lk(m);
-      return stop;
-    };
-    // hand the front piece on, as a window of whole lines (its last line's beginning is carried into the next)
-    auto emit_front = [&](bool last) {
-      Piece pc = std::move(out_q.front());
-      out_q.pop_front();
-      {
-        const double t0 = tnow();
-        if (pc.pending) pc.pending->wait();
-        t_wait_resolve += tnow() - t0;
-      }
-      const double t_e0 = tnow();
-      struct EmitNote {
-        double &acc, t0;
-        decltype(tnow) &now;
-        ~EmitNote() { acc += now() - t0; }
-      } emit_note{t_emit, t_e0, tnow};
-      uint8_t *base = pc.buf->v.data();
-      size_t a = pc.w_len, b = pc.w_len + pc.n;
-      if (!carry.empty()) {  // the line begun in the piece before: it lies right in front of this piece's bytes
-        if (carry.size() <= pc.w_len && memcmp(base + pc.w_len - carry.size(), carry.data(), carry.size()) == 0) {
-          a = pc.w_len - carry.size();
-        } else {  // (longer than the window in front: a block of its own)
-          auto nb = std::make_shared<Buf>();
-          nb->v.resize(carry.size() + pc.n + 64);
-          memcpy(nb->v.data(), carry.data(), carry.size());
-          memcpy(nb->v.data() + carry.size(), base + pc.w_len, pc.n);
-          pc.buf = nb;
-          base = nb->v.data();
-          a = 0;
-          b = carry.size() + pc.n;
-        }
-      }
-      if (last) {
-        carry.clear();
-        emit(Window{pc.buf, (const char *)base + a, b - a, true});
-        return;
-      }
-      const void *nl = b > a ? memrchr(base + a, '\n', b - a) : nullptr;
-      if (!nl) {  // no line ends in this piece: all of it is carried on
-        carry.assign(base + a, base + b);
-        return;
-      }
-      const size_t cut = (size_t)((const uint8_t *)nl - base) + 1;
-      carry.assign(base + cut, base + b);
-      emit(Window{pc.buf, (const char *)base + a, cut - a, false});
-    };
-    auto new_piece_block = [&](size_t n) {
-      auto b = std::make_shared<Buf>();
-      b->v.resize(W.size() + n + Inflater::OUT_SLACK + 64);
-      if (!W.empty()) memcpy(b->v.data(), W.data(), W.size());
-      return b;
-    };
-    auto roll_window = [&](const uint8_t *bytes, size_t n) {  // W := last 32 KiB of W ++ bytes
-      if (n >= 32768) {
-        W.assign(bytes + n - 32768, bytes + n);
-      } else {
-        const size_t keep = std::min(W.size(), (size_t)32768 - n);
-        std::vector<uint8_t> nw(W.end() - (long)keep, W.end());
-        nw.insert(nw.end(), bytes, bytes + n);
-        W.swap(nw);
-      }
-    };
-    // the ordinary decoder from the verified position on, up to the first block boundary at or behind `to_bit`
-    auto decode_here = [&](uint64_t to_bit) {
-      Inflater inf;
-      inf.seek(origin, end, verified);
-      inf.stop_origin = origin;
-      inf.stop_bit = to_bit;
-      size_t cap = std::max<size_t>(chunk_bytes * 6, 1u << 20);
-      auto b = new_piece_block(cap);
-      const size_t w_len = W.size();
-      size_t pos = w_len;
-      InflateStatus st;
-      for (;;) {
-        st = inf.run(b->v.data(), &pos, w_len + cap);
-        if (st == INF_OUTPUT_FULL && !inf.stopped_between_blocks) {  // more room
-          auto nb = std::make_shared<Buf>();
-          nb->v.resize(w_len + cap * 2 + Inflater::OUT_SLACK + 64);
-          memcpy(nb->v.data(), b->v.data(), pos);
-          b = std::move(nb);
-          cap *= 2;
-          if (is_stopped()) {
-            cancelled = true;
-            break;
-          }
-          continue;
-        }
-        break;
-      }
-      Piece pc;
-      pc.buf = b;
-      pc.w_len = w_len;
-      pc.n = pos - w_len;
-      roll_window(b->v.data() + w_len, pc.n);
-      ++n_here;
-      bytes_here += pc.n;
-      out_q.emplace_back(std::move(pc));
-      verified = inf.bit_position(origin);
-      if (st != INF_OUTPUT_FULL) {
-        status = st;
-        if (st == INF_STREAM_END) after = inf.input_after_stream();
-      }
-    };
-    // a verified chunk: its window is known now — the next chunk's window at once, its bytes by the workers
-    auto resolve = [&](SpecResult &r) {
-      const size_t n = r.n;
-      auto b = new_piece_block(n);
-      const size_t w_len = W.size();
-      // symbol 256 + w means byte w of a FULL 32 KiB window; with less decoded so far (w_len < 32768) the window's first
-      // 32768 − w_len places do not exist: a reference to one is no valid stream (the ordinary decoder says "distance
-      // too far back"): such a chunk cannot have been reached by a valid stream, and a verified one never has any
-      const size_t shift = 32768 - w_len;
-      auto byte_of = [shift, base = b->v.data()](uint16_t s2) -> uint8_t { return s2 < 256 ? (uint8_t)s2 : base[(size_t)(s2 - 256) - shift]; };
-      (void)byte_of;
-      Piece pc;
-      pc.buf = b;
-      pc.w_len = w_len;
-      pc.n = n;
-      pc.pending = std::make_shared<Pending>();
-      // the next window first (the last 32 KiB of this chunk's bytes), by this thread
-      {
-        const size_t t0 = n > 32768 ? n - 32768 : 0;
-        std::vector<uint8_t> tail(n - t0);
-        const uint16_t *sy = r.sym.data();
-        const uint8_t *wb = b->v.data();
-        bool bad = false;
-        for (size_t j = t0; j < n; ++j) {
-          const uint16_t s2 = sy[j];
-          if (s2 < 256) tail[j - t0] = (uint8_t)s2;
-          else if ((size_t)(s2 - 256) >= shift) tail[j - t0] = wb[(size_t)(s2 - 256) - shift];
-          else bad = true, tail[j - t0] = 0;
-        }
-        (void)bad;
-        roll_window(tail.data(), tail.size());
-      }
-      // all of it, in slices, by the workers
-      const size_t slice = 1u << 20;
-      const size_t n_slices = (n + slice - 1) / slice;
-      pc.pending->set((int)n_slices);
-      auto keep = std::make_shared<SpecResult>(std::move(r));
-      for (size_t sl = 0; sl < n_slices; ++sl) {
-        const size_t j0 = sl * slice, j1 = std::min(n, j0 + slice);
-        auto pend = pc.pending;
-        pool.post(true, [keep, b, w_len, shift, j0, j1, pend] {
-          const uint16_t *sy = keep->sym.data();
-          uint8_t *base = b->v.data();
-          uint8_t *dst = base + w_len;
-          for (size_t j = j0; j < j1; ++j) {
-            const uint16_t s2 = sy[j];
-            dst[j] = s2 < 256 ? (uint8_t)s2 : ((size_t)(s2 - 256) >= shift ? base[(size_t)(s2 - 256) - shift] : (uint8_t)0);
-          }
-          pend->done();
-        });
-      }
-      out_q.emplace_back(std::move(pc));
-    };
-    // (a piece goes out only while HOLD_BACK decoded bytes lie behind it: see reference_has_seen)
-    auto drain = [&](size_t keep_n) {
-      while (out_q.size() > keep_n && !cancelled) {
-        size_t behind = 0;
-        for (size_t i = 1; i < out_q.size() && behind < HOLD_BACK; ++i) behind += out_q[i].n;
-        if (behind < HOLD_BACK) break;
-        emitted_out += out_q.front().n;
-        emit_front(false);
-      }
-    };
-
-    // A chunk whose speculation is passed over gives its symbol buffer back at once (12 MB or more each, touched by
-    // the worker): a member where the finder keeps missing — stored or fixed blocks, false block starts — would
-    // otherwise hold one per chunk until its end, memory growing with the file.
-    auto drop_symbols = [](SpecResult &x) {
-      UBuf<uint16_t> none;
-      std::swap(x.sym, none);
-      x.n = 0;
-    };
-    // chunk 0, then chunk after chunk
-    decode_here((uint64_t)chunk_bytes * 8);
-    size_t next = 1;
-    while (status == INF_OUTPUT_FULL && !cancelled) {
-      if (is_stopped()) {
-        cancelled = true;
-        break;
-      }
-      drain(6);
-      if (next >= n_chunks) {  // behind the last cut: the rest of the stream, the ordinary way
-        decode_here(~0ull);
-        continue;
-      }
-      issue_up_to(next + ahead);
-      SpecResult &r = spec[next];
-      {
-        const double t0 = tnow();
-        std::unique_lock<std::mutex> lk(rm);
-        rcv.wait(lk, [&] { return r.ready; });
-        t_wait_spec += tnow() - t0;
-        t_workers += r.seconds;
-        t_find += r.find_seconds;
-      }
-      if (r.found && r.start_bit == verified) {
-        // (a symbol that points in front of everything decoded so far cannot come from a valid stream entered at a
-        // verified position — checked all the same, over the whole chunk, before anything of it is used)
-        bool sane = true;
-        if (W.size() < 32768) {
-          const size_t shift = 32768 - W.size();
-          for (size_t j = 0; j < r.n && sane; ++j) sane = r.sym[j] < 256 || (size_t)(r.sym[j] - 256) >= shift;
-        }
-        if (sane) {
-          const uint64_t e2 = r.end_bit;
-          const InflateStatus st2 = r.status;
-          const uint8_t *after2 = r.after;
-          ++n_spec_used;
-          bytes_spec += r.n;
-          resolve(r);
-          verified = e2;
-          if (st2 != INF_OUTPUT_FULL) {
-            status = st2;
-            after = after2;
-          }
-          ++next;
-          continue;
-        }
-        decode_here((uint64_t)(next + 1) * chunk_bytes * 8);  // (the ordinary decoder says what is wrong with it)
-        drop_symbols(r);
-        ++next;
-        continue;
-      }
-      if (r.found && r.start_bit > verified) {  // something the finder does not look for lies in between
-        decode_here(r.start_bit);
-        if (verified != r.start_bit) {  // (it was no block boundary after all: that chunk's result is void)
-          drop_symbols(r);
-          ++next;
-        }
-        continue;
-      }
-      // no entry point found in this chunk, or one in front of where the stream really stands: the ordinary way
-      if ((uint64_t)(next + 1) * chunk_bytes * 8 > verified) decode_here((uint64_t)(next + 1) * chunk_bytes * 8);
-      drop_symbols(r);
-      ++next;
-    }
-    if (!cancelled) {
-      if (out_q.empty()) {  // (nothing at all was decoded)
-        Piece pc;
-        pc.buf = std::make_shared<Buf>();
-        pc.buf->v.resize(64);
-        out_q.emplace_back(std::move(pc));
-      }
-      final_status = status == INF_OUTPUT_FULL ? INF_TRUNCATED : status;
-      if (final_status == INF_CORRUPT) {  // the reference's reader has not seen all of what lies in front of the damage
-        uint64_t n_ok = emitted_out;
-        for (const Piece &pc : out_q) n_ok += pc.n;
-        uint64_t cut = n_ok - reference_has_seen(n_ok, 0, origin, origin + (verified >> 3));
-        while (cut && !out_q.empty()) {  // (off the tail: resolved pieces first — their bytes are being written by workers)
-          Piece &pc = out_q.back();
-          const size_t t = (size_t)std::min<uint64_t>(cut, pc.n);
-          pc.n -= t;
-          cut -= t;
-          if (pc.n == 0 && out_q.size() > 1) {
-            if (pc.pending) pc.pending->wait();
-            out_q.pop_back();
-          } else if (pc.n == 0) {
-            break;
-          }
-        }
-      }
-      while (out_q.size() > 1) emit_front(false);
-      if (final_status == INF_STREAM_END && after) {  // where the trailer lies (GzMember::finish)
-        gz.inf.in = after;
-        gz.inf.bitcnt = 0;
-      }
-      emit_front(true);
-    }
-    if (getenv("SHK_FASTQ_DEBUG"))
-      fprintf(stderr, "[gzip member, %u threads, %zu chunks of %zu KiB] %zu chunks (%.1f MB) from the workers, %zu stretches (%.1f MB) decoded in order\n",
-              n_threads, n_chunks, chunk_bytes >> 10, n_spec_used, bytes_spec / 1e6, n_here, bytes_here / 1e6),
-          fprintf(stderr, "   workers %.0f ms in all (%.0f ms of it looking for entry points); this thread waited %.0f ms for chunks, %.0f ms for their bytes, %.0f ms handing windows on\n",
-                  t_workers * 1e3, t_find * 1e3, t_wait_spec * 1e3, t_wait_resolve * 1e3, t_emit * 1e3);
-    // (the workers are joined by ~Workers: what is still queued of the speculation is dropped)
-  }
-
+  // the decoding thread: which route the stream takes
   void run() {
     if (gz.header_error.kind != IO_NONE) {  // nothing can be read: an empty last window, the error follows it
       ticket_leave();
       emit(Window{nullptr, "", 0, true});
-      std::lock_guard<std::mutex> lk(m);
-      done = true;
-      cv.notify_all();
       return;
     }
     if (all_members) {
       ticket_leave();
       run_members();
-      std::lock_guard<std::mutex> lk(m);
-      done = true;
-      cv.notify_all();
       return;
     }
-    {
-      // several threads on the one member when it is large enough to pay (test hooks: SHK_PGZ_*)
-      const char *e_min = getenv("SHK_PGZ_MIN_KB"), *e_chunk = getenv("SHK_PGZ_CHUNK_KB"), *e_thr = getenv("SHK_PGZ_THREADS");
-      const size_t min_bytes = e_min ? (size_t)atoll(e_min) << 10 : (size_t)8 << 20;
-      const size_t chunk = std::max<size_t>(e_chunk ? (size_t)atoll(e_chunk) << 10 : (size_t)1 << 20, 512);
-      // (three quarters of the CPUs: the window parse and the copy-out run beside the decoder — on the 16-CPU box one .gz
-      // file gives 2.5-2.6 Gbases/s with 8 threads, 2.9-3.3 with 12, 2.2-3.0 with 16, 2.1 with 24)
-      const uint32_t thr = e_thr ? (uint32_t)atoi(e_thr) : std::max(2u, std::min(32u, usable_cpus() * 3 / 4));
-      if (thr > 1 && (size_t)(gz.inf.in_end - gz.inf.in) >= min_bytes) {
-        if (gate->enter(ticket, gate_abort)) run_parallel(thr, chunk);
-        ticket_leave();
-        std::lock_guard<std::mutex> lk(m);
-        done = true;
-        cv.notify_all();
-        return;
-      }
+    // several threads on the one member when it is large enough to pay (test hooks: SHK_PGZ_*)
+    const char *e_min = getenv("SHK_PGZ_MIN_KB"), *e_chunk = getenv("SHK_PGZ_CHUNK_KB"), *e_thr = getenv("SHK_PGZ_THREADS");
+    const size_t min_bytes = e_min ? (size_t)atoll(e_min) << 10 : (size_t)8 << 20;
+    const size_t chunk = std::max<size_t>(e_chunk ? (size_t)atoll(e_chunk) << 10 : (size_t)1 << 20, 512);
+    // (three quarters of the CPUs: the window parse and the copy-out run beside the decoder — on the 16-CPU box one .gz
+    // file gives 2.5-2.6 Gbases/s with 8 threads, 2.9-3.3 with 12, 2.2-3.0 with 16, 2.1 with 24)
+    const uint32_t thr = e_thr ? (uint32_t)atoi(e_thr) : std::max(2u, std::min(32u, usable_cpus() * 3 / 4));
+    if (thr > 1 && (size_t)(gz.inf.in_end - gz.inf.in) >= min_bytes) {
+      if (gate->enter(ticket, gate_abort)) run_parallel(thr, chunk);
+      ticket_leave();
+      return;
     }
     ticket_leave();  // (one thread is all this member gets: no turn needed)
-    size_t cap = window + 32768 + Inflater::OUT_SLACK;
-    auto b = std::make_shared<Buf>();
-    b->v.resize(cap);
-    size_t pos = 0, line0 = 0;  // decoded so far in this buffer; start of the bytes not handed out yet
-    uint64_t gone = 0;          // bytes of the stream that have left the buffer's front
-    const uint8_t *const deflate0 = gz.inf.in;
-    for (;;) {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        if (stop) break;
-      }
-      const InflateStatus st = gz.inf.run(b->v.data(), &pos, b->v.size());
-      if (st != INF_OUTPUT_FULL) {
-        final_status = st;
-        size_t end = pos;
-        if (st == INF_CORRUPT) {  // the reference's reader has not seen all of what lies in front of the damage
-          const uint64_t seen = reference_has_seen(gone + pos, 0, deflate0, gz.inf.in - (gz.inf.bitcnt >> 3));
-          end = (size_t)(seen - gone);  // (≥ line0: the last HOLD_BACK bytes were never handed on)
-        }
-        emit(Window{b, (const char *)b->v.data() + line0, end - line0, true});
-        break;
-      }
-      const size_t held = std::min(pos - line0, HOLD_BACK);
-      const void *nl = memrchr(b->v.data() + line0, '\n', pos - held - line0);
-      if (!nl) {  // a line longer than the window: a bigger buffer, everything moves along
-        auto nb = std::make_shared<Buf>();
-        nb->v.resize(b->v.size() * 2);
-        memcpy(nb->v.data(), b->v.data(), pos);
-        b = std::move(nb);
+    run_one_thread();
+  }
+  void run_parallel(uint32_t n_threads, size_t chunk_bytes) {
+    deflate0 = gz.inf.in;
+    // (the reference's reader has not seen all of what lies in front of the damage)
+    ParallelInflate par(deflate0, gz.inf.in_end, n_threads, chunk_bytes, *this,
+                        [this](uint64_t n_ok, const uint8_t *fail) { return reference_has_seen(n_ok, 0, deflate0, fail); });
+    ParallelInflate::Result r = par.run();
+    if (r.stopped) return;
+    final_status = r.status;
+    if (r.status == INF_STREAM_END && r.after) {  // where the trailer lies (GzMember::finish)
+      gz.inf.in = r.after;
+      gz.inf.bitcnt = 0;
+    }
+    emit(std::move(r.last));
+  }
+  void run_one_thread() {
+    LineWindows lw(window);
+    deflate0 = gz.inf.in;
+    while (!stopped()) {
+      const InflateStatus st = lw.inflate(gz.inf);
+      if (st == INF_OUTPUT_FULL) {
+        lw.roll(*this);
         continue;
       }
-      const size_t cut = (size_t)((const uint8_t *)nl - b->v.data()) + 1;
-      const size_t keep = std::min(pos, std::max<size_t>(32768, pos - cut));
-      auto nb = std::make_shared<Buf>();
-      nb->v.resize(std::max(cap, keep + window + Inflater::OUT_SLACK));
-      memcpy(nb->v.data(), b->v.data() + pos - keep, keep);
-      emit(Window{b, (const char *)b->v.data() + line0, cut - line0, false});
-      line0 = keep - (pos - cut);
-      gone += pos - keep;
-      pos = keep;
-      b = std::move(nb);
+      final_status = st;
+      // (corrupt: the reference's reader has not seen all of what lies in front of the damage)
+      lw.finish(st == INF_CORRUPT ? reference_has_seen(lw.appended(), 0, deflate0, gz.inf.in - (gz.inf.bitcnt >> 3)) : lw.appended(), *this);
+      break;
     }
-    std::lock_guard<std::mutex> lk(m);
-    done = true;
-    cv.notify_all();
   }
-  // every member, one after the other, by this thread (a bgzip file's 64 KB members, `cat a.gz b.gz`)
-  void run_members() {
-    const size_t cap = window + 32768 + Inflater::OUT_SLACK;
-    auto b = std::make_shared<Buf>();
-    b->v.resize(cap);
-    size_t pos = 0, line0 = 0, crc_from = 0;  // decoded so far in this buffer; first byte not handed out; first byte not in the CRC yet
-    uint32_t crc = 0;
-    uint64_t member_out = 0;
-    uint64_t gone = 0;                        // bytes of the stream that have left the buffer's front
-    const uint8_t *deflate0 = gz.inf.in;      // where the member being decoded begins
-    // ---- the batched route (bgzf_mode): BGZF members decoded side by side, in front of this loop -----------------------
-    // While the members at `member_hdr` are batchable (bgzf_scan), a batch of them is decoded into the buffer behind
-    // `pos` by the decoder — two batches in flight: the next one is scanned and submitted before this one is waited
-    // for — and every member's CRC-32 is checked here, on the pool.  The members in front of the first one that fails
-    // (status, CRC-32; a wrong ISIZE is a status) stay; at that member's header, or at the first member that is not
-    // batchable, this loop goes on the way it always has, with the state it would have there: a fresh member, nothing
-    // of it decoded.  What it then reports — error, text, the reference_has_seen cut — is its own.
-    const uint8_t *member_hdr = file_base;  // the header of the member the loop stands in front of
+
+  // ---- every member (a bgzip file's 64 KB members, `cat a.gz b.gz`) ------------------------------------------------
+  // the member being decoded: the CRC-32 and the count of its bytes so far, where its DEFLATE data begins
+  uint32_t crc = 0;
+  uint64_t member_out = 0;
+  const uint8_t *deflate0 = nullptr;
+  void open_member(const uint8_t *at) {  // stand in front of a fresh member: its header, its own history and checks
     const uint8_t *const file_end = gz.file_end;
-    bool batching = bgzf_mode != 0;
-    const MemberDecoderOps *ops = nullptr;
+    gz = GzMember();
+    gz.open(at, file_end);
+    members_err = gz.header_error;
+    crc = 0;
+    member_out = 0;
+    deflate0 = gz.inf.in;
+  }
+  // ---- the batched route (bgzf_mode): BGZF members decoded side by side, in front of the one-after-the-other loop ----
+  // While the members at `member_hdr` are batchable (bgzf_scan), a batch of them is decoded into the buffer behind
+  // `pos` by the decoder — two batches in flight: the next one is scanned and submitted before this one is waited
+  // for — and every member's CRC-32 is checked here, on the pool.  The members in front of the first one that fails
+  // (status, CRC-32; a wrong ISIZE is a status) stay; at that member's header, or at the first member that is not
+  // batchable, the one-after-the-other loop goes on the way it always has, with the state it would have there: a fresh
+  // member (open_member), nothing of it decoded.  What it then reports — error, text, the reference_has_seen cut — is
+  // its own.
+  enum class Front { FILE_END, HAND_OVER, HEADER_ERROR, STOPPED };  // a clean end of file; a member is open at the hand-over; its header is bad
+  Front run_batches(LineWindows &lw) {
+    const bool on_device = (bgzf_mode & SHK_FASTQ_BGZF_DEVICE) != 0;
+    const MemberDecoderOps *ops = on_device ? g_device_decoder.load() : &HOST_DECODER;
     void *dec = nullptr;
-    if (batching) {
-      if (bgzf_mode & SHK_FASTQ_BGZF_DEVICE) {
-        ops = g_device_decoder.load();
-        dec = ops ? ops->open(bgzf_device) : nullptr;
-      } else {
-        ops = &HOST_DECODER;
-        auto *hd = new HostMemberDecoder();
-        hd->pool = pool;
-        dec = hd;
-      }
-      if (!dec) batching = false;  // (the device went away after the reader was opened: one after the other)
+    if (on_device) {
+      dec = ops ? ops->open(bgzf_device) : nullptr;
+    } else {
+      auto *hd = new HostMemberDecoder();
+      hd->pool = pool;
+      dec = hd;
     }
+    if (!dec) return Front::HAND_OVER;  // (the device went away after the reader was opened: one after the other)
     struct DecClose {
-      const MemberDecoderOps *&ops;
-      void *&dec;
-      ~DecClose() {
-        if (dec) ops->close(dec);
-      }
+      const MemberDecoderOps *ops;
+      void *dec;
+      ~DecClose() { ops->close(dec); }
     } dec_close{ops, dec};
     // a batch's decoded bytes: 64 MiB keeps 16 host threads busy and the text in cache-sized steps (2.9 against 2.5
     // Gbases/s with 128); the device wants the ≈2000 members of 128 MiB — two batches fill its 4096 wave slots — and
     // gives 2.5-2.8 against 2.1-2.4 Gbases/s with 64
-    const uint64_t budget = bgzf_batch_budget((uint64_t)((bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 128 : 64) << 20);
+    const uint64_t budget = bgzf_batch_budget((uint64_t)(on_device ? 128 : 64) << 20);
+    const uint8_t *const file_end = gz.file_end;
+    const uint8_t *member_hdr = file_base;  // the header of the member the route stands in front of
     struct Batch : BgzfBatch {
       int slot = 0;
       bool live = false;  // submitted, not collected
     } batch[2];
-    int cur = 0;
     auto scan_submit = [&](Batch &B, const uint8_t *from, int slot_) {  // false: no batchable member there (or the decoder failed)
       B.slot = slot_;
       if (!bgzf_plan_batch(from, file_end, budget, &B)) return false;
       B.live = ops->submit(dec, slot_, from, (size_t)(B.end - from), B.jobs.data(), (uint32_t)B.jobs.size(), B.out_bytes) == 0;
       return B.live;
     };
-    auto drop_batch = [&](Batch &B) {
-      if (B.live) (void)ops->collect(dec, B.slot, nullptr, nullptr);
-      B.live = false;
-    };
-    // room for `need` more bytes behind pos: whole lines in front of it leave as a window (held back as below)
-    auto make_room = [&](size_t need) {
-      if (b->v.size() - pos >= need + Inflater::OUT_SLACK) return;
-      const size_t held = std::min(pos - line0, HOLD_BACK);
-      const void *nl = memrchr(b->v.data() + line0, '\n', pos - held - line0);
-      const size_t cut = nl ? (size_t)((const uint8_t *)nl - b->v.data()) + 1 : line0;
-      const size_t keep = std::min(pos, std::max<size_t>(32768, pos - cut));
-      auto nb = std::make_shared<Buf>();
-      // (sizes in steps of 8 MiB: Buf keeps blocks for reuse by their exact size)
-      nb->v.resize(std::max(cap, (keep + std::max(need, window) + Inflater::OUT_SLACK + (8u << 20) - 1) & ~(size_t)((8u << 20) - 1)));
-      memcpy(nb->v.data(), b->v.data() + pos - keep, keep);
-      if (cut > line0) emit(Window{b, (const char *)b->v.data() + line0, cut - line0, false});
-      line0 = keep - (pos - cut);
-      gone += pos - keep;
-      pos = keep;
-      crc_from = keep;
-      b = std::move(nb);
-    };
     std::vector<uint32_t> status;
-    for (;;) {
-      {
-        std::lock_guard<std::mutex> lk(m);
-        if (stop) break;
-      }
-      if (batching) {  // (in front of a member: crc = 0, member_out = 0, crc_from = pos)
-        Batch &B = batch[cur], &N = batch[cur ^ 1];
-        if (!B.live && !scan_submit(B, member_hdr, cur)) {
-          batching = false;
-          continue;
-        }
-        if (B.end < file_end) (void)scan_submit(N, B.end, cur ^ 1);
-        make_room((size_t)B.out_bytes);
-        const uint32_t n = (uint32_t)B.ms.size();
-        status.assign(n, ~0u);
-        const bool came = ops->collect(dec, B.slot, b->v.data() + pos, status.data()) == 0;
-        B.live = false;
-        uint8_t *const text = b->v.data() + pos;
-        if (came)
-          pool->parallel_for(n, [&](uint32_t i) {
-            if (status[i] == 0 && crc32_update(0, text + B.jobs[i].out_offset, B.jobs[i].out_len) != B.ms[i].crc) status[i] = ~0u - 1;
-          });
-        uint32_t k = 0;
-        while (k < n && status[k] == 0) ++k;
-        const size_t good = k < n ? (size_t)B.jobs[k].out_offset : (size_t)B.out_bytes;
-        pos += good;
-        crc_from = pos;
-        if (member_stats) member_stats[(bgzf_mode & SHK_FASTQ_BGZF_DEVICE) ? 0 : 1] += k;
-        member_hdr = k < n ? B.ms[k].header : B.end;
-        if (k == n && member_hdr >= file_end) {  // the file's end, clean: what INF_STREAM_END of the last member does below
-          emit(Window{b, (const char *)b->v.data() + line0, pos - line0, true});
-          break;
-        }
-        if (k == n && N.live) {
-          cur ^= 1;
-          continue;
-        }
-        // hand over: a member that failed, or one that is not batchable
-        drop_batch(N);
-        batching = false;
-        gz = GzMember();
-        gz.open(member_hdr, file_end);
-        members_err = gz.header_error;
-        crc = 0;
-        member_out = 0;
-        deflate0 = gz.inf.in;
-        if (members_err.kind != IO_NONE) {
-          emit(Window{b, (const char *)b->v.data() + line0, pos - line0, true});
-          break;
-        }
+    for (int cur = 0; !stopped(); cur ^= 1) {
+      Batch &B = batch[cur], &N = batch[cur ^ 1];
+      if (!B.live && !scan_submit(B, member_hdr, cur)) break;
+      if (B.end < file_end) (void)scan_submit(N, B.end, cur ^ 1);
+      lw.roll((size_t)B.out_bytes, *this);
+      const uint32_t n = (uint32_t)B.ms.size();
+      status.assign(n, ~0u);
+      uint8_t *const text = lw.data() + lw.pos;
+      const bool came = ops->collect(dec, B.slot, text, status.data()) == 0;
+      B.live = false;
+      if (came)
+        pool->parallel_for(n, [&](uint32_t i) {
+          if (status[i] == 0 && crc32_update(0, text + B.jobs[i].out_offset, B.jobs[i].out_len) != B.ms[i].crc) status[i] = ~0u - 1;
+        });
+      uint32_t k = 0;
+      while (k < n && status[k] == 0) ++k;
+      lw.advance(k < n ? (size_t)B.jobs[k].out_offset : (size_t)B.out_bytes);
+      if (member_stats) member_stats[on_device ? 0 : 1] += k;
+      member_hdr = k < n ? B.ms[k].header : B.end;
+      if (k == n && member_hdr >= file_end) return Front::FILE_END;
+      if (k == n && N.live) continue;
+      // hand over: a member that failed, or one that is not batchable
+      if (N.live) (void)ops->collect(dec, N.slot, nullptr, nullptr);
+      break;
+    }
+    if (stopped()) return Front::STOPPED;
+    open_member(member_hdr);
+    return members_err.kind == IO_NONE ? Front::HAND_OVER : Front::HEADER_ERROR;
+  }
+  // every member, one after the other, by this thread — behind the batched route where that is on
+  void run_members() {
+    LineWindows lw(window);
+    deflate0 = gz.inf.in;
+    if (bgzf_mode) {
+      const Front how = run_batches(lw);
+      if (how == Front::FILE_END || how == Front::HEADER_ERROR) lw.finish(lw.appended(), *this);
+      if (how != Front::HAND_OVER) return;
+    }
+    size_t crc_from = lw.pos;  // the first byte not in the CRC yet
+    while (!stopped()) {
+      gz.inf.history_bytes = member_out;  // (a member's matches reach back into that member only)
+      const InflateStatus st = lw.inflate(gz.inf);
+      crc = crc32_update(crc, lw.data() + crc_from, lw.pos - crc_from);
+      member_out += lw.pos - crc_from;
+      if (st == INF_OUTPUT_FULL) {
+        lw.roll(*this);
+        crc_from = lw.pos;
         continue;
       }
-      gz.inf.history_bytes = member_out;  // (a member's matches reach back into that member only)
-      const InflateStatus st = gz.inf.run(b->v.data(), &pos, b->v.size());
-      crc = crc32_update(crc, b->v.data() + crc_from, pos - crc_from);
-      member_out += pos - crc_from;
-      crc_from = pos;
-      if (st != INF_OUTPUT_FULL && member_stats) member_stats[2] += 1;
+      crc_from = lw.pos;
+      if (member_stats) member_stats[2] += 1;
+      members_err = gz.finish(st, crc, member_out);
+      uint64_t end = lw.appended();
       if (st == INF_STREAM_END) {
-        members_err = gz.finish(st, crc, member_out);
-        const uint8_t *nxt = gz.inf.input_after_stream() + 8, *fe = gz.file_end;
-        if (members_err.kind == IO_NONE && nxt < fe) {  // another member: its header, its own history and checks
-          gz = GzMember();
-          gz.open(nxt, fe);
-          members_err = gz.header_error;
-          crc = 0;
-          member_out = 0;
-          deflate0 = gz.inf.in;
+        const uint8_t *nxt = gz.inf.input_after_stream() + 8;
+        if (members_err.kind == IO_NONE && nxt < gz.file_end) {  // another member
+          open_member(nxt);
           if (members_err.kind == IO_NONE) continue;
         }
-        emit(Window{b, (const char *)b->v.data() + line0, pos - line0, true});
-        break;
+      } else if (st == INF_CORRUPT) {  // (see reference_has_seen: a member's end is where a read ends, too)
+        end = reference_has_seen(end, end - member_out, deflate0, gz.inf.in - (gz.inf.bitcnt >> 3));
       }
-      if (st != INF_OUTPUT_FULL) {  // a short or corrupt body
-        members_err = gz.finish(st, crc, member_out);
-        size_t end = pos;
-        if (st == INF_CORRUPT) {  // (see reference_has_seen: a member's end is where a read ends, too)
-          const uint64_t seen = reference_has_seen(gone + pos, gone + pos - member_out, deflate0, gz.inf.in - (gz.inf.bitcnt >> 3));
-          end = (size_t)(seen - gone);
-        }
-        emit(Window{b, (const char *)b->v.data() + line0, end - line0, true});
-        break;
-      }
-      const size_t held = std::min(pos - line0, HOLD_BACK);
-      const void *nl = memrchr(b->v.data() + line0, '\n', pos - held - line0);
-      if (!nl) {  // a line longer than the window: a bigger buffer, everything moves along
-        auto nb = std::make_shared<Buf>();
-        nb->v.resize(b->v.size() * 2);
-        memcpy(nb->v.data(), b->v.data(), pos);
-        b = std::move(nb);
-        continue;
-      }
-      const size_t cut = (size_t)((const uint8_t *)nl - b->v.data()) + 1;
-      const size_t keep = std::min(pos, std::max<size_t>(32768, pos - cut));
-      auto nb = std::make_shared<Buf>();
-      nb->v.resize(std::max(cap, keep + window + Inflater::OUT_SLACK));
-      memcpy(nb->v.data(), b->v.data() + pos - keep, keep);
-      emit(Window{b, (const char *)b->v.data() + line0, cut - line0, false});
-      line0 = keep - (pos - cut);
-      gone += pos - keep;
-      pos = keep;
-      crc_from = keep;
-      b = std::move(nb);
+      lw.finish(end, *this);
+      break;
     }
   }
   bool next(Window *w) override {
     std::unique_lock<std::mutex> lk(m);
     if (!started) {
       started = true;
-      th = std::thread([this] { run(); });
+      th = std::thread([this] {
+        run();
+        std::lock_guard<std::mutex> end(m);
+        done = true;
+        cv.notify_all();
+      });
     }
     cv.wait(lk, [&] { return stop || !q.empty() || done; });
     if (q.empty()) return false;
@@ -1409,7 +748,7 @@ struct GzSource final : Source {
     cv.notify_all();
     return true;
   }
-  IoError finish(uint32_t crc, uint64_t total) override { return all_members ? members_err : gz.finish(final_status, crc, total); }
+  IoError finish(uint32_t crc_all, uint64_t total) override { return all_members ? members_err : gz.finish(final_status, crc_all, total); }
 };
 
 // ---- chunks ------------------------------------------------------------------------------------------------------
