@@ -13,6 +13,9 @@ import numpy as np
 
 import pcr_ref
 import primer_ref
+import products_ref
+import prune_ref
+import thread_ref
 
 U32_MAX = 0xFFFFFFFF
 SHK_ERR_BAD_ARG, SHK_ERR_STATE = -2, -11  # include/shk.h
@@ -54,10 +57,12 @@ class MergedView:
 
 
 class LaneModel:
-    def __init__(self, orc, k: int, chunks: int, histo_max: int, multi_device: bool = False):
+    def __init__(self, orc, k: int, chunks: int, histo_max: int, multi_device: bool = False, group_graph: bool = False):
         self.orc, self.k, self.chunks, self.histo_max = orc, k, chunks, histo_max
         self.multi_device = multi_device  # (the same data model: only what the ABI refuses on such a context differs)
+        self.group_graph = group_graph    # SHK_FLAG_GROUP_GRAPH: a multi-device context answers the graph calls, merged
         self.n_lanes = max(chunks, 1)  # io.rs:378
+        self.retain = False  # shk_retain_reads: the switch outlives a reset, what is retained does not
         self.reset()
 
     # ---- operations ------------------------------------------------------------------------------
@@ -66,6 +71,7 @@ class LaneModel:
         self.lanes = [self.orc.KmerCounts(self.k) for _ in range(self.n_lanes)]
         self.read_index = 0
         self.n_reads = self.n_bases_read = self.n_bases_ingested = self.n_inserted = 0
+        self.retained = []  # the reads of every ingest since, in arrival order, as bytes
         self._obs = None
 
     def set_read_index(self, i: int):
@@ -93,6 +99,8 @@ class LaneModel:
         for i in range(len(off) - 1):
             self.lanes[lane_of(i)].ingest_seq(raw[off[i]:off[i + 1]])  # Chunk::ingest_seq, chunk.rs:25-30
         n = len(off) - 1
+        if self.retain:  # whatever the lane and the read index: the store is one list
+            self.retained += [raw[off[i]:off[i + 1]] for i in range(n)]
         self.n_reads += n
         self.n_bases_read += off[-1] - off[0]
         self.n_bases_ingested += int((bases[off[0]:off[-1]] != ord("N")).sum())  # chunk.rs:28
@@ -184,7 +192,7 @@ class LaneModel:
     def graph_table(self, what: str) -> MergedView:
         """The merged table as shk_lookup(canonical = 1) sees it — the saturating sum over the lanes, a key inserted
         with count 0 present with 0 — or the refusal include/shk.h states for `what`."""
-        if self.multi_device:
+        if self.multi_device and not self.group_graph:
             raise ModelError("%s needs the whole table on one device: this is a multi-device context (n_devices > 1)" % what,
                              SHK_ERR_STATE)
         if self.k < 2:
@@ -209,3 +217,98 @@ class LaneModel:
         counts); params: pcr_ref.pcr_extend's (min_count, table_min_count, high_coverage_ratio, max_num_nodes, sweep)."""
         table = self.graph_table("shk_pcr_extend")
         return pcr_ref.pcr_extend(fwd, rev, table, self.k, **params)
+
+    def neighborhood_panel(self, jobs, max_levels: int = 0):
+        """shk_neighborhood_panel: `neighborhood` per job (nodes, dirs, min_count, cap, fringe_cap), one max_levels."""
+        return [self.neighborhood(n, d, mc, max_levels, cap, fcap) for n, d, mc, cap, fcap in jobs]
+
+    # ---- retained reads (shk_retain_api.hip.h) ---------------------------------------------------
+    def _single_device(self):
+        if self.multi_device:
+            raise ModelError("not available on a multi-device context", SHK_ERR_STATE)
+
+    def retain_reads(self, on: bool = True):
+        """shk_retain_reads: on takes a context that holds no reads; off drops the store."""
+        self._single_device()
+        if not on:
+            self.retain, self.retained = False, []
+        elif not self.retain:
+            if self.n_reads or self.n_bases_read:
+                raise ModelError("shk_retain_reads: the context holds reads already; switch retention on after shk_create or shk_reset",
+                                 SHK_ERR_STATE)
+            self.retain = True
+        elif self.retained:
+            raise ModelError("reads are being retained already", SHK_ERR_STATE)
+
+    def _retaining(self, who: str):
+        self._single_device()
+        if not self.retain:
+            raise ModelError("%s: reads are not retained (shk_retain_reads)" % who, SHK_ERR_STATE)
+
+    def retained_info(self) -> dict:
+        self._single_device()
+        return dict(reads=len(self.retained), bases=sum(len(r) for r in self.retained))
+
+    def retained_export(self, first: int, n: int):
+        """shk_retained_export → (bases, offsets from 0) of retained reads first .. first + n."""
+        self._retaining("shk_retained_export")
+        if first > len(self.retained) or n > len(self.retained) - first:
+            raise ModelError("reads %d to %d are outside the %d retained reads" % (first, first + n, len(self.retained)), SHK_ERR_BAD_ARG)
+        part = self.retained[first:first + n]
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in part])
+        return np.frombuffer(b"".join(part), dtype=np.uint8), offsets
+
+    def filter_reads_panel(self, reads, genes) -> list:
+        """PrimerReadFilter::filter_reads per gene (read_filter.rs:24-55), as panel_cases.expected: the oracle's
+        KmerCounts.filter_matches per gene and read → ascending indices into `reads` (a list of bytes) per gene."""
+        rows = []
+        for gene in genes:
+            kc = self.orc.KmerCounts(self.k)
+            for x in np.atleast_1d(gene).tolist():
+                kc.insert(int(x), 1)
+            rows.append([i for i, r in enumerate(reads) if kc.filter_matches(r)])
+        return rows
+
+    def filter_retained(self, genes) -> list:
+        self._retaining("shk_filter_reads_panel_retained")
+        return self.filter_reads_panel(self.retained, genes)
+
+    def thread_reads_panel(self, reads, graphs, lists, read_index=None, mate=None) -> list:
+        """thread_reads[_paired] per gene over its listed reads in list order (tests/thread_ref.py, as
+        thread_panel_cases.expected).  graphs: (sub_kmers, [(source, target)]) per gene; reads: a list of bytes, or a
+        {index: bytes} of the listed ones → per gene (support_total, support_unambiguous, links, link_counts,
+        read_edges, n_paired_links)."""
+        if self.k < 2:
+            raise ModelError("shk_thread_reads needs k >= 2 (a node is a (k-1)-mer), got k=%d" % self.k, SHK_ERR_BAD_ARG)
+        out = []
+        for (sub, edges), ids in zip(graphs, lists):
+            g = thread_ref.Graph([int(x) for x in sub], [(int(s), int(t)) for s, t in edges])
+            seqs = [reads[int(i)] for i in ids]
+            if mate is None:
+                ann = thread_ref.thread_reads(g, seqs, self.k)
+            else:
+                ann = thread_ref.thread_reads_paired(g, seqs, [int(read_index[int(i)]) for i in ids], [int(mate[int(i)]) for i in ids], self.k)
+            out.append(tuple(thread_ref.as_arrays(ann, len(g.edges))) + (ann.n_paired_links,))
+        return out
+
+    def thread_retained(self, graphs, lists, read_index=None, mate=None) -> list:
+        self._retaining("shk_thread_reads_panel_retained")
+        return self.thread_reads_panel(self.retained, graphs, lists, read_index, mate)
+
+    # ---- the calls that need no table: the context's k is all they take ------------------------
+    def prune_panel(self, graphs, fractions, stages) -> list:
+        """shk_pcr_prune_panel → one prune_ref.Pruned per gene; graphs: (flags, edge_src, edge_tgt, edge_counts)."""
+        return [prune_ref.prune(*g, self.k, f, s) for g, f, s in zip(graphs, fractions, stages)]
+
+    @staticmethod
+    def dedup_panel(records, scores, thresholds) -> list:
+        """shk_pcr_dedup_panel → per gene (order, pair bits of the sorted order, kept, generated, retained) by
+        tests/products_ref.py's sort_and_deduplicate and its full-matrix edit distance."""
+        out = []
+        for seqs, sc, t in zip(records, scores, thresholds):
+            dist = products_ref.distance_matrix(seqs)
+            order = products_ref.sort_order(seqs, sc)
+            kept, retained = products_ref.sort_and_deduplicate(seqs, sc, t, dist)
+            out.append((order, products_ref.pair_matrix(seqs, order, t, dist), kept, len(seqs), retained))
+        return out

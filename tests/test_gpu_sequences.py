@@ -17,6 +17,16 @@ observations that settle, clear and may grow the table on their way (shk.h: "the
 is their own answer and, since the sequence goes on over a model they did not touch, every finalize, histogram column,
 counter and export after them.
 
+A third generator decides what lies beside the contexts — whether a one-device context retains its reads
+(shk_retain_reads, the first allocation 0, 64 or 1000 bases so that the store moves under queued appends) and whether
+a multi-device one is made with SHK_FLAG_GROUP_GRAPH, which then answers the graph calls as the merged view — and
+interleaves about two to six more operations: the retained store read back over drawn ranges, the panel filter and
+the panel threading over it, and the panel calls that share the context's scratch (thread_reads_panel as host and
+device batch, neighborhood_panel, pcr_prune_panel, pcr_dedup_panel).  Their expected answers are the lane model's —
+the oracle's filter_matches, tests/thread_ref.py, prune_ref.py, products_ref.py, pcr_ref.py — and each is followed by
+an export, so the table and everything later is checked against a model they did not touch.  Without the third
+generator's operations the plan is the one drawn before them (tests/test_lane_model_cpu.py holds that hash too).
+
 SHK_SEQ_SEEDS: how many seeds; SHK_SEQ_FIRST: the first one.  A failing case prints its seed, its context and the
 operations applied so far (name + parameters): SHK_SEQ_FIRST=<seed> SHK_SEQ_SEEDS=1 replays it.  `dry_run(seed)`
 runs the draw and the model without an engine (tests/test_lane_model_cpu.py checks the default set's coverage so)."""
@@ -32,14 +42,19 @@ from test_gpu_fuzz import HOOKS, draw_reads
 pytestmark = pytest.mark.gpu
 
 # 96 seeds from 0.  Positions and kinds follow from the draw alone and are checked without an engine
-# (tests/test_lane_model_cpu.py): the rarest, "neighborhood after a zero-count insert", is met by seeds 17, 47 and 55,
+# (tests/test_lane_model_cpu.py): the rarest, "neighborhood after a zero-count insert", is met by seeds 17, 47 and 55
+# (and by 2 and 45, whose multi-device contexts answer with SHK_FLAG_GROUP_GRAPH),
 # "neighborhood on a saturated count" by 12, 19, 24, 49, 73 and 93, the poison step and the saturated count by 8 seeds
-# each.  The routes need the engine: on an MI355X the rarest, `histo_rows` (a job whose one fresh page pass is
-# finalized as it is, on a FLAG_TIMING seed), was met by no seed of the first 48 and is met by seeds 25, 75 and 94 —
-# a neighborhood call in front of such a finalize drops the fused histogram on purpose (seed 25's first job has one),
-# and the three seeds still meet the route; `grow` by 11 seeds, `extend` by 16.
-# The 96 sequences (and the fixed ones below) take 59.3 s there with the two graph observations, 53.9 s without them
-# (the parent of the change that added them, same machine, same day), against 430 s for the rest of the GPU suite.
+# each.  Of the third generator's positions the rarest are "retained reads on the second context of a two-context life"
+# (seeds 84 and 88), "group-graph call after a zero-count insert" (2 and 45) and "retained reads across a poison step"
+# (20, 70 and 84).  The routes need the engine: on an MI355X the rarest, `histo_rows` (a job whose one fresh page pass
+# is finalized as it is, on a FLAG_TIMING seed), was met by no seed of the first 48 and by seeds 25, 75 and 94 before
+# the third generator — a neighborhood call in front of such a finalize drops the fused histogram on purpose (seed
+# 25's first job has one); with the third generator's operations between the others seed 25 still meets the route,
+# 75 and 94 no longer do; `grow` by 11 seeds, `extend` by 22; `share_grew` by seeds 1 and 2, `store_moved` by 36 seeds.
+# The 96 sequences (and the fixed ones below) take 77.8 s there with the third generator's operations, 55.4 s without
+# them (the parent of the change that added them, same machine, same day; 59.3 s and 53.9 s were the two numbers of
+# the graph observations), against 459 s for the rest of the GPU suite.
 DEFAULT_SEEDS = 96
 OVERRIDDEN = "SHK_SEQ_SEEDS" in os.environ or "SHK_SEQ_FIRST" in os.environ
 N_SEEDS = int(os.environ.get("SHK_SEQ_SEEDS", str(DEFAULT_SEEDS)))
@@ -49,17 +64,36 @@ G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 PANEL = [l.split("\t")[1:3] for l in open(os.path.join(G, "primer_panel_cnidaria.tsv")).read().splitlines()
          if l and not l.startswith("#")]
 MAX_BASES = 2_000_000
+SHK_ERR_INVALID_CHAR = -1   # include/shk.h: the code a poisoned context keeps
 PRE_FINALIZE = ("n_reads_ingested", "n_bases_read", "n_bases_ingested")
 POSITIONS = ("observation before the first finalize", "observation between two ingests",
              "ingest after finalize, then a second finalize", "reset followed by a job", "finalize twice",
              "poison step", "two-context life", "zero-count insert", "saturated count",
              "neighborhood between two ingests", "neighborhood before the first finalize",
              "neighborhood after a zero-count insert", "neighborhood on a saturated count", "pcr_extend after a reset",
-             "neighborhood refused on a multi-device context")
-ROUTES = ("direct", "scatter", "pages", "histo", "histo_rows", "grow", "insert", "lookup", "export", "extend")
+             "neighborhood refused on a multi-device context",
+             "retained call between two ingests", "retained call before the first finalize", "retained reads after a reset",
+             "retained reads on the second context of a two-context life", "retained reads across a poison step",
+             "retention with a packed ingest", "retention with a device ingest", "retention with a windowed ingest",
+             "retention with ingest_batch", "group-graph neighborhood between two ingests", "group-graph pcr_extend",
+             "group-graph call after a zero-count insert")
+# store_moved: retained_info()["device_bytes"] rose between two looks at one store; share_grew: counters()["n_grows"]
+# rose on a group-graph context between its creation or its last graph call and the end of a graph call
+ROUTES = ("direct", "scatter", "pages", "histo", "histo_rows", "grow", "insert", "lookup", "export", "extend", "store_moved",
+          "share_grew")
 GRAPH_OPS = ("neighborhood", "pcr_extend")
 GRAPH_SEED = 7_000_000   # the second generator: GRAPH_SEED + the sequence seed
 GRAPH_RATE = 0.2
+RETAIN_OPS = ("retain_switch", "retained_export", "filter_retained", "thread_retained", "thread_panel", "neighborhood_panel",
+              "prune_panel", "dedup_panel")
+RETAIN_SEED = 9_000_000  # the third generator: RETAIN_SEED + the sequence seed
+RETAIN_RATE = 0.2
+RETAIN_WEIGHTS = {True: (2.0, 2.5, 2.5, 1.0, 1.0, 1.2, 1.2),    # a context that retains: RETAIN_OPS[1:]
+                  False: (0.3, 0.3, 0.3, 1.5, 1.5, 1.5, 1.5)}   # one that does not: the three refusals now and then
+RETAIN_TEXTS = ("reads are not retained", "holds reads already", "not available on a multi-device context")
+STORED = {"packed": "retention with a packed ingest", "device": "retention with a device ingest",
+          "windowed": "retention with a windowed ingest", "ingest_batch": "retention with ingest_batch"}
+THREAD_READS, THREAD_LEN, FILTER_WINDOW, HOST_CHECK = 32, 1500, 3000, 4000   # bounds that keep the model cheap
 RECORD = {"positions": {}, "routes": {}, "kinds": {}, "seeds": set()}   # item → the seeds that met it
 
 
@@ -77,6 +111,42 @@ def draw_context(rng, kind=None):
 
 
 def draw_plan(seed):
+    """→ (contexts, hooks, operations): draw_graph_plan's, with the third generator's operations (RETAIN_OPS) after
+    about every fifth one and a retention switch after some resets of a one-device context."""
+    return _draw_third(seed)[:3]
+
+
+def draw_properties(seed):
+    """→ per context what lies beside it: dict(retain, capacity_bases, group_graph), from the third generator."""
+    return _draw_third(seed)[3]
+
+
+def _draw_third(seed):
+    contexts, hooks, base = draw_graph_plan(seed)
+    rng = np.random.default_rng(RETAIN_SEED + seed)
+    props = []
+    for ctx in contexts:
+        coin, capacity = rng.random() < 0.5, int(rng.choice([0, 64, 1000]))
+        plain = ctx["kind"] == "plain"
+        props.append(dict(retain=bool(plain and coin), capacity_bases=capacity if plain else 0, group_graph=bool(not plain and coin)))
+    ops, at, retaining = [], 0, props[0]["retain"]
+    for op in base:
+        ops.append(op)
+        if op[0] == "second_context":
+            at, retaining = 1, props[1]["retain"]
+        ctx = contexts[at]
+        if op[0] == "reset" and ctx["kind"] == "plain" and rng.random() < 0.4:   # off, or on again: the store goes to the cache
+            retaining = bool(rng.random() < 0.6)
+            ops.append(("retain_switch", dict(on=retaining, capacity_bases=int(rng.choice([0, 64, 1000])))))
+        if rng.random() < RETAIN_RATE:
+            w = np.array(RETAIN_WEIGHTS[retaining])
+            if ctx["k"] < 2:   # a node is a (k-1)-mer
+                w[[RETAIN_OPS.index(n) - 1 for n in ("thread_retained", "thread_panel", "prune_panel")]] = 0
+            ops.append((RETAIN_OPS[1 + int(rng.choice(len(w), p=w / w.sum()))], dict(r=int(rng.integers(1, 1 << 30)))))
+    return contexts, hooks, ops, props
+
+
+def draw_graph_plan(seed):
     """→ (contexts, hooks, operations): draw_base_plan's, with the graph observations of the second generator after
     about every fifth operation (name + sub-seed: nodes and parameters come from the model's table when applied)."""
     contexts, hooks, base = draw_base_plan(seed)
@@ -194,6 +264,25 @@ def random_kmers(rng, k, n):
     return rng.integers(0, 1 << (2 * k), size=n, dtype=np.uint64)
 
 
+COMPLEMENT = bytes.maketrans(b"ACGTN", b"TGCAN")
+
+
+def rc_bytes(s):
+    return s[::-1].translate(COMPLEMENT)
+
+
+def encode(s):
+    """ACGT bytes → the 2-bit number of kmer/encoding.rs, the first base highest."""
+    x = 0
+    for c in s:
+        x = (x << 2) | b"ACGT".index(c)
+    return x
+
+
+def f64_bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
 # ---- where in a context's life things happened ----------------------------------------------------------------
 
 class Positions:
@@ -204,7 +293,9 @@ class Positions:
     def fresh(self, after_reset=False):
         self.n_final = 0          # successful finalizes since create / reset
         self.nonempty = False
-        self.trail = ""           # i: ingest, o: observation, n: a neighborhood call, f: finalize — since create / reset
+        # i: ingest, o: observation, n: a neighborhood call, f: finalize — since create / reset; beside them r: a retained
+        # call that answered, G: a neighbourhood answered by a group-graph context
+        self.trail = ""
         self.after_reset = after_reset
 
     def ingest(self):
@@ -214,17 +305,23 @@ class Positions:
             self.met("observation between two ingests")
         if last >= 0 and "n" in self.trail[last + 1:]:
             self.met("neighborhood between two ingests")
+        if last >= 0 and "r" in self.trail[last + 1:]:
+            self.met("retained call between two ingests")
+        if last >= 0 and "G" in self.trail[last + 1:]:
+            self.met("group-graph neighborhood between two ingests")
         self.trail += "i"
 
     def mutate(self):
         self.nonempty = True
 
-    def observe(self, neighborhood=False):
+    def observe(self, neighborhood=False, retained=False, group_graph=False):
         if self.nonempty and self.n_final == 0:
             self.met("observation before the first finalize")
             if neighborhood:
                 self.met("neighborhood before the first finalize")
-        self.trail += "n" if neighborhood else "o"
+            if retained:
+                self.met("retained call before the first finalize")
+        self.trail += ("n" if neighborhood else "o") + ("r" if retained else "") + ("G" if group_graph else "")
 
     def finalized(self):
         self.n_final += 1
@@ -241,16 +338,18 @@ class Sequence:
     def __init__(self, orc, seed, engine=True):
         self.orc, self.seed, self.live = orc, seed, engine
         self.contexts, self.hooks, self.ops = draw_plan(seed)
+        self.props = draw_properties(seed)
         self.done = []
         self.met_here = set()
         self.routes = set()
+        self.facts = []  # (operation, what its expected answer held): tests/test_lane_model_cpu.py asks that they are not vacuous
         self.pos = Positions(self.met_here.add)
         self.keep = []   # device buffers of asynchronous ingests
         self.eng = None
 
     def report(self, what=""):
-        return "%s\nseed %d  hooks %s\ncontexts %s\noperations so far:\n  %s" % (
-            what, self.seed, self.hooks, self.contexts, "\n  ".join("%s %s" % o for o in self.done))
+        return "%s\nseed %d  hooks %s\ncontexts %s\nbeside them %s\noperations so far:\n  %s" % (
+            what, self.seed, self.hooks, self.contexts, self.props, "\n  ".join("%s %s" % o for o in self.done))
 
     # the engine's side of every step: nothing on a dry run
     def call(self, name, *a, **kw):
@@ -280,17 +379,42 @@ class Sequence:
             getattr(self.eng, name)(*a, **kw)
         except sa.ShkError as got:
             assert got.code == e.code, self.report("%s: code %d (%s), expected %d" % (name, got.code, got.msg, e.code))
+            for text in RETAIN_TEXTS:   # the retained calls' refusals: the text of shk_retain_api.hip.h too
+                assert text not in str(e) or text in got.msg, self.report("%s: message %r, expected %r in it" % (name, got.msg, text))
         else:
             raise AssertionError(self.report("%s did not fail; expected code %d" % (name, e.code)))
 
-    def open(self, ctx):
-        self.ctx, self.multi = ctx, ctx["kind"] != "plain"
-        self.model = LaneModel(self.orc, ctx["k"], ctx["chunks"], ctx["histo_max"], multi_device=self.multi)
+    def open(self, at):
+        ctx, prop = self.contexts[at], self.props[at]
+        self.ctx, self.ctx_at, self.multi = ctx, at, ctx["kind"] != "plain"
+        self.group_graph = self.multi and prop["group_graph"]
+        self.model = LaneModel(self.orc, ctx["k"], ctx["chunks"], ctx["histo_max"], multi_device=self.multi, group_graph=self.group_graph)
         self.pos.fresh()
+        self.fresh_store()
+        self.last_grows = 0
         self.met_here.add("kind " + ("multi-device" if self.multi else "plain"))
         if self.live:
             devs = {"plain": None, "multi2": [0, 0], "multi4": [0, 0, 0, 0]}[ctx["kind"]]
-            self.eng = sa.KmerEngine(ctx["k"], ctx["chunks"], ctx["histo_max"], capacity_hint=ctx["hint"], flags=ctx["flags"], device_ids=devs)
+            flags = ctx["flags"] | (sa.FLAG_GROUP_GRAPH if self.group_graph else 0)
+            self.eng = sa.KmerEngine(ctx["k"], ctx["chunks"], ctx["histo_max"], capacity_hint=ctx["hint"], flags=flags, device_ids=devs)
+        if prop["retain"]:
+            self.op_retain_switch(True, prop["capacity_bases"])
+
+    def fresh_store(self):
+        """The retained store is empty (create, reset, switched off): how its reads came, where its ingests ended."""
+        self.stored, self.bounds, self.last_bytes, self.n_retained = set(), [], 0, 0
+
+    def look_at_the_store(self):
+        """After every operation: where an ingest began in the store, and whether the store's allocation rose."""
+        n = len(self.model.retained)
+        if n > self.n_retained > 0:
+            self.bounds.append(self.n_retained)
+        self.n_retained = n
+        if self.live and self.model.retain:
+            held = self.eng.retained_info()["device_bytes"]
+            if held > self.last_bytes > 0:
+                self.routes.add("store_moved")
+            self.last_bytes = held
 
     def close(self):
         if self.live and self.eng is not None:
@@ -302,10 +426,11 @@ class Sequence:
 
     def run(self):
         try:
-            self.open(self.contexts[0])
+            self.open(0)
             for name, p in self.ops:
                 self.done.append((name, p))
                 getattr(self, "op_" + name)(**p)
+                self.look_at_the_store()
             if self.model.is_empty():
                 self.done.append(("ingest", dict(r=7, route="host", window=False)))
                 self.op_ingest(r=7, route="host", window=False)
@@ -344,12 +469,16 @@ class Sequence:
         self.model.ingest_reads(bases, offsets)
         self.hand_over(route, bases, offsets, window)
         self.pos.ingest()
+        if self.model.retain and len(offsets) > 1:   # (a window: the caller's offsets do not start at 0)
+            self.stored.add("windowed" if route == "host" and window and int(offsets[0]) > 0 else route)
 
     def op_ingest_batch(self, r, chunk_id):
         bases, offsets = small_batch(r, 1500)
         self.model.ingest_batch(chunk_id, bases, offsets)
         self.call("ingest_batch", chunk_id, bases, offsets)
         self.pos.ingest()
+        if self.model.retain and len(offsets) > 1:
+            self.stored.add("ingest_batch")
 
     def op_set_read_index(self, index):
         self.model.set_read_index(index)
@@ -388,17 +517,37 @@ class Sequence:
         self.call("ingest_batch", 0, bases, offsets)
         assert self.model.get_count([key])[0] == U32_MAX
         self.pos.ingest()
+        if self.model.retain:
+            self.stored.add("ingest_batch")
 
     def op_reset(self):
         self.model.reset()
         self.call("reset")
         self.pos.fresh(after_reset=True)
+        held = self.last_bytes   # (the store is emptied, its allocation stays)
+        self.fresh_store()
+        self.last_bytes = held
 
     def op_second_context(self):
         """The first context goes, the second is made of its blocks (the process-wide cache hands them on as they are)."""
         self.close()
-        self.open(self.contexts[1])
+        self.open(1)
         self.met_here.add("two-context life")
+
+    def op_retain_switch(self, on, capacity_bases):
+        """shk_retain_reads on a context that holds no reads: off hands the store's blocks to the cache, on starts a new one."""
+        try:
+            self.model.retain_reads(on)
+        except ModelError as e:
+            self.refused(e, "retain_reads", on, capacity_bases)
+            return
+        self.call("retain_reads", on, capacity_bases)
+        if self.live:
+            info = self.eng.retained_info()
+            self.same((info["reads"], info["bases"]), (0, 0), "retained_info after the switch")
+            assert on or info["device_bytes"] == 0, self.report("retain_reads(False) left %d bytes" % info["device_bytes"])
+        if not on:
+            self.fresh_store()
 
     def op_poison(self, r, route, byte, repeats):
         """One byte outside ACGTN: the call fails with the reference's text (encoding.rs:353-356) — or, where the
@@ -429,8 +578,22 @@ class Sequence:
                 self.raises(text, "hand_over", route, bases, offsets, False, exact=exact)
         for _ in range(repeats + 1):
             self.raises(text, "finalize", exact=exact)
+        if self.model.retain:   # the batch was appended before it poisoned: the store says so until the reset
+            if self.live:
+                for call in (lambda: self.eng.retained_reads(0, 0), lambda: self.eng.filter_reads_retained([[1]]),
+                             lambda: self.eng.thread_reads_retained([], [])):
+                    try:
+                        call()
+                    except sa.ShkError as e:
+                        assert (e.code, e.msg) == (SHK_ERR_INVALID_CHAR, text), self.report("retained call on a poisoned context: %d %r" % (e.code, e.msg))
+                    else:
+                        raise AssertionError(self.report("a retained call answered on a poisoned context"))
+            self.met_here.add("retained reads across a poison step")
         self.done.append(("reset", {}))
         self.op_reset()
+        if self.model.retain and self.live:
+            info = self.eng.retained_info()
+            self.same((info["reads"], info["bases"]), (0, 0), "retained_info after the poisoned context's reset")
         self.same(self.call("export_table"), self.model.export(), "export after the poisoned context's reset")
         self.check_pre_finalize_counters()
         self.raises(NO_READS, "finalize")
@@ -577,14 +740,30 @@ class Sequence:
             for what, g, w in zip(("k-mers", "counts", "fringe nodes", "fringe dirs", "levels done"), got, want):
                 self.same(g, w, "neighborhood %s" % what)
         self.met_here.update(marks)
-        self.pos.observe(neighborhood=True)
+        self.graph_call_answered(counts)
+        self.pos.observe(neighborhood=True, group_graph=self.group_graph)
 
-    def op_pcr_extend(self, r):
-        """shk_pcr_extend from the model's top-count k-mers in both orientations, the node budget small."""
-        rng = np.random.default_rng(r)
+    def graph_call_answered(self, counts):
+        """A graph call has answered.  On a group-graph context: whether a share grew since the last one (the share
+        directory is built anew from the shares' arrays), and whether the table holds a key of count 0."""
+        if not self.group_graph:
+            return
+        if len(counts) and not counts.all():
+            self.met_here.add("group-graph call after a zero-count insert")
+        if self.live:
+            grows = self.eng.counters()["n_grows"]
+            if grows > self.last_grows:
+                self.routes.add("share_grew")
+            self.last_grows = grows
+
+    def extend_args(self, rng):
+        """→ (forward set, reverse set, parameters) of a shk_pcr_extend from the model's top-count k-mers in both
+        orientations, the node budget small."""
         k = self.ctx["k"]
         keys, counts = self.model.export()
-        top = np.argsort(counts, kind="stable")[::-1][:8]
+        # np.argsort(counts, kind="stable")[::-1][:8], sorting only what can be among the eight
+        high = np.flatnonzero(counts >= np.partition(counts, len(counts) - 8)[len(counts) - 8]) if len(counts) > 8 else np.arange(len(counts))
+        top = high[np.argsort(counts[high], kind="stable")[::-1][:8]]
         sets = []
         for part in (top[0::2], top[1::2]):
             ks, cs = keys[part].copy(), counts[part].copy()
@@ -595,6 +774,13 @@ class Sequence:
         a = dict(min_count=int(rng.integers(1, 4)), table_min_count=int(rng.choice([1, 2])),
                  high_coverage_ratio=float(rng.choice([1.5, 10.0])), max_num_nodes=int(rng.choice([50, 1200])),
                  sweep=bool(rng.random() < 0.5))
+        return sets[0], sets[1], a
+
+    def op_pcr_extend(self, r):
+        """shk_pcr_extend with extend_args' draw."""
+        rng = np.random.default_rng(r)
+        sets = [None, None]
+        sets[0], sets[1], a = self.extend_args(rng)
         self.done[-1] = ("pcr_extend", dict(r=r, fwd=sets[0][0].tolist(), rev=sets[1][0].tolist(), **a))
         try:
             want, used, steps = self.model.pcr_extend(sets[0], sets[1], **a)
@@ -610,6 +796,9 @@ class Sequence:
             self.same((got.found_path, got.threshold_used, got.steps_run), (want.found_path, used, steps), "pcr_extend outcome")
         if self.pos.after_reset and self.pos.nonempty:
             self.met_here.add("pcr_extend after a reset")
+        if self.group_graph:
+            self.met_here.add("group-graph pcr_extend")
+        self.graph_call_answered(self.model.export()[1])
         self.pos.observe()
 
     def op_filter_reads(self, r):
@@ -652,6 +841,333 @@ class Sequence:
         self.check_pre_finalize_counters()
         self.pos.observe()
 
+    # ---- the third generator's operations: retained reads and the panel calls -------------------------
+    def retained_call_answered(self):
+        """A retained call has answered: where in the context's life, and how the reads it saw had come."""
+        self.pos.observe(retained=True)
+        if self.model.retained:
+            if self.pos.after_reset:
+                self.met_here.add("retained reads after a reset")
+            if self.ctx_at == 1:
+                self.met_here.add("retained reads on the second context of a two-context life")
+            self.met_here.update(STORED[route] for route in self.stored if route in STORED)
+
+    def canonical_kmer(self, window):
+        return int(self.orc.kmers_from_ascii(bytes(window), self.ctx["k"])[0])
+
+    def op_retained_export(self, r):
+        """shk_retained_export over (0, all), (n_reads, 0), a range across the start of an ingest and one from anywhere."""
+        rng = np.random.default_rng(r)
+        try:
+            info = self.model.retained_info()
+            self.model.retained_export(0, 0)
+        except ModelError as e:
+            self.refused(e, "retained_reads", 0, 0)
+            return
+        n = info["reads"]
+        ranges = [(0, n), (n, 0)]
+        if self.bounds:
+            first = max(self.bounds[int(rng.integers(0, len(self.bounds)))] - int(rng.integers(1, 40)), 0)
+            ranges.append((first, min(int(rng.integers(2, 80)), n - first)))
+        first = int(rng.integers(0, n + 1))
+        ranges.append((first, int(rng.integers(0, min(n - first, 200) + 1))))
+        self.done[-1] = ("retained_export", dict(r=r, ranges=ranges))
+        if self.live:
+            got = self.eng.retained_info()
+            self.same((got["reads"], got["bases"]), (n, info["bases"]), "retained_info")
+            for first, count in ranges:
+                for what, got, want in zip(("bases", "offsets"), self.eng.retained_reads(first, count), self.model.retained_export(first, count)):
+                    self.same(got, want, "retained reads %d + %d: %s" % (first, count, what))
+        self.retained_call_answered()
+        self.op_export()
+
+    def draw_genes(self, rng, reads):
+        """1-4 genes: the canonical k-mers of the first, the last and a middle window of a few of the reads (cut from
+        the read or from its reverse complement) and two from nowhere; one gene is sometimes empty."""
+        k = self.ctx["k"]
+        genes = []
+        n_genes = int(rng.integers(1, 5))
+        for _ in range(n_genes):
+            if n_genes > 1 and rng.random() < 0.2:
+                genes.append(np.zeros(0, dtype=np.uint64))
+                continue
+            new = random_kmers(rng, k, 2)
+            kmers = np.minimum(new, revcomp(new, k)).tolist()
+            for _ in range(int(rng.integers(1, 3)) if reads else 0):
+                read = reads[int(rng.integers(0, len(reads)))]
+                for at in (0, len(read) - k, int(rng.integers(0, max(len(read) - k, 0) + 1))):
+                    window = read[at:at + k] if at >= 0 else b""
+                    if len(window) == k and b"N" not in window:
+                        kmers.append(self.canonical_kmer(window if rng.random() < 0.5 else rc_bytes(window)))
+            genes.append(np.array(kmers, dtype=np.uint64))
+        return genes
+
+    def op_filter_retained(self, r):
+        """shk_filter_reads_panel_retained: per gene the ascending indices of the retained reads that match it — and, while
+        the store is small, what shk_filter_reads_panel answers over the same reads as a host batch."""
+        rng = np.random.default_rng(r)
+        genes = self.draw_genes(rng, self.model.retained)
+        self.done[-1] = ("filter_retained", dict(r=r, genes=[g.tolist() for g in genes]))
+        try:
+            want = self.model.filter_retained(genes)
+        except ModelError as e:
+            self.refused(e, "filter_reads_retained", genes)
+            return
+        self.facts.append(("filter_retained", dict(nonempty=any(want))))
+        if self.live:
+            got = self.eng.filter_reads_retained(genes)
+            self.same(len(got), len(want), "filter_reads_retained: genes")
+            for g, (a, b) in enumerate(zip(got, want)):
+                self.same(a, np.array(b, dtype=np.uint64), "filter_reads_retained: gene %d" % g)
+            if len(self.model.retained) <= HOST_CHECK:
+                host = self.eng.filter_reads_panel(*self.model.retained_export(0, len(self.model.retained)), genes)
+                for g, (a, b) in enumerate(zip(host, want)):
+                    self.same(a, np.array(b, dtype=np.uint64), "filter_reads_panel over the retained reads: gene %d" % g)
+        self.retained_call_answered()
+        self.op_export()
+
+    def draw_thread_case(self, rng, reads, n_total, lo):
+        """Two graphs and their read lists over reads lo .. lo + len(reads) of a batch of n_total.  One graph is a chain
+        over the (k-1)-mers of stretches of two or three of the reads, with one branch; the other is the model's
+        pcr_extend graph when the context has one with edges.  A list is what the model's filter keeps for a few of the
+        graph's edge k-mers, cut to THREAD_READS reads of at most THREAD_LEN bases, sometimes reversed or repeated.
+        → (graphs as (sub_kmers, [(source, target)]), lists, read_index, mate)."""
+        k = self.ctx["k"]
+        graphs = []
+        sub, edges, sources = [], [], []
+        for _ in range(int(rng.integers(2, 4))):
+            for _ in range(20 if reads else 0):   # a read with a stretch of k + 2 bases or more without an N
+                at = int(rng.integers(0, len(reads)))
+                parts = [p for p in reads[at][:THREAD_LEN].split(b"N") if len(p) >= k + 2]
+                if parts:
+                    part = parts[int(rng.integers(0, len(parts)))]
+                    start = int(rng.integers(0, len(part) - (k + 2) + 1))
+                    stretch = part[start:start + k + 2 + int(rng.integers(0, 60))]
+                    first = len(sub)
+                    sub += [encode(stretch[i:i + k - 1]) for i in range(len(stretch) - k + 2)]
+                    edges += [(i, i + 1) for i in range(first, len(sub) - 1)]
+                    sources.append(at)
+                    break
+        if sub:   # the branch: a second way out of the chain's second node, one base off the third
+            sub.append(sub[2] ^ 1)
+            edges.append((1, len(sub) - 1))
+        else:     # (no read has such a stretch: two nodes and no edge)
+            sub = [0, 1]
+        graphs.append((sub, edges))
+        try:
+            fwd, rev, a = self.extend_args(rng)
+            g = self.model.pcr_extend(fwd, rev, **a)[0]
+            if g.edges:
+                graphs.append((list(g.sub_kmer), [(s, t) for s, t, _ in g.edges]))
+        except ModelError:   # (a multi-device context without the flag has no such graph)
+            pass
+        lists = []
+        for sub, edges in graphs:
+            some = [edges[int(i)] for i in rng.integers(0, len(edges), size=min(len(edges), 12))] if edges else []
+            gene = [((sub[s] << 2) | (sub[t] & 3)) for s, t in some]
+            gene = [min(x, int(revcomp(np.array([x], dtype=np.uint64), k)[0])) for x in gene]
+            rows = self.model.filter_reads_panel(reads, [gene])[0] if gene else []
+            ids = [i for i in rows if len(reads[i]) <= THREAD_LEN]
+            if len(ids) > THREAD_READS:
+                ids = sorted(set(sources) & set(ids)) + [ids[int(i)] for i in rng.integers(0, len(ids), size=THREAD_READS)]
+            ids = [lo + i for i in ids[:THREAD_READS]]
+            way = rng.random()
+            lists.append(ids[::-1] if way < 0.25 else ids + ids if way < 0.5 else ids)
+        if rng.random() < 0.4:   # the paired form: mates side by side, now and then a read without one
+            read_index = np.arange(n_total, dtype=np.uint64) + np.uint64(int(rng.integers(0, 1000)) * 2)
+            mate = (1 + np.arange(n_total) % 2).astype(np.uint8)
+            mate[rng.random(n_total) < 0.1] = 0
+        else:
+            read_index = mate = None
+        return graphs, lists, read_index, mate
+
+    def thread_facts(self, name, want):
+        self.facts.append((name, dict(read_edges=sum(sum(w[4]) for w in want), links=sum(len(w[2]) for w in want))))
+
+    def same_annotations(self, got, want, what):
+        self.same(len(got), len(want), "%s: genes" % what)
+        for g, (a, w) in enumerate(zip(got, want)):
+            for field, x, y in (("support_total", a.support_total, w[0]), ("support_unambiguous", a.support_unambiguous, w[1]),
+                                ("links", a.links, np.array(w[2], dtype=np.uint32).reshape(-1, 2)), ("link_counts", a.link_counts, w[3]),
+                                ("read_edges", a.read_edges, w[4]), ("n_paired_links", a.n_paired_links, w[5])):
+                self.same(x, y, "%s: gene %d %s" % (what, g, field))
+
+    @staticmethod
+    def graph_arrays(graphs):
+        return [(np.array(sub, dtype=np.uint64), np.array([e[0] for e in edges], dtype=np.uint32), np.array([e[1] for e in edges], dtype=np.uint32))
+                for sub, edges in graphs]
+
+    def op_thread_retained(self, r):
+        """shk_thread_reads_panel_retained against tests/thread_ref.py: lists drawn from a window of the store."""
+        rng = np.random.default_rng(r)
+        try:
+            self.model.retained_export(0, 0)
+        except ModelError as e:
+            self.refused(e, "thread_reads_retained", [], [])
+            return
+        n = len(self.model.retained)
+        lo = int(rng.integers(0, max(n - FILTER_WINDOW, 0) + 1))
+        graphs, lists, read_index, mate = self.draw_thread_case(rng, self.model.retained[lo:lo + FILTER_WINDOW], n, lo)
+        self.done[-1] = ("thread_retained", dict(r=r, graphs=graphs, lists=lists, paired=mate is not None))
+        want = self.model.thread_retained(graphs, lists, read_index, mate)
+        self.thread_facts("thread_retained", want)
+        if self.live:
+            self.same_annotations(self.eng.thread_reads_retained(self.graph_arrays(graphs), lists, read_index, mate), want, "thread_reads_retained")
+        self.retained_call_answered()
+        self.op_export()
+
+    def op_thread_panel(self, r):
+        """shk_thread_reads_panel over a small batch, as host arrays and as device buffers, against tests/thread_ref.py."""
+        rng = np.random.default_rng(r)
+        bases, offsets = small_batch(r)
+        raw = bases.tobytes()
+        reads = [raw[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+        graphs, lists, read_index, mate = self.draw_thread_case(rng, reads, len(reads), 0)
+        self.done[-1] = ("thread_panel", dict(r=r, graphs=graphs, lists=lists, paired=mate is not None))
+        want = self.model.thread_reads_panel(reads, graphs, lists, read_index, mate)
+        self.thread_facts("thread_panel", want)
+        if self.live:
+            arrays = self.graph_arrays(graphs)
+            self.same_annotations(self.eng.thread_reads_panel(arrays, bases, offsets, lists, read_index, mate), want, "thread_reads_panel")
+            if len(bases):
+                import torch
+                db, do = torch.from_numpy(bases.copy()).cuda(), torch.from_numpy(offsets.astype(np.int64)).cuda()
+                torch.cuda.synchronize()
+                self.same_annotations(self.eng.thread_reads_panel(arrays, db, do, lists, read_index, mate, device=True), want,
+                                      "thread_reads_panel, device buffers")
+        self.op_export()
+
+    def op_neighborhood_panel(self, r):
+        """shk_neighborhood_panel: 2-3 jobs of op_neighborhood's kind and bounds, one max_levels for all."""
+        rng = np.random.default_rng(r)
+        jobs, marks = [], []
+        for _ in range(int(rng.integers(2, 4))):
+            nodes, dirs, counts, m = self.graph_seeds(rng) if self.ctx["k"] >= 2 else ([0], [1], np.zeros(0, np.uint32), [])
+            n_distinct = len({(n, b) for n, d in zip(nodes, dirs) for b in (1, 2) if d & b})
+            jobs.append((nodes, dirs, int(rng.choice([0, 1, 2, int(counts[int(rng.integers(0, len(counts)))]) if len(counts) else 3, U32_MAX])),
+                         int(rng.choice([0, 1, 64, 4096])), int(rng.choice([n_distinct, 64, 4096]))))
+        max_levels = int(rng.integers(1, 7))
+        self.done[-1] = ("neighborhood_panel", dict(r=r, jobs=jobs, max_levels=max_levels))
+        try:
+            want = self.model.neighborhood_panel(jobs, max_levels)
+        except ModelError as e:   # a multi-device context without the flag (SHK_ERR_STATE), k = 1 (SHK_ERR_BAD_ARG)
+            self.refused(e, "neighborhood_panel", jobs, max_levels)
+            return
+        if self.live:
+            got = self.eng.neighborhood_panel(jobs, max_levels)
+            self.same(len(got), len(want), "neighborhood_panel: jobs")
+            for j, (a, b) in enumerate(zip(got, want)):
+                for what, g, w in zip(("k-mers", "counts", "fringe nodes", "fringe dirs", "levels done"), a, b):
+                    self.same(g, w, "neighborhood_panel: job %d %s" % (j, what))
+        self.graph_call_answered(self.model.export()[1])
+        self.pos.observe(group_graph=self.group_graph)
+        self.op_export()
+
+    def op_prune_panel(self, r):
+        """shk_pcr_prune_panel against tests/prune_ref.py: the model's pcr_extend graph under the default parameters and
+        under drawn ones, and a drawn graph that has something to remove — a chain from a start to an end node, tips of
+        count 1 hanging off it and an island no walk reaches."""
+        rng = np.random.default_rng(r)
+        k = self.ctx["k"]
+        graphs, fractions, stages = [], [], []
+        try:
+            fwd, rev, a = self.extend_args(rng)
+            g = self.model.pcr_extend(fwd, rev, **a)[0]
+            extended = (list(g.sub_kmer), g.flags(), [e[0] for e in g.edges], [e[1] for e in g.edges], [e[2] for e in g.edges])
+            graphs += [extended, extended]
+            fractions += [0.1, float(rng.choice([0.0, 0.5, 1.0, 3.0]))]
+            stages += [3, int(rng.integers(1, 4))]
+        except ModelError:   # (a multi-device context without the flag has no such graph)
+            pass
+        n = int(rng.integers(4, 30))
+        flags = [1] + [0] * (n - 2) + [2]
+        src, tgt, counts = list(range(n - 1)), list(range(1, n)), [int(c) for c in rng.integers(20, 60, size=n - 1)]
+        for _ in range(int(rng.integers(1, 4))):   # a tip: one node, out of or into the chain
+            at = int(rng.integers(1, n - 1))
+            flags.append(0)
+            src.append(at if rng.random() < 0.5 else len(flags) - 1)
+            tgt.append(len(flags) - 1 if src[-1] == at else at)
+            counts.append(1)
+        flags += [0, 0]
+        src.append(len(flags) - 2)
+        tgt.append(len(flags) - 1)
+        counts.append(int(rng.integers(1, 60)))
+        graphs.append(([int(x) for x in random_kmers(rng, k - 1, len(flags))], flags, src, tgt, counts))
+        fractions.append(0.1)
+        stages.append(int(rng.choice([1, 2, 3, 3])))
+        self.done[-1] = ("prune_panel", dict(r=r, graphs=graphs, fractions=fractions, stages=stages))
+        want = self.model.prune_panel([g[1:] for g in graphs], fractions, stages)
+        self.facts.append(("prune_panel", dict(removed=sum(len(w.node_keep) - sum(w.node_keep) for w in want))))
+        if self.live:
+            got = self.eng.pcr_prune_panel([(np.array(g[0], dtype=np.uint64), g[1], g[2], g[3], g[4]) for g in graphs], fractions, stages)
+            self.same(len(got), len(want), "pcr_prune_panel: genes")
+            for i, (a, w, g) in enumerate(zip(got, want, graphs)):
+                for field, x, y in (("node_keep", a.node_keep, w.node_keep), ("node_index", a.node_index, w.node_index),
+                                    ("node_flags", a.node_flags, w.node_flags), ("node_sub_kmers", a.node_sub_kmers, [g[0][v] for v in w.node_index]),
+                                    ("edge_index", a.edge_index, w.edge_index), ("edge_src", a.edge_src, w.edge_src), ("edge_tgt", a.edge_tgt, w.edge_tgt),
+                                    ("edge_counts", a.edge_counts, w.edge_counts), ("coverage_ratio", f64_bits(a.coverage_ratio), f64_bits(w.coverage_ratio)),
+                                    ("median", f64_bits([a.median]), f64_bits([w.median])),
+                                    ("tip_rounds, tips_removed, unreachable_removed", (a.tip_rounds, a.tips_removed, a.unreachable_removed),
+                                     (w.tip_rounds, w.tips_removed, w.unreachable_removed))):
+                    self.same(np.asarray(x).ravel(), np.asarray(y).ravel(), "pcr_prune_panel: gene %d %s" % (i, field))
+        self.pos.observe()
+        self.op_export()
+
+    def op_dedup_panel(self, r):
+        """shk_pcr_dedup_panel against tests/products_ref.py: per gene 3-8 records — a stretch of a retained (or a batch's)
+        read, a copy of it, copies with a few substitutions and indels, a stretch from elsewhere."""
+        rng = np.random.default_rng(r)
+        reads = self.model.retained
+        if not reads:
+            bases, offsets = small_batch(r)
+            raw = bases.tobytes()
+            reads = [raw[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+        letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+        def stretch():
+            n = int(rng.integers(30, 120))
+            for _ in range(10 if reads else 0):
+                parts = [p for p in reads[int(rng.integers(0, len(reads)))][:THREAD_LEN].split(b"N") if len(p) >= n]
+                if parts:
+                    at = int(rng.integers(0, len(parts[0]) - n + 1))
+                    return parts[0][at:at + n].decode()
+            return letters[rng.integers(0, 4, size=n)].tobytes().decode()
+
+        def edited(s, n_edits):
+            s = list(s)
+            for _ in range(n_edits):
+                at, how = int(rng.integers(0, len(s))), int(rng.integers(0, 3))
+                if how == 0:
+                    s[at] = "ACGT"[("ACGT".index(s[at]) + 1 + int(rng.integers(0, 3))) % 4]
+                elif how == 1:
+                    s.insert(at, "ACGT"[int(rng.integers(0, 4))])
+                elif len(s) > 1:
+                    del s[at]
+            return "".join(s)
+
+        records, scores, thresholds = [], [], []
+        for _ in range(int(rng.integers(1, 3))):
+            base = stretch()
+            recs = [base, base, stretch()]
+            while len(recs) < int(rng.integers(3, 9)):
+                recs.append(edited(base, int(rng.choice([1, 1, 2, 3, 12]))))
+            recs = [recs[int(i)] for i in rng.permutation(len(recs))]
+            records.append(recs)
+            scores.append([float(x) for x in rng.integers(0, 3, size=len(recs))])
+            thresholds.append(int(rng.choice([0, 1, 10])))
+        self.done[-1] = ("dedup_panel", dict(r=r, records=records, scores=scores, thresholds=thresholds))
+        want = self.model.dedup_panel(records, scores, thresholds)
+        self.facts.append(("dedup_panel", dict(within=any(any(w[1]) for w in want), outside=any(not all(w[1]) for w in want))))
+        if self.live:
+            got = self.eng.pcr_dedup_panel(records, scores, thresholds, want_pairs=True)
+            self.same(len(got), len(want), "pcr_dedup_panel: genes")
+            for g, (a, w) in enumerate(zip(got, want)):
+                for field, x, y in (("order", a.order, w[0]), ("pair bits", a.pair_bits, w[1]), ("kept", a.kept, w[2]),
+                                    ("generated, retained", (a.generated, a.retained), w[3:])):
+                    self.same(np.asarray(x).ravel(), np.asarray(y).ravel(), "pcr_dedup_panel: gene %d %s" % (g, field))
+        self.pos.observe()
+        self.op_export()
+
 
 def _brief(x):
     if isinstance(x, tuple):
@@ -662,9 +1178,14 @@ def _brief(x):
 
 def dry_run(orc, seed):
     """The draw and the model alone → what the seed covers (positions and kinds; the routes need the engine)."""
+    return dry_sequence(orc, seed).met_here
+
+
+def dry_sequence(orc, seed):
+    """The same → the Sequence itself: met_here, and `facts` — what the third generator's expected answers held."""
     s = Sequence(orc, seed, engine=False)
     s.run()
-    return s.met_here
+    return s
 
 
 # ---- the sweep ----------------------------------------------------------------------------------------------

@@ -51,6 +51,7 @@ def test_ingest_in_any_number_of_calls_is_the_one_shot_run(orc, case):
     what = dict(case=case, k=k, chunks=chunks, histo_max=histo_max, shape=shape, n=n, cuts=cuts)
     run = orc.run_batch(bases, offsets, k, chunks, histo_max)
     model = LaneModel(orc, k, chunks, histo_max)
+    model.retain_reads()
     for a, b in zip(cuts[:-1], cuts[1:]):
         if (a + b) % 2:   # either way of handing a run of reads over: a window of the offsets, or a copy from 0
             model.ingest_reads(bases, offsets[a:b + 1])
@@ -59,6 +60,15 @@ def test_ingest_in_any_number_of_calls_is_the_one_shot_run(orc, case):
             model.ingest_reads(bases[lo:hi], offsets[a:b + 1] - offsets[a])
     assert model.read_index == n
     assert_model_is_run(model, run, what)
+    # the retained list is the concatenation of what went in, whatever the cuts and the lanes
+    raw = bases.tobytes()
+    assert model.retained == [raw[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])], what
+    assert model.retained_info() == dict(reads=n, bases=int(offsets[-1])), what
+    rb, ro = model.retained_export(0, n)
+    assert np.array_equal(rb, bases[:int(offsets[-1])]) and np.array_equal(ro, offsets), what
+    mid = cuts[len(cuts) // 2]
+    rb, ro = model.retained_export(mid, n - mid)
+    assert np.array_equal(rb, bases[int(offsets[mid]):int(offsets[-1])]) and np.array_equal(ro, offsets[mid:] - offsets[mid]), what
 
 
 def test_every_k_and_every_lane_count_is_drawn():
@@ -175,11 +185,45 @@ def test_the_sweep_s_default_draw_covers_every_position_and_kind(orc):
     routes need the engine).  Also a run of the sweep's own code: a draw the model refuses fails here first."""
     import test_gpu_sequences as seq
     met = {}
-    for seed in range(seq.DEFAULT_SEEDS):
-        for item in seq.dry_run(orc, seed):
+    for seed, s in enumerate(dry_sequences(orc)):
+        for item in s.met_here:
             met.setdefault(item, []).append(seed)
+    assert len(seq.POSITIONS) == 27
     missing = [p for p in seq.POSITIONS + ("kind plain", "kind multi-device") if len(met.get(p, ())) < 2]
     assert not missing, (missing, met)
+
+
+_dry = []
+
+
+def dry_sequences(orc):
+    """The default seeds' sequences applied to the model alone, once for the tests that read them."""
+    import test_gpu_sequences as seq
+    if not _dry:
+        for seed in range(seq.DEFAULT_SEEDS):
+            s = seq.dry_sequence(orc, seed)
+            s.model = None   # (what the tests read is met_here, facts and ops: the oracle's tables go now)
+            _dry.append(s)
+    return _dry
+
+
+def test_the_sweep_s_third_generator_is_not_vacuous(orc):
+    """What the retained and panel operations of the default seeds are expected to answer, from the model alone: filters
+    that keep reads, threadings with support and with branch links, prunings that remove nodes, dedups with pairs on
+    both sides of their threshold.  (Conditions on the draw: if one fails, the draw is what has to change.)"""
+    import test_gpu_sequences as seq
+    facts = {}
+    for s in dry_sequences(orc):
+        for name, what in s.facts:
+            facts.setdefault(name, []).append(what)
+    filters = facts["filter_retained"]
+    assert 2 * sum(f["nonempty"] for f in filters) >= len(filters) > 0
+    threads = facts["thread_retained"] + facts["thread_panel"]
+    assert sum(t["read_edges"] > 0 for t in threads) >= 10 and sum(t["links"] > 0 for t in threads) >= 3
+    assert sum(p["removed"] > 0 for p in facts["prune_panel"]) >= 5
+    assert sum(d["within"] and d["outside"] for d in facts["dedup_panel"]) >= 5
+    n_third = [sum(1 for o in s.ops if o[0] in seq.RETAIN_OPS) for s in dry_sequences(orc)]
+    assert 2 * seq.DEFAULT_SEEDS <= sum(n_third) <= 6 * seq.DEFAULT_SEEDS  # (about two to six operations a sequence)
 
 
 def test_the_graph_observations_leave_the_first_draw_as_it_was():
@@ -190,12 +234,31 @@ def test_the_graph_observations_leave_the_first_draw_as_it_was():
     n_graph = 0
     for seed in range(seq.DEFAULT_SEEDS):
         contexts, hooks, ops = seq.draw_plan(seed)
+        ops = [o for o in ops if o[0] not in seq.RETAIN_OPS]
         base = [o for o in ops if o[0] not in seq.GRAPH_OPS]
         assert (contexts, hooks, base) == seq.draw_base_plan(seed)
         n_graph += len(ops) - len(base)
         h.update(repr((contexts, hooks, base)).encode())
     assert seq.DEFAULT_SEEDS == 96 and h.hexdigest() == "4a017601738b1b7d2396d1b9a9f163ef8f466ec8ee85b189defd05e8fa99e9a3"
     assert n_graph > 2 * seq.DEFAULT_SEEDS  # (about one to five operations of 10-30)
+
+
+def test_the_third_generator_leaves_the_second_draw_as_it_was():
+    """The retained and panel operations come from a third generator: without them draw_plan(seed) is, for every default
+    seed, the plan with the graph observations that the sweep drew before they existed (the hash is of that plan's
+    repr).  What the generator decides beside the contexts is not in them."""
+    import test_gpu_sequences as seq
+    h = hashlib.sha256()
+    for seed in range(seq.DEFAULT_SEEDS):
+        contexts, hooks, ops = seq.draw_plan(seed)
+        second = [o for o in ops if o[0] not in seq.RETAIN_OPS]
+        assert (contexts, hooks, second) == seq.draw_graph_plan(seed)
+        h.update(repr((contexts, hooks, second)).encode())
+        props = seq.draw_properties(seed)
+        assert len(props) == len(contexts) and all(set(c) == {"k", "chunks", "histo_max", "flags", "hint", "kind"} for c in contexts)
+        for c, p in zip(contexts, props):   # retention on one device, the flag on several
+            assert not (p["retain"] and p["group_graph"]) and not p[("retain", "group_graph")[c["kind"] == "plain"]]
+    assert h.hexdigest() == "9cf56f8cfac95e70177655ca3bee93500600ba2b8271c2deafc40102a2b02467"
 
 
 def test_neighborhood_and_pcr_extend_over_the_merged_table(orc):
@@ -272,3 +335,104 @@ def test_the_graph_calls_sum_lanes_with_saturation_and_refuse_as_the_abi_does(or
         with pytest.raises(ModelError) as e:
             call(LaneModel(orc, 1, 2, 10))
         assert e.value.code == SHK_ERR_BAD_ARG
+    # SHK_FLAG_GROUP_GRAPH: the multi-device context answers as the merged view
+    flagged = LaneModel(orc, k, 2, 10, multi_device=True, group_graph=True)
+    flagged.insert(0, [x, y], [U32_MAX - 1, U32_MAX - 2])
+    flagged.insert(1, [x], [7])
+    assert flagged.neighborhood([x >> 2], [1], U32_MAX) == m.neighborhood([x >> 2], [1], U32_MAX)
+    assert flagged.neighborhood_panel([([x >> 2], [1], U32_MAX - 2, 64, 64)] * 2, 0) == [m.neighborhood([x >> 2], [1], U32_MAX - 2, 0, 64, 64)] * 2
+
+
+def test_retention_is_a_switch_and_a_list_and_refuses_as_the_abi_does(orc):
+    reads = [b"ACGTACGTTGCA", b"", b"NNACGTN", b"TTTTTTGCA"]
+    bases = np.frombuffer(b"".join(reads), dtype=np.uint8)
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    m = LaneModel(orc, 5, 3, 10)
+    for call in (lambda: m.retained_export(0, 0), lambda: m.filter_retained([[1]]), lambda: m.thread_retained([], [])):
+        with pytest.raises(ModelError, match="reads are not retained") as e:
+            call()
+        assert e.value.code == SHK_ERR_STATE
+    assert m.retained_info() == dict(reads=0, bases=0)
+    m.ingest_reads(bases, offsets)
+    assert m.retained == []
+    with pytest.raises(ModelError, match="holds reads already") as e:
+        m.retain_reads()
+    assert e.value.code == SHK_ERR_STATE
+    m.reset()
+    m.retain_reads()
+    m.retain_reads()   # on twice over an empty store: accepted
+    m.set_read_index(999)   # whatever the read index and the lane: arrival order
+    m.ingest_reads(bases, offsets[:3])
+    m.ingest_batch(2, bases, offsets[2:])
+    assert m.retained == reads and m.retained_info() == dict(reads=4, bases=len(bases))
+    with pytest.raises(ModelError, match="retained already"):
+        m.retain_reads()
+    with pytest.raises(ModelError, match="outside the 4 retained reads") as e:
+        m.retained_export(3, 2)
+    assert e.value.code == SHK_ERR_BAD_ARG
+    rb, ro = m.retained_export(1, 2)
+    assert bytes(rb) == b"NNACGTN" and ro.tolist() == [0, 0, 7] and m.retained_export(4, 0)[1].tolist() == [0]
+    m.reset()   # emptied; the switch stays
+    assert m.retained == [] and m.retain
+    m.ingest_reads(bases, offsets[:2])
+    assert m.retained == reads[:1]
+    m.retain_reads(False)
+    assert m.retained == [] and not m.retain
+    multi = LaneModel(orc, 5, 3, 10, multi_device=True, group_graph=True)   # the flag changes nothing here
+    for call in (lambda: multi.retain_reads(), lambda: multi.retained_info(), lambda: multi.retained_export(0, 0),
+                 lambda: multi.filter_retained([[1]]), lambda: multi.thread_retained([], [])):
+        with pytest.raises(ModelError, match="not available on a multi-device context") as e:
+            call()
+        assert e.value.code == SHK_ERR_STATE
+
+
+def test_the_model_s_panel_answers_are_the_reference_modules(orc):
+    """One fixed input each: the model's filter is panel_cases.expected (the oracle's filter_matches), its threading
+    tests/thread_ref.py as thread_panel_cases.expected reads it, its pruning tests/prune_ref.py, its dedup
+    tests/products_ref.py, its panel neighbourhood tests/pcr_ref.py — the sweep and the model cannot share a mistake there."""
+    import panel_cases as pc
+    import products_ref
+    import prune_cases
+    import thread_panel_cases as tp
+    # the filter: the several-genes case (a read in three genes, a duplicate k-mer, an empty gene)
+    case = [c for c in pc.crafted_cases(orc) if "a read in three genes" in c.name][0]
+    m = LaneModel(orc, case.k, 1, 10)
+    assert m.filter_reads_panel(case.reads, case.genes) == pc.expected(orc, case) == [[0], [0, 1], [], [0, 1, 3], [0, 1], []]
+    m.retain_reads()
+    m.ingest_reads(*pack(case.reads))
+    assert m.filter_retained(case.genes) == pc.expected(orc, case)
+    # the threading: every crafted case as one panel (reads with an invalid byte cannot be retained: the host form), and
+    # the paired panel through the store
+    for p, retained in ((tp.crafted_panel(), False), (tp.paired_panel(), True), (tp.lists_panel(), False)):
+        m = LaneModel(orc, p.k, 1, 10)
+        graphs = [(g.sub_kmer, g.edges) for g in p.graphs]
+        want = [tp.rows(a, len(g.edges)) for a, g in zip(tp.expected(p), p.graphs)]
+        assert m.thread_reads_panel(p.reads, graphs, p.lists, p.read_index, p.mate) == want, p.name
+        if retained:
+            m.retain_reads()
+            m.ingest_reads(*pack(p.reads))
+            assert m.thread_retained(graphs, p.lists, p.read_index, p.mate) == want and want[0][5] == 1, p.name
+    with pytest.raises(ModelError) as e:
+        LaneModel(orc, 1, 1, 10).thread_reads_panel([], [], [])
+    assert e.value.code == SHK_ERR_BAD_ARG
+    # the pruning: every crafted case, in one panel per k
+    cases = prune_cases.cases()
+    for k in sorted({c.k for c in cases}):
+        some = [c for c in cases if c.k == k]
+        got = LaneModel(orc, k, 1, 10).prune_panel([(c.flags, [e[0] for e in c.edges], [e[1] for e in c.edges], [e[2] for e in c.edges]) for c in some],
+                                                    [c.fraction for c in some], [c.stages for c in some])
+        assert got == [c.expected() for c in some]
+    assert any(sum(c.expected().node_keep) < len(c.flags) for c in cases)
+    # the dedup: the greedy pass follows the sorted order, not the input's
+    a, b, c = "ACGTACGTAC", "ACGTACGTAA", "ACGTACGTTA"   # a–b and b–c are one apart, a–c two
+    seqs, scores = [c, b, a], [1.0, 2.0, 3.0]
+    (got,) = LaneModel.dedup_panel([seqs], [scores], [1])
+    order = products_ref.sort_order(seqs, scores)
+    kept, retained = products_ref.sort_and_deduplicate(seqs, scores, 1)
+    assert got == (order, products_ref.pair_matrix(seqs, order, 1), kept, 3, retained)
+    assert got == ([2, 1, 0], [True, False, True], [2, 0], 3, 2)
+
+
+def pack(reads):
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    return np.frombuffer(b"".join(reads), dtype=np.uint8), offsets
