@@ -90,7 +90,14 @@ typedef struct shk_config {
    * partition a batch's records by owner for an exchange between the W contexts instead.  Read/base
    * counters count every read handed over; k-mer counters and histograms cover the owned share
    * (histogram bins are additive across shares: KmerCounts::extend over disjoint key sets,
-   * counting.rs:157-166, io.rs:1023-1028).  0: the whole key space.  1: the whole key space AS A SHARE — the
+   * counting.rs:157-166, io.rs:1023-1028).  "Handed over" is the share's own view: n_reads_ingested, n_bases_read and
+   * n_bases_ingested count the batches given to shk_ingest_* on THIS context and the batches THIS context scattered
+   * (shk_xchg_scatter_device, _begin, shk_xchg_wide_scatter_device), whether or not anybody absorbed the round's
+   * segments afterwards; shk_xchg_absorb and shk_insert_device add nothing to them.  Over the shares of an exchange
+   * job they add up to the job's reads (every read is scattered once), in drop mode to W times that; a round that was
+   * scattered and given up stays in the scattering share's counters until its shk_reset.  shk_finalize on a share that
+   * was handed nothing does not fail with SHK_ERR_NO_READS: the caller looks at the sum over the shares.
+   * 0: the whole key space.  1: the whole key space AS A SHARE — the
    * context takes the shk_xchg_* rounds like any owner share (one segment), so that the exchange path of a
    * W-process job runs unchanged in a world of one. */
   uint32_t n_owners;
@@ -1034,7 +1041,11 @@ typedef struct shk_xchg_layout {
   uint64_t segment_records; /* regions · region_cap */
 } shk_xchg_layout;
 /* layout_bases: what the segments are sized for — every rank of a round passes the same number
- * (≥ its n_bases; e.g. the round's batch size), so that all come out with the same layout; 0 = n_bases. */
+ * (≥ its n_bases; e.g. the round's batch size), so that all come out with the same layout; 0 = n_bases.
+ * The layout is a function of the configuration and of layout_bases, never of a table's size: a share is created with
+ * at least the level-1 fan-out's pages over all owners, so layout.log_p1 is the fan-out on every share from shk_create
+ * on, and a share whose table has grown scatters and absorbs the same segments as a peer whose table has not — no
+ * caller has anything to do about a peer's growth (tests/test_gpu_share_sequences.py: route `grew_alone`). */
 int shk_xchg_scatter_device(shk_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs,
                             uint64_t n_bases, uint64_t layout_bases, void **d_records, void **d_cursors,
                             shk_xchg_layout *layout, uint64_t *n_foreign_spilled);
@@ -1042,7 +1053,14 @@ int shk_xchg_scatter_device(shk_ctx *ctx, const void *d_bases, const void *d_off
  * scatter runs — the absorbs of the previous round's segments: _begin launches and returns at once, with the
  * segments' addresses and layout (functions of the configuration, not of the data), _end waits for the scatter
  * and reports what shk_xchg_scatter_device reports at its return (SHK_ERR_INVALID_CHAR and the poisoned context,
- * *n_foreign_spilled).  Between the two: shk_xchg_absorb only; the segments are complete when _end has returned.
+ * *n_foreign_spilled).  The segments are complete when _end has returned.  BETWEEN THE TWO the copy of the statistics
+ * is pending and the scatter's outcome has not been looked at; what stays allowed on the context is
+ *   shk_xchg_absorb, shk_reset (the round is given up), shk_destroy,
+ *   and the calls that touch neither the device nor the job's state: shk_last_error, shk_stream, shk_xchg_feasible,
+ *   shk_abi_version, shk_key_owner (shk_alloc_device and shk_free_device, which answer no code, are not looked at).
+ * Every other entry point that takes the context returns SHK_ERR_STATE, "an exchange scatter is begun and not ended
+ * (shk_xchg_scatter_end)", and leaves the context as it was but for that text: the _end that follows reports what it
+ * would have reported and the round completes exactly.
  * With the one-call form the GPU stood idle every round from the end of the scatter until the host had woken up
  * and launched the absorbs (io.rs has no counterpart: it is the counting loop's batch boundary, io.rs:340-361). */
 int shk_xchg_scatter_begin(shk_ctx *ctx, const void *d_bases, const void *d_offsets, uint64_t n_seqs,
@@ -1069,7 +1087,9 @@ int shk_xchg_wide_scatter_device(shk_ctx *ctx, const void *d_bases, const void *
 int shk_xchg_feasible(shk_ctx *ctx);
 /* KmerCounts::insert (counting.rs:152-154) from device memory with a chunk lane per record:
  * saturating add of d_counts[i] to d_kmers[i] in lane d_lanes[i]; k-mers the context does not own
- * are dropped; d_counts = NULL: one occurrence each.  Synchronous. */
+ * are dropped; d_counts = NULL: one occurrence each.  A count of 0 creates the entry all the same, as
+ * shk_insert_counts does (a key with merged count 0 sits in no histogram bin: io.rs:1127-1132 then fails finalize).
+ * Synchronous. */
 int shk_insert_device(shk_ctx *ctx, const void *d_kmers, const void *d_lanes, const void *d_counts, uint64_t n);
 /* The context's HIP stream (hipStream_t): device work queued by the calls above is ordered on it, so
  * a host that runs its collectives on the same stream needs no host-side synchronisation. */

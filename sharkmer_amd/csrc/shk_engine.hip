@@ -441,6 +441,16 @@ int single_device_only(shk_ctx *c) {
   return SHK_OK;
 }
 
+// Between shk_xchg_scatter_begin and _end the asynchronous copy of the statistics is pending and the scatter's outcome
+// has not been looked at: every entry point that takes the context opens with this, except the ones include/shk.h
+// lists there (shk_xchg_absorb, shk_reset, shk_destroy, and the calls that touch neither the device nor the job's state).
+// Nothing of the context is touched but its error text: the _end that follows reports what it would have reported.
+constexpr const char *XS_BEGUN = "an exchange scatter is begun and not ended (shk_xchg_scatter_end)";
+int xs_closed(shk_ctx *c) {
+  if (c && c->xs_pending) return fail(c, SHK_ERR_STATE, "%s", XS_BEGUN);
+  return SHK_OK;
+}
+
 // One call's arrays in a grow-only device buffer: take<T>(n) per array, in order (offsets, 16-byte aligned), one ensure()
 // of the total, then at<T>(offset).  Arrays taken one after the other are adjacent up to that padding.
 struct Scratch {
@@ -2658,6 +2668,7 @@ static int ingest_host(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets
 
 int shk_ingest_batch(shk_ctx *c, uint32_t chunk_id, const uint8_t *bases, const uint64_t *offsets,
                      uint64_t n_seqs) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (chunk_id >= c->n_lanes)
     return fail(c, SHK_ERR_BAD_ARG, "chunk_id %u out of range (n_chunks %u)", chunk_id, c->n_lanes);
@@ -2666,18 +2677,21 @@ int shk_ingest_batch(shk_ctx *c, uint32_t chunk_id, const uint8_t *bases, const 
 }
 
 int shk_ingest_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group) return group_ingest(c, bases, offsets, n_seqs, -1);
   return ingest_host(c, bases, offsets, n_seqs, -1);
 }
 
 // ---- 2-bit packed input (the reference's Read::from_str layout, encoding.rs:60-95, + an N mask) ----------
 int shk_ingest_packed(shk_ctx *c, const uint8_t *packed, const uint32_t *nmask, const uint64_t *offsets, uint64_t n_seqs) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group) return fail(c, SHK_ERR_STATE, "a multi-device context takes ASCII host buffers");
   if (n_seqs && !packed) return fail(c, SHK_ERR_BAD_ARG, "null packed stream");
   return ingest_host(c, nullptr, offsets, n_seqs, -1, packed, nmask);
 }
 
 int shk_pack_reads_device(shk_ctx *c, const void *d_bases, uint64_t n_bases, void *d_packed, void *d_nmask) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n_bases == 0) return SHK_OK;
   if (!d_bases || !d_packed || !d_nmask) return fail(c, SHK_ERR_BAD_ARG, "null buffer");
@@ -2698,6 +2712,7 @@ int shk_pack_reads_device(shk_ctx *c, const void *d_bases, uint64_t n_bases, voi
 }
 
 int shk_unpack_reads_device(shk_ctx *c, const void *d_packed, const void *d_nmask, uint64_t n_bases, void *d_bases) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n_bases == 0) return SHK_OK;
   if (!d_bases || !d_packed || !d_nmask) return fail(c, SHK_ERR_BAD_ARG, "null buffer");
@@ -2710,6 +2725,7 @@ int shk_unpack_reads_device(shk_ctx *c, const void *d_packed, const void *d_nmas
 
 int shk_ingest_packed_device(shk_ctx *c, const void *d_packed, const void *d_nmask, const void *d_offsets, uint64_t n_seqs,
                              uint64_t n_bases) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group) return fail(c, SHK_ERR_STATE, "a multi-device context takes host buffers");
   if (!c) return SHK_ERR_BAD_ARG;
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -2724,6 +2740,7 @@ int shk_ingest_packed_device(shk_ctx *c, const void *d_packed, const void *d_nma
 }
 
 int shk_set_read_index(shk_ctx *c, uint64_t next_read_index) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) c->group->next_read = next_read_index;
   c->n_reads_read = next_read_index;
@@ -2732,6 +2749,7 @@ int shk_set_read_index(shk_ctx *c, uint64_t next_read_index) {
 
 int shk_ingest_reads_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs,
                             uint64_t n_bases) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) return fail(c, SHK_ERR_STATE, "a multi-device context takes host buffers (shk_ingest_reads / shk_ingest_batch)");
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -2740,6 +2758,7 @@ int shk_ingest_reads_device(shk_ctx *c, const void *d_bases, const void *d_offse
 
 int shk_insert_counts(shk_ctx *c, uint32_t chunk_id, const uint64_t *kmers, const uint32_t *counts,
                       uint64_t n) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) {  // every share is offered every k-mer and keeps what it owns
     shk_group *g = c->group;
@@ -2805,7 +2824,7 @@ static int xchg_scatter_call(shk_ctx *c, const void *d_bases, const void *d_offs
   SHK_TRY(single_device_only(c));
   if (!d_records || !d_cursors || !layout) return SHK_ERR_BAD_ARG;
   HIPC(c, hipSetDevice(c->cfg.device));
-  if (c->xs_pending) return fail(c, SHK_ERR_STATE, "an exchange scatter is begun and not ended (shk_xchg_scatter_end)");
+  SHK_TRY(xs_closed(c));
   if (n_bases > SHK_XCHG_MAX_BASES || (layout_bases && layout_bases > SHK_XCHG_MAX_BASES))
     return fail(c, SHK_ERR_BAD_ARG, "an exchange batch takes at most %llu bases", (unsigned long long)SHK_XCHG_MAX_BASES);
   XchgOut xo{};
@@ -2863,6 +2882,7 @@ int shk_xchg_scatter_end(shk_ctx *c, uint64_t *n_foreign_spilled) {
 
 int shk_xchg_wide_scatter_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                                  void **d_kmers, void **d_lanes, uint64_t *counts) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!d_kmers || !d_lanes || !counts) return SHK_ERR_BAD_ARG;
   if (!c->is_share()) return fail(c, SHK_ERR_STATE, "not an owner share (shk_config.n_owners = 0: say 1 for a share that is the whole key space)");
@@ -2953,6 +2973,7 @@ int shk_xchg_absorb(shk_ctx *c, const void *d_records, const void *d_cursors, co
 }
 
 int shk_xchg_spill(shk_ctx *c, void **d_kmers, void **d_lanes, void **d_counts, uint64_t *n) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!n) return SHK_ERR_BAD_ARG;
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -2967,6 +2988,7 @@ int shk_xchg_spill(shk_ctx *c, void **d_kmers, void **d_lanes, void **d_counts, 
 }
 
 int shk_xchg_spill_clear(shk_ctx *c) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
   HIPC(c, hipMemsetAsync(&c->d_stats->scratch[0], 0, sizeof(unsigned long long), c->stream));
@@ -3037,6 +3059,7 @@ static int insert_list_paged(shk_ctx *c, const uint64_t *d_kmers, const uint32_t
 }
 
 int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, const void *d_counts, uint64_t n) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -3056,6 +3079,16 @@ int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, cons
   if (n == 0) return SHK_OK;
   if (!d_kmers) return fail(c, SHK_ERR_BAD_ARG, "null k-mers");
   c->finalized = c->hist_ready = false;
+  if (d_counts && !c->zero_count_keys) {  // counting.rs:152-154 creates the entry whatever the count: a 0 is noted as shk_insert_counts notes it
+    std::vector<uint32_t> h(n);           // (this is the synchronous path of global atomics: 4 bytes per record more on the bus)
+    HIPC(c, hipMemcpyAsync(h.data(), d_counts, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (uint32_t v : h)
+      if (v == 0) {
+        c->zero_count_keys = true;
+        break;
+      }
+  }
   int rc = ensure_capacity(c, n >> c->owner_bits);
   if (rc != SHK_OK) return rc;
   c->n_inserted += n;
@@ -3075,6 +3108,7 @@ int shk_insert_device(shk_ctx *c, const void *d_kmers, const void *d_lanes, cons
 void *shk_stream(shk_ctx *c) { return c && !c->group ? (void *)c->stream : nullptr; }
 
 int shk_sync(shk_ctx *c) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) {
     for (uint32_t d = 0; d < c->group->D; ++d) {
@@ -3199,6 +3233,7 @@ static int finalize_fetch(shk_ctx *c) {
 }
 
 int shk_finalize(shk_ctx *c) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) return group_finalize(c);
   if (c->poisoned) return fail(c, c->poison_code, "%s", c->err.c_str());
@@ -3242,6 +3277,7 @@ int shk_finalize(shk_ctx *c) {
 }
 
 int shk_finalize_begin(shk_ctx *c, uint64_t user_word, void **d_sum, uint64_t *n_words) {
+  SHK_TRY(xs_closed(c));
   if (!c || !d_sum || !n_words) return SHK_ERR_BAD_ARG;
   if (c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
   c->finalized = c->hist_ready = false;
@@ -3259,6 +3295,7 @@ int shk_finalize_begin(shk_ctx *c, uint64_t user_word, void **d_sum, uint64_t *n
 }
 
 int shk_finalize_end(shk_ctx *c, int *again, uint64_t *user_sum) {
+  SHK_TRY(xs_closed(c));
   if (!c || !again) return SHK_ERR_BAD_ARG;
   if (c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
   if (!c->fin_scanned) return fail(c, SHK_ERR_STATE, "shk_finalize_end without shk_finalize_begin");
@@ -3283,6 +3320,7 @@ int shk_finalize_end(shk_ctx *c, int *again, uint64_t *user_sum) {
 }
 
 int shk_histograms(shk_ctx *c, uint64_t *out) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) {
     if (!c->group->finalized && !c->group->hist_ready) return fail(c, SHK_ERR_STATE, "shk_histograms before shk_finalize");
@@ -3299,6 +3337,7 @@ int shk_histograms(shk_ctx *c, uint64_t *out) {
 }
 
 int shk_get_counters(shk_ctx *c, shk_counters *o) {
+  SHK_TRY(xs_closed(c));
   if (!c || !o) return SHK_ERR_BAD_ARG;
   if (c->group) return group_counters(c, o);
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -3335,6 +3374,7 @@ int shk_get_counters(shk_ctx *c, shk_counters *o) {
 }
 
 int shk_get_timings(shk_ctx *c, shk_timings *o) {
+  SHK_TRY(xs_closed(c));
   if (!c || !o) return SHK_ERR_BAD_ARG;
   if (c->group) {  // summed over the devices
     memset(o, 0, sizeof *o);
@@ -3352,6 +3392,7 @@ int shk_get_timings(shk_ctx *c, shk_timings *o) {
 }
 
 int shk_get_lazy_table_timing(shk_ctx *c, double *ms, uint64_t *launches) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   double m = 0;
   uint64_t n = 0;
@@ -3373,12 +3414,14 @@ int shk_get_lazy_table_timing(shk_ctx *c, double *ms, uint64_t *launches) {
 }
 
 int shk_get_scatter_segments(shk_ctx *c, uint32_t *segs) {
+  SHK_TRY(xs_closed(c));
   if (!c || !segs) return SHK_ERR_BAD_ARG;
   *segs = c->group ? (c->group->D ? c->group->ctx[0]->last_segs : 0u) : c->last_segs;
   return SHK_OK;
 }
 
 int shk_reset_timings(shk_ctx *c) {
+  SHK_TRY(xs_closed(c));
   if (!c) return SHK_ERR_BAD_ARG;
   if (c->group) {
     for (uint32_t d = 0; d < c->group->D; ++d) (void)shk_reset_timings(c->group->ctx[d]);
@@ -3462,6 +3505,7 @@ void shk_free_device(shk_ctx *c, void *p) {
 
 int shk_synth_reads_device(shk_ctx *c, const shk_synth *spec, uint64_t first_read, uint64_t n_reads,
                            void *d_bases, void *d_offsets) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!spec) return SHK_ERR_BAD_ARG;
   if (spec->read_len == 0 || spec->genome_len < spec->read_len)

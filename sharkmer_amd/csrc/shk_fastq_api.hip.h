@@ -314,6 +314,7 @@ int shk_fastq_device_totals(uint64_t *n_batches, uint64_t *n_records, uint64_t *
 
 int shk_fastq_parse_device(shk_ctx *c, const void *d_text, uint64_t n_bytes, const shk_fastq_text_params *params, void *d_bases, uint64_t bases_cap,
                            void *d_offsets, uint64_t offsets_cap, shk_fastq_text_result *out) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!params || !out || (n_bytes && !d_text)) return fail(c, SHK_ERR_BAD_ARG, "shk_fastq_parse_device: a null argument");
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -342,6 +343,7 @@ int shk_fastq_parse_device(shk_ctx *c, const void *d_text, uint64_t n_bytes, con
 }
 
 int shk_crc32_members_device(shk_ctx *c, const void *d_text, const void *d_jobs, uint32_t n, void *d_crc) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n && (!d_jobs || !d_crc)) return fail(c, SHK_ERR_BAD_ARG, "shk_crc32_members_device: a null argument");
   if (!n) return SHK_OK;
@@ -360,6 +362,7 @@ int shk_crc32_members_device(shk_ctx *c, const void *d_text, const void *d_jobs,
 
 int shk_ingest_fastq_files_device(shk_ctx *c, const char *const *paths, uint32_t n_paths, uint64_t max_reads, uint64_t validate_every,
                                   shk_fastq_device_stats *out) {
+  SHK_TRY(xs_closed(c));
   if (!c || !out) return SHK_ERR_BAD_ARG;
   *out = shk_fastq_device_stats{};
   auto not_eligible = [&] {

@@ -333,6 +333,7 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
 }  // namespace
 
 extern "C" int shk_pcr_run(shk_ctx *c, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params, shk_pcr_run_out *out) {
+  SHK_TRY(xs_closed(c));
   if (!c || !params || !out || !out->status || !out->records.record_offsets || (n_genes && !genes)) return SHK_ERR_BAD_ARG;
   try {
     return pcr_run_impl(c, genes, n_genes, params, out);

@@ -59,6 +59,7 @@ constexpr uint64_t DEDUP_DEVICE_PAIRS = 0;  // default of SHK_DEDUP_DEVICE_PAIRS
 
 extern "C" int shk_pcr_dedup_panel(shk_ctx *c, const uint8_t *seqs, const uint64_t *seq_offsets, const uint64_t *record_offsets,
                                    const double *scores, const uint32_t *thresholds, uint32_t n_genes, shk_pcr_dedup_out *out) {
+  SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) { return shk_pcr_dedup_panel(d, seqs, seq_offsets, record_offsets, scores, thresholds, n_genes, out); });
@@ -252,6 +253,7 @@ extern "C" int shk_pcr_dedup_panel(shk_ctx *c, const uint8_t *seqs, const uint64
 
 extern "C" int shk_pcr_products_panel(shk_ctx *c, const shk_pcr_graphs *graphs, const shk_pcr_paths_params *params, const uint32_t *thresholds,
                                       shk_pcr_records *out, uint32_t *retained, double *device_ms) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group) return on_any_device(c, [&](shk_ctx *d) { return shk_pcr_products_panel(d, graphs, params, thresholds, out, retained, device_ms); });
   if (!c || !out || !out->record_offsets) return SHK_ERR_BAD_ARG;
   if (device_ms) *device_ms = 0.0;

@@ -45,6 +45,7 @@ void prune_csr_side(const uint32_t *at, const uint32_t *other, const uint32_t *c
 extern "C" int shk_pcr_prune_panel(shk_ctx *c, const uint64_t *node_sub_kmers, const uint8_t *node_flags, const uint64_t *node_offsets,
                                    const uint32_t *edge_src, const uint32_t *edge_tgt, const uint32_t *edge_counts, const uint64_t *edge_offsets,
                                    uint32_t n_genes, const shk_pcr_prune_params *params, shk_pcr_prune_out *out) {
+  SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {

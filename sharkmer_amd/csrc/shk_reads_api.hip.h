@@ -127,6 +127,7 @@ extern "C" {
 
 int shk_filter_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
                      const uint64_t *primer_kmers, uint64_t n_kmers, uint8_t *out_matches) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) { return shk_filter_reads(d, bases, offsets, n_seqs, primer_kmers, n_kmers, out_matches); });
   if (!c || (n_seqs && (!offsets || !out_matches))) return SHK_ERR_BAD_ARG;
@@ -163,6 +164,7 @@ int shk_filter_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, 
 
 int shk_kmers_from_reads(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs,
                          uint64_t *kmers, uint64_t kmers_cap, uint32_t *n_kmers, uint8_t *bad_byte) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) { return shk_kmers_from_reads(d, bases, offsets, n_seqs, kmers, kmers_cap, n_kmers, bad_byte); });
   if (!c || (n_seqs && (!offsets || !n_kmers || !bad_byte))) return SHK_ERR_BAD_ARG;
@@ -562,6 +564,7 @@ int thread_panel_run(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, co
 int shk_thread_reads_device(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
                             uint64_t n_edges, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                             const uint64_t *read_index, const uint8_t *mate, shk_thread_out *out) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_thread_reads_device(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, d_bases, d_offsets, n_seqs, n_bases, read_index, mate, out);
@@ -580,6 +583,7 @@ int shk_thread_reads_device(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t
 int shk_thread_reads(shk_ctx *c, const uint64_t *node_sub_kmers, uint64_t n_nodes, const uint32_t *edge_src, const uint32_t *edge_tgt,
                      uint64_t n_edges, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *read_index,
                      const uint8_t *mate, shk_thread_out *out) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_thread_reads(d, node_sub_kmers, n_nodes, edge_src, edge_tgt, n_edges, bases, offsets, n_seqs, read_index, mate, out);
@@ -603,6 +607,7 @@ int shk_thread_reads_panel_device(shk_ctx *c, const uint64_t *node_sub_kmers, co
                                   const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const void *d_bases, const void *d_offsets,
                                   uint64_t n_seqs, uint64_t n_bases, const uint64_t *list_offsets, const uint64_t *list_reads,
                                   const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_thread_reads_panel_device(d, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, d_bases, d_offsets, n_seqs,
@@ -623,6 +628,7 @@ int shk_thread_reads_panel(shk_ctx *c, const uint64_t *node_sub_kmers, const uin
                            const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const uint8_t *bases, const uint64_t *offsets,
                            uint64_t n_seqs, const uint64_t *list_offsets, const uint64_t *list_reads, const uint64_t *read_index,
                            const uint8_t *mate, shk_thread_panel_out *out) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_thread_reads_panel(d, node_sub_kmers, node_offsets, edge_src, edge_tgt, edge_offsets, n_genes, bases, offsets, n_seqs, list_offsets,
@@ -744,6 +750,7 @@ int panel_core(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBa
 int shk_filter_reads_panel_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                                   const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets,
                                   uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_filter_reads_panel_device(d, d_bases, d_offsets, n_seqs, n_bases, primer_kmers, gene_offsets, n_genes, match_offsets, match_reads,
@@ -764,6 +771,7 @@ int shk_filter_reads_panel_device(shk_ctx *c, const void *d_bases, const void *d
 int shk_filter_reads_panel(shk_ctx *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_seqs, const uint64_t *primer_kmers,
                            const uint64_t *gene_offsets, uint32_t n_genes, uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap,
                            uint64_t *n_matches) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_filter_reads_panel(d, bases, offsets, n_seqs, primer_kmers, gene_offsets, n_genes, match_offsets, match_reads, match_cap, n_matches);
@@ -786,6 +794,7 @@ int shk_filter_reads_panel(shk_ctx *c, const uint8_t *bases, const uint64_t *off
 
 int shk_gather_reads_device(shk_ctx *c, const void *d_bases, const void *d_offsets, uint64_t n_seqs, const uint64_t *read_ids, uint64_t n_ids,
                             void *d_out_bases, uint64_t out_bases_cap, void *d_out_offsets, uint64_t *n_out_bases) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return on_any_device(c, [&](shk_ctx *d) {
       return shk_gather_reads_device(d, d_bases, d_offsets, n_seqs, read_ids, n_ids, d_out_bases, out_bases_cap, d_out_offsets, n_out_bases);

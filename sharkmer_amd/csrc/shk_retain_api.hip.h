@@ -32,6 +32,7 @@ int batch_from_retained(shk_ctx *c, const char *who, ReadBatch *b) {
 extern "C" {
 
 int shk_retain_reads(shk_ctx *c, int on, uint64_t capacity_bases_hint) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
   RetainStore &st = c->retain;
@@ -52,6 +53,7 @@ int shk_retain_reads(shk_ctx *c, int on, uint64_t capacity_bases_hint) {
 }
 
 int shk_retained_info(shk_ctx *c, uint64_t *n_reads, uint64_t *n_bases, uint64_t *device_bytes) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   const RetainStore &st = c->retain;
   if (n_reads) *n_reads = st.n_reads;
@@ -62,6 +64,7 @@ int shk_retained_info(shk_ctx *c, uint64_t *n_reads, uint64_t *n_bases, uint64_t
 
 int shk_retained_export(shk_ctx *c, uint64_t first_read, uint64_t n_reads, uint8_t *bases, uint64_t bases_cap, uint64_t *offsets,
                         uint64_t *n_bases) {
+  SHK_TRY(xs_closed(c));
   if (c && !c->group && (!offsets || !n_bases)) return SHK_ERR_BAD_ARG;
   SHK_TRY(retained_begin(c, "shk_retained_export"));
   const RetainStore &st = c->retain;
@@ -95,6 +98,7 @@ int shk_retained_export(shk_ctx *c, uint64_t first_read, uint64_t n_reads, uint8
 
 int shk_filter_reads_panel_retained(shk_ctx *c, const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes,
                                     uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches) {
+  SHK_TRY(xs_closed(c));
   if (c && !c->group && (!match_offsets || !n_matches)) return SHK_ERR_BAD_ARG;
   SHK_TRY(single_device_only(c));
   if (!c->retain.on) return fail(c, SHK_ERR_STATE, "shk_filter_reads_panel_retained: reads are not retained (shk_retain_reads)");
@@ -113,6 +117,7 @@ int shk_filter_reads_panel_retained(shk_ctx *c, const uint64_t *primer_kmers, co
 int shk_thread_reads_panel_retained(shk_ctx *c, const uint64_t *node_sub_kmers, const uint64_t *node_offsets, const uint32_t *edge_src,
                                     const uint32_t *edge_tgt, const uint64_t *edge_offsets, uint32_t n_genes, const uint64_t *list_offsets,
                                     const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
+  SHK_TRY(xs_closed(c));
   if (c && !c->group && !out) return SHK_ERR_BAD_ARG;
   SHK_TRY(single_device_only(c));
   if (!c->retain.on) return fail(c, SHK_ERR_STATE, "shk_thread_reads_panel_retained: reads are not retained (shk_retain_reads)");

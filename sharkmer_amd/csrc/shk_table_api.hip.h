@@ -406,6 +406,7 @@ int pcr_graphs_out(shk_ctx *c, const char *what, const std::vector<PcrGraph> &gs
 extern "C" {
 
 int shk_export_table(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
+  SHK_TRY(xs_closed(c));
   if (!c || !n_out) return SHK_ERR_BAD_ARG;
   if (c->group)
     return each_share_appends(c, kmers, counts, cap, n_out, [](shk_ctx *s, uint64_t *k, uint32_t *ct, uint64_t room, uint64_t *n) {
@@ -429,6 +430,7 @@ int shk_export_table(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap
 }
 
 int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group) {  // exactly one share owns a k-mer; the others answer 0
     std::vector<uint32_t> part(n);
     std::fill(counts, counts + n, 0u);
@@ -462,6 +464,7 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
                      uint32_t max_levels, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out,
                      uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t fringe_cap, uint64_t *n_fringe,
                      uint32_t *levels_done) {
+  SHK_TRY(xs_closed(c));
   if (!c || !n_out || !n_fringe || !levels_done || (n_seeds && (!nodes || !dirs))) return SHK_ERR_BAD_ARG;
   SHK_TRY(graph_call_begin(c, "shk_neighborhood"));
   const uint32_t k = c->cfg.k;
@@ -482,6 +485,7 @@ int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_co
                    uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t node_cap, uint64_t *n_nodes, uint32_t *edge_src,
                    uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t edge_cap, uint64_t *n_edges, uint32_t *found_path,
                    uint32_t *threshold_used, uint32_t *steps_run) {
+  SHK_TRY(xs_closed(c));
   if (!c || !p || !n_nodes || !n_edges || !found_path || !threshold_used || !steps_run) return SHK_ERR_BAD_ARG;
   if ((n_fwd && (!fwd_kmers || !fwd_counts)) || (n_rev && (!rev_kmers || !rev_counts))) return SHK_ERR_BAD_ARG;
   SHK_TRY(graph_call_begin(c, "shk_pcr_extend"));
@@ -510,6 +514,7 @@ int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dir
                            const uint32_t *min_counts, uint32_t max_levels, const uint64_t *caps, const uint64_t *fringe_caps,
                            uint64_t *kmers, uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs,
                            uint64_t *n_fringe, uint32_t *levels_done) {
+  SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (!c) return SHK_ERR_BAD_ARG;
   SHK_TRY(graph_call_begin(c, "shk_neighborhood_panel"));
@@ -544,6 +549,7 @@ int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_
                          uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts,
                          uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path, uint32_t *threshold_used,
                          uint32_t *steps_run) {
+  SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (!c || !node_offsets || !edge_offsets) return SHK_ERR_BAD_ARG;
   SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
@@ -580,6 +586,7 @@ int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_
 
 int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,
                     uint32_t min_count, uint64_t *kmers, uint32_t *counts, uint64_t cap, uint64_t *n_out) {
+  SHK_TRY(xs_closed(c));
   if (c && c->group)
     return each_share_appends(c, kmers, counts, cap, n_out, [&](shk_ctx *s, uint64_t *k, uint32_t *ct, uint64_t room, uint64_t *n) {
       return shk_find_oligos(s, oligos, n_oligos, oligo_len, min_count, k, ct, room, n);
@@ -678,6 +685,7 @@ int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, st
 
 int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
                      uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  SHK_TRY(xs_closed(c));
   if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
   if (n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
   const uint32_t k = c->cfg.k;
@@ -796,6 +804,7 @@ int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, 
 }
 
 int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
   SHK_TRY(settle(c));  // a pending spill may still grow the table
@@ -806,6 +815,7 @@ int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint
 }
 
 int shk_table_reserve_pages(shk_ctx *c, uint64_t n_pages) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   HIPC(c, hipSetDevice(c->cfg.device));
   SHK_TRY(settle(c));  // (no tb_fresh: grow_to carries nothing over from a table that was still to be cleared)
@@ -816,6 +826,7 @@ int shk_table_reserve_pages(shk_ctx *c, uint64_t n_pages) {
 }
 
 int shk_table_device_ptrs(shk_ctx *c, void **d_keys, void **d_vals) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   SHK_TRY(table_read_begin(c));
   HIPC(c, hipStreamSynchronize(c->stream));
@@ -826,6 +837,7 @@ int shk_table_device_ptrs(shk_ctx *c, void **d_keys, void **d_vals) {
 
 int shk_merge_pages(shk_ctx *c, uint64_t p0, uint64_t p1, const void *d_keys, const void *d_vals,
                     uint64_t vals_lane_stride) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (p1 <= p0) return SHK_OK;
   SHK_TRY(table_read_begin(c));
@@ -847,6 +859,7 @@ int shk_merge_pages(shk_ctx *c, uint64_t p0, uint64_t p1, const void *d_keys, co
 }
 
 int shk_owner_counts(shk_ctx *c, uint32_t n_owners, uint64_t *counts) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!counts || n_owners == 0) return SHK_ERR_BAD_ARG;
   SHK_TRY(owner_split_check(c, n_owners));
@@ -868,6 +881,7 @@ int shk_owner_counts(shk_ctx *c, uint32_t n_owners, uint64_t *counts) {
 // nothing launched in between — the segment offsets it is given were worked out from those counts.)
 int shk_compact_owners(shk_ctx *c, uint32_t n_owners, const uint64_t *seg_offsets, void *d_keys, void *d_vals,
                        uint64_t vals_lane_stride, int32_t skip_owner) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!seg_offsets || n_owners == 0) return SHK_ERR_BAD_ARG;
   SHK_TRY(owner_split_check(c, n_owners));
@@ -880,6 +894,7 @@ int shk_compact_owners(shk_ctx *c, uint32_t n_owners, const uint64_t *seg_offset
 
 // (No settle either, for the same reason: `counts` are shk_owner_counts' answer.)
 int shk_compact_owners_packed(shk_ctx *c, uint32_t n_owners, const uint64_t *counts, void *d_buf, int32_t skip_owner) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!counts || n_owners == 0) return SHK_ERR_BAD_ARG;
   SHK_TRY(owner_split_check(c, n_owners));
@@ -899,6 +914,7 @@ int shk_compact_owners_packed(shk_ctx *c, uint32_t n_owners, const uint64_t *cou
 }
 
 int shk_compact_owners_fixed(shk_ctx *c, uint32_t n_owners, uint64_t capacity, void *d_buf, int32_t skip_owner) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n_owners == 0 || capacity == 0 || !d_buf) return SHK_ERR_BAD_ARG;
   SHK_TRY(owner_split_check(c, n_owners));
@@ -928,6 +944,7 @@ int shk_compact_owners_fixed(shk_ctx *c, uint32_t n_owners, uint64_t capacity, v
 }
 
 int shk_merge_pieces_max(shk_ctx *c, uint64_t *max_count) {
+  SHK_TRY(xs_closed(c));
   if (!c || !max_count) return SHK_ERR_BAD_ARG;
   if (c->group) return fail(c, SHK_ERR_STATE, "not available on a multi-device context");
   HIPC(c, hipSetDevice(c->cfg.device));
@@ -940,12 +957,14 @@ static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint
                         uint64_t piece_cap, uint32_t skip_piece);
 
 int shk_merge_entries(shk_ctx *c, const void *d_keys, const void *d_vals, uint64_t n, uint64_t vals_lane_stride) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n == 0) return SHK_OK;
   return merge_launch(c, d_keys, d_vals, n, vals_lane_stride, 0, ~0u);
 }
 
 int shk_merge_pieces(shk_ctx *c, const void *d_buf, uint32_t n_pieces, uint64_t capacity, int32_t skip_piece) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (!d_buf) return SHK_ERR_BAD_ARG;
   if (n_pieces == 0 || capacity == 0) return SHK_OK;
@@ -989,6 +1008,7 @@ static int merge_launch(shk_ctx *c, const void *d_keys, const void *d_vals, uint
 }
 
 int shk_set_owned_pages(shk_ctx *c, uint64_t p0, uint64_t p1) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (p1 < p0 || p1 > (1ull << c->tb.log_pages)) return fail(c, SHK_ERR_BAD_ARG, "bad page range");
   c->own_p0 = p0;
@@ -1000,6 +1020,7 @@ int shk_set_owned_pages(shk_ctx *c, uint64_t p0, uint64_t p1) {
 }
 
 int shk_set_owner_share(shk_ctx *c, uint32_t n_owners, uint32_t owner) {
+  SHK_TRY(xs_closed(c));
   SHK_TRY(single_device_only(c));
   if (n_owners == 0 || (n_owners & (n_owners - 1)) || owner >= n_owners || n_owners > (1ull << c->tb.log_pages))
     return fail(c, SHK_ERR_BAD_ARG, "bad owner share %u of %u", owner, n_owners);

@@ -46,19 +46,22 @@ def exchange_parts(dist, out: torch.Tensor, inp: torch.Tensor, world: int, rank:
     mesh still carries a rank's W−1 transfers at once), the rank's own part by a device copy (skip_self: not at all —
     the caller uses it where it lies).  in_pieces: with UNEQUAL parts every rank must take the same route — the caller
     then says which (True: send/recv pairs), from a maximum it has reduced over the ranks."""
-    if in_splits is None:
+    explicit = in_splits is not None
+    if not explicit:
         per = inp.numel() // world
         assert inp.numel() == per * world and out.numel() == inp.numel()
         in_splits = out_splits = [per] * world
     esz = inp.element_size()
     if in_pieces is None:
         largest = max(max(in_splits), max(out_splits)) * esz
-        if len(set(in_splits)) != 1 or list(in_splits) != list(out_splits):
-            # UNEQUAL parts and nobody has agreed on the route: a rank only sees its own row and column of the W x W
+        if explicit:
+            # EXPLICIT parts and nobody has agreed on the route: a rank only sees its own row and column of the W x W
             # part sizes, and a rank whose parts are all small must not call all_to_all_single while a pair with a
             # large part waits in send/recv pairs (a hang on gloo, undefined pairing on RCCL).  One small
-            # all_reduce(MAX) makes the choice the same everywhere; callers that already hold a job-wide maximum
-            # pass in_pieces and skip it.
+            # all_reduce(MAX) makes the choice the same everywhere.  It runs whatever this rank's own sizes look like
+            # — a rank whose row and column happen to be equal (5 5 / 5 7: rank 0) cannot know that a peer's are not, and
+            # skipping the collective there is the very mismatch this prevents.  Callers that already hold a job-wide
+            # maximum pass in_pieces and skip it.
             t = torch.tensor([largest], dtype=torch.int64, device=inp.device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             largest = int(t.item())

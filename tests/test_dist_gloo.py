@@ -601,3 +601,35 @@ def test_a_byte_found_at_the_scatter_s_end_takes_every_rank_out(tmp_path, monkey
     mp.spawn(_owner_error_worker, args=(2, port, 21, str(tmp_path)), nprocs=2, join=True)
     assert "Invalid character 'x' in sequence. Only ACGTN allowed." in (tmp_path / "outcome_1.txt").read_text()
     assert "a peer rank failed" in (tmp_path / "outcome_0.txt").read_text()
+
+
+def _explicit_splits_worker(rank, world, port, out_dir):
+    """Part sizes a[s][d] (rank s sends rank d): 5 5 / 5 7.  Rank 0's row and column are both (5, 5); rank 1's are (5, 7)."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from sharkmer_amd.dist import exchange_parts
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import datetime
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
+    a = [[5, 5], [5, 7]]
+    send, recv = a[rank], [a[s][rank] for s in range(world)]
+    inp = torch.cat([torch.arange(n, dtype=torch.int64) + 1000 * rank + 100 * d for d, n in enumerate(send)])
+    out = torch.full((sum(recv),), -1, dtype=torch.int64)
+    exchange_parts(dist, out, inp, world, rank, in_splits=send, out_splits=recv)
+    np.save(os.path.join(out_dir, f"out_{rank}.npy"), out.numpy())
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(180)
+def test_explicit_splits_without_a_route_agree_on_it_whatever_a_rank_sees(tmp_path):
+    """exchange_parts with explicit splits and in_pieces = None, world 2, part sizes 5 5 / 5 7: rank 0 sees equal rows and
+    columns, rank 1 does not.  Both must make the agreeing all_reduce(MAX) — a rank that skipped it on its own view sat in
+    all_to_all_single while its peer sat in the all_reduce (gloo: both until the group's 60-second timeout)."""
+    port = _free_port()
+    mp.spawn(_explicit_splits_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    a = [[5, 5], [5, 7]]
+    for rank in (0, 1):
+        want = np.concatenate([np.arange(a[s][rank], dtype=np.int64) + 1000 * s + 100 * rank for s in (0, 1)])
+        assert np.array_equal(np.load(tmp_path / f"out_{rank}.npy"), want), rank
