@@ -71,6 +71,13 @@ extern "C" {
                                    * the first device and a distinct other one is missing the context is still created
                                    * and the graph calls answer SHK_ERR_STATE naming the two devices.  On a one-device
                                    * context the flag does nothing; owner shares (n_owners > 1) keep refusing. */
+#define SHK_FLAG_GROUP_READS 64u   /* a multi-device context (n_devices > 1) retains reads and answers the retained calls —
+                                   * shk_retain_reads, shk_retained_info, shk_retained_export, shk_filter_reads_panel_retained,
+                                   * shk_thread_reads_panel_retained, and with SHK_FLAG_GROUP_GRAPH shk_pcr_run over
+                                   * SHK_PCR_READS_RETAINED — instead of refusing: every device keeps the runs of reads the
+                                   * exchange rounds deal it, walks its own store, and the host stitches the answers
+                                   * (DESIGN.md §22).  No kernel reads another device's memory.  Opt-in: without it every
+                                   * refusal stands.  On a one-device context and on owner shares the flag does nothing. */
 
 typedef struct shk_ctx shk_ctx;
 
@@ -527,7 +534,11 @@ int shk_gather_reads_device(shk_ctx *ctx, const void *d_bases, const void *d_off
  *   holds no reads — freshly created or after shk_reset — otherwise SHK_ERR_STATE.  A retained read's index is its
  *   ordinal among the reads handed to the context since then, whatever shk_set_read_index says.  on = 0 frees the
  *   store, at any time.  shk_reset empties the store, keeps its allocation and leaves retention on; shk_destroy frees
- *   it.  Off by default.  A multi-device context refuses the call (SHK_ERR_STATE).
+ *   it.  Off by default.  A multi-device context refuses the call (SHK_ERR_STATE) unless it was created with
+ *   SHK_FLAG_GROUP_READS: then on = 1 switches every device's store on (each with its share of the hint) under the same
+ *   condition taken over the whole context, and a read's index is again its ordinal among the reads handed to the
+ *   context, whichever device holds it.  What such a context retains: every batch of shk_ingest_reads / _batch, the
+ *   room on every device reserved before the call's first round (SHK_ERR_NOMEM leaves the call undone).
  * WHAT IS RETAINED: every batch of shk_ingest_reads / _batch / _packed / _reads_device / _packed_device, on owner
  *   shares too (whole reads, not the share's k-mers), appended on the context's stream.  The exchange rounds (the
  *   shk_xchg_ scatter calls) retain nothing; shk_insert_counts and shk_insert_device add no reads.  The store grows
@@ -535,18 +546,25 @@ int shk_gather_reads_device(shk_ctx *ctx, const void *d_bases, const void *d_off
  *   nothing retained from that call.  An invalid byte poisons the context as without retention, and every retained
  *   call on a poisoned context returns that error. */
 int shk_retain_reads(shk_ctx *ctx, int on, uint64_t capacity_bases_hint);
-/* Reads and bases retained so far, and the device memory the store holds (0, 0, 0 with retention off). */
+/* Reads and bases retained so far, and the device memory the store holds (0, 0, 0 with retention off); summed over the
+ * devices of a multi-device context with SHK_FLAG_GROUP_READS. */
 int shk_retained_info(shk_ctx *ctx, uint64_t *n_reads, uint64_t *n_bases, uint64_t *device_bytes);
 /* Retained reads first_read .. first_read + n_reads as ASCII on the host (N where the read had one): offsets gets
  * n_reads + 1 entries from 0, *n_bases the total.  bases_cap too small: SHK_ERR_BAD_ARG with *n_bases set to the need
- * and nothing written.  Also SHK_ERR_BAD_ARG: a range beyond the retained reads; SHK_ERR_STATE: retention is off. */
+ * and nothing written.  Also SHK_ERR_BAD_ARG: a range beyond the retained reads; SHK_ERR_STATE: retention is off.
+ * A multi-device context with SHK_FLAG_GROUP_READS: the same, the pieces of the range exported by the devices that hold
+ * them and put together in order. */
 int shk_retained_export(shk_ctx *ctx, uint64_t first_read, uint64_t n_reads, uint8_t *bases, uint64_t bases_cap,
                         uint64_t *offsets, uint64_t *n_bases);
 /* shk_filter_reads_panel_device and shk_thread_reads_panel_device with the batch being every read retained so far, in
  * retention order: the same outputs, match_cap / link_cap protocol, limits, tuning and errors; read_index and mate take
  * one entry per retained read.  The walks read the planes as they lie — no byte loads, no ballots.  SHK_ERR_STATE
  * with retention off; zero retained reads: all-zero outputs.  They wait for every queued append, may be called in the
- * middle of a job (later ingests go on appending) and neither read nor write the table. */
+ * middle of a job (later ingests go on appending) and neither read nor write the table.
+ * A multi-device context with SHK_FLAG_GROUP_READS answers with the same outputs, protocols and errors, indices being
+ * the context's: every device walks its own store at the same time; the filter's lists are merged per gene into
+ * ascending order; the threading's supports are added, its links summed by (in, out), read_edges written back to list
+ * positions and n_paired_links counted on the host over all of them, so mates held by two devices pair up. */
 int shk_filter_reads_panel_retained(shk_ctx *ctx, const uint64_t *primer_kmers, const uint64_t *gene_offsets, uint32_t n_genes,
                                     uint64_t *match_offsets, uint64_t *match_reads, uint64_t match_cap, uint64_t *n_matches);
 int shk_thread_reads_panel_retained(shk_ctx *ctx, const uint64_t *node_sub_kmers, const uint64_t *node_offsets,
@@ -927,8 +945,10 @@ typedef struct shk_pcr_run_out {   /* every pointer optional except records.reco
  *   that the conversion refuses).  Multi-device contexts and owner shares: SHK_ERR_STATE, as shk_pcr_extend_panel.
  *   A multi-device context with SHK_FLAG_GROUP_GRAPH answers for SHK_PCR_READS_NONE and SHK_PCR_READS_HOST: the primer
  *   scan over its shares, the extension as shk_pcr_extend_panel, the host batch staged once on its first device, where
- *   the filter, the threading, the prune and the products run; it retains no reads (SHK_PCR_READS_RETAINED: "reads are
- *   not retained").  The result is the one-device context's, array for array.
+ *   the filter, the threading, the prune and the products run.  Created with SHK_FLAG_GROUP_READS as well, and reads
+ *   retained, it answers for SHK_PCR_READS_RETAINED too: the filter and the threading run over every device's store as
+ *   shk_filter_reads_panel_retained / shk_thread_reads_panel_retained do there; without that flag it retains no reads
+ *   (SHK_PCR_READS_RETAINED: "reads are not retained").  The result is the one-device context's, array for array.
  *   records.record_cap / seq_cap too small: SHK_ERR_BAD_ARG with n_records / n_seq_bytes the need and every per-gene
  *   array complete.  n_genes == 0: SHK_OK, nothing launched.
  * With SHK_TRACE set: one line per gene on stderr after the run. */
@@ -1342,16 +1362,17 @@ typedef struct shk_pcr_file_config {
                                    (main.rs:136-139) */
   uint32_t dump;                /* reserved, 0 (--dump-graph is not built) */
   uint64_t node_budget_global;  /* 0 = shk_pcr_node_budget(n_bases_ingested) */
-  uint64_t context_flags;       /* SHK_FLAG_* for the run's context: SHK_FLAG_GROUP_GRAPH or 0, anything else is
-                                   SHK_ERR_BAD_ARG (the first of what were four reserved words: same size and offsets) */
+  uint64_t context_flags;       /* SHK_FLAG_* for the run's context: SHK_FLAG_GROUP_GRAPH, SHK_FLAG_GROUP_READS, both
+                                   or 0, anything else is SHK_ERR_BAD_ARG (the first of what were four reserved words: same size and offsets) */
   uint64_t reserved[3];
 } shk_pcr_file_config;
 /* shk_run_files with main.rs:133-199: after the histograms, shk_pcr_run over pcr->genes, {sample}_{gene}.fasta for every
  * gene with products in gene order (stats.rs:102-125), then the stats file with pcr_results.  A run that fails leaves no
  * stats file.  pcr NULL or without genes: shk_run_files.  out (optional) is handed to shk_pcr_run as it is: the caller's
  * arrays and capacities; NULL: the call keeps the products to itself.  n_devices > 1 with genes: SHK_ERR_STATE, unless
- * context_flags has SHK_FLAG_GROUP_GRAPH: then the run proceeds over the multi-device context — without read_threading,
- * which is SHK_ERR_STATE before a read is read (a multi-device context keeps no reads). */
+ * context_flags has SHK_FLAG_GROUP_GRAPH: then the run proceeds over the multi-device context; read_threading there
+ * needs SHK_FLAG_GROUP_READS as well, and without it is SHK_ERR_STATE before a read is read (a multi-device context
+ * keeps no reads). */
 int shk_run_files_pcr(const shk_run_config *cfg, const shk_pcr_file_config *pcr, shk_run_stats *out_stats,
                       shk_pcr_run_out *out);
 

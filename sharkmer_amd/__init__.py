@@ -8,7 +8,7 @@ fallback: importing works anywhere, creating an engine needs a gfx950 GPU.
 """
 from .engine import (  # noqa: F401
     KmerEngine, ShkError, N_READS_PER_BATCH, lib_path, load_library,
-    FLAG_TIMING, FLAG_FORCE_DIRECT, FLAG_FORCE_PAGED, FLAG_DEFER_ERRORS, FLAG_TIMING_SAMPLED, FLAG_GROUP_GRAPH, KERNEL_NAMES, RESERVE_NONE,
+    FLAG_TIMING, FLAG_FORCE_DIRECT, FLAG_FORCE_PAGED, FLAG_DEFER_ERRORS, FLAG_TIMING_SAMPLED, FLAG_GROUP_GRAPH, FLAG_GROUP_READS, KERNEL_NAMES, RESERVE_NONE,
     Primer, primer_compile, PRIMER_LEVELS, PcrGraph, PrunedGraph, pcr_node_budget,
     PcrProducts, DedupResult, pcr_paths_panel, edit_within, PCR_SCORE_FIELDS, PCR_MAX_AMPLICONS,
     PcrGene, PcrOutcome, parse_pcr_primers, validate_pcr_gene, pcr_validation_report, pcr_failure_reason, write_fasta,

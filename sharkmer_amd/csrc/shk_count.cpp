@@ -34,6 +34,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> specs;  // --pcr-primers, in order
   bool read_threading = false;
   bool group_graph = false;  // --group-graph: sPCR over --devices (SHK_FLAG_GROUP_GRAPH; not a reference flag)
+  bool group_reads = false;  // --group-reads: --read-threading over --devices (SHK_FLAG_GROUP_READS; not a reference flag)
   unsigned long long min_kmer_count = 2, node_budget = 0, max_dfs_states = 100000, max_paths_per_pair = 20, max_node_visits = 2,
                      max_primer_kmers = 40;
   double high_coverage_ratio = 10.0, tip_coverage_fraction = 0.1;
@@ -80,6 +81,7 @@ int main(int argc, char **argv) {
     else if (key == "--min-kmer-count") num(&min_kmer_count);
     else if (key == "--read-threading") read_threading = true;
     else if (key == "--group-graph") group_graph = true;
+    else if (key == "--group-reads") group_reads = true;
     else if (key == "--node-budget-global") num(&node_budget);
     else if (key == "--max-dfs-states") num(&max_dfs_states);
     else if (key == "--max-paths-per-pair") num(&max_paths_per_pair);
@@ -115,7 +117,7 @@ int main(int argc, char **argv) {
     else if (key == "-h" || key == "--help") {
       printf("Usage: shk_count [-k K] [--chunks N] [--histo-max M] [-m READS] -s SAMPLE [-o OUTDIR] "
              "[--validate-every N] [--gzip-all-members] [--bgzf-batch | --bgzf-device [--device-parse]] [--pcr-primers \"forward=...,reverse=...,name=...\"]... "
-             "[--min-kmer-count N] [--read-threading] [--node-budget-global N] [--devices 0,1,... [--group-graph]] [FASTQ[.gz] ...]\n");
+             "[--min-kmer-count N] [--read-threading] [--node-budget-global N] [--devices 0,1,... [--group-graph] [--group-reads]] [FASTQ[.gz] ...]\n");
       return 0;
     } else if (a.size() > 1 && a[0] == '-' && a != "-") {
       fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str());
@@ -147,7 +149,7 @@ int main(int argc, char **argv) {
   pcr.n_genes = (uint32_t)genes.size();
   pcr.min_kmer_count = (uint32_t)min_kmer_count;
   pcr.read_threading = read_threading;
-  pcr.context_flags = group_graph ? SHK_FLAG_GROUP_GRAPH : 0;
+  pcr.context_flags = (group_graph ? SHK_FLAG_GROUP_GRAPH : 0) | (group_reads ? SHK_FLAG_GROUP_READS : 0);
   pcr.node_budget_global = node_budget;
   shk_run_config rc{};
   rc.inputs = inputs.data();

@@ -2420,6 +2420,8 @@ int shk_reset(shk_ctx *c) {
     g->next_read = 0;
     g->n_inserted = 0;
     g->finalized = g->hist_ready = false;
+    g->reads_dir.clear();  // (every share's store is empty again; retention as it was)
+    g->retain_rc = SHK_OK;
     c->err.clear();
     return SHK_OK;
   }

@@ -25,6 +25,8 @@
 #include <mutex>
 #include <thread>
 
+#include "shk_group_reads_core.h"
+
 struct shk_group {
   uint32_t D = 0;
   shk_config cfg{};
@@ -70,6 +72,13 @@ struct shk_group {
   // table there.  graph_peer: a distinct device the lead cannot reach — no hipDeviceCanAccessPeer, or enabling it
   // failed — (−1: none; found at group_create, answered by the graph calls).
   int32_t graph_peer = -1;
+  // SHK_FLAG_GROUP_READS: retention is on in every share's RetainStore or in none; reads_dir says which
+  // run of which store a retained read's global index lies in.  retain_rc: a round failed with retention on — some shares
+  // hold its run and some may not, so the retained calls answer that failure until shk_reset or the switch.
+  bool retain_on = false;
+  shk::GroupReadsDir reads_dir;
+  int retain_rc = SHK_OK;
+  std::string retain_err;
 
   // Returns whether any worker had failed WHEN THE LAST ONE ARRIVED — one answer for all of them, taken inside the
   // barrier, so that either every worker leaves the round early or none does (a worker that looked at status[] on its
@@ -231,6 +240,7 @@ int group_create(const shk_config *cfg, shk_ctx **out) {
   g->sp_c.assign(D, nullptr);
   g->status.assign(D, SHK_OK);
   g->job_rc.assign(D, SHK_OK);
+  g->reads_dir.init(D);
   for (uint32_t d = 0; d < D; ++d) g->th.emplace_back([g, d] { g->worker(d); });
   *out = top;
   return SHK_OK;
@@ -286,6 +296,8 @@ int group_round(shk_ctx *top, const uint8_t *bases, const uint64_t *offsets, con
       for (uint64_t j = 0; j <= ns; ++j) reb[j] = offsets[r0 + j] - o0;
       hipc(hipMemcpyAsync(g->in_offsets[d].p, reb, (ns + 1) * 8, hipMemcpyHostToDevice, c->stream));
     }
+    // retention (room reserved by group_ingest): my run behind my store, on my stream, whichever round counts it
+    if (g->retain_on && g->status[d] == SHK_OK) retain_append(c, (const uint8_t *)g->in_bases[d].p, (const uint64_t *)g->in_offsets[d].p, ns, nb, 0);
     if (g->wide) {  // ---- the wide round: whole k-mers grouped by owner, pulled and inserted by their owners
       if (g->status[d] == SHK_OK) {
         if (lane_fixed >= 0) c->xchg_lane_fixed = lane_fixed;
@@ -377,8 +389,13 @@ int group_round(shk_ctx *top, const uint8_t *bases, const uint64_t *offsets, con
     return g->status[d];
   };
   uint32_t who = 0;
-  const int rc = g->run(job, &who);
-  return rc == SHK_OK ? SHK_OK : group_fail(top, g, rc, who);
+  int rc = g->run(job, &who);
+  if (rc != SHK_OK) rc = group_fail(top, g, rc, who);
+  if (g->retain_on) {
+    for (uint32_t d = 0; d < D; ++d) g->reads_dir.append(d, cut[d + 1] - cut[d]);
+    if (rc != SHK_OK && g->retain_rc == SHK_OK) g->retain_rc = rc, g->retain_err = top->err;
+  }
+  return rc;
 }
 
 // Host buffers → rounds.  Every round deals D contiguous runs of whole reads, each ≤ R bases.
@@ -393,8 +410,10 @@ int group_ingest(shk_ctx *top, const uint8_t *bases, const uint64_t *offsets, ui
   if (total && !bases) return fail(top, SHK_ERR_BAD_ARG, "null bases");
   const uint64_t target = std::max<uint64_t>(std::min<uint64_t>(R, (total + D - 1) / D), 1);
   const uint64_t call_first = g->next_read;  // global index of this call's first read
-  uint64_t r = 0;
-  while (r < n_seqs) {
+  // the cuts of every round of the call, before anything runs
+  std::vector<std::vector<uint64_t>> rounds;
+  std::vector<uint64_t> round_bases;
+  for (uint64_t r = 0; r < n_seqs;) {
     std::vector<uint64_t> cut(D + 1, r);
     uint64_t round_max = 0;
     for (uint32_t d = 0; d < D; ++d) {
@@ -407,11 +426,20 @@ int group_ingest(shk_ctx *top, const uint8_t *bases, const uint64_t *offsets, ui
       cut[d + 1] = b;
       round_max = std::max(round_max, offsets[b] - offsets[a]);
     }
-    // (cut[] counts from the start of this call: so does the global index handed on)
-    const int rc = group_round(top, bases, offsets, cut, call_first, std::max<uint64_t>(round_max, 1), lane_fixed);
-    if (rc != SHK_OK) return rc;
     r = cut[D];
+    rounds.push_back(std::move(cut));
+    round_bases.push_back(std::max<uint64_t>(round_max, 1));
   }
+  if (g->retain_on) {  // room on every share for all it will append in this call: out of memory leaves the call undone
+    std::vector<uint64_t> nr(D, 0), nb(D, 0);
+    for (const auto &cut : rounds)
+      for (uint32_t d = 0; d < D; ++d) nr[d] += cut[d + 1] - cut[d], nb[d] += offsets[cut[d + 1]] - offsets[cut[d]];
+    uint32_t who = 0;
+    const int rc = g->run([&](uint32_t d) { return retain_reserve(g->ctx[d], nr[d], nb[d]); }, &who);
+    if (rc != SHK_OK) return group_fail(top, g, rc, who);
+  }
+  for (size_t i = 0; i < rounds.size(); ++i)  // (cut[] counts from the start of this call: so does the global index handed on)
+    SHK_TRY(group_round(top, bases, offsets, rounds[i], call_first, round_bases[i], lane_fixed));
   if (lane_fixed < 0) g->next_read = call_first + n_seqs;
   return SHK_OK;
 }

@@ -53,15 +53,15 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
           g_run_error = fmt("Duplicate gene name '%s' (from --pcr-primers)", pcr->genes[g].gene_name);
           return SHK_ERR_BAD_ARG;
         }
-    if (pcr->context_flags & ~(uint64_t)SHK_FLAG_GROUP_GRAPH) {
-      g_run_error = fmt("shk_pcr_file_config.context_flags 0x%llx: only SHK_FLAG_GROUP_GRAPH is taken", (unsigned long long)pcr->context_flags);
+    if (pcr->context_flags & ~(uint64_t)(SHK_FLAG_GROUP_GRAPH | SHK_FLAG_GROUP_READS)) {
+      g_run_error = fmt("shk_pcr_file_config.context_flags 0x%llx: only SHK_FLAG_GROUP_GRAPH and SHK_FLAG_GROUP_READS are taken", (unsigned long long)pcr->context_flags);
       return SHK_ERR_BAD_ARG;
     }
     if (rc->n_devices > 1 && !(pcr->context_flags & SHK_FLAG_GROUP_GRAPH)) {
       g_run_error = "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)";
       return SHK_ERR_STATE;
     }
-    if (rc->n_devices > 1 && pcr->read_threading) {
+    if (rc->n_devices > 1 && pcr->read_threading && !(pcr->context_flags & SHK_FLAG_GROUP_READS)) {
       g_run_error = "a multi-device context keeps no reads: --read-threading needs one device";
       return SHK_ERR_STATE;
     }

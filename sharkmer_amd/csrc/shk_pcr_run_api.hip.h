@@ -91,7 +91,9 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   shk_ctx *rd = c->group ? c->group->ctx[0] : c;
   auto on0 = [&](int rc) { return rc == SHK_OK || !c->group ? rc : group_fail(c, c->group, rc, 0); };
   const bool host = p->reads == SHK_PCR_READS_HOST, retained = p->reads == SHK_PCR_READS_RETAINED;
-  if (retained && !c->retain.on) return fail(c, SHK_ERR_STATE, "shk_pcr_run: reads are not retained (shk_retain_reads)");
+  // … and with SHK_FLAG_GROUP_READS too, over retained reads, every share runs them over its own store
+  const bool shared_reads = retained && c->group;
+  if (retained && !retain_is_on(c)) return fail(c, SHK_ERR_STATE, "shk_pcr_run: reads are not retained (shk_retain_reads)");
   const uint64_t *read_index = host ? p->read_index : nullptr;
   const uint8_t *mate = host ? p->mate : nullptr;
   if ((read_index == nullptr) != (mate == nullptr))
@@ -148,8 +150,14 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       SHK_TRY(on0(batch_from_host(rd, p->bases, p->offsets, p->n_seqs, host_max_len, &batch)));  // the one upload of the batch
       have_batch = true;
     } else if (retained) {
-      SHK_TRY(retained_begin(c, "shk_pcr_run"));
-      if (c->retain.n_reads) {
+      if (shared_reads) {
+        SHK_TRY(group_retained_begin(c, "shk_pcr_run"));
+        batch.n_seqs = c->group->reads_dir.total();  // (no batch is opened here: the shares open theirs)
+        have_batch = batch.n_seqs > 0;
+      } else {
+        SHK_TRY(retained_begin(c, "shk_pcr_run"));
+      }
+      if (!shared_reads && c->retain.n_reads) {
         SHK_TRY(batch_from_retained(c, "shk_pcr_run", &batch));
         have_batch = true;
       }
@@ -168,7 +176,8 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
     for (int attempt = 0; attempt < 2 && !pl.items.empty(); ++attempt) {
       mreads.reset(new uint64_t[std::max<uint64_t>(cap, 1)]);
       std::fill(moff.begin(), moff.end(), 0ull);
-      const int rc = on0(panel_core(rd, pl, na, batch, moff.data(), mreads.get(), cap, &n_matches));
+      const int rc = shared_reads ? group_filter_retained(c, pl, na, moff.data(), mreads.get(), cap, &n_matches)
+                                  : on0(panel_core(rd, pl, na, batch, moff.data(), mreads.get(), cap, &n_matches));
       if (rc == SHK_ERR_BAD_ARG && attempt == 0 && n_matches > cap) {  // (a panel whose lists outgrow 2^22 entries: once more, with room)
         cap = n_matches;
         continue;
@@ -266,7 +275,10 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       SHK_TRY(on0(thread_panel_plan(rd, tsub.data(), tnoff.data(), tes.data(), tet.data(), teoff.data(), nt, batch.n_seqs, tloff.data(), tlist.data(),
                                 read_index, mate, &shape, &tp)));
       ThreadPanelResult res{ttot.data(), tuna.data(), nullptr, {}, {}, {}, {}, {}};
-      SHK_TRY(on0(thread_panel_core(rd, tp, nt, batch, tloff.data(), tlist.data(), read_index, mate, &res, mate_rule)));
+      if (shared_reads)
+        SHK_TRY(group_thread_retained(c, tp, nt, tloff.data(), tlist.data(), read_index, mate, mate_rule, &res));
+      else
+        SHK_TRY(on0(thread_panel_core(rd, tp, nt, batch, tloff.data(), tlist.data(), read_index, mate, &res, mate_rule)));
       for (uint32_t t = 0, f = 0; f < nf; ++f) {  // into the layout of the pruned panel
         loff[f + 1] = loff[f];
         if (t == nt || thr[t] != f) continue;

@@ -410,12 +410,16 @@ int thread_links_out(shk_ctx *c, const ThreadPanelResult &res, uint64_t link_cap
   return SHK_OK;
 }
 
+struct ThreadListSpan { uint64_t l0, n_listed; };  // list_reads[l0 … l0 + n_listed) are the panel's lists
+
 // The launch over an opened batch (its offsets checked) and what follows it.  list_reads == nullptr: list position i (from
 // pp.l0) is read i — the one gene of shk_thread_reads, which lists every read.
 int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
                       const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, ThreadPanelResult *res,
-                      bool mate_rule = false /* no arrays: pairs by thread_paired_links' rule (needs list_reads) */) {
+                      bool mate_rule = false /* no arrays: pairs by thread_paired_links' rule (needs list_reads) */,
+                      const ThreadListSpan *span = nullptr /* the lists' extent where it is not the plan's (a share's lists) */) {
   const uint32_t k = c->cfg.k;
+  const uint64_t l0 = span ? span->l0 : pp.l0, n_listed = span ? span->n_listed : pp.n_listed;
   res->link_off.assign(n_genes + 1, 0);
   res->n_paired.assign(n_genes, 0);
   const int lds_edges = env_int("SHK_THREAD_LDS_EDGES", THREAD_LDS_EDGES);
@@ -453,7 +457,7 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
     d.items = put(pl.runs.items.data(), (size_t)E * 4), d.last = put(pl.runs.last.data(), pl.runs.last.size() * 4);
     d.mask = cap - 1, d.n_edges = E;
     for (uint64_t at = 0; at < n_list; at += job_reads)  // (gene, slice) order
-      jobs.push_back(ThreadJob{list_offsets[g] - pp.l0 + at, g, (uint32_t)std::min(job_reads, n_list - at)});
+      jobs.push_back(ThreadJob{list_offsets[g] - l0 + at, g, (uint32_t)std::min(job_reads, n_list - at)});
     n_walked += n_list;
   }
   if (jobs.empty()) return SHK_OK;  // (the outputs are zero already)
@@ -469,15 +473,15 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   if (block_cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)block_cap);
   blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, jobs.size()));
   Scratch m{c->misc};
-  const size_t o_up = m.take<uint8_t>(up.size()), o_jobs = m.take<ThreadJob>(jobs.size()), o_list = m.take<uint64_t>(list_reads ? pp.n_listed : 0);
-  const size_t n_cnt = 2 * (size_t)pp.n_edges + pp.n_slots + pp.n_listed;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
+  const size_t o_up = m.take<uint8_t>(up.size()), o_jobs = m.take<ThreadJob>(jobs.size()), o_list = m.take<uint64_t>(list_reads ? n_listed : 0);
+  const size_t n_cnt = 2 * (size_t)pp.n_edges + pp.n_slots + n_listed;  // ONE block, cleared as one: [total][unambiguous][link slots][read_edges]
   const size_t o_cnt = m.take<uint32_t>(n_cnt), o_scr = m.take<uint2>(blocks * wpb * stride);
   HIPC(c, m.ensure());
   uint32_t *dtot = m.at<uint32_t>(o_cnt), *dun = dtot + pp.n_edges, *dlinks = dun + pp.n_edges, *dre = dlinks + pp.n_slots;
   HIPC(c, hipMemcpyAsync(m.at<uint8_t>(o_up), up.data(), up.size(), hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemcpyAsync(m.at<ThreadJob>(o_jobs), jobs.data(), jobs.size() * sizeof(ThreadJob), hipMemcpyHostToDevice, c->stream));
   const uint64_t *dlist = list_reads ? m.at<uint64_t>(o_list) : nullptr;
-  if (list_reads) HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + pp.l0, pp.n_listed * 8, hipMemcpyHostToDevice, c->stream));
+  if (list_reads) HIPC(c, hipMemcpyAsync(m.at<uint64_t>(o_list), list_reads + l0, n_listed * 8, hipMemcpyHostToDevice, c->stream));
   HIPC(c, hipMemsetAsync(dtot, 0, n_cnt * 4, c->stream));
   if (getenv("SHK_TRACE"))  // (read at each call, like the knobs: the tests look for this line)
     fprintf(stderr, "[shk] thread_reads_panel: %u genes, %zu jobs, %llu blocks, %u genes in LDS, %u genes in global memory%s\n", n_genes, jobs.size(),
@@ -507,16 +511,16 @@ int thread_panel_core(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, c
   std::vector<uint32_t> slots(pp.n_slots), re_own;
   uint32_t *re = res->read_edges;
   if (!re && (mate || mate_rule)) {
-    re_own.resize(pp.n_listed);
+    re_own.resize(n_listed);
     re = re_own.data();
   }
   HIPC(c, hipMemcpyAsync(res->support_total, dtot, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipMemcpyAsync(res->support_unambiguous, dun, (size_t)pp.n_edges * 4, hipMemcpyDeviceToHost, c->stream));
   if (pp.n_slots) HIPC(c, hipMemcpyAsync(slots.data(), dlinks, pp.n_slots * 4, hipMemcpyDeviceToHost, c->stream));
-  if (re) HIPC(c, hipMemcpyAsync(re, dre, pp.n_listed * 4, hipMemcpyDeviceToHost, c->stream));
+  if (re) HIPC(c, hipMemcpyAsync(re, dre, n_listed * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps the upload and the jobs alive until their copies ran)
   for (uint32_t g = 0; g < n_genes; ++g) {
-    const uint64_t l_at = list_offsets[g] - pp.l0, n_list = list_offsets[g + 1] - list_offsets[g];
+    const uint64_t l_at = list_offsets[g] - l0, n_list = list_offsets[g + 1] - list_offsets[g];
     if (mate_rule && !mate)
       res->n_paired[g] = thread_paired_links(list_reads + list_offsets[g], n_list, nullptr, nullptr, re + l_at);
     else if (mate)
@@ -547,16 +551,21 @@ int thread_one_gene(shk_ctx *c, ThreadPlan &&pl, uint64_t n_edges, const ReadBat
   return thread_links_out(c, res, out->link_cap, out->link_in, out->link_out, out->link_counts);
 }
 
+// A result into shk_thread_reads_panel's out (the large arrays are where the result put them).
+int thread_panel_finish(shk_ctx *c, const ThreadPanelResult &res, uint32_t n_genes, shk_thread_panel_out *out) {
+  if (out->n_paired_links) std::copy(res.n_paired.begin(), res.n_paired.end(), out->n_paired_links);
+  if (out->link_offsets) std::copy(res.link_off.begin(), res.link_off.end(), out->link_offsets);
+  out->n_links = res.link_off[n_genes];
+  return thread_links_out(c, res, out->link_cap, out->link_in, out->link_out, out->link_counts);
+}
+
 // shk_thread_reads_panel[_device] after theirs.
 int thread_panel_run(shk_ctx *c, const ThreadPanelPlan &pp, uint32_t n_genes, const ReadBatch &b, const uint64_t *list_offsets,
                      const uint64_t *list_reads, const uint64_t *read_index, const uint8_t *mate, shk_thread_panel_out *out) {
   ThreadPanelResult res{out->support_total + pp.e0, out->support_unambiguous + pp.e0, out->read_edges ? out->read_edges + pp.l0 : nullptr,
                         {}, {}, {}, {}, {}};
   SHK_TRY(thread_panel_core(c, pp, n_genes, b, list_offsets, list_reads, read_index, mate, &res));
-  if (out->n_paired_links) std::copy(res.n_paired.begin(), res.n_paired.end(), out->n_paired_links);
-  if (out->link_offsets) std::copy(res.link_off.begin(), res.link_off.end(), out->link_offsets);
-  out->n_links = res.link_off[n_genes];
-  return thread_links_out(c, res, out->link_cap, out->link_in, out->link_out, out->link_counts);
+  return thread_panel_finish(c, res, n_genes, out);
 }
 
 }  // namespace
@@ -721,21 +730,28 @@ int panel_pass(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBa
   return SHK_OK;
 }
 
-// The passes and what follows them: the records sorted by (gene, read) are the answer.  Same preconditions as panel_pass.
-int panel_core(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBatch &b, uint64_t *match_offsets, uint64_t *match_reads,
-               uint64_t match_cap, uint64_t *n_matches) {
+// The passes: every record of the batch, (gene << FILTER_READ_BITS | read), sorted.  Same preconditions as panel_pass.
+int panel_records(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBatch &b, std::vector<uint64_t> *recs) {
   if (b.n_seqs >> FILTER_READ_BITS) return fail(c, SHK_ERR_BAD_ARG, "a batch of %llu reads", (unsigned long long)b.n_seqs);
   const uint64_t room = (uint64_t)std::max(env_int("SHK_FILTER_CANDIDATES", 1 << 20), 1);
-  std::vector<uint64_t> recs;
   uint64_t nt = 0;
-  SHK_TRY(panel_pass(c, pl, n_genes, b, room, &recs, &nt));
+  SHK_TRY(panel_pass(c, pl, n_genes, b, room, recs, &nt));
   if (nt > room) {  // the list overflowed: the pass counted what there is, so the second one has room for exactly that
     uint64_t n2 = 0;
-    SHK_TRY(panel_pass(c, pl, n_genes, b, nt, &recs, &n2));
+    SHK_TRY(panel_pass(c, pl, n_genes, b, nt, recs, &n2));
     if (n2 != nt)
       return fail(c, SHK_ERR_INVARIANT, "panel filter rerun produced %llu records, expected %llu", (unsigned long long)n2, (unsigned long long)nt);
   }
-  std::sort(recs.begin(), recs.end());  // arrival order is not part of the result
+  std::sort(recs->begin(), recs->end());  // arrival order is not part of the result
+  return SHK_OK;
+}
+
+// The passes and what follows them: the records sorted by (gene, read) are the answer.
+int panel_core(shk_ctx *c, const HostKeyRuns &pl, uint32_t n_genes, const ReadBatch &b, uint64_t *match_offsets, uint64_t *match_reads,
+               uint64_t match_cap, uint64_t *n_matches) {
+  std::vector<uint64_t> recs;
+  SHK_TRY(panel_records(c, pl, n_genes, b, &recs));
+  const uint64_t nt = recs.size();
   for (const uint64_t r : recs) ++match_offsets[(r >> FILTER_READ_BITS) + 1];
   for (uint32_t g = 0; g < n_genes; ++g) match_offsets[g + 1] += match_offsets[g];
   *n_matches = nt;

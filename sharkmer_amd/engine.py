@@ -40,6 +40,7 @@ def _bgzf_flags(bgzf) -> int:
     return FASTQ_BGZF_BATCH if bgzf == "host" else FASTQ_BGZF_DEVICE
 FLAG_DEFER_ERRORS = 8  # host-buffer ingests return once queued; errors surface at the next call (include/shk.h)
 FLAG_GROUP_GRAPH = 32  # a multi-device context answers the graph extension calls and pcr_run (opt-in; include/shk.h)
+FLAG_GROUP_READS = 64  # a multi-device context retains reads and answers the retained calls (opt-in; include/shk.h)
 
 KERNEL_NAMES = ["mark", "scan", "direct", "scatter", "pages", "histo", "grow", "insert",
                 "lookup", "export", "synth", "merge", "pcount", "pscan", "histo_rows", "extend"]
@@ -2214,13 +2215,13 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
               command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
               bgzf=None, parse=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0,
-              group_graph: bool = False, **tuning) -> dict:
+              group_graph: bool = False, group_reads: bool = False, **tuning) -> dict:
     """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
     strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
     tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
     max_primer_kmers, high_coverage_ratio, tip_coverage_fraction), which overwrite every gene's values.
     device_ids: run on one multi-device context (shk_run_config.n_devices); with pcr_primers that needs group_graph=True
-    (SHK_FLAG_GROUP_GRAPH) and no read_threading.  gzip_all_members, bgzf: see FastqReader
+    (SHK_FLAG_GROUP_GRAPH), and read_threading there needs group_reads=True (SHK_FLAG_GROUP_READS).  gzip_all_members, bgzf: see FastqReader
     (bgzf="device" decodes on the context's first device).  parse="device" (with bgzf="device" only): the decoded text
     stays on the device and is framed there (SHK_FASTQ_DEVICE_PARSE); a file the route gives up on is read the
     bgzf="device" way from its start."""
@@ -2255,7 +2256,7 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
             raise ShkError(-2, "min-kmer-count must be at least 1")
         arr = _pcr_genes(genes)
         pcfg = _PcrFileConfig(arr, len(genes), min_kmer_count, 1 if read_threading else 0, 0, node_budget_global,
-                              FLAG_GROUP_GRAPH if group_graph else 0)
+                              (FLAG_GROUP_GRAPH if group_graph else 0) | (FLAG_GROUP_READS if group_reads else 0))
         rc = L.shk_run_files_pcr(C.byref(cfg), C.byref(pcfg), C.byref(st), None)
     else:
         rc = L.shk_run_files(C.byref(cfg), C.byref(st))
