@@ -955,6 +955,57 @@ typedef struct shk_pcr_run_out {   /* every pointer optional except records.reco
 int shk_pcr_run(shk_ctx *ctx, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params,
                 shk_pcr_run_out *out);
 
+/* ---- sPCR depth sweep -------------------------------------------------------------------------------
+ * The table keeps one count lane per chunk, so the cumulative table at every chunk boundary is still there after
+ * shk_finalize.  On a context with n_chunks lanes (shk_counters.n_chunks), DEPTH d, 1 ≤ d ≤ n_chunks, is the table of
+ * chunks 0..d−1 merged: a key's count is the saturating sum of lanes 0..d−1 in lane order, and a key whose sum is 0 is
+ * not in that table.  Depth n_chunks is the merged table.  Every call below returns, for a depth d, what its plain form
+ * returns on a context that was handed only the reads of chunks < d — array for array, orders, level_hits, error texts
+ * and the capacity protocols included; hence wherever the plain form accepts count ≥ min_count, the depth form accepts
+ * the depth's count ≥ max(min_count, 1).
+ * ERRORS common to all of them, before the device is touched: SHK_ERR_BAD_ARG for a depth 0 or above n_chunks (a list:
+ * also n_depths 0 or above SHK_PCR_MAX_DEPTHS, or not strictly ascending); SHK_ERR_STATE on a multi-device context
+ * (SHK_FLAG_GROUP_GRAPH or not), on an owner share, and between shk_xchg_scatter_begin and _end.  Valid whenever the
+ * plain form is; the table is not written. */
+#define SHK_PCR_MAX_DEPTHS 16
+/* Chunk::n_bases of every chunk (n_chunks entries): shk_counters.n_bases_ingested is their sum.  After shk_finalize. */
+int shk_chunk_bases(shk_ctx *ctx, uint64_t *n_bases_ingested);
+/* shk_lookup at a depth. */
+int shk_lookup_depth(shk_ctx *ctx, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical, uint32_t depth);
+/* shk_primer_kmers at n_depths depths in ONE pass over the table: the mismatch levels of a (k-mer, primer) pair are
+ * computed once, whatever the number of depths.  Result slot j · n_primers + i is primer i at depths[j]: offsets has
+ * n_depths · n_primers + 1 entries, level_hits (optional) n_depths · n_primers × SHK_PRIMER_LEVELS, and depth j's block
+ * (slots j · n_primers .., offsets rebased) is exactly a shk_primer_kmers result.  cap ≥ n_depths · Σ max_kmers; also
+ * n_depths · n_primers < 2^24.  SHK_PRIMER_CANDIDATES: on an overflow the cut level is per (primer, depth). */
+int shk_primer_kmers_depths(shk_ctx *ctx, const shk_primer *primers, uint32_t n_primers, const uint32_t *depths,
+                            uint32_t n_depths, uint64_t *kmers, uint32_t *counts, uint8_t *levels, uint64_t cap,
+                            uint64_t *offsets, uint64_t *level_hits);
+/* shk_neighborhood_panel with one depth per job (jobs of different depths share the launches); all else identical. */
+int shk_neighborhood_panel_depths(shk_ctx *ctx, const uint64_t *nodes, const uint8_t *dirs,
+                                  const uint64_t *seed_offsets, uint32_t n_jobs, const uint32_t *min_counts,
+                                  const uint32_t *job_depths, uint32_t max_levels, const uint64_t *caps,
+                                  const uint64_t *fringe_caps, uint64_t *kmers, uint32_t *counts, uint64_t *n_out,
+                                  uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
+                                  uint32_t *levels_done);
+/* shk_pcr_extend_panel with one depth per gene; all else identical (tuning variables, round cutting, outputs). */
+int shk_pcr_extend_panel_depths(shk_ctx *ctx, const uint64_t *primer_kmers, const uint32_t *primer_counts,
+                                const uint64_t *primer_offsets, uint32_t n_genes, const shk_pcr_extend_params *params,
+                                const uint32_t *gene_depths, uint64_t *node_sub_kmers, uint8_t *node_flags,
+                                uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt,
+                                uint32_t *edge_counts, uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path,
+                                uint32_t *threshold_used, uint32_t *steps_run);
+/* shk_pcr_run (reads = SHK_PCR_READS_NONE) of the panel at every listed depth, as ONE pipeline over the
+ * n_genes · n_depths (gene, depth) pairs — pair j · n_genes + g is gene g at depths[j]: one fused primer scan, one
+ * shk_pcr_extend_panel_depths over the pairs with both primer sets, one prune, one products call; a stage with no pair
+ * left is not called.  outs[j] (n_depths of them, each with its own arrays and record capacities) is shk_pcr_run's
+ * result at depths[j].  max_num_nodes 0: shk_pcr_node_budget(Σ chunk bases below the depth), per depth.  The host
+ * checks run once per gene, in shk_pcr_run's order.  Record capacities: per outs[j]; on a short return
+ * (SHK_ERR_BAD_ARG) every outs[j] has its need and its per-gene arrays complete.
+ * ERRORS beyond the common ones: n_genes · n_depths > SHK_PCR_MAX_GENES; params->reads != SHK_PCR_READS_NONE
+ * ("a depth sweep takes no reads": the store does not keep a read's chunk) — SHK_ERR_BAD_ARG. */
+int shk_pcr_run_depths(shk_ctx *ctx, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params,
+                       const uint32_t *depths, uint32_t n_depths, shk_pcr_run_out *outs);
+
 /* The owner of a canonical k-mer among n_owners shares, as the engine assigns it (shk_config.n_owners, the shares of a
  * multi-device context): the top log2(n_owners) bits of the key mix of the 2k-bit value.  Host only, no context: what a
  * multi-process job routes a query by.  n_owners: a power of two ≤ 64 (1: always 0).  ~0u for k = 0, k ≥ 32 or an
@@ -1364,7 +1415,11 @@ typedef struct shk_pcr_file_config {
   uint64_t node_budget_global;  /* 0 = shk_pcr_node_budget(n_bases_ingested) */
   uint64_t context_flags;       /* SHK_FLAG_* for the run's context: SHK_FLAG_GROUP_GRAPH, SHK_FLAG_GROUP_READS, both
                                    or 0, anything else is SHK_ERR_BAD_ARG (the first of what were four reserved words: same size and offsets) */
-  uint64_t reserved[3];
+  const uint32_t *depths;       /* --pcr-depths: after the normal run, shk_pcr_run_depths at these depths (shk_pcr_check_depths
+                                   holds) with {sample}_{gene}.depth{d}.fasta and {sample}.pcr_depths.tsv; NULL: no sweep */
+  uint64_t n_depths;            /* (these two were reserved words: same size and offsets; more than SHK_PCR_MAX_DEPTHS go in
+                                   several calls) */
+  uint64_t reserved[1];
 } shk_pcr_file_config;
 /* shk_run_files with main.rs:133-199: after the histograms, shk_pcr_run over pcr->genes, {sample}_{gene}.fasta for every
  * gene with products in gene order (stats.rs:102-125), then the stats file with pcr_results.  A run that fails leaves no
@@ -1375,6 +1430,29 @@ typedef struct shk_pcr_file_config {
  * keeps no reads). */
 int shk_run_files_pcr(const shk_run_config *cfg, const shk_pcr_file_config *pcr, shk_run_stats *out_stats,
                       shk_pcr_run_out *out);
+
+/* ---- the depth sweep of a file run (shk_count --pcr-depths) ----
+ * With pcr->depths, shk_run_files_pcr runs shk_pcr_run_depths after the panel and writes, before the stats file,
+ * {sample}_{gene}.depth{d}.fasta (shk_write_fasta) for every (gene, depth) with products and {sample}.pcr_depths.tsv.
+ * Refused before a read is read (SHK_ERR_BAD_ARG, the text in shk_run_error()): no genes, read_threading, n_devices > 1,
+ * chunks == 0, and what shk_pcr_check_depths refuses.  Every file of a run without depths is what it was. */
+/* A depth list for a run of `chunks` chunks: n >= 1, every depth in 1..chunks, strictly ascending; else SHK_ERR_BAD_ARG
+ * with the reason in err (at most err_cap bytes with the NUL). */
+int shk_pcr_check_depths(const uint32_t *depths, uint64_t n, uint32_t chunks, char *err, size_t err_cap);
+/* --pcr-depths' value: "all" (1..chunks) or "d1,d2,…" → depths[0 .. *n_depths), checked as above.  *n_depths is the
+ * count also when it exceeds cap (SHK_ERR_BAD_ARG then, nothing beyond cap written). */
+int shk_pcr_parse_depths(const char *spec, uint32_t chunks, uint32_t *depths, uint64_t cap, uint64_t *n_depths, char *err,
+                         size_t err_cap);
+typedef struct shk_pcr_depth_row {
+  uint32_t depth;
+  uint32_t reserved;
+  uint64_t n_bases_ingested;       /* of the chunks below the depth */
+  shk_pcr_gene_stat gene;
+} shk_pcr_depth_row;
+/* {sample}.pcr_depths.tsv: the header "depth n_bases_ingested gene status failure_reason n_products product_lengths"
+ * (tab-separated), then one row per entry in the order given (the run: depth-major, then gene order); status "success"
+ * or "fail", failure_reason empty on success, the lengths comma-separated (empty without products). */
+int shk_write_pcr_depths_tsv(const char *path, const shk_pcr_depth_row *rows, uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ from .engine import (  # noqa: F401
     KmerEngine, ShkError, N_READS_PER_BATCH, lib_path, load_library,
     FLAG_TIMING, FLAG_FORCE_DIRECT, FLAG_FORCE_PAGED, FLAG_DEFER_ERRORS, FLAG_TIMING_SAMPLED, FLAG_GROUP_GRAPH, FLAG_GROUP_READS, KERNEL_NAMES, RESERVE_NONE,
     Primer, primer_compile, PRIMER_LEVELS, PcrGraph, PrunedGraph, pcr_node_budget,
-    PcrProducts, DedupResult, pcr_paths_panel, edit_within, PCR_SCORE_FIELDS, PCR_MAX_AMPLICONS,
+    PcrProducts, DedupResult, pcr_paths_panel, edit_within, PCR_SCORE_FIELDS, PCR_MAX_AMPLICONS, PCR_MAX_DEPTHS,
     PcrGene, PcrOutcome, parse_pcr_primers, validate_pcr_gene, pcr_validation_report, pcr_failure_reason, write_fasta,
     PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET,
     PackedReads, pack_reads, release_cached_memory, FastqReader, write_histo, write_final_histo, write_stats_yaml, validate_args, run_files,

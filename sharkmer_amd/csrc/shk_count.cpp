@@ -6,12 +6,15 @@
 // --validate-every (0).  sPCR (cli.rs:12-140, 234-330; main.rs:33-56, 133-199): --pcr-primers SPEC (repeatable),
 // --min-kmer-count (2), --read-threading, --node-budget-global, and the six global tuning flags that overwrite every
 // gene's values as the reference does: --max-dfs-states, --max-paths-per-pair, --max-node-visits, --max-primer-kmers,
-// --high-coverage-ratio, --tip-coverage-fraction.  With a gene, {sample}_{gene}.fasta is written for every gene with
+// --high-coverage-ratio, --tip-coverage-fraction; --pcr-depths all|d1,d2,… (not a reference flag: with --pcr-primers and
+// --chunks >= 1, the panel at every listed cumulative chunk from the one count — {sample}_{gene}.depth{d}.fasta and
+// {sample}.pcr_depths.tsv; refused with --read-threading and with more than one device).  With a gene, {sample}_{gene}.fasta is written for every gene with
 // products and the stats file carries pcr_results.  Exit status and "Error: …" on stderr follow anyhow's main().
 #include "../../include/shk.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -33,6 +36,7 @@ int main(int argc, char **argv) {
   std::vector<const char *> inputs;
   std::vector<const char *> specs;  // --pcr-primers, in order
   bool read_threading = false;
+  const char *pcr_depths = nullptr;  // --pcr-depths
   bool group_graph = false;  // --group-graph: sPCR over --devices (SHK_FLAG_GROUP_GRAPH; not a reference flag)
   bool group_reads = false;  // --group-reads: --read-threading over --devices (SHK_FLAG_GROUP_READS; not a reference flag)
   unsigned long long min_kmer_count = 2, node_budget = 0, max_dfs_states = 100000, max_paths_per_pair = 20, max_node_visits = 2,
@@ -80,6 +84,7 @@ int main(int argc, char **argv) {
     else if (key == "--pcr-primers") specs.push_back(val ? argv[i] + eq + 1 : need(i, key.c_str()));
     else if (key == "--min-kmer-count") num(&min_kmer_count);
     else if (key == "--read-threading") read_threading = true;
+    else if (key == "--pcr-depths") pcr_depths = val ? argv[i] + eq + 1 : need(i, key.c_str());
     else if (key == "--group-graph") group_graph = true;
     else if (key == "--group-reads") group_reads = true;
     else if (key == "--node-budget-global") num(&node_budget);
@@ -117,7 +122,7 @@ int main(int argc, char **argv) {
     else if (key == "-h" || key == "--help") {
       printf("Usage: shk_count [-k K] [--chunks N] [--histo-max M] [-m READS] -s SAMPLE [-o OUTDIR] "
              "[--validate-every N] [--gzip-all-members] [--bgzf-batch | --bgzf-device [--device-parse]] [--pcr-primers \"forward=...,reverse=...,name=...\"]... "
-             "[--min-kmer-count N] [--read-threading] [--node-budget-global N] [--devices 0,1,... [--group-graph] [--group-reads]] [FASTQ[.gz] ...]\n");
+             "[--min-kmer-count N] [--read-threading] [--pcr-depths all|D1,D2,...] [--node-budget-global N] [--devices 0,1,... [--group-graph] [--group-reads]] [FASTQ[.gz] ...]\n");
       return 0;
     } else if (a.size() > 1 && a[0] == '-' && a != "-") {
       fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str());
@@ -144,7 +149,33 @@ int main(int argc, char **argv) {
     fprintf(stderr, "Error: min-kmer-count must be at least 1\n");
     return 1;
   }
+  std::vector<uint32_t> depths;
+  if (pcr_depths) {  // refused before a read is read
+    if (genes.empty()) {
+      fprintf(stderr, "Error: --pcr-depths needs --pcr-primers\n");
+      return 1;
+    }
+    if (read_threading) {
+      fprintf(stderr, "Error: --pcr-depths takes no --read-threading: a depth sweep takes no reads\n");
+      return 1;
+    }
+    if (devices.size() > 1) {
+      fprintf(stderr, "Error: --pcr-depths needs one device: no depths on a multi-device context\n");
+      return 1;
+    }
+    char err[256];
+    uint64_t n = 0;
+    depths.resize(std::max<size_t>(chunks < (1ull << 32) ? (size_t)chunks : 0, strlen(pcr_depths)) + 1);
+    if (shk_pcr_parse_depths(pcr_depths, (uint32_t)std::min<unsigned long long>(chunks, 0xFFFFFFFFull), depths.data(), depths.size(), &n, err,
+                             sizeof err) != SHK_OK) {
+      fprintf(stderr, "Error: %s\n", err);
+      return 1;
+    }
+    depths.resize(n);
+  }
   shk_pcr_file_config pcr{};
+  pcr.depths = depths.empty() ? nullptr : depths.data();
+  pcr.n_depths = depths.size();
   pcr.genes = genes.data();
   pcr.n_genes = (uint32_t)genes.size();
   pcr.min_kmer_count = (uint32_t)min_kmer_count;

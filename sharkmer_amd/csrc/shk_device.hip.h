@@ -1248,14 +1248,22 @@ __device__ __forceinline__ uint64_t revcomp(uint64_t kmer, int k) {
   return x >> (64 - 2 * k);
 }
 
-__device__ __forceinline__ uint32_t merged_count(const TableRef &tb, uint64_t key) {
+// BOUNDED: the count at a depth — the saturating sum of lanes 0..lanes−1 only (1 ≤ lanes ≤ tb.n_lanes:
+// the host's check), 0 for a key that only later chunks hold.  A template parameter, so the merged probe is the code it was.
+template <bool BOUNDED>
+__device__ __forceinline__ uint32_t merged_count_upto(const TableRef &tb, uint64_t key, uint32_t lanes) {
   const Home hm = home_of(tb, key);
   if (!hm.owned) return 0u;
   int64_t s = find_slot(tb.keys, hm.base, hm.slot, key);
   if (s < 0) return 0;
   uint32_t cum = 0;
-  for (uint32_t l = 0; l < tb.n_lanes; ++l) cum = sat_add_u32(cum, tb.vals[(uint64_t)l * tb.cap + s]);
+  const uint32_t n = BOUNDED ? lanes : tb.n_lanes;
+  for (uint32_t l = 0; l < n; ++l) cum = sat_add_u32(cum, tb.vals[(uint64_t)l * tb.cap + s]);
   return cum;
+}
+__device__ __forceinline__ uint32_t merged_count(const TableRef &tb, uint64_t key) { return merged_count_upto<false>(tb, key, 0u); }
+__device__ __forceinline__ uint32_t merged_count(const TableRef &tb, uint64_t key, uint32_t lanes) {
+  return merged_count_upto<true>(tb, key, lanes);
 }
 
 // merged_count over the shares of a multi-device context (SHK_FLAG_GROUP_GRAPH): dir[d] is share d's table, 2^owner_bits
@@ -1265,6 +1273,12 @@ __device__ __forceinline__ uint32_t merged_count_sharded(const TableRef *dir, ui
   const uint32_t owner = hash64(key, dir[0].key_bits) >> (32 - owner_bits);
   const TableRef tb = dir[owner];  // (the descriptor once: 48 bytes)
   return merged_count(tb, key);    // (.owned holds by construction)
+}
+// (its depth form, for the day a multi-device context takes a depth: every share has the context's lanes)
+__device__ __forceinline__ uint32_t merged_count_sharded(const TableRef *dir, uint32_t owner_bits, uint64_t key, uint32_t lanes) {
+  const uint32_t owner = hash64(key, dir[0].key_bits) >> (32 - owner_bits);
+  const TableRef tb = dir[owner];
+  return merged_count(tb, key, lanes);
 }
 
 __global__ void __launch_bounds__(WG) k_lookup(TableRef tb, const uint64_t *__restrict__ kmers,
@@ -1278,6 +1292,19 @@ __global__ void __launch_bounds__(WG) k_lookup(TableRef tb, const uint64_t *__re
     key = key < rc ? key : rc;
   }
   out[i] = merged_count(tb, key);
+}
+// k_lookup at a depth: the counts of chunks 0..lanes−1.
+__global__ void __launch_bounds__(WG) k_lookup_depth(TableRef tb, const uint64_t *__restrict__ kmers,
+                                                     uint32_t *__restrict__ out, uint64_t n, int canonical,
+                                                     int k, uint32_t lanes) {
+  uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  uint64_t key = kmers[i];
+  if (canonical) {
+    uint64_t rc = revcomp(key, k);
+    key = key < rc ? key : rc;
+  }
+  out[i] = merged_count(tb, key, lanes);
 }
 
 __global__ void __launch_bounds__(WG) k_export(TableRef tb, uint64_t slot0, uint64_t slot1,
@@ -1334,7 +1361,9 @@ struct NbRef {
   uint64_t cap, fringe_cap;
   uint32_t min_count, max_levels;
   int k;
+  uint32_t lanes;              // the job's depth (the *_depths kernels read it; 0 otherwise): in what was tail padding
 };
+static_assert(sizeof(NbRef) == 96, "NbRef is a kernel argument and an uploaded array: lanes must not grow it");
 
 // 1: inserted, 0: was there, −1: no free slot
 __device__ __forceinline__ int nb_set_insert(uint64_t *set, uint64_t mask, uint64_t key) {
@@ -1359,10 +1388,13 @@ template <bool SHARDED>
 using NbTable = std::conditional_t<SHARDED, NbShards, TableRef>;
 __device__ __forceinline__ uint32_t nb_count(const TableRef &tb, uint64_t key) { return merged_count(tb, key); }
 __device__ __forceinline__ uint32_t nb_count(const NbShards &sh, uint64_t key) { return merged_count_sharded(sh.dir, sh.owner_bits, key); }
+__device__ __forceinline__ uint32_t nb_count(const TableRef &tb, uint64_t key, uint32_t lanes) { return merged_count(tb, key, lanes); }
+__device__ __forceinline__ uint32_t nb_count(const NbShards &sh, uint64_t key, uint32_t lanes) { return merged_count_sharded(sh.dir, sh.owner_bits, key, lanes); }
 
 // One (entry, base) pair of the current level.  k_n / next_n: the two fill counters (LDS in k_nb_narrow_panel, the control
 // block in k_nb_wide); lds_next: where k_nb_narrow_panel keeps the first NB_NARROW entries of the next level.
-template <class Table>
+// DEPTH: the probe stops at the job's nb.lanes, so jobs of different depths share a launch.
+template <bool DEPTH = false, class Table>
 __device__ __forceinline__ void nb_expand(const Table &tb, const NbRef &nb, uint64_t entry, uint32_t b,
                                           uint64_t *next_list, unsigned long long *k_n, unsigned long long *next_n,
                                           uint32_t *set_full, uint64_t *lds_next) {
@@ -1371,7 +1403,9 @@ __device__ __forceinline__ void nb_expand(const Table &tb, const NbRef &nb, uint
   const uint64_t x = dir ? ((uint64_t)b << sh) | node : (node << 2) | b;
   const uint64_t rc = revcomp(x, nb.k);
   const uint64_t cn = x < rc ? x : rc;
-  const uint32_t cnt = nb_count(tb, cn);
+  uint32_t cnt;
+  if constexpr (DEPTH) cnt = nb_count(tb, cn, nb.lanes);
+  else cnt = nb_count(tb, cn);
   if (cnt < nb.min_count) return;
   const int ins = nb_set_insert(nb.kset, nb.kset_mask, cn);
   if (ins < 0) {
@@ -1402,13 +1436,20 @@ __global__ void __launch_bounds__(WG) k_nb_wide(NbTable<SHARDED> tb, NbRef nb, N
   nb_expand(tb, nb, nb.list[cur_sel][t >> 2], (uint32_t)(t & 3), nb.list[cur_sel ^ 1], &ctl->k_n, &ctl->next_n,
             &ctl->set_full, nullptr);
 }
+// k_nb_wide with the probe bounded by nb.lanes (one table; a multi-device context takes no depth).
+__global__ void __launch_bounds__(WG) k_nb_wide_depth(TableRef tb, NbRef nb, NbCtl *ctl, uint32_t cur_sel, uint64_t cur_n) {
+  const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= cur_n * 4) return;
+  nb_expand<true>(tb, nb, nb.list[cur_sel][t >> 2], (uint32_t)(t & 3), nb.list[cur_sel ^ 1], &ctl->k_n, &ctl->next_n,
+                  &ctl->set_full, nullptr);
+}
 
 // NARROW: one workgroup takes a level of at most NB_NARROW entries through as many levels as it stays that thin —
 // the two entry lists and the fill counters in LDS, a workgroup barrier between levels, no host round trip.  It
 // stops with ctl->status = why: the neighbourhood is complete, max_levels reached, the next level did not fit the
 // caller's capacities (ctl then describes the level before it), or it is too wide for one workgroup (k_nb_wide's).
 // (The level loop itself; k_nb_narrow_panel runs it for its job.)
-template <class Table>
+template <bool DEPTH = false, class Table>
 __device__ __forceinline__ void nb_narrow_levels(const Table &tb, const NbRef &nb, NbCtl *ctl) {
   __shared__ uint64_t s_list[2][NB_NARROW];
   __shared__ unsigned long long s_kn, s_kstart, s_nextn, s_curfull;  // s_curfull: the current level's size, s_curn capped
@@ -1432,7 +1473,7 @@ __device__ __forceinline__ void nb_narrow_levels(const Table &tb, const NbRef &n
   while (true) {
     const uint32_t sel = s_sel, cur_n = s_curn;
     for (uint32_t t = tid; t < cur_n * 4; t += NB_WG)
-      nb_expand(tb, nb, s_list[sel][t >> 2], t & 3, sel ? nb.list[0] : nb.list[1], &s_kn, &s_nextn, &s_full, s_list[sel ^ 1]);
+      nb_expand<DEPTH>(tb, nb, s_list[sel][t >> 2], t & 3, sel ? nb.list[0] : nb.list[1], &s_kn, &s_nextn, &s_full, s_list[sel ^ 1]);
     __syncthreads();
     if (tid == 0) {
       if (s_full || s_kn > nb.cap || s_nextn > nb.fringe_cap) {
@@ -1509,6 +1550,13 @@ __global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel(NbTable<SHARDED> tb, 
   } else {
     nb_narrow_levels(tb, nb, ctl);
   }
+}
+// k_nb_narrow_panel with every job's probe bounded by its own refs[job].lanes (one table).
+__global__ void __launch_bounds__(NB_WG) k_nb_narrow_panel_depth(TableRef tb, const NbRef *__restrict__ refs, NbCtl *ctls) {
+  NbCtl *ctl = &ctls[blockIdx.x];
+  if (ctl->status != NB_RUN || ctl->cur_n == 0 || ctl->cur_n > NB_NARROW) return;
+  const NbRef nb = refs[blockIdx.x];
+  nb_narrow_levels<true>(tb, nb, ctl);
 }
 
 // What a job hands back, packed: its k_n k-mers and counts from pack_k, its n_f fringe entries (the unexpanded level,
@@ -1671,6 +1719,105 @@ __global__ void __launch_bounds__(WG) k_primer_scan(TableRef tb, uint64_t slot0,
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n_prim * stride; i += WG)
     if (cnt[i]) atomicAdd(&hits[(uint64_t)(p_base + i / stride) * SHK_PRIMER_LEVELS + i % stride], (unsigned long long)cnt[i]);
+}
+
+// K_PRIMER at several depths in one pass (shk_primer_kmers_depths).  Per slot the running saturating lane
+// sum is snapshot at the listed depths (ascending, at most SHK_PCR_MAX_DEPTHS: the loops over them are unrolled, so the
+// snapshots stay in registers); f and r are computed once per (key, primer) whatever the number of depths.  A hit at
+// depth j is snap[j] ≥ min_count (the host passes max(min_count, 1): a key whose prefix sum is 0 is not in that table)
+// at a level ≤ cut[j], the primer's M or its cut level at that depth on a rerun.  Hits are monotone in j, so a
+// (key, primer) that misses at the last depth is dropped before any per-depth work.  Records and hit counters are those
+// of k_primer_scan for the virtual primer j · n_all + p.
+struct PrimerDepths {  // a kernel argument: uniform, in scalar registers
+  uint32_t n;
+  uint32_t d[SHK_PCR_MAX_DEPTHS];
+};
+struct PrimerDevD {    // 64 B
+  PrimerDev p;         // (p.M: the highest cut of any depth)
+  uint8_t cut[SHK_PCR_MAX_DEPTHS];
+};
+
+__global__ void __launch_bounds__(WG) k_primer_scan_depths(TableRef tb, uint64_t slot0, uint64_t slot1, int k,
+                                                           const PrimerDevD *__restrict__ prim, uint32_t n_prim,
+                                                           uint32_t p_base, uint32_t n_all /* primers of the call */,
+                                                           uint32_t stride, PrimerDepths dep,
+                                                           PrimerRec *__restrict__ out, uint64_t cap,
+                                                           unsigned long long *__restrict__ n_out,
+                                                           unsigned long long *__restrict__ hits /* [depth][p][SHK_PRIMER_LEVELS] */) {
+  extern __shared__ uint64_t lds[];
+  PrimerDevD *sp = (PrimerDevD *)lds;
+  uint32_t *cnt = (uint32_t *)(sp + n_prim);  // [p][depth][stride]
+  const uint32_t n_cnt = n_prim * dep.n * stride;
+  for (uint32_t i = threadIdx.x; i < n_prim * 8; i += WG) lds[i] = ((const uint64_t *)prim)[i];
+  for (uint32_t i = threadIdx.x; i < n_cnt; i += WG) cnt[i] = 0;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint64_t s0 = slot0 + (uint64_t)blockIdx.x * WG; s0 < slot1; s0 += (uint64_t)gridDim.x * WG) {
+    const uint64_t s = s0 + threadIdx.x;
+    const uint64_t key = s < slot1 ? tb.keys[s] : EMPTY;
+    uint32_t snap[SHK_PCR_MAX_DEPTHS];
+    {
+      uint32_t cum = 0, l = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < SHK_PCR_MAX_DEPTHS; ++j) {
+        if (j < dep.n && key != EMPTY)
+          for (; l < dep.d[j]; ++l) cum = sat_add_u32(cum, tb.vals[(uint64_t)l * tb.cap + s]);
+        snap[j] = cum;  // (beyond dep.n: the last depth's, never read)
+      }
+    }
+    const uint32_t deepest = snap[SHK_PCR_MAX_DEPTHS - 1];
+    if (!__any(deepest != 0)) continue;
+    const uint64_t rk = revcomp(key, k);
+    uint64_t ef[4], er[4];
+    base_planes(key, ef);
+    base_planes(rk, er);
+    for (uint32_t p = 0; p < n_prim; ++p) {
+      const PrimerDev &P = sp[p].p;
+      const bool ok = key != EMPTY && deepest >= P.min_count;
+      const uint32_t f = P.L - (uint32_t)__popcll((ef[0] & P.allow[0]) | (ef[1] & P.allow[1]) |
+                                                  (ef[2] & P.allow[2]) | (ef[3] & P.allow[3]));
+      const uint32_t r = P.L - (uint32_t)__popcll((er[0] & P.allow[0]) | (er[1] & P.allow[1]) |
+                                                  (er[2] & P.allow[2]) | (er[3] & P.allow[3]));
+      const bool cf = ok && f <= P.M;
+      const bool cr = ok && r <= P.M && r != f;
+      if (!__any(cf || cr)) continue;
+#pragma unroll
+      for (uint32_t j = 0; j < SHK_PCR_MAX_DEPTHS; ++j) {
+        if (j < dep.n) {  // (uniform)
+          const uint32_t cut = sp[p].cut[j];
+          const bool here = snap[j] >= P.min_count;
+          const bool hf = cf && here && f <= cut;
+          const bool hr = cr && here && r <= cut;
+          const uint64_t bf = __ballot(hf), br = __ballot(hr);
+          if (bf | br) {
+            const uint32_t nf = (uint32_t)__popcll(bf);
+            unsigned long long at = 0;
+            if (lane == 0) at = atomicAdd(n_out, (unsigned long long)(nf + __popcll(br)));
+            at = __shfl(at, 0);
+            const uint32_t tag = (j * n_all + p_base + p) << 8;
+            uint32_t *c = cnt + (p * dep.n + j) * stride;
+            if (hf) {
+              const unsigned long long i = at + __popcll(bf & below);
+              if (i < cap) out[i] = PrimerRec{key, snap[j], tag | f};
+              atomicAdd(&c[f], 1u);
+            }
+            if (hr) {
+              const unsigned long long i = at + nf + __popcll(br & below);
+              if (i < cap) out[i] = PrimerRec{rk, snap[j], tag | r};
+              atomicAdd(&c[r], 1u);
+            }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n_cnt; i += WG)
+    if (cnt[i]) {
+      const uint32_t p = i / (dep.n * stride), j = i / stride % dep.n, m = i % stride;
+      atomicAdd(&hits[((uint64_t)j * n_all + p_base + p) * SHK_PRIMER_LEVELS + m], (unsigned long long)cnt[i]);
+    }
 }
 
 // ==========================================================================================

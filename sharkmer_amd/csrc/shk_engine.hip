@@ -3375,6 +3375,23 @@ int shk_get_counters(shk_ctx *c, shk_counters *o) {
   return SHK_OK;
 }
 
+// The per-lane terms of shk_get_counters' n_bases_ingested.
+int shk_chunk_bases(shk_ctx *c, uint64_t *out) {
+  SHK_TRY(xs_closed(c));
+  if (!c || !out) return SHK_ERR_BAD_ARG;
+  SHK_TRY(single_device_only(c));
+  HIPC(c, hipSetDevice(c->cfg.device));
+  SHK_TRY(settle(c));
+  if (!c->finalized && !c->hist_ready) {  // (as shk_get_counters)
+    HIPC(c, hipMemcpyAsync(c->h_lane_bases, c->d_lane_bases, sizeof(unsigned long long) * c->n_lanes,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+  }
+  const unsigned long long *lb = c->fin_summed && c->finalized ? c->h_lane_sum : c->h_lane_bases;
+  for (uint32_t l = 0; l < c->n_lanes; ++l) out[l] = lb[l];
+  return SHK_OK;
+}
+
 int shk_get_timings(shk_ctx *c, shk_timings *o) {
   SHK_TRY(xs_closed(c));
   if (!c || !o) return SHK_ERR_BAD_ARG;

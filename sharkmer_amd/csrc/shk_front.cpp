@@ -2083,6 +2083,75 @@ int shk_write_fasta(const char *path, const char *sample, const shk_pcr_gene *ge
   return fclose(f) == 0 ? SHK_OK : SHK_ERR_IO;
 }
 
+// ---- the depth sweep's host side: the --pcr-depths value, its check, the TSV ----
+
+int shk_pcr_check_depths(const uint32_t *depths, uint64_t n, uint32_t chunks, char *err, size_t err_cap) {
+  put_text(err, err_cap, "");
+  auto bail = [&](const std::string &why) {
+    put_text(err, err_cap, why);
+    return SHK_ERR_BAD_ARG;
+  };
+  if (chunks == 0) return bail("--pcr-depths needs --chunks of at least 1: a depth is a number of chunks");
+  if (n == 0 || !depths) return bail("--pcr-depths: no depth given");
+  for (uint64_t j = 0; j < n; ++j) {
+    if (depths[j] == 0 || depths[j] > chunks) return bail(fmt("--pcr-depths: depth %u is not in 1..%u (--chunks)", depths[j], chunks));
+    if (j && depths[j] <= depths[j - 1])
+      return bail(fmt("--pcr-depths: depths must be strictly ascending (%u after %u)", depths[j], depths[j - 1]));
+  }
+  return SHK_OK;
+}
+
+int shk_pcr_parse_depths(const char *spec, uint32_t chunks, uint32_t *depths, uint64_t cap, uint64_t *n_depths, char *err, size_t err_cap) {
+  put_text(err, err_cap, "");
+  if (!spec || !n_depths || (cap && !depths)) return SHK_ERR_BAD_ARG;
+  *n_depths = 0;
+  std::vector<uint32_t> d;
+  const std::string s = spec;
+  if (s == "all") {
+    for (uint32_t i = 1; i <= chunks; ++i) d.push_back(i);
+    if (d.empty()) return shk_pcr_check_depths(nullptr, 0, chunks, err, err_cap);  // (chunks == 0: its text)
+  } else {
+    for (size_t a = 0; a <= s.size();) {
+      const size_t b = std::min(s.find(',', a), s.size());
+      uint64_t v = 0;
+      if (!parse_uint(s.substr(a, b - a), 0xFFFFFFFFull, &v)) {
+        put_text(err, err_cap, fmt("--pcr-depths: '%s' is neither 'all' nor a list of depths d1,d2,...", spec));
+        return SHK_ERR_BAD_ARG;
+      }
+      d.push_back((uint32_t)v);
+      a = b + 1;
+    }
+  }
+  *n_depths = d.size();
+  const int rc = shk_pcr_check_depths(d.data(), d.size(), chunks, err, err_cap);
+  if (rc != SHK_OK) return rc;
+  if (d.size() > cap) {
+    put_text(err, err_cap, fmt("--pcr-depths: %zu depths do not fit %llu", d.size(), (unsigned long long)cap));
+    return SHK_ERR_BAD_ARG;
+  }
+  std::copy(d.begin(), d.end(), depths);
+  return SHK_OK;
+}
+
+int shk_write_pcr_depths_tsv(const char *path, const shk_pcr_depth_row *rows, uint64_t n) {
+  if (!path || (n && !rows)) return SHK_ERR_BAD_ARG;
+  for (uint64_t i = 0; i < n; ++i)
+    if (!rows[i].gene.gene_name || (rows[i].gene.n_products && !rows[i].gene.product_lengths)) return SHK_ERR_BAD_ARG;
+  FILE *f = fopen(path, "w");
+  if (!f) return SHK_ERR_IO;
+  fprintf(f, "depth\tn_bases_ingested\tgene\tstatus\tfailure_reason\tn_products\tproduct_lengths\n");
+  for (uint64_t i = 0; i < n; ++i) {
+    const shk_pcr_depth_row &r = rows[i];
+    const bool ok = r.gene.status == SHK_PCR_SUCCESS;
+    const char *reason = shk_pcr_failure_reason(r.gene.status);
+    fprintf(f, "%u\t%llu\t%s\t%s\t%s\t%u\t", r.depth, (unsigned long long)r.n_bases_ingested, r.gene.gene_name, ok ? "success" : "fail",
+            ok ? "" : reason ? reason : "unknown (no reason reported by PCR pipeline)", r.gene.n_products);
+    for (uint32_t p = 0; p < r.gene.n_products; ++p) fprintf(f, "%s%llu", p ? "," : "", (unsigned long long)r.gene.product_lengths[p]);
+    fputc('\n', f);
+  }
+  return fclose(f) == 0 ? SHK_OK : SHK_ERR_IO;
+}
+
 const char *shk_run_error(void) { return run_error().c_str(); }
 
 int shk_validate_args(uint32_t k, uint64_t histo_max, const char *sample) {

@@ -40,6 +40,10 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
   g_run_error.clear();
   int v = shk_validate_args(rc->k, rc->histo_max, rc->sample);
   if (v != SHK_OK) return v;
+  if (pcr && !n_genes && (pcr->depths || pcr->n_depths)) {
+    g_run_error = "--pcr-depths needs --pcr-primers";
+    return SHK_ERR_BAD_ARG;
+  }
   if (n_genes) {  // collect_pcr_params (cli.rs:528-581), before a read is read
     if (!pcr->genes) return SHK_ERR_BAD_ARG;
     std::vector<char> report(4096 + 2048 * (size_t)n_genes);
@@ -56,6 +60,21 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
     if (pcr->context_flags & ~(uint64_t)(SHK_FLAG_GROUP_GRAPH | SHK_FLAG_GROUP_READS)) {
       g_run_error = fmt("shk_pcr_file_config.context_flags 0x%llx: only SHK_FLAG_GROUP_GRAPH and SHK_FLAG_GROUP_READS are taken", (unsigned long long)pcr->context_flags);
       return SHK_ERR_BAD_ARG;
+    }
+    if (pcr->depths || pcr->n_depths) {  // --pcr-depths: what the sweep does not take, before a read is read
+      char why[256];
+      if (pcr->read_threading) {
+        g_run_error = "--pcr-depths takes no --read-threading: a depth sweep takes no reads";
+        return SHK_ERR_BAD_ARG;
+      }
+      if (rc->n_devices > 1) {
+        g_run_error = "--pcr-depths needs one device: no depths on a multi-device context";
+        return SHK_ERR_BAD_ARG;
+      }
+      if (shk_pcr_check_depths(pcr->depths, pcr->n_depths, rc->chunks, why, sizeof why) != SHK_OK) {
+        g_run_error = why;
+        return SHK_ERR_BAD_ARG;
+      }
     }
     if (rc->n_devices > 1 && !(pcr->context_flags & SHK_FLAG_GROUP_GRAPH)) {
       g_run_error = "shk_pcr_extend_panel needs the whole table on one device: this is a multi-device context (n_devices > 1)";
@@ -358,6 +377,86 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
         return v;
       }
     }
+  }
+  // --pcr-depths: the panel at the listed depths, SHK_PCR_MAX_DEPTHS per call; {sample}_{gene}.depth{d}.fasta for every
+  // (gene, depth) with products and {sample}.pcr_depths.tsv, depth-major then gene order
+  if (n_genes && pcr->depths) {
+    std::vector<uint64_t> chunk_bases(cn.n_chunks), all_lengths;
+    std::vector<shk_pcr_depth_row> rows;
+    std::vector<std::pair<uint64_t, uint32_t>> row_lengths;  // per row: where its lengths start in all_lengths, how many
+    if ((v = shk_chunk_bases(ctx, chunk_bases.data())) != SHK_OK) {
+      g_run_error = shk_last_error(ctx);
+      cleanup();
+      return v;
+    }
+    shk_pcr_run_params pp{};
+    pp.min_kmer_count = pcr->min_kmer_count;
+    pp.reads = SHK_PCR_READS_NONE;
+    pp.max_num_nodes = pcr->node_budget_global;
+    const uint64_t cap = (uint64_t)SHK_PCR_MAX_AMPLICONS * n_genes;
+    struct DepthOut {
+      std::vector<uint32_t> status;
+      std::vector<uint64_t> roff, soff, cmin, cmax;
+      std::vector<uint8_t> seqs;
+      std::vector<double> mean, median, score;
+    };
+    for (uint64_t d0 = 0; d0 < pcr->n_depths; d0 += SHK_PCR_MAX_DEPTHS) {
+      const uint32_t D = (uint32_t)std::min<uint64_t>(SHK_PCR_MAX_DEPTHS, pcr->n_depths - d0);
+      std::vector<DepthOut> bufs(D);
+      std::vector<shk_pcr_run_out> outs(D);
+      std::vector<uint64_t> seq_cap(D, 1ull << 20);
+      for (int attempt = 0;; ++attempt) {
+        for (uint32_t j = 0; j < D; ++j) {
+          DepthOut &b = bufs[j];
+          b.status.assign(n_genes, 0), b.roff.assign(n_genes + 1, 0), b.soff.assign(cap + 1, 0), b.cmin.assign(cap, 0), b.cmax.assign(cap, 0);
+          b.mean.assign(cap, 0), b.median.assign(cap, 0), b.score.assign(cap, 0), b.seqs.assign(seq_cap[j], 0);
+          outs[j] = shk_pcr_run_out{};
+          outs[j].status = b.status.data();
+          shk_pcr_records &R = outs[j].records;
+          R.record_offsets = b.roff.data(), R.seq_offsets = b.soff.data(), R.seqs = b.seqs.data(), R.record_cap = cap, R.seq_cap = seq_cap[j];
+          R.count_mean = b.mean.data(), R.count_median = b.median.data(), R.count_min = b.cmin.data(), R.count_max = b.cmax.data();
+          R.score = b.score.data();
+        }
+        v = shk_pcr_run_depths(ctx, pcr->genes, n_genes, &pp, pcr->depths + d0, D, outs.data());
+        bool grew = false;
+        for (uint32_t j = 0; j < D; ++j)
+          if (outs[j].records.n_seq_bytes > seq_cap[j]) seq_cap[j] = outs[j].records.n_seq_bytes, grew = true;
+        if (v == SHK_ERR_BAD_ARG && attempt == 0 && grew) continue;  // products beyond a megabase: once more
+        break;
+      }
+      if (v != SHK_OK) {
+        g_run_error = shk_last_error(ctx);
+        cleanup();
+        return v;
+      }
+      for (uint32_t j = 0; j < D; ++j) {
+        const uint32_t depth = pcr->depths[d0 + j];
+        uint64_t below = 0;
+        for (uint32_t l = 0; l < depth && l < chunk_bases.size(); ++l) below += chunk_bases[l];
+        const shk_pcr_records &R = outs[j].records;
+        for (uint32_t g = 0; g < n_genes; ++g) {
+          const uint64_t a = R.record_offsets[g], b = R.record_offsets[g + 1];
+          row_lengths.push_back({all_lengths.size(), (uint32_t)(b - a)});
+          for (uint64_t r = a; r < b; ++r) all_lengths.push_back(R.seq_offsets[r + 1] - R.seq_offsets[r]);
+          rows.push_back(shk_pcr_depth_row{depth, 0, below, shk_pcr_gene_stat{pcr->genes[g].gene_name, outs[j].status[g], (uint32_t)(b - a), nullptr}});
+          if (b == a) continue;
+          const std::string path = dir + sample + "_" + pcr->genes[g].gene_name + fmt(".depth%u.fasta", depth);
+          if ((v = shk_write_fasta(path.c_str(), sample.c_str(), &pcr->genes[g], &R, a, b - a)) != SHK_OK) {
+            g_run_error = fmt("Failed to create FASTA file: %s", path.c_str());
+            cleanup();
+            return v;
+          }
+        }
+      }
+    }
+    for (size_t i = 0; i < rows.size(); ++i) rows[i].gene.product_lengths = all_lengths.data() + row_lengths[i].first;  // (all_lengths is complete)
+    const std::string tsv = dir + sample + ".pcr_depths.tsv";
+    if ((v = shk_write_pcr_depths_tsv(tsv.c_str(), rows.data(), rows.size())) != SHK_OK) {
+      g_run_error = fmt("Failed to create depth table: %s", tsv.c_str());
+      cleanup();
+      return v;
+    }
+    mark("sPCR depth sweep");
   }
   shk_run_stats st{};
   st.sharkmer_version = version;

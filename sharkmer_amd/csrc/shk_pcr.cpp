@@ -327,7 +327,8 @@ struct Raw {
 // who: the public call, for its error texts.  The panel-only knobs (SHK_PCR_PANEL_*) are the panel's: the single call
 // has no launch budget to share, one thread, and no trace line.
 int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params, bool panel,
-              const char *who, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
+              const char *who, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err,
+              const uint32_t *gene_depths) {
   const uint64_t fetch_cap = env_u64("SHK_PCR_FETCH_CAP", 0);  // 0: sized by the replay's room
   const uint64_t budget = panel ? env_u64("SHK_PCR_PANEL_FETCH_CAP", 1ull << 22) : ~0ull;
   const char *env_threads = panel ? getenv("SHK_PCR_PANEL_THREADS") : "1";  // default 8; whatever is given is clamped to 1..16
@@ -344,7 +345,7 @@ int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_ge
   struct Launch {
     std::vector<uint64_t> nodes, seed_offsets, caps, n_out, n_fringe;
     std::vector<uint8_t> dirs;
-    std::vector<uint32_t> min_counts, levels;
+    std::vector<uint32_t> min_counts, levels, depths;
     Raw<uint64_t> kmers, fnodes;
     Raw<uint32_t> counts;
     Raw<uint8_t> fdirs;
@@ -392,7 +393,7 @@ int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_ge
       const uint64_t share = budget / n_jobs;
       if (launches_used == launches.size()) launches.emplace_back();
       Launch &L = launches[launches_used++];
-      L.nodes.clear(), L.dirs.clear(), L.min_counts.clear(), L.caps.clear();
+      L.nodes.clear(), L.dirs.clear(), L.min_counts.clear(), L.caps.clear(), L.depths.clear();
       L.seed_offsets.assign(1, 0);
       uint64_t total = 0;
       for (size_t i = a; i < b; ++i) {
@@ -403,15 +404,21 @@ int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_ge
         }
         L.seed_offsets.push_back(L.nodes.size());
         L.min_counts.push_back(ex.cn.accept);
+        if (gene_depths) L.depths.push_back(gene_depths[active[i]]);
         // level 0 always fits 4 k-mers and 4 successors per entry: every fetch gets at least one level further
         L.caps.push_back(std::max<uint64_t>(fetch_cap ? fetch_cap : std::min(share, ex.room), 4 * ex.seeds.size()));
         total += L.caps.back();
       }
       L.n_out.resize(n_jobs), L.n_fringe.resize(n_jobs), L.levels.resize(n_jobs);
-      const int rc = shk_neighborhood_panel(ctx, L.nodes.data(), L.dirs.data(), L.seed_offsets.data(), n_jobs, L.min_counts.data(),
-                                            0, L.caps.data(), L.caps.data(), L.kmers.need(total), L.counts.need(total),
-                                            L.n_out.data(), L.fnodes.need(total), L.fdirs.need(total), L.n_fringe.data(),
-                                            L.levels.data());
+      uint64_t *const lk = L.kmers.need(total), *const lfn = L.fnodes.need(total);
+      uint32_t *const lc = L.counts.need(total);
+      uint8_t *const lfd = L.fdirs.need(total);
+      const int rc = gene_depths ? shk_neighborhood_panel_depths(ctx, L.nodes.data(), L.dirs.data(), L.seed_offsets.data(), n_jobs,
+                                                                 L.min_counts.data(), L.depths.data(), 0, L.caps.data(), L.caps.data(), lk,
+                                                                 lc, L.n_out.data(), lfn, lfd, L.n_fringe.data(), L.levels.data())
+                                 : shk_neighborhood_panel(ctx, L.nodes.data(), L.dirs.data(), L.seed_offsets.data(), n_jobs,
+                                                          L.min_counts.data(), 0, L.caps.data(), L.caps.data(), lk, lc, L.n_out.data(), lfn,
+                                                          lfd, L.n_fringe.data(), L.levels.data());
       if (rc != SHK_OK) return rc;
       n_launches += 1;
       // 3. each job's answer to its gene (merged by the gene's thread of the next round)
@@ -442,10 +449,11 @@ int panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_ge
 }  // namespace
 
 int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params,
-                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err) {
+                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err,
+                         const uint32_t *gene_depths) {
   const char *who = panel ? "shk_pcr_extend_panel" : "shk_pcr_extend";
   try {
-    return panel_run(ctx, k, primers, n_genes, params, panel, who, out, threshold_used, steps_run, err);
+    return panel_run(ctx, k, primers, n_genes, params, panel, who, out, threshold_used, steps_run, err, gene_depths);
   } catch (const std::exception &e) {  // bad_alloc on the calling thread: an error code, not an exception across the C ABI
     *err = std::string(who) + ": " + e.what();
     return SHK_ERR_NOMEM;

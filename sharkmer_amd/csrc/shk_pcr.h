@@ -37,6 +37,8 @@ struct PcrPrimers {  // one gene's two primer sets
 // shk_neighborhood_panel call per round, made by the calling thread.  panel: shk_pcr_extend_panel's call; else
 // shk_pcr_extend's, one gene on the calling thread, which the SHK_PCR_PANEL_* knobs do not govern.  Returns SHK_OK or
 // the code of a failed shk_neighborhood_panel (its text is the context's last error); *err is set for failures of its
-// own, a failed host allocation among them (SHK_ERR_NOMEM).
+// own, a failed host allocation among them (SHK_ERR_NOMEM).  gene_depths (or nullptr): gene g reads the table at depth
+// gene_depths[g] — its fetches go through shk_neighborhood_panel_depths, all else is the same.
 int pcr_extend_panel_run(shk_ctx *ctx, uint32_t k, const PcrPrimers *primers, uint32_t n_genes, const shk_pcr_extend_params *params,
-                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err);
+                         bool panel, std::vector<PcrGraph> *out, uint32_t *threshold_used, uint32_t *steps_run, std::string *err,
+                         const uint32_t *gene_depths = nullptr);

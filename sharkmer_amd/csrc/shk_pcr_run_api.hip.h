@@ -38,9 +38,8 @@ void pcr_fill(T *p, uint32_t n, T v) {
   if (p) std::fill(p, p + n, v);
 }
 
-int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, shk_pcr_run_out *out) {
-  using ull = unsigned long long;
-  const uint32_t k = c->cfg.k;
+// A run's outputs before anything is known: no records, every per-gene figure 0, every status NO_PATH.
+void pcr_out_clear(shk_pcr_run_out *out, uint32_t ng) {
   shk_pcr_records &R = out->records;
   R.n_records = R.n_seq_bytes = 0;
   std::fill(R.record_offsets, R.record_offsets + ng + 1, 0ull);
@@ -51,17 +50,20 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   pcr_fill(out->n_pruned_edges, ng, (uint64_t)0), pcr_fill(out->n_reads_matched, ng, (uint64_t)0), pcr_fill(out->n_paired_links, ng, (uint64_t)0);
   pcr_fill(out->threaded, ng, (uint8_t)0), pcr_fill(out->low_primer_counts, ng, (uint8_t)0);
   pcr_fill(out->status, ng, (uint32_t)SHK_PCR_NO_PATH);
+}
 
-  // ---- everything that is refused, the first in gene order, before the device is touched ----
-  if (ng > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", ng, (unsigned)SHK_PCR_MAX_GENES);
-  if (p->reads > SHK_PCR_READS_HOST) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run: reads = %u is none of SHK_PCR_READS_*", p->reads);
+// The host checks of a panel, the first gene in gene order that fails one, and what the primer scan takes: gene g's two
+// directions at primers[2g], primers[2g + 1] with the clamped min_count[g]; *primer_cap = Σ 2 · max_primer_kmers.
+int pcr_genes_check(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, std::vector<shk_primer> *primers_out,
+                    std::vector<uint32_t> *min_count_out, uint64_t *primer_cap_out) {
   // per gene, the first in gene order wins: validate_pcr_params (mod.rs:295-399; the gene's first failure), the name taken
   // by an earlier gene (cli.rs:572-581), then get_primer_kmers' own errors in its order (primers.rs:440-478): too many
   // variants forward, reverse, then an invalid character forward, reverse — one batched shk_primer_kmers call would
   // report every gene's variants before any gene's characters.  Step 1's clamp is here too (cli.rs:556-570).
-  const uint32_t floor = std::max(p->min_kmer_count, 1u);
-  std::vector<shk_primer> primers(2 * (size_t)ng);
-  std::vector<uint32_t> min_count(ng);
+  const uint32_t k = c->cfg.k, floor = std::max(p->min_kmer_count, 1u);
+  std::vector<shk_primer> &primers = *primers_out;
+  std::vector<uint32_t> &min_count = *min_count_out;
+  primers.resize(2 * (size_t)ng), min_count.resize(ng);
   uint64_t primer_cap = 0;
   for (uint32_t g = 0; g < ng; ++g) {
     char text[1024];
@@ -84,6 +86,93 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
     const int code = rf == SHK_ERR_BAD_ARG ? rf : rr == SHK_ERR_BAD_ARG ? rr : rf != SHK_OK ? rf : rr;
     if (why) return fail(c, code, "gene %u '%s': %s", g, genes[g].gene_name, why);
   }
+  *primer_cap_out = primer_cap;
+  return SHK_OK;
+}
+
+// ---- the stages shk_pcr_run and shk_pcr_run_depths share: each is handed its genes (or (gene, depth) pairs) gathered ----
+
+// Step 4's output: the extended graphs of the alive genes back to back, and per gene what the sweep reports.
+struct PcrExtended {
+  std::vector<uint64_t> sub, noff, eoff;
+  std::vector<uint8_t> flags;
+  std::vector<uint32_t> es, et, ec, found, thr, steps;
+  explicit PcrExtended(uint32_t na) : noff(na + 1, 0), eoff(na + 1, 0), found(std::max(na, 1u), 0), thr(std::max(na, 1u), 0), steps(std::max(na, 1u), 0) {}
+};
+// Step 4's call for na genes: shk_pcr_extend_panel, or with gene_depths its depth form, with room that grows once to what
+// the offsets say it needs.
+int pcr_extend_stage(shk_ctx *c, const std::vector<uint64_t> &ak, const std::vector<uint32_t> &ac, const std::vector<uint64_t> &aoff, uint32_t na,
+                     const std::vector<shk_pcr_extend_params> &xp, const uint32_t *gene_depths, PcrExtended *x) {
+  uint64_t node_cap = 4096ull * na, edge_cap = 8192ull * na;
+  for (int attempt = 0;; ++attempt) {
+    x->sub.resize(node_cap), x->flags.resize(node_cap), x->es.resize(edge_cap), x->et.resize(edge_cap), x->ec.resize(edge_cap);
+    const int rc =
+        gene_depths ? shk_pcr_extend_panel_depths(c, ak.data(), ac.data(), aoff.data(), na, xp.data(), gene_depths, x->sub.data(), x->flags.data(),
+                                                  x->noff.data(), node_cap, x->es.data(), x->et.data(), x->ec.data(), x->eoff.data(), edge_cap,
+                                                  x->found.data(), x->thr.data(), x->steps.data())
+                    : shk_pcr_extend_panel(c, ak.data(), ac.data(), aoff.data(), na, xp.data(), x->sub.data(), x->flags.data(), x->noff.data(), node_cap,
+                                           x->es.data(), x->et.data(), x->ec.data(), x->eoff.data(), edge_cap, x->found.data(), x->thr.data(),
+                                           x->steps.data());
+    if (rc == SHK_ERR_BAD_ARG && attempt == 0 && (x->noff[na] > node_cap || x->eoff[na] > edge_cap)) {  // the offsets say what it needs
+      node_cap = std::max(node_cap, x->noff[na]), edge_cap = std::max(edge_cap, x->eoff[na]);
+      continue;
+    }
+    return rc;
+  }
+}
+
+// Step 6's pruned graphs of the genes with a path, back to back (the layout shk_pcr_products_panel takes).
+struct PcrPruned {
+  std::vector<uint64_t> sub, noff, eoff;
+  std::vector<uint8_t> flags;
+  std::vector<uint32_t> es, et, ec;
+  std::vector<double> ratio;
+};
+// The prune of the graphs `found` (positions in x) under tip[f], one shk_pcr_prune_panel call.
+int pcr_prune_stage(shk_ctx *c, const PcrExtended &x, const std::vector<uint32_t> &found, const std::vector<double> &tip, PcrPruned *q) {
+  const uint32_t nf = (uint32_t)found.size();
+  std::vector<uint64_t> fsub, fnoff = pcr_gather_offsets(x.noff, found), feoff = pcr_gather_offsets(x.eoff, found);
+  std::vector<uint8_t> fflags;
+  std::vector<uint32_t> fes, fet, fec;
+  pcr_gather(x.sub.data(), x.noff, found, &fsub), pcr_gather(x.flags.data(), x.noff, found, &fflags);
+  pcr_gather(x.es.data(), x.eoff, found, &fes), pcr_gather(x.et.data(), x.eoff, found, &fet), pcr_gather(x.ec.data(), x.eoff, found, &fec);
+  std::vector<shk_pcr_prune_params> pp(nf);
+  for (uint32_t f = 0; f < nf; ++f) pp[f] = shk_pcr_prune_params{tip[f], 3u, 0u};
+  const uint64_t nn = fnoff[nf], ne = feoff[nf];
+  std::vector<uint8_t> keep(std::max<uint64_t>(nn, 1));
+  q->flags.assign(std::max<uint64_t>(nn, 1), 0), q->sub.assign(std::max<uint64_t>(nn, 1), 0), q->noff.assign(nf + 1, 0), q->eoff.assign(nf + 1, 0);
+  q->es.assign(std::max<uint64_t>(ne, 1), 0), q->et.assign(q->es.size(), 0), q->ec.assign(q->es.size(), 0), q->ratio.assign(q->es.size(), 0.0);
+  shk_pcr_prune_out po{};
+  po.node_keep = keep.data(), po.out_node_offsets = q->noff.data(), po.out_edge_offsets = q->eoff.data();
+  po.node_sub_kmers = q->sub.data(), po.node_flags = q->flags.data(), po.node_cap = nn;
+  po.edge_src = q->es.data(), po.edge_tgt = q->et.data(), po.edge_counts = q->ec.data(), po.coverage_ratio = q->ratio.data(), po.edge_cap = ne;
+  return shk_pcr_prune_panel(c, fsub.data(), fflags.data(), fnoff.data(), fes.data(), fet.data(), fec.data(), feoff.data(), nf, pp.data(), &po);
+}
+
+// What shk_pcr_products_panel takes per gene, for the genes fgene (indices into genes).
+void pcr_products_params(const shk_pcr_gene *genes, const std::vector<uint32_t> &fgene, std::vector<shk_pcr_paths_params> *path_p,
+                         std::vector<uint32_t> *dedup_t) {
+  path_p->resize(fgene.size()), dedup_t->resize(fgene.size());
+  for (size_t f = 0; f < fgene.size(); ++f) {
+    const shk_pcr_gene &ge = genes[fgene[f]];
+    (*path_p)[f] = shk_pcr_paths_params{ge.min_length, ge.max_length, ge.max_dfs_states, ge.max_paths_per_pair, ge.max_node_visits};
+    (*dedup_t)[f] = ge.dedup_edit_threshold;
+  }
+}
+
+int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, shk_pcr_run_out *out) {
+  using ull = unsigned long long;
+  const uint32_t k = c->cfg.k;
+  shk_pcr_records &R = out->records;
+  pcr_out_clear(out, ng);
+
+  // ---- everything that is refused, the first in gene order, before the device is touched ----
+  if (ng > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", ng, (unsigned)SHK_PCR_MAX_GENES);
+  if (p->reads > SHK_PCR_READS_HOST) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run: reads = %u is none of SHK_PCR_READS_*", p->reads);
+  std::vector<shk_primer> primers;
+  std::vector<uint32_t> min_count;
+  uint64_t primer_cap = 0;
+  SHK_TRY(pcr_genes_check(c, genes, ng, p, &primers, &min_count, &primer_cap));
   SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
   // A multi-device context (SHK_FLAG_GROUP_GRAPH): the calls that take the context take it as it is — the primer scan
   // goes over the shares, the extension through the share directory, prune and products on the first device — and the
@@ -189,9 +278,9 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   }
 
   // ---- step 4: the extension of the alive genes ----
-  std::vector<uint64_t> xsub, xnoff(na + 1, 0), xeoff(na + 1, 0);
-  std::vector<uint8_t> xflags;
-  std::vector<uint32_t> xes, xet, xec, xfound(std::max(na, 1u), 0), xthr(std::max(na, 1u), 0), xsteps(std::max(na, 1u), 0);
+  PcrExtended X(na);
+  const std::vector<uint64_t> &xnoff = X.noff, &xeoff = X.eoff;
+  const std::vector<uint32_t> &xfound = X.found, &xthr = X.thr, &xsteps = X.steps;
   std::vector<uint32_t> found;  // positions in alive of the genes whose last step found a path
   if (na) {
     std::vector<uint64_t> ak, aoff(2 * (size_t)na + 1, 0);
@@ -205,18 +294,7 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       aoff[2 * a + 2] = aoff[2 * a] + (poff[2 * g + 2] - poff[2 * g]);
       xp[a] = shk_pcr_extend_params{min_count[g], p->min_kmer_count, genes[g].high_coverage_ratio, budget, 1u, 0u};
     }
-    uint64_t node_cap = 4096ull * na, edge_cap = 8192ull * na;
-    for (int attempt = 0;; ++attempt) {
-      xsub.resize(node_cap), xflags.resize(node_cap), xes.resize(edge_cap), xet.resize(edge_cap), xec.resize(edge_cap);
-      const int rc = shk_pcr_extend_panel(c, ak.data(), ac.data(), aoff.data(), na, xp.data(), xsub.data(), xflags.data(), xnoff.data(), node_cap,
-                                          xes.data(), xet.data(), xec.data(), xeoff.data(), edge_cap, xfound.data(), xthr.data(), xsteps.data());
-      if (rc == SHK_ERR_BAD_ARG && attempt == 0 && (xnoff[na] > node_cap || xeoff[na] > edge_cap)) {  // the offsets say what it needs
-        node_cap = std::max(node_cap, xnoff[na]), edge_cap = std::max(edge_cap, xeoff[na]);
-        continue;
-      }
-      SHK_TRY(rc);
-      break;
-    }
+    SHK_TRY(pcr_extend_stage(c, ak, ac, aoff, na, xp, nullptr, &X));
     for (uint32_t a = 0; a < na; ++a) {
       const uint32_t g = alive[a];
       const uint64_t nn = xnoff[a + 1] - xnoff[a];
@@ -234,23 +312,15 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   // ---- step 6, for the genes with a path: prune, thread, products ----
   int products_rc = SHK_OK;
   if (nf) {
-    std::vector<uint64_t> fsub, fnoff = pcr_gather_offsets(xnoff, found), feoff = pcr_gather_offsets(xeoff, found);
-    std::vector<uint8_t> fflags;
-    std::vector<uint32_t> fes, fet, fec;
-    pcr_gather(xsub.data(), xnoff, found, &fsub), pcr_gather(xflags.data(), xnoff, found, &fflags);
-    pcr_gather(xes.data(), xeoff, found, &fes), pcr_gather(xet.data(), xeoff, found, &fet), pcr_gather(xec.data(), xeoff, found, &fec);
-    std::vector<shk_pcr_prune_params> pp(nf);
-    for (uint32_t f = 0; f < nf; ++f) pp[f] = shk_pcr_prune_params{genes[alive[found[f]]].tip_coverage_fraction, 3u, 0u};
-    const uint64_t nn = fnoff[nf], ne = feoff[nf];
-    std::vector<uint8_t> keep(std::max<uint64_t>(nn, 1)), qflags(std::max<uint64_t>(nn, 1));
-    std::vector<uint64_t> qsub(std::max<uint64_t>(nn, 1)), qnoff(nf + 1, 0), qeoff(nf + 1, 0);
-    std::vector<uint32_t> qes(std::max<uint64_t>(ne, 1)), qet(qes.size()), qec(qes.size());
-    std::vector<double> qratio(qes.size());
-    shk_pcr_prune_out po{};
-    po.node_keep = keep.data(), po.out_node_offsets = qnoff.data(), po.out_edge_offsets = qeoff.data();
-    po.node_sub_kmers = qsub.data(), po.node_flags = qflags.data(), po.node_cap = nn;
-    po.edge_src = qes.data(), po.edge_tgt = qet.data(), po.edge_counts = qec.data(), po.coverage_ratio = qratio.data(), po.edge_cap = ne;
-    SHK_TRY(shk_pcr_prune_panel(c, fsub.data(), fflags.data(), fnoff.data(), fes.data(), fet.data(), fec.data(), feoff.data(), nf, pp.data(), &po));
+    std::vector<uint32_t> fgene(nf);  // the genes with a path
+    std::vector<double> tip(nf);
+    for (uint32_t f = 0; f < nf; ++f) fgene[f] = alive[found[f]], tip[f] = genes[fgene[f]].tip_coverage_fraction;
+    PcrPruned Q;
+    SHK_TRY(pcr_prune_stage(c, X, found, tip, &Q));
+    std::vector<uint64_t> &qsub = Q.sub, &qnoff = Q.noff, &qeoff = Q.eoff;
+    std::vector<uint8_t> &qflags = Q.flags;
+    std::vector<uint32_t> &qes = Q.es, &qet = Q.et, &qec = Q.ec;
+    std::vector<double> &qratio = Q.ratio;
     // the threaded genes: reads were given and the gene's list is not empty (mod.rs:664-697)
     std::vector<uint32_t> thr;  // positions in found
     for (uint32_t f = 0; f < nf && have_batch; ++f)
@@ -305,13 +375,9 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       G.support_total = stot.data(), G.support_unambiguous = suna.data(), G.link_offsets = loff.data();
       G.link_in = lin.data(), G.link_out = lout.data(), G.link_counts = lcnt.data(), G.has_threading = has.data();
     }
-    std::vector<shk_pcr_paths_params> path_p(nf);
-    std::vector<uint32_t> dedup_t(nf);
-    for (uint32_t f = 0; f < nf; ++f) {
-      const shk_pcr_gene &ge = genes[alive[found[f]]];
-      path_p[f] = shk_pcr_paths_params{ge.min_length, ge.max_length, ge.max_dfs_states, ge.max_paths_per_pair, ge.max_node_visits};
-      dedup_t[f] = ge.dedup_edit_threshold;
-    }
+    std::vector<shk_pcr_paths_params> path_p;
+    std::vector<uint32_t> dedup_t;
+    pcr_products_params(genes, fgene, &path_p, &dedup_t);
     std::vector<uint64_t> roff(nf + 1, 0), paths_found(nf, 0), generated(nf, 0), states(nf, 0);
     shk_pcr_records loc = R;  // the caller's record arrays and capacities; the per-gene arrays are this call's
     loc.record_offsets = roff.data(), loc.paths_found = paths_found.data(), loc.generated = generated.data(), loc.states_explored = states.data();
@@ -342,7 +408,205 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   return products_rc;  // (SHK_OK, or the record capacities' SHK_ERR_BAD_ARG with everything per gene complete)
 }
 
+// shk_pcr_run_depths: pcr_run_impl's stages for reads = NONE over the virtual genes v = j · ng + g (gene g
+// at depths[j]) — each stage called once for the virtual genes still alive — and every figure to outs[j]'s slot g.
+int pcr_run_depths_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, const uint32_t *depths,
+                        uint32_t D, shk_pcr_run_out *outs) {
+  using ull = unsigned long long;
+  // ---- everything that is refused, before the device is touched ----
+  SHK_TRY(depth_call_begin(c, "shk_pcr_run_depths", depths, D, true));
+  for (uint32_t j = 0; j < D; ++j)
+    if (!outs[j].status || !outs[j].records.record_offsets) return SHK_ERR_BAD_ARG;
+  if ((uint64_t)ng * D > SHK_PCR_MAX_GENES)
+    return fail(c, SHK_ERR_BAD_ARG, "n_genes %u x n_depths %u above SHK_PCR_MAX_GENES (%u)", ng, D, (unsigned)SHK_PCR_MAX_GENES);
+  for (uint32_t j = 0; j < D; ++j) pcr_out_clear(&outs[j], ng);
+  if (p->reads != SHK_PCR_READS_NONE) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run_depths: a depth sweep takes no reads");
+  std::vector<shk_primer> primers;
+  std::vector<uint32_t> min_count;
+  uint64_t primer_cap = 0;
+  SHK_TRY(pcr_genes_check(c, genes, ng, p, &primers, &min_count, &primer_cap));
+  if (ng == 0) return SHK_OK;
+  const uint32_t nv = ng * D;
+  auto out_of = [&](uint32_t v) -> shk_pcr_run_out & { return outs[v / ng]; };
+
+  // ---- step 2: the primer k-mers of every (gene, depth) in one fused table pass: slot 2v + direction ----
+  primer_cap *= D;
+  std::vector<uint64_t> pk(std::max<uint64_t>(primer_cap, 1)), poff(2 * (size_t)nv + 1, 0);
+  std::vector<uint32_t> pc(pk.size());
+  std::vector<uint8_t> plev(pk.size());
+  SHK_TRY(shk_primer_kmers_depths(c, primers.data(), 2 * ng, depths, D, pk.data(), pc.data(), plev.data(), primer_cap, poff.data(), nullptr));
+  std::vector<uint64_t> budget(D, p->max_num_nodes);
+  if (!p->max_num_nodes) {  // main.rs:147-165 on the bases of the chunks below the depth
+    std::vector<uint64_t> cb(c->n_lanes);
+    SHK_TRY(shk_chunk_bases(c, cb.data()));
+    uint64_t sum = 0;
+    for (uint32_t j = 0, l = 0; j < D; ++j) {
+      for (; l < depths[j]; ++l) sum += cb[l];
+      budget[j] = shk_pcr_node_budget(sum);
+    }
+  }
+  std::vector<uint32_t> status(nv, SHK_PCR_NO_PATH), alive;  // alive: both sets found
+  for (uint32_t v = 0; v < nv; ++v) {
+    shk_pcr_run_out &o = out_of(v);
+    const uint32_t g = v % ng;
+    const uint64_t nf = poff[2 * v + 1] - poff[2 * v], nr = poff[2 * v + 2] - poff[2 * v + 1];
+    const uint32_t mf = nf ? *std::max_element(pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 1]) : 0;
+    const uint32_t mr = nr ? *std::max_element(pc.begin() + poff[2 * v + 1], pc.begin() + poff[2 * v + 2]) : 0;
+    if (o.n_fwd_kmers) o.n_fwd_kmers[g] = (uint32_t)nf;
+    if (o.n_rev_kmers) o.n_rev_kmers[g] = (uint32_t)nr;
+    if (o.max_fwd_count) o.max_fwd_count[g] = mf;
+    if (o.max_rev_count) o.max_rev_count[g] = mr;
+    if (!nf || !nr) {
+      status[v] = !nf && !nr ? SHK_PCR_NO_PRIMERS : !nf ? SHK_PCR_NO_FORWARD : SHK_PCR_NO_REVERSE;
+      continue;
+    }
+    if (o.median_primer_count)
+      o.median_primer_count[g] = std::min(pcr_median_count(pc.data() + poff[2 * v], nf), pcr_median_count(pc.data() + poff[2 * v + 1], nr));
+    if (o.low_primer_counts) o.low_primer_counts[g] = mf < 5 || mr < 5;
+    alive.push_back(v);
+  }
+  const uint32_t na = (uint32_t)alive.size();
+
+  // ---- step 4: the extension of the alive pairs, each at its depth ----
+  PcrExtended X(na);
+  const std::vector<uint64_t> &xnoff = X.noff, &xeoff = X.eoff;
+  const std::vector<uint32_t> &xfound = X.found, &xthr = X.thr, &xsteps = X.steps;
+  std::vector<uint32_t> found;  // positions in alive
+  if (na) {
+    std::vector<uint64_t> ak, aoff(2 * (size_t)na + 1, 0);
+    std::vector<uint32_t> ac, adepth(na);
+    std::vector<shk_pcr_extend_params> xp(na);
+    for (uint32_t a = 0; a < na; ++a) {
+      const uint32_t v = alive[a], g = v % ng;
+      ak.insert(ak.end(), pk.begin() + poff[2 * v], pk.begin() + poff[2 * v + 2]);
+      ac.insert(ac.end(), pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 2]);
+      aoff[2 * a + 1] = aoff[2 * a] + (poff[2 * v + 1] - poff[2 * v]);
+      aoff[2 * a + 2] = aoff[2 * a] + (poff[2 * v + 2] - poff[2 * v]);
+      xp[a] = shk_pcr_extend_params{min_count[g], p->min_kmer_count, genes[g].high_coverage_ratio, budget[v / ng], 1u, 0u};
+      adepth[a] = depths[v / ng];
+    }
+    SHK_TRY(pcr_extend_stage(c, ak, ac, aoff, na, xp, adepth.data(), &X));
+    for (uint32_t a = 0; a < na; ++a) {
+      const uint32_t v = alive[a], g = v % ng;
+      shk_pcr_run_out &o = out_of(v);
+      const uint64_t nn = xnoff[a + 1] - xnoff[a];
+      if (o.threshold_used) o.threshold_used[g] = xthr[a];
+      if (o.steps_run) o.steps_run[g] = xsteps[a];
+      if (o.found_path) o.found_path[g] = xfound[a];
+      if (o.n_nodes) o.n_nodes[g] = nn;
+      if (o.n_edges) o.n_edges[g] = xeoff[a + 1] - xeoff[a];
+      status[v] = nn >= budget[v / ng] ? SHK_PCR_NODE_BUDGET : SHK_PCR_NO_PATH;
+      if (xfound[a]) found.push_back(a);
+    }
+  }
+  const uint32_t nf = (uint32_t)found.size();
+
+  // ---- step 6, for the pairs with a path: one prune, one products call (no reads: no threading) ----
+  int short_rc = SHK_OK;
+  if (nf) {
+    std::vector<uint32_t> fgene(nf);  // the gene of every pair with a path
+    std::vector<double> tip(nf);
+    for (uint32_t f = 0; f < nf; ++f) fgene[f] = alive[found[f]] % ng, tip[f] = genes[fgene[f]].tip_coverage_fraction;
+    PcrPruned Q;
+    SHK_TRY(pcr_prune_stage(c, X, found, tip, &Q));
+    const std::vector<uint64_t> &qnoff = Q.noff, &qeoff = Q.eoff;
+    shk_pcr_graphs G{};
+    G.n_genes = nf;
+    G.node_sub_kmers = Q.sub.data(), G.node_flags = Q.flags.data(), G.node_offsets = Q.noff.data();
+    G.edge_src = Q.es.data(), G.edge_tgt = Q.et.data(), G.edge_counts = Q.ec.data(), G.coverage_ratio = Q.ratio.data(), G.edge_offsets = Q.eoff.data();
+    std::vector<shk_pcr_paths_params> path_p;
+    std::vector<uint32_t> dedup_t;
+    pcr_products_params(genes, fgene, &path_p, &dedup_t);
+    // the records of all pairs into arrays of this call's (sized by a second call when the first guess was short) …
+    std::vector<uint64_t> roff(nf + 1, 0), paths_found(nf, 0), generated(nf, 0), states(nf, 0), seq_off, path_nodes, cmin, cmax;
+    std::vector<uint8_t> seqs;
+    std::vector<uint32_t> start_node;
+    std::vector<double> cmean, cmedian, score, fields;
+    shk_pcr_records loc{};
+    uint64_t rcap = 64ull * nf, scap = 1ull << 20;
+    for (int attempt = 0;; ++attempt) {
+      seq_off.assign(rcap + 1, 0), seqs.resize(std::max<uint64_t>(scap, 1)), start_node.resize(std::max<uint64_t>(rcap, 1));
+      path_nodes.resize(start_node.size()), cmin.resize(start_node.size()), cmax.resize(start_node.size());
+      cmean.resize(start_node.size()), cmedian.resize(start_node.size()), score.resize(start_node.size());
+      fields.resize(start_node.size() * SHK_PCR_SCORE_FIELDS);
+      loc = shk_pcr_records{};
+      loc.record_offsets = roff.data(), loc.seq_offsets = seq_off.data(), loc.seqs = seqs.data(), loc.record_cap = rcap, loc.seq_cap = scap;
+      loc.start_node = start_node.data(), loc.path_nodes = path_nodes.data(), loc.count_mean = cmean.data(), loc.count_median = cmedian.data();
+      loc.count_min = cmin.data(), loc.count_max = cmax.data(), loc.score = score.data(), loc.score_fields = fields.data();
+      loc.paths_found = paths_found.data(), loc.generated = generated.data(), loc.states_explored = states.data();
+      const int rc = shk_pcr_products_panel(c, &G, path_p.data(), dedup_t.data(), &loc, nullptr, nullptr);
+      if (rc == SHK_ERR_BAD_ARG && attempt == 0 && (loc.n_records > rcap || loc.n_seq_bytes > scap)) {
+        rcap = std::max(rcap, (uint64_t)loc.n_records), scap = std::max(scap, (uint64_t)loc.n_seq_bytes);
+        continue;
+      }
+      SHK_TRY(rc);
+      break;
+    }
+    // … and from there each depth's into its outs[j], under that one's capacities: found is ascending in v, so a
+    // depth's pairs are a run [f0, f1) of it and their records a run of the records
+    for (uint32_t j = 0, f0 = 0; j < D; ++j) {
+      uint32_t f1 = f0;
+      while (f1 < nf && alive[found[f1]] / ng == j) ++f1;
+      shk_pcr_run_out &o = outs[j];
+      shk_pcr_records &R = o.records;
+      for (uint32_t f = f0; f < f1; ++f) {
+        const uint32_t v = alive[found[f]], g = v % ng;
+        R.record_offsets[g + 1] = roff[f + 1] - roff[f];  // (lengths; summed below)
+        if (R.paths_found) R.paths_found[g] = paths_found[f];
+        if (R.generated) R.generated[g] = generated[f];
+        if (R.states_explored) R.states_explored[g] = states[f];
+        if (o.n_pruned_nodes) o.n_pruned_nodes[g] = qnoff[f + 1] - qnoff[f];
+        if (o.n_pruned_edges) o.n_pruned_edges[g] = qeoff[f + 1] - qeoff[f];
+        if (generated[f]) status[v] = SHK_PCR_SUCCESS;
+      }
+      for (uint32_t g = 0; g < ng; ++g) R.record_offsets[g + 1] += R.record_offsets[g];
+      const uint64_t r0 = roff[f0], nr = roff[f1] - r0, b0 = seq_off[r0], nb = seq_off[roff[f1]] - b0;
+      R.n_records = nr, R.n_seq_bytes = nb;
+      f0 = f1;
+      if (nr > R.record_cap || (R.seqs && nb > R.seq_cap)) {  // pcr_records_store's condition and text
+        if (short_rc == SHK_OK)
+          short_rc = fail(c, SHK_ERR_BAD_ARG, "%llu records of %llu bases do not fit record_cap %llu / seq_cap %llu", (ull)nr, (ull)nb,
+                          (ull)R.record_cap, (ull)R.seq_cap);
+        continue;
+      }
+      if (R.seq_offsets) R.seq_offsets[0] = 0;
+      if (R.seqs && nb) memcpy(R.seqs, seqs.data() + b0, nb);
+      for (uint64_t i = 0; i < nr; ++i) {
+        if (R.seq_offsets) R.seq_offsets[i + 1] = seq_off[r0 + i + 1] - b0;
+        if (R.start_node) R.start_node[i] = start_node[r0 + i];
+        if (R.path_nodes) R.path_nodes[i] = path_nodes[r0 + i];
+        if (R.count_mean) R.count_mean[i] = cmean[r0 + i];
+        if (R.count_median) R.count_median[i] = cmedian[r0 + i];
+        if (R.count_min) R.count_min[i] = cmin[r0 + i];
+        if (R.count_max) R.count_max[i] = cmax[r0 + i];
+        if (R.score) R.score[i] = score[r0 + i];
+        if (R.score_fields)
+          std::copy(fields.begin() + SHK_PCR_SCORE_FIELDS * (r0 + i), fields.begin() + SHK_PCR_SCORE_FIELDS * (r0 + i + 1),
+                    R.score_fields + SHK_PCR_SCORE_FIELDS * i);
+      }
+    }
+  }
+  for (uint32_t v = 0; v < nv; ++v) out_of(v).status[v % ng] = status[v];
+  if (getenv("SHK_TRACE"))
+    for (uint32_t v = 0; v < nv; ++v)
+      fprintf(stderr, "[shk] pcr_run_depths: depth %u gene %u '%s': %s, primer k-mers %llu + %llu\n", depths[v / ng], v % ng,
+              genes[v % ng].gene_name, status[v] == SHK_PCR_SUCCESS ? "success" : shk_pcr_failure_reason(status[v]),
+              (ull)(poff[2 * v + 1] - poff[2 * v]), (ull)(poff[2 * v + 2] - poff[2 * v + 1]));
+  return short_rc;  // (SHK_OK, or the record capacities' SHK_ERR_BAD_ARG with every outs[j] complete)
+}
+
 }  // namespace
+
+extern "C" int shk_pcr_run_depths(shk_ctx *c, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params,
+                                  const uint32_t *depths, uint32_t n_depths, shk_pcr_run_out *outs) {
+  SHK_TRY(xs_closed(c));
+  if (!c || !params || !outs || (n_genes && !genes)) return SHK_ERR_BAD_ARG;
+  try {
+    return pcr_run_depths_impl(c, genes, n_genes, params, depths, n_depths, outs);
+  } catch (...) {  // no exception leaves the C ABI
+    return fail(c, SHK_ERR_NOMEM, "shk_pcr_run_depths: out of host memory");
+  }
+}
 
 extern "C" int shk_pcr_run(shk_ctx *c, const shk_pcr_gene *genes, uint32_t n_genes, const shk_pcr_run_params *params, shk_pcr_run_out *out) {
   SHK_TRY(xs_closed(c));

@@ -73,6 +73,7 @@ int compact_owners_launch(shk_ctx *c, uint32_t n_owners, const uint64_t *h_off, 
 struct NbTableArg {
   TableRef one{};
   NbShards shards{nullptr, 0};
+  bool depths = false;  // every job's probe stops at its NbRef::lanes (the *_depth kernels; one table only)
   bool sharded() const { return shards.dir != nullptr; }
 };
 
@@ -82,7 +83,12 @@ struct NbTableArg {
 void nb_launch(shk_ctx *c, const NbTableArg &tb, const NbRef *drefs, NbCtl *dctl, uint32_t n_jobs, const NbRef *wide, const NbCtl *h) {
   ScopedTimer t(c, SHK_K_EXTEND);
   const dim3 grid(wide ? (uint32_t)((h->cur_n * 4 + WG - 1) / WG) : n_jobs), block(wide ? WG : NB_WG);
-  if (wide) {
+  if (tb.depths) {
+    if (wide)
+      hipLaunchKernelGGL(k_nb_wide_depth, grid, block, 0, c->stream, tb.one, *wide, dctl, h->cur_sel, (uint64_t)h->cur_n);
+    else
+      hipLaunchKernelGGL(k_nb_narrow_panel_depth, grid, block, 0, c->stream, tb.one, drefs, dctl);
+  } else if (wide) {
     if (tb.sharded())
       hipLaunchKernelGGL(k_nb_wide<true>, grid, block, 0, c->stream, tb.shards, *wide, dctl, h->cur_sel, (uint64_t)h->cur_n);
     else
@@ -198,7 +204,8 @@ void nb_sorted_out(const uint64_t *hk, const uint32_t *hc, uint64_t nk, uint64_t
 // g: every share is settled on its own device and its stream drained, the directory of their tables goes up with the
 // call's one upload, and the job logic runs as it is on c — its scratch, stream and timing slots; *who: the share whose
 // error text is the call's.
-int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
+// job_lanes (or nullptr): job j reads the table at depth job_lanes[j] (g == nullptr then).
+int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, const uint32_t *job_lanes, uint32_t max_levels,
                   const uint64_t *caps, const uint64_t *fringe_caps, const uint64_t *out_at, const uint64_t *fr_at, uint64_t *kmers,
                   uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
                   uint32_t *levels_done) {
@@ -269,6 +276,7 @@ int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint
     nb.min_count = std::max(min_counts[j], 1u);
     nb.max_levels = max_levels;
     nb.k = (int)k;
+    nb.lanes = job_lanes ? job_lanes[j] : 0u;
     hctl[j].cur_n = seeds[j].size();
     hctl[j].status = seeds[j].empty() ? NB_COMPLETE : seeds[j].size() > NB_NARROW ? NB_WIDE : NB_RUN;
     hstart[j] = at;
@@ -280,6 +288,7 @@ int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint
   hstart[n_jobs] = at;
   NbTableArg tb;
   tb.one = c->tb;
+  tb.depths = job_lanes != nullptr;
   if (g) {
     std::copy(shares.begin(), shares.end(), (TableRef *)(up.data() + (o_dir - o_refs)));
     uint32_t owner_bits = 0;
@@ -350,13 +359,13 @@ int nb_panel_run(shk_ctx *c, shk_group *g, uint32_t *who, const std::vector<uint
   return SHK_OK;
 }
 
-int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, uint32_t max_levels,
+int nb_panel_core(shk_ctx *c, const std::vector<uint64_t> *seeds, uint32_t n_jobs, const uint32_t *min_counts, const uint32_t *job_lanes, uint32_t max_levels,
                   const uint64_t *caps, const uint64_t *fringe_caps, const uint64_t *out_at, const uint64_t *fr_at, uint64_t *kmers,
                   uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe,
                   uint32_t *levels_done) {
   shk_group *g = c->group;
   uint32_t who = 0;
-  const int rc = nb_panel_run(g ? g->ctx[0] : c, g, &who, seeds, n_jobs, min_counts, max_levels, caps, fringe_caps, out_at, fr_at, kmers, counts,
+  const int rc = nb_panel_run(g ? g->ctx[0] : c, g, &who, seeds, n_jobs, min_counts, job_lanes, max_levels, caps, fringe_caps, out_at, fr_at, kmers, counts,
                               n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
   return rc == SHK_OK || !g ? rc : group_fail(c, g, rc, who);
 }
@@ -368,6 +377,24 @@ int graph_call_begin(shk_ctx *c, const char *name) {
   if (c->group) return group_graph_begin(c);
   if (c->n_owners > 1)
     return fail(c, SHK_ERR_STATE, "%s needs the whole table on one device: this context is an owner share (n_owners > 1)", name);
+  return SHK_OK;
+}
+
+// How the depth calls refuse, before the device is touched: a multi-device context (whatever its flags)
+// and an owner share, then a depth that is none — 0 or above the context's lanes; a list: empty, longer than
+// SHK_PCR_MAX_DEPTHS or not strictly ascending.
+int depth_call_begin(shk_ctx *c, const char *name, const uint32_t *depths, uint32_t n, bool list) {
+  if (c->group) return fail(c, SHK_ERR_STATE, "%s: no depths on a multi-device context (n_devices > 1)", name);
+  if (c->n_owners > 1) return fail(c, SHK_ERR_STATE, "%s: no depths on an owner share (n_owners > 1)", name);
+  if (list && (n == 0 || n > SHK_PCR_MAX_DEPTHS))
+    return fail(c, SHK_ERR_BAD_ARG, "%s: n_depths %u is not 1..%u", name, n, (unsigned)SHK_PCR_MAX_DEPTHS);
+  if (n && !depths) return SHK_ERR_BAD_ARG;
+  for (uint32_t j = 0; j < n; ++j) {
+    if (depths[j] == 0 || depths[j] > c->n_lanes)
+      return fail(c, SHK_ERR_BAD_ARG, "%s: depth %u is not 1..%u (n_chunks)", name, depths[j], c->n_lanes);
+    if (list && j && depths[j] <= depths[j - 1])
+      return fail(c, SHK_ERR_BAD_ARG, "%s: depths are not strictly ascending (%u after %u)", name, depths[j], depths[j - 1]);
+  }
   return SHK_OK;
 }
 
@@ -429,6 +456,9 @@ int shk_export_table(shk_ctx *c, uint64_t *kmers, uint32_t *counts, uint64_t cap
   return fetch_appended(c, dn, dk, dc, cap, kmers, counts, n_out);
 }
 
+// shk_lookup on one device; lanes != 0: shk_lookup_depth at that depth.
+static int lookup_one(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical, uint32_t lanes);
+
 int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical) {
   SHK_TRY(xs_closed(c));
   if (c && c->group) {  // exactly one share owns a k-mer; the others answer 0
@@ -442,6 +472,17 @@ int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, 
     return SHK_OK;
   }
   if (!c) return SHK_ERR_BAD_ARG;
+  return lookup_one(c, kmers, counts, n, canonical, 0);
+}
+
+int shk_lookup_depth(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical, uint32_t depth) {
+  SHK_TRY(xs_closed(c));
+  if (!c) return SHK_ERR_BAD_ARG;
+  SHK_TRY(depth_call_begin(c, "shk_lookup_depth", &depth, 1, false));
+  return lookup_one(c, kmers, counts, n, canonical, depth);
+}
+
+static int lookup_one(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, int canonical, uint32_t lanes) {
   if (n == 0) return SHK_OK;
   SHK_TRY(table_read_begin(c));
   Scratch m{c->misc};
@@ -452,8 +493,11 @@ int shk_lookup(shk_ctx *c, const uint64_t *kmers, uint32_t *counts, uint64_t n, 
   HIPC(c, hipMemcpyAsync(dk, kmers, n * 8, hipMemcpyHostToDevice, c->stream));
   {
     ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_lookup, dim3((uint32_t)((n + WG - 1) / WG)), dim3(WG), 0, c->stream, c->tb, dk, dc,
-                       n, canonical, (int)c->cfg.k);
+    const dim3 grid((uint32_t)((n + WG - 1) / WG));
+    if (lanes)
+      hipLaunchKernelGGL(k_lookup_depth, grid, dim3(WG), 0, c->stream, c->tb, dk, dc, n, canonical, (int)c->cfg.k, lanes);
+    else
+      hipLaunchKernelGGL(k_lookup, grid, dim3(WG), 0, c->stream, c->tb, dk, dc, n, canonical, (int)c->cfg.k);
   }
   HIPC(c, hipMemcpyAsync(counts, dc, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
@@ -476,7 +520,7 @@ int shk_neighborhood(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, uin
   SHK_TRY(nb_level0(c, "", nodes, dirs, n_seeds, k, fringe_cap, &seeds));
   // one job of the panel's core: its outputs at the start of the caller's arrays
   const uint64_t at0 = 0;
-  return nb_panel_core(c, &seeds, 1, &min_count, max_levels, &cap, &fringe_cap, &at0, &at0, kmers, counts, n_out, fringe_nodes,
+  return nb_panel_core(c, &seeds, 1, &min_count, nullptr, max_levels, &cap, &fringe_cap, &at0, &at0, kmers, counts, n_out, fringe_nodes,
                        fringe_dirs, n_fringe, levels_done);
 }
 
@@ -510,13 +554,17 @@ int shk_pcr_extend(shk_ctx *c, const uint64_t *fwd_kmers, const uint32_t *fwd_co
   return rc_out;
 }
 
-int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
-                           const uint32_t *min_counts, uint32_t max_levels, const uint64_t *caps, const uint64_t *fringe_caps,
-                           uint64_t *kmers, uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs,
-                           uint64_t *n_fringe, uint32_t *levels_done) {
+// shk_neighborhood_panel, and with job_depths shk_neighborhood_panel_depths (the same call but for the depth check and
+// the bounded probe).
+static int nb_panel_call(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
+                         const uint32_t *min_counts, const uint32_t *job_depths, uint32_t max_levels, const uint64_t *caps,
+                         const uint64_t *fringe_caps, uint64_t *kmers, uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes,
+                         uint8_t *fringe_dirs, uint64_t *n_fringe, uint32_t *levels_done) {
   SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (!c) return SHK_ERR_BAD_ARG;
+  // (at most SHK_PCR_MAX_GENES depths are looked at: a longer list is refused below, by the n_jobs check, whatever its rest holds)
+  if (job_depths) SHK_TRY(depth_call_begin(c, "shk_neighborhood_panel_depths", job_depths, std::min<uint32_t>(n_jobs, SHK_PCR_MAX_GENES), false));
   SHK_TRY(graph_call_begin(c, "shk_neighborhood_panel"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_neighborhood_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
@@ -540,18 +588,39 @@ int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dir
     fr_at[j + 1] = fr_at[j] + fringe_caps[j];
   }
   if ((out_at[n_jobs] && (!kmers || !counts)) || (fr_at[n_jobs] && (!fringe_nodes || !fringe_dirs))) return SHK_ERR_BAD_ARG;
-  return nb_panel_core(c, seeds.data(), n_jobs, min_counts, max_levels, caps, fringe_caps, out_at.data(), fr_at.data(), kmers, counts,
-                       n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
+  return nb_panel_core(c, seeds.data(), n_jobs, min_counts, job_depths, max_levels, caps, fringe_caps, out_at.data(), fr_at.data(), kmers,
+                       counts, n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
 }
 
-int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
-                         uint32_t n_genes, const shk_pcr_extend_params *params, uint64_t *node_sub_kmers, uint8_t *node_flags,
-                         uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts,
-                         uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path, uint32_t *threshold_used,
-                         uint32_t *steps_run) {
+int shk_neighborhood_panel(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
+                           const uint32_t *min_counts, uint32_t max_levels, const uint64_t *caps, const uint64_t *fringe_caps,
+                           uint64_t *kmers, uint32_t *counts, uint64_t *n_out, uint64_t *fringe_nodes, uint8_t *fringe_dirs,
+                           uint64_t *n_fringe, uint32_t *levels_done) {
+  return nb_panel_call(c, nodes, dirs, seed_offsets, n_jobs, min_counts, nullptr, max_levels, caps, fringe_caps, kmers, counts, n_out,
+                       fringe_nodes, fringe_dirs, n_fringe, levels_done);
+}
+
+int shk_neighborhood_panel_depths(shk_ctx *c, const uint64_t *nodes, const uint8_t *dirs, const uint64_t *seed_offsets, uint32_t n_jobs,
+                                  const uint32_t *min_counts, const uint32_t *job_depths, uint32_t max_levels, const uint64_t *caps,
+                                  const uint64_t *fringe_caps, uint64_t *kmers, uint32_t *counts, uint64_t *n_out,
+                                  uint64_t *fringe_nodes, uint8_t *fringe_dirs, uint64_t *n_fringe, uint32_t *levels_done) {
+  if (c && n_jobs && !job_depths) return SHK_ERR_BAD_ARG;
+  static const uint32_t none = 0;  // (n_jobs == 0: the plain call's answer after the depth call's state checks)
+  return nb_panel_call(c, nodes, dirs, seed_offsets, n_jobs, min_counts, job_depths ? job_depths : &none, max_levels, caps, fringe_caps,
+                       kmers, counts, n_out, fringe_nodes, fringe_dirs, n_fringe, levels_done);
+}
+
+// shk_pcr_extend_panel, and with gene_depths shk_pcr_extend_panel_depths.
+static int pcr_extend_panel_call(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
+                                 uint32_t n_genes, const shk_pcr_extend_params *params, const uint32_t *gene_depths,
+                                 uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t *node_offsets, uint64_t node_cap,
+                                 uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t *edge_offsets, uint64_t edge_cap,
+                                 uint32_t *found_path, uint32_t *threshold_used, uint32_t *steps_run) {
   SHK_TRY(xs_closed(c));
   using ull = unsigned long long;
   if (!c || !node_offsets || !edge_offsets) return SHK_ERR_BAD_ARG;
+  // (as above: the n_genes check below refuses a list longer than SHK_PCR_MAX_GENES)
+  if (gene_depths) SHK_TRY(depth_call_begin(c, "shk_pcr_extend_panel_depths", gene_depths, std::min<uint32_t>(n_genes, SHK_PCR_MAX_GENES), false));
   SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
   const uint32_t k = c->cfg.k;
   if (k < 2) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_extend_panel needs k >= 2 (a node is a (k-1)-mer), got k=%u", k);
@@ -578,10 +647,32 @@ int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_
   }
   std::vector<PcrGraph> gs;
   std::string msg;
-  const int rc = pcr_extend_panel_run(c, k, primers.data(), n_genes, params, true, &gs, threshold_used, steps_run, &msg);
+  const int rc = pcr_extend_panel_run(c, k, primers.data(), n_genes, params, true, &gs, threshold_used, steps_run, &msg, gene_depths);
   if (rc != SHK_OK) return msg.empty() ? rc : fail(c, rc, "%s", msg.c_str());  // (else shk_neighborhood_panel's own text stands)
   return pcr_graphs_out(c, "panel", gs, node_sub_kmers, node_flags, node_offsets, node_cap, edge_src, edge_tgt, edge_counts, edge_offsets,
                         edge_cap, found_path);
+}
+
+int shk_pcr_extend_panel(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
+                         uint32_t n_genes, const shk_pcr_extend_params *params, uint64_t *node_sub_kmers, uint8_t *node_flags,
+                         uint64_t *node_offsets, uint64_t node_cap, uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts,
+                         uint64_t *edge_offsets, uint64_t edge_cap, uint32_t *found_path, uint32_t *threshold_used,
+                         uint32_t *steps_run) {
+  return pcr_extend_panel_call(c, primer_kmers, primer_counts, primer_offsets, n_genes, params, nullptr, node_sub_kmers, node_flags,
+                               node_offsets, node_cap, edge_src, edge_tgt, edge_counts, edge_offsets, edge_cap, found_path, threshold_used,
+                               steps_run);
+}
+
+int shk_pcr_extend_panel_depths(shk_ctx *c, const uint64_t *primer_kmers, const uint32_t *primer_counts, const uint64_t *primer_offsets,
+                                uint32_t n_genes, const shk_pcr_extend_params *params, const uint32_t *gene_depths,
+                                uint64_t *node_sub_kmers, uint8_t *node_flags, uint64_t *node_offsets, uint64_t node_cap,
+                                uint32_t *edge_src, uint32_t *edge_tgt, uint32_t *edge_counts, uint64_t *edge_offsets, uint64_t edge_cap,
+                                uint32_t *found_path, uint32_t *threshold_used, uint32_t *steps_run) {
+  if (c && n_genes && !gene_depths) return SHK_ERR_BAD_ARG;
+  static const uint32_t none = 0;  // (n_genes == 0: the plain call's answer after the depth call's state checks)
+  return pcr_extend_panel_call(c, primer_kmers, primer_counts, primer_offsets, n_genes, params, gene_depths ? gene_depths : &none,
+                               node_sub_kmers, node_flags, node_offsets, node_cap, edge_src, edge_tgt, edge_counts, edge_offsets, edge_cap,
+                               found_path, threshold_used, steps_run);
 }
 
 int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint32_t oligo_len,
@@ -681,6 +772,106 @@ int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, st
   return SHK_OK;
 }
 
+// Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
+// sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
+// here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
+// and two entries never yield the same k-mer because the table holds canonical k-mers only — so the reference's
+// "already found at a lower level" filter (primers.rs:398-403) never drops anything.
+// all: the records, tagged with the searched primer j; hits: [j][SHK_PRIMER_LEVELS]; searched primer j is result slot
+// who[j] (ascending) of n_slots, max_kmers[j] its cap.
+void primer_select(const std::vector<PrimerRec> &all, const std::vector<uint64_t> &hits, const std::vector<uint32_t> &who,
+                   const std::vector<uint64_t> &max_kmers, uint32_t n_slots, uint64_t *kmers, uint32_t *counts, uint8_t *levels, uint64_t *offsets,
+                   uint64_t *level_hits) {
+  const uint32_t n = (uint32_t)who.size();
+  std::vector<uint64_t> first(n + 1, 0);
+  for (const PrimerRec &r : all) ++first[(r.tag >> 8) + 1];
+  for (uint32_t j = 0; j < n; ++j) first[j + 1] += first[j];
+  std::vector<PrimerRec> by(all.size());
+  {
+    std::vector<uint64_t> at(first.begin(), first.end() - 1);
+    for (const PrimerRec &r : all) by[at[r.tag >> 8]++] = r;
+  }
+  auto before = [](const PrimerRec &a, const PrimerRec &b) {
+    const uint32_t la = a.tag & 0xFF, lb = b.tag & 0xFF;
+    if (la != lb) return la < lb;
+    if (a.count != b.count) return a.count > b.count;
+    return a.kmer < b.kmer;
+  };
+  uint64_t o = 0;
+  uint32_t j = 0;
+  for (uint32_t i = 0; i < n_slots; ++i) {
+    offsets[i] = o;
+    if (j >= n || who[j] != i) continue;
+    PrimerRec *b = by.data() + first[j], *e = by.data() + first[j + 1];
+    const uint64_t take = std::min<uint64_t>(max_kmers[j], (uint64_t)(e - b));
+    std::partial_sort(b, b + take, e, before);
+    for (uint64_t t = 0; t < take; ++t, ++o) {
+      kmers[o] = b[t].kmer;
+      counts[o] = b[t].count;
+      levels[o] = (uint8_t)(b[t].tag & 0xFF);
+    }
+    if (level_hits) std::copy(hits.begin() + (size_t)j * SHK_PRIMER_LEVELS, hits.begin() + (size_t)(j + 1) * SHK_PRIMER_LEVELS,
+                              level_hits + (size_t)i * SHK_PRIMER_LEVELS);
+    ++j;
+  }
+  offsets[n_slots] = o;
+}
+
+// The fused pass of shk_primer_kmers_depths: k_primer_scan_depths over c's slots for the searched primers dev at the
+// depths dep; cut[j · n + p]: the highest level kept of primer p at depth j.  Records and hits come back for the
+// virtual primers j · n + p, as primer_pass returns them for its primers.
+int primer_pass_depths(shk_ctx *c, const std::vector<PrimerDev> &dev, const std::vector<uint32_t> &cut, const PrimerDepths &dep,
+                       uint64_t room, std::vector<PrimerRec> *recs, std::vector<uint64_t> *hits, uint64_t *n_total) {
+  SHK_TRY(table_read_begin(c));
+  const uint32_t n = (uint32_t)dev.size(), D = dep.n;
+  std::vector<PrimerDevD> devd(n);
+  uint32_t stride = 1;  // LDS counters per (primer, depth): levels 0..max cut
+  for (uint32_t p = 0; p < n; ++p) {
+    devd[p].p = dev[p];
+    devd[p].p.M = 0;
+    for (uint32_t j = 0; j < SHK_PCR_MAX_DEPTHS; ++j) {
+      const uint32_t m = j < D ? cut[(size_t)j * n + p] : 0u;
+      devd[p].cut[j] = (uint8_t)m;
+      devd[p].p.M = std::max(devd[p].p.M, m);
+    }
+    stride = std::max(stride, devd[p].p.M + 1);
+  }
+  // primers per launch group: their table and D × the counters in 48 KiB of LDS (three workgroups per CU)
+  const uint32_t per_primer = (uint32_t)sizeof(PrimerDevD) + 4 * stride * D;
+  const uint32_t per_launch = std::max(1u, (48u << 10) / per_primer);
+  const size_t n_hits = (size_t)D * n * SHK_PRIMER_LEVELS;
+  Scratch m{c->misc};
+  const size_t o_n = m.take<unsigned long long>(1), o_hits = m.take<unsigned long long>(n_hits);  // (adjacent)
+  const size_t o_prim = m.take<PrimerDevD>(n), o_rec = m.take<PrimerRec>(room);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n), *dhits = m.at<unsigned long long>(o_hits);
+  PrimerDevD *dprim = m.at<PrimerDevD>(o_prim);
+  PrimerRec *drec = m.at<PrimerRec>(o_rec);
+  HIPC(c, hipMemsetAsync(dn, 0, o_prim - o_n, c->stream));  // the record counter and the hits
+  HIPC(c, hipMemcpyAsync(dprim, devd.data(), (size_t)n * sizeof(PrimerDevD), hipMemcpyHostToDevice, c->stream));
+  const auto [s0, s1] = owned_slots(c);
+  for (uint32_t b = 0; b < n; b += per_launch) {
+    const uint32_t nb = std::min(per_launch, n - b);
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    hipLaunchKernelGGL(k_primer_scan_depths, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG), (size_t)nb * per_primer, c->stream,
+                       c->tb, s0, s1, (int)c->cfg.k, (const PrimerDevD *)(dprim + b), nb, b, n, stride, dep, drec, (uint64_t)room, dn,
+                       dhits);
+  }
+  HIPC(c, hipGetLastError());
+  unsigned long long nt = 0;
+  hits->assign(n_hits, 0);
+  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(hits->data(), dhits, n_hits * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps devd alive until its copy ran)
+  *n_total = nt;
+  recs->clear();
+  if (nt <= room && nt) {
+    recs->resize(nt);
+    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
+  }
+  return SHK_OK;
+}
+
 }  // namespace
 
 int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
@@ -763,43 +954,89 @@ int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, 
       all.insert(all.end(), recs.begin(), recs.end());
     }
   }
-  // Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
-  // sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
-  // here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
-  // and two entries never yield the same k-mer because the table holds canonical k-mers only — so the reference's
-  // "already found at a lower level" filter (primers.rs:398-403) never drops anything.
-  std::vector<uint64_t> first(n + 1, 0);
-  for (const PrimerRec &r : all) ++first[(r.tag >> 8) + 1];
-  for (uint32_t j = 0; j < n; ++j) first[j + 1] += first[j];
-  std::vector<PrimerRec> by(all.size());
-  {
-    std::vector<uint64_t> at(first.begin(), first.end() - 1);
-    for (const PrimerRec &r : all) by[at[r.tag >> 8]++] = r;
-  }
-  auto before = [](const PrimerRec &a, const PrimerRec &b) {
-    const uint32_t la = a.tag & 0xFF, lb = b.tag & 0xFF;
-    if (la != lb) return la < lb;
-    if (a.count != b.count) return a.count > b.count;
-    return a.kmer < b.kmer;
-  };
-  uint64_t o = 0;
-  uint32_t j = 0;
+  std::vector<uint64_t> max_kmers(n);
+  for (uint32_t j = 0; j < n; ++j) max_kmers[j] = plans[who[j]].max_kmers;
+  primer_select(all, hits, who, max_kmers, n_primers, kmers, counts, levels, offsets, level_hits);
+  return SHK_OK;
+}
+
+// shk_primer_kmers over the virtual primers j · n_primers + i (primer i at depths[j]): the same checks, one fused pass
+// (and, on an overflow of the candidate buffer, one rerun with a cut level per virtual primer), the same selection.
+int shk_primer_kmers_depths(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, const uint32_t *depths, uint32_t n_depths,
+                            uint64_t *kmers, uint32_t *counts, uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  SHK_TRY(xs_closed(c));
+  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
+  SHK_TRY(depth_call_begin(c, "shk_primer_kmers_depths", depths, n_depths, true));
+  const uint32_t D = n_depths;
+  if ((uint64_t)n_primers * D >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u at %u depths)", n_primers, D);
+  const uint32_t k = c->cfg.k;
+  std::vector<PrimerPlan> plans(n_primers);
+  std::string msg;
   for (uint32_t i = 0; i < n_primers; ++i) {
-    offsets[i] = o;
-    if (j >= n || who[j] != i) continue;
-    PrimerRec *b = by.data() + first[j], *e = by.data() + first[j + 1];
-    const uint64_t take = std::min<uint64_t>(plans[i].max_kmers, (uint64_t)(e - b));
-    std::partial_sort(b, b + take, e, before);
-    for (uint64_t t = 0; t < take; ++t, ++o) {
-      kmers[o] = b[t].kmer;
-      counts[o] = b[t].count;
-      levels[o] = (uint8_t)(b[t].tag & 0xFF);
-    }
-    if (level_hits) std::copy(hits.begin() + (size_t)j * SHK_PRIMER_LEVELS, hits.begin() + (size_t)(j + 1) * SHK_PRIMER_LEVELS,
-                              level_hits + (size_t)i * SHK_PRIMER_LEVELS);
-    ++j;
+    const int rc = primer_plan(&primers[i], k, &plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
   }
-  offsets[n_primers] = o;
+  for (uint32_t i = 0; i < n_primers; ++i) {
+    const int rc = primer_check_chars(plans[i], &msg);
+    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
+  }
+  uint64_t need = 0;
+  for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
+  need *= D;
+  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < n_depths x sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
+  if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
+  const uint32_t n_slots = n_primers * D;
+  if (level_hits) std::fill(level_hits, level_hits + (size_t)n_slots * SHK_PRIMER_LEVELS, 0ull);
+  std::vector<uint32_t> who1;  // searched primer p = primers[who1[p]]
+  std::vector<PrimerDev> dev;
+  for (uint32_t i = 0; i < n_primers; ++i)
+    if (plans[i].scanned()) {
+      const PrimerPlan &pl = plans[i];
+      who1.push_back(i);
+      // (a key whose count at the depth is 0 is not in that depth's table: the floor of 1)
+      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, std::max(pl.min_count, 1u), 0});
+    }
+  const uint32_t n = (uint32_t)dev.size();
+  std::vector<uint32_t> who((size_t)n * D);  // searched virtual primer j · n + p is result slot j · n_primers + who1[p]
+  for (uint32_t j = 0; j < D; ++j)
+    for (uint32_t p = 0; p < n; ++p) who[(size_t)j * n + p] = j * n_primers + who1[p];
+  std::vector<PrimerRec> all;
+  std::vector<uint64_t> hits((size_t)n * D * SHK_PRIMER_LEVELS, 0);
+  if (n) {
+    PrimerDepths dep{};
+    dep.n = D;
+    for (uint32_t j = 0; j < D; ++j) dep.d[j] = depths[j];
+    const uint64_t room = (uint64_t)std::max(env_int("SHK_PRIMER_CANDIDATES", 1 << 18), 1);
+    std::vector<uint32_t> cut((size_t)n * D);
+    for (uint32_t j = 0; j < D; ++j)
+      for (uint32_t p = 0; p < n; ++p) cut[(size_t)j * n + p] = dev[p].M;
+    uint64_t n_total = 0;
+    SHK_TRY(primer_pass_depths(c, dev, cut, dep, room, &all, &hits, &n_total));
+    if (n_total > room) {  // as shk_primer_kmers: the counts are complete, so every virtual primer's cut level is known
+      uint64_t exact = 0;
+      for (size_t v = 0; v < cut.size(); ++v) {
+        const uint64_t max_kmers = plans[who1[v % n]].max_kmers;
+        uint64_t acc = 0;
+        for (uint32_t m = 0; m <= dev[v % n].M; ++m) {
+          acc += hits[v * SHK_PRIMER_LEVELS + m];
+          if (acc >= max_kmers) {
+            cut[v] = m;
+            break;
+          }
+        }
+        for (uint32_t m = 0; m <= cut[v]; ++m) exact += hits[v * SHK_PRIMER_LEVELS + m];
+      }
+      std::vector<uint64_t> h2;
+      uint64_t n2 = 0;
+      SHK_TRY(primer_pass_depths(c, dev, cut, dep, exact, &all, &h2, &n2));
+      if (n2 != exact)
+        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu", (unsigned long long)n2,
+                    (unsigned long long)exact);
+    }
+  }
+  std::vector<uint64_t> max_kmers(who.size());
+  for (size_t v = 0; v < who.size(); ++v) max_kmers[v] = plans[who1[v % n]].max_kmers;
+  primer_select(all, hits, who, max_kmers, n_slots, kmers, counts, levels, offsets, level_hits);
   return SHK_OK;
 }
 

@@ -250,6 +250,7 @@ class _PcrDedupOut(C.Structure):
 PCR_SCORE_FIELDS = ("kmer_min_count", "coverage_cv", "max_coverage_ratio", "zero_support_edges", "median_unambiguous_support",
                     "edge_support_fraction")  # SHK_PCR_SCORE_FIELDS; NaN stands for None
 PCR_MAX_AMPLICONS = 20  # SHK_PCR_MAX_AMPLICONS = MAX_NUM_AMPLICONS (pcr/paths.rs:20)
+PCR_MAX_DEPTHS = 16  # SHK_PCR_MAX_DEPTHS: depths per depth-sweep call
 
 
 def _fmt_f64(x: float) -> str:
@@ -402,6 +403,46 @@ def _pcr_records_call(ng, call, retained=None):
     return res
 
 
+class _PcrRecordBuf:
+    """One shk_pcr_records with arrays of its own (ng genes, rcap records, scap sequence bytes): pcr_run_depths keeps one per
+    depth.  struct(): what the call takes; after it, take(struct) copies the needs back and products() reads the arrays."""
+
+    def __init__(self, ng: int, rcap: int, scap: int):
+        self.ng, self.rcap, self.scap = ng, rcap, scap
+        self.roff = np.zeros(ng + 1, dtype=np.uint64)
+        self.found, self.gen, self.states = (np.zeros(max(ng, 1), dtype=np.uint64) for _ in range(3))
+        n = max(rcap, 1)
+        self.soff = np.zeros(n + 1, dtype=np.uint64)
+        self.seqs = np.zeros(max(scap, 1), dtype=np.uint8)
+        self.start = np.zeros(n, dtype=np.uint32)
+        self.nodes, self.cmin, self.cmax = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        self.mean, self.med, self.score = (np.zeros(n, dtype=np.float64) for _ in range(3))
+        self.fields = np.zeros((n, len(PCR_SCORE_FIELDS)), dtype=np.float64)
+        self.n_records = self.n_seq_bytes = 0
+
+    def struct(self) -> "_PcrRecords":
+        return _PcrRecords(self.roff.ctypes.data, self.soff.ctypes.data, self.seqs.ctypes.data, self.rcap, self.scap, 0, 0,
+                           self.start.ctypes.data, self.nodes.ctypes.data, self.mean.ctypes.data, self.med.ctypes.data,
+                           self.cmin.ctypes.data, self.cmax.ctypes.data, self.score.ctypes.data, self.fields.ctypes.data,
+                           self.found.ctypes.data, self.gen.ctypes.data, self.states.ctypes.data)
+
+    def take(self, R):
+        self.n_records, self.n_seq_bytes = int(R.n_records), int(R.n_seq_bytes)
+
+    def short(self) -> bool:
+        return self.n_records > self.rcap or self.n_seq_bytes > self.scap
+
+    def products(self) -> list:
+        res = []
+        for g in range(self.ng):
+            a, b = int(self.roff[g]), int(self.roff[g + 1])
+            ss = [self.seqs[int(self.soff[r]):int(self.soff[r + 1])].tobytes().decode("ascii") for r in range(a, b)]
+            res.append(PcrProducts(ss, self.start[a:b].copy(), self.nodes[a:b].copy(), self.mean[a:b].copy(), self.med[a:b].copy(),
+                                   self.cmin[a:b].copy(), self.cmax[a:b].copy(), self.score[a:b].copy(), self.fields[a:b].copy(),
+                                   int(self.found[g]), int(self.gen[g]), int(self.states[g]), None))
+        return res
+
+
 def pcr_paths_panel(k: int, graphs, annotations=None, min_length=0, max_length=10000, max_dfs_states=100000, max_paths_per_pair=20,
                     max_node_visits=2) -> list:
     """resolve_bubbles, get_assembly_paths and generate_sequences_from_paths (pcr/bubble.rs, pcr/paths.rs:78-356) for
@@ -463,7 +504,8 @@ class _PcrGeneStat(C.Structure):
 
 class _PcrFileConfig(C.Structure):
     _fields_ = [("genes", C.POINTER(_PcrGene)), ("n_genes", C.c_uint32), ("min_kmer_count", C.c_uint32), ("read_threading", C.c_uint32),
-                ("dump", C.c_uint32), ("node_budget_global", C.c_uint64), ("context_flags", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+                ("dump", C.c_uint32), ("node_budget_global", C.c_uint64), ("context_flags", C.c_uint64), ("depths", C.c_void_p), ("n_depths", C.c_uint64),
+                ("reserved", C.c_uint64 * 1)]
 
 
 PCR_SUCCESS, PCR_NO_FORWARD, PCR_NO_REVERSE, PCR_NO_PRIMERS, PCR_NO_PATH, PCR_NODE_BUDGET = range(6)  # SHK_PCR_* (include/shk.h)
@@ -644,6 +686,8 @@ ABI_SYMBOLS = [
     "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
     "shk_pcr_run", "shk_write_fasta", "shk_write_stats_yaml_pcr", "shk_run_files_pcr",
     "shk_key_owner",
+    "shk_chunk_bases", "shk_lookup_depth", "shk_primer_kmers_depths", "shk_neighborhood_panel_depths", "shk_pcr_extend_panel_depths",
+    "shk_pcr_run_depths", "shk_pcr_check_depths", "shk_pcr_parse_depths", "shk_write_pcr_depths_tsv",
 ]
 
 _lib = None
@@ -680,6 +724,7 @@ FRONT_SYMBOLS = [
     "shk_packed_sizes", "shk_pack_reads",
     "shk_pcr_gene_defaults", "shk_pcr_parse_primers", "shk_pcr_validate_gene", "shk_pcr_validation_report", "shk_pcr_failure_reason",
     "shk_write_fasta", "shk_write_stats_yaml_pcr",
+    "shk_pcr_check_depths", "shk_pcr_parse_depths", "shk_write_pcr_depths_tsv",
 ]
 
 
@@ -715,6 +760,9 @@ def _type_front(L):
     L.shk_pcr_failure_reason.restype = C.c_char_p
     L.shk_write_fasta.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(_PcrGene), C.POINTER(_PcrRecords), u64, u64]
     L.shk_write_stats_yaml_pcr.argtypes = [C.c_char_p, C.POINTER(_RunStats), C.POINTER(_PcrGeneStat), u32]
+    L.shk_pcr_check_depths.argtypes = [vp, u64, u32, C.c_char_p, C.c_size_t]
+    L.shk_pcr_parse_depths.argtypes = [C.c_char_p, u32, vp, u64, C.POINTER(u64), C.c_char_p, C.c_size_t]
+    L.shk_write_pcr_depths_tsv.argtypes = [C.c_char_p, vp, u64]
 
 
 _front = None
@@ -858,6 +906,12 @@ def load_library():
     L.shk_run_files.argtypes = [C.POINTER(_RunConfig), C.POINTER(_RunStats)]
     L.shk_run_files_pcr.argtypes = [C.POINTER(_RunConfig), C.POINTER(_PcrFileConfig), C.POINTER(_RunStats), C.POINTER(_PcrRunOut)]
     L.shk_pcr_run.argtypes = [vp, C.POINTER(_PcrGene), u32, C.POINTER(_PcrRunParams), C.POINTER(_PcrRunOut)]
+    L.shk_chunk_bases.argtypes = [vp, vp]
+    L.shk_lookup_depth.argtypes = [vp, vp, vp, u64, C.c_int, u32]
+    L.shk_primer_kmers_depths.argtypes = [vp, vp, u32, vp, u32, vp, vp, vp, u64, vp, vp]
+    L.shk_neighborhood_panel_depths.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.shk_pcr_extend_panel_depths.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp]
+    L.shk_pcr_run_depths.argtypes = [vp, C.POINTER(_PcrGene), u32, C.POINTER(_PcrRunParams), vp, u32, C.POINTER(_PcrRunOut)]
     for name in ABI_SYMBOLS:
         getattr(L, name)  # AttributeError here = the .so is stale
     _lib = L
@@ -1092,12 +1146,24 @@ class KmerEngine:
         o = np.argsort(keys, kind="stable")
         return keys[o], cnts[o]
 
-    def lookup(self, kmers, canonical: bool = False) -> np.ndarray:
-        """get_count (counting.rs:224-226) / get_canonical_count (:205-209)."""
+    def chunk_bases(self) -> np.ndarray:
+        """Chunk::n_bases of every chunk (u64[n_chunks]; counters()["n_bases_ingested"] is their sum): what a depth's
+        node budget is computed from (pcr_run_depths)."""
+        out = np.zeros(self.counters()["n_chunks"], dtype=np.uint64)
+        self._check(self._L.shk_chunk_bases(self._h, out.ctypes.data))
+        return out
+
+    def lookup(self, kmers, canonical: bool = False, depth: int | None = None) -> np.ndarray:
+        """get_count (counting.rs:224-226) / get_canonical_count (:205-209).  depth d (1..n_chunks): in the table of
+        chunks 0..d-1 only (shk_lookup_depth); None: the merged table."""
         kmers = np.ascontiguousarray(np.atleast_1d(kmers), dtype=np.uint64)
         out = np.zeros(len(kmers), dtype=np.uint32)
-        self._check(self._L.shk_lookup(self._h, kmers.ctypes.data, out.ctypes.data, len(kmers),
-                                       1 if canonical else 0))
+        if depth is None:
+            self._check(self._L.shk_lookup(self._h, kmers.ctypes.data, out.ctypes.data, len(kmers),
+                                           1 if canonical else 0))
+        else:
+            self._check(self._L.shk_lookup_depth(self._h, kmers.ctypes.data, out.ctypes.data, len(kmers),
+                                                 1 if canonical else 0, depth))
         return out
 
     def find_oligos(self, oligos, oligo_len: int, min_count: int = 1):
@@ -1135,6 +1201,31 @@ class KmerEngine:
         for i in range(n):
             a, b = int(offsets[i]), int(offsets[i + 1])
             out.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[i].copy()))
+        return out
+
+    def primer_kmers_depths(self, primers, depths) -> list:
+        """primer_kmers at every depth of `depths` (strictly ascending, at most PCR_MAX_DEPTHS) in one pass over the table
+        (shk_primer_kmers_depths) → per depth what primer_kmers returns on a context that got the chunks below it only."""
+        primers = list(primers)
+        dep = np.ascontiguousarray(np.atleast_1d(depths), dtype=np.uint32)
+        n, nd = len(primers), len(dep)
+        arr = (_Primer * max(n, 1))(*[p._c() for p in primers])
+        cap = nd * sum(p.max_kmers for p in primers)
+        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
+        counts = np.zeros(max(cap, 1), dtype=np.uint32)
+        levels = np.zeros(max(cap, 1), dtype=np.uint8)
+        offsets = np.zeros(n * nd + 1, dtype=np.uint64)
+        hits = np.zeros((max(n * nd, 1), PRIMER_LEVELS), dtype=np.uint64)
+        self._check(self._L.shk_primer_kmers_depths(self._h, C.cast(arr, C.c_void_p), n, dep.ctypes.data, nd, kmers.ctypes.data,
+                                                    counts.ctypes.data, levels.ctypes.data, cap, offsets.ctypes.data,
+                                                    hits.ctypes.data))
+        out = []
+        for j in range(nd):
+            block = []
+            for i in range(n):
+                a, b = int(offsets[j * n + i]), int(offsets[j * n + i + 1])
+                block.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[j * n + i].copy()))
+            out.append(block)
         return out
 
     def primer_pair_kmers(self, forward: str, reverse: str, **params):
@@ -1195,12 +1286,17 @@ class KmerEngine:
             return PcrGraph(sub[:n].copy(), flags[:n].copy(), es[:e].copy(), et[:e].copy(), ec[:e].copy(),
                             bool(found.value), int(thr.value), int(steps.value))
 
-    def neighborhood_panel(self, jobs, max_levels: int = 0) -> list:
+    def neighborhood_panel(self, jobs, max_levels: int = 0, depths=None) -> list:
         """shk_neighborhood_panel: the neighbourhoods of many independent seed sets in one call.  jobs: a sequence of
         (nodes, dirs, min_count) or (nodes, dirs, min_count, cap, fringe_cap) — the arguments of `neighborhood`, the
-        capacities 2^16 when left out; max_levels holds for all.  → per job the tuple `neighborhood` returns."""
+        capacities 2^16 when left out; max_levels holds for all.  → per job the tuple `neighborhood` returns.
+        depths: one depth per job (shk_neighborhood_panel_depths); None: the merged table."""
         jobs = [tuple(j) for j in jobs]
         nj = len(jobs)
+        if depths is not None:
+            depths = np.ascontiguousarray(np.atleast_1d(depths), dtype=np.uint32)
+            if len(depths) != nj:
+                raise ValueError("one depth per job")
         ns = [np.ascontiguousarray(np.atleast_1d(j[0]), dtype=np.uint64).reshape(-1) for j in jobs]
         ds = [np.ascontiguousarray(np.atleast_1d(j[1]), dtype=np.uint8).reshape(-1) for j in jobs]
         if any(len(a) != len(b) for a, b in zip(ns, ds)):
@@ -1221,23 +1317,31 @@ class KmerEngine:
         fd = np.zeros(max(int(fa[-1]), 1), dtype=np.uint8)
         n_out, n_fr = np.zeros(max(nj, 1), dtype=np.uint64), np.zeros(max(nj, 1), dtype=np.uint64)
         lv = np.zeros(max(nj, 1), dtype=np.uint32)
-        self._check(self._L.shk_neighborhood_panel(self._h, nodes.ctypes.data, dirs.ctypes.data, soff.ctypes.data, nj,
-                                                   mcs.ctypes.data, max_levels, caps.ctypes.data, fcaps.ctypes.data,
-                                                   kmers.ctypes.data, counts.ctypes.data, n_out.ctypes.data, fn.ctypes.data,
-                                                   fd.ctypes.data, n_fr.ctypes.data, lv.ctypes.data))
+        if depths is None:
+            self._check(self._L.shk_neighborhood_panel(self._h, nodes.ctypes.data, dirs.ctypes.data, soff.ctypes.data, nj,
+                                                       mcs.ctypes.data, max_levels, caps.ctypes.data, fcaps.ctypes.data,
+                                                       kmers.ctypes.data, counts.ctypes.data, n_out.ctypes.data, fn.ctypes.data,
+                                                       fd.ctypes.data, n_fr.ctypes.data, lv.ctypes.data))
+        else:
+            self._check(self._L.shk_neighborhood_panel_depths(self._h, nodes.ctypes.data, dirs.ctypes.data, soff.ctypes.data, nj,
+                                                              mcs.ctypes.data, depths.ctypes.data, max_levels, caps.ctypes.data,
+                                                              fcaps.ctypes.data, kmers.ctypes.data, counts.ctypes.data,
+                                                              n_out.ctypes.data, fn.ctypes.data, fd.ctypes.data, n_fr.ctypes.data,
+                                                              lv.ctypes.data))
         out = []
         for j in range(nj):
             a, b, n, f = int(ka[j]), int(fa[j]), int(n_out[j]), int(n_fr[j])
             out.append((kmers[a:a + n].copy(), counts[a:a + n].copy(), fn[b:b + f].copy(), fd[b:b + f].copy(), int(lv[j])))
         return out
 
-    def pcr_extend_panel(self, primer_results, params=None) -> list:
+    def pcr_extend_panel(self, primer_results, params=None, depths=None) -> list:
         """shk_pcr_extend for every gene of a panel in one call (shk_pcr_extend_panel) → one PcrGraph per gene, a list
         thread_reads_panel takes as it is.  primer_results: what primer_kmers returns for primers ordered forward,
         reverse per gene (entry 2g gene g's forward set, 2g + 1 its reverse set; k-mers first, counts second), or the
         raw arrays (kmers, counts, offsets) of shk_primer_kmers.  params: one dict of pcr_extend's keyword arguments
         (min_count, table_min_count, high_coverage_ratio, max_num_nodes, sweep) per gene, or one for all;
-        max_num_nodes None = compute_node_budget of the bases this context has ingested."""
+        max_num_nodes None = compute_node_budget of the bases this context has ingested.  depths: one depth per gene
+        (shk_pcr_extend_panel_depths; max_num_nodes None is still the whole context's budget); None: the merged table."""
         raw = len(primer_results) == 3 and all(isinstance(x, np.ndarray) and x.ndim == 1 for x in primer_results)
         if raw:
             pk = np.ascontiguousarray(primer_results[0], dtype=np.uint64)
@@ -1263,6 +1367,10 @@ class KmerEngine:
             params = [params or {}] * ng
         if len(params) != ng:
             raise ValueError("one set of parameters per gene")
+        if depths is not None:
+            depths = np.ascontiguousarray(np.atleast_1d(depths), dtype=np.uint32)
+            if len(depths) != ng:
+                raise ValueError("one depth per gene")
         budget = None
         prm = (_PcrExtendParams * max(ng, 1))()
         for g, p in enumerate(params):
@@ -1281,10 +1389,17 @@ class KmerEngine:
             sub = np.zeros(node_cap, dtype=np.uint64)
             flags = np.zeros(node_cap, dtype=np.uint8)
             es, et, ec = (np.zeros(edge_cap, dtype=np.uint32) for _ in range(3))
-            rcode = self._L.shk_pcr_extend_panel(self._h, pk.ctypes.data, pc.ctypes.data, po.ctypes.data, ng, C.cast(prm, C.c_void_p),
-                                                 sub.ctypes.data, flags.ctypes.data, noff.ctypes.data, node_cap, es.ctypes.data,
-                                                 et.ctypes.data, ec.ctypes.data, eoff.ctypes.data, edge_cap, found.ctypes.data,
-                                                 thr.ctypes.data, steps.ctypes.data)
+            if depths is None:
+                rcode = self._L.shk_pcr_extend_panel(self._h, pk.ctypes.data, pc.ctypes.data, po.ctypes.data, ng, C.cast(prm, C.c_void_p),
+                                                     sub.ctypes.data, flags.ctypes.data, noff.ctypes.data, node_cap, es.ctypes.data,
+                                                     et.ctypes.data, ec.ctypes.data, eoff.ctypes.data, edge_cap, found.ctypes.data,
+                                                     thr.ctypes.data, steps.ctypes.data)
+            else:
+                rcode = self._L.shk_pcr_extend_panel_depths(self._h, pk.ctypes.data, pc.ctypes.data, po.ctypes.data, ng,
+                                                            C.cast(prm, C.c_void_p), depths.ctypes.data, sub.ctypes.data,
+                                                            flags.ctypes.data, noff.ctypes.data, node_cap, es.ctypes.data,
+                                                            et.ctypes.data, ec.ctypes.data, eoff.ctypes.data, edge_cap,
+                                                            found.ctypes.data, thr.ctypes.data, steps.ctypes.data)
             n, e = int(noff[ng]), int(eoff[ng])
             if attempt == 0 and rcode == -2 and (n > node_cap or e > edge_cap):  # too small: the offsets say what it needs
                 node_cap, edge_cap = max(node_cap, n), max(edge_cap, e)
@@ -1710,6 +1825,59 @@ class KmerEngine:
             v = {f: int(a[g]) for f, a in cols.items()}
             v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
             out.append(PcrOutcome(gene_name=genes[g].gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
+        return out
+
+    def pcr_run_depths(self, genes, depths, min_kmer_count: int = 2, max_num_nodes: int = 0, record_cap: int | None = None,
+                       seq_cap: int | None = None) -> list:
+        """pcr_run(reads=None) of the panel at every depth of `depths` (strictly ascending, at most PCR_MAX_DEPTHS) as one
+        pipeline over the (gene, depth) pairs (shk_pcr_run_depths) → per depth the list pcr_run returns on a context that got
+        the chunks below it only.  max_num_nodes 0: compute_node_budget of the bases of the chunks below the depth.
+        record_cap / seq_cap: fixed capacities per depth (no second call when they are too small)."""
+        genes = [g if isinstance(g, PcrGene) else parse_pcr_primers(g) for g in genes]
+        dep = np.ascontiguousarray(np.atleast_1d(depths), dtype=np.uint32)
+        ng, nd = len(genes), len(dep)
+        arr = _pcr_genes(genes)
+        prm = _PcrRunParams(min_kmer_count, PCR_READS_NONE, 0, 0, max_num_nodes, None, None, 0, None, None)
+        n1 = max(ng, 1)
+        cols = []
+        for _ in range(nd):
+            c = {f: np.zeros(n1, dtype=np.uint32) for f in _PCR_RUN_U32}
+            c.update({f: np.zeros(n1, dtype=np.uint64) for f in _PCR_RUN_U64A + ("n_paired_links",)})
+            c.update({f: np.zeros(n1, dtype=np.uint8) for f in ("threaded", "low_primer_counts")})
+            cols.append(c)
+        fixed = record_cap is not None or seq_cap is not None
+        bufs = [_PcrRecordBuf(ng, max(64 * ng, 1) if record_cap is None else record_cap, 1 << 16 if seq_cap is None else seq_cap)
+                for _ in range(nd)]
+        for attempt in (0, 1):
+            O = (_PcrRunOut * max(nd, 1))()
+            for j in range(nd):
+                for f, a in cols[j].items():
+                    setattr(O[j], f, a.ctypes.data)
+                O[j].records = bufs[j].struct()
+            rc = self._L.shk_pcr_run_depths(self._h, arr, ng, C.byref(prm), dep.ctypes.data, nd, O)
+            for j in range(nd):
+                bufs[j].take(O[j].records)
+            if rc == -2 and any(b.short() for b in bufs):
+                if attempt == 0 and not fixed:  # too small: every depth says what it needs
+                    bufs = [_PcrRecordBuf(ng, max(b.rcap, b.n_records), max(b.scap, b.n_seq_bytes)) for b in bufs]
+                    continue
+                try:
+                    self._check(rc)
+                except ShkError as e:  # what the call left: every depth's needs and per-gene arrays, which are complete
+                    e.needs = [(b.n_records, b.n_seq_bytes) for b in bufs]
+                    e.per_gene = [{f: a[:ng].copy() for f, a in c.items()} for c in cols]
+                    raise
+            self._check(rc)
+            break
+        out = []
+        for j in range(nd):
+            prods = bufs[j].products()
+            block = []
+            for g in range(ng):
+                v = {f: int(a[g]) for f, a in cols[j].items()}
+                v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
+                block.append(PcrOutcome(gene_name=genes[g].gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
+            out.append(block)
         return out
 
     def gather_reads(self, bases_t, offsets_t, read_ids):
@@ -2215,7 +2383,7 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
               max_reads: int = 0, validate_every: int = 0, device: int = 0, capacity_hint: int = 0,
               command: str = "", batch_reads: int = 0, batch_bases: int = 0, device_ids=None, gzip_all_members: bool = False,
               bgzf=None, parse=None, pcr_primers=None, read_threading: bool = False, min_kmer_count: int = 2, node_budget_global: int = 0,
-              group_graph: bool = False, group_reads: bool = False, **tuning) -> dict:
+              group_graph: bool = False, group_reads: bool = False, pcr_depths=None, **tuning) -> dict:
     """main.rs:112-199: FASTQ files → counts → .histo/.final.histo/.stats.yaml, and with pcr_primers (specification
     strings or PcrGene) sPCR's {sample}_{gene}.fasta files and pcr_results in the stats file (shk_run_files_pcr).
     tuning: the six global flags of main.rs:49-56 (max_dfs_states, max_paths_per_pair, max_node_visits,
@@ -2224,7 +2392,8 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
     (SHK_FLAG_GROUP_GRAPH), and read_threading there needs group_reads=True (SHK_FLAG_GROUP_READS).  gzip_all_members, bgzf: see FastqReader
     (bgzf="device" decodes on the context's first device).  parse="device" (with bgzf="device" only): the decoded text
     stays on the device and is framed there (SHK_FASTQ_DEVICE_PARSE); a file the route gives up on is read the
-    bgzf="device" way from its start."""
+    bgzf="device" way from its start.  pcr_depths: "all" or a list of depths (chunks >= 1, one device, no read_threading):
+    after the panel, pcr_run_depths with {sample}_{gene}.depth{d}.fasta and {sample}.pcr_depths.tsv (shk_count --pcr-depths)."""
     if parse not in (None, "device"):
         raise ValueError(f"parse must be None or 'device', not {parse!r}")
     known = ("max_dfs_states", "max_paths_per_pair", "max_node_visits", "max_primer_kmers", "high_coverage_ratio", "tip_coverage_fraction")
@@ -2257,7 +2426,14 @@ def run_files(inputs, k: int, chunks: int, sample: str, outdir: str = "./", hist
         arr = _pcr_genes(genes)
         pcfg = _PcrFileConfig(arr, len(genes), min_kmer_count, 1 if read_threading else 0, 0, node_budget_global,
                               (FLAG_GROUP_GRAPH if group_graph else 0) | (FLAG_GROUP_READS if group_reads else 0))
+        if pcr_depths is not None:
+            dep = np.arange(1, chunks + 1, dtype=np.uint32) if isinstance(pcr_depths, str) and pcr_depths == "all" else \
+                np.ascontiguousarray(np.atleast_1d(pcr_depths), dtype=np.uint32)
+            dep = dep if len(dep) else np.zeros(1, dtype=np.uint32)  # (an empty list is refused as depth 0 is)
+            pcfg.depths, pcfg.n_depths = dep.ctypes.data, len(dep)
         rc = L.shk_run_files_pcr(C.byref(cfg), C.byref(pcfg), C.byref(st), None)
+    elif pcr_depths is not None:
+        raise ShkError(-2, "--pcr-depths needs --pcr-primers")
     else:
         rc = L.shk_run_files(C.byref(cfg), C.byref(st))
     if rc != 0:
