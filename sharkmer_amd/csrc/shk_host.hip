@@ -4,6 +4,7 @@
 // built under sanitizers, `make san`); only what touches HIP (pinned buffers, device memory in use) lives here.
 #include "../../include/shk.h"
 #include "shk_front.h"
+#include "shk_products.h"
 
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -326,35 +327,25 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
   // run_pcr (stats.rs:49-145): the panel, then one FASTA file per gene with products, in gene order
   std::vector<shk_pcr_gene_stat> gene_stats(n_genes);
   std::vector<uint64_t> product_lengths;
-  if (n_genes) {
-    shk_pcr_run_params pp{};
-    pp.min_kmer_count = pcr->min_kmer_count;
-    pp.reads = threading ? SHK_PCR_READS_RETAINED : SHK_PCR_READS_NONE;
-    pp.max_num_nodes = pcr->node_budget_global;
-    // the call's own record arrays where the caller brought none: at most SHK_PCR_MAX_AMPLICONS records per gene
-    std::vector<uint32_t> status(n_genes);
-    std::vector<uint64_t> roff(n_genes + 1), soff, cmin, cmax;
-    std::vector<uint8_t> seqs;
-    std::vector<double> mean, median, score;
-    shk_pcr_run_out own{};
-    shk_pcr_run_out *po = pcr_out ? pcr_out : &own;
-    uint64_t seq_cap = 1ull << 20;
+  // One sPCR call, run(outs), of D output blocks — `given`, or where the caller brought none record arrays of this
+  // function's (at most SHK_PCR_MAX_AMPLICONS records per gene; the sequence room grows once: products beyond a megabase)
+  // — then per (block, gene) row(j, g, block, a, b) and, for one with products, the FASTA file {sample}_{gene}{suffix(j)}.
+  auto pcr_blocks = [&](uint32_t D, shk_pcr_run_out *given, auto run, const char *done, auto suffix, auto row) {
+    std::vector<PcrRecordArrays> bufs(given ? 0 : D, PcrRecordArrays((uint64_t)SHK_PCR_MAX_AMPLICONS * n_genes, 1ull << 20));
+    std::vector<std::vector<uint32_t>> status(bufs.size());
+    std::vector<shk_pcr_run_out> own(bufs.size());
+    shk_pcr_run_out *outs = given ? given : own.data();
     for (int attempt = 0;; ++attempt) {
-      if (!pcr_out) {
-        const uint64_t cap = (uint64_t)SHK_PCR_MAX_AMPLICONS * n_genes;
-        soff.assign(cap + 1, 0), cmin.assign(cap, 0), cmax.assign(cap, 0), mean.assign(cap, 0), median.assign(cap, 0), score.assign(cap, 0);
-        seqs.assign(seq_cap, 0);
-        own.status = status.data();
-        own.records.record_offsets = roff.data(), own.records.seq_offsets = soff.data(), own.records.seqs = seqs.data();
-        own.records.record_cap = cap, own.records.seq_cap = seq_cap;
-        own.records.count_mean = mean.data(), own.records.count_median = median.data(), own.records.count_min = cmin.data();
-        own.records.count_max = cmax.data(), own.records.score = score.data();
+      for (size_t j = 0; j < bufs.size(); ++j) {
+        status[j].assign(n_genes, 0);
+        own[j] = shk_pcr_run_out{};
+        own[j].status = status[j].data(), own[j].records = bufs[j].bind(n_genes, 0);
       }
-      v = shk_pcr_run(ctx, pcr->genes, n_genes, &pp, po);
-      if (v == SHK_ERR_BAD_ARG && !pcr_out && attempt == 0 && own.records.n_seq_bytes > seq_cap) {  // products beyond a megabase: once more
-        seq_cap = own.records.n_seq_bytes;
-        continue;
-      }
+      v = run(outs);
+      bool grew = false;
+      for (size_t j = 0; j < bufs.size(); ++j)
+        if (PcrRecordArrays::is_short(own[j].records)) bufs[j].grow(own[j].records), grew = true;
+      if (v == SHK_ERR_BAD_ARG && attempt == 0 && grew) continue;  // once more
       break;
     }
     if (v != SHK_OK) {
@@ -362,21 +353,38 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
       cleanup();
       return v;
     }
-    mark("sPCR");
-    const shk_pcr_records &R = po->records;
-    product_lengths.resize(R.record_offsets[n_genes]);
-    for (uint32_t g = 0; g < n_genes; ++g) {
-      const uint64_t a = R.record_offsets[g], b = R.record_offsets[g + 1];
-      for (uint64_t r = a; r < b; ++r) product_lengths[r] = R.seq_offsets[r + 1] - R.seq_offsets[r];
-      gene_stats[g] = shk_pcr_gene_stat{pcr->genes[g].gene_name, po->status[g], (uint32_t)(b - a), product_lengths.data() + a};
-      if (b == a) continue;
-      const std::string path = dir + sample + "_" + pcr->genes[g].gene_name + ".fasta";  // stats.rs:106
-      if ((v = shk_write_fasta(path.c_str(), sample.c_str(), &pcr->genes[g], &R, a, b - a)) != SHK_OK) {
-        g_run_error = fmt("Failed to create FASTA file: %s", path.c_str());
-        cleanup();
-        return v;
+    if (done) mark(done);
+    for (uint32_t j = 0; j < D; ++j) {
+      const shk_pcr_records &R = outs[j].records;
+      for (uint32_t g = 0; g < n_genes; ++g) {
+        const uint64_t a = R.record_offsets[g], b = R.record_offsets[g + 1];
+        row(j, g, outs[j], a, b);
+        if (b == a) continue;
+        const std::string path = dir + sample + "_" + pcr->genes[g].gene_name + suffix(j);  // stats.rs:106
+        if ((v = shk_write_fasta(path.c_str(), sample.c_str(), &pcr->genes[g], &R, a, b - a)) != SHK_OK) {
+          g_run_error = fmt("Failed to create FASTA file: %s", path.c_str());
+          cleanup();
+          return v;
+        }
       }
     }
+    return (int)SHK_OK;
+  };
+  shk_pcr_run_params pp{};
+  if (n_genes) {
+    pp.min_kmer_count = pcr->min_kmer_count;
+    pp.reads = threading ? SHK_PCR_READS_RETAINED : SHK_PCR_READS_NONE;
+    pp.max_num_nodes = pcr->node_budget_global;
+    std::vector<uint64_t> first(n_genes);  // gene g's lengths start at product_lengths[first[g]]
+    auto run = [&](shk_pcr_run_out *outs) { return shk_pcr_run(ctx, pcr->genes, n_genes, &pp, outs); };
+    auto suffix = [](uint32_t) { return std::string(".fasta"); };
+    auto row = [&](uint32_t, uint32_t g, const shk_pcr_run_out &o, uint64_t a, uint64_t b) {
+      first[g] = a;
+      for (uint64_t r = a; r < b; ++r) product_lengths.push_back(o.records.seq_offsets[r + 1] - o.records.seq_offsets[r]);
+      gene_stats[g] = shk_pcr_gene_stat{pcr->genes[g].gene_name, o.status[g], (uint32_t)(b - a), nullptr};
+    };
+    if ((v = pcr_blocks(1, pcr_out, run, "sPCR", suffix, row)) != SHK_OK) return v;
+    for (uint32_t g = 0; g < n_genes; ++g) gene_stats[g].product_lengths = product_lengths.data() + first[g];  // (product_lengths is complete)
   }
   // --pcr-depths: the panel at the listed depths, SHK_PCR_MAX_DEPTHS per call; {sample}_{gene}.depth{d}.fasta for every
   // (gene, depth) with products and {sample}.pcr_depths.tsv, depth-major then gene order
@@ -389,65 +397,19 @@ int run_files_impl(const shk_run_config *rc, const shk_pcr_file_config *pcr, shk
       cleanup();
       return v;
     }
-    shk_pcr_run_params pp{};
-    pp.min_kmer_count = pcr->min_kmer_count;
     pp.reads = SHK_PCR_READS_NONE;
-    pp.max_num_nodes = pcr->node_budget_global;
-    const uint64_t cap = (uint64_t)SHK_PCR_MAX_AMPLICONS * n_genes;
-    struct DepthOut {
-      std::vector<uint32_t> status;
-      std::vector<uint64_t> roff, soff, cmin, cmax;
-      std::vector<uint8_t> seqs;
-      std::vector<double> mean, median, score;
-    };
     for (uint64_t d0 = 0; d0 < pcr->n_depths; d0 += SHK_PCR_MAX_DEPTHS) {
-      const uint32_t D = (uint32_t)std::min<uint64_t>(SHK_PCR_MAX_DEPTHS, pcr->n_depths - d0);
-      std::vector<DepthOut> bufs(D);
-      std::vector<shk_pcr_run_out> outs(D);
-      std::vector<uint64_t> seq_cap(D, 1ull << 20);
-      for (int attempt = 0;; ++attempt) {
-        for (uint32_t j = 0; j < D; ++j) {
-          DepthOut &b = bufs[j];
-          b.status.assign(n_genes, 0), b.roff.assign(n_genes + 1, 0), b.soff.assign(cap + 1, 0), b.cmin.assign(cap, 0), b.cmax.assign(cap, 0);
-          b.mean.assign(cap, 0), b.median.assign(cap, 0), b.score.assign(cap, 0), b.seqs.assign(seq_cap[j], 0);
-          outs[j] = shk_pcr_run_out{};
-          outs[j].status = b.status.data();
-          shk_pcr_records &R = outs[j].records;
-          R.record_offsets = b.roff.data(), R.seq_offsets = b.soff.data(), R.seqs = b.seqs.data(), R.record_cap = cap, R.seq_cap = seq_cap[j];
-          R.count_mean = b.mean.data(), R.count_median = b.median.data(), R.count_min = b.cmin.data(), R.count_max = b.cmax.data();
-          R.score = b.score.data();
-        }
-        v = shk_pcr_run_depths(ctx, pcr->genes, n_genes, &pp, pcr->depths + d0, D, outs.data());
-        bool grew = false;
-        for (uint32_t j = 0; j < D; ++j)
-          if (outs[j].records.n_seq_bytes > seq_cap[j]) seq_cap[j] = outs[j].records.n_seq_bytes, grew = true;
-        if (v == SHK_ERR_BAD_ARG && attempt == 0 && grew) continue;  // products beyond a megabase: once more
-        break;
-      }
-      if (v != SHK_OK) {
-        g_run_error = shk_last_error(ctx);
-        cleanup();
-        return v;
-      }
-      for (uint32_t j = 0; j < D; ++j) {
-        const uint32_t depth = pcr->depths[d0 + j];
+      const uint32_t D = (uint32_t)std::min<uint64_t>(SHK_PCR_MAX_DEPTHS, pcr->n_depths - d0), *depths = pcr->depths + d0;
+      auto run = [&](shk_pcr_run_out *outs) { return shk_pcr_run_depths(ctx, pcr->genes, n_genes, &pp, depths, D, outs); };
+      auto suffix = [&](uint32_t j) { return fmt(".depth%u.fasta", depths[j]); };
+      auto row = [&](uint32_t j, uint32_t g, const shk_pcr_run_out &o, uint64_t a, uint64_t b) {
         uint64_t below = 0;
-        for (uint32_t l = 0; l < depth && l < chunk_bases.size(); ++l) below += chunk_bases[l];
-        const shk_pcr_records &R = outs[j].records;
-        for (uint32_t g = 0; g < n_genes; ++g) {
-          const uint64_t a = R.record_offsets[g], b = R.record_offsets[g + 1];
-          row_lengths.push_back({all_lengths.size(), (uint32_t)(b - a)});
-          for (uint64_t r = a; r < b; ++r) all_lengths.push_back(R.seq_offsets[r + 1] - R.seq_offsets[r]);
-          rows.push_back(shk_pcr_depth_row{depth, 0, below, shk_pcr_gene_stat{pcr->genes[g].gene_name, outs[j].status[g], (uint32_t)(b - a), nullptr}});
-          if (b == a) continue;
-          const std::string path = dir + sample + "_" + pcr->genes[g].gene_name + fmt(".depth%u.fasta", depth);
-          if ((v = shk_write_fasta(path.c_str(), sample.c_str(), &pcr->genes[g], &R, a, b - a)) != SHK_OK) {
-            g_run_error = fmt("Failed to create FASTA file: %s", path.c_str());
-            cleanup();
-            return v;
-          }
-        }
-      }
+        for (uint32_t l = 0; l < depths[j] && l < chunk_bases.size(); ++l) below += chunk_bases[l];
+        row_lengths.push_back({all_lengths.size(), (uint32_t)(b - a)});
+        for (uint64_t r = a; r < b; ++r) all_lengths.push_back(o.records.seq_offsets[r + 1] - o.records.seq_offsets[r]);
+        rows.push_back(shk_pcr_depth_row{depths[j], 0, below, shk_pcr_gene_stat{pcr->genes[g].gene_name, o.status[g], (uint32_t)(b - a), nullptr}});
+      };
+      if ((v = pcr_blocks(D, nullptr, run, nullptr, suffix, row)) != SHK_OK) return v;
     }
     for (size_t i = 0; i < rows.size(); ++i) rows[i].gene.product_lengths = all_lengths.data() + row_lengths[i].first;  // (all_lengths is complete)
     const std::string tsv = dir + sample + ".pcr_depths.tsv";

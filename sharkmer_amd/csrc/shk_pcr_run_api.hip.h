@@ -1,9 +1,11 @@
-// shk_pcr_run_api.hip.h — shk_pcr_run (included by shk_engine.hip, same translation unit, behind the stage files whose
-// calls and cores it runs): do_pcr for every gene of a panel (src/pcr/mod.rs:431-819) as run_pcr drives it
-// (src/stats.rs:84-98), the genes side by side — each stage once for the genes still alive.  No kernel
-// of its own: the primer scan, the extension's fetches, the panel filter, the prune, the threading and the dedup are the
-// stage calls', launched through shk_primer_kmers, shk_pcr_extend_panel, panel_core, shk_pcr_prune_panel,
-// thread_panel_core and shk_pcr_products_panel.  The two read-side stages share ONE opened batch.
+// shk_pcr_run_api.hip.h — shk_pcr_run and shk_pcr_run_depths (included by shk_engine.hip, same translation unit, behind
+// the stage files whose calls and cores it runs): do_pcr for every gene of a panel (src/pcr/mod.rs:431-819) as run_pcr
+// drives it (src/stats.rs:84-98), the genes side by side — each stage once for the genes still alive.
+// ONE pipeline (pcr_pipeline) over the virtual genes v = j · ng + g of D output blocks: shk_pcr_run is D = 1 on the table
+// as it is, shk_pcr_run_depths gene g at depths[j].  No kernel of its own: the primer scan, the
+// extension's fetches, the panel filter, the prune, the threading and the dedup are the stage calls', launched through
+// shk_primer_kmers[_depths], shk_pcr_extend_panel[_depths], panel_core, shk_pcr_prune_panel, thread_panel_core and
+// shk_pcr_products_panel.  The two read-side stages share ONE opened batch.
 namespace {
 
 // Slices [off[g], off[g + 1]) of src for the genes of sel, back to back.
@@ -90,7 +92,7 @@ int pcr_genes_check(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const sh
   return SHK_OK;
 }
 
-// ---- the stages shk_pcr_run and shk_pcr_run_depths share: each is handed its genes (or (gene, depth) pairs) gathered ----
+// ---- the stages of the pipeline: each is handed its virtual genes gathered ----
 
 // Step 4's output: the extended graphs of the alive genes back to back, and per gene what the sweep reports.
 struct PcrExtended {
@@ -160,25 +162,55 @@ void pcr_products_params(const shk_pcr_gene *genes, const std::vector<uint32_t> 
   }
 }
 
-int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, shk_pcr_run_out *out) {
+// The SHK_TRACE line of virtual gene v (gene g of o): shk_pcr_run's, or with a depth shk_pcr_run_depths'.
+void pcr_trace_line(const shk_pcr_gene &gene, uint32_t g, uint32_t status, uint64_t n_fwd, uint64_t n_rev, const shk_pcr_run_out &o, uint32_t depth) {
+  using ull = unsigned long long;
+  const char *what = status == SHK_PCR_SUCCESS ? "success" : shk_pcr_failure_reason(status);
+  if (depth) {
+    fprintf(stderr, "[shk] pcr_run_depths: depth %u gene %u '%s': %s, primer k-mers %llu + %llu\n", depth, g, gene.gene_name, what, (ull)n_fwd, (ull)n_rev);
+    return;
+  }
+  fprintf(stderr, "[shk] pcr_run: gene %u '%s': %s, primer k-mers %llu + %llu, threshold %u after %u steps, %llu nodes, %llu edges, %llu reads matched%s, %llu products\n",
+          g, gene.gene_name, what, (ull)n_fwd, (ull)n_rev, o.threshold_used ? o.threshold_used[g] : 0u, o.steps_run ? o.steps_run[g] : 0u,
+          (ull)(o.n_nodes ? o.n_nodes[g] : 0), (ull)(o.n_edges ? o.n_edges[g] : 0), (ull)(o.n_reads_matched ? o.n_reads_matched[g] : 0),
+          o.threaded && o.threaded[g] ? ", threaded" : "", (ull)(o.records.record_offsets[g + 1] - o.records.record_offsets[g]));
+}
+
+// The pipeline of shk_pcr_run and shk_pcr_run_depths over the virtual genes v = j · ng + g: gene g into
+// slot g of outs[j], each stage called once for the virtual genes still alive.
+//   plain (sweep false): D = 1 — outs is the caller's one block, the table as it is, any of the three read modes, the
+//     records written by the products call straight into the caller's arrays;
+//   sweep: gene g at depths[j] for D depths, no reads, the records into arrays of this call's and from there dealt out to
+//     every outs[j] under that block's own capacities.
+int pcr_pipeline(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, bool sweep, const uint32_t *depths,
+                 uint32_t D, shk_pcr_run_out *outs) {
   using ull = unsigned long long;
   const uint32_t k = c->cfg.k;
-  shk_pcr_records &R = out->records;
-  pcr_out_clear(out, ng);
-
-  // ---- everything that is refused, the first in gene order, before the device is touched ----
-  if (ng > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", ng, (unsigned)SHK_PCR_MAX_GENES);
-  if (p->reads > SHK_PCR_READS_HOST) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run: reads = %u is none of SHK_PCR_READS_*", p->reads);
+  // ---- everything that is refused, the first in gene order, before the device is touched: each entry point in its order ----
+  if (sweep) {
+    SHK_TRY(depth_call_begin(c, "shk_pcr_run_depths", depths, D, true));
+    for (uint32_t j = 0; j < D; ++j)
+      if (!outs[j].status || !outs[j].records.record_offsets) return SHK_ERR_BAD_ARG;
+    if ((uint64_t)ng * D > SHK_PCR_MAX_GENES)
+      return fail(c, SHK_ERR_BAD_ARG, "n_genes %u x n_depths %u above SHK_PCR_MAX_GENES (%u)", ng, D, (unsigned)SHK_PCR_MAX_GENES);
+    for (uint32_t j = 0; j < D; ++j) pcr_out_clear(&outs[j], ng);
+    if (p->reads != SHK_PCR_READS_NONE) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run_depths: a depth sweep takes no reads");
+  } else {
+    pcr_out_clear(outs, ng);
+    if (ng > SHK_PCR_MAX_GENES) return fail(c, SHK_ERR_BAD_ARG, "n_genes %u above SHK_PCR_MAX_GENES (%u)", ng, (unsigned)SHK_PCR_MAX_GENES);
+    if (p->reads > SHK_PCR_READS_HOST) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run: reads = %u is none of SHK_PCR_READS_*", p->reads);
+  }
   std::vector<shk_primer> primers;
   std::vector<uint32_t> min_count;
   uint64_t primer_cap = 0;
   SHK_TRY(pcr_genes_check(c, genes, ng, p, &primers, &min_count, &primer_cap));
-  SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
+  if (!sweep) SHK_TRY(graph_call_begin(c, "shk_pcr_extend_panel"));
   // A multi-device context (SHK_FLAG_GROUP_GRAPH): the calls that take the context take it as it is — the primer scan
   // goes over the shares, the extension through the share directory, prune and products on the first device — and the
   // read-side cores run on the lead share rd, the device the public read calls use; on0: their error text to the context.
   shk_ctx *rd = c->group ? c->group->ctx[0] : c;
   auto on0 = [&](int rc) { return rc == SHK_OK || !c->group ? rc : group_fail(c, c->group, rc, 0); };
+  // (a sweep has reads = NONE: none of the checks of the reads below can refuse it)
   const bool host = p->reads == SHK_PCR_READS_HOST, retained = p->reads == SHK_PCR_READS_RETAINED;
   // … and with SHK_FLAG_GROUP_READS too, over retained reads, every share runs them over its own store
   const bool shared_reads = retained && c->group;
@@ -197,42 +229,55 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   }
   const bool mate_rule = !mate && p->paired && p->reads != SHK_PCR_READS_NONE;
   if (ng == 0) return SHK_OK;
+  const uint32_t nv = ng * D;
 
-  // ---- step 2: the primer k-mers of the whole panel in one table pass ----
-  std::vector<uint64_t> pk(std::max<uint64_t>(primer_cap, 1)), poff(2 * (size_t)ng + 1, 0);
+  // ---- step 2: the primer k-mers of every virtual gene in one table pass (a sweep: the fused one): slot 2v + direction ----
+  primer_cap *= D;
+  std::vector<uint64_t> pk(std::max<uint64_t>(primer_cap, 1)), poff(2 * (size_t)nv + 1, 0);
   std::vector<uint32_t> pc(pk.size());
   std::vector<uint8_t> plev(pk.size());
-  SHK_TRY(shk_primer_kmers(c, primers.data(), 2 * ng, pk.data(), pc.data(), plev.data(), primer_cap, poff.data(), nullptr));
-  uint64_t budget = p->max_num_nodes;
-  if (!budget) {  // main.rs:147-165
+  SHK_TRY(sweep ? shk_primer_kmers_depths(c, primers.data(), 2 * ng, depths, D, pk.data(), pc.data(), plev.data(), primer_cap, poff.data(), nullptr)
+                : shk_primer_kmers(c, primers.data(), 2 * ng, pk.data(), pc.data(), plev.data(), primer_cap, poff.data(), nullptr));
+  std::vector<uint64_t> budget(D, p->max_num_nodes);  // per block
+  if (!p->max_num_nodes && sweep) {  // main.rs:147-165 on the bases of the chunks below the depth
+    std::vector<uint64_t> cb(c->n_lanes);
+    SHK_TRY(shk_chunk_bases(c, cb.data()));
+    uint64_t sum = 0;
+    for (uint32_t j = 0, l = 0; j < D; ++j) {
+      for (; l < depths[j]; ++l) sum += cb[l];
+      budget[j] = shk_pcr_node_budget(sum);
+    }
+  } else if (!p->max_num_nodes) {  // main.rs:147-165
     shk_counters cn{};
     SHK_TRY(shk_get_counters(c, &cn));
-    budget = shk_pcr_node_budget(cn.n_bases_ingested);
+    budget[0] = shk_pcr_node_budget(cn.n_bases_ingested);
   }
-  std::vector<uint32_t> status(ng, SHK_PCR_NO_PATH), alive;  // alive: both sets found
-  for (uint32_t g = 0; g < ng; ++g) {
-    const uint64_t nf = poff[2 * g + 1] - poff[2 * g], nr = poff[2 * g + 2] - poff[2 * g + 1];
-    const uint32_t mf = nf ? *std::max_element(pc.begin() + poff[2 * g], pc.begin() + poff[2 * g + 1]) : 0;
-    const uint32_t mr = nr ? *std::max_element(pc.begin() + poff[2 * g + 1], pc.begin() + poff[2 * g + 2]) : 0;
-    if (out->n_fwd_kmers) out->n_fwd_kmers[g] = (uint32_t)nf;
-    if (out->n_rev_kmers) out->n_rev_kmers[g] = (uint32_t)nr;
-    if (out->max_fwd_count) out->max_fwd_count[g] = mf;
-    if (out->max_rev_count) out->max_rev_count[g] = mr;
+  std::vector<uint32_t> status(nv, SHK_PCR_NO_PATH), alive;  // alive: both sets found
+  for (uint32_t v = 0; v < nv; ++v) {
+    shk_pcr_run_out &o = outs[v / ng];
+    const uint32_t g = v % ng;
+    const uint64_t nf = poff[2 * v + 1] - poff[2 * v], nr = poff[2 * v + 2] - poff[2 * v + 1];
+    const uint32_t mf = nf ? *std::max_element(pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 1]) : 0;
+    const uint32_t mr = nr ? *std::max_element(pc.begin() + poff[2 * v + 1], pc.begin() + poff[2 * v + 2]) : 0;
+    if (o.n_fwd_kmers) o.n_fwd_kmers[g] = (uint32_t)nf;
+    if (o.n_rev_kmers) o.n_rev_kmers[g] = (uint32_t)nr;
+    if (o.max_fwd_count) o.max_fwd_count[g] = mf;
+    if (o.max_rev_count) o.max_rev_count[g] = mr;
     if (!nf || !nr) {  // mod.rs:446-468: nothing more for this gene
-      status[g] = !nf && !nr ? SHK_PCR_NO_PRIMERS : !nf ? SHK_PCR_NO_FORWARD : SHK_PCR_NO_REVERSE;
+      status[v] = !nf && !nr ? SHK_PCR_NO_PRIMERS : !nf ? SHK_PCR_NO_FORWARD : SHK_PCR_NO_REVERSE;
       continue;
     }
-    if (out->median_primer_count)
-      out->median_primer_count[g] = std::min(pcr_median_count(pc.data() + poff[2 * g], nf), pcr_median_count(pc.data() + poff[2 * g + 1], nr));
-    if (out->low_primer_counts) out->low_primer_counts[g] = mf < 5 || mr < 5;  // mod.rs:752-759
-    alive.push_back(g);
+    if (o.median_primer_count)
+      o.median_primer_count[g] = std::min(pcr_median_count(pc.data() + poff[2 * v], nf), pcr_median_count(pc.data() + poff[2 * v + 1], nr));
+    if (o.low_primer_counts) o.low_primer_counts[g] = mf < 5 || mr < 5;  // mod.rs:752-759
+    alive.push_back(v);
   }
   const uint32_t na = (uint32_t)alive.size();
 
-  // ---- step 3: the reads, opened once for the filter and the threading; the alive genes' lists ----
+  // ---- step 3 (never in a sweep): the reads, opened once for the filter and the threading; the alive genes' lists ----
   ReadBatch batch{};
   bool have_batch = false;
-  std::vector<uint64_t> moff(na + 1, 0);  // per alive gene
+  std::vector<uint64_t> moff;  // per alive gene, with a batch
   std::unique_ptr<uint64_t[]> mreads;
   if (na && p->reads != SHK_PCR_READS_NONE) {
     if (host && p->n_seqs) {
@@ -255,13 +300,14 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
   if (have_batch) {
     std::vector<uint64_t> fk, foff(na + 1, 0);
     for (uint32_t a = 0; a < na; ++a) {  // from_primer_kmers (read_filter.rs:24-41): the canonical forms of both sets
-      const uint32_t g = alive[a];
-      for (uint64_t j = poff[2 * g]; j < poff[2 * g + 2]; ++j) fk.push_back(pcr_canonical(pk[j], k));
+      const uint32_t v = alive[a];
+      for (uint64_t j = poff[2 * v]; j < poff[2 * v + 2]; ++j) fk.push_back(pcr_canonical(pk[j], k));
       foff[a + 1] = fk.size();
     }
     HostKeyRuns pl;
     SHK_TRY(on0(panel_plan(rd, fk.data(), foff.data(), na, &pl)));
     uint64_t cap = std::min<uint64_t>(batch.n_seqs * na, 1ull << 22), n_matches = 0;
+    moff.assign(na + 1, 0);
     for (int attempt = 0; attempt < 2 && !pl.items.empty(); ++attempt) {
       mreads.reset(new uint64_t[std::max<uint64_t>(cap, 1)]);
       std::fill(moff.begin(), moff.end(), 0ull);
@@ -274,47 +320,50 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
       SHK_TRY(rc);
       break;
     }
-    for (uint32_t a = 0; a < na && out->n_reads_matched; ++a) out->n_reads_matched[alive[a]] = moff[a + 1] - moff[a];
+    for (uint32_t a = 0; a < na; ++a)
+      if (uint64_t *matched = outs[alive[a] / ng].n_reads_matched) matched[alive[a] % ng] = moff[a + 1] - moff[a];
   }
 
-  // ---- step 4: the extension of the alive genes ----
+  // ---- step 4: the extension of the alive virtual genes, in a sweep each at its depth ----
   PcrExtended X(na);
   const std::vector<uint64_t> &xnoff = X.noff, &xeoff = X.eoff;
   const std::vector<uint32_t> &xfound = X.found, &xthr = X.thr, &xsteps = X.steps;
-  std::vector<uint32_t> found;  // positions in alive of the genes whose last step found a path
+  std::vector<uint32_t> found;  // positions in alive of the virtual genes whose last step found a path
   if (na) {
     std::vector<uint64_t> ak, aoff(2 * (size_t)na + 1, 0);
-    std::vector<uint32_t> ac;
+    std::vector<uint32_t> ac, adepth(sweep ? na : 0);
     std::vector<shk_pcr_extend_params> xp(na);
     for (uint32_t a = 0; a < na; ++a) {
-      const uint32_t g = alive[a];
-      ak.insert(ak.end(), pk.begin() + poff[2 * g], pk.begin() + poff[2 * g + 2]);
-      ac.insert(ac.end(), pc.begin() + poff[2 * g], pc.begin() + poff[2 * g + 2]);
-      aoff[2 * a + 1] = aoff[2 * a] + (poff[2 * g + 1] - poff[2 * g]);
-      aoff[2 * a + 2] = aoff[2 * a] + (poff[2 * g + 2] - poff[2 * g]);
-      xp[a] = shk_pcr_extend_params{min_count[g], p->min_kmer_count, genes[g].high_coverage_ratio, budget, 1u, 0u};
+      const uint32_t v = alive[a], g = v % ng;
+      ak.insert(ak.end(), pk.begin() + poff[2 * v], pk.begin() + poff[2 * v + 2]);
+      ac.insert(ac.end(), pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 2]);
+      aoff[2 * a + 1] = aoff[2 * a] + (poff[2 * v + 1] - poff[2 * v]);
+      aoff[2 * a + 2] = aoff[2 * a] + (poff[2 * v + 2] - poff[2 * v]);
+      xp[a] = shk_pcr_extend_params{min_count[g], p->min_kmer_count, genes[g].high_coverage_ratio, budget[v / ng], 1u, 0u};
+      if (sweep) adepth[a] = depths[v / ng];
     }
-    SHK_TRY(pcr_extend_stage(c, ak, ac, aoff, na, xp, nullptr, &X));
+    SHK_TRY(pcr_extend_stage(c, ak, ac, aoff, na, xp, sweep ? adepth.data() : nullptr, &X));
     for (uint32_t a = 0; a < na; ++a) {
-      const uint32_t g = alive[a];
+      const uint32_t v = alive[a], g = v % ng;
+      shk_pcr_run_out &o = outs[v / ng];
       const uint64_t nn = xnoff[a + 1] - xnoff[a];
-      if (out->threshold_used) out->threshold_used[g] = xthr[a];
-      if (out->steps_run) out->steps_run[g] = xsteps[a];
-      if (out->found_path) out->found_path[g] = xfound[a];
-      if (out->n_nodes) out->n_nodes[g] = nn;
-      if (out->n_edges) out->n_edges[g] = xeoff[a + 1] - xeoff[a];
-      status[g] = nn >= budget ? SHK_PCR_NODE_BUDGET : SHK_PCR_NO_PATH;  // step 5 (mod.rs:567, 621-623)
+      if (o.threshold_used) o.threshold_used[g] = xthr[a];
+      if (o.steps_run) o.steps_run[g] = xsteps[a];
+      if (o.found_path) o.found_path[g] = xfound[a];
+      if (o.n_nodes) o.n_nodes[g] = nn;
+      if (o.n_edges) o.n_edges[g] = xeoff[a + 1] - xeoff[a];
+      status[v] = nn >= budget[v / ng] ? SHK_PCR_NODE_BUDGET : SHK_PCR_NO_PATH;  // step 5 (mod.rs:567, 621-623)
       if (xfound[a]) found.push_back(a);
     }
   }
   const uint32_t nf = (uint32_t)found.size();
 
-  // ---- step 6, for the genes with a path: prune, thread, products ----
-  int products_rc = SHK_OK;
+  // ---- step 6, for the virtual genes with a path: one prune, the threading where reads were given, one products call ----
+  int short_rc = SHK_OK;
   if (nf) {
-    std::vector<uint32_t> fgene(nf);  // the genes with a path
+    std::vector<uint32_t> fgene(nf);  // the gene of every virtual gene with a path
     std::vector<double> tip(nf);
-    for (uint32_t f = 0; f < nf; ++f) fgene[f] = alive[found[f]], tip[f] = genes[fgene[f]].tip_coverage_fraction;
+    for (uint32_t f = 0; f < nf; ++f) fgene[f] = alive[found[f]] % ng, tip[f] = genes[fgene[f]].tip_coverage_fraction;
     PcrPruned Q;
     SHK_TRY(pcr_prune_stage(c, X, found, tip, &Q));
     std::vector<uint64_t> &qsub = Q.sub, &qnoff = Q.noff, &qeoff = Q.eoff;
@@ -326,10 +375,11 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
     for (uint32_t f = 0; f < nf && have_batch; ++f)
       if (moff[found[f] + 1] > moff[found[f]]) thr.push_back(f);
     const uint32_t nt = (uint32_t)thr.size();
-    std::vector<uint8_t> has(nf, 0);
-    std::vector<uint32_t> stot(std::max<uint64_t>(qeoff[nf], 1), 0), suna(stot.size(), 0), lin, lout, lcnt;
-    std::vector<uint64_t> loff(nf + 1, 0);
+    std::vector<uint8_t> has;  // the annotations in the layout of the pruned panel: sized only where a gene is threaded
+    std::vector<uint32_t> stot, suna, lin, lout, lcnt;
+    std::vector<uint64_t> loff;
     if (nt) {
+      has.assign(nf, 0), stot.assign(std::max<uint64_t>(qeoff[nf], 1), 0), suna.assign(stot.size(), 0), loff.assign(nf + 1, 0);
       std::vector<uint64_t> tsub, tnoff = pcr_gather_offsets(qnoff, thr), teoff = pcr_gather_offsets(qeoff, thr), tloff(nt + 1, 0), tlist;
       std::vector<uint32_t> tes, tet;
       pcr_gather(qsub.data(), qnoff, thr, &tsub), pcr_gather(qes.data(), qeoff, thr, &tes), pcr_gather(qet.data(), qeoff, thr, &tet);
@@ -359,9 +409,9 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
         lout.insert(lout.end(), res.link_out.begin() + res.link_off[t], res.link_out.begin() + res.link_off[t + 1]);
         lcnt.insert(lcnt.end(), res.link_counts.begin() + res.link_off[t], res.link_counts.begin() + res.link_off[t + 1]);
         loff[f + 1] = lin.size();
-        const uint32_t g = alive[found[f]];
-        if (out->threaded) out->threaded[g] = 1;
-        if (out->n_paired_links) out->n_paired_links[g] = res.n_paired[t];
+        shk_pcr_run_out &o = outs[alive[found[f]] / ng];
+        if (o.threaded) o.threaded[fgene[f]] = 1;
+        if (o.n_paired_links) o.n_paired_links[fgene[f]] = res.n_paired[t];
         ++t;
       }
     }
@@ -370,229 +420,60 @@ int pcr_run_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_p
     G.n_genes = nf;
     G.node_sub_kmers = qsub.data(), G.node_flags = qflags.data(), G.node_offsets = qnoff.data();
     G.edge_src = qes.data(), G.edge_tgt = qet.data(), G.edge_counts = qec.data(), G.coverage_ratio = qratio.data(), G.edge_offsets = qeoff.data();
-    lin.resize(std::max<size_t>(lin.size(), 1)), lout.resize(lin.size()), lcnt.resize(lin.size());
     if (nt) {
+      lin.resize(std::max<size_t>(lin.size(), 1)), lout.resize(lin.size()), lcnt.resize(lin.size());
       G.support_total = stot.data(), G.support_unambiguous = suna.data(), G.link_offsets = loff.data();
       G.link_in = lin.data(), G.link_out = lout.data(), G.link_counts = lcnt.data(), G.has_threading = has.data();
     }
     std::vector<shk_pcr_paths_params> path_p;
     std::vector<uint32_t> dedup_t;
     pcr_products_params(genes, fgene, &path_p, &dedup_t);
+    // The records: plain, into the caller's arrays under the caller's capacities — short there is this call's outcome, with
+    // everything per gene complete; a sweep, into arrays of this call's, sized by a second call when the first guess was
+    // short.  The per-gene arrays are this call's either way.
     std::vector<uint64_t> roff(nf + 1, 0), paths_found(nf, 0), generated(nf, 0), states(nf, 0);
-    shk_pcr_records loc = R;  // the caller's record arrays and capacities; the per-gene arrays are this call's
-    loc.record_offsets = roff.data(), loc.paths_found = paths_found.data(), loc.generated = generated.data(), loc.states_explored = states.data();
-    products_rc = shk_pcr_products_panel(c, &G, path_p.data(), dedup_t.data(), &loc, nullptr, nullptr);
-    if (products_rc != SHK_OK && !(products_rc == SHK_ERR_BAD_ARG && (loc.n_records > R.record_cap || loc.n_seq_bytes > R.seq_cap))) return products_rc;
-    R.n_records = loc.n_records, R.n_seq_bytes = loc.n_seq_bytes;
-    for (uint32_t f = 0; f < nf; ++f) {
-      const uint32_t g = alive[found[f]];
-      R.record_offsets[g + 1] = roff[f + 1] - roff[f];  // (lengths; summed below)
-      if (R.paths_found) R.paths_found[g] = paths_found[f];
-      if (R.generated) R.generated[g] = generated[f];
-      if (R.states_explored) R.states_explored[g] = states[f];
-      if (out->n_pruned_nodes) out->n_pruned_nodes[g] = qnoff[f + 1] - qnoff[f];
-      if (out->n_pruned_edges) out->n_pruned_edges[g] = qeoff[f + 1] - qeoff[f];
-      if (generated[f]) status[g] = SHK_PCR_SUCCESS;  // mod.rs:735-743; otherwise the reason of step 5 stays
-    }
-    for (uint32_t g = 0; g < ng; ++g) R.record_offsets[g + 1] += R.record_offsets[g];
-  }
-  std::copy(status.begin(), status.end(), out->status);
-  if (getenv("SHK_TRACE"))  // (read at each call, like the stages' lines)
-    for (uint32_t g = 0; g < ng; ++g)
-      fprintf(stderr, "[shk] pcr_run: gene %u '%s': %s, primer k-mers %llu + %llu, threshold %u after %u steps, %llu nodes, %llu edges, %llu reads matched%s, %llu products\n",
-              g, genes[g].gene_name, status[g] == SHK_PCR_SUCCESS ? "success" : shk_pcr_failure_reason(status[g]),
-              (ull)(poff[2 * g + 1] - poff[2 * g]), (ull)(poff[2 * g + 2] - poff[2 * g + 1]), out->threshold_used ? out->threshold_used[g] : 0u,
-              out->steps_run ? out->steps_run[g] : 0u, (ull)(out->n_nodes ? out->n_nodes[g] : 0), (ull)(out->n_edges ? out->n_edges[g] : 0),
-              (ull)(out->n_reads_matched ? out->n_reads_matched[g] : 0), out->threaded && out->threaded[g] ? ", threaded" : "",
-              (ull)(R.record_offsets[g + 1] - R.record_offsets[g]));
-  return products_rc;  // (SHK_OK, or the record capacities' SHK_ERR_BAD_ARG with everything per gene complete)
-}
-
-// shk_pcr_run_depths: pcr_run_impl's stages for reads = NONE over the virtual genes v = j · ng + g (gene g
-// at depths[j]) — each stage called once for the virtual genes still alive — and every figure to outs[j]'s slot g.
-int pcr_run_depths_impl(shk_ctx *c, const shk_pcr_gene *genes, uint32_t ng, const shk_pcr_run_params *p, const uint32_t *depths,
-                        uint32_t D, shk_pcr_run_out *outs) {
-  using ull = unsigned long long;
-  // ---- everything that is refused, before the device is touched ----
-  SHK_TRY(depth_call_begin(c, "shk_pcr_run_depths", depths, D, true));
-  for (uint32_t j = 0; j < D; ++j)
-    if (!outs[j].status || !outs[j].records.record_offsets) return SHK_ERR_BAD_ARG;
-  if ((uint64_t)ng * D > SHK_PCR_MAX_GENES)
-    return fail(c, SHK_ERR_BAD_ARG, "n_genes %u x n_depths %u above SHK_PCR_MAX_GENES (%u)", ng, D, (unsigned)SHK_PCR_MAX_GENES);
-  for (uint32_t j = 0; j < D; ++j) pcr_out_clear(&outs[j], ng);
-  if (p->reads != SHK_PCR_READS_NONE) return fail(c, SHK_ERR_BAD_ARG, "shk_pcr_run_depths: a depth sweep takes no reads");
-  std::vector<shk_primer> primers;
-  std::vector<uint32_t> min_count;
-  uint64_t primer_cap = 0;
-  SHK_TRY(pcr_genes_check(c, genes, ng, p, &primers, &min_count, &primer_cap));
-  if (ng == 0) return SHK_OK;
-  const uint32_t nv = ng * D;
-  auto out_of = [&](uint32_t v) -> shk_pcr_run_out & { return outs[v / ng]; };
-
-  // ---- step 2: the primer k-mers of every (gene, depth) in one fused table pass: slot 2v + direction ----
-  primer_cap *= D;
-  std::vector<uint64_t> pk(std::max<uint64_t>(primer_cap, 1)), poff(2 * (size_t)nv + 1, 0);
-  std::vector<uint32_t> pc(pk.size());
-  std::vector<uint8_t> plev(pk.size());
-  SHK_TRY(shk_primer_kmers_depths(c, primers.data(), 2 * ng, depths, D, pk.data(), pc.data(), plev.data(), primer_cap, poff.data(), nullptr));
-  std::vector<uint64_t> budget(D, p->max_num_nodes);
-  if (!p->max_num_nodes) {  // main.rs:147-165 on the bases of the chunks below the depth
-    std::vector<uint64_t> cb(c->n_lanes);
-    SHK_TRY(shk_chunk_bases(c, cb.data()));
-    uint64_t sum = 0;
-    for (uint32_t j = 0, l = 0; j < D; ++j) {
-      for (; l < depths[j]; ++l) sum += cb[l];
-      budget[j] = shk_pcr_node_budget(sum);
-    }
-  }
-  std::vector<uint32_t> status(nv, SHK_PCR_NO_PATH), alive;  // alive: both sets found
-  for (uint32_t v = 0; v < nv; ++v) {
-    shk_pcr_run_out &o = out_of(v);
-    const uint32_t g = v % ng;
-    const uint64_t nf = poff[2 * v + 1] - poff[2 * v], nr = poff[2 * v + 2] - poff[2 * v + 1];
-    const uint32_t mf = nf ? *std::max_element(pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 1]) : 0;
-    const uint32_t mr = nr ? *std::max_element(pc.begin() + poff[2 * v + 1], pc.begin() + poff[2 * v + 2]) : 0;
-    if (o.n_fwd_kmers) o.n_fwd_kmers[g] = (uint32_t)nf;
-    if (o.n_rev_kmers) o.n_rev_kmers[g] = (uint32_t)nr;
-    if (o.max_fwd_count) o.max_fwd_count[g] = mf;
-    if (o.max_rev_count) o.max_rev_count[g] = mr;
-    if (!nf || !nr) {
-      status[v] = !nf && !nr ? SHK_PCR_NO_PRIMERS : !nf ? SHK_PCR_NO_FORWARD : SHK_PCR_NO_REVERSE;
-      continue;
-    }
-    if (o.median_primer_count)
-      o.median_primer_count[g] = std::min(pcr_median_count(pc.data() + poff[2 * v], nf), pcr_median_count(pc.data() + poff[2 * v + 1], nr));
-    if (o.low_primer_counts) o.low_primer_counts[g] = mf < 5 || mr < 5;
-    alive.push_back(v);
-  }
-  const uint32_t na = (uint32_t)alive.size();
-
-  // ---- step 4: the extension of the alive pairs, each at its depth ----
-  PcrExtended X(na);
-  const std::vector<uint64_t> &xnoff = X.noff, &xeoff = X.eoff;
-  const std::vector<uint32_t> &xfound = X.found, &xthr = X.thr, &xsteps = X.steps;
-  std::vector<uint32_t> found;  // positions in alive
-  if (na) {
-    std::vector<uint64_t> ak, aoff(2 * (size_t)na + 1, 0);
-    std::vector<uint32_t> ac, adepth(na);
-    std::vector<shk_pcr_extend_params> xp(na);
-    for (uint32_t a = 0; a < na; ++a) {
-      const uint32_t v = alive[a], g = v % ng;
-      ak.insert(ak.end(), pk.begin() + poff[2 * v], pk.begin() + poff[2 * v + 2]);
-      ac.insert(ac.end(), pc.begin() + poff[2 * v], pc.begin() + poff[2 * v + 2]);
-      aoff[2 * a + 1] = aoff[2 * a] + (poff[2 * v + 1] - poff[2 * v]);
-      aoff[2 * a + 2] = aoff[2 * a] + (poff[2 * v + 2] - poff[2 * v]);
-      xp[a] = shk_pcr_extend_params{min_count[g], p->min_kmer_count, genes[g].high_coverage_ratio, budget[v / ng], 1u, 0u};
-      adepth[a] = depths[v / ng];
-    }
-    SHK_TRY(pcr_extend_stage(c, ak, ac, aoff, na, xp, adepth.data(), &X));
-    for (uint32_t a = 0; a < na; ++a) {
-      const uint32_t v = alive[a], g = v % ng;
-      shk_pcr_run_out &o = out_of(v);
-      const uint64_t nn = xnoff[a + 1] - xnoff[a];
-      if (o.threshold_used) o.threshold_used[g] = xthr[a];
-      if (o.steps_run) o.steps_run[g] = xsteps[a];
-      if (o.found_path) o.found_path[g] = xfound[a];
-      if (o.n_nodes) o.n_nodes[g] = nn;
-      if (o.n_edges) o.n_edges[g] = xeoff[a + 1] - xeoff[a];
-      status[v] = nn >= budget[v / ng] ? SHK_PCR_NODE_BUDGET : SHK_PCR_NO_PATH;
-      if (xfound[a]) found.push_back(a);
-    }
-  }
-  const uint32_t nf = (uint32_t)found.size();
-
-  // ---- step 6, for the pairs with a path: one prune, one products call (no reads: no threading) ----
-  int short_rc = SHK_OK;
-  if (nf) {
-    std::vector<uint32_t> fgene(nf);  // the gene of every pair with a path
-    std::vector<double> tip(nf);
-    for (uint32_t f = 0; f < nf; ++f) fgene[f] = alive[found[f]] % ng, tip[f] = genes[fgene[f]].tip_coverage_fraction;
-    PcrPruned Q;
-    SHK_TRY(pcr_prune_stage(c, X, found, tip, &Q));
-    const std::vector<uint64_t> &qnoff = Q.noff, &qeoff = Q.eoff;
-    shk_pcr_graphs G{};
-    G.n_genes = nf;
-    G.node_sub_kmers = Q.sub.data(), G.node_flags = Q.flags.data(), G.node_offsets = Q.noff.data();
-    G.edge_src = Q.es.data(), G.edge_tgt = Q.et.data(), G.edge_counts = Q.ec.data(), G.coverage_ratio = Q.ratio.data(), G.edge_offsets = Q.eoff.data();
-    std::vector<shk_pcr_paths_params> path_p;
-    std::vector<uint32_t> dedup_t;
-    pcr_products_params(genes, fgene, &path_p, &dedup_t);
-    // the records of all pairs into arrays of this call's (sized by a second call when the first guess was short) …
-    std::vector<uint64_t> roff(nf + 1, 0), paths_found(nf, 0), generated(nf, 0), states(nf, 0), seq_off, path_nodes, cmin, cmax;
-    std::vector<uint8_t> seqs;
-    std::vector<uint32_t> start_node;
-    std::vector<double> cmean, cmedian, score, fields;
+    PcrRecordArrays own(64ull * nf, 1ull << 20);
     shk_pcr_records loc{};
-    uint64_t rcap = 64ull * nf, scap = 1ull << 20;
     for (int attempt = 0;; ++attempt) {
-      seq_off.assign(rcap + 1, 0), seqs.resize(std::max<uint64_t>(scap, 1)), start_node.resize(std::max<uint64_t>(rcap, 1));
-      path_nodes.resize(start_node.size()), cmin.resize(start_node.size()), cmax.resize(start_node.size());
-      cmean.resize(start_node.size()), cmedian.resize(start_node.size()), score.resize(start_node.size());
-      fields.resize(start_node.size() * SHK_PCR_SCORE_FIELDS);
-      loc = shk_pcr_records{};
-      loc.record_offsets = roff.data(), loc.seq_offsets = seq_off.data(), loc.seqs = seqs.data(), loc.record_cap = rcap, loc.seq_cap = scap;
-      loc.start_node = start_node.data(), loc.path_nodes = path_nodes.data(), loc.count_mean = cmean.data(), loc.count_median = cmedian.data();
-      loc.count_min = cmin.data(), loc.count_max = cmax.data(), loc.score = score.data(), loc.score_fields = fields.data();
-      loc.paths_found = paths_found.data(), loc.generated = generated.data(), loc.states_explored = states.data();
-      const int rc = shk_pcr_products_panel(c, &G, path_p.data(), dedup_t.data(), &loc, nullptr, nullptr);
-      if (rc == SHK_ERR_BAD_ARG && attempt == 0 && (loc.n_records > rcap || loc.n_seq_bytes > scap)) {
-        rcap = std::max(rcap, (uint64_t)loc.n_records), scap = std::max(scap, (uint64_t)loc.n_seq_bytes);
-        continue;
-      }
-      SHK_TRY(rc);
-      break;
+      loc = sweep ? own.bind(0, PcrRecordArrays::NODES | PcrRecordArrays::SCORE_FIELDS) : outs[0].records;
+      loc.record_offsets = roff.data(), loc.paths_found = paths_found.data(), loc.generated = generated.data(), loc.states_explored = states.data();
+      short_rc = shk_pcr_products_panel(c, &G, path_p.data(), dedup_t.data(), &loc, nullptr, nullptr);
+      if (!(short_rc == SHK_ERR_BAD_ARG && PcrRecordArrays::is_short(loc))) SHK_TRY(short_rc);  // (anything but short room)
+      if (short_rc == SHK_OK || !sweep) break;
+      if (attempt) return short_rc;
+      own.grow(loc);
     }
-    // … and from there each depth's into its outs[j], under that one's capacities: found is ascending in v, so a
-    // depth's pairs are a run [f0, f1) of it and their records a run of the records
+    // found is ascending in v, so a block's virtual genes are a run [f0, f1) of it and their records a run of the records
     for (uint32_t j = 0, f0 = 0; j < D; ++j) {
       uint32_t f1 = f0;
       while (f1 < nf && alive[found[f1]] / ng == j) ++f1;
       shk_pcr_run_out &o = outs[j];
       shk_pcr_records &R = o.records;
       for (uint32_t f = f0; f < f1; ++f) {
-        const uint32_t v = alive[found[f]], g = v % ng;
+        const uint32_t g = fgene[f];
         R.record_offsets[g + 1] = roff[f + 1] - roff[f];  // (lengths; summed below)
         if (R.paths_found) R.paths_found[g] = paths_found[f];
         if (R.generated) R.generated[g] = generated[f];
         if (R.states_explored) R.states_explored[g] = states[f];
         if (o.n_pruned_nodes) o.n_pruned_nodes[g] = qnoff[f + 1] - qnoff[f];
         if (o.n_pruned_edges) o.n_pruned_edges[g] = qeoff[f + 1] - qeoff[f];
-        if (generated[f]) status[v] = SHK_PCR_SUCCESS;
+        if (generated[f]) status[alive[found[f]]] = SHK_PCR_SUCCESS;  // mod.rs:735-743; otherwise the reason of step 5 stays
       }
       for (uint32_t g = 0; g < ng; ++g) R.record_offsets[g + 1] += R.record_offsets[g];
-      const uint64_t r0 = roff[f0], nr = roff[f1] - r0, b0 = seq_off[r0], nb = seq_off[roff[f1]] - b0;
-      R.n_records = nr, R.n_seq_bytes = nb;
+      std::string err;
+      if (!sweep)
+        R.n_records = loc.n_records, R.n_seq_bytes = loc.n_seq_bytes;  // (the records are where the products call wrote them)
+      else if (pcr_records_slice(loc, roff[f0], roff[f1] - roff[f0], &R, &err) != SHK_OK && short_rc == SHK_OK)
+        short_rc = fail(c, SHK_ERR_BAD_ARG, "%s", err.c_str());  // (the first short block's text; every block is still completed)
       f0 = f1;
-      if (nr > R.record_cap || (R.seqs && nb > R.seq_cap)) {  // pcr_records_store's condition and text
-        if (short_rc == SHK_OK)
-          short_rc = fail(c, SHK_ERR_BAD_ARG, "%llu records of %llu bases do not fit record_cap %llu / seq_cap %llu", (ull)nr, (ull)nb,
-                          (ull)R.record_cap, (ull)R.seq_cap);
-        continue;
-      }
-      if (R.seq_offsets) R.seq_offsets[0] = 0;
-      if (R.seqs && nb) memcpy(R.seqs, seqs.data() + b0, nb);
-      for (uint64_t i = 0; i < nr; ++i) {
-        if (R.seq_offsets) R.seq_offsets[i + 1] = seq_off[r0 + i + 1] - b0;
-        if (R.start_node) R.start_node[i] = start_node[r0 + i];
-        if (R.path_nodes) R.path_nodes[i] = path_nodes[r0 + i];
-        if (R.count_mean) R.count_mean[i] = cmean[r0 + i];
-        if (R.count_median) R.count_median[i] = cmedian[r0 + i];
-        if (R.count_min) R.count_min[i] = cmin[r0 + i];
-        if (R.count_max) R.count_max[i] = cmax[r0 + i];
-        if (R.score) R.score[i] = score[r0 + i];
-        if (R.score_fields)
-          std::copy(fields.begin() + SHK_PCR_SCORE_FIELDS * (r0 + i), fields.begin() + SHK_PCR_SCORE_FIELDS * (r0 + i + 1),
-                    R.score_fields + SHK_PCR_SCORE_FIELDS * i);
-      }
     }
   }
-  for (uint32_t v = 0; v < nv; ++v) out_of(v).status[v % ng] = status[v];
-  if (getenv("SHK_TRACE"))
+  for (uint32_t v = 0; v < nv; ++v) outs[v / ng].status[v % ng] = status[v];
+  if (getenv("SHK_TRACE"))  // (read at each call, like the stages' lines)
     for (uint32_t v = 0; v < nv; ++v)
-      fprintf(stderr, "[shk] pcr_run_depths: depth %u gene %u '%s': %s, primer k-mers %llu + %llu\n", depths[v / ng], v % ng,
-              genes[v % ng].gene_name, status[v] == SHK_PCR_SUCCESS ? "success" : shk_pcr_failure_reason(status[v]),
-              (ull)(poff[2 * v + 1] - poff[2 * v]), (ull)(poff[2 * v + 2] - poff[2 * v + 1]));
-  return short_rc;  // (SHK_OK, or the record capacities' SHK_ERR_BAD_ARG with every outs[j] complete)
+      pcr_trace_line(genes[v % ng], v % ng, status[v], poff[2 * v + 1] - poff[2 * v], poff[2 * v + 2] - poff[2 * v + 1], outs[v / ng],
+                     sweep ? depths[v / ng] : 0u);
+  return short_rc;  // (SHK_OK, or the record capacities' SHK_ERR_BAD_ARG with every block complete)
 }
 
 }  // namespace
@@ -602,7 +483,7 @@ extern "C" int shk_pcr_run_depths(shk_ctx *c, const shk_pcr_gene *genes, uint32_
   SHK_TRY(xs_closed(c));
   if (!c || !params || !outs || (n_genes && !genes)) return SHK_ERR_BAD_ARG;
   try {
-    return pcr_run_depths_impl(c, genes, n_genes, params, depths, n_depths, outs);
+    return pcr_pipeline(c, genes, n_genes, params, true, depths, n_depths, outs);
   } catch (...) {  // no exception leaves the C ABI
     return fail(c, SHK_ERR_NOMEM, "shk_pcr_run_depths: out of host memory");
   }
@@ -612,7 +493,7 @@ extern "C" int shk_pcr_run(shk_ctx *c, const shk_pcr_gene *genes, uint32_t n_gen
   SHK_TRY(xs_closed(c));
   if (!c || !params || !out || !out->status || !out->records.record_offsets || (n_genes && !genes)) return SHK_ERR_BAD_ARG;
   try {
-    return pcr_run_impl(c, genes, n_genes, params, out);
+    return pcr_pipeline(c, genes, n_genes, params, false, nullptr, 1, out);
   } catch (...) {  // no exception leaves the C ABI
     return fail(c, SHK_ERR_NOMEM, "shk_pcr_run: out of host memory");
   }

@@ -368,9 +368,40 @@ int pcr_paths_panel_run(uint32_t k, const shk_pcr_graphs *gr, const shk_pcr_path
   return SHK_OK;
 }
 
+int pcr_records_fit(const shk_pcr_records &out, std::string *err) {
+  using ull = unsigned long long;
+  if (out.n_records <= out.record_cap && (!out.seqs || out.n_seq_bytes <= out.seq_cap)) return SHK_OK;
+  char buf[256];
+  snprintf(buf, sizeof buf, "%llu records of %llu bases do not fit record_cap %llu / seq_cap %llu", (ull)out.n_records, (ull)out.n_seq_bytes,
+           (ull)out.record_cap, (ull)out.seq_cap);
+  *err = buf;
+  return SHK_ERR_BAD_ARG;
+}
+
+int pcr_records_slice(const shk_pcr_records &src, uint64_t r0, uint64_t nr, shk_pcr_records *out, std::string *err) {
+  const uint64_t b0 = src.seq_offsets[r0], nb = src.seq_offsets[r0 + nr] - b0;
+  out->n_records = nr, out->n_seq_bytes = nb;
+  if (const int rc = pcr_records_fit(*out, err)) return rc;
+  if (out->seq_offsets) out->seq_offsets[0] = 0;
+  if (out->seqs && nb) memcpy(out->seqs, src.seqs + b0, nb);
+  for (uint64_t i = 0, r = r0; i < nr; ++i, ++r) {
+    if (out->seq_offsets) out->seq_offsets[i + 1] = src.seq_offsets[r + 1] - b0;
+    if (out->start_node) out->start_node[i] = src.start_node[r];
+    if (out->path_nodes) out->path_nodes[i] = src.path_nodes[r];
+    if (out->count_mean) out->count_mean[i] = src.count_mean[r];
+    if (out->count_median) out->count_median[i] = src.count_median[r];
+    if (out->count_min) out->count_min[i] = src.count_min[r];
+    if (out->count_max) out->count_max[i] = src.count_max[r];
+    if (out->score) out->score[i] = src.score[r];
+    if (out->score_fields)
+      std::copy(src.score_fields + SHK_PCR_SCORE_FIELDS * r, src.score_fields + SHK_PCR_SCORE_FIELDS * (r + 1),
+                out->score_fields + SHK_PCR_SCORE_FIELDS * i);
+  }
+  return SHK_OK;
+}
+
 int pcr_records_store(const std::vector<PcrGeneRecords> &records, const std::vector<std::vector<uint32_t>> *pick, shk_pcr_records *out,
                       std::string *err) {
-  using ull = unsigned long long;
   const size_t ng = records.size();
   uint64_t nr = 0, nb = 0;
   out->record_offsets[0] = 0;
@@ -388,13 +419,7 @@ int pcr_records_store(const std::vector<PcrGeneRecords> &records, const std::vec
     if (out->states_explored) out->states_explored[g] = r.states_explored;
   }
   out->n_records = nr, out->n_seq_bytes = nb;
-  if (nr > out->record_cap || (out->seqs && nb > out->seq_cap)) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%llu records of %llu bases do not fit record_cap %llu / seq_cap %llu", (ull)nr, (ull)nb, (ull)out->record_cap,
-             (ull)out->seq_cap);
-    *err = buf;
-    return SHK_ERR_BAD_ARG;
-  }
+  if (const int rc = pcr_records_fit(*out, err)) return rc;
   uint64_t at = 0, sb = 0;
   if (out->seq_offsets) out->seq_offsets[0] = 0;
   for (size_t g = 0; g < ng; ++g) {

@@ -1,5 +1,7 @@
 // The part of the C ABI that reads the table or hands it to a peer: export, lookup, the sPCR scans (neighborhood, extend,
-// find_oligos, primer_kmers), the read filters, and the owner exchange (geometry, merge, counts, compaction, owned ranges).
+// find_oligos, primer_kmers — each of the first two and the last with its depth form as a second caller of ONE body:
+// nb_panel_call, pcr_extend_panel_call, primer_scan), the read filters, and the owner exchange (geometry, merge, counts,
+// compaction, owned ranges).
 // Included at the end of shk_engine.hip (one translation unit: the context, settle and the helpers beside HIPC are there).
 //
 // A call that reads the table begins with table_read_begin; one that does not says why where it departs.
@@ -428,6 +430,45 @@ int pcr_graphs_out(shk_ctx *c, const char *what, const std::vector<PcrGraph> &gs
   return SHK_OK;
 }
 
+// One primer scan pass over c's slots (the owned pages of an owner share) for the searched primers dev, per_launch of
+// them at a time: launch(grid, s0, s1, the launch's primers on the device, how many, the first one's index, drec, dn,
+// dhits) starts k_primer_scan or k_primer_scan_depths.  Back come the n_hits per-(primer, level) hits and, when they fit
+// in `room`, the records.  *n_total = records the pass produced (> room: none returned).
+template <class Dev, class Launch>
+int primer_pass(shk_ctx *c, const std::vector<Dev> &dev, size_t n_hits, uint32_t per_launch, uint64_t room, std::vector<PrimerRec> *recs,
+                std::vector<uint64_t> *hits, uint64_t *n_total, Launch launch) {
+  SHK_TRY(table_read_begin(c));
+  const uint32_t n = (uint32_t)dev.size();
+  Scratch m{c->misc};
+  const size_t o_n = m.take<unsigned long long>(1), o_hits = m.take<unsigned long long>(n_hits);  // (adjacent)
+  const size_t o_prim = m.take<Dev>(n), o_rec = m.take<PrimerRec>(room);
+  HIPC(c, m.ensure());
+  unsigned long long *dn = m.at<unsigned long long>(o_n), *dhits = m.at<unsigned long long>(o_hits);
+  Dev *dprim = m.at<Dev>(o_prim);
+  PrimerRec *drec = m.at<PrimerRec>(o_rec);
+  HIPC(c, hipMemsetAsync(dn, 0, o_prim - o_n, c->stream));  // the record counter and the hits
+  HIPC(c, hipMemcpyAsync(dprim, dev.data(), (size_t)n * sizeof(Dev), hipMemcpyHostToDevice, c->stream));
+  const auto [s0, s1] = owned_slots(c);
+  for (uint32_t b = 0; b < n; b += per_launch) {
+    const uint32_t nb = std::min(per_launch, n - b);
+    ScopedTimer t(c, SHK_K_LOOKUP);
+    launch(dim3(grid_for(s1 - s0, WG * 8, 2048)), s0, s1, (const Dev *)(dprim + b), nb, b, drec, dn, dhits);
+  }
+  HIPC(c, hipGetLastError());
+  unsigned long long nt = 0;
+  hits->assign(n_hits, 0);
+  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(hits->data(), dhits, n_hits * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps dev alive until its copy ran)
+  *n_total = nt;
+  recs->clear();
+  if (nt <= room && nt) {
+    recs->resize(nt);
+    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
+  }
+  return SHK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -729,49 +770,6 @@ int shk_find_oligos(shk_ctx *c, const uint64_t *oligos, uint32_t n_oligos, uint3
 
 namespace {
 
-// One k_primer_scan pass over c's slots (the owned pages of an owner share): the per-(primer, level) hits (dev's
-// order) and, when they fit in `room`, the records.  *n_total = records the pass produced (> room: none returned).
-int primer_pass(shk_ctx *c, const std::vector<PrimerDev> &dev, uint64_t room, std::vector<PrimerRec> *recs,
-                std::vector<uint64_t> *hits, uint64_t *n_total) {
-  SHK_TRY(table_read_begin(c));
-  const uint32_t n = (uint32_t)dev.size();
-  uint32_t stride = 1;  // LDS counters per primer: levels 0..max M
-  for (const PrimerDev &d : dev) stride = std::max(stride, d.M + 1);
-  // primers per launch: their table and counters in 48 KiB of LDS (three workgroups per CU)
-  const uint32_t per_launch = (48u << 10) / (uint32_t)(sizeof(PrimerDev) + 4 * stride);
-  const size_t hits_b = (size_t)n * SHK_PRIMER_LEVELS * 8, prim_b = (size_t)n * sizeof(PrimerDev);
-  Scratch m{c->misc};
-  const size_t o_n = m.take<unsigned long long>(1), o_hits = m.take<unsigned long long>((size_t)n * SHK_PRIMER_LEVELS);  // (adjacent)
-  const size_t o_prim = m.take<PrimerDev>(n), o_rec = m.take<PrimerRec>(room);
-  HIPC(c, m.ensure());
-  unsigned long long *dn = m.at<unsigned long long>(o_n), *dhits = m.at<unsigned long long>(o_hits);
-  PrimerDev *dprim = m.at<PrimerDev>(o_prim);
-  PrimerRec *drec = m.at<PrimerRec>(o_rec);
-  HIPC(c, hipMemsetAsync(dn, 0, o_prim - o_n, c->stream));  // the record counter and the hits
-  HIPC(c, hipMemcpyAsync(dprim, dev.data(), prim_b, hipMemcpyHostToDevice, c->stream));
-  const auto [s0, s1] = owned_slots(c);
-  for (uint32_t b = 0; b < n; b += per_launch) {
-    const uint32_t nb = std::min(per_launch, n - b);
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_primer_scan, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG),
-                       (size_t)nb * (sizeof(PrimerDev) + 4 * stride), c->stream, c->tb, s0, s1, (int)c->cfg.k,
-                       (const PrimerDev *)(dprim + b), nb, b, stride, drec, (uint64_t)room, dn, dhits);
-  }
-  HIPC(c, hipGetLastError());
-  unsigned long long nt = 0;
-  hits->assign((size_t)n * SHK_PRIMER_LEVELS, 0);
-  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(hits->data(), dhits, hits_b, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps dev alive until its copy ran)
-  *n_total = nt;
-  recs->clear();
-  if (nt <= room && nt) {
-    recs->resize(nt);
-    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
-  }
-  return SHK_OK;
-}
-
 // Selection: per primer, level ascending, count descending, k-mer ascending (discover_primer_kmers_by_round's
 // sort, primers.rs:407-408, applied round by round), the first max_kmers.  Equal output k-mers are never merged
 // here: a table entry x yields x and revcomp(x) (distinct unless x is a palindrome, and then f = r yields it once),
@@ -817,68 +815,16 @@ void primer_select(const std::vector<PrimerRec> &all, const std::vector<uint64_t
   offsets[n_slots] = o;
 }
 
-// The fused pass of shk_primer_kmers_depths: k_primer_scan_depths over c's slots for the searched primers dev at the
-// depths dep; cut[j · n + p]: the highest level kept of primer p at depth j.  Records and hits come back for the
-// virtual primers j · n + p, as primer_pass returns them for its primers.
-int primer_pass_depths(shk_ctx *c, const std::vector<PrimerDev> &dev, const std::vector<uint32_t> &cut, const PrimerDepths &dep,
-                       uint64_t room, std::vector<PrimerRec> *recs, std::vector<uint64_t> *hits, uint64_t *n_total) {
-  SHK_TRY(table_read_begin(c));
-  const uint32_t n = (uint32_t)dev.size(), D = dep.n;
-  std::vector<PrimerDevD> devd(n);
-  uint32_t stride = 1;  // LDS counters per (primer, depth): levels 0..max cut
-  for (uint32_t p = 0; p < n; ++p) {
-    devd[p].p = dev[p];
-    devd[p].p.M = 0;
-    for (uint32_t j = 0; j < SHK_PCR_MAX_DEPTHS; ++j) {
-      const uint32_t m = j < D ? cut[(size_t)j * n + p] : 0u;
-      devd[p].cut[j] = (uint8_t)m;
-      devd[p].p.M = std::max(devd[p].p.M, m);
-    }
-    stride = std::max(stride, devd[p].p.M + 1);
-  }
-  // primers per launch group: their table and D × the counters in 48 KiB of LDS (three workgroups per CU)
-  const uint32_t per_primer = (uint32_t)sizeof(PrimerDevD) + 4 * stride * D;
-  const uint32_t per_launch = std::max(1u, (48u << 10) / per_primer);
-  const size_t n_hits = (size_t)D * n * SHK_PRIMER_LEVELS;
-  Scratch m{c->misc};
-  const size_t o_n = m.take<unsigned long long>(1), o_hits = m.take<unsigned long long>(n_hits);  // (adjacent)
-  const size_t o_prim = m.take<PrimerDevD>(n), o_rec = m.take<PrimerRec>(room);
-  HIPC(c, m.ensure());
-  unsigned long long *dn = m.at<unsigned long long>(o_n), *dhits = m.at<unsigned long long>(o_hits);
-  PrimerDevD *dprim = m.at<PrimerDevD>(o_prim);
-  PrimerRec *drec = m.at<PrimerRec>(o_rec);
-  HIPC(c, hipMemsetAsync(dn, 0, o_prim - o_n, c->stream));  // the record counter and the hits
-  HIPC(c, hipMemcpyAsync(dprim, devd.data(), (size_t)n * sizeof(PrimerDevD), hipMemcpyHostToDevice, c->stream));
-  const auto [s0, s1] = owned_slots(c);
-  for (uint32_t b = 0; b < n; b += per_launch) {
-    const uint32_t nb = std::min(per_launch, n - b);
-    ScopedTimer t(c, SHK_K_LOOKUP);
-    hipLaunchKernelGGL(k_primer_scan_depths, dim3(grid_for(s1 - s0, WG * 8, 2048)), dim3(WG), (size_t)nb * per_primer, c->stream,
-                       c->tb, s0, s1, (int)c->cfg.k, (const PrimerDevD *)(dprim + b), nb, b, n, stride, dep, drec, (uint64_t)room, dn,
-                       dhits);
-  }
-  HIPC(c, hipGetLastError());
-  unsigned long long nt = 0;
-  hits->assign(n_hits, 0);
-  HIPC(c, hipMemcpyAsync(&nt, dn, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipMemcpyAsync(hits->data(), dhits, n_hits * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(c, hipStreamSynchronize(c->stream));  // (also keeps devd alive until its copy ran)
-  *n_total = nt;
-  recs->clear();
-  if (nt <= room && nt) {
-    recs->resize(nt);
-    HIPC(c, hipMemcpy(recs->data(), drec, nt * sizeof(PrimerRec), hipMemcpyDeviceToHost));
-  }
-  return SHK_OK;
-}
-
-}  // namespace
-
-int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
-                     uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
-  SHK_TRY(xs_closed(c));
-  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
-  if (n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
+// shk_primer_kmers and shk_primer_kmers_depths: ONE scan over parts × virtual primers j · n_primers + i (primer i in
+// block j).  Plain (sweep false): one block, no lane bound, k_primer_scan over the shares of a multi-device context
+// (disjoint: the answer is the top of the union) or over the context itself.  Sweep: primer i at depths[j] for D depths
+// in one part, the fused k_primer_scan_depths.  Either way: a first pass per part; on an overflow of a part's candidate
+// buffer — the counts are complete, so every virtual primer's cut level is known — a rerun of that part, sized exactly.
+int primer_scan(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, bool sweep, const uint32_t *depths, uint32_t D, uint64_t *kmers,
+                uint32_t *counts, uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  using ull = unsigned long long;
+  if (!sweep && n_primers >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u)", n_primers);
+  if (sweep && (uint64_t)n_primers * D >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u at %u depths)", n_primers, D);
   const uint32_t k = c->cfg.k;
   // preprocess_primer_by_mismatch of every direction before any scan (primers.rs:440-450), then the conversion
   // check of the searched ones (their first round, primers.rs:383-393)
@@ -894,96 +840,8 @@ int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, 
   }
   uint64_t need = 0;
   for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
-  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
-  if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
-  if (level_hits) std::fill(level_hits, level_hits + (size_t)n_primers * SHK_PRIMER_LEVELS, 0ull);
-  std::vector<uint32_t> who;  // searched primer j = primers[who[j]]
-  std::vector<PrimerDev> dev;
-  for (uint32_t i = 0; i < n_primers; ++i)
-    if (plans[i].scanned()) {
-      const PrimerPlan &pl = plans[i];
-      who.push_back(i);
-      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, pl.min_count, 0});
-    }
-  const uint32_t n = (uint32_t)dev.size();
-  std::vector<shk_ctx *> parts;  // a multi-device context: its shares are disjoint, the answer is the top of the union
-  if (c->group)
-    for (uint32_t d = 0; d < c->group->D; ++d) parts.push_back(c->group->ctx[d]);
-  else
-    parts.push_back(c);
-  auto part_fail = [&](int rc, uint32_t d) { return c->group ? group_fail(c, c->group, rc, d) : rc; };
-  std::vector<PrimerRec> all;
-  std::vector<uint64_t> hits((size_t)n * SHK_PRIMER_LEVELS, 0);
-  if (n) {
-    const int env_room = env_int("SHK_PRIMER_CANDIDATES", 1 << 18);
-    const uint64_t room = (uint64_t)std::max(env_room, 1);
-    std::vector<std::vector<uint64_t>> part_hits(parts.size());
-    std::vector<uint64_t> part_n(parts.size());
-    std::vector<PrimerRec> recs;
-    for (uint32_t d = 0; d < parts.size(); ++d) {
-      const int rc = primer_pass(parts[d], dev, room, &recs, &part_hits[d], &part_n[d]);
-      if (rc != SHK_OK) return part_fail(rc, d);
-      all.insert(all.end(), recs.begin(), recs.end());
-      for (size_t j = 0; j < hits.size(); ++j) hits[j] += part_hits[d][j];
-    }
-    // The record buffer overflowed: the counts are complete, so each primer's cut level is known — the first level
-    // at which its hits reach max_kmers.  Nothing above it can be selected; rerun keeping levels ≤ cut, sized exactly.
-    std::vector<PrimerDev> cut = dev;
-    for (uint32_t j = 0; j < n; ++j) {
-      uint64_t acc = 0;
-      for (uint32_t m = 0; m <= dev[j].M; ++m) {
-        acc += hits[(size_t)j * SHK_PRIMER_LEVELS + m];
-        if (acc >= plans[who[j]].max_kmers) {
-          cut[j].M = m;
-          break;
-        }
-      }
-    }
-    for (uint32_t d = 0; d < parts.size(); ++d) {
-      if (part_n[d] <= room) continue;
-      uint64_t exact = 0;
-      for (uint32_t j = 0; j < n; ++j)
-        for (uint32_t m = 0; m <= cut[j].M; ++m) exact += part_hits[d][(size_t)j * SHK_PRIMER_LEVELS + m];
-      std::vector<uint64_t> h2;
-      uint64_t n2 = 0;
-      const int rc = primer_pass(parts[d], cut, exact, &recs, &h2, &n2);
-      if (rc != SHK_OK) return part_fail(rc, d);
-      if (n2 != exact)
-        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu",
-                    (unsigned long long)n2, (unsigned long long)exact);
-      all.insert(all.end(), recs.begin(), recs.end());
-    }
-  }
-  std::vector<uint64_t> max_kmers(n);
-  for (uint32_t j = 0; j < n; ++j) max_kmers[j] = plans[who[j]].max_kmers;
-  primer_select(all, hits, who, max_kmers, n_primers, kmers, counts, levels, offsets, level_hits);
-  return SHK_OK;
-}
-
-// shk_primer_kmers over the virtual primers j · n_primers + i (primer i at depths[j]): the same checks, one fused pass
-// (and, on an overflow of the candidate buffer, one rerun with a cut level per virtual primer), the same selection.
-int shk_primer_kmers_depths(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, const uint32_t *depths, uint32_t n_depths,
-                            uint64_t *kmers, uint32_t *counts, uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
-  SHK_TRY(xs_closed(c));
-  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
-  SHK_TRY(depth_call_begin(c, "shk_primer_kmers_depths", depths, n_depths, true));
-  const uint32_t D = n_depths;
-  if ((uint64_t)n_primers * D >= (1u << 24)) return fail(c, SHK_ERR_BAD_ARG, "too many primers (%u at %u depths)", n_primers, D);
-  const uint32_t k = c->cfg.k;
-  std::vector<PrimerPlan> plans(n_primers);
-  std::string msg;
-  for (uint32_t i = 0; i < n_primers; ++i) {
-    const int rc = primer_plan(&primers[i], k, &plans[i], &msg);
-    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
-  }
-  for (uint32_t i = 0; i < n_primers; ++i) {
-    const int rc = primer_check_chars(plans[i], &msg);
-    if (rc != SHK_OK) return fail(c, rc, "%s", msg.c_str());
-  }
-  uint64_t need = 0;
-  for (const PrimerPlan &pl : plans) need += pl.scanned() ? pl.max_kmers : 0;
   need *= D;
-  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, "cap %llu < n_depths x sum of max_kmers %llu", (unsigned long long)cap, (unsigned long long)need);
+  if (cap < need) return fail(c, SHK_ERR_BAD_ARG, sweep ? "cap %llu < n_depths x sum of max_kmers %llu" : "cap %llu < sum of max_kmers %llu", (ull)cap, (ull)need);
   if (need && (!kmers || !counts || !levels)) return SHK_ERR_BAD_ARG;
   const uint32_t n_slots = n_primers * D;
   if (level_hits) std::fill(level_hits, level_hits + (size_t)n_slots * SHK_PRIMER_LEVELS, 0ull);
@@ -993,51 +851,121 @@ int shk_primer_kmers_depths(shk_ctx *c, const shk_primer *primers, uint32_t n_pr
     if (plans[i].scanned()) {
       const PrimerPlan &pl = plans[i];
       who1.push_back(i);
-      // (a key whose count at the depth is 0 is not in that depth's table: the floor of 1)
-      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, std::max(pl.min_count, 1u), 0});
+      // (a sweep: a key whose count at the depth is 0 is not in that depth's table — the floor of 1)
+      dev.push_back(PrimerDev{{pl.allow[0], pl.allow[1], pl.allow[2], pl.allow[3]}, pl.L, pl.M, sweep ? std::max(pl.min_count, 1u) : pl.min_count, 0});
     }
   const uint32_t n = (uint32_t)dev.size();
-  std::vector<uint32_t> who((size_t)n * D);  // searched virtual primer j · n + p is result slot j · n_primers + who1[p]
-  for (uint32_t j = 0; j < D; ++j)
-    for (uint32_t p = 0; p < n; ++p) who[(size_t)j * n + p] = j * n_primers + who1[p];
-  std::vector<PrimerRec> all;
-  std::vector<uint64_t> hits((size_t)n * D * SHK_PRIMER_LEVELS, 0);
-  if (n) {
-    PrimerDepths dep{};
-    dep.n = D;
-    for (uint32_t j = 0; j < D; ++j) dep.d[j] = depths[j];
-    const uint64_t room = (uint64_t)std::max(env_int("SHK_PRIMER_CANDIDATES", 1 << 18), 1);
-    std::vector<uint32_t> cut((size_t)n * D);
-    for (uint32_t j = 0; j < D; ++j)
-      for (uint32_t p = 0; p < n; ++p) cut[(size_t)j * n + p] = dev[p].M;
-    uint64_t n_total = 0;
-    SHK_TRY(primer_pass_depths(c, dev, cut, dep, room, &all, &hits, &n_total));
-    if (n_total > room) {  // as shk_primer_kmers: the counts are complete, so every virtual primer's cut level is known
-      uint64_t exact = 0;
-      for (size_t v = 0; v < cut.size(); ++v) {
-        const uint64_t max_kmers = plans[who1[v % n]].max_kmers;
-        uint64_t acc = 0;
-        for (uint32_t m = 0; m <= dev[v % n].M; ++m) {
-          acc += hits[v * SHK_PRIMER_LEVELS + m];
-          if (acc >= max_kmers) {
-            cut[v] = m;
-            break;
-          }
-        }
-        for (uint32_t m = 0; m <= cut[v]; ++m) exact += hits[v * SHK_PRIMER_LEVELS + m];
+  const size_t nv = (size_t)n * D, n_hits = nv * SHK_PRIMER_LEVELS;
+  std::vector<uint32_t> who(nv);  // searched virtual primer j · n + p is result slot j · n_primers + who1[p]
+  std::vector<uint64_t> max_kmers(nv);
+  for (size_t v = 0; v < nv; ++v) who[v] = (uint32_t)(v / n) * n_primers + who1[v % n], max_kmers[v] = plans[who1[v % n]].max_kmers;
+  std::vector<shk_ctx *> parts;
+  if (c->group)
+    for (uint32_t d = 0; d < c->group->D; ++d) parts.push_back(c->group->ctx[d]);
+  else
+    parts.push_back(c);
+  auto part_fail = [&](int rc, uint32_t d) { return c->group ? group_fail(c, c->group, rc, d) : rc; };
+  PrimerDepths dep{};
+  for (uint32_t j = 0; sweep && j < D; ++j) dep.d[dep.n++] = depths[j];
+  // one pass over a part keeping, of virtual primer v, the levels 0..cut[v]
+  auto pass = [&](shk_ctx *part, const std::vector<uint32_t> &cut, uint64_t room, std::vector<PrimerRec> *recs, std::vector<uint64_t> *hits,
+                  uint64_t *n_total) {
+    uint32_t stride = 1;  // LDS counters per virtual primer: levels 0..max cut
+    for (const uint32_t m : cut) stride = std::max(stride, m + 1);
+    if (!sweep) {
+      std::vector<PrimerDev> pd = dev;
+      for (uint32_t p = 0; p < n; ++p) pd[p].M = cut[p];
+      // primers per launch: their table and counters in 48 KiB of LDS (three workgroups per CU)
+      const uint32_t per_primer = (uint32_t)sizeof(PrimerDev) + 4 * stride;
+      return primer_pass(part, pd, n_hits, (48u << 10) / per_primer, room, recs, hits, n_total,
+                         [&](dim3 grid, auto s0, auto s1, const PrimerDev *dp, uint32_t nb, uint32_t b, PrimerRec *drec, ull *dn, ull *dhits) {
+                           hipLaunchKernelGGL(k_primer_scan, grid, dim3(WG), (size_t)nb * per_primer, part->stream, part->tb, s0, s1, (int)part->cfg.k,
+                                              dp, nb, b, stride, drec, room, dn, dhits);
+                         });
+    }
+    std::vector<PrimerDevD> pd(n);
+    for (uint32_t p = 0; p < n; ++p) {
+      pd[p].p = dev[p];
+      pd[p].p.M = 0;
+      for (uint32_t j = 0; j < SHK_PCR_MAX_DEPTHS; ++j) {
+        const uint32_t m = j < D ? cut[(size_t)j * n + p] : 0u;
+        pd[p].cut[j] = (uint8_t)m;
+        pd[p].p.M = std::max(pd[p].p.M, m);
       }
+    }
+    // primers per launch group: their table and D × the counters in 48 KiB of LDS (three workgroups per CU)
+    const uint32_t per_primer = (uint32_t)sizeof(PrimerDevD) + 4 * stride * D;
+    return primer_pass(part, pd, n_hits, std::max(1u, (48u << 10) / per_primer), room, recs, hits, n_total,
+                       [&](dim3 grid, auto s0, auto s1, const PrimerDevD *dp, uint32_t nb, uint32_t b, PrimerRec *drec, ull *dn, ull *dhits) {
+                         hipLaunchKernelGGL(k_primer_scan_depths, grid, dim3(WG), (size_t)nb * per_primer, part->stream, part->tb, s0, s1,
+                                            (int)part->cfg.k, dp, nb, b, n, stride, dep, drec, room, dn, dhits);
+                       });
+  };
+  std::vector<PrimerRec> all;
+  std::vector<uint64_t> hits(n_hits, 0);
+  if (n) {
+    const uint64_t room = (uint64_t)std::max(env_int("SHK_PRIMER_CANDIDATES", 1 << 18), 1);
+    std::vector<std::vector<uint64_t>> part_hits(parts.size());
+    std::vector<uint64_t> part_n(parts.size());
+    std::vector<PrimerRec> recs;
+    std::vector<uint32_t> cut(nv);
+    for (size_t v = 0; v < nv; ++v) cut[v] = dev[v % n].M;
+    // a pass over part d whose records are appended to `all` (straight into it while it is empty: no copy with one part)
+    auto pass_into_all = [&](uint32_t d, uint64_t room_d, std::vector<uint64_t> *hits_d, uint64_t *n_d) {
+      if (all.empty()) return pass(parts[d], cut, room_d, &all, hits_d, n_d);
+      const int rc = pass(parts[d], cut, room_d, &recs, hits_d, n_d);
+      all.insert(all.end(), recs.begin(), recs.end());
+      return rc;
+    };
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      const int rc = pass_into_all(d, room, &part_hits[d], &part_n[d]);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      for (size_t j = 0; j < n_hits; ++j) hits[j] += part_hits[d][j];
+    }
+    // A part overflowed.  The cut level of a virtual primer: the first level at which its hits, over all parts, reach
+    // max_kmers.  Nothing above it can be selected: the parts that overflowed run again keeping levels ≤ cut, sized exactly.
+    const bool overflowed = std::any_of(part_n.begin(), part_n.end(), [&](uint64_t x) { return x > room; });
+    for (size_t v = 0; overflowed && v < nv; ++v) {
+      uint64_t acc = 0;
+      for (uint32_t m = 0; m <= dev[v % n].M; ++m) {
+        acc += hits[v * SHK_PRIMER_LEVELS + m];
+        if (acc >= max_kmers[v]) {
+          cut[v] = m;
+          break;
+        }
+      }
+    }
+    for (uint32_t d = 0; d < parts.size(); ++d) {
+      if (part_n[d] <= room) continue;
+      uint64_t exact = 0;
+      for (size_t v = 0; v < nv; ++v)
+        for (uint32_t m = 0; m <= cut[v]; ++m) exact += part_hits[d][v * SHK_PRIMER_LEVELS + m];
       std::vector<uint64_t> h2;
       uint64_t n2 = 0;
-      SHK_TRY(primer_pass_depths(c, dev, cut, dep, exact, &all, &h2, &n2));
-      if (n2 != exact)
-        return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu", (unsigned long long)n2,
-                    (unsigned long long)exact);
+      const int rc = pass_into_all(d, exact, &h2, &n2);
+      if (rc != SHK_OK) return part_fail(rc, d);
+      if (n2 != exact) return fail(c, SHK_ERR_INVARIANT, "primer scan rerun produced %llu records, expected %llu", (ull)n2, (ull)exact);
     }
   }
-  std::vector<uint64_t> max_kmers(who.size());
-  for (size_t v = 0; v < who.size(); ++v) max_kmers[v] = plans[who1[v % n]].max_kmers;
   primer_select(all, hits, who, max_kmers, n_slots, kmers, counts, levels, offsets, level_hits);
   return SHK_OK;
+}
+
+}  // namespace
+
+int shk_primer_kmers(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, uint64_t *kmers, uint32_t *counts,
+                     uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  SHK_TRY(xs_closed(c));
+  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
+  return primer_scan(c, primers, n_primers, false, nullptr, 1, kmers, counts, levels, cap, offsets, level_hits);
+}
+
+int shk_primer_kmers_depths(shk_ctx *c, const shk_primer *primers, uint32_t n_primers, const uint32_t *depths, uint32_t n_depths,
+                            uint64_t *kmers, uint32_t *counts, uint8_t *levels, uint64_t cap, uint64_t *offsets, uint64_t *level_hits) {
+  SHK_TRY(xs_closed(c));
+  if (!c || (n_primers && !primers) || !offsets) return SHK_ERR_BAD_ARG;
+  SHK_TRY(depth_call_begin(c, "shk_primer_kmers_depths", depths, n_depths, true));
+  return primer_scan(c, primers, n_primers, true, depths, n_depths, kmers, counts, levels, cap, offsets, level_hits);
 }
 
 int shk_table_geometry(shk_ctx *c, uint64_t *n_pages, uint32_t *page_slots, uint32_t *n_lanes) {

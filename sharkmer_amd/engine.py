@@ -611,6 +611,27 @@ class PcrOutcome:
     low_primer_counts: bool
 
 
+def _pcr_out_columns(O, ng: int) -> dict:
+    """The per-gene column arrays of one out block (shk_pcr_run_out), bound into O."""
+    n1 = max(ng, 1)
+    cols = {f: np.zeros(n1, dtype=np.uint32) for f in _PCR_RUN_U32}
+    cols.update({f: np.zeros(n1, dtype=np.uint64) for f in _PCR_RUN_U64A + ("n_paired_links",)})
+    cols.update({f: np.zeros(n1, dtype=np.uint8) for f in ("threaded", "low_primer_counts")})
+    for f, a in cols.items():
+        setattr(O, f, a.ctypes.data)
+    return cols
+
+
+def _pcr_outcomes(genes, cols: dict, prods) -> list:
+    """One PcrOutcome per gene from an out block's columns and its products."""
+    out = []
+    for g, gene in enumerate(genes):
+        v = {f: int(a[g]) for f, a in cols.items()}
+        v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
+        out.append(PcrOutcome(gene_name=gene.gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
+    return out
+
+
 def _records_struct(recs: PcrProducts):
     """One gene's PcrProducts as a shk_pcr_records (and the arrays it points into)."""
     n = len(recs.sequences)
@@ -1185,46 +1206,35 @@ class KmerEngine:
         """get_primer_kmers (pcr/primers.rs:234-480) for every primer direction in one pass over the table
         (shk_primer_kmers) → per primer (kmers u64, counts u32, levels u8, level_hits u64[PRIMER_LEVELS]), the
         k-mers in the reference's insertion order: level ascending, count descending, k-mer ascending."""
-        primers = list(primers)
-        n = len(primers)
-        arr = (_Primer * max(n, 1))(*[p._c() for p in primers])
-        cap = sum(p.max_kmers for p in primers)
-        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
-        counts = np.zeros(max(cap, 1), dtype=np.uint32)
-        levels = np.zeros(max(cap, 1), dtype=np.uint8)
-        offsets = np.zeros(n + 1, dtype=np.uint64)
-        hits = np.zeros((max(n, 1), PRIMER_LEVELS), dtype=np.uint64)
-        self._check(self._L.shk_primer_kmers(self._h, C.cast(arr, C.c_void_p), n, kmers.ctypes.data,
-                                             counts.ctypes.data, levels.ctypes.data, cap, offsets.ctypes.data,
-                                             hits.ctypes.data))
-        out = []
-        for i in range(n):
-            a, b = int(offsets[i]), int(offsets[i + 1])
-            out.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[i].copy()))
-        return out
+        (block,) = self._primer_blocks(list(primers), 1, lambda *a: self._L.shk_primer_kmers(self._h, *a))
+        return block
 
     def primer_kmers_depths(self, primers, depths) -> list:
         """primer_kmers at every depth of `depths` (strictly ascending, at most PCR_MAX_DEPTHS) in one pass over the table
         (shk_primer_kmers_depths) → per depth what primer_kmers returns on a context that got the chunks below it only."""
-        primers = list(primers)
         dep = np.ascontiguousarray(np.atleast_1d(depths), dtype=np.uint32)
-        n, nd = len(primers), len(dep)
+        return self._primer_blocks(list(primers), len(dep),
+                                   lambda arr, n, *a: self._L.shk_primer_kmers_depths(self._h, arr, n, dep.ctypes.data, len(dep), *a))
+
+    def _primer_blocks(self, primers, n_blocks: int, call) -> list:
+        """The arrays of a primer scan over n_blocks result blocks, call(primers, n, kmers, counts, levels, cap, offsets,
+        level_hits) and its result sliced → per block, per primer (kmers, counts, levels, level_hits)."""
+        n = len(primers)
         arr = (_Primer * max(n, 1))(*[p._c() for p in primers])
-        cap = nd * sum(p.max_kmers for p in primers)
+        cap = n_blocks * sum(p.max_kmers for p in primers)
         kmers = np.zeros(max(cap, 1), dtype=np.uint64)
         counts = np.zeros(max(cap, 1), dtype=np.uint32)
         levels = np.zeros(max(cap, 1), dtype=np.uint8)
-        offsets = np.zeros(n * nd + 1, dtype=np.uint64)
-        hits = np.zeros((max(n * nd, 1), PRIMER_LEVELS), dtype=np.uint64)
-        self._check(self._L.shk_primer_kmers_depths(self._h, C.cast(arr, C.c_void_p), n, dep.ctypes.data, nd, kmers.ctypes.data,
-                                                    counts.ctypes.data, levels.ctypes.data, cap, offsets.ctypes.data,
-                                                    hits.ctypes.data))
+        offsets = np.zeros(n * n_blocks + 1, dtype=np.uint64)
+        hits = np.zeros((max(n * n_blocks, 1), PRIMER_LEVELS), dtype=np.uint64)
+        self._check(call(C.cast(arr, C.c_void_p), n, kmers.ctypes.data, counts.ctypes.data, levels.ctypes.data, cap, offsets.ctypes.data,
+                         hits.ctypes.data))
         out = []
-        for j in range(nd):
+        for j in range(n_blocks):
             block = []
-            for i in range(n):
-                a, b = int(offsets[j * n + i]), int(offsets[j * n + i + 1])
-                block.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[j * n + i].copy()))
+            for i in range(j * n, j * n + n):
+                a, b = int(offsets[i]), int(offsets[i + 1])
+                block.append((kmers[a:b].copy(), counts[a:b].copy(), levels[a:b].copy(), hits[i].copy()))
             out.append(block)
         return out
 
@@ -1796,13 +1806,8 @@ class KmerEngine:
                 keep += [ri, mt]
                 prm.read_index = None if ri is None else ri.ctypes.data
                 prm.mate = None if mt is None else mt.ctypes.data
-        n1 = max(ng, 1)
-        cols = {f: np.zeros(n1, dtype=np.uint32) for f in _PCR_RUN_U32}
-        cols.update({f: np.zeros(n1, dtype=np.uint64) for f in _PCR_RUN_U64A + ("n_paired_links",)})
-        cols.update({f: np.zeros(n1, dtype=np.uint8) for f in ("threaded", "low_primer_counts")})
         O = _PcrRunOut()
-        for f, a in cols.items():
-            setattr(O, f, a.ctypes.data)
+        cols = _pcr_out_columns(O, ng)
 
         def call(R):
             R.record_cap = R.record_cap if record_cap is None else record_cap
@@ -1819,13 +1824,7 @@ class KmerEngine:
                     raise
             return rc, self._check
 
-        prods = _pcr_records_call(ng, call)
-        out = []
-        for g in range(ng):
-            v = {f: int(a[g]) for f, a in cols.items()}
-            v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
-            out.append(PcrOutcome(gene_name=genes[g].gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
-        return out
+        return _pcr_outcomes(genes, cols, _pcr_records_call(ng, call))
 
     def pcr_run_depths(self, genes, depths, min_kmer_count: int = 2, max_num_nodes: int = 0, record_cap: int | None = None,
                        seq_cap: int | None = None) -> list:
@@ -1838,21 +1837,13 @@ class KmerEngine:
         ng, nd = len(genes), len(dep)
         arr = _pcr_genes(genes)
         prm = _PcrRunParams(min_kmer_count, PCR_READS_NONE, 0, 0, max_num_nodes, None, None, 0, None, None)
-        n1 = max(ng, 1)
-        cols = []
-        for _ in range(nd):
-            c = {f: np.zeros(n1, dtype=np.uint32) for f in _PCR_RUN_U32}
-            c.update({f: np.zeros(n1, dtype=np.uint64) for f in _PCR_RUN_U64A + ("n_paired_links",)})
-            c.update({f: np.zeros(n1, dtype=np.uint8) for f in ("threaded", "low_primer_counts")})
-            cols.append(c)
+        O = (_PcrRunOut * max(nd, 1))()
+        cols = [_pcr_out_columns(O[j], ng) for j in range(nd)]
         fixed = record_cap is not None or seq_cap is not None
         bufs = [_PcrRecordBuf(ng, max(64 * ng, 1) if record_cap is None else record_cap, 1 << 16 if seq_cap is None else seq_cap)
                 for _ in range(nd)]
         for attempt in (0, 1):
-            O = (_PcrRunOut * max(nd, 1))()
             for j in range(nd):
-                for f, a in cols[j].items():
-                    setattr(O[j], f, a.ctypes.data)
                 O[j].records = bufs[j].struct()
             rc = self._L.shk_pcr_run_depths(self._h, arr, ng, C.byref(prm), dep.ctypes.data, nd, O)
             for j in range(nd):
@@ -1869,16 +1860,7 @@ class KmerEngine:
                     raise
             self._check(rc)
             break
-        out = []
-        for j in range(nd):
-            prods = bufs[j].products()
-            block = []
-            for g in range(ng):
-                v = {f: int(a[g]) for f, a in cols[j].items()}
-                v["found_path"], v["threaded"], v["low_primer_counts"] = bool(v["found_path"]), bool(v["threaded"]), bool(v["low_primer_counts"])
-                block.append(PcrOutcome(gene_name=genes[g].gene_name, failure_reason=pcr_failure_reason(v["status"]), products=prods[g], **v))
-            out.append(block)
-        return out
+        return [_pcr_outcomes(genes, cols[j], bufs[j].products()) for j in range(nd)]
 
     def gather_reads(self, bases_t, offsets_t, read_ids):
         """The reads read_ids (any order, repeats allowed) of a batch that lies on this context's device, as a batch of

@@ -239,6 +239,29 @@ def test_pcr_run_depths_record_capacities(mixed, orc):
         assert_outcomes(block, ws, f"retry, depth {d}")
 
 
+# Launches per timing slot of one call over the mixed panel on the 4-chunk context, read from commit 38af4a5 ("sPCR depth
+# sweep: a panel at every cumulative chunk from one count"), where the plain call and the sweep were two pipelines: the
+# one pipeline launches what each of them launched.  Counts, not times: equal or wrong.
+LAUNCHES_PCR_RUN = {"lookup": 1, "extend": 11}
+LAUNCHES_PCR_RUN_DEPTHS_4 = {"lookup": 1, "extend": 11}
+
+
+def launches(e, call):
+    e.reset_timings()
+    call()
+    return {slot: n for slot, (_, n) in e.timings().items()}
+
+
+def test_launches_per_timing_slot(mixed):
+    p, genes, full, subs = mixed
+    plain = launches(full, lambda: full.pcr_run(genes))
+    sweep = launches(full, lambda: full.pcr_run_depths(genes, [4]))
+    print("launches pcr_run:", plain)
+    print("launches pcr_run_depths [4]:", sweep)
+    assert plain == LAUNCHES_PCR_RUN
+    assert sweep == LAUNCHES_PCR_RUN_DEPTHS_4
+
+
 def test_pcr_run_depths_18s(orc):
     seq, bases, offsets, gene, _, _ = cases.case_18s(orc)
     n = dc.CHUNKS_18S

@@ -257,6 +257,27 @@ def test_states_and_capacities(mixed, orc):
     assert err.value.code == -2 and err.value.needs[1] > 10 and err.value.per_gene["status"].tolist() == [w.status for w in want]
 
 
+def test_record_cap_one_short_on_the_plain_call(mixed, orc):
+    """The plain call writes its records straight into the caller's arrays: one record of room too few is that call's own
+    refusal, with the same needs as any short call and every per-gene figure of an unconstrained run."""
+    # (this file's own mixed fixture, the same panel on one chunk: test_gpu_pcr_depths.py, whose fixture has four, imports
+    # from this file, and no depth enters the plain call)
+    e, p, genes = mixed
+    free = e.pcr_run(genes, max_num_nodes=pc.MIXED_BUDGET)
+    with pytest.raises(sa.ShkError) as first:
+        e.pcr_run(genes, max_num_nodes=pc.MIXED_BUDGET, record_cap=1)
+    need_records, need_bases = first.value.needs
+    assert need_records == sum(len(o.products.sequences) for o in free) > 1
+    with pytest.raises(sa.ShkError) as err:
+        e.pcr_run(genes, max_num_nodes=pc.MIXED_BUDGET, record_cap=need_records - 1)
+    assert err.value.code == -2
+    assert f"{need_records} records of {need_bases} bases do not fit record_cap {need_records - 1}" in err.value.msg
+    assert err.value.needs == first.value.needs
+    for f in ("status", "n_nodes", "n_pruned_edges"):
+        assert err.value.per_gene[f].tolist() == [getattr(o, f) for o in free], f
+    same_outcomes(e.pcr_run(genes, max_num_nodes=pc.MIXED_BUDGET, record_cap=need_records, seq_cap=need_bases), free, "exactly what it needs")
+
+
 # ---- the command line and run_files ---------------------------------------------------------------------------------------
 
 def write_fastq(path, bases, offsets):
